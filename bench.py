@@ -10,12 +10,17 @@ A step = one frozen forward of one batch: fp32 images resident in HBM -> fp32 lo
 collective, and each step ends with one RCCL all_gather of the logits (the reference's DataParallel
 gather, quant_train.py:358) through ``hawq_amd.dist.gather_logits``.  ``--gpus N`` without a launcher
 (no WORLD_SIZE in the environment) starts the N ranks itself (``torch.distributed.run`` on 127.0.0.1).
-A multi-rank run measures BOTH decompositions and reports ``--scaling`` (default weak) as ``value``:
+A multi-rank run with ``--full`` measures BOTH decompositions and reports ``--scaling`` (default weak) as ``value``:
   weak    every rank processes its own batch of 128; value = N * 128 * K / t
   strong  ONE batch of 128 is sharded 128/N images per rank; value = 128 * K / t
 ``n_gpus`` is the number of ranks the process group actually has.  Prints ONE JSON line on rank 0.
 ``--dry-spawn`` runs the same launch / shard / gather / report path on CPU (gloo) with a stand-in forward:
 what the CPU test of the N > 1 plumbing uses (there is no CPU path for the network itself).
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, plan, timing, roofline arithmetic of this run).
+``--full`` adds everything else: the parity check against the oracle fixture, the per-launch profile and dominant kernel, the CPU
+baseline, the secondary workloads (``extra``) and, N > 1, the second decomposition.  ``--dump-outputs DIR`` writes the logits of
+the last timed step as ``DIR/logits.npy`` (float32; N > 1: the gathered logits of the decomposition ``value`` reports).
 """
 from __future__ import annotations
 
@@ -157,6 +162,23 @@ def golden_parity(arch, scheme, batch, seed, logits, lo=0):
         return None
     y = logits.cpu().numpy()
     return bool(np.array_equal(y, fx["logits"][lo:lo + y.shape[0]]))
+
+
+def last_output(eng, world, batch_total=None):
+    """What a caller of the timed path receives from its last step: the engine's logits, gathered over the ranks when N > 1
+    (a collective: every rank calls it).  A copy, so that later work on the engine cannot change it."""
+    if world == 1:
+        return eng.logits.clone()
+    from hawq_amd.dist import gather_logits
+    return gather_logits(eng.logits, batch_total).clone()
+
+
+def write_outputs(path, arrays):
+    """``--dump-outputs``: every array as ``<path>/<name>.npy`` in float32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def timed_steps(eng, steps, warmup, world, batch_total=None):
@@ -571,9 +593,15 @@ def main():
     ap.add_argument("--arch", default="resnet50")
     ap.add_argument("--scheme", default="uniform8")
     ap.add_argument("--batch", type=int, default=128, help="images per GPU per step (weak) / per job per step (strong)")
-    ap.add_argument("--scaling", choices=("weak", "strong"), default="weak", help="which decomposition `value` reports (N > 1 measures both)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads / per-kernel table")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
+                    help="which decomposition `value` reports (N > 1 with --full measures both)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and secondary measurements: oracle parity, per-launch profile, CPU baseline, "
+                         "secondary workloads, both N > 1 decompositions")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
+    ap.add_argument("--no-extra", action="store_true", help="(with --full) skip the secondary workloads / per-kernel table")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
     ap.add_argument("--per-op", default=None, help="write a per-launch roofline table (markdown) to this file")
     ap.add_argument("--dry-spawn", action="store_true", help="CPU / gloo stand-in forward: exercises the N > 1 launch, shard, gather and report path")
     ap.add_argument("--plan", default=os.path.join(ROOT, "profiles", "plans.json"),
@@ -629,18 +657,22 @@ def main():
     same_plan = plans_identical(eng.export_plan())
     local_batch = args.batch
     wall, gpu_ms, blocks = timed_steps(eng, args.steps, args.warmup, world)
+    strong_needed = world > 1 and (args.full or args.scaling == "strong")
+    dumped = last_output(eng, world) if args.dump_outputs and not (world > 1 and args.scaling == "strong") else None
     overflow = eng.overflowed()
-    parity = golden_parity(args.arch, args.scheme, args.batch, seed, eng.logits) if rank == 0 else None
+    parity = golden_parity(args.arch, args.scheme, args.batch, seed, eng.logits) if rank == 0 and args.full else None
     runs = {"weak": dict(value=round(world * args.batch * args.steps / wall, 1), ms_per_step=round(wall / args.steps * 1e3, 4),
                          global_batch=world * args.batch, batch_per_gpu=args.batch)}
-    # ---- strong (N > 1 only): ONE batch of `batch` images, rank r evaluates images shard_bounds(batch, r, N)
-    if world > 1:
+    # ---- strong (N > 1, --full or --scaling strong): ONE batch of `batch` images, rank r evaluates images shard_bounds(batch, r, N)
+    if strong_needed:
         lo, hi = shard_bounds(args.batch, rank, world)
         # the SAME model object (built and calibrated once), a second engine for the shard's batch shape; one shared plan again
         m2, e2, x2 = setup_workload(args.arch, args.scheme, args.batch, dev, seed=1, shard=(lo, hi), plans=plans, model=model, share=True)
         same_plan = same_plan and plans_identical(e2.export_plan())
         w2, g2, b2 = timed_steps(e2, args.steps, args.warmup, world, batch_total=args.batch)
-        p2 = all_ranks(golden_parity(args.arch, args.scheme, args.batch, 1, e2.logits, lo))
+        if args.dump_outputs and args.scaling == "strong":
+            dumped = last_output(e2, world, args.batch)
+        p2 = all_ranks(golden_parity(args.arch, args.scheme, args.batch, 1, e2.logits, lo)) if args.full else None
         runs["strong"] = dict(value=round(args.batch * args.steps / w2, 1), ms_per_step=round(w2 / args.steps * 1e3, 4),
                               global_batch=args.batch, batch_per_gpu=hi - lo, gpu_ms_per_step=round(g2, 4),
                               every_rank_logits_bit_equal_oracle=p2, concurrent_sub_batches=e2.chains)
@@ -723,13 +755,16 @@ def main():
                          "traffic_over_plan_bytes": round(traffic / plan_bytes, 3) if traffic and plan_bytes else None,
                          "mfma_frac": round(mfma_frac, 4)},
         }
-        try:
-            out["roofline"]["dominant_kernel"] = dominant_kernel(eng, args, plan_rows(args.arch, args.scheme) if args.arch in roofline.ARCH else {})
-        except Exception as exc:   # a reporting extra must never cost the bench line
-            out["roofline"]["dominant_kernel"] = {"error": f"{type(exc).__name__}: {exc}"}
+        if not args.full:   # the checks and secondary figures below belong to --full
+            del out["parity"]
+        else:
+            try:
+                out["roofline"]["dominant_kernel"] = dominant_kernel(eng, args, plan_rows(args.arch, args.scheme) if args.arch in roofline.ARCH else {})
+            except Exception as exc:   # a reporting extra must never cost the bench line
+                out["roofline"]["dominant_kernel"] = {"error": f"{type(exc).__name__}: {exc}"}
         if world > 1:
             out["weak"], out["strong"] = runs["weak"], runs.get("strong")
-        if (not args.no_extra or args.per_op) and world == 1:
+        if ((args.full and not args.no_extra) or args.per_op) and world == 1:
             ops = eng.profile_ops()
             tot = sum(ms for _, ms in ops)
             rows = plan_rows(args.arch, args.scheme)
@@ -749,11 +784,13 @@ def main():
                 "mfma_frac": round(2 * dm / (dms * 1e-3) / (roofline.MFMA_I8_PEAK_TOPS * 1e12), 4)}
             if args.per_op:
                 write_per_op(args.per_op, ops, rows, nb)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(model, x, eng.logits, sample=args.cpu_sample)
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
-    if not args.no_extra and world == 1 and rank == 0:
+        if dumped is not None:
+            write_outputs(args.dump_outputs, {"logits": dumped})
+    if args.full and not args.no_extra and world == 1 and rank == 0:
         if args.extras_child:
             out = {"extra": run_extras(args, dev, plans, model, eng), "plans_used": plans.used}
             print(json.dumps(out), flush=True)
@@ -768,28 +805,23 @@ def main():
         tmp = tempfile.NamedTemporaryFile("w", suffix="_plans.json", delete=False)
         json.dump(child_plans, tmp)
         tmp.close()
-        cmd = [sys.executable, os.path.abspath(__file__), "--extras-child", "--no-cpu-baseline", "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--arch", args.arch, "--scheme", args.scheme, "--batch", str(args.batch), "--plan", tmp.name]
-        extra = None
-        for attempt in (1, 2):   # one retry: the failure seen was sporadic
-            try:
-                r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=sys.stderr, timeout=900,
-                                   env=dict(os.environ, HAWQ_PLAN_LABEL=(os.path.relpath(args.plan, ROOT) if not args.retune else "the plans this run tuned")))
-                line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
-                if r.returncode == 0 and line:
-                    child = json.loads(line[-1])
-                    extra = child["extra"]
-                    plans.used.update(child.get("plans_used", {}))
-                    if attempt > 1:
-                        extra["extras_child_attempts"] = attempt
-                    break
-                err = f"child exited with code {r.returncode}"
-            except subprocess.TimeoutExpired as exc:   # a hang is not retried: the bench must end in bounded time
-                extra = {"error": f"the secondary workloads did not complete (timeout after {exc.timeout:.0f} s); the headline above is unaffected"}
-                break
-            except Exception as exc:   # unparsable output
-                err = f"{type(exc).__name__}: {exc}"
-            extra = {"error": f"the secondary workloads did not complete ({err}); the headline above is unaffected"}
+        cmd = [sys.executable, os.path.abspath(__file__), "--extras-child", "--full", "--no-cpu-baseline", "--gpus", "1", "--steps", str(args.steps),
+               "--warmup", str(args.warmup), "--arch", args.arch, "--scheme", args.scheme, "--batch", str(args.batch), "--plan", tmp.name]
+        # one attempt: a child that failed on the GPU is not started again (the headline above is kept either way)
+        try:
+            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=sys.stderr, timeout=900,
+                               env=dict(os.environ, HAWQ_PLAN_LABEL=(os.path.relpath(args.plan, ROOT) if not args.retune else "the plans this run tuned")))
+            line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+            if r.returncode == 0 and line:
+                child = json.loads(line[-1])
+                extra = child["extra"]
+                plans.used.update(child.get("plans_used", {}))
+            else:
+                extra = {"error": f"the secondary workloads did not complete (child exited with code {r.returncode}); the headline above is unaffected"}
+        except subprocess.TimeoutExpired as exc:
+            extra = {"error": f"the secondary workloads did not complete (timeout after {exc.timeout:.0f} s); the headline above is unaffected"}
+        except Exception as exc:   # unparsable output
+            extra = {"error": f"the secondary workloads did not complete ({type(exc).__name__}: {exc}); the headline above is unaffected"}
         os.unlink(tmp.name)
         out["extra"] = extra
     if args.save_plan and rank == 0:

@@ -31,6 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 from oracle import ref_live  # noqa: E402
 from hawq_amd.skeleton import synthetic_images  # noqa: E402
+from tests.helpers import savez_parts  # noqa: E402  (parts of at most ~1 MB each, read back as one by tests/helpers.load)
 
 
 def digest(a) -> np.ndarray:
@@ -268,7 +269,7 @@ def main():
     if "--extra-only" in sys.argv:
         for arch, scheme, b in EXTRA:
             fx = net_fixture(arch, scheme, b, light=True)
-            np.savez_compressed(os.path.join(HERE, f"net_{arch}_{scheme}_b{b}.npz"), **fx)
+            savez_parts(os.path.join(HERE, f"net_{arch}_{scheme}_b{b}.npz"), fx)
             print(arch, scheme, "acc_absmax", int(fx["acc_absmax"]), "wpatches", len(fx["conv_wpatch"]), flush=True)
         return
     np.savez_compressed(os.path.join(HERE, "kat_functions.npz"), **kat_functions(qu))
@@ -276,20 +277,20 @@ def main():
     for arch, scheme, b in (("resnet18", "uniform8", 2), ("resnet18", "uniform4", 2), ("resnet18", "bops_0.5", 2),
                             ("resnet50", "uniform8", 2), ("resnet50", "uniform4", 2), ("resnet50", "bops_0.5", 2)):
         fx = net_fixture(arch, scheme, b)
-        np.savez_compressed(os.path.join(HERE, f"net_{arch}_{scheme}_b{b}.npz"), **fx)
+        savez_parts(os.path.join(HERE, f"net_{arch}_{scheme}_b{b}.npz"), fx)
         print(arch, scheme, "acc_absmax", int(fx["acc_absmax"]), "wpatches", len(fx["conv_wpatch"]), flush=True)
     # further shipped graphs / schedules (ResNet101, the stride-on-3x3 ResNet50b, mixed-width schedules): "light"
     # fixtures without the two full accumulator tensors
     for arch, scheme, b in EXTRA:
         fx = net_fixture(arch, scheme, b, light=True)
-        np.savez_compressed(os.path.join(HERE, f"net_{arch}_{scheme}_b{b}.npz"), **fx)
+        savez_parts(os.path.join(HERE, f"net_{arch}_{scheme}_b{b}.npz"), fx)
         print(arch, scheme, "acc_absmax", int(fx["acc_absmax"]), "wpatches", len(fx["conv_wpatch"]), flush=True)
     # the one real-image fixture the reference ships (tvm_benchmark/models/input_image_batch_1.npy, NHWC)
     img = np.load(os.path.join(ref_live.REF_ROOT, "tvm_benchmark", "models", "input_image_batch_1.npy"))
     img = torch.from_numpy(np.ascontiguousarray(img.transpose(0, 3, 1, 2))).float()
     np.save(os.path.join(HERE, "real_image_nchw.npy"), img.numpy())
     fx = net_fixture("resnet18", "uniform8", 1, image=img)
-    np.savez_compressed(os.path.join(HERE, "net_resnet18_uniform8_realimg.npz"), **fx)
+    savez_parts(os.path.join(HERE, "net_resnet18_uniform8_realimg.npz"), fx)
 
 
 if __name__ == "__main__":

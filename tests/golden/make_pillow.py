@@ -13,6 +13,7 @@ against the build container's.
 import hashlib
 import io
 import os
+import sys
 
 import numpy as np
 import PIL
@@ -63,7 +64,9 @@ def main():
     out["jpeg_decoded_sha"] = np.array(hashlib.sha256(dec.tobytes()).hexdigest())
     out["jpeg_decoded"] = dec
     out["jpeg_crop"] = pipeline(dec)[1]
-    np.savez_compressed(os.path.join(HERE, "pillow_resize.npz"), **out)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from tests.helpers import savez_parts   # parts of at most ~1 MB each, read back as one fixture by tests/helpers.load
+    savez_parts(os.path.join(HERE, "pillow_resize.npz"), out)
     print("wrote pillow_resize.npz (Pillow", PIL.__version__ + ")")
 
 

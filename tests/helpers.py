@@ -14,8 +14,77 @@ NET_CONFIGS_EXTRA = [("resnet101", "uniform8"), ("resnet50b", "uniform4"), ("res
                      ("resnet50", "modelsize_0.25")]
 
 
+PART_BYTES = 1_000_000   # a fixture whose compressed arrays exceed this is stored as <stem>.npz + <stem>.part1.npz + ...
+
+
+class Fixture(dict):
+    """The arrays of a fixture stored in one or more parts, by name (``.files`` as np.load's NpzFile has)."""
+
+    @property
+    def files(self):
+        return list(self)
+
+    def __getitem__(self, k):   # a fresh array per access, as NpzFile reads one
+        return dict.__getitem__(self, k).copy()
+
+
 def load(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    path = os.path.join(GOLDEN, name)
+    stem = path[:-len(".npz")]
+    raw, part = {}, 0
+    while os.path.isfile(path):
+        with np.load(path, allow_pickle=False) as z:
+            raw.update({k: z[k] for k in z.files})
+        part += 1
+        path = f"{stem}.part{part}.npz"
+    if not raw:
+        raise FileNotFoundError(os.path.join(GOLDEN, name))
+    out = Fixture()
+    for k, v in raw.items():   # an array stored in pieces (savez_parts): "<key>#shape", "<key>#0", "<key>#1", ...
+        if k.endswith("#shape"):
+            base = k[:-len("#shape")]
+            pieces = []
+            while f"{base}#{len(pieces)}" in raw:
+                pieces.append(raw[f"{base}#{len(pieces)}"])
+            out[base] = np.concatenate(pieces).reshape(v)
+        elif "#" not in k:
+            out[k] = v
+    return out
+
+
+def savez_parts(path, arrays):
+    """np.savez_compressed ``arrays`` as ``path`` and, when their compressed size would pass PART_BYTES, further parts
+    ``<stem>.part1.npz``, ... (read back as one fixture by ``load``).  Arrays keep their order; an array that alone would
+    pass PART_BYTES is stored flat in pieces, one part each."""
+    import io
+    import zlib
+
+    def packed(v):
+        buf = io.BytesIO()
+        np.save(buf, np.asarray(v), allow_pickle=False)
+        return len(zlib.compress(buf.getvalue(), 6))
+
+    entries = []
+    for k, v in arrays.items():
+        n = packed(v)
+        if n <= PART_BYTES:
+            entries.append((k, v, n))
+            continue
+        v = np.asarray(v)
+        pieces = np.array_split(v.reshape(-1), -(-n // (PART_BYTES // 2)))
+        entries.append((f"{k}#shape", np.array(v.shape, np.int64), 0))
+        entries += [(f"{k}#{i}", p, packed(p)) for i, p in enumerate(pieces)]
+    stem = path[:-len(".npz")]
+    parts, cur, size = [], {}, 0
+    for k, v, n in entries:
+        if cur and size + n > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += n
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        np.savez_compressed(path if i == 0 else f"{stem}.part{i}.npz", **p)
 
 
 def net_fixture(arch, scheme, batch=2):

@@ -1,5 +1,5 @@
 """quantized_checkpoint.pth.tar (quant_train.py:665-670): writer / loader of the reference's format.
-CPU: structure round trip, strictness, and - in the build container - the file the LIVE reference writes.
+CPU: structure round trip, strictness, and the files the LIVE reference writes (their records under tests/golden/).
 GPU: a network restored from the checkpoint alone (other float weights, no calibration) gives the same logits."""
 import os
 import sys
@@ -80,18 +80,30 @@ def test_dataparallel_prefixed_checkpoint_and_partial_files(tmp_path):
     assert b._engine is None
 
 
-@pytest.mark.reference
+def _reference_state(name, seed):
+    """A state_dict the live reference produced, from its record (tests/golden/make_reference_records.py): every key in the
+    reference's order, shape and dtype, with the reference's values where the record holds them (scales, biases, ranges, BN
+    statistics) and a seeded fill of the recorded layout for the large weight tensors."""
+    import json
+    from tests import helpers as H
+    fx = H.load(name)
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for i, (k, shape, dt) in enumerate(zip(fx["keys"], json.loads(str(fx["shapes"])), fx["dtypes"])):
+        if f"value_{i}" in fx.files:
+            sd[str(k)] = torch.from_numpy(np.array(fx[f"value_{i}"]))
+        elif "weight_integer" in str(k):
+            sd[str(k)] = torch.randint(-100, 100, shape, generator=g).to(getattr(torch, str(dt)))
+        else:
+            sd[str(k)] = (0.05 * torch.randn(shape, generator=g)).to(getattr(torch, str(dt)))
+    return sd
+
+
 def test_loads_the_file_the_live_reference_writes(tmp_path):
     """The reference's own frozen ResNet18 -> its torch.save(...) of quant_train.py:665-670 -> our loader (strict):
     every key finds its buffer and the integer weights / biases / scales arrive unchanged."""
     from hawq_amd.api import build_quantized_resnet, load_quantized_checkpoint
-    from hawq_amd.skeleton import synthetic_images
-    from oracle import ref_live
-    q = ref_live.build_reference_model("resnet18", "uniform8", seed=0)
-    ref_live.calibrate_and_freeze(q, synthetic_images(2, seed=0))
-    with torch.no_grad():
-        q(synthetic_images(2, seed=0))  # a frozen forward fills weight_integer / bias_integer / scales
-    sd = q.state_dict()
+    sd = _reference_state("ref_ckpt_resnet18_uniform8.npz", seed=7)
     path = str(tmp_path / "quantized_checkpoint.pth.tar")
     torch.save({g: {k: v for k, v in sd.items() if g in k} for g in GROUPS}, path)  # quant_train.py:665-670 verbatim
     ours = build_quantized_resnet("resnet18", "uniform8", seed=5)  # different float weights on purpose
@@ -106,18 +118,12 @@ def test_loads_the_file_the_live_reference_writes(tmp_path):
     assert n > 60
 
 
-@pytest.mark.reference
 def test_loads_a_float_checkpoint_of_the_live_reference():
     """checkpoint.pth.tar as quant_train.py writes it ({'state_dict': DataParallel-prefixed}) from the reference's
     calibrated ResNet18 -> hawq_amd.api.load_checkpoint: every float weight, BN statistic and activation range arrives,
     nothing is missing or unexpected (same module / buffer names)."""
     from hawq_amd.api import build_quantized_resnet, load_checkpoint
-    from hawq_amd.skeleton import synthetic_images
-    from oracle import ref_live
-    q = ref_live.build_reference_model("resnet18", "uniform8", seed=0)
-    with torch.no_grad():
-        q(synthetic_images(2, seed=0))  # un-frozen forward: QuantAct ranges initialise (quant_modules.py:247-250)
-    sd = q.state_dict()
+    sd = _reference_state("ref_float_ckpt_resnet18_uniform8.npz", seed=8)
     ckpt = {"epoch": 1, "arch": "resnet18", "state_dict": {"module." + k: v for k, v in sd.items()}, "best_acc1": 0.0}
     ours = build_quantized_resnet("resnet18", "uniform8", seed=5)
     ours, missing, unexpected = load_checkpoint(ours, ckpt)

@@ -233,18 +233,12 @@ def _all_schedules():
     return out
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("arch,scheme", [c for c in _all_schedules() if c not in H.NET_CONFIGS + H.NET_CONFIGS_EXTRA])
 def test_every_other_shipped_schedule_against_the_live_reference(arch, scheme):
-    """The 16 ResNet bit schedules that have no committed fixture: run the unmodified reference here (build container
-    only; skipped where /root/reference is absent) and hold the oracle to the same checks, on one image."""
-    sys_path_golden = __import__("os").path.join(__import__("os").path.dirname(__file__), "golden")
-    import sys
-    if sys_path_golden not in sys.path:
-        sys.path.insert(0, sys_path_golden)
-    import make_golden
-    fx = make_golden.net_fixture(arch, scheme, 1, light=True)
-    _check_oracle_against_fixture(arch, scheme, fx, batch=1)
+    """The 16 ResNet bit schedules that have no batch-2 fixture: the unmodified reference's run on one image, recorded as a
+    light fixture (tests/golden/net_<arch>_<scheme>_b1.npz, tests/golden/make_reference_records.py); the oracle is held to
+    the same checks."""
+    _check_oracle_against_fixture(arch, scheme, H.net_fixture(arch, scheme, 1), batch=1)
 
 
 @pytest.mark.parametrize("arch,scheme", [("resnet18", "uniform8"), ("resnet50", "uniform8")])

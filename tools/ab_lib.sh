@@ -10,6 +10,6 @@ export HAWQ_TILES=$(cfg autotuned_tiles) HAWQ_CHAINS=$(cfg concurrent_sub_batche
 echo "plan: chains $HAWQ_CHAINS tiles $HAWQ_TILES fused $HAWQ_ER_TILES"
 pr() { python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$1', d['value'], 'img/s; gpu ms', d['timing']['mean_ms'], '+-', d['timing']['std_ms'], 'min', d['timing']['min_ms'], 'parity', d['parity']['gpu_logits_bit_equal_oracle'])"; }
 for i in $(seq $reps); do
-  HAWQ_LIB=$A python bench.py --no-extra --no-cpu-baseline --steps 100 --warmup 10 2>/dev/null | pr A
-  HAWQ_LIB=$B python bench.py --no-extra --no-cpu-baseline --steps 100 --warmup 10 2>/dev/null | pr B
+  HAWQ_LIB=$A python bench.py --full --no-extra --no-cpu-baseline --steps 100 --warmup 10 2>/dev/null | pr A
+  HAWQ_LIB=$B python bench.py --full --no-extra --no-cpu-baseline --steps 100 --warmup 10 2>/dev/null | pr B
 done

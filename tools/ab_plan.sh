@@ -13,5 +13,5 @@ print("A", {k: (v["fused_variants"], v["tiles"]) for k, v in json.load(open("$O/
 print("B", {k: (v["fused_variants"], v["tiles"]) for k, v in d.items()})
 PY
 for rep in $(seq 1 ${2:-3}); do for ab in a b; do
-  python bench.py --no-cpu-baseline --no-extra --plan $O/ab_plans_$ab.json --steps 100 --warmup 20 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$ab', d['value'], d['timing']['mean_ms'], d['timing']['min_ms'], d['parity']['gpu_logits_bit_equal_oracle'], d['config']['plan_source'][:30])"
+  python bench.py --full --no-cpu-baseline --no-extra --plan $O/ab_plans_$ab.json --steps 100 --warmup 20 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$ab', d['value'], d['timing']['mean_ms'], d['timing']['min_ms'], d['parity']['gpu_logits_bit_equal_oracle'], d['config']['plan_source'][:30])"
 done; done

@@ -16,7 +16,7 @@ mkdir -p $O
 cd $R
 W="--arch $ARCH --scheme $SCHEME"
 if [ "$ARCH $SCHEME" = "resnet50 uniform8" ] && [ -z "$LIGHT" ]; then
-  python bench.py ${BENCH_ARGS} --save-plan $O/${tag}_plans.json > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+  python bench.py --full ${BENCH_ARGS} --save-plan $O/${tag}_plans.json > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 else
   python bench.py $W --no-cpu-baseline --no-extra ${BENCH_ARGS} --save-plan $O/${tag}_plans.json > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 fi

@@ -13,12 +13,12 @@ for scheme in ${1:-uniform8}; do
   W="--arch ${ARCH:-resnet50} --scheme $scheme"
   {
   for c in 2 3; do for i in 1 2; do
-    HAWQ_CHAINS=$c python bench.py $W --retune --no-cpu-baseline --no-extra --save-plan $O/r6c_${scheme}_plans_c${c}_$i.json 2>/dev/null | pr "$scheme tuned, $c chains, #$i:"
+    HAWQ_CHAINS=$c python bench.py --full $W --retune --no-cpu-baseline --no-extra --save-plan $O/r6c_${scheme}_plans_c${c}_$i.json 2>/dev/null | pr "$scheme tuned, $c chains, #$i:"
   done; done
   for rnd in 1 2 3; do
-    python bench.py $W --no-extra --no-cpu-baseline --steps 60 --warmup 10 2>/dev/null | pr "$scheme round $rnd recorded (or tuned, if stale):"
+    python bench.py --full $W --no-extra --no-cpu-baseline --steps 60 --warmup 10 2>/dev/null | pr "$scheme round $rnd recorded (or tuned, if stale):"
     for c in 2 3; do for i in 1 2; do
-      python bench.py $W --plan $O/r6c_${scheme}_plans_c${c}_$i.json --no-extra --no-cpu-baseline --steps 60 --warmup 10 2>/dev/null | pr "$scheme round $rnd c$c #$i:"
+      python bench.py --full $W --plan $O/r6c_${scheme}_plans_c${c}_$i.json --no-extra --no-cpu-baseline --steps 60 --warmup 10 2>/dev/null | pr "$scheme round $rnd c$c #$i:"
     done; done
   done
   } > $O/r6c_${scheme}_playoff.txt

@@ -12,7 +12,7 @@ import json, sys
 d = json.loads(sys.stdin.readline()); e = d.get('extra', {})
 print('$1', d['value'], 'img/s', d['ms_per_step'], 'ms | trials', d['config'].get('plan_trials_ms'), '|', ' '.join(f\"{k.replace('resnet50_uniform8_','').replace('_b128','')}:{v.get('images_per_s')}\" for k, v in e.items() if isinstance(v, dict)))"; }
 for i in $(seq $n); do
-  python bench.py --retune --no-cpu-baseline --save-plan $O/r6_plans_t$i.json 2> $O/r6_tune_t$i.err | tee $O/r6_tune_t$i.json | pr "tuning run t$i:"
+  python bench.py --full --retune --no-cpu-baseline --save-plan $O/r6_plans_t$i.json 2> $O/r6_tune_t$i.err | tee $O/r6_tune_t$i.json | pr "tuning run t$i:"
 done > $O/r6_plan_choice.txt
 for rnd in 1 2; do
   for i in $(seq $n); do

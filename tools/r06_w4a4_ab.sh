@@ -8,7 +8,7 @@ reps=${1:-2}
 export HAWQ_TUNE_TRIALS=${HAWQ_TUNE_TRIALS:-2}
 run() {  # label scheme env...
   label=$1; scheme=$2; shift 2
-  env "$@" timeout 600 python bench.py --scheme $scheme --retune --steps 100 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" timeout 600 python bench.py --full --scheme $scheme --retune --steps 100 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); c = d['config']
 print('$label', d['value'], 'img/s', d['ms_per_step'], 'ms  parity', d['parity']['gpu_logits_bit_equal_oracle'], ' chains', c['concurrent_sub_batches'], ' fused pairs', c['fused_expand_reduce_launches'], ' tiles', c['autotuned_tiles'], ' variants', c['fused_variants'])"
