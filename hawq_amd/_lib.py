@@ -66,6 +66,9 @@ SIGNATURES = {
     "hawq_conv2d_num_gemm2_tiles": [],
     "hawq_conv2d_gemm2_first": [],
     "hawq_pack_w1x1_k128": [vp, vp, i32, i32],
+    "hawq_conv2d_splitk_ok": [C.POINTER(ConvArgs), i32],
+    "hawq_conv2d_splitk_workspace": [C.POINTER(ConvArgs), i32, C.POINTER(i64), C.POINTER(i64)],
+    "hawq_conv2d_splitk": [C.POINTER(ConvArgs), i32, vp, vp, vp],
     "hawq_fc_dequant_ok": [i32, i32, i32],
     "hawq_fc_dequant": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "hawq_conv_expand_reduce": [C.POINTER(ExpandReduceArgs), vp],

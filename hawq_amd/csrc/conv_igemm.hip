@@ -252,9 +252,11 @@ __device__ __attribute__((aligned(16))) const int g_zero16[4] = {0, 0, 0, 0};
 // packed bytes travel through LDS untouched and every fragment (8 B = 16 channels per lane) is unpacked to
 // int8 in registers right before its MFMA (activations zero-extended, weights as value*16 with the
 // accumulators shifted back by 4 at the end - exact).  Needs Cin % 128 == 0 (launcher-checked).
-template <class C, bool DUAL, bool NIB>
+// RANGE (cross-workgroup split-K, conv_splitk.hip): only ring stages [kb, ke) of the chunk sequence run; a range lies inside one
+// branch.  PLANAR: the first branch reads channel-group planes [Cin / 16][N*H*W][16 B] (in_planar) instead of NHWC rows.
+template <class C, bool DUAL, bool NIB, bool RANGE = false, bool PLANAR = false>
 __device__ __forceinline__ void gemm_pipeline(v16i (&acc)[C::CT][C::PT], v16i (&acc2)[DUAL ? C::CT : 1][DUAL ? C::PT : 1],
-                                              const ConvP &p, int m0, int c0, char *smem) {
+                                              const ConvP &p, int m0, int c0, char *smem, int kb = 0, int ke = 0) {
     constexpr int CSH = NIB ? 7 : 6;  // log2(channels per 64-byte chunk)
     constexpr int NS = C::NS, L = C::AL + C::WL, STAGE = C::STAGE_BYTES;
     static_assert((NS - 2) * L * C::KSUB / C::KG <= 60, "vmcnt range");
@@ -295,6 +297,14 @@ __device__ __forceinline__ void gemm_pipeline(v16i (&acc)[C::CT][C::PT], v16i (&
 
     constexpr int KSUB = C::KSUB, SUBB = (C::BM + C::BN) * 64;  // bytes of one 64-channel sub-chunk (A rows, then W rows)
     int kh = 0, kw = 0, cc = 0, jissue = 0, istage = 0;  // coordinates of the next sub-chunk to ISSUE
+    if constexpr (RANGE) {
+        jissue = kb * KSUB;
+        if (jissue < nk1) {
+            const int tap = jissue / cch1;
+            cc = jissue - tap * cch1, kh = tap / p.KW, kw = tap - (tap / p.KW) * p.KW;
+        }
+    }
+    const size_t plane = PLANAR ? (size_t)p.N * p.H * p.W * 16 : 0;   // bytes of one 16-channel plane
     auto issue_sub = [&](int sub) {
         char *sa = smem + istage * STAGE + sub * SUBB + wave * 1024;  // + i * RPP * 64: RPP rows x 64 B per pass
         char *sw = sa + C::BM * 64;
@@ -318,7 +328,9 @@ __device__ __forceinline__ void gemm_pipeline(v16i (&acc)[C::CT][C::PT], v16i (&
             for (int i = 0; i < C::AL; ++i) {
                 const int iy = iy0[i] + kh, ix = ix0[i] + kw;
                 const bool v = mval[i] && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-                const char *src = v ? (const char *)p.in + (size_t)(pix_base[i] + tap_off) * p.in_pitch + (cc << 6) + asw[i] : zero;
+                const char *src = !v ? zero
+                                  : PLANAR ? (const char *)p.in + (size_t)((cc << 2) + (asw[i] >> 4)) * plane + (size_t)(pix_base[i] + tap_off) * 16
+                                           : (const char *)p.in + (size_t)(pix_base[i] + tap_off) * p.in_pitch + (cc << 6) + asw[i];
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                                  (__attribute__((address_space(3))) void *)(sa + i * (C::RPP * 64)), 16, 0, 0);
             }
@@ -407,10 +419,11 @@ __device__ __forceinline__ void gemm_pipeline(v16i (&acc)[C::CT][C::PT], v16i (&
         }
     };
 
-    const int ns1 = nk1 / KSUB, nst = nk / KSUB;  // ring stages of the first branch / in total
+    const int ns1 = nk1 / KSUB, nst = RANGE ? ke : nk / KSUB;  // ring stages of the first branch / end of the stages run
+    const int kfirst = RANGE ? kb : 0;
 #pragma unroll
     for (int j = 0; j < NS - 1; ++j)
-        if (j < nst) issue();
+        if (kfirst + j < nst) issue();
     int cstage = 0;
     constexpr int LS = L * KSUB / C::KG;  // loads per thread per stage
     auto step = [&](auto &a, int k) {
@@ -429,13 +442,13 @@ __device__ __forceinline__ void gemm_pipeline(v16i (&acc)[C::CT][C::PT], v16i (&
             }
         }
         __builtin_amdgcn_s_barrier();
-        if (jissue < nk && !HAWQ_DBG_BIT(p.dbg, 1)) issue();
+        if (jissue < (RANGE ? nst * KSUB : nk) && !HAWQ_DBG_BIT(p.dbg, 1)) issue();
         if (!HAWQ_DBG_BIT(p.dbg, 2)) compute(a, cstage);
         if (++cstage == NS) cstage = 0;
     };
-    for (int k = 0; k < ns1; ++k) step(acc, k);
+    for (int k = kfirst; k < (RANGE ? min(ns1, nst) : ns1); ++k) step(acc, k);
     if constexpr (DUAL)
-        for (int k = ns1; k < nst; ++k) step(acc2, k);
+        for (int k = RANGE ? max(ns1, kfirst) : ns1; k < nst; ++k) step(acc2, k);
     if constexpr (NIB) {  // weights were unpacked as value*16
 #pragma unroll
         for (int c = 0; c < C::CT; ++c)
@@ -993,6 +1006,7 @@ __global__ __launch_bounds__(C::NT, C::MINB) void conv_kernel(const ConvP p) {
     }
 }
 
+#ifndef HAWQ_CONV_IGEMM_DEVICE_ONLY   // conv_splitk.hip includes the device code above (ConvP, pipeline, epilogues) and nothing below
 // =============================================================== 3x3 / stride 1 / pad 1 "band" kernel
 // The generic pipeline re-fetches the activation tile once per filter tap (9x) and synchronises the workgroup
 // once per 64-deep K chunk.  Here a workgroup that owns BM consecutive output pixels keeps, per 64-channel
@@ -1441,7 +1455,9 @@ int pick_tile(int M, int Cout, bool dual) {
     return 2;
 }
 
+#endif  // HAWQ_CONV_IGEMM_DEVICE_ONLY
 }  // namespace
+#ifndef HAWQ_CONV_IGEMM_DEVICE_ONLY
 
 // band_persist.hip: weight-stationary persistent 3x3 kernel for Cin == Cout == 64 (the id after the band tiles)
 bool band_persist_applies(const hawq_conv_args *a);
@@ -1740,3 +1756,4 @@ extern "C" int hawq_conv2d(const hawq_conv_args *a, void *stream) {
     }
     return 0;
 }
+#endif  // HAWQ_CONV_IGEMM_DEVICE_ONLY

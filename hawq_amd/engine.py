@@ -68,24 +68,64 @@ class StalePlan(ValueError):
     """A recorded plan does not fit the launch list / kernel inventory of this build: the engine falls back to tuning."""
 
 
+# K-slice counts the tuner tries for a hawq_conv2d launch with fewer output tiles than the chip has CUs (hawq_conv2d_splitk)
+SPLITK_CANDIDATES = (2, 4, 8, 16, 32)
+
+
+class _SplitWorkspace:
+    """Slab and arrival counters of the split-K launches of ONE chain.  The launches of a chain run in stream order, so they
+    share it; the counters are zero when allocated and every split-K launch leaves them zero.  Grows (zeroed) on demand, which
+    only happens while a plan is tuned or applied - before the hipGraph is captured."""
+
+    def __init__(self, dev):
+        self.dev, self.slab, self.counters = dev, None, None
+
+    def fit(self, a, slices):
+        slab, cnt = C.c_int64(), C.c_int64()
+        _lib.call("hawq_conv2d_splitk_workspace", C.byref(a), slices, C.byref(slab), C.byref(cnt))
+        if self.slab is None or self.slab.numel() < slab.value:
+            self.slab = torch.zeros(slab.value, dtype=torch.uint8, device=self.dev)
+        if self.counters is None or self.counters.numel() < cnt.value // 4:
+            self.counters = torch.zeros(cnt.value // 4, dtype=torch.int32, device=self.dev)
+
+    def launch(self, a, slices, stream):
+        """hawq_conv2d of `a`, or its split-K form with `slices` K slices (slices > 0)."""
+        if slices:
+            _lib.call("hawq_conv2d_splitk", C.byref(a), slices, self.slab.data_ptr(), self.counters.data_ptr(), stream)
+        else:
+            _lib.call("hawq_conv2d", C.byref(a), stream)
+
+
+class _ConvLaunch:
+    """One hawq_conv2d entry of the launch list; ``splitk`` > 0 runs it as hawq_conv2d_splitk with that many K slices."""
+
+    def __init__(self, a, ws, stream):
+        self.a, self.ws, self.sp, self.splitk = a, ws, stream, 0
+
+    def __call__(self):
+        self.ws.launch(self.a, self.splitk, self.sp)
+
+
 class _FusedPair:
     """One entry of the launch list that covers TWO layers - the expand conv (+ residual epilogue) of unit i and the reduce
     conv of unit i+1 - either as one hawq_conv_expand_reduce launch or as two hawq_conv2d launches, whichever the
     autotuner measured faster for this batch shape (results are identical)."""
 
-    def __init__(self, er, expand, reduce, stream):
+    def __init__(self, er, expand, reduce, stream, ws):
         # reduce None: a "solo" entry - the expand conv alone, either through hawq_conv_expand_reduce (reduce.wgt == NULL:
         # the wave-private kernel of fused_wp.hip) or through hawq_conv2d
         self.er, self.expand, self.reduce, self.sp = er, expand, reduce, stream
         self.fused = True
+        # the two-launch form: K slices of each launch (0 = hawq_conv2d, else hawq_conv2d_splitk on the chain's workspace)
+        self.ws, self.split_e, self.split_r = ws, 0, 0
 
     def __call__(self):
         if self.fused:
             _lib.call("hawq_conv_expand_reduce", C.byref(self.er), self.sp)
         else:
-            _lib.call("hawq_conv2d", C.byref(self.expand), self.sp)
+            self.ws.launch(self.expand, self.split_e, self.sp)
             if self.reduce is not None:
-                _lib.call("hawq_conv2d", C.byref(self.reduce), self.sp)
+                self.ws.launch(self.reduce, self.split_r, self.sp)
 
 
 class _Conv:
@@ -455,7 +495,7 @@ class IntegerEngine:
         r1.wgt, r1.w_bits = c.w.data_ptr(), c.w_bits
         # the two-launch form reads the block input at its storage width: the 128-byte K chunks of the weights must be of that width too
         r1.wgt_k128 = c.k128().data_ptr() if (c.k128() is not None and c.w_bits == nxt['a_bits']) else None
-        pair = _FusedPair(er, a, r1, self.stream.cuda_stream)
+        pair = _FusedPair(er, a, r1, self.stream.cuda_stream, self._ws)
         keep += [out, er, q, r1, pair]
         return pair, out, ob, planar
 
@@ -468,7 +508,7 @@ class IntegerEngine:
         C.memmove(C.byref(er.expand), C.byref(a), C.sizeof(a))
         if _lib.load().hawq_conv_expand_reduce_variants(C.byref(er)) == 0:
             return None
-        pair = _FusedPair(er, a, None, self.stream.cuda_stream)
+        pair = _FusedPair(er, a, None, self.stream.cuda_stream, self._ws)
         keep += [er, pair]
         return pair
 
@@ -588,9 +628,9 @@ class IntegerEngine:
         self._build_chains(N, H, W, x_view, logits_view)
 
     def _fixed(self, key):
-        """Recorded choice for `key` ("chains" / "tiles" / "fused_variants" / "fused_split_tiles"): the plan handed to the constructor
+        """Recorded choice for `key` ("chains" / "tiles" / "fused_variants" / "fused_split_tiles" / "splitk"): the plan handed to the constructor
         while the batch shape it was recorded for is being built (`_plan_on`; the chains of a multi-chain engine inherit it), else
-        the measurement switches HAWQ_CHAINS / HAWQ_TILES / HAWQ_ER_TILES / HAWQ_ER_SPLIT_TILES, else None (tune)."""
+        the measurement switches HAWQ_CHAINS / HAWQ_TILES / HAWQ_ER_TILES / HAWQ_ER_SPLIT_TILES / HAWQ_SPLITK, else None (tune)."""
         pl = getattr(self, "plan", None)
         if pl and getattr(self, "_plan_on", False):
             # chains whose tuned choices differ (uneven sub-batches, layers only one tile takes) are recorded one by one
@@ -604,21 +644,31 @@ class IntegerEngine:
             if pl.get(key) not in (None, ""):
                 return str(pl[key])
         return os.environ.get({"chains": "HAWQ_CHAINS", "tiles": "HAWQ_TILES", "fused_variants": "HAWQ_ER_TILES",
-                               "fused_split_tiles": "HAWQ_ER_SPLIT_TILES"}[key])
+                               "fused_split_tiles": "HAWQ_ER_SPLIT_TILES", "splitk": "HAWQ_SPLITK"}[key])
 
     def export_plan(self):
         """The plan of the batch shape built last, as plain strings (what bench.py prints as config.autotuned_tiles / fused_variants /
-        fused_split_tiles / concurrent_sub_batches): feed it back through ``IntegerEngine(model, plan=...)`` to replay it."""
+        fused_split_tiles / concurrent_sub_batches): feed it back through ``IntegerEngine(model, plan=...)`` to replay it.
+        "splitk" (only written when some launch runs split-K): the K-slice count of every conv launch in the order of "tiles",
+        then two per pair in the order of "fused_variants" (its two-launch form: expand, reduce), 0 = hawq_conv2d."""
         if self._batch is None:
             raise RuntimeError("export_plan: no batch shape has been built yet")
 
-        def strings(e):
-            return {"tiles": ".".join(str(t) for t in e.tile_choice.values()),
-                    "fused_variants": ".".join(str(t) for t in e.er_choice.values()),
-                    "fused_split_tiles": ".".join(f"{a}.{b}" for a, b in getattr(e, "er_split_tiles", {}).values())}
+        any_split = any(any(e.splitk_choice()) for e in (self.subs or [self]))
+
+        def strings(e):   # (with a split launch in any chain, every chain's entry names its own split counts, zeros included)
+            out = {"tiles": ".".join(str(t) for t in e.tile_choice.values()),
+                   "fused_variants": ".".join(str(t) for t in e.er_choice.values()),
+                   "fused_split_tiles": ".".join(f"{a}.{b}" for a, b in getattr(e, "er_split_tiles", {}).values())}
+            if any_split:
+                out["splitk"] = ".".join(str(v) for v in e.splitk_choice())
+            return out
         per = [strings(e) for e in self.subs]
         # the top-level strings are chain 0's; "per_chain" is only written when another chain runs something else
         extra = {"per_chain": per} if any(p != per[0] for p in per[1:]) else {}
+        sk0 = (self.subs[0] if self.subs else self).splitk_choice()
+        if any(sk0):
+            extra["splitk"] = ".".join(str(v) for v in sk0)
         return {"batch": int(self._batch[0]), "chains": int(self.chains), "expand_in8": self.expand_in8, **extra,
                 "tiles": ".".join(str(t) for t in self.tile_choice.values()),
                 "fused_variants": ".".join(str(t) for t in self.er_choice.values()),
@@ -628,9 +678,49 @@ class IntegerEngine:
                 "num_conv_tiles": int(_lib.load().hawq_conv2d_num_tiles()),
                 "pair_variant_counts": [int(_lib.load().hawq_conv_expand_reduce_variants(C.byref(p.er))) for p in (self.subs[0] if self.subs else self)._er_args]}
 
+    def splitk_choice(self):
+        """K-slice count of every conv launch, then of both launches of every pair's two-launch form (0 = not split)."""
+        if self.subs:
+            return self.subs[0].splitk_choice()
+        return [op.splitk for op in self._conv_ops] + [v for p in self._er_args for v in (p.split_e, p.split_r)]
+
+    def n_splitk(self) -> int:
+        """Split-K launches in the forward as built (a pair's two-launch form counts only when the pair runs unfused)."""
+        engines = self.subs or [self]
+        return sum(sum(op.splitk > 0 for op in e._conv_ops) +
+                   sum((p.split_e > 0) + (p.split_r > 0) for p in e._er_args if not p.fused) for e in engines)
+
+    def _set_splitk(self, values):
+        """Apply a splitk_choice() list to this chain (the library must take every non-zero entry)."""
+        ops = list(self._conv_ops) + [None] * (2 * len(self._er_args))
+        if len(values) != len(ops):
+            raise StalePlan(f"the recorded plan lists {len(values)} split-K entries, this plan has {len(ops)} launches")
+        slots = [(op.a, op, "splitk") for op in self._conv_ops]
+        for p in self._er_args:
+            slots += [(p.expand, p, "split_e"), (p.reduce, p, "split_r")]
+        for (a, obj, attr), v in zip(slots, values):
+            v = int(v)
+            if v:
+                if a is None or not _lib.load().hawq_conv2d_splitk_ok(C.byref(a), v):
+                    raise StalePlan(f"the library refuses split-K with {v} slices for a recorded launch")
+                self._ws.fit(a, v)
+            setattr(obj, attr, v)
+
+    def _splitk_options(self, a):
+        """K-slice counts the tuner times for hawq_conv2d launch `a`: the candidates the library takes, when even the library's smallest
+        output tiles (64 px x 64 ch, the split-K kernel's own) are fewer than the chip's CUs - then every tile leaves CUs idle and each
+        launch lasts one workgroup's whole K loop.  HAWQ_NO_SPLITK=1 turns the candidates off (A/B switch)."""
+        if os.environ.get("HAWQ_NO_SPLITK"):
+            return []
+        ho = (a.H + 2 * a.pad - a.KH) // max(1, a.stride) + 1
+        wo = (a.W + 2 * a.pad - a.KW) // max(1, a.stride) + 1
+        if -(-a.N * ho * wo // 64) * (a.Cout // 64) >= torch.cuda.get_device_properties(self.dev).multi_processor_count:
+            return []
+        return [s for s in SPLITK_CANDIDATES if _lib.load().hawq_conv2d_splitk_ok(C.byref(a), s)]
+
     def _plan_snapshot(self):
-        """Tile / fused-variant choice of every launch of the current plan (one entry per chain)."""
-        return [dict(tiles=[a.tile for a in e._conv_args],
+        """Tile / fused-variant / split-K choice of every launch of the current plan (one entry per chain)."""
+        return [dict(tiles=[a.tile for a in e._conv_args], splitk=e.splitk_choice(),
                      pairs=[(p.fused, p.er.tile, p.expand.tile, p.reduce.tile if p.reduce is not None else 0) for p in e._er_args],
                      tile_choice=dict(e.tile_choice), er_choice=dict(e.er_choice), er_split=dict(getattr(e, "er_split_tiles", {})))
                 for e in (self.subs or [self])]
@@ -647,6 +737,7 @@ class IntegerEngine:
                 p.fused, p.er.tile, p.expand.tile = fused, vt, te
                 if p.reduce is not None:
                     p.reduce.tile = tr
+            e._set_splitk(pl["splitk"])
             e.tile_choice.clear(), e.tile_choice.update(pl["tile_choice"])
             e.er_choice.clear(), e.er_choice.update(pl["er_choice"])
             if hasattr(e, "er_split_tiles"):
@@ -719,6 +810,8 @@ class IntegerEngine:
         self.subs = []
         ops, keep = _OpList(), []
         self._conv_args, self._conv_names = [], []
+        self._conv_ops = []   # the _ConvLaunch of every entry of _conv_args
+        self._ws = _SplitWorkspace(dev)
         self.acc_taps = {}
         self.res_taps = {}   # unit name -> (stored post-ReLU residual tensor of this plan, NHWC shape): parity tests read them back
         self.n_fast = self.n_conv = self.n_k0 = self.n_tie = self.n_ck0 = 0  # how many conv launches run the fast-contract kernels (/ shift-free)
@@ -870,8 +963,9 @@ class IntegerEngine:
                     continue
                 self._conv_args.append(a)
                 self._conv_names.append(tap_name)
+                self._conv_ops.append(_ConvLaunch(a, self._ws, sp))
                 ops.next_name = tap_name + ("+identity" if (a.in2 is not None) else "")
-                ops.append(partial(_lib.call, "hawq_conv2d", C.byref(a), sp))
+                ops.append(self._conv_ops[-1])
                 if ci < len(u['convs']) - 1:
                     x_in, x_bits, hin, win, x_planar = x_next, xb_next, ho, wo, planar_next
             res, qa, h, w = new_res, new_qa, ho, wo
@@ -903,7 +997,8 @@ class IntegerEngine:
             ops.append(partial(_lib.call, "hawq_fc_dequant", qf.data_ptr(), fc['w'].data_ptr(), fc['bias'].data_ptr(), fc['fscale'].data_ptr(),
                                self.logits.data_ptr(), N, fc['k'], fc['nout_p'], fc['nout'], fc['nout'], sp))
         else:
-            ops.append(partial(_lib.call, "hawq_conv2d", C.byref(a), sp))
+            self._conv_ops.append(_ConvLaunch(a, self._ws, sp))
+            ops.append(self._conv_ops[-1])
             self._conv_args.append(a)  # the FC GEMM (M = batch, K = 2048) is tile-tuned like the convs
             self._conv_names.append("quant_output")
         keep += [qf, pooled, a]
@@ -984,15 +1079,32 @@ class IntegerEngine:
                 elif not pair.fused:
                     raise StalePlan("the recorded plan runs a pair as two launches but lists no tiles for them")
                 self.er_choice[name] = pair.er.tile
+            sk = self._fixed("splitk")   # absent (every plan recorded before split-K existed): no launch is split
+            self._set_splitk([int(v) for v in sk.split(".")] if sk else [0] * (len(self._conv_ops) + 2 * len(self._er_args)))
             return
         # the events are created only on the timing path (the replay branch above returns or raises StalePlan without them)
         e0, e1 = C.c_void_p(), C.c_void_p()
         _lib.call("hawq_event_create", C.byref(e0))
         _lib.call("hawq_event_create", C.byref(e1))
         ms = C.c_float()
+        def time_split(a, times):   # split-K candidates of one launch (keys -S: S K slices), two rounds, per-count minimum
+            for rnd in range(2):
+                for sk in self._splitk_options(a):
+                    try:
+                        self._ws.fit(a, sk)
+                        self._ws.launch(a, sk, sp)  # warm
+                        _lib.call("hawq_event_record", e0, sp)
+                        for _ in range(reps):
+                            self._ws.launch(a, sk, sp)
+                        _lib.call("hawq_event_record", e1, sp)
+                        _lib.call("hawq_event_elapsed_ms", e0, e1, C.byref(ms))
+                    except RuntimeError:
+                        continue
+                    times[-sk] = min(times.get(-sk, ms.value), ms.value)
+
         with torch.cuda.stream(self.stream):
             self._launch_all()  # every buffer holds valid data
-            for name, a in [(n, k) for n, k in zip(self._conv_names, self._conv_args)]:
+            for name, a, op in [(n, k, o) for n, k, o in zip(self._conv_names, self._conv_args, self._conv_ops)]:
                 if os.environ.get("HAWQ_TILE_RES") or os.environ.get("HAWQ_TILE_REQ"):
                     break
                 times = {}
@@ -1011,14 +1123,18 @@ class IntegerEngine:
                         except RuntimeError:
                             continue
                         times[tile] = min(times.get(tile, ms.value), ms.value)
-                best_t = min(times, key=times.get)
-                self._tile_times[name] = dict(times)
-                log = [f"{t}:{v / reps * 1e3:.1f}" for t, v in times.items()]
-                if os.environ.get("HAWQ_AUTOTUNE_LOG"):
-                    print(f"[autotune N={a.N}] {name}: best {best_t}  us per tile: {' '.join(log)}", file=sys.stderr)
+                best_t = min((t for t in times if t > 0), key=times.get)
                 a.tile = best_t
+                time_split(a, times)
+                best_any = min(times, key=times.get)
+                op.splitk = -best_any if best_any < 0 else 0   # split-K keeps the best tile for the unsplit form of the plan
+                self._tile_times[name] = dict(times)
+                log = [f"{t if t > 0 else f's{-t}'}:{v / reps * 1e3:.1f}" for t, v in times.items()]
+                if os.environ.get("HAWQ_AUTOTUNE_LOG"):
+                    print(f"[autotune N={a.N}] {name}: best {best_t}{f' split {op.splitk}' if op.splitk else ''}  us per tile "
+                          f"(sS: split-K, S slices): {' '.join(log)}", file=sys.stderr)
                 self.tile_choice[name] = best_t
-            def best_tile(a):   # fastest applicable tile of one hawq_conv2d launch: (tile, ms per `reps` launches)
+            def best_tile(a):   # fastest applicable tile of one hawq_conv2d launch, and its split-K form: (tile, slices, ms per `reps` launches)
                 times = {}
                 for rnd in range(2):
                     for tile in range(1, n_tiles + 1):
@@ -1036,7 +1152,10 @@ class IntegerEngine:
                             continue
                         times[tile] = min(times.get(tile, ms.value), ms.value)
                 t = min(times, key=times.get)
-                return t, times[t]
+                a.tile = t
+                time_split(a, times)
+                best = min(times, key=times.get)
+                return t, (-best if best < 0 else 0), times[best]
 
             fixed_er = os.environ.get("HAWQ_ER_TILES")   # dotted list as printed by bench.py; 0 = two separate launches
             for k, (name, pair) in enumerate(zip(self._er_names, self._er_args)):
@@ -1065,8 +1184,8 @@ class IntegerEngine:
                         times[tile] = min(times.get(tile, ms.value), ms.value)
                 er.tile = min(times, key=times.get)
                 self._er_times[name] = dict(times)
-                te, ms_e = best_tile(pair.expand)
-                tr, ms_r = best_tile(pair.reduce) if pair.reduce is not None else (0, 0.0)
+                te, pair.split_e, ms_e = best_tile(pair.expand)
+                tr, pair.split_r, ms_r = best_tile(pair.reduce) if pair.reduce is not None else (0, 0, 0.0)
                 pair.expand.tile = te
                 if pair.reduce is not None:
                     pair.reduce.tile = tr
@@ -1074,7 +1193,8 @@ class IntegerEngine:
                 if os.environ.get("HAWQ_AUTOTUNE_LOG"):
                     log = [f"{t}:{v / reps * 1e3:.1f}" for t, v in times.items()]
                     print(f"[autotune N={er.expand.N}] {name}+next reduce: fused variants (us) {' '.join(log)} | separate "
-                          f"{ms_e / reps * 1e3:.1f} (tile {te}) + {ms_r / reps * 1e3:.1f} (tile {tr}) -> {'fused' if pair.fused else 'separate'}",
+                          f"{ms_e / reps * 1e3:.1f} (tile {te}, split {pair.split_e}) + {ms_r / reps * 1e3:.1f} (tile {tr}, split {pair.split_r})"
+                          f" -> {'fused' if pair.fused else 'separate'}",
                           file=sys.stderr)
                 self.er_choice[name] = er.tile if pair.fused else 0
                 self.er_split_tiles = getattr(self, "er_split_tiles", {})
@@ -1093,7 +1213,6 @@ class IntegerEngine:
         isolated time is within `slack` of the best is timed again with ALL chains launching that layer at once (each on its own
         stream), and the tile with the shortest joint time wins - the same for a fused pair against its two-launch form."""
         subs = self.subs
-        lib_call = _lib.call
         slack, top = float(os.environ.get("HAWQ_JOINT_SLACK", slack)), int(os.environ.get("HAWQ_JOINT_TOP", top))
 
         def joint_ms(launch):
@@ -1131,17 +1250,22 @@ class IntegerEngine:
                 lim = slack * min(iso.values())
                 cand = sorted((t for t, v in iso.items() if v <= lim), key=iso.get)[:top]
                 res = {}
+                tiles0 = [sub._conv_args[k].tile for sub in subs]   # each chain's best tile: what a split-K choice keeps for the unsplit form
+
+                def choose(t):   # t > 0: tile id; t < 0: split-K with -t slices
+                    for sub, t0 in zip(subs, tiles0):
+                        sub._conv_args[k].tile = t if t > 0 else t0
+                        sub._conv_ops[k].splitk = -t if t < 0 else 0
                 for t in cand:
-                    for sub in subs:
-                        sub._conv_args[k].tile = t
-                    res[t] = joint_ms(lambda sub: lib_call("hawq_conv2d", C.byref(sub._conv_args[k]), sub.stream.cuda_stream))
+                    choose(t)
+                    res[t] = joint_ms(lambda sub: sub._conv_ops[k]())
                 best = min(res, key=res.get)
                 if log:
                     print(f"[joint tune] {name}: " + " ".join(f"{t}:{iso[t] / reps * 1e3:.1f}/{res[t] / reps * 1e3:.1f}" for t in cand)
-                          + f" (us alone / all chains) -> {best}", file=sys.stderr)
+                          + f" (us alone / all chains; negative: split-K slices) -> {best}", file=sys.stderr)
+                choose(best)
                 for sub in subs:
-                    sub._conv_args[k].tile = best
-                    sub.tile_choice[name] = best
+                    sub.tile_choice[name] = sub._conv_args[k].tile
             n_er = len(subs[0]._er_args)
             if all(len(sub._er_args) == n_er and sub._er_names == subs[0]._er_names for sub in subs):
                 for k, name in enumerate(subs[0]._er_names):

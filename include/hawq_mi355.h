@@ -187,6 +187,24 @@ int hawq_conv2d_num_gemm2_tiles(void);
 int hawq_conv2d_gemm2_first(void);
 int hawq_pack_w1x1_k128(const int8_t *src, int8_t *dst, int32_t Cout, int32_t Cin);
 
+/* Cross-workgroup split-K form of hawq_conv2d for launches with few output tiles (batch 1-16): the same arguments, the same
+ * integers (conv_splitk.hip).  The grid is (64-pixel x 64-channel output tiles) x (K slices); each slice workgroup writes its int32
+ * partial tile to `slab`, the last one to arrive at a tile (one int32 arrival counter per tile in `counters`) sums the slabs and
+ * runs hawq_conv2d's epilogue.  args->tile is ignored.  Takes: 1x1 / pad 0 or 3x3 / pad 1 convs with stride 1 or 2; int8 operands
+ * (both branches) and int8 out_q; HAWQ_EPI_RAW, REQUANT or RESIDUAL (pass-through identity, or the identity 1x1 conv as second
+ * branch); NHWC or planar in / out (planar input: single-branch fast-contract launches); any M.  Refuses 4-bit operands or
+ * outputs, n_valid / in_pitch / out_pitch, HAWQ_EPI_DEQUANT, and slice counts that do not divide the KH * KW * Cin / 64 K chunks.
+ * The second branch's Cin2 / 64 chunks become S2 extra slices of q2 chunks, q2 = the largest divisor of Cin2 / 64 that is
+ * <= KH * KW * Cin / 64 / slices.
+ *   hawq_conv2d_splitk_ok: 1 = the kernel takes this launch with `slices` slices of the main branch, 0 = it refuses (host only).
+ *   hawq_conv2d_splitk_workspace: slab_bytes = tiles * (slices + S2) * 64 * 64 * 4, counter_bytes = tiles * 4 with
+ *     tiles = ceil(N * Ho * Wo / 64) * Cout / 64 (host only; non-zero return if the launch is refused).
+ *   hawq_conv2d_splitk: `counters` must be zero before the first launch; every launch leaves them zero, so launches on one stream
+ *     (and graph replays) may share one workspace.  Launches that may run concurrently need workspaces of their own. */
+int hawq_conv2d_splitk_ok(const hawq_conv_args *args, int32_t slices);
+int hawq_conv2d_splitk_workspace(const hawq_conv_args *args, int32_t slices, int64_t *slab_bytes, int64_t *counter_bytes);
+int hawq_conv2d_splitk(const hawq_conv_args *args, int32_t slices, void *slab, int32_t *counters, void *stream);
+
 /* Fused launch of two consecutive layers of the bottleneck graph (q_resnet.py:231-260): the 1x1 expand conv of unit i
  * with its RESIDUAL epilogue (x + identity -> quant_act_int32 -> ReLU -> quant_act of unit i+1) and the 1x1 reduce
  * conv of unit i+1 with its REQUANT epilogue (ReLU -> quant_act1).  `expand` and `reduce` are filled exactly as for
