@@ -52,6 +52,30 @@ class BottleneckArgs(C.Structure):
                 ("dw_stride", i32), ("dw_q_lo", i32), ("dw_q_hi", i32), ("dw_fast_tables", i32), ("c_mid", i32), ("tile", i32)]
 
 
+class IncepConvArgs(C.Structure):
+    """struct hawq_incep_conv_args (include/hawq_mi355.h): the InceptionV3 rectangular conv."""
+    _fields_ = [
+        ("in_", vp), ("wgt", vp), ("bias", vp),
+        ("N", i32), ("H", i32), ("W", i32), ("Cin", i32), ("Cout", i32), ("KH", i32), ("KW", i32),
+        ("stride", i32), ("pad_h", i32), ("pad_w", i32),
+        ("epilogue", i32), ("relu", i32),
+        ("m", vp), ("ek", vp),
+        ("q_lo", i32), ("q_hi", i32), ("m2", i32), ("ek2", i32), ("q2_lo", i32), ("q2_hi", i32),
+        ("out", vp),
+        ("out_bits", i32), ("ldo", i32), ("c_off", i32), ("reserved", i32),
+    ]
+
+
+INCEP_RAW, INCEP_REQUANT, INCEP_REQUANT2 = 0, 1, 2
+
+
+class IncepPoolArgs(C.Structure):
+    """struct hawq_incep_pool_args (include/hawq_mi355.h): the InceptionV3 plan's pool / requant launches."""
+    _fields_ = [("in_", vp), ("out", vp)] + [(n, i32) for n in (
+        "N", "H", "W", "C", "in_bits", "in_pitch", "in_off", "out_bits", "ldo", "c_off",
+        "pre", "m1", "ek1", "lo1", "hi1", "post", "m2", "ek2", "lo2", "hi2")]
+
+
 # name -> (argtypes); every function returns int except hawq_last_error
 SIGNATURES = {
     "hawq_abi_version": [],
@@ -100,6 +124,12 @@ SIGNATURES = {
     "hawq_resample_u8": [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp],
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
+    "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],
+    "hawq_avgpool3x3_f32": [vp, vp, i32, i32, i32, f32, vp],
+    "hawq_incep_requant": [C.POINTER(IncepPoolArgs), vp],
+    "hawq_incep_maxpool3s2": [C.POINTER(IncepPoolArgs), vp],
+    "hawq_incep_avgpool_branch": [C.POINTER(IncepPoolArgs), vp],
+    "hawq_incep_global_avgpool": [C.POINTER(IncepPoolArgs), vp],
     "hawq_graph_begin": [vp],
     "hawq_graph_end": [vp, C.POINTER(vp)],
     "hawq_graph_launch": [vp, vp],

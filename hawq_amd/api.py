@@ -13,7 +13,11 @@ from .skeleton import build_float_resnet, init_synthetic
 def build_quantized_resnet(arch: str, scheme: str, seed: int | None = 0, float_model=None):
     """Float skeleton (synthetic weights unless ``float_model`` is given) -> Q_ResNet (or, ``mobilenetv2_w1``,
     Q_MobileNetV2) with the ``bit_config_<arch>_<scheme>`` schedule applied; eval mode, un-frozen."""
-    if arch == "mobilenetv2_w1":
+    if arch == "inceptionv3":
+        from .q_inceptionv3 import q_inceptionv3
+        from .skeleton import build_float_inceptionv3
+        build, quantize = build_float_inceptionv3, q_inceptionv3
+    elif arch == "mobilenetv2_w1":
         from .q_mobilenetv2 import q_mobilenetv2_w1
         from .skeleton import build_float_mobilenetv2
         build, quantize = build_float_mobilenetv2, q_mobilenetv2_w1

@@ -51,6 +51,33 @@ def mobilenetv2_module_names(stray: bool = False) -> list[str]:
     return names + ["quant_act_before_final_block", "features.final_block", "quant_act_int32_final", "quant_act_output", "output"]
 
 
+def inceptionv3_module_names() -> list[str]:
+    """Names of the quantized modules of Q_InceptionV3 in the order of the reference's schedules (bit_config.py:3056-3601).  That
+    order is registration order except in the average-pool branches, which list ``q_conv.q_convbn`` before ``q_pool_act``."""
+    from .skeleton import inception_unit_branches, inception_units
+
+    def conv(p):
+        return [p + ".q_convbn", p + ".q_activ"]
+
+    p = "features.q_init_block."
+    names = [p + "q_input_activ"] + [n for i in range(1, 6) for n in conv(p + f"q_conv{i}")]
+    for si, ui, kind, _, cout, mid in inception_units():
+        u = f"features.stage{si}.unit{ui}."
+        for bi, br in enumerate(inception_unit_branches(kind, cout, mid)):
+            b = u + f"branches.branch{bi + 1}."
+            names.append(b + "q_input_act")
+            if br[0] == "conv1x1":
+                names += conv(b + "q_conv")
+            elif br[0] == "avgpool":
+                names += [b + "q_conv.q_convbn", b + "q_pool_act", b + "q_conv.q_activ"]
+            elif br[0] in ("seq", "seq3x3"):
+                names += [n for i in range(1, len(br[1]) + 1) for n in conv(b + f"q_conv_list.q_conv{i}")]
+                if br[0] == "seq3x3":
+                    names += conv(b + "q_conv1x3") + conv(b + "q_conv3x1") + [b + "q_rescaling_activ"]
+        names.append(u + "q_rescaling_activ")
+    return names + ["features.q_concat_activ", "output.q_fc"]
+
+
 _MOBILENET_TABLE = {   # tools/gen_bit_schedules.py
     "mobilenetv2_w1_uniform8": "88g888888g888888g888888g888888g888888g888888g888888g888888g888888g888888g88888888g888888g888888g888888g888888g888888g888888g88g88",
     "mobilenetv2_w1_modelsize_0.5": "88g888888g888888g888888g888888g448888g448888g888888g448844g448844g448844g888888g448844g448844g888888g448844g888888g888888g88g88",
@@ -87,6 +114,11 @@ _TABLE = {
     "resnet101_uniform4": "88g4444444g444444g444444g4444444g444444g444444g444444g4444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g444444g4444444g444444g444444g88",
 }
 
+_INCEPTION_TABLE = {   # tools/gen_bit_schedules.py; the reference's `(8, 'hook')` entries are stored as their bit width
+    "inceptionv3_uniform8": "8888888888g88g8888g888888gg88gg88g8888g888888gg88gg88g8888g888888gg88gg88g888888ggg88g888888g8888888888gg88gg88g888888g8888888888gg88gg88g888888g8888888888gg88gg88g888888g8888888888gg88gg8888g88888888ggg88g8888g8gg888888g8ggg88gg88g8888g8gg888888g8ggg88gg88",
+    "inceptionv3_uniform4": "8844444444g44g4444g444444gg44gg44g4444g444444gg44gg44g4444g444444gg44gg44g444444ggg44g444444g4444444444gg44gg44g444444g4444444444gg44gg44g444444g4444444444gg44gg44g444444g4444444444gg44gg4444g44444444ggg44g4444g4gg444444g4ggg44gg44g4444g4gg444444g4ggg44gg88",
+}
+
 _BITS = {"4": 4, "8": 8, "g": 16}
 
 bit_config_dict = {}
@@ -102,6 +134,15 @@ for _name, _s in _MOBILENET_TABLE.items():
     assert len(_names) == len(_s), _name
     bit_config_dict["bit_config_" + _name] = {n: _BITS[c] for n, c in zip(_names, _s)}
 
+# The InceptionV3 schedules live in a dict of their own: ``bit_config_dict`` keeps exactly the 30 schedules the integer engines
+# were built for, which callers (and tests) enumerate; ``get_bit_config`` serves both.
+inception_bit_config_dict = {}
+for _name, _s in _INCEPTION_TABLE.items():
+    _names = inceptionv3_module_names()
+    assert len(_names) == len(_s), _name
+    inception_bit_config_dict["bit_config_" + _name] = {n: _BITS[c] for n, c in zip(_names, _s)}
+
 
 def get_bit_config(arch: str, scheme: str) -> dict:
-    return bit_config_dict[f"bit_config_{arch}_{scheme}"]
+    key = f"bit_config_{arch}_{scheme}"
+    return inception_bit_config_dict[key] if key in inception_bit_config_dict else bit_config_dict[key]

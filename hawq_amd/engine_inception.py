@@ -1,0 +1,344 @@
+"""Fused integer plan of a frozen Q_InceptionV3 (hawq_amd/q_inceptionv3.py): one plan per batch shape, captured once into a
+hipGraph and replayed.
+
+Buffers are NHWC integers: int16 for the unit tensors (the 16-bit ``q_rescaling_activ`` outputs) and int8 for everything a
+conv reads (every conv input of the schedules is at most 8 bits; 4-bit values travel in int8 containers).  Per unit, the
+branches launch one after another on the plan's stream:
+* conv branches: ``hawq_incep_requant`` (the branch's ``q_input_act``, int16 -> int8), then one ``hawq_incep_conv`` per conv
+  (REQUANT: ReLU + the conv's ``q_activ``); the branch's last conv uses REQUANT2, whose second requant is the unit's concat
+  rescale (branch scale -> unit scale, quant_modules.py:275-286), and writes its channel slice of the unit buffer in place;
+* Inception-C's 3x3 branches: the 1x3 / 3x1 convs write their REQUANT2 results (conv scale -> the branch's inner concat scale)
+  into an int16 buffer of their own, and ``hawq_incep_requant`` rescales it into the unit buffer;
+* average-pool branches: ``hawq_incep_avgpool_branch`` (16-bit ``q_input_act``, 3x3 sum, trunc rule, ``q_pool_act``) -> int8,
+  then the 1x1 conv as above;
+* max-pool branches: ``hawq_incep_maxpool3s2`` (16-bit ``q_input_act``, max, concat rescale) into the unit buffer.
+Stem: the input QuantAct (``hawq_fakequant_f32`` + ``hawq_f32_nchw_to_q_nhwc``), five convs, two max pools.  Head:
+``hawq_incep_global_avgpool`` (8 x 8 trunc rule + ``q_concat_activ``), the classifier as a 1x1 RAW conv and
+``hawq_acc_nhwc_to_f32_nchw`` (fp32 logits = (acc + bias) * fl(S_w * S_a), quant_modules.py:125-130).
+
+Every requant is the exact dyadic form of fixedpoint_fn (``requant_table(..., lift=False)``); tiles are fixed (no tuning).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from functools import partial
+
+import numpy as np
+import torch
+
+from . import _lib
+from .quant_modules import QuantAct
+from .quant_utils import requant_table
+
+
+class PlanNotApplicable(RuntimeError):
+    pass
+
+
+def _pad16(c):
+    return (c + 15) // 16 * 16
+
+
+def _rng(act: QuantAct):
+    b = act.activation_bit
+    return (-(1 << (b - 1)), (1 << (b - 1)) - 1) if act.quant_mode == "symmetric" else (0, (1 << b) - 1)
+
+
+def _scale(act: QuantAct):
+    if getattr(act, "use_integer_buffers", False):
+        return act.act_scaling_factor.detach().reshape(-1)[:1].float().cpu()
+    return act.compute_scale().detach().reshape(-1)[:1].float().cpu()
+
+
+def _scalar_table(s_in, s_out):
+    m, ek = requant_table(s_in, torch.ones(1), s_out, lift=False)
+    return int(m[0]), int(ek[0])
+
+
+class _T:
+    """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale."""
+
+    def __init__(self, buf, h, w, c, pitch, scale, bits):
+        self.buf, self.h, self.w, self.c, self.pitch, self.scale, self.bits = buf, h, w, c, pitch, scale, bits
+
+
+class InceptionEngine:
+    def __init__(self, model, use_graph: bool = True):
+        self.model, self.use_graph = model, use_graph
+        self.dev = next(model.parameters()).device
+        self.stream = None   # created with the first plan: building the engine object needs no device
+        self._batch, self._graph, self._ops = None, None, []
+
+    def _zeros(self, *a, **k):
+        """a plan buffer: kept alive with the plan (the captured launches hold its address)"""
+        t = torch.zeros(*a, **k)
+        self._keep.append(t)
+        return t
+
+    # ------------------------------------------------------------------ launch builders
+    def _pool(self, name, src: _T, out_buf, out_bits, ldo, c_off, c, h, w, pre=None, post=None):
+        a = _lib.IncepPoolArgs()
+        a.in_, a.out = src.buf.data_ptr(), out_buf.data_ptr()
+        a.N, a.H, a.W, a.C = self.N, src.h, src.w, c
+        a.in_bits, a.in_pitch, a.in_off = src.bits, src.pitch, 0
+        a.out_bits, a.ldo, a.c_off = out_bits, ldo, c_off
+        if pre is not None:
+            a.pre, (a.m1, a.ek1, a.lo1, a.hi1) = 1, pre
+        if post is not None:
+            a.post, (a.m2, a.ek2, a.lo2, a.hi2) = 1, post
+        self._keep.append(a)
+        self._ops.append(partial(_lib.call, name, C.byref(a), self.stream.cuda_stream))
+
+    def _conv(self, ic, src: _T, dst=None, c_off=0, second=None):
+        """Q_InceptConv `ic` on `src` (int8): REQUANT into a new buffer, or - `dst`, `second` = (s_out2, act2) - REQUANT2 into the
+        channel slice `c_off` of `dst`.  Returns the output tensor (or `dst`)."""
+        cb, act = ic.q_convbn, ic.q_activ
+        if src.bits != 8:
+            raise PlanNotApplicable("a conv input wider than 8 bits")
+        if cb.conv.groups != 1 or cb.conv.dilation != (1, 1) or cb.conv.stride[0] != cb.conv.stride[1]:
+            raise PlanNotApplicable("grouped, dilated or anisotropic-stride conv")
+        s_a = src.scale
+        bias_scale = cb.prepare(s_a.to(self.dev))
+        w_int = cb.weight_integer.detach().cpu().numpy().astype(np.int8)
+        Cout, Cin, KH, KW = w_int.shape
+        cin_p, cout_p = src.pitch, _pad16(Cout)
+        w = np.zeros((cout_p, KH, KW, cin_p), np.int8)
+        w[:Cout, :, :, :Cin] = w_int.transpose(0, 2, 3, 1)
+        b = np.zeros(cout_p, np.int32)
+        b[:Cout] = cb.bias_integer.detach().cpu().numpy().astype(np.int64).clip(-2 ** 31, 2 ** 31 - 1)
+        s_out = _scale(act)
+        m, ek = requant_table(s_a, cb.convbn_scaling_factor.detach().reshape(-1).float().cpu(), s_out, lift=False)
+        mp, ekp = np.zeros(cout_p, np.int32), np.full(cout_p, 33, np.int32)
+        mp[:Cout], ekp[:Cout] = m, ek
+        ph, pw = cb.conv.padding
+        st = cb.conv.stride[0]
+        Ho, Wo = (src.h + 2 * ph - KH) // st + 1, (src.w + 2 * pw - KW) // st + 1
+        lo, hi = _rng(act)
+        a = _lib.IncepConvArgs()
+        if dst is None:
+            bits = 8 if act.activation_bit <= 8 else 16
+            out = _T(self._zeros(self.N * Ho * Wo * cout_p, dtype=torch.int8 if bits == 8 else torch.int16, device=self.dev),
+                     Ho, Wo, Cout, cout_p, s_out, bits)
+            a.epilogue, ldo = _lib.INCEP_REQUANT, cout_p
+        else:
+            if Cout % 16 or (dst.h, dst.w) != (Ho, Wo):
+                raise PlanNotApplicable("concat slice does not fit")
+            out = dst
+            s2, act2 = second
+            a.epilogue, ldo = _lib.INCEP_REQUANT2, dst.pitch
+            a.m2, a.ek2 = _scalar_table(s_out, s2)
+            a.q2_lo, a.q2_hi = _rng(act2)
+            cout_p = Cout
+        t = [torch.from_numpy(w).to(self.dev), torch.from_numpy(b).to(self.dev), torch.from_numpy(mp).to(self.dev),
+             torch.from_numpy(ekp).to(self.dev)]
+        a.in_, a.wgt, a.bias, a.out = src.buf.data_ptr(), t[0].data_ptr(), t[1].data_ptr(), out.buf.data_ptr()
+        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = self.N, src.h, src.w, cin_p, cout_p, KH, KW
+        a.stride, a.pad_h, a.pad_w, a.relu = st, ph, pw, 1
+        a.m, a.ek, a.q_lo, a.q_hi = t[2].data_ptr(), t[3].data_ptr(), lo, hi
+        a.out_bits, a.ldo, a.c_off = out.bits, ldo, c_off
+        self._keep += t + [a]
+        self._ops.append(partial(_lib.call, "hawq_incep_conv", C.byref(a), self.stream.cuda_stream))
+        return out
+
+    def _requant_input(self, act, src: _T):
+        """a branch's q_input_act of width <= 8: int16 unit tensor -> int8 branch tensor"""
+        if act.activation_bit > 8:
+            raise PlanNotApplicable("a 16-bit conv-branch input")
+        s = _scale(act)
+        out = _T(self._zeros(self.N * src.h * src.w * src.pitch, dtype=torch.int8, device=self.dev), src.h, src.w, src.c,
+                 src.pitch, s, 8)
+        self._pool("hawq_incep_requant", src, out.buf, 8, src.pitch, 0, src.pitch, src.h, src.w,
+                   post=(*_scalar_table(src.scale, s), *_rng(act)))
+        return out
+
+    def _unit(self, unit, src: _T):
+        from .q_inceptionv3 import Q_AvgPoolBranch, Q_ConvSeq3x3Branch, Q_MaxPoolBranch
+        uact = unit.q_rescaling_activ
+        if uact.activation_bit != 16 or uact.quant_mode != "symmetric":
+            raise PlanNotApplicable("unit output other than 16-bit symmetric")
+        s_u = _scale(uact)
+        branches = list(unit.branches.children())
+        widths, Ho, Wo = [], None, None
+        for br in branches:   # output widths and size of each branch
+            if isinstance(br, Q_MaxPoolBranch):
+                widths.append(src.c)
+                h, w = (src.h - 3) // 2 + 1, (src.w - 3) // 2 + 1
+            else:
+                convs = [m for m in br.modules() if hasattr(m, "q_convbn")]
+                c = convs[-1].q_convbn.conv
+                widths.append(c.out_channels * (2 if isinstance(br, Q_ConvSeq3x3Branch) else 1))
+                h, w = src.h, src.w
+                for ic in (list(br.q_conv_list) if hasattr(br, "q_conv_list") else [br.q_conv]):
+                    k, p, st = ic.q_convbn.conv.kernel_size, ic.q_convbn.conv.padding, ic.q_convbn.conv.stride[0]
+                    h, w = (h + 2 * p[0] - k[0]) // st + 1, (w + 2 * p[1] - k[1]) // st + 1
+            if Ho is not None and (Ho, Wo) != (h, w):
+                raise PlanNotApplicable("branches disagree on the output size")
+            Ho, Wo = h, w
+        cu = sum(widths)
+        if cu % 16 or any(x % 16 for x in widths):
+            raise PlanNotApplicable("channel counts must be multiples of 16")
+        dst = _T(self._zeros(self.N * Ho * Wo * cu, dtype=torch.int16, device=self.dev), Ho, Wo, cu, cu, s_u, 16)
+        off = 0
+        for br, wd in zip(branches, widths):
+            if isinstance(br, Q_MaxPoolBranch):
+                ia = br.q_input_act
+                s_b = _scale(ia)
+                self._pool("hawq_incep_maxpool3s2", src, dst.buf, 16, cu, off, src.c, src.h, src.w,
+                           pre=(*_scalar_table(src.scale, s_b), *_rng(ia)), post=(*_scalar_table(s_b, s_u), *_rng(uact)))
+            elif isinstance(br, Q_AvgPoolBranch):
+                ia, pa = br.q_input_act, br.q_pool_act
+                if pa.activation_bit > 8:
+                    raise PlanNotApplicable("a 16-bit q_pool_act")
+                s_b, s_p = _scale(ia), _scale(pa)
+                t = _T(self._zeros(self.N * src.h * src.w * src.pitch, dtype=torch.int8, device=self.dev), src.h, src.w,
+                       src.c, src.pitch, s_p, 8)
+                self._pool("hawq_incep_avgpool_branch", src, t.buf, 8, src.pitch, 0, src.c, src.h, src.w,
+                           pre=(*_scalar_table(src.scale, s_b), *_rng(ia)), post=(*_scalar_table(s_b, s_p), *_rng(pa)))
+                self._conv(br.q_conv, t, dst, off, (s_u, uact))
+            else:
+                x = self._requant_input(br.q_input_act, src)
+                convs = list(br.q_conv_list) if hasattr(br, "q_conv_list") else [br.q_conv]
+                if isinstance(br, Q_ConvSeq3x3Branch):
+                    for ic in convs:
+                        x = self._conv(ic, x)
+                    ra = br.q_rescaling_activ
+                    s_r = _scale(ra)
+                    half = wd // 2
+                    inner = _T(self._zeros(self.N * Ho * Wo * wd, dtype=torch.int16, device=self.dev), Ho, Wo, wd, wd, s_r, 16)
+                    self._conv(br.q_conv1x3, x, inner, 0, (s_r, ra))
+                    self._conv(br.q_conv3x1, x, inner, half, (s_r, ra))
+                    self._pool("hawq_incep_requant", inner, dst.buf, 16, cu, off, wd, Ho, Wo,
+                               post=(*_scalar_table(s_r, s_u), *_rng(uact)))
+                else:
+                    for ic in convs[:-1]:
+                        x = self._conv(ic, x)
+                    self._conv(convs[-1], x, dst, off, (s_u, uact))
+            off += wd
+        return dst
+
+    # ------------------------------------------------------------------ plan
+    def _build(self, N, H, W):
+        self._drop_graph()
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.dev)
+        self.N, dev, q = N, self.dev, self.model
+        self._ops, self._keep, self.unit_out = [], [], {}
+        ib = q.features.q_init_block
+        ia = ib.q_input_activ
+        s_in = _scale(ia)
+        lo, hi = _rng(ia)
+        self.x_in = torch.zeros(N, 3, H, W, dtype=torch.float32, device=dev)
+        xq_f = torch.zeros_like(self.x_in)
+        x0 = _T(self._zeros(N * H * W * 16, dtype=torch.int8, device=dev), H, W, 3, 16, s_in, 8)
+        inv = float((1. / s_in).item())
+        self._keep += [xq_f]
+        self._ops.append(partial(_lib.call, "hawq_fakequant_f32", self.x_in.data_ptr(), xq_f.data_ptr(), self.x_in.numel(), inv,
+                                 1.0, lo, hi, self.stream.cuda_stream))
+        self._ops.append(partial(_lib.call, "hawq_f32_nchw_to_q_nhwc", xq_f.data_ptr(), x0.buf.data_ptr(), N, 3, H, W, 16, 8, 1.0,
+                                 self.stream.cuda_stream))
+        x = x0
+        for name in ("q_conv1", "q_conv2", "q_conv3", "q_pool1", "q_conv4", "q_conv5", "q_pool2"):
+            if name.startswith("q_pool"):
+                h, w = (x.h - 3) // 2 + 1, (x.w - 3) // 2 + 1
+                y = _T(self._zeros(N * h * w * x.pitch, dtype=x.buf.dtype, device=dev), h, w, x.c, x.pitch, x.scale, x.bits)
+                self._pool("hawq_incep_maxpool3s2", x, y.buf, x.bits, x.pitch, 0, x.pitch, x.h, x.w)
+                x = y
+            else:
+                x = self._conv(getattr(ib, name), x)
+        if x.bits != 16 or x.pitch != x.c:
+            raise PlanNotApplicable("the stem output must be 16-bit")
+        for uname, unit in q.units():
+            x = self._unit(unit, x)
+            self.unit_out[uname] = x
+        ca = q.features.q_concat_activ
+        if ca.activation_bit > 8:
+            raise PlanNotApplicable("a 16-bit q_concat_activ")
+        s_c = _scale(ca)
+        feat = _T(self._zeros(N * x.c, dtype=torch.int8, device=dev), 1, 1, x.c, x.c, s_c, 8)
+        self._pool("hawq_incep_global_avgpool", x, feat.buf, 8, x.c, 0, x.c, x.h, x.w,
+                   post=(*_scalar_table(x.scale, s_c), *_rng(ca)))
+        fc = q.output.q_fc
+        bias_scale = fc.prepare(s_c.to(dev))
+        K, O = fc.in_features, fc.out_features
+        op = _pad16(O)
+        wf = np.zeros((op, 1, 1, K), np.int8)
+        wf[:O, 0, 0, :] = fc.weight_integer.detach().cpu().numpy().astype(np.int8)
+        bf = np.zeros(op, np.int32)
+        bf[:O] = fc.bias_integer.detach().cpu().numpy().astype(np.int64).clip(-2 ** 31, 2 ** 31 - 1)
+        fs = np.zeros(op, np.float32)
+        fs[:O] = bias_scale.detach().reshape(-1).cpu().numpy()
+        t = [torch.from_numpy(wf).to(dev), torch.from_numpy(bf).to(dev), torch.from_numpy(fs).to(dev)]
+        acc = torch.zeros(N * op, dtype=torch.int32, device=dev)
+        self.logits = torch.zeros(N, O, dtype=torch.float32, device=dev)
+        a = _lib.IncepConvArgs()
+        a.in_, a.wgt, a.bias, a.out = feat.buf.data_ptr(), t[0].data_ptr(), t[1].data_ptr(), acc.data_ptr()
+        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride = N, 1, 1, K, op, 1, 1, 1
+        a.epilogue, a.ldo, a.c_off = _lib.INCEP_RAW, op, 0
+        self._keep += t + [a, acc]
+        self._ops.append(partial(_lib.call, "hawq_incep_conv", C.byref(a), self.stream.cuda_stream))
+        self._ops.append(partial(_lib.call, "hawq_acc_nhwc_to_f32_nchw", acc.data_ptr(), self.logits.data_ptr(), N, O, 1, 1, op,
+                                 t[2].data_ptr(), self.stream.cuda_stream))
+        self._batch = (N, H, W)
+
+    def _drop_graph(self):
+        if self._graph is not None:
+            _lib.call("hawq_graph_destroy", self._graph)
+            self._graph = None
+
+    def __del__(self):
+        try:
+            self._drop_graph()
+        except Exception:
+            pass
+
+    def _launch_all(self):
+        for op in self._ops:
+            op()
+
+    def run_resident(self):
+        """One forward over ``self.x_in`` on ``self.stream``: graph replay, or (use_graph False) the launches one by one."""
+        if not self.use_graph:
+            self._launch_all()
+            return
+        if self._graph is None:
+            self._launch_all()   # warm-up outside capture
+            torch.cuda.synchronize(self.dev)
+            _lib.call("hawq_graph_begin", self.stream.cuda_stream)
+            g = C.c_void_p()
+            try:
+                self._launch_all()
+            finally:
+                _lib.call("hawq_graph_end", self.stream.cuda_stream, C.byref(g))
+            self._graph = g
+        _lib.call("hawq_graph_launch", self._graph, self.stream.cuda_stream)
+
+    @property
+    def n_launches(self):
+        return len(self._ops)
+
+    def __call__(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("InceptionEngine: input must be on the MI355X (no CPU path)")
+        N, Cc, H, W = x.shape
+        if Cc != 3:
+            raise ValueError("expected [N,3,H,W] images")
+        if self._batch != (N, H, W):
+            self._build(N, H, W)
+        cur = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self.x_in.copy_(x, non_blocking=True)
+            self.run_resident()
+            out = self.logits.clone()
+        cur.wait_stream(self.stream)
+        return out
+
+    def forward_uint8(self, x_u8, mean=None, std=None):
+        raise NotImplementedError("uint8 image input (look-up-table input quantiser) is not built for InceptionV3")
+
+    def unit_output(self, name):
+        """int64 NCHW numpy array of a unit's integer output (after its q_rescaling_activ) of the last forward."""
+        t = self.unit_out[name]
+        torch.cuda.synchronize(self.dev)
+        a = t.buf.view(self.N, t.h, t.w, t.pitch)[..., :t.c].permute(0, 3, 1, 2)
+        return a.cpu().numpy().astype(np.int64)

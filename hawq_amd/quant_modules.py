@@ -95,9 +95,10 @@ class QuantAct(Module):
 
     def forward(self, x, pre_act_scaling_factor=None, pre_weight_scaling_factor=None, identity=None,
                 identity_scaling_factor=None, identity_weight_scaling_factor=None):
+        channel_num = None
         if type(x) is tuple:
-            if len(x) == 3:
-                raise NotImplementedError("multi-branch (Inception) QuantAct is outside the ResNet hot path")
+            if len(x) == 3:   # (concat of branch outputs, [branch scales], [branch widths]) of InceptionV3's Q_Concurrent
+                channel_num = x[2]
             pre_act_scaling_factor = x[1]
             x = x[0]
         if self.quant_mode == "symmetric":
@@ -133,7 +134,16 @@ class QuantAct(Module):
         if (pre_act_scaling_factor is None) or (self.fixed_point_quantization is True):
             quant_act_int = self.act_function(x, self.activation_bit, self.act_scaling_factor)
         elif type(pre_act_scaling_factor) is list:
-            raise NotImplementedError("multi-branch (Inception) QuantAct is outside the ResNet hot path")
+            # multi-branch requant (quant_modules.py:275-286): each branch's channel slice from its own scale to this one, with
+            # the weight scale s / s of the reference
+            parts, start = [], 0
+            for s_i, c_i in zip(pre_act_scaling_factor, channel_num):
+                parts.append(fixedpoint_fn.apply(x[:, start:start + c_i], self.activation_bit, self.quant_mode,
+                                                 self.act_scaling_factor, 0, s_i, s_i / s_i))
+                start += c_i
+            if start != x.shape[1]:
+                raise ValueError(f"QuantAct: branch widths {channel_num} do not add up to {x.shape[1]} channels")
+            quant_act_int = torch.cat(parts, dim=1)
         elif identity is None:
             if pre_weight_scaling_factor is None:
                 pre_weight_scaling_factor = self.pre_weight_scaling_factor
@@ -228,7 +238,58 @@ class _IntConvMixin:
         _lib.call("hawq_acc_nhwc_to_f32_nchw", acc.data_ptr(), y.data_ptr(), N, Cout, Ho, Wo, Cout, self._dev_fs.data_ptr(), _stream())
         return y
 
-class QuantBnConv2d(_IntConvMixin, Module):
+def _pad16(c):
+    return (c + 15) // 16 * 16
+
+
+class _RectConvMixin:
+    """fp32 NCHW (int*scale) -> hawq_incep_conv (RAW epilogue: exact int32 accumulators) -> fp32 NCHW, for any KH x KW window
+    up to 7 with its own padding per axis.  Activations of at most 8 bits (4-bit ones in int8 containers), channels padded
+    to 16 with zeros."""
+
+    def _run_rect_conv(self, x, pre_act_scaling_factor, weight_integer, bias_integer, bias_scale, stride, padding, groups=1):
+        if groups != 1 or stride[0] != stride[1]:
+            raise NotImplementedError("hawq_incep_conv: grouped convs and unequal strides are outside the path")
+        if getattr(self, "input_bit", 8) > 8 or tuple(self.conv.dilation) != (1, 1):
+            raise NotImplementedError("hawq_incep_conv: inputs wider than 8 bits and dilated convs are outside the path")
+        N, Cin, H, W = x.shape
+        Cout, _, KH, KW = weight_integer.shape
+        dev = x.device
+        key = ("rect", weight_integer.data_ptr(), weight_integer._version, bias_integer.data_ptr(), bias_integer._version, str(dev))
+        if getattr(self, "_dev_key", None) != key:
+            cin_p, cout_p = _pad16(Cin), _pad16(Cout)
+            w = np.zeros((cout_p, KH, KW, cin_p), np.int8)
+            w[:Cout, :, :, :Cin] = weight_integer.detach().cpu().numpy().astype(np.int8).transpose(0, 2, 3, 1)
+            b = np.zeros(cout_p, np.int32)
+            b[:Cout] = bias_integer.detach().cpu().numpy().astype(np.int64).clip(-2 ** 31, 2 ** 31 - 1)
+            fs = np.zeros(cout_p, np.float32)
+            fs[:Cout] = bias_scale.detach().reshape(-1).cpu().numpy()
+            self._dev_w, self._dev_b = torch.from_numpy(w).to(dev), torch.from_numpy(b).to(dev)
+            self._dev_fs = torch.from_numpy(fs).to(dev)
+            self._dev_cin_p, self._dev_cout_p = cin_p, cout_p
+            self._dev_key = key
+        cin_p, cout_p = self._dev_cin_p, self._dev_cout_p
+        x = x.contiguous().float()
+        s_a = float(pre_act_scaling_factor.detach().reshape(-1)[0].item())
+        xq = torch.empty(N * H * W * cin_p, dtype=torch.int8, device=dev)
+        _lib.call("hawq_f32_nchw_to_q_nhwc", x.data_ptr(), xq.data_ptr(), N, Cin, H, W, cin_p, 8, s_a, _stream())
+        Ho = (H + 2 * padding[0] - KH) // stride[0] + 1
+        Wo = (W + 2 * padding[1] - KW) // stride[0] + 1
+        acc = torch.empty(N * Ho * Wo * cout_p, dtype=torch.int32, device=dev)
+        a = _lib.IncepConvArgs()
+        a.in_, a.wgt, a.bias, a.out = xq.data_ptr(), self._dev_w.data_ptr(), self._dev_b.data_ptr(), acc.data_ptr()
+        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, cin_p, cout_p, KH, KW
+        a.stride, a.pad_h, a.pad_w = stride[0], padding[0], padding[1]
+        a.epilogue, a.ldo, a.c_off = _lib.INCEP_RAW, cout_p, 0
+        _lib.call("hawq_incep_conv", a, _stream())
+        y = torch.empty(N, Cout, Ho, Wo, dtype=torch.float32, device=dev)
+        _lib.call("hawq_acc_nhwc_to_f32_nchw", acc.data_ptr(), y.data_ptr(), N, Cout, Ho, Wo, cout_p,
+                  self._dev_fs.data_ptr(), _stream())
+        self.last_accumulators = (acc, (N, Ho, Wo, cout_p))  # int32 NHWC, for parity checks
+        return y
+
+
+class QuantBnConv2d(_IntConvMixin, _RectConvMixin, Module):
     """Conv with folded BatchNorm (reference: quant_modules.py:308-494); frozen/folded branch."""
 
     def __init__(self, weight_bit=4, bias_bit=None, full_precision_flag=False, quant_mode="symmetric",
@@ -324,6 +385,12 @@ class QuantBnConv2d(_IntConvMixin, Module):
         _require_device(x, "QuantBnConv2d")
         bias_scale = self.prepare(pre_act_scaling_factor)
         in_bits = getattr(self, "input_bit", 8)
+        KH, KW = self.conv.kernel_size
+        if getattr(self, "incep_conv", False) or KH != KW or self.conv.padding[0] != self.conv.padding[1]:
+            # InceptionV3's windows (1x7, 7x1, 5x5, ...) with their own padding per axis
+            y = self._run_rect_conv(x, pre_act_scaling_factor, self.weight_integer, self.bias_integer, bias_scale,
+                                    self.conv.stride, self.conv.padding, self.conv.groups)
+            return (y, self.convbn_scaling_factor)
         y = self._run_int_conv(x, pre_act_scaling_factor, self.weight_integer, self.bias_integer, bias_scale, in_bits,
                                self.conv.stride[0], self.conv.padding[0], self.conv.groups)
         return (y, self.convbn_scaling_factor)
@@ -503,6 +570,14 @@ class QuantAveragePool2d(Module):
             return self.final_pool(x)
         _require_device(x, "QuantAveragePool2d")
         N, Cc, H, W = x.shape
+        if self.kernel_size == 3 and self.stride == 1 and self.padding == 1:
+            # InceptionV3's average-pool branches: count_include_pad, so the divisor is 9 at the borders too
+            x_scaling_factor = x_scaling_factor.view(-1)
+            x = x.contiguous().float()
+            y = torch.empty_like(x)
+            _lib.call("hawq_avgpool3x3_f32", x.data_ptr(), y.data_ptr(), N * Cc, H, W, float(x_scaling_factor[0].item()),
+                      _stream())
+            return (y, x_scaling_factor)
         if not (H == W == self.kernel_size and self.padding == 0):
             raise NotImplementedError("only the global (kernel == feature map) average pool of the ResNets")
         x_scaling_factor = x_scaling_factor.view(-1)

@@ -136,3 +136,99 @@ def synthetic_images(batch: int, seed: int = 0, size: int = 224) -> torch.Tensor
     """Normalised-image-like synthetic input: seeded N(0,1)."""
     g = torch.Generator().manual_seed(1000 + seed)
     return torch.randn(batch, 3, size, size, generator=g)
+
+
+# InceptionV3 (pytorchcv ``inceptionv3``): per unit kind, the branches in registration order.  A branch is ("conv1x1", out),
+# ("seq", [(out, kernel, stride, padding), ...]), ("seq3x3", [...]) - a sequence followed by parallel 1x3 / 3x1 convs -,
+# ("avgpool", out) or ("maxpool",).  Kernels / paddings are int or (h, w).
+INCEPTION_STAGES = [[256, 288, 288], [768, 768, 768, 768, 768], [1280, 2048, 2048]]
+INCEPTION_B_MID = [128, 160, 160, 192]
+
+
+def inception_unit_branches(kind: str, out_channels: int, mid: int = 0):
+    """Branches of one InceptionV3 unit (the structure utils/models/q_inceptionv3.py:327-572 dereferences)."""
+    if kind == "A":
+        return [("conv1x1", 64), ("seq", [(48, 1, 1, 0), (64, 5, 1, 2)]),
+                ("seq", [(64, 1, 1, 0), (96, 3, 1, 1), (96, 3, 1, 1)]), ("avgpool", out_channels - 224)]
+    if kind == "RA":
+        return [("seq", [(384, 3, 2, 0)]), ("seq", [(64, 1, 1, 0), (96, 3, 1, 1), (96, 3, 2, 0)]), ("maxpool",)]
+    if kind == "B":
+        return [("conv1x1", 192),
+                ("seq", [(mid, 1, 1, 0), (mid, (1, 7), 1, (0, 3)), (192, (7, 1), 1, (3, 0))]),
+                ("seq", [(mid, 1, 1, 0), (mid, (7, 1), 1, (3, 0)), (mid, (1, 7), 1, (0, 3)), (mid, (7, 1), 1, (3, 0)),
+                         (192, (1, 7), 1, (0, 3))]),
+                ("avgpool", 192)]
+    if kind == "RB":
+        return [("seq", [(192, 1, 1, 0), (320, 3, 2, 0)]),
+                ("seq", [(192, 1, 1, 0), (192, (1, 7), 1, (0, 3)), (192, (7, 1), 1, (3, 0)), (192, 3, 2, 0)]), ("maxpool",)]
+    if kind == "C":
+        return [("conv1x1", 320), ("seq3x3", [(384, 1, 1, 0)]), ("seq3x3", [(448, 1, 1, 0), (384, 3, 1, 1)]), ("avgpool", 192)]
+    raise KeyError(kind)
+
+
+def inception_units():
+    """(stage, unit, kind, in_channels, out_channels, mid) of every InceptionV3 unit in order."""
+    cin, out = 192, []
+    for si, per_stage in enumerate(INCEPTION_STAGES):
+        for ui, cout in enumerate(per_stage):
+            kind = ("RA", "RB")[si - 1] if (ui == 0 and si > 0) else ("A", "B", "C")[si]
+            mid = INCEPTION_B_MID[ui - 1] if kind == "B" else 0
+            out.append((si + 1, ui + 1, kind, cin, cout, mid))
+            cin = cout
+    return out
+
+
+def _incept_conv(cin, cout, k, stride, pad):
+    blk = nn.Module()
+    blk.conv = nn.Conv2d(cin, cout, k, stride, pad, bias=False)
+    blk.bn = nn.BatchNorm2d(cout, eps=1e-3)
+    blk.activ = nn.ReLU(inplace=True)
+    return blk
+
+
+def build_float_inceptionv3(num_classes: int = 1000) -> nn.Module:
+    """pytorchcv ``inceptionv3`` attribute tree as utils/models/q_inceptionv3.py dereferences it:
+    ``features.init_block.conv1..conv5``, ``features.stageN.unitM.branches.branchK`` with ``conv`` (1x1 and average-pool
+    branches, the latter also ``pool``), ``conv_list.convI`` (sequences) and ``conv1x3`` / ``conv3x1`` (Inception-C), each conv
+    a ``{conv, bn}`` block; ``features.final_pool`` (AvgPool2d(8)), ``output.fc``.  Input 299 x 299."""
+    net = nn.Module()
+    net.arch = "inceptionv3"
+    net.features = nn.Module()
+    ib = nn.Module()
+    for i, (cin, cout, k, s, p) in enumerate(((3, 32, 3, 2, 0), (32, 32, 3, 1, 0), (32, 64, 3, 1, 1))):
+        setattr(ib, f"conv{i + 1}", _incept_conv(cin, cout, k, s, p))
+    ib.pool1 = nn.MaxPool2d(3, 2)
+    ib.conv4 = _incept_conv(64, 80, 1, 1, 0)
+    ib.conv5 = _incept_conv(80, 192, 3, 1, 0)
+    ib.pool2 = nn.MaxPool2d(3, 2)
+    net.features.init_block = ib
+    for si, ui, kind, cin, cout, mid in inception_units():
+        if ui == 1:
+            setattr(net.features, f"stage{si}", nn.Module())
+        unit = nn.Module()
+        unit.branches = nn.Module()
+        for bi, br in enumerate(inception_unit_branches(kind, cout, mid)):
+            b = nn.Module()
+            if br[0] == "conv1x1":
+                b.conv = _incept_conv(cin, br[1], 1, 1, 0)
+            elif br[0] in ("seq", "seq3x3"):
+                b.conv_list = nn.Module()
+                c = cin
+                for i, (co, k, s, p) in enumerate(br[1]):
+                    setattr(b.conv_list, f"conv{i + 1}", _incept_conv(c, co, k, s, p))
+                    c = co
+                if br[0] == "seq3x3":
+                    b.conv1x3 = _incept_conv(c, c, (1, 3), 1, (0, 1))
+                    b.conv3x1 = _incept_conv(c, c, (3, 1), 1, (1, 0))
+            elif br[0] == "avgpool":
+                b.pool = nn.AvgPool2d(3, 1, 1)
+                b.conv = _incept_conv(cin, br[1], 1, 1, 0)
+            else:
+                b.pool = nn.MaxPool2d(3, 2)
+            setattr(unit.branches, f"branch{bi + 1}", b)
+        setattr(getattr(net.features, f"stage{si}"), f"unit{ui}", unit)
+    net.features.final_pool = nn.AvgPool2d(8, 1)
+    net.output = nn.Module()
+    net.output.dropout = nn.Dropout(0.5)
+    net.output.fc = nn.Linear(2048, num_classes)
+    return net

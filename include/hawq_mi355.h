@@ -427,6 +427,59 @@ int hawq_minmax_f32(const float *x, int64_t n, float *out2, void *scratch, void 
  * Exact (radix select on the order-preserving integer image of the floats).  scratch: >= 1040 bytes of device memory. */
 int hawq_kthvalue_f32(const float *x, int64_t n, int64_t k, int32_t negate, float *out, void *scratch, void *stream);
 
+/* ---- InceptionV3 (inception.hip) -----------------------------------------------------------
+ * Rectangular implicit-GEMM conv on int8 MFMA: KH, KW in 1..7 with their own padding, stride 1 or 2, any H / W.
+ * in:   int8 NHWC [N][H][W][Cin], Cin % 16 == 0 (4-bit activations travel in int8 containers)
+ * wgt:  int8 [Cout][KH][KW][Cin], Cout % 16 == 0;  bias: int32 [Cout]
+ * Output pixel p = (n * Ho + oy) * Wo + ox, channel co goes to out[p * ldo + c_off + co] (ldo >= c_off + Cout), so a branch
+ * writes its slice of the unit's concat buffer in place; other channels of the row are never touched.
+ *   HAWQ_INCEP_RAW:      int32 acc + bias
+ *   HAWQ_INCEP_REQUANT:  q = clamp(dyadic(relu ? max(acc + bias, 0) : acc + bias; m[co], ek[co]), q_lo, q_hi)
+ *   HAWQ_INCEP_REQUANT2: then q2 = clamp(dyadic(q; m2, ek2), q2_lo, q2_hi)  (a branch output rescaled to the concat scale)
+ * REQUANT* store int8 (out_bits 8) or int16 (out_bits 16).  (m, ek) as in the conv epilogues (common.h dyadic_rne). */
+#define HAWQ_INCEP_RAW 0
+#define HAWQ_INCEP_REQUANT 1
+#define HAWQ_INCEP_REQUANT2 2
+typedef struct hawq_incep_conv_args {
+    const void *in;
+    const void *wgt;
+    const int32_t *bias;
+    int32_t N, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w;
+    int32_t epilogue, relu;
+    const int32_t *m;
+    const int32_t *ek;
+    int32_t q_lo, q_hi, m2, ek2, q2_lo, q2_hi;
+    void *out;
+    int32_t out_bits, ldo, c_off, reserved;
+} hawq_incep_conv_args;
+int hawq_incep_conv(const hawq_incep_conv_args *a, void *stream);
+/* Average pool 3x3 / stride 1 / pad 1 of QuantAveragePool2d (count_include_pad: divisor 9 everywhere) on the fp32 (integer *
+ * scale) NCHW tensor of the module path: x_int = rint(x / scale), s = sum of the window, p = trunc(s / 9 + 0.01) computed
+ * exactly as (100 s + 9) / 900 in C integer division (truncation toward zero), y = p * scale. */
+int hawq_avgpool3x3_f32(const float *x, float *y, int32_t NC, int32_t H, int32_t W, float scale, void *stream);
+
+/* Integer NHWC pool / requant launches of the fused InceptionV3 plan (hawq_amd/engine_inception.py).  Every input element
+ * first goes through the optional `pre` requant, every output element through the optional `post` requant:
+ *   q = clamp(dyadic(v; m, ek), lo, hi)   (per tensor; (m, ek) as in the conv epilogues, k = 0)
+ * in:  int8 / int16 (in_bits) [N][H][W] rows of in_pitch elements, channels in_off .. in_off + C - 1
+ * out: int8 / int16 (out_bits) rows of ldo elements, channels c_off .. c_off + C - 1; other channels are never touched.
+ *   hawq_incep_requant:         elementwise (Ho, Wo = H, W)
+ *   hawq_incep_maxpool3s2:      max over 3 x 3 windows, stride 2, no padding
+ *   hawq_incep_avgpool_branch:  3 x 3 / stride 1 / pad 1 window sum s (zeros in the padding), p = (100 s + 9) / 900
+ *   hawq_incep_global_avgpool:  H x W window (one output pixel per image), p = (100 s + HW) / (100 HW)
+ * (the average rules are trunc(s / d + 0.01) of QuantAveragePool2d, C division truncating toward zero) */
+typedef struct hawq_incep_pool_args {
+    const void *in;
+    void *out;
+    int32_t N, H, W, C, in_bits, in_pitch, in_off, out_bits, ldo, c_off;
+    int32_t pre, m1, ek1, lo1, hi1;
+    int32_t post, m2, ek2, lo2, hi2;
+} hawq_incep_pool_args;
+int hawq_incep_requant(const hawq_incep_pool_args *a, void *stream);
+int hawq_incep_maxpool3s2(const hawq_incep_pool_args *a, void *stream);
+int hawq_incep_avgpool_branch(const hawq_incep_pool_args *a, void *stream);
+int hawq_incep_global_avgpool(const hawq_incep_pool_args *a, void *stream);
+
 /* ---- hipGraph helpers: capture a sequence of the launches above once, replay per batch */
 int hawq_graph_begin(void *stream);
 int hawq_graph_end(void *stream, void **graph_exec_out);
