@@ -157,11 +157,13 @@ def load_checkpoint(model, ckpt, freeze: bool = True):
 
 # ------------------------------------------------------------------ evaluation loop (quant_train.py:625-674)
 def validate(model, loader, uint8: bool = False, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), device="cuda"):
-    """Top-1 / top-5 accuracy (percent) of a frozen ``Q_ResNet*`` over ``loader`` = iterable of (images, target):
-    the body of the reference's ``validate()`` (freeze, eval, no_grad, ``accuracy(output, target, topk=(1, 5))``,
+    """Top-1 / top-5 accuracy (percent) of a frozen ``Q_ResNet*`` / ``Q_InceptionV3`` over ``loader`` = iterable of (images,
+    target): the body of the reference's ``validate()`` (freeze, eval, no_grad, ``accuracy(output, target, topk=(1, 5))``,
     sample-weighted averages).  ``images`` are normalised fp32 NCHW batches as the reference's pipeline produces, or -
-    ``uint8`` - raw uint8 NHWC batches that go through the look-up-table input quantiser (``forward_uint8``);
-    ``hawq_amd.image.preprocess_batch`` turns decoded images of any size into such batches (Resize(256) + CenterCrop(224)).
+    ``uint8`` - raw uint8 NHWC batches that go through the look-up-table input quantiser (``model.engine().forward_uint8``);
+    ``hawq_amd.image.preprocess_batch`` / ``folder_loader`` turn decoded images of any size into such batches, with the
+    geometry of the network: ``hawq_amd.image.eval_geometry(arch)`` (Resize(342) + CenterCrop(299) for InceptionV3,
+    Resize(256) + CenterCrop(224) otherwise).
     Returns (top1, top5, n_images)."""
     freeze_model(model)
     model.eval()
@@ -172,7 +174,7 @@ def validate(model, loader, uint8: bool = False, mean=(0.485, 0.456, 0.406), std
             images = images.to(device, non_blocking=True)
             target = target.to(device, non_blocking=True)
             if uint8 and not hasattr(model, "engine"):
-                raise NotImplementedError(f"uint8 image input needs the fused ResNet engine; {type(model).__name__} has none")
+                raise NotImplementedError(f"uint8 image input needs a fused engine; {type(model).__name__} has none")
             output = model.engine().forward_uint8(images, mean, std) if uint8 else model(images)
             _, pred = output.topk(5, 1, True, True)
             correct = pred.t().eq(target.view(1, -1).expand(5, -1))

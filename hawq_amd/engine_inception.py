@@ -15,6 +15,8 @@ branches launch one after another on the plan's stream:
 Stem: the input QuantAct (``hawq_fakequant_f32`` + ``hawq_f32_nchw_to_q_nhwc``), five convs, two max pools.  Head:
 ``hawq_incep_global_avgpool`` (8 x 8 trunc rule + ``q_concat_activ``), the classifier as a 1x1 RAW conv and
 ``hawq_acc_nhwc_to_f32_nchw`` (fp32 logits = (acc + bias) * fl(S_w * S_a), quant_modules.py:125-130).
+uint8 images (``forward_uint8``): the same plan and buffers with its first three launches (input QuantAct + conv1) replaced by one
+``hawq_incep_stem_u8``, whose table look-up is ToTensor + Normalize + the input QuantAct (``input_quant_lut``); a graph of its own.
 
 Every requant is the exact dyadic form of fixedpoint_fn (``requant_table(..., lift=False)``); tiles are fixed (no tuning).
 """
@@ -55,6 +57,15 @@ def _scalar_table(s_in, s_out):
     return int(m[0]), int(ek[0])
 
 
+def pack_stem_u8_weights(w_int, cout_p):
+    """int8 [Cout][3][3][3] conv1 weights -> the [cout_p][32] rows of ``hawq_incep_stem_u8``: k = (kh * 3 + kw) * 3 + c for
+    k < 27, zeros for k = 27 .. 31 and for rows Cout .. cout_p - 1."""
+    co = w_int.shape[0]
+    w = np.zeros((cout_p, 32), np.int8)
+    w[:co, :27] = np.asarray(w_int, np.int8).transpose(0, 2, 3, 1).reshape(co, 27)
+    return w
+
+
 class _T:
     """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale."""
 
@@ -68,6 +79,7 @@ class InceptionEngine:
         self.dev = next(model.parameters()).device
         self.stream = None   # created with the first plan: building the engine object needs no device
         self._batch, self._graph, self._ops = None, None, []
+        self._graph_u8, self._ops_u8, self._u8_why = None, None, None
 
     def _zeros(self, *a, **k):
         """a plan buffer: kept alive with the plan (the captured launches hold its address)"""
@@ -138,6 +150,7 @@ class InceptionEngine:
         a.out_bits, a.ldo, a.c_off = out.bits, ldo, c_off
         self._keep += t + [a]
         self._ops.append(partial(_lib.call, "hawq_incep_conv", C.byref(a), self.stream.cuda_stream))
+        self._last_conv = (a, w_int)
         return out
 
     def _requant_input(self, act, src: _T):
@@ -224,13 +237,11 @@ class InceptionEngine:
         self.N, dev, q = N, self.dev, self.model
         self._ops, self._keep, self.unit_out = [], [], {}
         ib = q.features.q_init_block
-        ia = ib.q_input_activ
-        s_in = _scale(ia)
-        lo, hi = _rng(ia)
+        s_in = _scale(ib.q_input_activ)
+        inv, lo, hi = self._input_quant()
         self.x_in = torch.zeros(N, 3, H, W, dtype=torch.float32, device=dev)
         xq_f = torch.zeros_like(self.x_in)
         x0 = _T(self._zeros(N * H * W * 16, dtype=torch.int8, device=dev), H, W, 3, 16, s_in, 8)
-        inv = float((1. / s_in).item())
         self._keep += [xq_f]
         self._ops.append(partial(_lib.call, "hawq_fakequant_f32", self.x_in.data_ptr(), xq_f.data_ptr(), self.x_in.numel(), inv,
                                  1.0, lo, hi, self.stream.cuda_stream))
@@ -245,6 +256,9 @@ class InceptionEngine:
                 x = y
             else:
                 x = self._conv(getattr(ib, name), x)
+                if name == "q_conv1":   # the launches up to here are what hawq_incep_stem_u8 replaces
+                    self._conv1, self._n_stem_ops = self._last_conv, len(self._ops)
+        self._ops_u8, self._u8_why = None, self._stem_u8_refusal(ib)
         if x.bits != 16 or x.pitch != x.c:
             raise PlanNotApplicable("the stem output must be 16-bit")
         for uname, unit in q.units():
@@ -281,9 +295,10 @@ class InceptionEngine:
         self._batch = (N, H, W)
 
     def _drop_graph(self):
-        if self._graph is not None:
-            _lib.call("hawq_graph_destroy", self._graph)
-            self._graph = None
+        for attr in ("_graph", "_graph_u8"):
+            if getattr(self, attr, None) is not None:
+                _lib.call("hawq_graph_destroy", getattr(self, attr))
+                setattr(self, attr, None)
 
     def __del__(self):
         try:
@@ -291,30 +306,37 @@ class InceptionEngine:
         except Exception:
             pass
 
-    def _launch_all(self):
-        for op in self._ops:
+    def _launch_all(self, u8: bool = False):
+        for op in (self._ops_u8 if u8 else self._ops):
             op()
 
-    def run_resident(self):
-        """One forward over ``self.x_in`` on ``self.stream``: graph replay, or (use_graph False) the launches one by one."""
+    def run_resident(self, u8: bool = False):
+        """One forward over ``self.x_in`` (or, ``u8``, over ``self.x_u8``) on ``self.stream``: graph replay, or (use_graph False)
+        the launches one by one."""
         if not self.use_graph:
-            self._launch_all()
+            self._launch_all(u8)
             return
-        if self._graph is None:
-            self._launch_all()   # warm-up outside capture
+        attr = "_graph_u8" if u8 else "_graph"
+        if getattr(self, attr) is None:
+            self._launch_all(u8)   # warm-up outside capture
             torch.cuda.synchronize(self.dev)
             _lib.call("hawq_graph_begin", self.stream.cuda_stream)
             g = C.c_void_p()
             try:
-                self._launch_all()
+                self._launch_all(u8)
             finally:
                 _lib.call("hawq_graph_end", self.stream.cuda_stream, C.byref(g))
-            self._graph = g
-        _lib.call("hawq_graph_launch", self._graph, self.stream.cuda_stream)
+            setattr(self, attr, g)
+        _lib.call("hawq_graph_launch", getattr(self, attr), self.stream.cuda_stream)
 
     @property
     def n_launches(self):
         return len(self._ops)
+
+    @property
+    def n_launches_u8(self):
+        """launches of the uint8 plan (built by the first ``forward_uint8`` of a batch shape)"""
+        return len(self._ops_u8)
 
     def __call__(self, x):
         if not x.is_cuda:
@@ -333,8 +355,78 @@ class InceptionEngine:
         cur.wait_stream(self.stream)
         return out
 
-    def forward_uint8(self, x_u8, mean=None, std=None):
-        raise NotImplementedError("uint8 image input (look-up-table input quantiser) is not built for InceptionV3")
+    # ------------------------------------------------------------------ uint8 image input (quant_train.py:427-440)
+    def _input_quant(self):
+        """(fl(1/S), lo, hi) of the input QuantAct: the arguments of the fp32 plan's ``hawq_fakequant_f32`` and of the uint8 table."""
+        ia = self.model.features.q_init_block.q_input_activ
+        return (float((1. / _scale(ia)).item()), *_rng(ia))
+
+    def input_lut(self, mean, std) -> torch.Tensor:
+        """int8 [3][256]: lut[c][u] = the input QuantAct of Normalize_c(ToTensor(u)), in the reference pipeline's own float32
+        operations on the host (``input_quant_lut``) - a look-up is bit-identical to what the fp32 plan does to that tensor."""
+        from .quant_utils import input_quant_lut
+        inv, lo, hi = self._input_quant()
+        return input_quant_lut(inv, mean, std, lo, hi)
+
+    @staticmethod
+    def _stem_u8_refusal(ib):
+        """why ``hawq_incep_stem_u8`` cannot stand for the input QuantAct + conv1 of init block `ib` (None: it can)"""
+        lo, hi = _rng(ib.q_input_activ)
+        if ib.q_input_activ.activation_bit != 8 or lo < -128 or hi > 127:
+            return "the input QuantAct is not 8-bit with an int8 range"
+        conv = ib.q_conv1.q_convbn.conv
+        if conv.in_channels != 3 or conv.out_channels % 16 or conv.kernel_size != (3, 3) or conv.stride != (2, 2) or \
+                conv.padding != (0, 0) or conv.groups != 1 or conv.dilation != (1, 1):
+            return "conv1 is not a 3 -> 16k channel 3x3 / stride 2 / pad 0 conv"
+        if ib.q_conv1.q_activ.activation_bit > 8:
+            return "conv1's output is wider than 8 bits"
+        return None
+
+    def _ensure_u8(self):
+        """the uint8 plan of the current batch shape: image buffer, table, packed conv1 weights and the launch list"""
+        if self._ops_u8 is not None:
+            return
+        if self._u8_why is not None:
+            raise PlanNotApplicable(f"uint8 input: {self._u8_why}")
+        N, H, W = self._batch
+        a1, w_int = self._conv1
+        wt = self._zeros(a1.Cout, 32, dtype=torch.int8, device=self.dev)
+        wt.copy_(torch.from_numpy(pack_stem_u8_weights(w_int, a1.Cout)))
+        self.x_u8 = self._zeros(N, H, W, 3, dtype=torch.uint8, device=self.dev)
+        self.lut_dev = self._zeros(3, 256, dtype=torch.int8, device=self.dev)
+        self._lut_key = None
+        a = _lib.IncepConvArgs.from_buffer_copy(a1)   # conv1's bias, tables, clamp, output buffer and pitch
+        a.in_, a.wgt, a.Cin = None, wt.data_ptr(), 3
+        self._keep.append(a)
+        if not _lib.load().hawq_incep_stem_u8_ok(self.x_u8.data_ptr(), self.lut_dev.data_ptr(), C.byref(a)):
+            raise PlanNotApplicable("uint8 input: hawq_incep_stem_u8 refuses conv1")
+        stem = partial(_lib.call, "hawq_incep_stem_u8", self.x_u8.data_ptr(), self.lut_dev.data_ptr(), C.byref(a),
+                       self.stream.cuda_stream)
+        self._ops_u8 = [stem] + self._ops[self._n_stem_ops:]
+
+    def forward_uint8(self, x_u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+        """uint8 NHWC images [N,H,W,3] (decoder output, after resize / crop) -> fp32 logits, equal bit for bit to ``self(x)`` with
+        x = Normalize(mean, std)(ToTensor(image)) as the reference's data pipeline builds it; the fp32 tensor never exists."""
+        if not x_u8.is_cuda:
+            raise NotImplementedError("InceptionEngine: uint8 images must be on the MI355X (there is no CPU path)")
+        if x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3:
+            raise ValueError("expected a uint8 NHWC [N,H,W,3] tensor")
+        N, H, W, _ = x_u8.shape
+        if self._batch != (N, H, W):
+            self._build(N, H, W)
+        self._ensure_u8()
+        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
+        cur = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            if self._lut_key != key:
+                self.lut_dev.copy_(self.input_lut(mean, std).to(self.dev), non_blocking=False)
+                self._lut_key = key
+            self.x_u8.copy_(x_u8, non_blocking=True)
+            self.run_resident(u8=True)
+            out = self.logits.clone()
+        cur.wait_stream(self.stream)
+        return out
 
     def unit_output(self, name):
         """int64 NCHW numpy array of a unit's integer output (after its q_rescaling_activ) of the last forward."""

@@ -1,6 +1,7 @@
-"""Image pipeline in front of the uint8 input path (quant_train.py:428-440): ``transforms.Resize(256)`` and
-``transforms.CenterCrop(224)`` on the decoded image, on the MI355X; ``ToTensor`` + ``Normalize`` + the input QuantAct are
-the look-up table of ``IntegerEngine.forward_uint8``.
+"""Image pipeline in front of the uint8 input path (quant_train.py:427-440): ``transforms.Resize(resize)`` and
+``transforms.CenterCrop(crop)`` on the decoded image, on the MI355X, with (resize, crop) = ``eval_geometry(arch)``: (342, 299) for
+InceptionV3, (256, 224) for every other network; ``ToTensor`` + ``Normalize`` + the input QuantAct are the look-up table of
+``forward_uint8`` (``IntegerEngine`` and ``InceptionEngine``).
 
 torchvision's Resize on a PIL image is ``Image.resize(..., BILINEAR)``: Pillow's antialiased separable resampling
 (libImaging/Resample.c).  The coefficient construction below restates its ``precompute_coeffs`` (binary64, support scaled by
@@ -52,6 +53,12 @@ def bilinear_coeffs(in_size: int, out_size: int):
     return bounds, coef.astype(np.int32), ksize
 
 
+def eval_geometry(arch: str):
+    """(resize, crop) of the reference's validation pipeline for `arch` (quant_train.py:427-429, ``test_resolution``):
+    Resize(342) + CenterCrop(299) for InceptionV3, Resize(256) + CenterCrop(224) otherwise."""
+    return (342, 299) if arch == "inceptionv3" else (256, 224)
+
+
 def resize_crop_geometry(h: int, w: int, resize: int = 256, crop: int = 224):
     """torchvision Resize(int) (smaller edge -> resize, other edge int(resize * long / short)) + CenterCrop(crop):
     (resized h, resized w, crop top, crop left)."""
@@ -100,7 +107,8 @@ def resize_center_crop(img: torch.Tensor, resize: int = 256, crop: int = 224) ->
 
 
 def preprocess_batch(images, resize: int = 256, crop: int = 224) -> torch.Tensor:
-    """List of decoded uint8 HWC images (any sizes, host or device) -> uint8 [N, crop, crop, C] for ``forward_uint8``."""
+    """List of decoded uint8 HWC images (any sizes, host or device) -> uint8 [N, crop, crop, C] for ``forward_uint8``.
+    (resize, crop) per network: ``eval_geometry(arch)``."""
     return torch.stack([resize_center_crop(im.cuda() if not im.is_cuda else im, resize, crop) for im in images])
 
 
@@ -140,7 +148,8 @@ def image_folder(root: str):
 
 def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int = 224, device="cuda"):
     """Iterate an ImageFolder tree as ``(uint8 [n, crop, crop, 3] on the MI355X, int64 targets)`` batches - the validation loader of
-    quant_train.py:428-445 (shuffle off) with everything behind the decoder on the device; feed it to ``api.validate(uint8=True)``."""
+    quant_train.py:428-445 (shuffle off) with everything behind the decoder on the device; feed it to ``api.validate(uint8=True)``.
+    The defaults are the ResNets' geometry; InceptionV3 wants ``resize=342, crop=299`` (``eval_geometry(arch)``)."""
     samples, _ = image_folder(root)
     for i in range(0, len(samples), batch_size):
         part = samples[i:i + batch_size]

@@ -453,6 +453,17 @@ typedef struct hawq_incep_conv_args {
     int32_t out_bits, ldo, c_off, reserved;
 } hawq_incep_conv_args;
 int hawq_incep_conv(const hawq_incep_conv_args *a, void *stream);
+/* InceptionV3's input QuantAct + Conv2d_1a_3x3 from uint8 images in one launch (incep_stem.hip): Q_InceptInitBlock's q_input_activ and
+ * q_conv1 (q_inceptionv3.py of the reference) on the tensor that ToTensor + Normalize (quant_train.py:432-440) make of the image, with
+ * the QuantAct as a table look-up (quant_modules.py:271-274; lut int8 [3][256] from hawq_amd.quant_utils.input_quant_lut).
+ * x:    uint8 NHWC [N][H][W][3], H, W >= 3
+ * conv: in = NULL, Cin = 3, KH = KW = 3, stride 2, pad 0, Cout % 16 == 0; wgt int8 [Cout][32] with k = (kh * 3 + kw) * 3 + c for
+ *       k < 27 and zeros for k = 27 .. 31 (16-byte aligned); epilogue HAWQ_INCEP_REQUANT with out_bits 8, exactly hawq_incep_conv's;
+ *       output pixel p = (n * Ho + oy) * Wo + ox, Ho = (H - 3) / 2 + 1, channel co at out[p * ldo + c_off + co] (out 16-byte
+ *       aligned, ldo and c_off multiples of 16); other channels of a row are never touched.
+ * hawq_incep_stem_u8_ok: 1 when the launch takes this description. */
+int hawq_incep_stem_u8(const uint8_t *x, const int8_t *lut, const hawq_incep_conv_args *conv, void *stream);
+int hawq_incep_stem_u8_ok(const uint8_t *x, const int8_t *lut, const hawq_incep_conv_args *conv);
 /* Average pool 3x3 / stride 1 / pad 1 of QuantAveragePool2d (count_include_pad: divisor 9 everywhere) on the fp32 (integer *
  * scale) NCHW tensor of the module path: x_int = rint(x / scale), s = sum of the window, p = trunc(s / 9 + 0.01) computed
  * exactly as (100 s + 9) / 900 in C integer division (truncation toward zero), y = p * scale. */
