@@ -125,6 +125,9 @@ SIGNATURES = {
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
     "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],
+    "hawq_incep_conv_num_tiles": [],
+    "hawq_incep_conv_tile_ok": [C.POINTER(IncepConvArgs), i32],
+    "hawq_incep_conv_tiled": [C.POINTER(IncepConvArgs), i32, vp],
     "hawq_incep_stem_u8": [vp, vp, C.POINTER(IncepConvArgs), vp],
     "hawq_incep_stem_u8_ok": [vp, vp, C.POINTER(IncepConvArgs)],
     "hawq_avgpool3x3_f32": [vp, vp, i32, i32, i32, f32, vp],

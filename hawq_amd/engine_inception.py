@@ -18,17 +18,30 @@ Stem: the input QuantAct (``hawq_fakequant_f32`` + ``hawq_f32_nchw_to_q_nhwc``),
 uint8 images (``forward_uint8``): the same plan and buffers with its first three launches (input QuantAct + conv1) replaced by one
 ``hawq_incep_stem_u8``, whose table look-up is ToTensor + Normalize + the input QuantAct (``input_quant_lut``); a graph of its own.
 
-Every requant is the exact dyadic form of fixedpoint_fn (``requant_table(..., lift=False)``); tiles are fixed (no tuning).
+Every requant is the exact dyadic form of fixedpoint_fn (``requant_table(..., lift=False)``).
+
+Conv tiles.  By default every conv launch (94 convs + the classifier) is ``hawq_incep_conv``.  ``InceptionEngine(model, tune=True)``
+times, once the buffers of a batch shape exist and before the graph is captured, every conv launch on its own buffers with tile 0
+(that kernel) and with every LDS-tiled kernel of ``hawq_incep_conv_tiled`` that ``hawq_incep_conv_tile_ok`` accepts (HIP events,
+``_TUNE_WARMUP`` untimed + ``_TUNE_REPS`` timed launches, the median), keeps the fastest id per launch and issues
+``hawq_incep_conv_tiled`` with it; launch list, order, stream and buffers are those of the default plan, and every tile computes
+the same integers, so the result is bit-identical.  The uint8 plan shares the choice (its stem kernel replaces conv1).
+``export_plan()`` returns the choice as a JSON-serialisable dict (``make_plan``); ``InceptionEngine(model, plan=p)`` replays it
+without timing anything and raises ``engine.StalePlan`` when it does not fit (``check_plan``: another launch list, tile inventory
+or batch shape, or a tile the library now refuses).
 """
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
+import json
 from functools import partial
 
 import numpy as np
 import torch
 
 from . import _lib
+from .engine import StalePlan
 from .quant_modules import QuantAct
 from .quant_utils import requant_table
 
@@ -66,6 +79,48 @@ def pack_stem_u8_weights(w_int, cout_p):
     return w
 
 
+# ---------------------------------------------------------------------- conv tile plans (pure functions: no device, no library)
+_KEY_FIELDS = ("H", "W", "Cin", "Cout", "KH", "KW", "stride", "pad_h", "pad_w", "epilogue", "out_bits", "ldo", "c_off")
+_TUNE_WARMUP, _TUNE_REPS = 2, 5
+
+
+def launch_key(a):
+    """what identifies a conv launch in a plan: geometry, epilogue, out_bits, ldo, c_off of its argument block (not the batch)"""
+    return tuple(int(getattr(a, f)) for f in _KEY_FIELDS)
+
+
+def launch_digest(keys):
+    """sha256 over the conv launch list (``launch_key`` tuples, in launch order)"""
+    return hashlib.sha256(json.dumps([list(map(int, k)) for k in keys], separators=(",", ":")).encode()).hexdigest()
+
+
+def make_plan(batch, keys, num_tiles, tiles, us):
+    """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
+    and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``)"""
+    return {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
+            "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
+            "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
+
+
+def check_plan(plan, batch, keys, num_tiles, ok):
+    """The tile ids of `plan` for the conv launches `keys` at batch shape `batch`, or StalePlan when the plan was recorded for
+    another batch shape, launch list or tile inventory, or names a tile that ``ok(i, tile)`` (launch index, tile id) refuses."""
+    try:
+        p_batch, p_digest, p_tiles, p_num = list(plan["batch"]), plan["launches"], list(plan["tiles"]), plan["num_tiles"]
+    except (KeyError, TypeError) as exc:
+        raise StalePlan(f"not an InceptionV3 conv tile plan: {exc!r}") from exc
+    if p_batch != [int(v) for v in batch]:
+        raise StalePlan(f"plan recorded for batch shape {p_batch}, not {list(batch)}")
+    if p_num != num_tiles:
+        raise StalePlan(f"plan recorded with {p_num} conv tiles; this library has {num_tiles}")
+    if p_digest != launch_digest(keys) or len(p_tiles) != len(keys):
+        raise StalePlan("plan recorded for another conv launch list")
+    for i, t in enumerate(p_tiles):
+        if not isinstance(t, int) or isinstance(t, bool) or not 0 <= t <= num_tiles or not ok(i, t):
+            raise StalePlan(f"conv launch {i} {tuple(keys[i])}: tile {t!r} is refused")
+    return p_tiles
+
+
 class _T:
     """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale."""
 
@@ -74,8 +129,11 @@ class _T:
 
 
 class InceptionEngine:
-    def __init__(self, model, use_graph: bool = True):
+    def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None):
         self.model, self.use_graph = model, use_graph
+        self.tune, self.plan = bool(tune), plan
+        self.n_timing_launches = 0           # conv launches issued to time tiles (0 for a default or a replayed plan)
+        self.conv_tiles, self.conv_us = None, None
         self.dev = next(model.parameters()).device
         self.stream = None   # created with the first plan: building the engine object needs no device
         self._batch, self._graph, self._ops = None, None, []
@@ -149,6 +207,7 @@ class InceptionEngine:
         a.m, a.ek, a.q_lo, a.q_hi = t[2].data_ptr(), t[3].data_ptr(), lo, hi
         a.out_bits, a.ldo, a.c_off = out.bits, ldo, c_off
         self._keep += t + [a]
+        self._convs.append((len(self._ops), a))
         self._ops.append(partial(_lib.call, "hawq_incep_conv", C.byref(a), self.stream.cuda_stream))
         self._last_conv = (a, w_int)
         return out
@@ -232,10 +291,12 @@ class InceptionEngine:
     # ------------------------------------------------------------------ plan
     def _build(self, N, H, W):
         self._drop_graph()
+        self._batch = None   # until the plan below is complete (a StalePlan leaves no half-built plan behind)
         if self.stream is None:
             self.stream = torch.cuda.Stream(device=self.dev)
         self.N, dev, q = N, self.dev, self.model
-        self._ops, self._keep, self.unit_out = [], [], {}
+        self._ops, self._keep, self.unit_out, self._convs = [], [], {}, []
+        self.conv_tiles, self.conv_us = None, None
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
@@ -289,10 +350,83 @@ class InceptionEngine:
         a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride = N, 1, 1, K, op, 1, 1, 1
         a.epilogue, a.ldo, a.c_off = _lib.INCEP_RAW, op, 0
         self._keep += t + [a, acc]
+        self._convs.append((len(self._ops), a))
         self._ops.append(partial(_lib.call, "hawq_incep_conv", C.byref(a), self.stream.cuda_stream))
         self._ops.append(partial(_lib.call, "hawq_acc_nhwc_to_f32_nchw", acc.data_ptr(), self.logits.data_ptr(), N, O, 1, 1, op,
                                  t[2].data_ptr(), self.stream.cuda_stream))
+        if self.plan is not None or self.tune:
+            self._choose_tiles((N, H, W))
         self._batch = (N, H, W)
+
+    # ------------------------------------------------------------------ conv tiles
+    @property
+    def op_names(self):
+        """library entry point of every launch of the fp32 plan, in order"""
+        return [op.args[0] for op in self._ops]
+
+    @property
+    def conv_launches(self):
+        """``launch_key`` of every conv launch (the classifier last), in launch order"""
+        return [launch_key(a) for _, a in self._convs]
+
+    def _tile_ok(self, i, tile):
+        return bool(_lib.load().hawq_incep_conv_tile_ok(C.byref(self._convs[i][1]), tile))
+
+    def _choose_tiles(self, batch):
+        """replay ``self.plan`` or time the tiles, then re-issue every conv launch as ``hawq_incep_conv_tiled`` with its id"""
+        keys, T = self.conv_launches, _lib.load().hawq_incep_conv_num_tiles()
+        if self.plan is not None:
+            tiles = check_plan(self.plan, batch, keys, T, self._tile_ok)
+            us = [dict(d) for d in self.plan.get("us", [])] or [{} for _ in keys]
+        else:
+            us = self._time_tiles(T)
+            tiles = [min(d, key=lambda t: (d[t], t)) for d in us]   # tile 0 always competes; ties go to the lower id
+        for (idx, a), t in zip(self._convs, tiles):
+            self._ops[idx] = partial(_lib.call, "hawq_incep_conv_tiled", C.byref(a), int(t), self.stream.cuda_stream)
+        self.conv_tiles, self.conv_us = [int(t) for t in tiles], us
+
+    def _time_tiles(self, T):
+        """microseconds of every accepted tile id per conv launch: each launch on its real buffers, which hold the forward of a
+        random image (every conv launch is a pure function of its input buffer, so repeating it changes nothing)"""
+        sp, n = self.stream.cuda_stream, _TUNE_REPS
+        evs = []
+        for _ in range(n + 1):
+            e = C.c_void_p()
+            _lib.call("hawq_event_create", C.byref(e))
+            evs.append(e)
+        ms, us = C.c_float(), []
+        torch.cuda.synchronize(self.dev)
+        with torch.cuda.stream(self.stream):
+            self.x_in.normal_()
+            self._launch_all()
+            for i, (_, a) in enumerate(self._convs):
+                times = {}
+                for tile in range(T + 1):
+                    if tile and not self._tile_ok(i, tile):
+                        continue
+                    for _ in range(_TUNE_WARMUP):
+                        _lib.call("hawq_incep_conv_tiled", C.byref(a), tile, sp)
+                    _lib.call("hawq_event_record", evs[0], sp)
+                    for r in range(n):
+                        _lib.call("hawq_incep_conv_tiled", C.byref(a), tile, sp)
+                        _lib.call("hawq_event_record", evs[r + 1], sp)
+                    self.n_timing_launches += _TUNE_WARMUP + n
+                    samples = []
+                    for r in range(n):
+                        _lib.call("hawq_event_elapsed_ms", evs[r], evs[r + 1], C.byref(ms))
+                        samples.append(ms.value * 1000.0)
+                    times[tile] = sorted(samples)[n // 2]
+                us.append(times)
+        for e in evs:
+            _lib.call("hawq_event_destroy", e)
+        torch.cuda.synchronize(self.dev)
+        return us
+
+    def export_plan(self):
+        """The conv tile choice of the current batch shape as a JSON-serialisable dict (``make_plan``), for ``plan=``."""
+        if self.conv_tiles is None:
+            raise RuntimeError("export_plan: no tuned plan (build the engine with tune=True or plan=... and run a forward first)")
+        return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us)
 
     def _drop_graph(self):
         for attr in ("_graph", "_graph_u8"):

@@ -453,6 +453,20 @@ typedef struct hawq_incep_conv_args {
     int32_t out_bits, ldo, c_off, reserved;
 } hawq_incep_conv_args;
 int hawq_incep_conv(const hawq_incep_conv_args *a, void *stream);
+/* LDS-tiled kernels for the same launch (incep_tiled.hip): both operand tiles staged through a two-stage LDS ring (K steps of 64
+ * bytes per row, K = taps x Cin walked in 16-channel units), several 32 x 32 MFMA tiles per wave, 16-byte stores.  Same argument
+ * block, same integers: every tile id computes, byte for byte, what hawq_incep_conv computes.
+ *   hawq_incep_conv_num_tiles: T; tile ids 1 .. T exist (1: 128 px x 128 ch, 2: 256 x 64, 3: 128 x 64, 4: 64 x 32 with the K steps
+ *       split between two wave sets), id 0 is hawq_incep_conv's kernel.
+ *   hawq_incep_conv_tile_ok:   1 if that tile takes this launch.  Host arithmetic on the argument block only: no pointer is
+ *       dereferenced, nothing is launched, no device is needed.  0 for ids outside 0 .. T and for every block hawq_incep_conv
+ *       refuses; ids > 0 also need out, in and wgt 16-byte aligned with ldo and c_off multiples of 16, tile 1 Cout > 64 and tile 4
+ *       KH * KW * Cin >= 512.
+ *   hawq_incep_conv_tiled:     the launch; tile 0 is hawq_incep_conv(a, stream).  A refused tile returns an error (the reason in
+ *       hawq_last_error()), launches nothing and writes no byte of out. */
+int hawq_incep_conv_num_tiles(void);
+int hawq_incep_conv_tile_ok(const hawq_incep_conv_args *a, int tile);
+int hawq_incep_conv_tiled(const hawq_incep_conv_args *a, int tile, void *stream);
 /* InceptionV3's input QuantAct + Conv2d_1a_3x3 from uint8 images in one launch (incep_stem.hip): Q_InceptInitBlock's q_input_activ and
  * q_conv1 (q_inceptionv3.py of the reference) on the tensor that ToTensor + Normalize (quant_train.py:432-440) make of the image, with
  * the QuantAct as a table look-up (quant_modules.py:271-274; lut int8 [3][256] from hawq_amd.quant_utils.input_quant_lut).

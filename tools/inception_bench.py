@@ -8,8 +8,16 @@ same images as uint8 NHWC, in ``--blocks`` alternating blocks of ``--steps`` for
 the ResNet uint8 entry), and checks that the two give the same logits.  ``--stem-launches K`` then issues the fp32 plan's three stem
 launches and ``hawq_incep_stem_u8`` K times each, eagerly, for a kernel trace of just those.
 
+``--tune`` (or ``--plan FILE``) compares the fixed plan (every conv on ``hawq_incep_conv``) with the tuned plan (per-launch conv tiles
+of ``hawq_incep_conv_tiled``, timed by the engine or replayed from FILE) of the same calibrated model: ``--blocks`` alternating blocks of
+``--steps`` forwards per plan in one process, mean and spread of the blocks per plan, and an assertion that the two plans' logits are
+bit-equal.  With ``--tune`` it prints the per-launch table (geometry, microseconds of tile 0, chosen tile, its microseconds) and the
+sums over the conv launches; ``--save-plan FILE`` writes the last batch size's plan (``export_plan()``) as JSON.
+
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --input f32,u8 [--blocks 6] [--stem-launches 0]
+    python tools/inception_bench.py --tune [--batches 128] [--blocks 6] [--save-plan plan.json]
+    python tools/inception_bench.py --plan plan.json --batches 128
 """
 import argparse
 import json
@@ -77,6 +85,50 @@ def compare_inputs(model, args, b, kinds):
                                       "ms_per_stem": round(t / args.stem_launches, 4)}), flush=True)
 
 
+def compare_plans(model, args, b):
+    """the fixed plan against the tuned (or replayed) plan of one model, alternating blocks; returns the tuned engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    plan = json.load(open(args.plan)) if args.plan else None
+    engines = {"fixed": InceptionEngine(model), "tuned": InceptionEngine(model, tune=plan is None, plan=plan)}
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    with torch.no_grad():
+        y = {k: e(x) for k, e in engines.items()}
+        equal = bool(torch.equal(y["fixed"], y["tuned"]))
+        assert equal, "the tuned plan's logits differ from the fixed plan's"
+        tuned = engines["tuned"]
+        if plan is None:
+            keys = ("H", "W", "Cin", "Cout", "KH", "KW", "stride", "pad_h", "pad_w", "epilogue", "out_bits", "ldo", "c_off")
+            print(f"# {wl}: conv launch | " + " ".join(keys) + " | tile 0 us | chosen tile | its us | all tiles us")
+            for i, (key, t, us) in enumerate(zip(tuned.conv_launches, tuned.conv_tiles, tuned.conv_us)):
+                print(f"# {i:2d} | " + " ".join(str(v) for v in key) + f" | {us[0]:.1f} | {t} | {us[t]:.1f} | " +
+                      " ".join(f"{k}:{v:.1f}" for k, v in sorted(us.items())))
+            s0, s1 = sum(us[0] for us in tuned.conv_us), sum(us[t] for t, us in zip(tuned.conv_tiles, tuned.conv_us))
+            print(json.dumps({"workload": wl, "conv_launches": len(tuned.conv_tiles), "conv_us_tile0_sum": round(s0, 1),
+                              "conv_us_chosen_sum": round(s1, 1), "timing_launches": tuned.n_timing_launches,
+                              "launches_per_tile": {str(t): tuned.conv_tiles.count(t) for t in sorted(set(tuned.conv_tiles))}}),
+                  flush=True)
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": k, "ms_per_batch": round(mean, 4),
+                              "images_per_s": round(b * 1000.0 / mean, 1), "block_min_ms": round(min(v), 4),
+                              "block_max_ms": round(max(v), 4), "blocks": len(v), "steps": args.steps, "launches": e.n_launches,
+                              "logits_bit_equal": equal}), flush=True)
+        mf, mt = sum(ms["fixed"]) / args.blocks, sum(ms["tuned"]) / args.blocks
+        print(json.dumps({"workload": wl, "tuned_over_fixed_rate": round(mf / mt, 4),
+                          "fixed_block_spread_ms": round(max(ms["fixed"]) - min(ms["fixed"]), 4),
+                          "gain_ms": round(mf - mt, 4)}), flush=True)
+    return tuned
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheme", default="uniform8")
@@ -87,12 +139,21 @@ def main():
     ap.add_argument("--input", default=None, help="f32,u8 (or one of them): compare the fused plan's two inputs instead of --paths")
     ap.add_argument("--blocks", type=int, default=6, help="--input: alternating blocks of --steps forwards per kind")
     ap.add_argument("--stem-launches", type=int, default=0, help="--input: then issue each stem form K times (for a kernel trace)")
+    ap.add_argument("--tune", action="store_true", help="compare the fixed plan with the plan on tuned conv tiles")
+    ap.add_argument("--plan", default=None, help="like --tune, but replay the conv tile plan of this JSON file instead of timing")
+    ap.add_argument("--save-plan", default=None, help="--tune / --plan: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
     for b in (int(v) for v in args.batches.split(",")):
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
+            continue
+        if args.tune or args.plan:
+            tuned = compare_plans(model, args, b)
+            if args.save_plan:
+                with open(args.save_plan, "w") as f:
+                    json.dump(tuned.export_plan(), f)
             continue
         x = synthetic_images(b, seed=1, size=299).cuda()
         for path in args.paths.split(","):
