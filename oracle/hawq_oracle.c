@@ -10,6 +10,7 @@
  *   hq_dyadic          utils/quantization_utils/quant_utils.py:390-413, 416-456 (fixedpoint_fn)
  *   hq_quantize_f32    utils/quantization_utils/quant_utils.py:73-97, 237-258, 281-308
  *   hq_conv2d_nchw     utils/quantization_utils/quant_modules.py:489-494 (F.conv2d on integers)
+ *   hq_conv2d_rect_nchw  the same lines with conv.padding = (pad_h, pad_w) (InceptionV3's 1x7 / 7x1 / 1x3 / 3x1 windows)
  *   hq_linear          utils/quantization_utils/quant_modules.py:125-130
  *   hq_maxpool_nchw    utils/models/q_resnet.py:93,119 (nn.MaxPool2d(3,2,1))
  *   hq_avgpool_floor   utils/quantization_utils/quant_modules.py:596-600 + quant_utils.py:334-337
@@ -128,6 +129,45 @@ void hq_conv2d_nchw(const int16_t *x, int64_t N, int64_t Ci, int64_t H, int64_t 
         }
 }
 
+/* hq_conv2d_nchw with a padding per axis (conv.padding = (pad_h, pad_w)): InceptionV3's 1x7 / 7x1 / 1x3 / 3x1 convs.
+ * Same layouts and the same exact int64 sums; out [N][Co][Ho][Wo], Ho = (H + 2 pad_h - KH) / stride + 1 and likewise Wo. */
+void hq_conv2d_rect_nchw(const int16_t *x, int64_t N, int64_t Ci, int64_t H, int64_t W, const int8_t *w,
+                         const int64_t *bias, int64_t Co, int64_t KH, int64_t KW, int64_t stride,
+                         int64_t pad_h, int64_t pad_w, int64_t *out) {
+    const int64_t Ho = (H + 2 * pad_h - KH) / stride + 1;
+    const int64_t Wo = (W + 2 * pad_w - KW) / stride + 1;
+#pragma omp parallel for collapse(2) schedule(dynamic, 1)
+    for (int64_t n = 0; n < N; ++n)
+        for (int64_t co = 0; co < Co; ++co) {
+            int64_t *o = out + (n * Co + co) * Ho * Wo;
+            for (int64_t i = 0; i < Ho * Wo; ++i) o[i] = bias ? bias[co] : 0;
+            for (int64_t ci = 0; ci < Ci; ++ci) {
+                const int16_t *xp = x + (n * Ci + ci) * H * W;
+                const int8_t *wp = w + ((co * Ci + ci) * KH) * KW;
+                for (int64_t kh = 0; kh < KH; ++kh)
+                    for (int64_t kw = 0; kw < KW; ++kw) {
+                        const int64_t wv = wp[kh * KW + kw];
+                        if (wv == 0) continue;
+                        /* valid ox range: 0 <= ox*stride - pad_w + kw < W */
+                        int64_t ox0 = 0, ox1 = Wo;
+                        while (ox0 < Wo && ox0 * stride - pad_w + kw < 0) ++ox0;
+                        while (ox1 > ox0 && (ox1 - 1) * stride - pad_w + kw >= W) --ox1;
+                        const int64_t base = -pad_w + kw;
+                        for (int64_t oy = 0; oy < Ho; ++oy) {
+                            const int64_t iy = oy * stride - pad_h + kh;
+                            if (iy < 0 || iy >= H) continue;
+                            const int16_t *xr = xp + iy * W + base;
+                            int64_t *orow = o + oy * Wo;
+                            if (stride == 1)
+                                for (int64_t ox = ox0; ox < ox1; ++ox) orow[ox] += wv * (int64_t)xr[ox];
+                            else
+                                for (int64_t ox = ox0; ox < ox1; ++ox) orow[ox] += wv * (int64_t)xr[ox * stride];
+                        }
+                    }
+            }
+        }
+}
+
 /* x [B][K] (int16 holding 8-bit values), w [O][K] int8, bias [O] int64 -> out [B][O] int64 */
 void hq_linear(const int16_t *x, int64_t B, int64_t K, const int8_t *w, const int64_t *bias,
                int64_t O, int64_t *out) {
@@ -171,4 +211,29 @@ void hq_avgpool_trunc(const int64_t *x, int64_t NC, int64_t HW, int64_t *out) {
         int64_t num = 100 * s + HW, den = 100 * HW;
         out[p] = num / den; /* C division truncates toward zero */
     }
+}
+
+/* QuantAveragePool2d AS THE REFERENCE EVALUATES IT (quant_modules.py:596-600, quant_utils.py:334-337), in binary32:
+ * nn.AvgPool2d(k, stride 1, pad) of the integers held in float - the window sum over the taps inside the map (exact: fewer than
+ * 2^24), divided by k*k whatever the window covers (count_include_pad) - then + 0.01f and trunc.  Planes [NC][H][W] ->
+ * [NC][Ho][Wo].  No integer rule is substituted for the float operations. */
+void hq_avgpool_f32_trunc(const int64_t *x, int64_t NC, int64_t H, int64_t W, int64_t k, int64_t pad, int64_t *out) {
+    const int64_t Ho = H + 2 * pad - k + 1, Wo = W + 2 * pad - k + 1;
+    const float div = (float)(k * k);
+#pragma omp parallel for schedule(static)
+    for (int64_t p = 0; p < NC; ++p)
+        for (int64_t oy = 0; oy < Ho; ++oy)
+            for (int64_t ox = 0; ox < Wo; ++ox) {
+                float s = 0.0f;
+                for (int64_t ky = 0; ky < k; ++ky)
+                    for (int64_t kx = 0; kx < k; ++kx) {
+                        int64_t iy = oy - pad + ky, ix = ox - pad + kx;
+                        if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+                        volatile float t = s + (float)x[(p * H + iy) * W + ix];
+                        s = t;
+                    }
+                volatile float q = s / div;
+                volatile float r = q + 0.01f;
+                out[(p * Ho + oy) * Wo + ox] = (int64_t)truncf(r);
+            }
 }

@@ -57,6 +57,8 @@ def lib():
         l.hq_dyadic_nchw.argtypes = [i64p, L, L, L, i64p, i32p, L, C.c_int, L, L, i64p]
         l.hq_quantize_f32.argtypes = [f32p, L, C.c_float, C.c_float, C.c_float, i64p]
         l.hq_conv2d_nchw.argtypes = [i16p, L, L, L, L, i8p, C.c_void_p, L, L, L, L, L, i64p]
+        l.hq_conv2d_rect_nchw.argtypes = [i16p, L, L, L, L, i8p, C.c_void_p, L, L, L, L, L, L, i64p]
+        l.hq_avgpool_f32_trunc.argtypes = [i64p, L, L, L, L, L, i64p]
         l.hq_linear.argtypes = [i16p, L, L, i8p, C.c_void_p, L, i64p]
         l.hq_maxpool_nchw.argtypes = [i64p, L, L, L, L, L, L, i64p]
         l.hq_avgpool_trunc.argtypes = [i64p, L, L, i64p]
@@ -133,6 +135,18 @@ def conv2d(x, w, bias, stride, pad):
     return out
 
 
+def conv2d_rect(x, w, bias, stride, pad_h, pad_w):
+    """conv2d with a padding per axis (conv.padding = (pad_h, pad_w)): the InceptionV3 windows."""
+    x = np.ascontiguousarray(x, np.int16)
+    w = np.ascontiguousarray(w, np.int8)
+    n, ci, h, wd = x.shape
+    co, _, kh, kw = w.shape
+    out = np.empty((n, co, (h + 2 * pad_h - kh) // stride + 1, (wd + 2 * pad_w - kw) // stride + 1), np.int64)
+    b = None if bias is None else np.ascontiguousarray(bias, np.int64)
+    lib().hq_conv2d_rect_nchw(x, n, ci, h, wd, w, None if b is None else b.ctypes.data, co, kh, kw, stride, pad_h, pad_w, out)
+    return out
+
+
 def linear(x, w, bias):
     x = np.ascontiguousarray(x, np.int16)
     w = np.ascontiguousarray(w, np.int8)
@@ -157,6 +171,15 @@ def avgpool_trunc(x):
     n, c = x.shape[:2]
     out = np.empty((n, c), np.int64)
     lib().hq_avgpool_trunc(x, n * c, int(np.prod(x.shape[2:])), out)
+    return out
+
+
+def avgpool_f32_trunc(x, k, pad):
+    """QuantAveragePool2d(k, 1, pad) in the reference's own binary32 steps: AvgPool (padding counted), + 0.01, trunc."""
+    x = np.ascontiguousarray(x, np.int64)
+    n, c, h, w = x.shape
+    out = np.empty((n, c, h + 2 * pad - k + 1, w + 2 * pad - k + 1), np.int64)
+    lib().hq_avgpool_f32_trunc(x, n * c, h, w, k, pad, out)
     return out
 
 

@@ -150,11 +150,11 @@ def test_avgpool3x3_equals_brute_force(shape):
     assert torch.equal(y.cpu(), want)
 
 
-def _pool_call(name, x, out, N, H, W, C, in_bits, ldo, c_off, out_bits, pre=None, post=None):
+def _pool_call(name, x, out, N, H, W, C, in_bits, ldo, c_off, out_bits, pre=None, post=None, in_pitch=None, in_off=0):
     L = _lib()
     a = L.IncepPoolArgs()
     a.in_, a.out = x.data_ptr(), out.data_ptr()
-    a.N, a.H, a.W, a.C, a.in_bits, a.in_pitch, a.in_off = N, H, W, C, in_bits, C, 0
+    a.N, a.H, a.W, a.C, a.in_bits, a.in_pitch, a.in_off = N, H, W, C, in_bits, (C if in_pitch is None else in_pitch), in_off
     a.out_bits, a.ldo, a.c_off = out_bits, ldo, c_off
     if pre:
         a.pre, (a.m1, a.ek1, a.lo1, a.hi1) = 1, pre
@@ -174,42 +174,130 @@ def _trunc_avg(s, d):
     return np.where(num >= 0, num // (100 * d), -((-num) // (100 * d)))
 
 
-@pytest.mark.parametrize("op", ["requant", "maxpool", "avgpool", "global"])
-def test_pool_kernels_match_brute_force_and_write_only_their_slice(op):
-    """The fused plan's pool / requant launches: int16 NHWC in, optional requant before (per element) and after, stored into a
-    channel slice of a wider row whose other channels keep their sentinel."""
-    N, H, W, C = 2, {"requant": 9, "maxpool": 17, "avgpool": 17, "global": 8}[op], 0, 48
-    W = H
-    gen = np.random.default_rng(len(op))
-    x = gen.integers(-32768, 32768, (N, H, W, C)).astype(np.int16)
-    x[0, 0, 0, 0], x[1, -1, -1, -1] = 32767, -32768
-    pre = (3 << 28, 30, -32768, 32767)                 # ratio 3/4, ties at 2 mod 4
-    post8 = (5 << 27, 33, -128, 127)                   # ratio 5/64 to 8 bits
-    post16 = (1 << 30, 31, -20000, 20000)              # ratio 1/2, every odd value a tie
-    name, out_bits, pre_t, post_t = {
-        "requant": ("hawq_incep_requant", 8, None, post8),
-        "maxpool": ("hawq_incep_maxpool3s2", 16, pre, post16),
-        "avgpool": ("hawq_incep_avgpool_branch", 8, pre, post8),
-        "global": ("hawq_incep_global_avgpool", 8, None, post8)}[op]
-    v = x.astype(np.int64)
+POOL_NAMES = {"requant": "hawq_incep_requant", "maxpool": "hawq_incep_maxpool3s2", "avgpool": "hawq_incep_avgpool_branch",
+              "global": "hawq_incep_global_avgpool"}
+PRE = (3 << 28, 30, -32768, 32767)                 # ratio 3/4, ties at 2 mod 4
+POST8 = (5 << 27, 33, -128, 127)                   # ratio 5/64 to 8 bits
+POST16 = (1 << 30, 31, -20000, 20000)              # ratio 1/2, every odd value a tie
+
+
+def _check_pool(op, N, H, W, C, in_bits, out_bits, pre_t, post_t, ldo, c_off, in_pitch=None, in_off=0, seed=0):
+    """one pool / requant launch against brute-force host maths: NHWC integers of `in_bits` in rows of `in_pitch` channels, of which
+    the kernel reads [in_off, in_off + C); optional requant before (per element) and after; stored into the channel slice
+    [c_off, c_off + C) of rows `ldo` wide, whose other channels must keep their sentinel"""
+    in_pitch = C if in_pitch is None else in_pitch
+    lim = 1 << (in_bits - 1)
+    gen = np.random.default_rng(seed)
+    xf = gen.integers(-lim, lim, (N, H, W, in_pitch)).astype(np.int16 if in_bits == 16 else np.int8)
+    xf[0, 0, 0, in_off], xf[-1, -1, -1, in_off + C - 1] = lim - 1, -lim
+    v = xf[..., in_off:in_off + C].astype(np.int64)
     if pre_t:
         v = _rq(v, pre_t)
     if op == "requant":
         r = v
     elif op == "maxpool":
-        Ho = (H - 3) // 2 + 1
-        r = np.max(np.stack([v[:, dy:dy + 2 * Ho - 1:2, dx:dx + 2 * Ho - 1:2] for dy in range(3) for dx in range(3)]), 0)
+        Ho, Wo = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+        r = np.max(np.stack([v[:, dy:dy + 2 * Ho - 1:2, dx:dx + 2 * Wo - 1:2] for dy in range(3) for dx in range(3)]), 0)
     elif op == "avgpool":
         p = np.pad(v, ((0, 0), (1, 1), (1, 1), (0, 0)))
         r = _trunc_avg(sum(p[:, dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)), 9)
     else:
         r = _trunc_avg(v.sum((1, 2), keepdims=True), H * W)
-    want = _rq(r, post_t)
-    ldo, c_off = C + 48, 32
+    want = _rq(r, post_t) if post_t else r
     dt = torch.int8 if out_bits == 8 else torch.int16
     out = torch.full((N * want.shape[1] * want.shape[2] * ldo,), -3, dtype=dt, device="cuda")
-    xd = torch.from_numpy(x).cuda()
-    _pool_call(name, xd, out, N, H, W, C, 16, ldo, c_off, out_bits, pre=pre_t, post=post_t)
+    xd = torch.from_numpy(xf).cuda()
+    _pool_call(POOL_NAMES[op], xd, out, N, H, W, C, in_bits, ldo, c_off, out_bits, pre=pre_t, post=post_t, in_pitch=in_pitch,
+               in_off=in_off)
     got = out.cpu().numpy().reshape(N, want.shape[1], want.shape[2], ldo)
     assert np.array_equal(got[..., c_off:c_off + C], want)
     assert (got[..., :c_off] == -3).all() and (got[..., c_off + C:] == -3).all()
+    assert np.abs(want).max() > 3   # the slice does not pass for sentinels
+    return want
+
+
+@pytest.mark.parametrize("op", ["requant", "maxpool", "avgpool", "global"])
+def test_pool_kernels_match_brute_force_and_write_only_their_slice(op):
+    """The fused plan's pool / requant launches: int16 NHWC in, optional requant before (per element) and after, stored into a
+    channel slice of a wider row whose other channels keep their sentinel."""
+    N, H, C = 2, {"requant": 9, "maxpool": 17, "avgpool": 17, "global": 8}[op], 48
+    out_bits, pre_t, post_t = {"requant": (8, None, POST8), "maxpool": (16, PRE, POST16), "avgpool": (8, PRE, POST8),
+                               "global": (8, None, POST8)}[op]
+    _check_pool(op, N, H, H, C, 16, out_bits, pre_t, post_t, ldo=C + 48, c_off=32, seed=len(op))
+
+
+def _engine_pool_descriptions():
+    """(op, in_bits, out_bits, pre, post, C, in_pitch, ldo, c_off) of every pool / requant launch a built InceptionEngine issues,
+    for both shipped schedules"""
+    from hawq_amd import _lib as L
+    from hawq_amd.api import build_quantized_resnet
+    from hawq_amd.engine_inception import InceptionEngine
+    from hawq_amd.quant_modules import QuantAct, freeze_model
+    by_name = {v: k for k, v in POOL_NAMES.items()}
+    out = []
+    for scheme in ("uniform8", "uniform4"):
+        model = build_quantized_resnet("inceptionv3", scheme, seed=0).cuda()
+        for m in model.modules():
+            if isinstance(m, QuantAct):
+                m.x_min.fill_(-1.0 if m.quant_mode == "symmetric" else 0.0), m.x_max.fill_(1.0)
+                m.compute_scale()
+        freeze_model(model)
+        eng = InceptionEngine(model)
+        eng._build(1, 299, 299)   # the plan only: nothing is launched
+        args = [a for a in eng._keep if isinstance(a, L.IncepPoolArgs)]
+        names = [n for n in eng.op_names if n in by_name]
+        assert len(args) == len(names) == eng.n_launches - 95 - 3   # all but the convs, the two input launches and the logits'
+        out += [(by_name[n], a.in_bits, a.out_bits, bool(a.pre), bool(a.post), a.C, a.in_pitch, a.ldo, a.c_off)
+                for n, a in zip(names, args)]
+    return out
+
+
+def test_pool_kernels_at_every_description_the_engine_launches():
+    """Every distinct (op, widths, requants present, channel count, row pitches, slice offset) among the pool / requant launches of
+    a built InceptionEngine - `_pool` is used five ways - at a small H != W map against the brute-force host maths."""
+    descs = _engine_pool_descriptions()
+    distinct = sorted(set(descs))
+    kinds = {d[:5] for d in distinct}
+    assert kinds == {("requant", 16, 8, False, True),    # a conv branch's q_input_act
+                     ("maxpool", 8, 8, False, False),    # the stem's first max pool
+                     ("maxpool", 16, 16, False, False),  # the stem's second
+                     ("maxpool", 16, 16, True, True),    # a reduction unit's max-pool branch, into its slice
+                     ("avgpool", 16, 8, True, True),     # an average-pool branch
+                     ("requant", 16, 16, False, True),   # Inception-C's inner concat into the unit's slice
+                     ("global", 16, 8, False, True)}, kinds
+    assert {288, 768, 1280, 2048} <= {d[5] for d in distinct}
+    assert any(d[0] == "maxpool" and d[8] > 0 for d in distinct) and any(d[:3] == ("requant", 16, 16) and d[8] > 0 for d in distinct)
+    for i, (op, in_bits, out_bits, pre, post, C, in_pitch, ldo, c_off) in enumerate(distinct):
+        assert in_pitch == C   # the engine never reads a slice: in_off > 0 is covered by the edge cases below
+        H, W = {"requant": (5, 4), "maxpool": (7, 5), "avgpool": (5, 4), "global": (8, 8)}[op]
+        post_t = (POST8 if out_bits == 8 else POST16) if post else None
+        _check_pool(op, 2, H, W, C, in_bits, out_bits, PRE if pre else None, post_t, ldo=ldo, c_off=c_off, seed=100 + i)
+    print(f"{len(descs)} pool launches, {len(distinct)} distinct descriptions")
+
+
+@pytest.mark.parametrize("case", ["in_slice_requant", "in_slice_maxpool", "in_slice_avgpool", "in_slice_global", "in8_avgpool",
+                                  "in8_requant_to_16", "in8_global", "maxpool_3x3_map", "maxpool_3x4_map", "grid_stride_twice"])
+def test_pool_kernel_edges(case):
+    """What the kernel supports and no plan exercises: an input channel slice (in_off > 0, in_pitch > C), 8-bit input with requants,
+    H != W, a map of exactly the max pool's window, and more elements than the 8192 x 256 grid covers in one pass."""
+    if case.startswith("in_slice_"):
+        op = case[len("in_slice_"):]
+        out_bits, pre_t, post_t = {"requant": (8, None, POST8), "maxpool": (16, PRE, POST16), "avgpool": (8, PRE, POST8),
+                                   "global": (8, None, POST8)}[op]
+        _check_pool(op, 2, 9, 7, 48, 16, out_bits, pre_t, post_t, ldo=96, c_off=32, in_pitch=112, in_off=48, seed=1)
+    elif case == "in8_avgpool":
+        _check_pool("avgpool", 2, 6, 9, 80, 8, 8, (3 << 28, 30, -128, 127), (1 << 30, 31, -128, 127), ldo=80, c_off=0, seed=2)
+    elif case == "in8_requant_to_16":
+        _check_pool("requant", 3, 5, 3, 32, 8, 16, None, (5 << 28, 28, -32768, 32767), ldo=64, c_off=16, in_pitch=48, in_off=16, seed=3)
+    elif case == "in8_global":
+        _check_pool("global", 2, 8, 5, 64, 8, 8, None, (1 << 30, 29, -128, 127), ldo=64, c_off=0, seed=4)
+    elif case == "maxpool_3x3_map":
+        want = _check_pool("maxpool", 2, 3, 3, 96, 16, 16, PRE, POST16, ldo=128, c_off=16, seed=5)
+        assert want.shape == (2, 1, 1, 96)
+    elif case == "maxpool_3x4_map":
+        want = _check_pool("maxpool", 2, 3, 4, 64, 8, 8, None, None, ldo=64, c_off=0, seed=6)
+        assert want.shape == (2, 1, 1, 64)
+    else:
+        N, H, W, C = 2, 24, 23, 2048
+        assert N * H * W * C > 8192 * 256
+        _check_pool("requant", N, H, W, C, 16, 8, None, POST8, ldo=C + 16, c_off=16, seed=7)
