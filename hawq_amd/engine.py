@@ -12,7 +12,8 @@ quant_modules.py:441-484, quant_utils.py:188-213), producing
                           (+residual add, ReLU, next unit's QuantAct, 16-bit residual out)
       avgpool(+QuantAct8) -> FC(+per-class dequant) -> fp32 logits
 
-  * optionally a hipGraph of the whole list, replayed per batch.
+  * optionally a hipGraph of the whole list, replayed per batch (capture, replay, sub-batch chains, entry points and the
+    tuners' event timing are hawq_amd/runner.py, shared with the MobileNetV2 and InceptionV3 engines).
 
 Integer semantics follow SURVEY.md App. A; the graph is q_resnet.py:53-74 / 114-135 / 231-316.
 """
@@ -28,25 +29,16 @@ import torch
 
 from . import _lib, packing
 from .quant_utils import requant_table, tables_are_fast, tables_fit_fast
+from .runner import EventTimer, GraphRunner, _act_range, _i32, two_round_min
 
 
 RES_VBITS = 20  # residual / pooled values are 16-bit-ish (uint16 storage saturates at 65535)
 U16_VBITS = 17  # tie-freeness proofs for values that live in uint16 residual tensors (< 2^16 unless flagged)
 
 
-def _i32(arr, dev):
-    return torch.from_numpy(np.ascontiguousarray(arr, np.int32)).to(dev)
-
-
 def _no_preshift(ek) -> bool:
     """True if no entry of a device table (e | k << 8) carries a pre-shift k."""
     return bool((np.asarray(ek, dtype=np.int64) >> 8 == 0).all())
-
-
-def _act_range(bits, mode):
-    if mode == 'symmetric':
-        return -(2 ** (bits - 1)), 2 ** (bits - 1) - 1
-    return 0, 2 ** bits - 1
 
 
 class _OpList(list):
@@ -190,7 +182,7 @@ class _Conv:
             self._w_k128 = None
 
 
-class IntegerEngine:
+class IntegerEngine(GraphRunner):
     """Callable: fp32 NCHW images on the GPU -> fp32 logits, bit-identical to the reference's
     frozen forward.  ``residual_bits`` 16 stores post-ReLU residuals as uint16 with a sticky
     overflow flag (``overflowed()``); 32 stores int32.  ``from_buffers`` trusts the modules'
@@ -744,39 +736,14 @@ class IntegerEngine:
                 e.er_split_tiles.clear(), e.er_split_tiles.update(pl["er_split"])
         self._drop_graph()
 
-    def _drop_graph(self):
-        for attr in ("_graph", "_graph_u8"):
-            if getattr(self, attr, None) is not None:
-                _lib.call("hawq_graph_destroy", getattr(self, attr))
-                setattr(self, attr, None)
+    def _on_graph_dropped(self):
         self.x_u8 = None
         self._lut_key = None  # the look-up table lives in buffers that a rebuild replaces
 
     def _time_graph(self, reps: int = 8) -> float:
-        """ms per replay of the captured graph (tuning only) on synthetic images ~ N(0, 1): an all-zero batch switches fewer
-        bits in every pipe than real data does and replays ~1.5 % faster, which is not the regime the plans are chosen for."""
-        if os.environ.get("HAWQ_TUNE_INPUT", "normal") == "zero":
-            self.x_in.zero_()
-        else:
-            g = torch.Generator(device=self.dev)
-            g.manual_seed(0)
-            self.x_in.normal_(generator=g)
-        e0, e1, ms = C.c_void_p(), C.c_void_p(), C.c_float()
-        _lib.call("hawq_event_create", C.byref(e0))
-        _lib.call("hawq_event_create", C.byref(e1))
-        with torch.cuda.stream(self.stream):
-            for _ in range(2):
-                self.run_resident()
-            _lib.call("hawq_event_record", e0, self.stream.cuda_stream)
-            for _ in range(reps):
-                self.run_resident()
-            _lib.call("hawq_event_record", e1, self.stream.cuda_stream)
-        torch.cuda.synchronize(self.dev)
-        _lib.call("hawq_event_elapsed_ms", e0, e1, C.byref(ms))
-        _lib.call("hawq_event_destroy", e0)
-        _lib.call("hawq_event_destroy", e1)
+        ms = super()._time_graph(reps)
         self.flags.zero_()
-        return ms.value / reps
+        return ms
 
     def _build_chains(self, N, H, W, x_view=None, logits_view=None):
         P, dev = self.P, self.dev
@@ -1082,78 +1049,42 @@ class IntegerEngine:
             sk = self._fixed("splitk")   # absent (every plan recorded before split-K existed): no launch is split
             self._set_splitk([int(v) for v in sk.split(".")] if sk else [0] * (len(self._conv_ops) + 2 * len(self._er_args)))
             return
-        # the events are created only on the timing path (the replay branch above returns or raises StalePlan without them)
-        e0, e1 = C.c_void_p(), C.c_void_p()
-        _lib.call("hawq_event_create", C.byref(e0))
-        _lib.call("hawq_event_create", C.byref(e1))
-        ms = C.c_float()
-        def time_split(a, times):   # split-K candidates of one launch (keys -S: S K slices), two rounds, per-count minimum
-            for rnd in range(2):
-                for sk in self._splitk_options(a):
-                    try:
-                        self._ws.fit(a, sk)
-                        self._ws.launch(a, sk, sp)  # warm
-                        _lib.call("hawq_event_record", e0, sp)
-                        for _ in range(reps):
-                            self._ws.launch(a, sk, sp)
-                        _lib.call("hawq_event_record", e1, sp)
-                        _lib.call("hawq_event_elapsed_ms", e0, e1, C.byref(ms))
-                    except RuntimeError:
-                        continue
-                    times[-sk] = min(times.get(-sk, ms.value), ms.value)
+        tiles = [t for t in range(1, n_tiles + 1) if t not in retired]
 
-        with torch.cuda.stream(self.stream):
+        def time_tiles(timer, a):
+            """ms per `reps` launches of hawq_conv2d launch `a` for every tile that takes it (keys: tile ids) and, with the fastest of
+            them set in `a`, for its split-K candidates (keys -S: S K slices): (times, fastest tile).  Split-K keeps that tile for
+            the unsplit form of the plan."""
+            def tile(t):
+                a.tile = t
+                return partial(_lib.call, "hawq_conv2d", C.byref(a), sp)
+
+            def split(k):
+                self._ws.fit(a, -k)
+                return partial(self._ws.launch, a, -k, sp)
+            times = two_round_min(timer, tiles, tile, reps)
+            a.tile = best_t = min(times, key=times.get)
+            two_round_min(timer, [-s for s in self._splitk_options(a)], split, reps, times)
+            return times, best_t
+
+        # the events are created only on the timing path (the replay branch above returns or raises StalePlan without them)
+        with torch.cuda.stream(self.stream), EventTimer(sp) as timer:
             self._launch_all()  # every buffer holds valid data
-            for name, a, op in [(n, k, o) for n, k, o in zip(self._conv_names, self._conv_args, self._conv_ops)]:
+            for name, a, op in zip(self._conv_names, self._conv_args, self._conv_ops):
                 if os.environ.get("HAWQ_TILE_RES") or os.environ.get("HAWQ_TILE_REQ"):
                     break
-                times = {}
-                for rnd in range(2):  # two rounds, per-tile minimum: one hiccup must not decide a layer's tile
-                    for tile in range(1, n_tiles + 1):
-                        if (rnd and tile not in times) or tile in retired:
-                            continue
-                        a.tile = tile
-                        try:
-                            _lib.call("hawq_conv2d", C.byref(a), sp)  # warm
-                            _lib.call("hawq_event_record", e0, sp)
-                            for _ in range(reps):
-                                _lib.call("hawq_conv2d", C.byref(a), sp)
-                            _lib.call("hawq_event_record", e1, sp)
-                            _lib.call("hawq_event_elapsed_ms", e0, e1, C.byref(ms))
-                        except RuntimeError:
-                            continue
-                        times[tile] = min(times.get(tile, ms.value), ms.value)
-                best_t = min((t for t in times if t > 0), key=times.get)
-                a.tile = best_t
-                time_split(a, times)
+                times, best_t = time_tiles(timer, a)
                 best_any = min(times, key=times.get)
-                op.splitk = -best_any if best_any < 0 else 0   # split-K keeps the best tile for the unsplit form of the plan
+                op.splitk = -best_any if best_any < 0 else 0
                 self._tile_times[name] = dict(times)
                 log = [f"{t if t > 0 else f's{-t}'}:{v / reps * 1e3:.1f}" for t, v in times.items()]
                 if os.environ.get("HAWQ_AUTOTUNE_LOG"):
                     print(f"[autotune N={a.N}] {name}: best {best_t}{f' split {op.splitk}' if op.splitk else ''}  us per tile "
                           f"(sS: split-K, S slices): {' '.join(log)}", file=sys.stderr)
                 self.tile_choice[name] = best_t
+
             def best_tile(a):   # fastest applicable tile of one hawq_conv2d launch, and its split-K form: (tile, slices, ms per `reps` launches)
-                times = {}
-                for rnd in range(2):
-                    for tile in range(1, n_tiles + 1):
-                        if (rnd and tile not in times) or tile in retired:
-                            continue
-                        a.tile = tile
-                        try:
-                            _lib.call("hawq_conv2d", C.byref(a), sp)
-                            _lib.call("hawq_event_record", e0, sp)
-                            for _ in range(reps):
-                                _lib.call("hawq_conv2d", C.byref(a), sp)
-                            _lib.call("hawq_event_record", e1, sp)
-                            _lib.call("hawq_event_elapsed_ms", e0, e1, C.byref(ms))
-                        except RuntimeError:
-                            continue
-                        times[tile] = min(times.get(tile, ms.value), ms.value)
-                t = min(times, key=times.get)
-                a.tile = t
-                time_split(a, times)
+                times, t = time_tiles(timer, a)
                 best = min(times, key=times.get)
                 return t, (-best if best < 0 else 0), times[best]
 
@@ -1172,16 +1103,11 @@ class IntegerEngine:
                     continue
                 nvar = _lib.load().hawq_conv_expand_reduce_variants(C.byref(er))
                 times = {}
-                for rnd in range(2):
+                for rnd in range(2):   # (no variant may be refused here: an error propagates)
                     for tile in range(1, nvar + 1):
                         er.tile = tile
-                        _lib.call("hawq_conv_expand_reduce", C.byref(er), sp)
-                        _lib.call("hawq_event_record", e0, sp)
-                        for _ in range(reps):
-                            _lib.call("hawq_conv_expand_reduce", C.byref(er), sp)
-                        _lib.call("hawq_event_record", e1, sp)
-                        _lib.call("hawq_event_elapsed_ms", e0, e1, C.byref(ms))
-                        times[tile] = min(times.get(tile, ms.value), ms.value)
+                        ms = timer.elapsed_ms(partial(_lib.call, "hawq_conv_expand_reduce", C.byref(er), sp), reps)
+                        times[tile] = min(times.get(tile, ms), ms)
                 er.tile = min(times, key=times.get)
                 self._er_times[name] = dict(times)
                 te, pair.split_e, ms_e = best_tile(pair.expand)
@@ -1199,8 +1125,6 @@ class IntegerEngine:
                 self.er_choice[name] = er.tile if pair.fused else 0
                 self.er_split_tiles = getattr(self, "er_split_tiles", {})
                 self.er_split_tiles[name] = (te, tr)
-        _lib.call("hawq_event_destroy", e0)
-        _lib.call("hawq_event_destroy", e1)
         torch.cuda.synchronize(self.dev)
         self.flags.zero_()  # tuning launches ran on whatever the buffers held; only real forwards may raise the flag
 
@@ -1293,46 +1217,17 @@ class IntegerEngine:
             sub.flags.zero_()
 
     # ------------------------------------------------------------------ execution
-    def _launch_all(self, u8: bool = False):
-        if self.subs:  # fork: every chain on its own stream, joined back into self.stream
-            fork = torch.cuda.Event()
-            fork.record(self.stream)
-            for sub in self.subs:
-                sub.stream.wait_event(fork)
-                sub._launch_all(u8)
-                join = torch.cuda.Event()
-                join.record(sub.stream)
-                self.stream.wait_event(join)
-            return
+    def _launch_chain(self, u8):
         for i, op in enumerate(self._ops):
             if u8 and i == 0:
                 self._stem_u8_op()
             else:
                 op()
 
-    def __call__(self, x):
-        """fp32 NCHW images on the GPU -> a FRESH fp32 logits tensor.  With the uint16 residual plan the sticky
-        overflow flag is read back after the forward (one stream synchronisation) and an overflowing batch is
-        transparently recomputed with int32 residuals: the reference never clamps there (quant_utils.py:456)."""
-        if not x.is_cuda:
-            raise RuntimeError("IntegerEngine: input must be on the MI355X (no CPU path)")
-        N, Cc, H, W = x.shape
-        if Cc != 3:
-            raise ValueError("expected [N,3,H,W] images")
-        if self._batch != (N, H, W):
-            self._build(N, H, W)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.x_in.copy_(x, non_blocking=True)
-            self.run_resident()
-            out = self._checked_logits(lambda wide: wide(x))
-        cur.wait_stream(self.stream)
-        return out
-
-    def _checked_logits(self, redo):
-        """Clone of ``self.logits`` for the forward just queued on ``self.stream`` - or, if that forward saturated a
-        uint16 residual, the logits of ``redo(int32-residual engine)``.  Called inside ``torch.cuda.stream(self.stream)``."""
+    def _collect_logits(self, redo):
+        """Clone of ``self.logits`` for the forward just queued on ``self.stream``.  With the uint16 residual plan the sticky
+        overflow flag is read back first (one stream synchronisation), and if that forward saturated a uint16 residual the
+        result is ``redo(int32-residual engine)`` instead: the reference never clamps there (quant_utils.py:456)."""
         out = self.logits.clone()
         if self.res_bits != 16:
             return out
@@ -1351,24 +1246,6 @@ class IntegerEngine:
             self._wide = IntegerEngine(self.model, residual_bits=32, from_buffers=self.from_buffers, use_graph=False,
                                        fast=self.fast, autotune=False, chains=1)
         return self._wide
-
-    def run_resident(self, u8: bool = False):
-        """One forward over ``self.x_in`` (or, ``u8``, over ``self.x_u8``) already resident, on ``self.stream``."""
-        if self.use_graph:
-            attr = "_graph_u8" if u8 else "_graph"
-            if getattr(self, attr, None) is None:
-                self._launch_all(u8)  # warm-up outside capture (module loading, first-touch)
-                torch.cuda.synchronize(self.dev)
-                _lib.call("hawq_graph_begin", self.stream.cuda_stream)
-                try:
-                    self._launch_all(u8)
-                finally:
-                    g = C.c_void_p()
-                    _lib.call("hawq_graph_end", self.stream.cuda_stream, C.byref(g))
-                setattr(self, attr, g)
-            _lib.call("hawq_graph_launch", getattr(self, attr), self.stream.cuda_stream)
-        else:
-            self._launch_all(u8)
 
     # ------------------------------------------------------------------ uint8 image input (quant_train.py:432-440)
     def input_lut(self, mean, std) -> torch.Tensor:
@@ -1409,46 +1286,22 @@ class IntegerEngine:
         (4x the bytes) never exists."""
         if not x_u8.is_cuda or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3:
             raise ValueError("expected a uint8 NHWC [N,H,W,3] tensor on the MI355X")
-        N, H, W, _ = x_u8.shape
-        if self._batch != (N, H, W):
-            self._build(N, H, W)
-        self._ensure_u8(N, H, W)
-        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            if getattr(self, "_lut_key", None) != key:
-                self.lut_dev.copy_(self.input_lut(mean, std).to(self.dev), non_blocking=False)
-                self._lut_key = key
-            self.x_u8.copy_(x_u8, non_blocking=True)
-            self.run_resident(u8=True)
-            out = self._checked_logits(lambda wide: wide.forward_uint8(x_u8, mean, std))
-        cur.wait_stream(self.stream)
-        return out
+        return self._forward_uint8(x_u8, mean, std)
 
     def profile_ops(self, repeats: int = 5):
         """Per-launch durations (ms, median of ``repeats``) measured with HIP events around each
         eager launch on the engine stream.  Returns [(name, ms)] in launch order."""
         if self.subs:
             return self.subs[0].profile_ops(repeats)
-        sp = self.stream.cuda_stream
-        evs = []
-        for _ in range(len(self._ops) + 1):
-            e = C.c_void_p()
-            _lib.call("hawq_event_create", C.byref(e))
-            evs.append(e)
         samples = [[] for _ in self._ops]
-        for _ in range(repeats):
-            _lib.call("hawq_event_record", evs[0], sp)
-            for i, op in enumerate(self._ops):
-                op()
-                _lib.call("hawq_event_record", evs[i + 1], sp)
-            for i in range(len(self._ops)):
-                ms = C.c_float()
-                _lib.call("hawq_event_elapsed_ms", evs[i], evs[i + 1], C.byref(ms))
-                samples[i].append(ms.value)
-        for e in evs:
-            _lib.call("hawq_event_destroy", e)
+        with EventTimer(self.stream.cuda_stream, len(self._ops) + 1) as ev:
+            for _ in range(repeats):
+                ev.record(0)
+                for i, op in enumerate(self._ops):
+                    op()
+                    ev.record(i + 1)
+                for i in range(len(self._ops)):
+                    samples[i].append(ev.ms(i, i + 1))
         return [(n, sorted(v)[len(v) // 2]) for n, v in zip(self._ops.names, samples)]
 
     def overflowed(self) -> bool:
@@ -1474,9 +1327,3 @@ class IntegerEngine:
         acc, shp = self.acc_taps[name]
         a = acc.cpu().numpy().reshape(shp)
         return a.transpose(0, 3, 1, 2) if len(shp) == 4 else a
-
-    def __del__(self):
-        try:
-            self._drop_graph()
-        except Exception:
-            pass

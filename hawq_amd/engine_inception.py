@@ -1,5 +1,5 @@
 """Fused integer plan of a frozen Q_InceptionV3 (hawq_amd/q_inceptionv3.py): one plan per batch shape, captured once into a
-hipGraph and replayed.
+hipGraph and replayed (hawq_amd/runner.py).
 
 Buffers are NHWC integers: int16 for the unit tensors (the 16-bit ``q_rescaling_activ`` outputs) and int8 for everything a
 conv reads (every conv input of the schedules is at most 8 bits; 4-bit values travel in int8 containers).  Per unit, the
@@ -44,6 +44,7 @@ from . import _lib
 from .engine import StalePlan
 from .quant_modules import QuantAct
 from .quant_utils import requant_table
+from .runner import EventTimer, GraphRunner, _rng
 
 
 class PlanNotApplicable(RuntimeError):
@@ -52,11 +53,6 @@ class PlanNotApplicable(RuntimeError):
 
 def _pad16(c):
     return (c + 15) // 16 * 16
-
-
-def _rng(act: QuantAct):
-    b = act.activation_bit
-    return (-(1 << (b - 1)), (1 << (b - 1)) - 1) if act.quant_mode == "symmetric" else (0, (1 << b) - 1)
 
 
 def _scale(act: QuantAct):
@@ -128,7 +124,7 @@ class _T:
         self.buf, self.h, self.w, self.c, self.pitch, self.scale, self.bits = buf, h, w, c, pitch, scale, bits
 
 
-class InceptionEngine:
+class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None):
         self.model, self.use_graph = model, use_graph
         self.tune, self.plan = bool(tune), plan
@@ -136,8 +132,7 @@ class InceptionEngine:
         self.conv_tiles, self.conv_us = None, None
         self.dev = next(model.parameters()).device
         self.stream = None   # created with the first plan: building the engine object needs no device
-        self._batch, self._graph, self._ops = None, None, []
-        self._graph_u8, self._ops_u8, self._u8_why = None, None, None
+        self._batch, self._ops, self._ops_u8, self._u8_why = None, [], None, None
 
     def _zeros(self, *a, **k):
         """a plan buffer: kept alive with the plan (the captured launches hold its address)"""
@@ -388,37 +383,26 @@ class InceptionEngine:
     def _time_tiles(self, T):
         """microseconds of every accepted tile id per conv launch: each launch on its real buffers, which hold the forward of a
         random image (every conv launch is a pure function of its input buffer, so repeating it changes nothing)"""
-        sp, n = self.stream.cuda_stream, _TUNE_REPS
-        evs = []
-        for _ in range(n + 1):
-            e = C.c_void_p()
-            _lib.call("hawq_event_create", C.byref(e))
-            evs.append(e)
-        ms, us = C.c_float(), []
-        torch.cuda.synchronize(self.dev)
-        with torch.cuda.stream(self.stream):
-            self.x_in.normal_()
-            self._launch_all()
-            for i, (_, a) in enumerate(self._convs):
-                times = {}
-                for tile in range(T + 1):
-                    if tile and not self._tile_ok(i, tile):
-                        continue
-                    for _ in range(_TUNE_WARMUP):
-                        _lib.call("hawq_incep_conv_tiled", C.byref(a), tile, sp)
-                    _lib.call("hawq_event_record", evs[0], sp)
-                    for r in range(n):
-                        _lib.call("hawq_incep_conv_tiled", C.byref(a), tile, sp)
-                        _lib.call("hawq_event_record", evs[r + 1], sp)
-                    self.n_timing_launches += _TUNE_WARMUP + n
-                    samples = []
-                    for r in range(n):
-                        _lib.call("hawq_event_elapsed_ms", evs[r], evs[r + 1], C.byref(ms))
-                        samples.append(ms.value * 1000.0)
-                    times[tile] = sorted(samples)[n // 2]
-                us.append(times)
-        for e in evs:
-            _lib.call("hawq_event_destroy", e)
+        sp, n, us = self.stream.cuda_stream, _TUNE_REPS, []
+        with EventTimer(sp, n + 1) as ev:
+            torch.cuda.synchronize(self.dev)
+            with torch.cuda.stream(self.stream):
+                self.x_in.normal_()
+                self._launch_all()
+                for i, (_, a) in enumerate(self._convs):
+                    times = {}
+                    for tile in range(T + 1):
+                        if tile and not self._tile_ok(i, tile):
+                            continue
+                        for _ in range(_TUNE_WARMUP):
+                            _lib.call("hawq_incep_conv_tiled", C.byref(a), tile, sp)
+                        ev.record(0)
+                        for r in range(n):
+                            _lib.call("hawq_incep_conv_tiled", C.byref(a), tile, sp)
+                            ev.record(r + 1)
+                        self.n_timing_launches += _TUNE_WARMUP + n
+                        times[tile] = sorted(ev.ms(r, r + 1) * 1000.0 for r in range(n))[n // 2]
+                    us.append(times)
         torch.cuda.synchronize(self.dev)
         return us
 
@@ -428,40 +412,9 @@ class InceptionEngine:
             raise RuntimeError("export_plan: no tuned plan (build the engine with tune=True or plan=... and run a forward first)")
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us)
 
-    def _drop_graph(self):
-        for attr in ("_graph", "_graph_u8"):
-            if getattr(self, attr, None) is not None:
-                _lib.call("hawq_graph_destroy", getattr(self, attr))
-                setattr(self, attr, None)
-
-    def __del__(self):
-        try:
-            self._drop_graph()
-        except Exception:
-            pass
-
-    def _launch_all(self, u8: bool = False):
+    def _launch_chain(self, u8):
         for op in (self._ops_u8 if u8 else self._ops):
             op()
-
-    def run_resident(self, u8: bool = False):
-        """One forward over ``self.x_in`` (or, ``u8``, over ``self.x_u8``) on ``self.stream``: graph replay, or (use_graph False)
-        the launches one by one."""
-        if not self.use_graph:
-            self._launch_all(u8)
-            return
-        attr = "_graph_u8" if u8 else "_graph"
-        if getattr(self, attr) is None:
-            self._launch_all(u8)   # warm-up outside capture
-            torch.cuda.synchronize(self.dev)
-            _lib.call("hawq_graph_begin", self.stream.cuda_stream)
-            g = C.c_void_p()
-            try:
-                self._launch_all(u8)
-            finally:
-                _lib.call("hawq_graph_end", self.stream.cuda_stream, C.byref(g))
-            setattr(self, attr, g)
-        _lib.call("hawq_graph_launch", getattr(self, attr), self.stream.cuda_stream)
 
     @property
     def n_launches(self):
@@ -471,23 +424,6 @@ class InceptionEngine:
     def n_launches_u8(self):
         """launches of the uint8 plan (built by the first ``forward_uint8`` of a batch shape)"""
         return len(self._ops_u8)
-
-    def __call__(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("InceptionEngine: input must be on the MI355X (no CPU path)")
-        N, Cc, H, W = x.shape
-        if Cc != 3:
-            raise ValueError("expected [N,3,H,W] images")
-        if self._batch != (N, H, W):
-            self._build(N, H, W)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.x_in.copy_(x, non_blocking=True)
-            self.run_resident()
-            out = self.logits.clone()
-        cur.wait_stream(self.stream)
-        return out
 
     # ------------------------------------------------------------------ uint8 image input (quant_train.py:427-440)
     def _input_quant(self):
@@ -516,13 +452,12 @@ class InceptionEngine:
             return "conv1's output is wider than 8 bits"
         return None
 
-    def _ensure_u8(self):
+    def _ensure_u8(self, N, H, W):
         """the uint8 plan of the current batch shape: image buffer, table, packed conv1 weights and the launch list"""
         if self._ops_u8 is not None:
             return
         if self._u8_why is not None:
             raise PlanNotApplicable(f"uint8 input: {self._u8_why}")
-        N, H, W = self._batch
         a1, w_int = self._conv1
         wt = self._zeros(a1.Cout, 32, dtype=torch.int8, device=self.dev)
         wt.copy_(torch.from_numpy(pack_stem_u8_weights(w_int, a1.Cout)))
@@ -545,22 +480,7 @@ class InceptionEngine:
             raise NotImplementedError("InceptionEngine: uint8 images must be on the MI355X (there is no CPU path)")
         if x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3:
             raise ValueError("expected a uint8 NHWC [N,H,W,3] tensor")
-        N, H, W, _ = x_u8.shape
-        if self._batch != (N, H, W):
-            self._build(N, H, W)
-        self._ensure_u8()
-        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            if self._lut_key != key:
-                self.lut_dev.copy_(self.input_lut(mean, std).to(self.dev), non_blocking=False)
-                self._lut_key = key
-            self.x_u8.copy_(x_u8, non_blocking=True)
-            self.run_resident(u8=True)
-            out = self.logits.clone()
-        cur.wait_stream(self.stream)
-        return out
+        return self._forward_uint8(x_u8, mean, std)
 
     def unit_output(self, name):
         """int64 NCHW numpy array of a unit's integer output (after its q_rescaling_activ) of the last forward."""

@@ -35,7 +35,8 @@ Round 4 (97 k -> 209 k img/s at batch 128):
     fast REQUANT epilogue, the depthwise layers ``hawq_depthwise3x3_requant``;
   * tapped plans (``keep_accumulators``) always run the round-3 launch list - the taps ARE the intermediate tensors.
 Every ``hawq_conv2d`` launch is tile-tuned by timing, and the batch runs as one or two concurrent sub-batch chains inside the one
-hipGraph, whichever replays faster.  Switches (results never change): HAWQ_MBV2_UNFUSED=1 three launches per unit and the im2col init
+hipGraph, whichever replays faster (graph, chains, entry points and event timing: hawq_amd/runner.py).
+Switches (results never change): HAWQ_MBV2_UNFUSED=1 three launches per unit and the im2col init
 block; HAWQ_MBV2_UNIT_TILE=1..4 organisation of the unit launch (``hawq_bottleneck_args.tile``); HAWQ_MBV2_EXACT=1 exact closing
 epilogues; HAWQ_MBV2_PAD64=1 round 3's 64-padded tensors; HAWQ_MBV2_CHAINS, HAWQ_MBV2_TILES.
 """
@@ -49,8 +50,9 @@ import numpy as np
 import torch
 
 from . import _lib, packing
-from .quant_modules import QuantAct, QuantBnConv2d
-from .quant_utils import quantize_weight_per_channel, requant_table, tables_are_fast, tables_fit_fast
+from .quant_modules import QuantBnConv2d
+from .quant_utils import input_quant_lut, quantize_weight_per_channel, requant_table, tables_are_fast, tables_fit_fast
+from .runner import EventTimer, GraphRunner, _i32, _rng, two_round_min
 
 
 def _pad64(c: int) -> int:
@@ -64,15 +66,6 @@ def _pitch(c: int) -> int:
     writes only the first `out_pitch` channels of its 64-channel tiles (include/hawq_mi355.h, ABI 4).  HAWQ_MBV2_PAD64=1 restores the
     64-padded tensors of round 3 (A/B switch for measurements)."""
     return _pad64(c) if os.environ.get("HAWQ_MBV2_PAD64") else (c + 15) // 16 * 16
-
-
-def _rng(act: QuantAct):
-    b = act.activation_bit
-    return (-(2 ** (b - 1)), 2 ** (b - 1) - 1) if act.quant_mode == 'symmetric' else (0, 2 ** b - 1)
-
-
-def _i32(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
 
 
 def _padded(v, n, fill=0):
@@ -185,7 +178,7 @@ def _relu6_is_relu(s_a, s_w, m, e, q_hi) -> bool:
     return True
 
 
-class MobileNetV2Engine:
+class MobileNetV2Engine(GraphRunner):
     """Callable: fp32 NCHW images on the GPU -> fp32 logits of the frozen Q_MobileNetV2 (see the module docstring)."""
 
     def __init__(self, model, from_buffers=None, use_graph: bool = True, keep_accumulators: bool = False, chains: int = 0):
@@ -405,35 +398,9 @@ class MobileNetV2Engine:
         ops.append(partial(_lib.call, "hawq_conv2d", C.byref(r), self.stream.cuda_stream))
 
     def _time_graph(self, reps: int = 12) -> float:
-        # seeded N(0, 1) images (HAWQ_TUNE_INPUT=zero: an all-zero batch), as IntegerEngine._time_graph does: uninitialised memory made
-        # the 1-vs-2 chain choice depend on whatever the allocator handed out
-        if os.environ.get("HAWQ_TUNE_INPUT", "normal") == "zero":
-            self.x_in.zero_()
-        else:
-            g = torch.Generator(device=self.dev)
-            g.manual_seed(0)
-            self.x_in.normal_(generator=g)
-        e0, e1, ms = C.c_void_p(), C.c_void_p(), C.c_float()
-        _lib.call("hawq_event_create", C.byref(e0))
-        _lib.call("hawq_event_create", C.byref(e1))
-        with torch.cuda.stream(self.stream):
-            for _ in range(2):
-                self.run_resident()
-            _lib.call("hawq_event_record", e0, self.stream.cuda_stream)
-            for _ in range(reps):
-                self.run_resident()
-            _lib.call("hawq_event_record", e1, self.stream.cuda_stream)
-        torch.cuda.synchronize(self.dev)
-        _lib.call("hawq_event_elapsed_ms", e0, e1, C.byref(ms))
-        _lib.call("hawq_event_destroy", e0)
-        _lib.call("hawq_event_destroy", e1)
-        return ms.value / reps
+        return super()._time_graph(reps)
 
-    def _drop_graph(self):
-        for attr in ("_graph", "_graph_u8"):
-            if getattr(self, attr, None) is not None:
-                _lib.call("hawq_graph_destroy", getattr(self, attr))
-            setattr(self, attr, None)
+    def _on_graph_dropped(self):
         self.x_u8 = None
 
     def _build(self, N, H, W, x_view=None, logits_view=None):
@@ -683,27 +650,13 @@ class MobileNetV2Engine:
             return
         lib, sp = _lib.load(), self.stream.cuda_stream
         n_tiles = lib.hawq_conv2d_num_tiles() - lib.hawq_conv2d_num_band_tiles()   # the 3x3 band tiles are not for 1x1 layers
-        e0, e1, ms = C.c_void_p(), C.c_void_p(), C.c_float()
-        _lib.call("hawq_event_create", C.byref(e0))
-        _lib.call("hawq_event_create", C.byref(e1))
-        for _, a in self._convs:
-            times = {}
-            for rnd in range(2):
-                for tile in range(1, n_tiles + 1):
-                    if rnd and tile not in times:
-                        continue
-                    a.tile = tile
-                    if lib.hawq_conv2d(C.byref(a), sp) != 0:   # this tile does not take the launch
-                        continue
-                    _lib.call("hawq_event_record", e0, sp)
-                    for _ in range(reps):
-                        _lib.call("hawq_conv2d", C.byref(a), sp)
-                    _lib.call("hawq_event_record", e1, sp)
-                    _lib.call("hawq_event_elapsed_ms", e0, e1, C.byref(ms))
-                    times[tile] = min(times.get(tile, ms.value), ms.value)
-            a.tile = min(times, key=times.get) if times else 0
-        _lib.call("hawq_event_destroy", e0)
-        _lib.call("hawq_event_destroy", e1)
+        with EventTimer(sp) as timer:
+            for _, a in self._convs:
+                def tile(t):
+                    a.tile = t
+                    return partial(_lib.call, "hawq_conv2d", C.byref(a), sp)   # (raises when this tile does not take the launch)
+                times = two_round_min(timer, range(1, n_tiles + 1), tile, reps)
+                a.tile = min(times, key=times.get) if times else 0
 
     @property
     def tile_choice(self):
@@ -718,17 +671,7 @@ class MobileNetV2Engine:
         return self.subs[0].n_fast if self.subs else self.n_fast
 
     # ------------------------------------------------------------------ execution
-    def _launch_all(self, u8: bool = False):
-        if self.subs:   # fork: every chain on its own stream, joined back into self.stream
-            fork = torch.cuda.Event()
-            fork.record(self.stream)
-            for sub in self.subs:
-                sub.stream.wait_event(fork)
-                sub._launch_all(u8)
-                join = torch.cuda.Event()
-                join.record(sub.stream)
-                self.stream.wait_event(join)
-            return
+    def _launch_chain(self, u8):
         if not self._tuned and not self.keep_acc:
             for op in self._ops:   # every buffer holds valid data before launches are timed on it
                 op()
@@ -738,24 +681,6 @@ class MobileNetV2Engine:
                 self._u8_op()
             else:
                 op()
-
-    def run_resident(self, u8: bool = False):
-        """One forward over ``self.x_in`` (or, ``u8``, over ``self.x_u8``) already resident, on ``self.stream``."""
-        if self.use_graph:
-            attr = "_graph_u8" if u8 else "_graph"
-            if getattr(self, attr, None) is None:
-                self._launch_all(u8)   # warm-up (and tile tuning) outside capture
-                torch.cuda.synchronize(self.dev)
-                _lib.call("hawq_graph_begin", self.stream.cuda_stream)
-                try:
-                    self._launch_all(u8)
-                finally:
-                    g = C.c_void_p()
-                    _lib.call("hawq_graph_end", self.stream.cuda_stream, C.byref(g))
-                setattr(self, attr, g)
-            _lib.call("hawq_graph_launch", getattr(self, attr), self.stream.cuda_stream)
-        else:
-            self._launch_all(u8)
 
     # ------------------------------------------------------------------ uint8 image input (quant_train.py:428-440)
     def _ensure_u8(self, N, H, W, x_view=None, lut=None):
@@ -784,57 +709,19 @@ class MobileNetV2Engine:
         """uint8 NHWC images [N,H,W,3] (decoder output, after resize / crop) -> fp32 logits; bit for bit what ``self(normalised
         fp32 NCHW tensor)`` returns for the tensor the reference's data pipeline would have built (ToTensor + Normalize + the input
         QuantAct are one table look-up, ``hawq_amd.quant_utils.input_quant_lut``)."""
-        from .quant_utils import input_quant_lut
         if not x_u8.is_cuda or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3:
             raise ValueError("expected a uint8 NHWC [N,H,W,3] tensor on the MI355X")
-        N, H, W, _ = x_u8.shape
-        if self._batch != (N, H, W):
-            self._build(N, H, W)
-        self._ensure_u8(N, H, W)
-        key = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            if getattr(self, "_lut_key", None) != key:
-                self.lut_dev.copy_(input_quant_lut(self.P['inv_s_in'], mean, std).reshape(-1).to(self.dev), non_blocking=False)
-                self._lut_key = key
-            self.x_u8.copy_(x_u8, non_blocking=True)
-            self.run_resident(u8=True)
-            out = self.logits.clone()
-        cur.wait_stream(self.stream)
-        return out
+        return self._forward_uint8(x_u8, mean, std)
+
+    def _upload_lut(self, mean, std):   # (this engine's kernels read the table flat)
+        self.lut_dev.copy_(input_quant_lut(self.P['inv_s_in'], mean, std).reshape(-1).to(self.dev), non_blocking=False)
 
     @property
     def n_launches(self):
         return sum(len(sub._ops) for sub in self.subs) if self.subs else len(self._ops)
-
-    def __call__(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("MobileNetV2Engine: input must be on the MI355X (no CPU path)")
-        N, Cc, H, W = x.shape
-        if Cc != 3:
-            raise ValueError("expected [N,3,H,W] images")
-        if self._batch != (N, H, W):
-            self._build(N, H, W)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.x_in.copy_(x, non_blocking=True)
-            self.run_resident()
-            out = self.logits.clone()
-        cur.wait_stream(self.stream)
-        return out
 
     def tap(self, name):
         """int32 / int8 NHWC tensor of a tapped stage as an NCHW int64 numpy array without the padding channels."""
         t, shp, c = self.taps[name]
         a = t.cpu().numpy().reshape(shp).astype(np.int64)[..., :c]
         return a.transpose(0, 3, 1, 2)
-
-    def __del__(self):
-        try:
-            for attr in ("_graph", "_graph_u8"):
-                if getattr(self, attr, None) is not None:
-                    _lib.call("hawq_graph_destroy", getattr(self, attr))
-        except Exception:
-            pass

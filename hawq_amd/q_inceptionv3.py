@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .quant_modules import QuantAct, QuantAveragePool2d, QuantBnConv2d, QuantDropout, QuantLinear, QuantMaxPool2d
-from .skeleton import inception_unit_branches, inception_units
+from .skeleton import EngineOwner, inception_unit_branches, inception_units
 
 
 class Q_InceptConv(nn.Module):
@@ -194,7 +194,7 @@ class Q_InceptInitBlock(nn.Module):
         return x
 
 
-class Q_InceptionV3(nn.Module):
+class Q_InceptionV3(EngineOwner, nn.Module):
     """Quantised mirror of a pytorchcv-style float InceptionV3 (q_inceptionv3.py:652-744)."""
 
     def __init__(self, model, dropout_rate=0.5, in_size=(299, 299), num_classes=1000):
@@ -245,16 +245,6 @@ class Q_InceptionV3(nn.Module):
         if self._engine is None or kw:
             self._engine = InceptionEngine(self, **kw)
         return self._engine
-
-    def invalidate_engine(self):
-        self._engine = None
-
-    def _on_state_dict_loaded(self):
-        from .quant_modules import trust_integer_buffers
-        self.invalidate_engine()
-        trust_integer_buffers(self, False)
-        if getattr(self, "engine_defaults", None):
-            self.engine_defaults = dict(self.engine_defaults, from_buffers=False)
 
 
 def q_inceptionv3(model):

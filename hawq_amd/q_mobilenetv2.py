@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .quant_modules import QuantAct, QuantAveragePool2d, QuantBnConv2d, QuantConv2d
+from .skeleton import EngineOwner
 
 # (float child, QuantAct that consumes its ReLU6'd output) of a unit's activated layers, in execution order; the projection
 # `conv3` has no activation of its own and feeds the unit-closing `quant_act_int32`
@@ -71,7 +72,7 @@ class Q_LinearBottleneck(nn.Module):
         return self.quant_act_int32(x + skip, scale, w_scale, skip, scaling_factor_int32, None)
 
 
-class Q_MobileNetV2(nn.Module):
+class Q_MobileNetV2(EngineOwner, nn.Module):
     """Quantised mirror of a pytorchcv-style float MobileNetV2 (role of q_mobilenetv2.py:96-209)."""
 
     def __init__(self, model):
@@ -151,16 +152,6 @@ class Q_MobileNetV2(nn.Module):
             opts = {k: v for k, v in getattr(self, "engine_defaults", {}).items() if k == "from_buffers"}
             self._engine = MobileNetV2Engine(self, **{**opts, **kw})
         return self._engine
-
-    def invalidate_engine(self):
-        self._engine = None
-
-    def _on_state_dict_loaded(self):
-        from .quant_modules import trust_integer_buffers
-        self.invalidate_engine()
-        trust_integer_buffers(self, False)
-        if getattr(self, "engine_defaults", None):
-            self.engine_defaults = dict(self.engine_defaults, from_buffers=False)
 
 
 def q_get_mobilenetv2(model, width_scale, remove_exp_conv=False):

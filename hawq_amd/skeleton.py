@@ -232,3 +232,21 @@ def build_float_inceptionv3(num_classes: int = 1000) -> nn.Module:
     net.output.dropout = nn.Dropout(0.5)
     net.output.fc = nn.Linear(2048, num_classes)
     return net
+
+
+class EngineOwner:
+    """What the three quantised networks share in keeping their fused executor (each model's ``engine()`` builds it into
+    ``self._engine``): dropping it when it has gone stale."""
+
+    def invalidate_engine(self):
+        self._engine = None
+
+    def _on_state_dict_loaded(self):
+        """load_state_dict brought new float parameters / ranges: the cached plan is stale, and so is any trust in integer
+        buffers loaded earlier from a quantized checkpoint (hawq_amd.api.load_quantized_checkpoint sets it again itself)."""
+        from .quant_modules import trust_integer_buffers
+        self.invalidate_engine()
+        trust_integer_buffers(self, False)
+        if getattr(self, "engine_defaults", None):
+            self.engine_defaults = dict(self.engine_defaults, from_buffers=False)
+
