@@ -67,6 +67,8 @@ class IncepConvArgs(C.Structure):
 
 
 INCEP_RAW, INCEP_REQUANT, INCEP_REQUANT2 = 0, 1, 2
+# op ids of hawq_incep_pool_v, by the entry point each one stands for
+INCEP_POOL_OPS = {"hawq_incep_requant": 0, "hawq_incep_maxpool3s2": 1, "hawq_incep_avgpool_branch": 2, "hawq_incep_global_avgpool": 3}
 
 
 class IncepPoolArgs(C.Structure):
@@ -135,6 +137,9 @@ SIGNATURES = {
     "hawq_incep_maxpool3s2": [C.POINTER(IncepPoolArgs), vp],
     "hawq_incep_avgpool_branch": [C.POINTER(IncepPoolArgs), vp],
     "hawq_incep_global_avgpool": [C.POINTER(IncepPoolArgs), vp],
+    "hawq_incep_pool_v_ok": [C.POINTER(IncepPoolArgs), i32],
+    "hawq_incep_pool_v": [C.POINTER(IncepPoolArgs), i32, vp],
+    "hawq_incep_pool_v_avg3_tile": [C.POINTER(IncepPoolArgs), C.POINTER(i32), C.POINTER(i32)],
     "hawq_graph_begin": [vp],
     "hawq_graph_end": [vp, C.POINTER(vp)],
     "hawq_graph_launch": [vp, vp],

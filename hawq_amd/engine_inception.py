@@ -29,6 +29,12 @@ the same integers, so the result is bit-identical.  The uint8 plan shares the ch
 ``export_plan()`` returns the choice as a JSON-serialisable dict (``make_plan``); ``InceptionEngine(model, plan=p)`` replays it
 without timing anything and raises ``engine.StalePlan`` when it does not fit (``check_plan``: another launch list, tile inventory
 or batch shape, or a tile the library now refuses).
+
+Pool kernels.  By default the 49 pool / requant launches are the four entry points named above.  ``InceptionEngine(model,
+fast_pools=True)`` issues every one of them that ``hawq_incep_pool_v_ok`` accepts as ``hawq_incep_pool_v`` with the op id of its entry
+point instead (``pool_launches``): the vectorised kernels of hawq_amd/csrc/incep_pool.hip on the same argument block, buffers and
+stream, which write the same bytes - launch list and results are unchanged.  The choice is an engine argument, not part of a plan:
+it composes with ``tune`` and ``plan``.
 """
 from __future__ import annotations
 
@@ -125,9 +131,9 @@ class _T:
 
 
 class InceptionEngine(GraphRunner):
-    def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None):
+    def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False):
         self.model, self.use_graph = model, use_graph
-        self.tune, self.plan = bool(tune), plan
+        self.tune, self.plan, self.fast_pools = bool(tune), plan, bool(fast_pools)
         self.n_timing_launches = 0           # conv launches issued to time tiles (0 for a default or a replayed plan)
         self.conv_tiles, self.conv_us = None, None
         self.dev = next(model.parameters()).device
@@ -152,7 +158,12 @@ class InceptionEngine(GraphRunner):
         if post is not None:
             a.post, (a.m2, a.ek2, a.lo2, a.hi2) = 1, post
         self._keep.append(a)
-        self._ops.append(partial(_lib.call, name, C.byref(a), self.stream.cuda_stream))
+        op = _lib.INCEP_POOL_OPS[name]
+        self._pools.append((len(self._ops), a, op))
+        if self.fast_pools and _lib.load().hawq_incep_pool_v_ok(C.byref(a), op):
+            self._ops.append(partial(_lib.call, "hawq_incep_pool_v", C.byref(a), op, self.stream.cuda_stream))
+        else:
+            self._ops.append(partial(_lib.call, name, C.byref(a), self.stream.cuda_stream))
 
     def _conv(self, ic, src: _T, dst=None, c_off=0, second=None):
         """Q_InceptConv `ic` on `src` (int8): REQUANT into a new buffer, or - `dst`, `second` = (s_out2, act2) - REQUANT2 into the
@@ -290,7 +301,7 @@ class InceptionEngine(GraphRunner):
         if self.stream is None:
             self.stream = torch.cuda.Stream(device=self.dev)
         self.N, dev, q = N, self.dev, self.model
-        self._ops, self._keep, self.unit_out, self._convs = [], [], {}, []
+        self._ops, self._keep, self.unit_out, self._convs, self._pools = [], [], {}, [], []
         self.conv_tiles, self.conv_us = None, None
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
@@ -363,6 +374,11 @@ class InceptionEngine(GraphRunner):
     def conv_launches(self):
         """``launch_key`` of every conv launch (the classifier last), in launch order"""
         return [launch_key(a) for _, a in self._convs]
+
+    @property
+    def pool_launches(self):
+        """(library entry point, op id of ``hawq_incep_pool_v``) of every pool / requant launch, in launch order"""
+        return [(self._ops[idx].args[0], op) for idx, _, op in self._pools]
 
     def _tile_ok(self, i, tile):
         return bool(_lib.load().hawq_incep_conv_tile_ok(C.byref(self._convs[i][1]), tile))

@@ -504,6 +504,21 @@ int hawq_incep_requant(const hawq_incep_pool_args *a, void *stream);
 int hawq_incep_maxpool3s2(const hawq_incep_pool_args *a, void *stream);
 int hawq_incep_avgpool_branch(const hawq_incep_pool_args *a, void *stream);
 int hawq_incep_global_avgpool(const hawq_incep_pool_args *a, void *stream);
+/* The same launches on vectorised kernels (hawq_amd/csrc/incep_pool.hip): a lane owns 16 consecutive channels of a pixel and moves
+ * them with 16-byte loads and stores; the average pool stages its pre-requantised tile in LDS, the max pool applies `pre` once after
+ * the max, the global pool splits the pixels of an image over lanes.  hawq_incep_pool_v writes exactly the bytes the op's entry point
+ * above writes for the same argument block.  hawq_incep_pool_v_ok: 1 when hawq_incep_pool_v takes this launch (it launches nothing):
+ * C, in_pitch, in_off, ldo and c_off multiples of 16, in / out 16-byte aligned, and per op
+ *   MAX3S2 with pre: m1 >= 0, k = 0, e1 >= in_bits (pre is then monotone, so it commutes with the max);
+ *   AVG3 with pre:   lo1, hi1 inside int16 (the staged tile is int16);
+ *   GLOBAL:          100 * H * W * max|summand| + H * W < 2^31 (int32 average rule).
+ * On a refused description hawq_incep_pool_v returns non-zero, sets hawq_last_error() and launches nothing. */
+enum { HAWQ_INCEP_POOL_REQUANT = 0, HAWQ_INCEP_POOL_MAX3S2 = 1, HAWQ_INCEP_POOL_AVG3 = 2, HAWQ_INCEP_POOL_GLOBAL = 3 };
+int hawq_incep_pool_v_ok(const hawq_incep_pool_args *a, int op);
+int hawq_incep_pool_v(const hawq_incep_pool_args *a, int op, void *stream);
+/* the workgroup tile (th rows x tw columns of output pixels, x 32 channels) hawq_incep_pool_v uses for this AVG3 description (it
+ * depends on the map and, through the workgroup count, on N and C); non-zero with hawq_last_error() on a refused description */
+int hawq_incep_pool_v_avg3_tile(const hawq_incep_pool_args *a, int32_t *th, int32_t *tw);
 
 /* ---- hipGraph helpers: capture a sequence of the launches above once, replay per batch */
 int hawq_graph_begin(void *stream);

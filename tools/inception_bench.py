@@ -14,10 +14,17 @@ of ``hawq_incep_conv_tiled``, timed by the engine or replayed from FILE) of the 
 bit-equal.  With ``--tune`` it prints the per-launch table (geometry, microseconds of tile 0, chosen tile, its microseconds) and the
 sums over the conv launches; ``--save-plan FILE`` writes the last batch size's plan (``export_plan()``) as JSON.
 
+``--pools`` (alone, or with ``--tune`` / ``--plan FILE``, whose conv tiles both engines then share) compares the plan on the four pool
+entry points of inception.hip with the same plan on ``hawq_incep_pool_v`` (``fast_pools=True``): alternating blocks as above, an
+assertion that the logits are bit-equal, and a table of the 49 pool / requant launches - each timed alone on the plan's own buffers
+(HIP events, 2 untimed + 5 timed launches, the median) with the old and the new kernel, the bytes it has to move (input read once +
+output written once, from the shapes) and that byte count over 6.29 TB/s.  ``--skip-pool-table`` leaves the table out (kernel traces).
+
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --input f32,u8 [--blocks 6] [--stem-launches 0]
     python tools/inception_bench.py --tune [--batches 128] [--blocks 6] [--save-plan plan.json]
     python tools/inception_bench.py --plan plan.json --batches 128
+    python tools/inception_bench.py --tune --pools --batches 128,1
 """
 import argparse
 import json
@@ -129,6 +136,98 @@ def compare_plans(model, args, b):
     return tuned
 
 
+STREAM_TBS = 6.29   # what the MI355X streams (profiles/inception.md): the floor of a launch is its bytes over this
+POOL_NAMES = ("hawq_incep_requant", "hawq_incep_maxpool3s2", "hawq_incep_avgpool_branch", "hawq_incep_global_avgpool")
+
+
+def pool_bytes(a, op):
+    """bytes a pool launch has to move: its input slice read once and its output slice written once"""
+    ho, wo = {0: (a.H, a.W), 1: ((a.H - 3) // 2 + 1, (a.W - 3) // 2 + 1), 2: (a.H, a.W), 3: (1, 1)}[op]
+    return a.N * a.C * (a.H * a.W * a.in_bits + ho * wo * a.out_bits) // 8
+
+
+def time_pools(eng, reps=5, warmup=2):
+    """[(old us, new us or None)] per pool launch of `eng`, each launch alone on the plan's buffers, which hold a forward (every
+    pool launch is a pure function of its input buffer, so repeating it changes nothing)"""
+    import ctypes as C
+    from hawq_amd import _lib
+    from hawq_amd.runner import EventTimer
+    sp, out = eng.stream.cuda_stream, []
+    old_of = {v: k for k, v in _lib.INCEP_POOL_OPS.items()}
+    with EventTimer(sp, reps + 1) as ev:
+        torch.cuda.synchronize()
+        with torch.cuda.stream(eng.stream):
+            for _, a, op in eng._pools:
+                row = []
+                for new in (False, True):
+                    if new and not _lib.load().hawq_incep_pool_v_ok(C.byref(a), op):
+                        row.append(None)
+                        continue
+                    launch = (lambda: _lib.call("hawq_incep_pool_v", C.byref(a), op, sp)) if new else \
+                        (lambda: _lib.call(old_of[op], C.byref(a), sp))
+                    for _ in range(warmup):
+                        launch()
+                    ev.record(0)
+                    for r in range(reps):
+                        launch()
+                        ev.record(r + 1)
+                    row.append(sorted(ev.ms(r, r + 1) * 1000.0 for r in range(reps))[reps // 2])
+                out.append(tuple(row))
+    torch.cuda.synchronize()
+    return out
+
+
+def compare_pools(model, args, b):
+    """one plan on the old pool kernels against the same plan with fast_pools=True, alternating blocks; returns the fast engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    plan = json.load(open(args.plan)) if args.plan else None
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    with torch.no_grad():
+        old = InceptionEngine(model, tune=args.tune and plan is None, plan=plan)
+        y_old = old(x)
+        if old.conv_tiles is not None:
+            plan = old.export_plan()   # the fast engine replays the same conv tiles: only the pool kernels differ
+        fast = InceptionEngine(model, plan=plan, fast_pools=True)
+        engines = {"old_pools": old, "fast_pools": fast}
+        equal = bool(torch.equal(y_old, fast(x)))
+        assert equal, "the logits with fast_pools differ from the old pool kernels'"
+        assert old.conv_tiles == fast.conv_tiles and old.n_launches == fast.n_launches
+        if not args.skip_pool_table:
+            us = time_pools(fast)
+            print(f"# {wl}: pool launch | entry point | H W C in_bits out_bits ldo c_off | old us | new us | bytes | floor us (bytes / "
+                  f"{STREAM_TBS} TB/s) | issued as")
+            for i, ((_, a, op), (name, _), (t0, t1)) in enumerate(zip(fast._pools, fast.pool_launches, us)):
+                nb = pool_bytes(a, op)
+                print(f"# {i:2d} | {POOL_NAMES[op]} | {a.H} {a.W} {a.C} {a.in_bits} {a.out_bits} {a.ldo} {a.c_off} | {t0:.1f} | " +
+                      ("refused" if t1 is None else f"{t1:.1f}") + f" | {nb} | {nb / (STREAM_TBS * 1e6):.1f} | {name}")
+            s0 = sum(t0 for t0, _ in us)
+            s1 = sum(t0 if t1 is None else t1 for t0, t1 in us)
+            print(json.dumps({"workload": wl, "pool_launches": len(us), "pool_us_old_sum": round(s0, 1), "pool_us_new_sum": round(s1, 1),
+                              "pool_floor_us_sum": round(sum(pool_bytes(a, op) for _, a, op in fast._pools) / (STREAM_TBS * 1e6), 1),
+                              "taken_by_pool_v": sum(n == "hawq_incep_pool_v" for n, _ in fast.pool_launches),
+                              "slower_launches": [i for i, (t0, t1) in enumerate(us) if t1 is not None and t1 > t0]}), flush=True)
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": "tuned" if e.conv_tiles is not None else "fixed", "pools": k,
+                              "ms_per_batch": round(mean, 4), "images_per_s": round(b * 1000.0 / mean, 1),
+                              "block_min_ms": round(min(v), 4), "block_max_ms": round(max(v), 4), "blocks": len(v),
+                              "steps": args.steps, "launches": e.n_launches, "logits_bit_equal": equal}), flush=True)
+        mo, mf = sum(ms["old_pools"]) / args.blocks, sum(ms["fast_pools"]) / args.blocks
+        print(json.dumps({"workload": wl, "fast_over_old_rate": round(mo / mf, 4), "gain_ms": round(mo - mf, 4),
+                          "old_block_spread_ms": round(max(ms["old_pools"]) - min(ms["old_pools"]), 4),
+                          "fast_block_spread_ms": round(max(ms["fast_pools"]) - min(ms["fast_pools"]), 4)}), flush=True)
+    return fast
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheme", default="uniform8")
@@ -141,16 +240,20 @@ def main():
     ap.add_argument("--stem-launches", type=int, default=0, help="--input: then issue each stem form K times (for a kernel trace)")
     ap.add_argument("--tune", action="store_true", help="compare the fixed plan with the plan on tuned conv tiles")
     ap.add_argument("--plan", default=None, help="like --tune, but replay the conv tile plan of this JSON file instead of timing")
+    ap.add_argument("--pools", action="store_true", help="compare the old pool kernels with fast_pools=True on one plan")
+    ap.add_argument("--skip-pool-table", action="store_true", help="--pools: do not time the 49 pool launches one by one")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
+    if args.save_plan and not (args.tune or args.plan):
+        ap.error("--save-plan needs --tune or --plan: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
     for b in (int(v) for v in args.batches.split(",")):
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.tune or args.plan:
-            tuned = compare_plans(model, args, b)
+        if args.tune or args.plan or args.pools:
+            tuned = (compare_pools if args.pools else compare_plans)(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
                     json.dump(tuned.export_plan(), f)
