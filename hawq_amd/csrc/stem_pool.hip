@@ -140,15 +140,52 @@ __global__ __launch_bounds__(256) void stem_conv7_kernel(const int8_t *__restric
 
 // ------------------------------------------------------------------ fused stem
 // input quantiser + 7x7/2 conv + bias + 3x3/2 max-pool + QuantAct16 + ReLU + first unit's QuantAct in
-// ONE kernel (q_resnet.py:115-122 + 234/239).  A workgroup owns an 8x8 block of POOLED pixels of two
-// images (one 4x8 sub-block per wave).  The fp32 input patch it needs (39x39 pixels per image) is
-// quantised straight into an int8 NHWC4 LDS patch; each wave then walks the 3x3 pooling window: for
-// window position (dy,dx) one MFMA pixel tile holds conv pixel (2py+dy-1, 2px+dx-1) of the lane's pooled
-// pixel, so the max over the window is a register max over 9 accumulator tiles - taken on the raw
-// accumulators, because the per-channel requantisation is monotone (m > 0) and the bias is constant.
-// The 16-bit conv output at 112x112 (205 MB per 128-image batch) never exists in memory.
-constexpr int SF_PW = 40;                       // patch width in pixels (39 used + 1 zero column)
-constexpr int SF_PATCH = 39 * SF_PW * 4;        // bytes per image patch
+// ONE kernel (q_resnet.py:115-122 + 234/239).  The 16-bit conv output at 112x112 (205 MB per 128-image
+// batch) never exists in memory, and every conv pixel is computed exactly once per workgroup.
+//
+// A workgroup owns a strip of SF_R = 8 pooled rows x SF_T = 28 pooled columns of ONE image.  The input
+// patch it needs (39 rows x 120 pixels) is quantised straight into an int8 NHWC4 LDS patch.  Wave w takes
+// the 32-channel half w & 1 of the four pooled rows 4 (w >> 1) ... + 3 and keeps that half's weights (7
+// fragments) in registers throughout.  Its 32 pixel lanes hold CONSECUTIVE pooled columns px0 + lane, and it
+// walks down the 9 conv rows 2 py - 1 ... of its pooled rows.  Per conv row two MFMA tiles are computed:
+// T0 = conv column 2 px - 1 and T1 = conv column 2 px of the lane's pooled pixel.  The third window column,
+// 2 px + 1, is T0 of lane + 1, so
+//     rowmax = max(T0, T0 of lane + 1, T1)
+// costs one DPP-shifted v_max per accumulator register, and the pooled pixel is the max of three consecutive
+// row maxima; an odd conv row (2 py + 1) closes pooled row py and opens py + 1, so it is computed once and
+// carried.  The max is taken on the raw accumulators, because the per-channel requantisation is monotone
+// (m > 0) and the bias is constant.  Lanes 28-31 are halo lanes: lane 28 feeds lane 27's third column, none of
+// them stores (the next workgroup owns those columns); 28 tiles ImageNet's 56 pooled columns without waste.
+// Per 32 channels and pooled row that is 28 MFMAs (+ 14 per wave for the opening row) where the window walk of
+// the first version took 63.
+//
+// Max-pool padding is -inf: a conv row outside the conv map is skipped (wave-uniform), and of the conv columns
+// only T0 can be outside for a lane whose result is used (2 px <= Wc - 1 for every px < Wp) - one select per
+// accumulator register, on border strips only.
+//
+// LDS patch: pixel PAIRS (8 bytes) are de-interleaved into two planes, E = even pairs, O = odd pairs, each
+// [39][30] pairs.  A lane's B fragment (16 bytes = pairs 2 j + dx, 2 j + dx + 1 with j = lane + k-half) is
+// {E[j], O[j]} for T0 and {O[j], E[j + 1]} for T1: three ds_read_b64 per weight row serve both tiles, every
+// one of them 32 lanes x 8 contiguous bytes (no bank conflict, no alignment replay) from a single copy of the
+// patch - the first version needed a second, 8-byte-shifted copy and three stores per group for that.
+// Halo lanes read up to 32 bytes past a row (into the next row / the pad): harmless, never stored.
+//
+// Resources (hipcc -O3, gfx950): 104 VGPRs with uint8 input, 120 with fp32 input, no scratch; 20 560 / 19 792 bytes of LDS per
+// workgroup; N x ceil(Hp / 8) x ceil(Wp / 28) workgroups (1792 at 128 ImageNet images).  Registers allow 4 workgroups per CU
+// (LDS would allow 7), so fill, MFMA and epilogue phases of different workgroups still overlap, four deep where the window walk
+// ran six deep at 80 VGPRs: both accumulator tiles, the open pooled row and 7 weight fragments are live in the MFMA part.  The
+// weight fragments are re-read per conv row (L1-resident) so that they do not also live through the epilogue.
+constexpr int SF_T = 28;                        // pooled columns a workgroup stores
+constexpr int SF_R = 8;                         // pooled rows per workgroup (two wave pairs x 4)
+constexpr int SF_ROWS = 4 * SF_R + 7;           // input rows of the patch (39)
+constexpr int SF_SLOTS = SF_T + 2;              // pixel pairs per row and plane (30: 120 pixels)
+constexpr int SF_ROWB = SF_SLOTS * 8;           // bytes per row of one plane
+constexpr int SF_PLANE = SF_ROWS * SF_ROWB;     // bytes per plane (9360: no multiple of 512, > 2040 - the E and O reads of a fragment stay separate ds_read_b64)
+constexpr int SF_NG = SF_ROWS * SF_SLOTS;       // groups of 4 pixels (one pair for each plane)
+constexpr int SF_GPT = (SF_NG + 255) / 256;     // groups per thread (5)
+
+// lane i <- lane i + 1 (wave_shl:1; lane 63 keeps its own value).  Lane 31 receives lane 32's - a halo lane.
+__device__ __forceinline__ int sf_lane_up(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x130, 0xf, 0xf, false); }
 
 // U8: the image arrives as uint8 NHWC [N][H][W][Cin] (what an image decoder produces) together with a [3][256] int8
 // table lut[c][u] = QuantAct(normalise_c(u / 255)) built on the host with the reference's own float operations
@@ -161,19 +198,12 @@ __global__ __launch_bounds__(256, 4) void stem_fused_kernel(
     const int32_t *__restrict__ e, int a_lo, int a_hi, int Hc, int Wc, int Hp, int Wp,
     uint16_t *__restrict__ res_out, void *__restrict__ out_q, int out_bits, int mq, int eq, int q_lo, int q_hi,
     int fast, int dbg) {
-    // Two copies of the int8 patch: `patch` and, 16 bytes into the second half, the SAME bytes shifted down by 8 (copy byte a =
-    // patch byte a + 8).  A lane's B fragment is 16 consecutive bytes starting at a multiple of 8: window columns dx = 0 / 2
-    // read it 16-byte aligned from `patch`, dx = 1 from the shifted copy - one conflict-free ds_read_b128 per MFMA instead of
-    // two ds_read_b64 that reach only half of the LDS banks (lanes are 16 bytes apart: 8-byte reads leave every other bank
-    // pair idle, and the 4 pooled rows of a wave fold onto each other two-way).  The 126 fragment reads per wave were the
-    // kernel's largest single cost (4 MB of LDS reads per CU per 8 workgroups).
-    __shared__ __attribute__((aligned(16))) char patch[4 * SF_PATCH + 32];
+    __shared__ __attribute__((aligned(16))) char patch[2 * SF_PLANE + 48];
     // fast contract: per-channel fused requant constants {m, (e - 32) | k << 8, lo32(C), hi32(C)}, C = (bias << k) * m + 2^(e-1) - the form
     // of hawq_amd.packing.pack_ctab, built here from (bias, m, e) by the first 64 threads while the others already fetch the patch.  The
     // epilogue then reads ONE 16-byte LDS entry per output instead of three global table words, and a requant is shift + v_mad_i64_i32 +
-    // shift (round 4: the epilogue was 11 of the launch's 54 us at batch 64, tools/stemprobe.py with HAWQ_DBG=64)
+    // shift
     __shared__ __attribute__((aligned(16))) int ctab_s[64 * 4];
-    char *const patch8 = patch + 2 * SF_PATCH + 16;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (fast && t < 64) {
         const int mm = m[t], ek = e[t], ee = ek & 0xff, kk = ek >> 8;
@@ -182,41 +212,47 @@ __global__ __launch_bounds__(256, 4) void stem_fused_kernel(
         *reinterpret_cast<v4i *>(ctab_s + 4 * t) = ent;
     }
     const int l31 = lane & 31, h = lane >> 5;
-    const int bw = (Wp + 7) >> 3, bh = (Hp + 7) >> 3;
+    const int bw = (Wp + SF_T - 1) / SF_T, bh = (Hp + SF_R - 1) / SF_R;
     int b = blockIdx.x;
     const int bx = b % bw;
     b /= bw;
     const int by = b % bh;
-    const int n0 = (b / bh) * 2;
-    const int py0 = by * 8, px0 = bx * 8;
+    const int n = b / bh;
+    const int py0 = by * SF_R, px0 = bx * SF_T;
 
+    // ---- fill: group g = 4 pixels (one pair for each plane) at patch row g / 30; input pixel (4 py0 - 5 + row, 4 px0 - 5 + 4 slot).
+    // All global loads of a batch of groups are issued before any is consumed (the fill is latency-bound otherwise); coordinates are
+    // clamped into the image so every load is legal, out-of-image pixels are zeroed by mask (the conv's zero padding).
+    auto group_geom = [&](int k, int &gaddr, unsigned &gmask, int &iy, int &ix) {
+        const int g = t + 256 * k;
+        const int gg = g < SF_NG ? g : SF_NG - 1;
+        const int r = gg / SF_SLOTS, s = gg - r * SF_SLOTS;
+        iy = 4 * py0 - 5 + r, ix = 4 * px0 - 5 + 4 * s;
+        const bool rowok = g < SF_NG && (unsigned)iy < (unsigned)H && !HAWQ_DBG_BIT(dbg, 16);
+        gaddr = r * SF_ROWB + s * 8;
+        gmask = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (rowok && (unsigned)(ix + j) < (unsigned)W) gmask |= 1u << j;
+    };
+    auto store_group = [&](int gaddr, const int (&w)[4]) {
+        *reinterpret_cast<v2i *>(patch + gaddr) = v2i{w[0], w[1]};
+        *reinterpret_cast<v2i *>(patch + SF_PLANE + gaddr) = v2i{w[2], w[3]};
+    };
     if constexpr (U8) {
         // ---- uint8 input: table look-up straight into the LDS patch
         __shared__ int8_t lut_s[3 * 256];
         for (int i = t; i < 3 * 256 / 4; i += 256) reinterpret_cast<int *>(lut_s)[i] = reinterpret_cast<const int *>(lut)[i];
         __syncthreads();
-        constexpr int NG = 2 * 39 * (SF_PW / 4);       // groups of 4 pixels (one 16-B LDS store each)
-        constexpr int GPT = (NG + 255) / 256;          // groups per thread
-        // all byte loads of the thread's groups are issued before any is consumed (the fill is latency-bound otherwise);
-        // coordinates are clamped into the image so every load is legal, out-of-image pixels are zeroed by mask
-        unsigned raw[GPT][3];   // the group's 12 bytes (4 pixels x 3 channels), little-endian
-        unsigned gmask[GPT];
-        int gaddr[GPT];
+        unsigned raw[SF_GPT][3];   // the group's 12 bytes (4 pixels x 3 channels), little-endian
+        unsigned gmask[SF_GPT];
+        int gaddr[SF_GPT];
 #pragma unroll
-        for (int k = 0; k < GPT; ++k) {
-            const int g = t + 256 * k;
-            const int gg = g < NG ? g : NG - 1;
-            const int img = gg / (39 * (SF_PW / 4)), rem = gg - img * (39 * (SF_PW / 4));
-            const int r = rem / (SF_PW / 4), c = (rem - r * (SF_PW / 4)) * 4;
-            const int iy = 4 * py0 - 5 + r, ix = 4 * px0 - 5 + c, n = n0 + img;
-            const bool rowok = g < NG && n < N && (unsigned)iy < (unsigned)H && !HAWQ_DBG_BIT(dbg, 16);
-            gaddr[k] = img * SF_PATCH + (r * SF_PW + c) * 4;
-            gmask[k] = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (rowok && (unsigned)(ix + j) < (unsigned)W && c + j < 39) gmask[k] |= 1u << j;
-            const int nn = n < N ? n : N - 1, yy = min(max(iy, 0), H - 1);
-            const size_t rowoff = ((size_t)nn * H + yy) * W * Cin;
+        for (int k = 0; k < SF_GPT; ++k) {
+            int iy, ix;
+            group_geom(k, gaddr[k], gmask[k], iy, ix);
+            const int yy = min(max(iy, 0), H - 1);
+            const size_t rowoff = ((size_t)n * H + yy) * W * Cin;
             if (Cin == 3 && ix >= 0 && ix + 5 < W) {
                 // 4 aligned dwords cover the 12 bytes at any misalignment (and stay inside the row: ix + 5 < W)
                 const size_t b0 = rowoff + (size_t)ix * 3;
@@ -227,21 +263,21 @@ __global__ __launch_bounds__(256, 4) void stem_fused_kernel(
                 raw[k][1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
                 raw[k][2] = __builtin_amdgcn_alignbyte(d3, d2, sh);
             } else {  // image borders / fewer channels: byte loads with clamped coordinates
-                unsigned char b[12];
+                unsigned char bb[12];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const uint8_t *px = xu8 + rowoff + (size_t)min(max(ix + j, 0), W - 1) * Cin;
 #pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) b[3 * j + ch] = ch < Cin ? px[ch] : 0;
+                    for (int ch = 0; ch < 3; ++ch) bb[3 * j + ch] = ch < Cin ? px[ch] : 0;
                 }
 #pragma unroll
                 for (int d = 0; d < 3; ++d)
-                    raw[k][d] = (unsigned)b[4 * d] | ((unsigned)b[4 * d + 1] << 8) | ((unsigned)b[4 * d + 2] << 16) | ((unsigned)b[4 * d + 3] << 24);
+                    raw[k][d] = (unsigned)bb[4 * d] | ((unsigned)bb[4 * d + 1] << 8) | ((unsigned)bb[4 * d + 2] << 16) | ((unsigned)bb[4 * d + 3] << 24);
             }
         }
 #pragma unroll
-        for (int k = 0; k < GPT; ++k) {
-            if (t + 256 * k >= NG) continue;
+        for (int k = 0; k < SF_GPT; ++k) {
+            if (t + 256 * k >= SF_NG) continue;
             int w[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -251,129 +287,119 @@ __global__ __launch_bounds__(256, 4) void stem_fused_kernel(
                                           Cin > 2 ? lut_s[512 + byte_at(3 * j + 2)] : 0, 0)
                           : 0;
             }
-            v4i o = {w[0], w[1], w[2], w[3]};
-            *reinterpret_cast<v4i *>(patch + gaddr[k]) = o;
-            *reinterpret_cast<v2i *>(patch8 + gaddr[k] - 8) = v2i{o.x, o.y};
-            *reinterpret_cast<v2i *>(patch8 + gaddr[k]) = v2i{o.z, o.w};
+            store_group(gaddr[k], w);
         }
     } else {
-    // ---- quantise the input patch(es) into LDS: q = clamp(rint(fl(1/S) * x))  (quant_utils.py:73-97)
-    const size_t plane = (size_t)H * W;
-    auto quant1 = [&](float v) {
-        v = rintf(__fmul_rn(inv_scale, v));
-        return (int)fminf(fmaxf(v, (float)in_lo), (float)in_hi);
-    };
-    // 4 pixels (one 16-B LDS store) per step.  All global loads of the thread's groups are issued before any
-    // is consumed (coordinates are clamped into the image so every load is legal; out-of-image pixels are
-    // zeroed by mask afterwards) - the fill is latency-bound otherwise.
-    constexpr int NG = 2 * 39 * (SF_PW / 4);       // 780 groups of 4 pixels
-    constexpr int GPT = (NG + 255) / 256;          // groups per thread
-    float4 v[GPT][3];
-    int gaddr[GPT];
-    unsigned gmask[GPT];  // bit k: pixel k of the group is inside the image
+        // ---- fp32 input: q = clamp(rint(fl(1/S) * x))  (quant_utils.py:73-97), in two batches of groups (3 + 2) so that the
+        // loads in flight (3 float4 per group) stay inside the register budget of the MFMA phase
+        const size_t plane = (size_t)H * W;
+        auto quant1 = [&](float v) {
+            v = rintf(__fmul_rn(inv_scale, v));
+            return (int)fminf(fmaxf(v, (float)in_lo), (float)in_hi);
+        };
+        constexpr int GB = 3;
 #pragma unroll
-    for (int k = 0; k < GPT; ++k) {
-        const int g = t + 256 * k;
-        const int gg = g < NG ? g : NG - 1;
-        const int img = gg / (39 * (SF_PW / 4)), rem = gg - img * (39 * (SF_PW / 4));
-        const int r = rem / (SF_PW / 4), c = (rem - r * (SF_PW / 4)) * 4;
-        const int iy = 4 * py0 - 5 + r, ix = 4 * px0 - 5 + c, n = n0 + img;
-        const bool rowok = g < NG && n < N && (unsigned)iy < (unsigned)H && !HAWQ_DBG_BIT(dbg, 16);
-        gaddr[k] = img * SF_PATCH + (r * SF_PW + c) * 4;
-        gmask[k] = 0;
+        for (int kb = 0; kb < SF_GPT; kb += GB) {
+            float4 v[GB][3];
+            int gaddr[GB];
+            unsigned gmask[GB];  // bit j: pixel j of the group is inside the image
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (rowok && (unsigned)(ix + j) < (unsigned)W && c + j < 39) gmask[k] |= 1u << j;
-        const int nn = n < N ? n : N - 1, yy = min(max(iy, 0), H - 1);
-        const float *src = x + ((size_t)nn * Cin) * plane + (size_t)yy * W;
-        const bool interior = ix >= 0 && ix + 3 < W;
+            for (int k = 0; k < GB; ++k) {
+                if (kb + k >= SF_GPT) continue;
+                int iy, ix;
+                group_geom(kb + k, gaddr[k], gmask[k], iy, ix);
+                const int yy = min(max(iy, 0), H - 1);
+                const float *src = x + ((size_t)n * Cin) * plane + (size_t)yy * W;
+                const bool interior = ix >= 0 && ix + 3 < W;
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            if (ch < Cin) {
-                if (interior) {
-                    v[k][ch] = *reinterpret_cast<const float4 *>(src + ch * plane + ix);
-                } else {
-                    const float *s1 = src + ch * plane;
-                    v[k][ch].x = s1[min(max(ix, 0), W - 1)], v[k][ch].y = s1[min(max(ix + 1, 0), W - 1)];
-                    v[k][ch].z = s1[min(max(ix + 2, 0), W - 1)], v[k][ch].w = s1[min(max(ix + 3, 0), W - 1)];
+                for (int ch = 0; ch < 3; ++ch) {
+                    if (ch < Cin) {
+                        if (interior) {
+                            v[k][ch] = *reinterpret_cast<const float4 *>(src + ch * plane + ix);
+                        } else {
+                            const float *s1 = src + ch * plane;
+                            v[k][ch].x = s1[min(max(ix, 0), W - 1)], v[k][ch].y = s1[min(max(ix + 1, 0), W - 1)];
+                            v[k][ch].z = s1[min(max(ix + 2, 0), W - 1)], v[k][ch].w = s1[min(max(ix + 3, 0), W - 1)];
+                        }
+                    } else {
+                        v[k][ch] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
                 }
-            } else {
-                v[k][ch] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int k = 0; k < GB; ++k) {
+                if (kb + k >= SF_GPT || t + 256 * (kb + k) >= SF_NG) continue;
+                const float px4[4][3] = {{v[k][0].x, v[k][1].x, v[k][2].x}, {v[k][0].y, v[k][1].y, v[k][2].y},
+                                         {v[k][0].z, v[k][1].z, v[k][2].z}, {v[k][0].w, v[k][1].w, v[k][2].w}};
+                int w[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool ok = (gmask[k] >> j) & 1;
+                    w[j] = ok ? (int)pack4_i8(quant1(px4[j][0]), Cin > 1 ? quant1(px4[j][1]) : 0, Cin > 2 ? quant1(px4[j][2]) : 0, 0) : 0;
+                }
+                store_group(gaddr[k], w);
             }
         }
-    }
-#pragma unroll
-    for (int k = 0; k < GPT; ++k) {
-        if (t + 256 * k >= NG) continue;
-        const float px4[4][3] = {{v[k][0].x, v[k][1].x, v[k][2].x}, {v[k][0].y, v[k][1].y, v[k][2].y},
-                                 {v[k][0].z, v[k][1].z, v[k][2].z}, {v[k][0].w, v[k][1].w, v[k][2].w}};
-        int w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool ok = (gmask[k] >> j) & 1;
-            w[j] = ok ? (int)pack4_i8(quant1(px4[j][0]), Cin > 1 ? quant1(px4[j][1]) : 0, Cin > 2 ? quant1(px4[j][2]) : 0, 0) : 0;
-        }
-        v4i o = {w[0], w[1], w[2], w[3]};
-        *reinterpret_cast<v4i *>(patch + gaddr[k]) = o;
-        *reinterpret_cast<v2i *>(patch8 + gaddr[k] - 8) = v2i{o.x, o.y};
-        *reinterpret_cast<v2i *>(patch8 + gaddr[k]) = v2i{o.z, o.w};
-    }
     }
     __syncthreads();
 
-    const int img = wave >> 1;
-    const int pr = (wave & 1) * 4 + (l31 >> 3), pc = l31 & 7;  // pooled pixel of this lane inside the block
-    const int py = py0 + pr, px = px0 + pc, n = n0 + img;
-    const bool pvalid = n < N && py < Hp && px < Wp;
-    const int poff = img * SF_PATCH + ((4 * pr) * SF_PW + 4 * pc + 4 * h) * 4;   // multiple of 16
-    const char *pbase = patch + poff, *pbase8 = patch8 + poff;
-    const size_t opix = ((size_t)n * Hp + py) * Wp + px;
-
-    // The two 32-channel halves are walked one after the other: weights of ONE half (7 fragments, 28 VGPRs), one
-    // accumulator tile and one running maximum live at a time - 80 instead of 138 VGPRs, 6 instead of 3 workgroups per
-    // CU, whose fill (HBM), MFMA and max / requant (VALU) phases then overlap.  The price is reading every B fragment of
-    // the LDS patch twice: 2 x 126 ds_read_b64 per wave, ~500 LDS cycles beside 4000 cycles of MFMA.
-    // a block none of whose 17 x 17 conv pixels leaves the conv map (36 of ImageNet's 49 blocks) needs no select at all
-    const bool interior = py0 > 0 && px0 > 0 && 2 * (py0 + 7) + 1 < Hc && 2 * (px0 + 7) + 1 < Wc;
-#pragma unroll 1
-    for (int c = 0; c < 2; ++c) {
-    v4i wf[7];
+    // ---- conv rows -> row maxima -> pooled rows, all in registers
+    const int c = wave & 1;                        // 32-channel half of this wave
+    const int pyw = py0 + 4 * (wave >> 1);         // its first pooled row
+    const int px = px0 + l31;
+    const bool store_lane = l31 < SF_T && px < Wp;
+    // T0 (conv column 2 px - 1) outside the conv map: the left image border, and - odd Wc only - the column right of the last pooled pixel
+    const bool t0_in = (unsigned)(2 * px - 1) < (unsigned)Wc;
+    const bool border = px0 == 0 || 2 * (px0 + SF_T) - 1 >= Wc;   // wave-uniform: some lane that matters needs the select
+    const int8_t *wlane = wgt + ((c * 32 + cperm(l31)) * 7) * 32 + h * 16;
+    const char *rb = patch + (16 * (wave >> 1)) * SF_ROWB + 8 * (l31 + h);   // pair j = lane + k-half of the wave's first patch row
+    const int ch = c * 32 + h * 16;
+    const int NEG = (int)0x80000000;
+    int run[16];   // max of the conv rows seen so far of the pooled row that is open
 #pragma unroll
-    for (int kh = 0; kh < 7; ++kh)
-        wf[kh] = *reinterpret_cast<const v4i *>(wgt + ((c * 32 + cperm(l31)) * 7 + kh) * 32 + h * 16);
-    int best[16];
+    for (int r = 0; r < 16; ++r) run[r] = NEG;
+#pragma unroll 1   // one copy of the row body and of the epilogue; conv row k = 0 ... 8 is cy = 2 pyw - 1 + k, patch rows 2 k ... 2 k + 6
+    for (int k = 0; k <= 8; ++k, rb += 2 * SF_ROWB) {
+        const int cy = 2 * pyw - 1 + k;
+        if (cy > Hc) break;
+        int rm[16];
+        if ((unsigned)cy < (unsigned)Hc && !(HAWQ_DBG_BIT(dbg, 32) && k > 0)) {
+            v4i wf[7];   // re-read per conv row (14 KB in all, L1-resident): 28 registers that need not live through the epilogue
 #pragma unroll
-    for (int r = 0; r < 16; ++r) best[r] = (int)0x80000000;
-#pragma unroll 1
-    for (int dy = 0; dy < (HAWQ_DBG_BIT(dbg, 32) ? 1 : 3); ++dy) {  // not unrolled: keeps the 9 window tiles from living at once
-        const int cy = 2 * py + dy - 1;
-#pragma unroll 1
-        for (int dx = 0; dx < 3; ++dx) {
-            const int cx = 2 * px + dx - 1;
-            const bool cvalid = (unsigned)cy < (unsigned)Hc && (unsigned)cx < (unsigned)Wc;
-            v16i acc0;
+            for (int kh = 0; kh < 7; ++kh) wf[kh] = *reinterpret_cast<const v4i *>(wlane + kh * 32);
+            v16i t0, t1;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[r] = 0;
-            const char *wbase = dx == 1 ? pbase8 : pbase + 8 * dx;   // patch bytes [8 dx, 8 dx + 16) of the row segment, 16-byte aligned
+            for (int r = 0; r < 16; ++r) t0[r] = 0, t1[r] = 0;
 #pragma unroll
             for (int kh = 0; kh < 7; ++kh) {
-                const v4i af = *reinterpret_cast<const v4i *>(wbase + ((2 * dy + kh) * SF_PW) * 4);
-                acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[kh], af, acc0, 0, 0, 0);
+                const char *p = rb + kh * SF_ROWB;
+                const v2i e0 = *reinterpret_cast<const v2i *>(p), o0 = *reinterpret_cast<const v2i *>(p + SF_PLANE),
+                          e1 = *reinterpret_cast<const v2i *>(p + 8);
+                const v4i a0 = {e0.x, e0.y, o0.x, o0.y}, a1 = {o0.x, o0.y, e1.x, e1.y};
+                t0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[kh], a0, t0, 0, 0, 0);
+                t1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[kh], a1, t1, 0, 0, 0);
             }
-            // window positions that can fall outside the conv map (max-pool padding = -inf): the top row / left column, and - for
-            // odd conv sizes only - the bottom row / right column of the last pooled pixel
-            if (!interior && (dy == 0 || dx == 0 || (((Hc | Wc) & 1) && (dy == 2 || dx == 2)))) {
+            if (border) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) best[r] = max(best[r], cvalid ? acc0[r] : (int)0x80000000);
-            } else {   // 4 of the 9 positions (ImageNet's even 112 x 112 map) are inside for every pooled pixel: no select
-#pragma unroll
-                for (int r = 0; r < 16; ++r) best[r] = max(best[r], acc0[r]);
+                for (int r = 0; r < 16; ++r) t0[r] = t0_in ? t0[r] : NEG;
             }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) rm[r] = max(max(t0[r], sf_lane_up(t0[r])), t1[r]);
+        } else {   // max-pool padding: -inf
+#pragma unroll
+            for (int r = 0; r < 16; ++r) rm[r] = NEG;
         }
-    }
-    {
-        if (!pvalid || HAWQ_DBG_BIT(dbg, 64)) continue;
-        const int ch = c * 32 + h * 16;
+        if (k & 1) {   // conv row 2 py: the middle row of the open pooled row
+#pragma unroll
+            for (int r = 0; r < 16; ++r) run[r] = max(run[r], rm[r]);
+            continue;
+        }
+        int best[16];   // conv row 2 py + 1 closes pooled row py = pyw + k / 2 - 1 and opens the next one
+#pragma unroll
+        for (int r = 0; r < 16; ++r) best[r] = max(run[r], rm[r]), run[r] = rm[r];
+        const int py = pyw + (k >> 1) - 1;
+        if (k == 0 || py >= Hp || HAWQ_DBG_BIT(dbg, 64)) continue;   // wave-uniform
+        const size_t opix = ((size_t)n * Hp + py) * Wp + px;
         int r16[16], qa[16];
         if (fast) {  // host-proved tie-free tables (hawq_amd.quant_utils.tables_are_fast): fused constants from LDS, 3-instruction requants
             const DyNt dq = dynt_prepare(mq, eq);
@@ -402,7 +428,7 @@ __global__ __launch_bounds__(256, 4) void stem_fused_kernel(
                 }
             }
         }
-        if (res_out) {
+        if (res_out && store_lane) {
             v4i lo, hi;
             lo.x = r16[0] | (r16[1] << 16), lo.y = r16[2] | (r16[3] << 16), lo.z = r16[4] | (r16[5] << 16), lo.w = r16[6] | (r16[7] << 16);
             hi.x = r16[8] | (r16[9] << 16), hi.y = r16[10] | (r16[11] << 16), hi.z = r16[12] | (r16[13] << 16), hi.w = r16[14] | (r16[15] << 16);
@@ -410,7 +436,7 @@ __global__ __launch_bounds__(256, 4) void stem_fused_kernel(
             dst[0] = lo;
             dst[1] = hi;
         }
-        if (out_q) {
+        if (out_q && store_lane) {
             if (out_bits == 8) {
                 v4i w = {(int)pack4_i8(qa[0], qa[1], qa[2], qa[3]), (int)pack4_i8(qa[4], qa[5], qa[6], qa[7]),
                          (int)pack4_i8(qa[8], qa[9], qa[10], qa[11]), (int)pack4_i8(qa[12], qa[13], qa[14], qa[15])};
@@ -421,7 +447,6 @@ __global__ __launch_bounds__(256, 4) void stem_fused_kernel(
             }
         }
     }
-    }  // c
 }
 
 // ------------------------------------------------------------------ 3x3/2 max-pool (+ QuantAct)
@@ -661,7 +686,7 @@ int stem_fused_launch(const float *x, const uint8_t *xu8, const int8_t *lut, int
     HAWQ_REQUIRE(!lut || (reinterpret_cast<size_t>(lut) & 3) == 0, "hawq_stem_fused_u8: lut must be 4-byte aligned");
     const int Hc = (H + 6 - 7) / 2 + 1, Wc = (W + 6 - 7) / 2 + 1;    // conv 7x7 / 2, pad 3
     const int Hp = (Hc + 2 - 3) / 2 + 1, Wp = (Wc + 2 - 3) / 2 + 1;  // max-pool 3x3 / 2, pad 1
-    const long long blocks = (long long)((Wp + 7) / 8) * ((Hp + 7) / 8) * ((N + 1) / 2);
+    const long long blocks = (long long)((Wp + SF_T - 1) / SF_T) * ((Hp + SF_R - 1) / SF_R) * N;
     HAWQ_REQUIRE(blocks < (1ll << 31), "hawq_stem_fused: problem too large");
     const int dbg = HAWQ_DBG_ENV();
     if (xu8)

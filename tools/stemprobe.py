@@ -1,5 +1,6 @@
 """The fused stem launch alone (fp32 and uint8 input), microseconds at the given batches; with the probe library and HAWQ_DBG bits
-(16 = no input loads, 32 = one of three window rows, 64 = no epilogue) it bounds what each phase costs.
+(16 = no input loads, 32 = only the first of a wave's nine conv rows runs its MFMAs and maxima, 64 = no epilogue) it bounds what
+each phase costs.
 usage (GPU box): [HAWQ_LIB=.../libhawq_mi355_ablate.so HAWQ_DBG=16] python tools/stemprobe.py [batch ...]"""
 import sys
 import numpy as np, torch
