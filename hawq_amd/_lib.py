@@ -132,6 +132,8 @@ SIGNATURES = {
     "hawq_incep_conv_tiled": [C.POINTER(IncepConvArgs), i32, vp],
     "hawq_incep_stem_u8": [vp, vp, C.POINTER(IncepConvArgs), vp],
     "hawq_incep_stem_u8_ok": [vp, vp, C.POINTER(IncepConvArgs)],
+    "hawq_incep_stem_f32": [vp, f32, i32, i32, C.POINTER(IncepConvArgs), vp],
+    "hawq_incep_stem_f32_ok": [vp, f32, i32, i32, C.POINTER(IncepConvArgs)],
     "hawq_avgpool3x3_f32": [vp, vp, i32, i32, i32, f32, vp],
     "hawq_incep_requant": [C.POINTER(IncepPoolArgs), vp],
     "hawq_incep_maxpool3s2": [C.POINTER(IncepPoolArgs), vp],

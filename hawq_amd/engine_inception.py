@@ -12,7 +12,8 @@ branches launch one after another on the plan's stream:
 * average-pool branches: ``hawq_incep_avgpool_branch`` (16-bit ``q_input_act``, 3x3 sum, trunc rule, ``q_pool_act``) -> int8,
   then the 1x1 conv as above;
 * max-pool branches: ``hawq_incep_maxpool3s2`` (16-bit ``q_input_act``, max, concat rescale) into the unit buffer.
-Stem: the input QuantAct (``hawq_fakequant_f32`` + ``hawq_f32_nchw_to_q_nhwc``), five convs, two max pools.  Head:
+Stem: the input QuantAct (``hawq_fakequant_f32`` + ``hawq_f32_nchw_to_q_nhwc``; under ``fused_stem`` one launch with conv1),
+five convs, two max pools.  Head:
 ``hawq_incep_global_avgpool`` (8 x 8 trunc rule + ``q_concat_activ``), the classifier as a 1x1 RAW conv and
 ``hawq_acc_nhwc_to_f32_nchw`` (fp32 logits = (acc + bias) * fl(S_w * S_a), quant_modules.py:125-130).
 uint8 images (``forward_uint8``): the same plan and buffers with its first three launches (input QuantAct + conv1) replaced by one
@@ -35,6 +36,15 @@ fast_pools=True)`` issues every one of them that ``hawq_incep_pool_v_ok`` accept
 point instead (``pool_launches``): the vectorised kernels of hawq_amd/csrc/incep_pool.hip on the same argument block, buffers and
 stream, which write the same bytes - launch list and results are unchanged.  The choice is an engine argument, not part of a plan:
 it composes with ``tune`` and ``plan``.
+
+Fused fp32 stem.  ``InceptionEngine(model, fused_stem=True)`` replaces the fp32 plan's first three launches (``hawq_fakequant_f32``,
+``hawq_f32_nchw_to_q_nhwc``, conv1) by one ``hawq_incep_stem_f32`` on ``x_in`` (hawq_amd/csrc/incep_stem_f32.hip), the fp32 twin of the
+uint8 stem kernel: the same bytes in conv1's output buffer, 145 launches instead of 147, and neither the fake-quantised fp32 copy nor
+the 16-channel int8 image is allocated.  A model whose input QuantAct or conv1 the kernel cannot take raises ``PlanNotApplicable``
+(``_stem_refusal``, ``hawq_incep_stem_f32_ok``) - there is no fall-back to the three launches.  ``conv_launches`` keeps conv1's key,
+so plans are interchangeable between engines with and without the option; a fused-stem plan carries conv1's tile id and ignores it,
+as the uint8 plan does, and ``tune=True`` does not time conv1 (its entry records tile 0 and no times).  An engine argument like
+``fast_pools``, composing with it, ``tune``, ``plan`` and ``use_graph``.
 """
 from __future__ import annotations
 
@@ -131,14 +141,16 @@ class _T:
 
 
 class InceptionEngine(GraphRunner):
-    def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False):
+    def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
+                 fused_stem: bool = False):
         self.model, self.use_graph = model, use_graph
-        self.tune, self.plan, self.fast_pools = bool(tune), plan, bool(fast_pools)
+        self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
         self.n_timing_launches = 0           # conv launches issued to time tiles (0 for a default or a replayed plan)
         self.conv_tiles, self.conv_us = None, None
         self.dev = next(model.parameters()).device
         self.stream = None   # created with the first plan: building the engine object needs no device
         self._batch, self._ops, self._ops_u8, self._u8_why = None, [], None, None
+        self._stem_conv = None               # index in ``_convs`` of a conv the fp32 plan does not launch (conv1 under fused_stem)
 
     def _zeros(self, *a, **k):
         """a plan buffer: kept alive with the plan (the captured launches hold its address)"""
@@ -207,7 +219,8 @@ class InceptionEngine(GraphRunner):
             cout_p = Cout
         t = [torch.from_numpy(w).to(self.dev), torch.from_numpy(b).to(self.dev), torch.from_numpy(mp).to(self.dev),
              torch.from_numpy(ekp).to(self.dev)]
-        a.in_, a.wgt, a.bias, a.out = src.buf.data_ptr(), t[0].data_ptr(), t[1].data_ptr(), out.buf.data_ptr()
+        a.in_ = src.buf.data_ptr() if src.buf is not None else None   # None: the fused stem's conv1, which reads x_in
+        a.wgt, a.bias, a.out = t[0].data_ptr(), t[1].data_ptr(), out.buf.data_ptr()
         a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = self.N, src.h, src.w, cin_p, cout_p, KH, KW
         a.stride, a.pad_h, a.pad_w, a.relu = st, ph, pw, 1
         a.m, a.ek, a.q_lo, a.q_hi = t[2].data_ptr(), t[3].data_ptr(), lo, hi
@@ -307,14 +320,20 @@ class InceptionEngine(GraphRunner):
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
         self.x_in = torch.zeros(N, 3, H, W, dtype=torch.float32, device=dev)
-        xq_f = torch.zeros_like(self.x_in)
-        x0 = _T(self._zeros(N * H * W * 16, dtype=torch.int8, device=dev), H, W, 3, 16, s_in, 8)
-        self._keep += [xq_f]
-        self._ops.append(partial(_lib.call, "hawq_fakequant_f32", self.x_in.data_ptr(), xq_f.data_ptr(), self.x_in.numel(), inv,
-                                 1.0, lo, hi, self.stream.cuda_stream))
-        self._ops.append(partial(_lib.call, "hawq_f32_nchw_to_q_nhwc", xq_f.data_ptr(), x0.buf.data_ptr(), N, 3, H, W, 16, 8, 1.0,
-                                 self.stream.cuda_stream))
-        x = x0
+        self._stem_a, self._stem_conv, stem_why = None, None, self._stem_refusal(ib)
+        if self.fused_stem:
+            if stem_why is not None:
+                raise PlanNotApplicable(f"fused_stem: {stem_why}")
+            # conv1's input as the default plan lays it out (that is conv1's launch key); the buffer itself never exists
+            x = _T(None, H, W, 3, 16, s_in, 8)
+        else:
+            xq_f = torch.zeros_like(self.x_in)
+            x = _T(self._zeros(N * H * W * 16, dtype=torch.int8, device=dev), H, W, 3, 16, s_in, 8)
+            self._keep += [xq_f]
+            self._ops.append(partial(_lib.call, "hawq_fakequant_f32", self.x_in.data_ptr(), xq_f.data_ptr(), self.x_in.numel(), inv,
+                                     1.0, lo, hi, self.stream.cuda_stream))
+            self._ops.append(partial(_lib.call, "hawq_f32_nchw_to_q_nhwc", xq_f.data_ptr(), x.buf.data_ptr(), N, 3, H, W, 16, 8,
+                                     1.0, self.stream.cuda_stream))
         for name in ("q_conv1", "q_conv2", "q_conv3", "q_pool1", "q_conv4", "q_conv5", "q_pool2"):
             if name.startswith("q_pool"):
                 h, w = (x.h - 3) // 2 + 1, (x.w - 3) // 2 + 1
@@ -324,8 +343,16 @@ class InceptionEngine(GraphRunner):
             else:
                 x = self._conv(getattr(ib, name), x)
                 if name == "q_conv1":   # the launches up to here are what hawq_incep_stem_u8 replaces
-                    self._conv1, self._n_stem_ops = self._last_conv, len(self._ops)
-        self._ops_u8, self._u8_why = None, self._stem_u8_refusal(ib)
+                    self._conv1 = self._last_conv
+                    if self.fused_stem:   # ... and what hawq_incep_stem_f32 stands for: conv1 keeps its place in `_convs`
+                        a = self._stem_args()
+                        if not _lib.load().hawq_incep_stem_f32_ok(self.x_in.data_ptr(), inv, lo, hi, C.byref(a)):
+                            raise PlanNotApplicable("fused_stem: hawq_incep_stem_f32 refuses conv1")
+                        self._stem_conv = len(self._convs) - 1
+                        self._ops[-1] = partial(_lib.call, "hawq_incep_stem_f32", self.x_in.data_ptr(), inv, lo, hi, C.byref(a),
+                                                self.stream.cuda_stream)
+                    self._n_stem_ops = len(self._ops)
+        self._ops_u8, self._u8_why = None, stem_why
         if x.bits != 16 or x.pitch != x.c:
             raise PlanNotApplicable("the stem output must be 16-bit")
         for uname, unit in q.units():
@@ -381,6 +408,8 @@ class InceptionEngine(GraphRunner):
         return [(self._ops[idx].args[0], op) for idx, _, op in self._pools]
 
     def _tile_ok(self, i, tile):
+        if i == self._stem_conv:   # not launched: its tile id is carried through a plan, never used
+            return True
         return bool(_lib.load().hawq_incep_conv_tile_ok(C.byref(self._convs[i][1]), tile))
 
     def _choose_tiles(self, batch):
@@ -391,8 +420,11 @@ class InceptionEngine(GraphRunner):
             us = [dict(d) for d in self.plan.get("us", [])] or [{} for _ in keys]
         else:
             us = self._time_tiles(T)
-            tiles = [min(d, key=lambda t: (d[t], t)) for d in us]   # tile 0 always competes; ties go to the lower id
-        for (idx, a), t in zip(self._convs, tiles):
+            # tile 0 always competes; ties go to the lower id; a conv that was not timed records tile 0
+            tiles = [min(d, key=lambda t: (d[t], t)) if d else 0 for d in us]
+        for i, ((idx, a), t) in enumerate(zip(self._convs, tiles)):
+            if i == self._stem_conv:
+                continue
             self._ops[idx] = partial(_lib.call, "hawq_incep_conv_tiled", C.byref(a), int(t), self.stream.cuda_stream)
         self.conv_tiles, self.conv_us = [int(t) for t in tiles], us
 
@@ -407,6 +439,9 @@ class InceptionEngine(GraphRunner):
                 self._launch_all()
                 for i, (_, a) in enumerate(self._convs):
                     times = {}
+                    if i == self._stem_conv:   # not launched, not timed
+                        us.append(times)
+                        continue
                     for tile in range(T + 1):
                         if tile and not self._tile_ok(i, tile):
                             continue
@@ -455,8 +490,9 @@ class InceptionEngine(GraphRunner):
         return input_quant_lut(inv, mean, std, lo, hi)
 
     @staticmethod
-    def _stem_u8_refusal(ib):
-        """why ``hawq_incep_stem_u8`` cannot stand for the input QuantAct + conv1 of init block `ib` (None: it can)"""
+    def _stem_refusal(ib):
+        """why a one-launch stem kernel (``hawq_incep_stem_u8``, ``hawq_incep_stem_f32``) cannot stand for the input QuantAct + conv1
+        of init block `ib` (None: it can)"""
         lo, hi = _rng(ib.q_input_activ)
         if ib.q_input_activ.activation_bit != 8 or lo < -128 or hi > 127:
             return "the input QuantAct is not 8-bit with an int8 range"
@@ -468,21 +504,28 @@ class InceptionEngine(GraphRunner):
             return "conv1's output is wider than 8 bits"
         return None
 
+    def _stem_args(self):
+        """conv1 as the one-launch stem kernels take it (one block per plan): `in` NULL, 3 input channels, [Cout][32] weights"""
+        if self._stem_a is None:
+            a1, w_int = self._conv1
+            wt = self._zeros(a1.Cout, 32, dtype=torch.int8, device=self.dev)
+            wt.copy_(torch.from_numpy(pack_stem_u8_weights(w_int, a1.Cout)))
+            a = _lib.IncepConvArgs.from_buffer_copy(a1)   # conv1's bias, tables, clamp, output buffer and pitch
+            a.in_, a.wgt, a.Cin = None, wt.data_ptr(), 3
+            self._keep.append(a)
+            self._stem_a = a
+        return self._stem_a
+
     def _ensure_u8(self, N, H, W):
         """the uint8 plan of the current batch shape: image buffer, table, packed conv1 weights and the launch list"""
         if self._ops_u8 is not None:
             return
         if self._u8_why is not None:
             raise PlanNotApplicable(f"uint8 input: {self._u8_why}")
-        a1, w_int = self._conv1
-        wt = self._zeros(a1.Cout, 32, dtype=torch.int8, device=self.dev)
-        wt.copy_(torch.from_numpy(pack_stem_u8_weights(w_int, a1.Cout)))
         self.x_u8 = self._zeros(N, H, W, 3, dtype=torch.uint8, device=self.dev)
         self.lut_dev = self._zeros(3, 256, dtype=torch.int8, device=self.dev)
         self._lut_key = None
-        a = _lib.IncepConvArgs.from_buffer_copy(a1)   # conv1's bias, tables, clamp, output buffer and pitch
-        a.in_, a.wgt, a.Cin = None, wt.data_ptr(), 3
-        self._keep.append(a)
+        a = self._stem_args()
         if not _lib.load().hawq_incep_stem_u8_ok(self.x_u8.data_ptr(), self.lut_dev.data_ptr(), C.byref(a)):
             raise PlanNotApplicable("uint8 input: hawq_incep_stem_u8 refuses conv1")
         stem = partial(_lib.call, "hawq_incep_stem_u8", self.x_u8.data_ptr(), self.lut_dev.data_ptr(), C.byref(a),

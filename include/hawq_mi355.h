@@ -478,6 +478,17 @@ int hawq_incep_conv_tiled(const hawq_incep_conv_args *a, int tile, void *stream)
  * hawq_incep_stem_u8_ok: 1 when the launch takes this description. */
 int hawq_incep_stem_u8(const uint8_t *x, const int8_t *lut, const hawq_incep_conv_args *conv, void *stream);
 int hawq_incep_stem_u8_ok(const uint8_t *x, const int8_t *lut, const hawq_incep_conv_args *conv);
+/* The same from fp32 images in one launch (incep_stem_f32.hip): Q_InceptInitBlock's q_input_activ (quant_modules.py:271-274, the
+ * input case of quant_utils.py:73-97) and q_conv1 on the fp32 NCHW tensor itself.  It writes, byte for byte, what hawq_fakequant_f32
+ * (scale 1.0) + hawq_f32_nchw_to_q_nhwc (Cpad 16, scale 1.0) + hawq_incep_conv write into conv1's output.
+ * x:    fp32 NCHW [N][3][H][W], H, W >= 3, 4-byte aligned;  q = (int) fminf(fmaxf(rintf(inv_scale * x), in_lo), in_hi) in binary32
+ *       (round half to even; -128 <= in_lo <= in_hi <= 127, inv_scale finite and > 0)
+ * conv: exactly hawq_incep_stem_u8's description: in = NULL, Cin = 3, the [Cout][32] weight rows, REQUANT with out_bits 8.
+ * A workgroup stages 9 input rows x 320 columns of quantised pixels in LDS (each input value is read and quantised once), then one
+ * v_mfma_i32_32x32x32_i8 per 32 pixels x 32 channels.  Other channels of an output row are never touched.
+ * hawq_incep_stem_f32_ok: 1 when the launch takes this description (host arithmetic only; nothing is launched or dereferenced). */
+int hawq_incep_stem_f32(const float *x, float inv_scale, int32_t in_lo, int32_t in_hi, const hawq_incep_conv_args *conv, void *stream);
+int hawq_incep_stem_f32_ok(const float *x, float inv_scale, int32_t in_lo, int32_t in_hi, const hawq_incep_conv_args *conv);
 /* Average pool 3x3 / stride 1 / pad 1 of QuantAveragePool2d (count_include_pad: divisor 9 everywhere) on the fp32 (integer *
  * scale) NCHW tensor of the module path: x_int = rint(x / scale), s = sum of the window, p = trunc(s / 9 + 0.01) computed
  * exactly as (100 s + 9) / 900 in C integer division (truncation toward zero), y = p * scale. */

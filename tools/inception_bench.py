@@ -20,11 +20,19 @@ assertion that the logits are bit-equal, and a table of the 49 pool / requant la
 (HIP events, 2 untimed + 5 timed launches, the median) with the old and the new kernel, the bytes it has to move (input read once +
 output written once, from the shapes) and that byte count over 6.29 TB/s.  ``--skip-pool-table`` leaves the table out (kernel traces).
 
+``--fused-stem`` (alone, or with ``--tune`` / ``--plan FILE`` and / or ``--pools``, which then apply to both engines: the fused-stem
+engine replays the other's conv tiles) compares the default fp32 plan with the same plan under ``fused_stem=True`` (one
+``hawq_incep_stem_f32`` instead of the input QuantAct's two launches + conv1): alternating blocks as above and an assertion that the
+logits are bit-equal.  ``--stem-launches K`` then times, eagerly on the plan's own buffers, the three launches one by one, the three
+together and the one launch, K launches each in two alternating rounds, with the one launch's byte floor (fp32 in + int8 out over
+6.29 TB/s).
+
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --input f32,u8 [--blocks 6] [--stem-launches 0]
     python tools/inception_bench.py --tune [--batches 128] [--blocks 6] [--save-plan plan.json]
     python tools/inception_bench.py --plan plan.json --batches 128
     python tools/inception_bench.py --tune --pools --batches 128,1
+    python tools/inception_bench.py --fused-stem [--tune --pools] --batches 128,1 --stem-launches 20
 """
 import argparse
 import json
@@ -228,6 +236,70 @@ def compare_pools(model, args, b):
     return fast
 
 
+def compare_stems(model, args, b):
+    """the default fp32 plan against the same plan with fused_stem=True, alternating blocks; returns the fused-stem engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    plan = json.load(open(args.plan)) if args.plan else None
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    with torch.no_grad():
+        base = InceptionEngine(model, tune=args.tune and plan is None, plan=plan, fast_pools=args.pools)
+        y0 = base(x)
+        if base.conv_tiles is not None:
+            plan = base.export_plan()   # the fused-stem engine replays the same conv tiles: only the stem differs
+        fused = InceptionEngine(model, plan=plan, fast_pools=args.pools, fused_stem=True)
+        engines = {"three_launch_stem": base, "fused_stem": fused}
+        equal = bool(torch.equal(y0, fused(x)))
+        assert equal, "the logits with fused_stem differ from the default plan's"
+        assert base.conv_launches == fused.conv_launches and fused.n_launches == base.n_launches - 2
+        assert fused.op_names[0] == "hawq_incep_stem_f32"
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": "tuned" if e.conv_tiles is not None else "fixed",
+                              "fast_pools": e.fast_pools, "stem": k, "ms_per_batch": round(mean, 4),
+                              "images_per_s": round(b * 1000.0 / mean, 1), "block_min_ms": round(min(v), 4),
+                              "block_max_ms": round(max(v), 4), "blocks": len(v), "steps": args.steps, "launches": e.n_launches,
+                              "logits_bit_equal": equal}), flush=True)
+        m0, m1 = sum(ms["three_launch_stem"]) / args.blocks, sum(ms["fused_stem"]) / args.blocks
+        print(json.dumps({"workload": wl, "fused_over_default_rate": round(m0 / m1, 4), "gain_ms": round(m0 - m1, 4),
+                          "default_block_spread_ms": round(max(ms["three_launch_stem"]) - min(ms["three_launch_stem"]), 4),
+                          "fused_block_spread_ms": round(max(ms["fused_stem"]) - min(ms["fused_stem"]), 4)}), flush=True)
+        if args.stem_launches:
+            a1 = base._conv1[0]
+            ho, wo = (a1.H - 3) // 2 + 1, (a1.W - 3) // 2 + 1
+            floor_us = (b * 3 * a1.H * a1.W * 4 + b * ho * wo * a1.Cout) / (STREAM_TBS * 1e6)
+            three = base._ops[:base._n_stem_ops]
+            # (name, launches, the engine on whose stream they are issued)
+            groups = [(op.args[0], [op], base) for op in three] + [("three_launches", three, base),
+                                                                   ("hawq_incep_stem_f32", fused._ops[:1], fused)]
+            us = {name: [] for name, _, _ in groups}
+            torch.cuda.synchronize()
+            for _ in range(2):
+                for name, ops, eng in groups:
+                    def run(ops=ops):
+                        for op in ops:
+                            op()
+                    with torch.cuda.stream(eng.stream):
+                        run()
+                        us[name].append(_timed(run, args.stem_launches) * 1000.0 / args.stem_launches)
+            for name, ops, _ in groups:
+                print(json.dumps({"workload": wl, "stem": name, "launches": len(ops), "us_per_call_rounds": [round(v, 2) for v in us[name]],
+                                  "us_per_call": round(min(us[name]), 2)}), flush=True)
+            t3, t1 = min(us["three_launches"]), min(us["hawq_incep_stem_f32"])
+            print(json.dumps({"workload": wl, "stem_f32_us": round(t1, 2), "three_launches_us": round(t3, 2),
+                              "three_over_one": round(t3 / t1, 3), "byte_floor_us": round(floor_us, 2),
+                              "stem_f32_over_floor": round(t1 / floor_us, 2)}), flush=True)
+    return fused
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheme", default="uniform8")
@@ -237,11 +309,13 @@ def main():
     ap.add_argument("--paths", default="fused,module")
     ap.add_argument("--input", default=None, help="f32,u8 (or one of them): compare the fused plan's two inputs instead of --paths")
     ap.add_argument("--blocks", type=int, default=6, help="--input: alternating blocks of --steps forwards per kind")
-    ap.add_argument("--stem-launches", type=int, default=0, help="--input: then issue each stem form K times (for a kernel trace)")
+    ap.add_argument("--stem-launches", type=int, default=0,
+                    help="--input: then issue each stem form K times (for a kernel trace); --fused-stem: time the stem launches, K each")
     ap.add_argument("--tune", action="store_true", help="compare the fixed plan with the plan on tuned conv tiles")
     ap.add_argument("--plan", default=None, help="like --tune, but replay the conv tile plan of this JSON file instead of timing")
     ap.add_argument("--pools", action="store_true", help="compare the old pool kernels with fast_pools=True on one plan")
     ap.add_argument("--skip-pool-table", action="store_true", help="--pools: do not time the 49 pool launches one by one")
+    ap.add_argument("--fused-stem", action="store_true", help="compare the default fp32 plan with fused_stem=True on one plan")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
     if args.save_plan and not (args.tune or args.plan):
@@ -252,8 +326,8 @@ def main():
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.tune or args.plan or args.pools:
-            tuned = (compare_pools if args.pools else compare_plans)(model, args, b)
+        if args.tune or args.plan or args.pools or args.fused_stem:
+            tuned = (compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans)(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
                     json.dump(tuned.export_plan(), f)
