@@ -67,6 +67,14 @@ class IncepConvArgs(C.Structure):
 
 
 INCEP_RAW, INCEP_REQUANT, INCEP_REQUANT2 = 0, 1, 2
+INCEP_GROUP_MAX = 8
+
+
+class IncepGroupArgs(C.Structure):
+    """struct hawq_incep_group_args (include/hawq_mi355.h): the members of one grouped conv launch."""
+    _fields_ = [("n", i32), ("reserved", i32), ("conv", IncepConvArgs * INCEP_GROUP_MAX)]
+
+
 # op ids of hawq_incep_pool_v, by the entry point each one stands for
 INCEP_POOL_OPS = {"hawq_incep_requant": 0, "hawq_incep_maxpool3s2": 1, "hawq_incep_avgpool_branch": 2, "hawq_incep_global_avgpool": 3}
 
@@ -130,6 +138,8 @@ SIGNATURES = {
     "hawq_incep_conv_num_tiles": [],
     "hawq_incep_conv_tile_ok": [C.POINTER(IncepConvArgs), i32],
     "hawq_incep_conv_tiled": [C.POINTER(IncepConvArgs), i32, vp],
+    "hawq_incep_conv_group_ok": [C.POINTER(IncepGroupArgs), i32],
+    "hawq_incep_conv_group": [C.POINTER(IncepGroupArgs), i32, vp],
     "hawq_incep_stem_u8": [vp, vp, C.POINTER(IncepConvArgs), vp],
     "hawq_incep_stem_u8_ok": [vp, vp, C.POINTER(IncepConvArgs)],
     "hawq_incep_stem_f32": [vp, f32, i32, i32, C.POINTER(IncepConvArgs), vp],

@@ -45,6 +45,21 @@ the 16-channel int8 image is allocated.  A model whose input QuantAct or conv1 t
 so plans are interchangeable between engines with and without the option; a fused-stem plan carries conv1's tile id and ignores it,
 as the uint8 plan does, and ``tune=True`` does not time conv1 (its entry records tile 0 and no times).  An engine argument like
 ``fast_pools``, composing with it, ``tune``, ``plan`` and ``use_graph``.
+
+Grouped conv launches.  ``InceptionEngine(model, grouped=True)`` issues the sibling convs at one depth of a unit's branches
+(``conv_levels``) as ONE ``hawq_incep_conv_group`` launch (hawq_amd/csrc/incep_group.hip): members keep their argument blocks, buffers
+and output slices, only the grid is shared, and the launch writes the bytes the single launches write.  A grouped unit issues its
+entry pool / requant launches first (branch-input requants, the average pool, the max-pool branch), then level 1, level 2, ...; the
+inner-concat requant of an 8 x 8 unit follows the level that holds its 1x3 / 3x1 pair.  Every op owns its output buffer, so the order
+across branches is free.  A level of one conv stays a single launch: 27 grouped launches holding 74 convs and 21 single ones instead
+of 95, ``n_launches`` 100 instead of 147.  ``conv_launches`` keeps the default plan's order, so tile plans cross over between engines
+with and without the option.  Which levels are grouped, and on which tile (one id in 1 .. T for a whole group):
+* neither ``tune`` nor ``plan``: every level of two or more convs on tile 3 if ``hawq_incep_conv_group_ok`` takes it, else singles;
+* ``tune=True``: after the per-conv timing every such level is timed on every tile the group accepts (the same method and buffers)
+  and kept with its fastest tile only if that beats the sum of its members' best single times (``group_candidates`` has both);
+* ``plan=``: the ``"groups"`` entries of the plan (``check_groups``), none if it has no such field; no timing launch.
+``export_plan()`` of a grouped engine writes ``"groups"``; an engine without ``grouped`` ignores the field.  ``group_launches`` lists
+(member conv indices, tile) per grouped launch in launch order.  Not the default.
 """
 from __future__ import annotations
 
@@ -106,12 +121,17 @@ def launch_digest(keys):
     return hashlib.sha256(json.dumps([list(map(int, k)) for k in keys], separators=(",", ":")).encode()).hexdigest()
 
 
-def make_plan(batch, keys, num_tiles, tiles, us):
+def make_plan(batch, keys, num_tiles, tiles, us, groups=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
-    and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``)"""
-    return {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
+    and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
+    ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field"""
+    plan = {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
             "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
             "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
+    if groups is not None:
+        plan["groups"] = [{"convs": [int(c) for c in g["convs"]], "tile": int(g["tile"]),
+                           "us": {str(k): round(float(v), 3) for k, v in g.get("us", {}).items()}} for g in groups]
+    return plan
 
 
 def check_plan(plan, batch, keys, num_tiles, ok):
@@ -133,6 +153,56 @@ def check_plan(plan, batch, keys, num_tiles, ok):
     return p_tiles
 
 
+def unit_convs(unit):
+    """the Q_InceptConv modules of a unit in the default plan's launch order (branch by branch), each with (branch, depth): depth d
+    is the conv's place in its branch, from 1; the 1x3 / 3x1 pair of a Q_ConvSeq3x3Branch shares the depth after its last sequential
+    conv; the conv of a pool branch has depth 1"""
+    out = []
+    for bi, br in enumerate(unit.branches.children()):
+        seq = list(br.q_conv_list) if hasattr(br, "q_conv_list") else ([br.q_conv] if hasattr(br, "q_conv") else [])
+        out += [(ic, bi, d + 1) for d, ic in enumerate(seq)]
+        if hasattr(br, "q_conv1x3"):
+            out += [(br.q_conv1x3, bi, len(seq) + 1), (br.q_conv3x1, bi, len(seq) + 1)]
+    return out
+
+
+def conv_levels(unit):
+    """The conv levels of a unit: ``levels[d - 1]`` lists the convs at depth d of their branch as indices into ``unit_convs(unit)``
+    (ascending).  The convs of one level do not depend on each other; each depends on level d - 1 of its own branch only."""
+    levels = []
+    for i, (_, _, d) in enumerate(unit_convs(unit)):
+        while len(levels) < d:
+            levels.append([])
+        levels[d - 1].append(i)
+    return levels
+
+
+def check_groups(groups, n_convs, levels, ok):
+    """The grouped launches ``[(conv indices, tile), ...]`` of a plan's ``"groups"`` field (None: no such field, no group), or
+    StalePlan: an index outside 0 .. n_convs - 1 or named twice, an entry whose convs are not exactly one of `levels` (one level
+    of one unit, as lists of conv indices), or a tile that ``ok(convs, tile)`` refuses."""
+    out, seen, whole = [], set(), {frozenset(lv) for lv in levels}
+    if groups is None:
+        return out
+    try:
+        entries = [(list(g["convs"]), g["tile"]) for g in groups]
+    except (KeyError, TypeError) as exc:
+        raise StalePlan(f"not a list of conv groups: {exc!r}") from exc
+    for convs, tile in entries:
+        for c in convs:
+            if not isinstance(c, int) or isinstance(c, bool) or not 0 <= c < n_convs:
+                raise StalePlan(f"conv group {convs}: no conv launch {c!r}")
+            if c in seen:
+                raise StalePlan(f"conv group {convs}: conv launch {c} is named twice")
+            seen.add(c)
+        if frozenset(convs) not in whole:
+            raise StalePlan(f"conv group {convs} is not one level of one unit")
+        if not isinstance(tile, int) or isinstance(tile, bool) or not ok(convs, tile):
+            raise StalePlan(f"conv group {convs}: tile {tile!r} is refused")
+        out.append((convs, tile))
+    return out
+
+
 class _T:
     """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale."""
 
@@ -142,9 +212,11 @@ class _T:
 
 class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
-                 fused_stem: bool = False):
+                 fused_stem: bool = False, grouped: bool = False):
         self.model, self.use_graph = model, use_graph
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
+        self.grouped = bool(grouped)
+        self.group_launches, self.group_candidates = [], []
         self.n_timing_launches = 0           # conv launches issued to time tiles (0 for a default or a replayed plan)
         self.conv_tiles, self.conv_us = None, None
         self.dev = next(model.parameters()).device
@@ -269,7 +341,7 @@ class InceptionEngine(GraphRunner):
         if cu % 16 or any(x % 16 for x in widths):
             raise PlanNotApplicable("channel counts must be multiples of 16")
         dst = _T(self._zeros(self.N * Ho * Wo * cu, dtype=torch.int16, device=self.dev), Ho, Wo, cu, cu, s_u, 16)
-        off = 0
+        off, op0, conv0, inner_ops = 0, len(self._ops), len(self._convs), []
         for br, wd in zip(branches, widths):
             if isinstance(br, Q_MaxPoolBranch):
                 ia = br.q_input_act
@@ -300,11 +372,16 @@ class InceptionEngine(GraphRunner):
                     self._conv(br.q_conv3x1, x, inner, half, (s_r, ra))
                     self._pool("hawq_incep_requant", inner, dst.buf, 16, cu, off, wd, Ho, Wo,
                                post=(*_scalar_table(s_r, s_u), *_rng(uact)))
+                    inner_ops.append((len(self._ops) - 1, len(self._convs) - 1))   # this requant reads what that conv completes
                 else:
                     for ic in convs[:-1]:
                         x = self._conv(ic, x)
                     self._conv(convs[-1], x, dst, off, (s_u, uact))
             off += wd
+        levels = [[conv0 + i for i in lv] for lv in conv_levels(unit)]
+        if sorted(c for lv in levels for c in lv) != list(range(conv0, len(self._convs))):
+            raise PlanNotApplicable("conv_levels does not describe this unit's conv launches")
+        self._units.append((op0, len(self._ops), levels, inner_ops))
         return dst
 
     # ------------------------------------------------------------------ plan
@@ -315,7 +392,9 @@ class InceptionEngine(GraphRunner):
             self.stream = torch.cuda.Stream(device=self.dev)
         self.N, dev, q = N, self.dev, self.model
         self._ops, self._keep, self.unit_out, self._convs, self._pools = [], [], {}, [], []
+        self._units = []                     # per unit: (first op, end op, conv levels as indices into `_convs`, inner-concat requants)
         self.conv_tiles, self.conv_us = None, None
+        self.group_launches, self.group_candidates = [], []
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
@@ -389,6 +468,8 @@ class InceptionEngine(GraphRunner):
                                  t[2].data_ptr(), self.stream.cuda_stream))
         if self.plan is not None or self.tune:
             self._choose_tiles((N, H, W))
+        if self.grouped:
+            self._schedule_groups(self._choose_groups())
         self._batch = (N, H, W)
 
     # ------------------------------------------------------------------ conv tiles
@@ -457,11 +538,126 @@ class InceptionEngine(GraphRunner):
         torch.cuda.synchronize(self.dev)
         return us
 
+    # ------------------------------------------------------------------ grouped conv launches
+    @property
+    def conv_level_list(self):
+        """every conv level of every unit, in unit order, as lists of indices into ``conv_launches``"""
+        return [lv for _, _, levels, _ in self._units for lv in levels]
+
+    def _group_args(self, convs):
+        """the argument block of one grouped launch: copies of the members' blocks, in the order of `convs`"""
+        g = _lib.IncepGroupArgs()
+        g.n = len(convs)
+        for k, c in enumerate(convs):
+            g.conv[k] = self._convs[c][1]
+        return g
+
+    def _group_ok(self, convs, tile):
+        if not 1 <= len(convs) <= _lib.INCEP_GROUP_MAX or not isinstance(tile, int):
+            return False
+        return bool(_lib.load().hawq_incep_conv_group_ok(C.byref(self._group_args(convs)), tile))
+
+    def _choose_groups(self):
+        """[(member conv indices, tile), ...]: from the plan, from timing (``tune``), or every level of two or more convs on tile 3"""
+        # members with the longest K loop first, so that the heavy workgroups start first (the order is free, and unmeasured)
+        klen = lambda c: -(self._convs[c][1].KH * self._convs[c][1].KW * self._convs[c][1].Cin)   # noqa: E731
+        cands = [sorted(lv, key=klen) for lv in self.conv_level_list if len(lv) >= 2]
+        if self.plan is not None:
+            chosen = check_groups(self.plan.get("groups"), len(self._convs), self.conv_level_list, self._group_ok)
+            us = {tuple(g["convs"]): dict(g.get("us", {})) for g in self.plan.get("groups") or []}
+            self.group_candidates = [{"convs": list(c), "tile": t, "us": us[tuple(c)], "kept": True} for c, t in chosen]
+            return chosen
+        if not self.tune:
+            return [(c, 3) for c in cands if self._group_ok(c, 3)]
+        T = _lib.load().hawq_incep_conv_num_tiles()
+        timed = self._time_groups([(c, [t for t in range(1, T + 1) if self._group_ok(c, t)]) for c in cands])
+        chosen = []
+        for c, us in zip(cands, timed):
+            if not us:
+                continue
+            tile = min(us, key=lambda t: (us[t], t))
+            singles = sum(self.conv_us[i][self.conv_tiles[i]] for i in c)
+            kept = us[tile] < singles
+            self.group_candidates.append({"convs": c, "tile": tile, "us": {**{str(t): v for t, v in us.items()}, "singles": singles},
+                                          "kept": kept})
+            if kept:
+                chosen.append((c, tile))
+        return chosen
+
+    def _time_groups(self, cands):
+        """microseconds of every (group, tile) of `cands` = [(convs, tiles)], as ``_time_tiles`` times a conv: on the plan's buffers,
+        which hold the forward ``_time_tiles`` ran"""
+        sp, n, out = self.stream.cuda_stream, _TUNE_REPS, []
+        with EventTimer(sp, n + 1) as ev:
+            with torch.cuda.stream(self.stream):
+                for convs, tiles in cands:
+                    g, times = self._group_args(convs), {}
+                    for tile in tiles:
+                        for _ in range(_TUNE_WARMUP):
+                            _lib.call("hawq_incep_conv_group", C.byref(g), tile, sp)
+                        ev.record(0)
+                        for r in range(n):
+                            _lib.call("hawq_incep_conv_group", C.byref(g), tile, sp)
+                            ev.record(r + 1)
+                        self.n_timing_launches += _TUNE_WARMUP + n
+                        times[tile] = sorted(ev.ms(r, r + 1) * 1000.0 for r in range(n))[n // 2]
+                    out.append(times)
+        torch.cuda.synchronize(self.dev)
+        return out
+
+    def _schedule_groups(self, groups):
+        """Re-issue the units' launches in the grouped order (entry pools / requants, then level by level, an inner-concat requant
+        after the level of its pair) with every group of `groups` as one ``hawq_incep_conv_group`` launch at the place of its
+        level; ``_convs`` / ``_pools`` follow their launches (the members of a group share its index)."""
+        sp, old, new, at = self.stream.cuda_stream, self._ops, [], {}
+        op_of = {c: idx for c, (idx, _) in enumerate(self._convs)}
+        group_of = {c: gi for gi, (convs, _) in enumerate(groups) for c in convs}
+        self.group_launches, done = [], 0
+
+        def emit(idx):
+            at[idx] = len(new)
+            new.append(old[idx])
+
+        for op0, op1, levels, inner_ops in self._units:
+            for idx in range(done, op0):
+                emit(idx)
+            later = {op_of[c] for lv in levels for c in lv} | {idx for idx, _ in inner_ops}
+            for idx in range(op0, op1):   # what a branch does before its first conv
+                if idx not in later:
+                    emit(idx)
+            for lv in levels:
+                issued = set()
+                for c in lv:
+                    gi = group_of.get(c)
+                    if gi is None:
+                        emit(op_of[c])
+                    elif gi not in issued:
+                        issued.add(gi)
+                        convs, tile = groups[gi]
+                        g = self._group_args(convs)
+                        self._keep.append(g)
+                        for m in convs:
+                            at[op_of[m]] = len(new)
+                        new.append(partial(_lib.call, "hawq_incep_conv_group", C.byref(g), int(tile), sp))
+                        self.group_launches.append((list(convs), int(tile)))
+                for idx, c in inner_ops:
+                    if c in lv:
+                        emit(idx)
+            done = op1
+        for idx in range(done, len(old)):
+            emit(idx)
+        self._ops = new
+        self._convs = [(at[idx], a) for idx, a in self._convs]
+        self._pools = [(at[idx], a, op) for idx, a, op in self._pools]
+
     def export_plan(self):
-        """The conv tile choice of the current batch shape as a JSON-serialisable dict (``make_plan``), for ``plan=``."""
+        """The conv tile choice of the current batch shape (and, of a grouped engine, its grouped launches) as a JSON-serialisable
+        dict (``make_plan``), for ``plan=``."""
         if self.conv_tiles is None:
             raise RuntimeError("export_plan: no tuned plan (build the engine with tune=True or plan=... and run a forward first)")
-        return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us)
+        groups = [g for g in self.group_candidates if g["kept"]] if self.grouped else None
+        return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
+                         groups)
 
     def _launch_chain(self, u8):
         for op in (self._ops_u8 if u8 else self._ops):

@@ -467,6 +467,25 @@ int hawq_incep_conv(const hawq_incep_conv_args *a, void *stream);
 int hawq_incep_conv_num_tiles(void);
 int hawq_incep_conv_tile_ok(const hawq_incep_conv_args *a, int tile);
 int hawq_incep_conv_tiled(const hawq_incep_conv_args *a, int tile, void *stream);
+/* Grouped launch of the tiled kernels (incep_group.hip): up to HAWQ_INCEP_GROUP_MAX independent convs - the sibling convs at one depth
+ * of an Inception unit's branches - in ONE launch.  Members keep their own argument blocks and may differ in everything a block holds;
+ * only the grid is shared: a 1-D grid in which member i owns ceil(P_i / BM) * ceil(Cout_i / BN) consecutive workgroups of tile `tile`
+ * (one id in 1 .. hawq_incep_conv_num_tiles() for the whole group).  Each workgroup runs the tiled kernel's own body on its member.
+ *   hawq_incep_conv_group:     writes, byte for byte, what hawq_incep_conv_tiled(&g->conv[i], tile, stream) for i = 0 .. n - 1 write.
+ *   hawq_incep_conv_group_ok:  1 if the launch takes this group.  Host arithmetic only: nothing is dereferenced or launched, no device
+ *       is needed.  0 for n outside 1 .. 8, a tile outside 1 .. T, a member hawq_incep_conv_tile_ok(member, tile) refuses, 2^31 or more
+ *       workgroups in all, and for members that are not independent: two that write intersecting channel intervals
+ *       [c_off, c_off + Cout) of one buffer (same out, ldo, element width) or intersecting byte extents of different buffers, or one
+ *       whose input bytes intersect any member's output bytes.
+ * A refused group makes hawq_incep_conv_group return non-zero (the reason in hawq_last_error()), launch nothing and write no byte.
+ * conv[n .. 7] are ignored. */
+#define HAWQ_INCEP_GROUP_MAX 8
+typedef struct hawq_incep_group_args {
+    int32_t n, reserved;
+    hawq_incep_conv_args conv[HAWQ_INCEP_GROUP_MAX];
+} hawq_incep_group_args;
+int hawq_incep_conv_group_ok(const hawq_incep_group_args *g, int tile);
+int hawq_incep_conv_group(const hawq_incep_group_args *g, int tile, void *stream);
 /* InceptionV3's input QuantAct + Conv2d_1a_3x3 from uint8 images in one launch (incep_stem.hip): Q_InceptInitBlock's q_input_activ and
  * q_conv1 (q_inceptionv3.py of the reference) on the tensor that ToTensor + Normalize (quant_train.py:432-440) make of the image, with
  * the QuantAct as a table look-up (quant_modules.py:271-274; lut int8 [3][256] from hawq_amd.quant_utils.input_quant_lut).

@@ -27,12 +27,18 @@ logits are bit-equal.  ``--stem-launches K`` then times, eagerly on the plan's o
 together and the one launch, K launches each in two alternating rounds, with the one launch's byte floor (fp32 in + int8 out over
 6.29 TB/s).
 
+``--grouped`` compares, on one tuned conv tile plan with ``fast_pools=True, fused_stem=True``, the plan without and with grouped conv
+launches (``grouped=True``, tuned: the grouped engine times tiles and groups, the other engine replays its tile plan and ignores the
+groups): alternating blocks as above, an assertion that the logits are bit-equal, the launch counts, and a table of the candidate
+groups - member conv launches, fastest tile, its microseconds, the sum of the members' best single microseconds, kept or not.
+
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --input f32,u8 [--blocks 6] [--stem-launches 0]
     python tools/inception_bench.py --tune [--batches 128] [--blocks 6] [--save-plan plan.json]
     python tools/inception_bench.py --plan plan.json --batches 128
     python tools/inception_bench.py --tune --pools --batches 128,1
     python tools/inception_bench.py --fused-stem [--tune --pools] --batches 128,1 --stem-launches 20
+    python tools/inception_bench.py --grouped --batches 1,16,128 [--blocks 6]
 """
 import argparse
 import json
@@ -300,6 +306,55 @@ def compare_stems(model, args, b):
     return fused
 
 
+def compare_grouped(model, args, b):
+    """one tuned tile plan (fast pools, fused stem) without and with grouped conv launches, alternating blocks; returns the grouped
+    engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    with torch.no_grad():
+        grouped = InceptionEngine(model, tune=True, fast_pools=True, fused_stem=True, grouped=True)
+        y1 = grouped(x)
+        single = InceptionEngine(model, plan=grouped.export_plan(), fast_pools=True, fused_stem=True)   # the same tiles, no groups
+        engines = {"single": single, "grouped": grouped}
+        equal = bool(torch.equal(single(x), y1))
+        assert equal, "the logits with grouped launches differ from the single launches'"
+        assert single.conv_tiles == grouped.conv_tiles and not single.group_launches
+        print(f"# {wl}: group | member conv launches (Cout KHxKW each) | fastest tile | group us | sum of members' best single us | kept")
+        for i, g in enumerate(grouped.group_candidates):
+            keys = [grouped.conv_launches[c] for c in g["convs"]]
+            print(f"# {i:2d} | " + " ".join(f"{c}({k[3]} {k[4]}x{k[5]})" for c, k in zip(g["convs"], keys)) +
+                  f" | {g['tile']} | {g['us'][str(g['tile'])]:.1f} | {g['us']['singles']:.1f} | {'kept' if g['kept'] else 'singles'}")
+        kept = [g for g in grouped.group_candidates if g["kept"]]
+        print(json.dumps({"workload": wl, "launches_single": single.n_launches, "launches_grouped": grouped.n_launches,
+                          "conv_launches_single": len(single.conv_launches) - 1,
+                          "conv_launches_grouped": len(grouped.conv_launches) - 1 - sum(len(g["convs"]) - 1 for g in kept),
+                          "groups_kept": len(kept), "groups_rejected": len(grouped.group_candidates) - len(kept),
+                          "kept_group_us_sum": round(sum(g["us"][str(g["tile"])] for g in kept), 1),
+                          "kept_members_single_us_sum": round(sum(g["us"]["singles"] for g in kept), 1),
+                          "tiles_of_kept_groups": {str(t): [g["tile"] for g in kept].count(t) for t in sorted({g["tile"] for g in kept})}}),
+              flush=True)
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": "tuned", "fast_pools": True, "fused_stem": True, "convs": k,
+                              "ms_per_batch": round(mean, 4), "images_per_s": round(b * 1000.0 / mean, 1),
+                              "block_min_ms": round(min(v), 4), "block_max_ms": round(max(v), 4), "blocks": len(v),
+                              "steps": args.steps, "launches": e.n_launches, "logits_bit_equal": equal}), flush=True)
+        m0, m1 = sum(ms["single"]) / args.blocks, sum(ms["grouped"]) / args.blocks
+        print(json.dumps({"workload": wl, "grouped_over_single_rate": round(m0 / m1, 4), "gain_ms": round(m0 - m1, 4),
+                          "single_block_spread_ms": round(max(ms["single"]) - min(ms["single"]), 4),
+                          "grouped_block_spread_ms": round(max(ms["grouped"]) - min(ms["grouped"]), 4)}), flush=True)
+    return grouped
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheme", default="uniform8")
@@ -316,18 +371,21 @@ def main():
     ap.add_argument("--pools", action="store_true", help="compare the old pool kernels with fast_pools=True on one plan")
     ap.add_argument("--skip-pool-table", action="store_true", help="--pools: do not time the 49 pool launches one by one")
     ap.add_argument("--fused-stem", action="store_true", help="compare the default fp32 plan with fused_stem=True on one plan")
-    ap.add_argument("--save-plan", default=None, help="--tune / --plan: write export_plan() of the last batch size to this file")
+    ap.add_argument("--grouped", action="store_true",
+                    help="compare one tuned plan (fast pools, fused stem) without and with grouped conv launches")
+    ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
-    if args.save_plan and not (args.tune or args.plan):
-        ap.error("--save-plan needs --tune or --plan: there is no conv tile plan to save otherwise")
+    if args.save_plan and not (args.tune or args.plan or args.grouped):
+        ap.error("--save-plan needs --tune, --plan or --grouped: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
     for b in (int(v) for v in args.batches.split(",")):
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.tune or args.plan or args.pools or args.fused_stem:
-            tuned = (compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans)(model, args, b)
+        if args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
+            compare = compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
+            tuned = compare(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
                     json.dump(tuned.export_plan(), f)
