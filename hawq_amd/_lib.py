@@ -38,6 +38,7 @@ class ConvArgs(C.Structure):
         ("res_no_relu", i32), ("res_clamp16", i32),
         ("in_pitch", i32), ("out_pitch", i32),
         ("wgt_band", vp), ("wgt_k128", vp), ("wgt2_k128", vp),
+        ("out_sub", i32),
     ]
 
 

@@ -52,6 +52,8 @@ struct ConvP {
     int in_planar, out_planar;  // activation layout of in / out_q: 0 = NHWC rows, 1 = channel-group planes (hawq_mi355.h)
     int gfast;                  // general (direct) RESIDUAL epilogue with the fast contract's arithmetic: 32-bit / signed residuals whose tables the host has proved
     int in_pitch, out_pitch;    // bytes per pixel row of `in` / channels per pixel row of out_q, res_out, res_in (hawq_conv_args, ABI 4; always > 0 here)
+    int res_sub;                // hawq_conv_args.out_sub = s >= 2 (else 0): the launch is a 1x1 conv of stride s (Ho, Wo, M are the subsampled grid's) and
+                                // res_in, a tensor of the H x W source map, is read at pixel (n, s oy, s ox) of it
     int dbg;  // HAWQ_DBG ablation bits (timing experiments only): 1 = skip operand loads, 2 = skip MFMAs
     long long *dbgbuf;  // HAWQ_DBG & 128: per-phase cycle sums of workgroup 0 / wave 0 (band kernel)
 };
@@ -481,6 +483,15 @@ __device__ __forceinline__ void run_segment(v16i (&acc)[C::CT][C::PT], const uin
 
 __device__ __forceinline__ v4i ld4(const int32_t *p) { return *reinterpret_cast<const v4i *>(p); }
 
+// pixel row of res_in that output pixel `pix` (< M) adds: its own, or with out_sub its source pixel on the H x W map
+__device__ __forceinline__ size_t res_row(const ConvP &p, int pix) {
+    if (p.res_sub > 1) {
+        const int hw = p.Ho * p.Wo, n = pix / hw, r = pix - n * hw, oy = r / p.Wo, ox = r - oy * p.Wo;
+        return ((size_t)n * p.H + (size_t)oy * p.res_sub) * p.W + (size_t)ox * p.res_sub;
+    }
+    return (size_t)pix;
+}
+
 
 // =============================================================== exact general epilogue (BITS == 0)
 // Direct per-lane global accesses, dyadic_rne everywhere: any e in [1,62], any pre-shift, ties
@@ -491,6 +502,12 @@ __device__ __forceinline__ void epilogue_generic(const ConvP &p, v16i (&acc)[C::
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wave_m = wave % C::WM, wave_c = wave / C::WM;
     const int l31 = lane & 31, h = lane >> 5;
+    size_t rrow[C::PT];   // pixel row of res_in per pixel tile (out_sub: the source pixel), worked out once, outside the unrolled epilogue
+#pragma unroll
+    for (int q = 0; q < C::PT; ++q) {
+        const int pix = m0 + wave_m * (C::PT * 32) + q * 32 + l31;
+        rrow[q] = (EPI == HAWQ_EPI_RESIDUAL && !DUAL) ? res_row(p, pix < p.M ? pix : 0) : (size_t)pix;
+    }
 #pragma unroll
     for (int c = 0; c < C::CT; ++c) {
         const int ch = c0 + wave_c * (C::CT * 32) + c * 32 + h * 16;
@@ -502,6 +519,7 @@ __device__ __forceinline__ void epilogue_generic(const ConvP &p, v16i (&acc)[C::
             constexpr bool PITCHED = EPI == HAWQ_EPI_REQUANT || EPI == HAWQ_EPI_RESIDUAL;
             const int opitch = PITCHED ? p.out_pitch : p.Cout;
             const size_t elem = (size_t)pix * opitch + ch;
+            const size_t relem = rrow[q] * opitch + ch;   // (res_in rows: out_sub)
             bool ovf = false;
             int qw[4] = {0, 0, 0, 0};   // int8 output: the lane's 16 channels leave as ONE 16-byte store after the loop
 #pragma unroll
@@ -545,8 +563,8 @@ __device__ __forceinline__ void epilogue_generic(const ConvP &p, v16i (&acc)[C::
                         const int av = acc[c][q][4 * g + j];
                         int ov = tie ? dyadic_tie(av, dm) : dyadic_nt(av, dm);
                         if (p.res_in) {
-                            const int r = p.res_in_bits == 16 ? (int)((const uint16_t *)p.res_in)[elem + 4 * g + j]
-                                                              : ((const int32_t *)p.res_in)[elem + 4 * g + j];
+                            const int r = p.res_in_bits == 16 ? (int)((const uint16_t *)p.res_in)[relem + 4 * g + j]
+                                                              : ((const int32_t *)p.res_in)[relem + 4 * g + j];
                             ov += tie ? dyadic_tie(r, dids) : dyadic_nt(r, dids);
                         }
                         if (!p.res_no_relu) ov = max(ov, 0);
@@ -592,8 +610,8 @@ __device__ __forceinline__ void epilogue_generic(const ConvP &p, v16i (&acc)[C::
                         } else if (p.res_in) {
 #pragma unroll
                             for (int j = 0; j < 4; ++j) {
-                                const int r = p.res_in_bits == 16 ? (int)((const uint16_t *)p.res_in)[elem + 4 * g + j]
-                                                                  : ((const int32_t *)p.res_in)[elem + 4 * g + j];
+                                const int r = p.res_in_bits == 16 ? (int)((const uint16_t *)p.res_in)[relem + 4 * g + j]
+                                                                  : ((const int32_t *)p.res_in)[relem + 4 * g + j];
                                 idv[j] = dyadic_rne(r, p.m_id_s, p.e_id_s);
                             }
                         } else {   // no identity branch (MobileNetV2 units that change shape): fixedpoint_fn case 0
@@ -672,8 +690,8 @@ __device__ __forceinline__ void prefetch_residual(const ConvP &p, int m0, int c0
         if (base >= C::BM * S::RCPR) break;   // (16-wave workgroups on a 64-pixel tile: half of the waves have no piece)
         const int idx = base + lane;
         const int row = idx / S::RCPR, j = idx % S::RCPR;
-        const int grow = (m0 + row < p.M) ? m0 + row : m0;
-        const char *src = (const char *)p.res_in + ((size_t)grow * p.Cout + c0) * 2 + ((j ^ S::rsw(row)) << 4);
+        const size_t grow = res_row(p, (m0 + row < p.M) ? m0 + row : m0);
+        const char *src = (const char *)p.res_in + (grow * p.Cout + c0) * 2 + ((j ^ S::rsw(row)) << 4);
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                          (__attribute__((address_space(3))) void *)(res_tile + base * 16), 16, 0, 0);
     }
@@ -1360,7 +1378,7 @@ bool band_applies(const BandInfo &bi, const hawq_conv_args *a) {
     const bool epi_ok = (a->epilogue == HAWQ_EPI_REQUANT && a->out_q) ||
                         (res && a->res_in && a->res_in_bits == 16 && (!a->res_out || a->res_out_bits == 16));
     const bool dense = (a->in_pitch == 0 || a->in_pitch == a->Cin * a->in_bits / 8) && (a->out_pitch == 0 || a->out_pitch == a->Cout);
-    return a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->in2 == nullptr && a->fast_tables != 0 && epi_ok && dense &&
+    return a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->out_sub < 2 && a->in2 == nullptr && a->fast_tables != 0 && epi_ok && dense &&
            ((a->in_bits == 8 && a->w_bits == 8) || (nib && a->Cin % 128 == 0)) && a->Cout % bi.bn == 0 &&
            band_rows * (wo + 2) <= bi.band_px - 4 && (bi.bstages > 1 || (a->Cin >> (nib ? 7 : 6)) == 1);
 }
@@ -1501,17 +1519,24 @@ extern "C" int hawq_conv2d(const hawq_conv_args *a, void *stream) {
                  "hawq_conv2d: in_bits/w_bits must be 4 or 8 (got %d/%d)", a->in_bits, a->w_bits);
     HAWQ_REQUIRE(a->KH > 0 && a->KW > 0 && a->stride > 0 && a->pad >= 0 && a->N > 0 && a->H > 0 && a->W > 0,
                  "hawq_conv2d: bad geometry");
+    // out_sub = s >= 2: only the output pixels (n, s y', s x') of a 1x1 / stride 1 / pad 0 launch, stored densely - the 1x1 conv of stride s
+    // on `in`, with res_in read at the same source pixels (ConvP.res_sub)
+    const int sub = a->out_sub >= 2 ? a->out_sub : 1;
+    HAWQ_REQUIRE(sub == 1 || (a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad == 0 && !a->in2 && !a->res_out && a->epilogue == HAWQ_EPI_RESIDUAL &&
+                              !a->in_planar && !a->out_planar && a->in_pitch == 0 && a->out_pitch == 0),
+                 "hawq_conv2d: out_sub=%d needs a 1x1 / stride 1 / pad 0 single-branch RESIDUAL launch without res_out, dense NHWC rows", a->out_sub);
     ConvP p;
     p.in = (const uint8_t *)a->in;
     p.wgt = (const uint8_t *)a->wgt;
     p.bias = a->bias;
     p.N = a->N, p.H = a->H, p.W = a->W, p.Cin = a->Cin, p.Cout = a->Cout;
-    p.KH = a->KH, p.KW = a->KW, p.stride = a->stride, p.pad = a->pad;
-    p.Ho = (a->H + 2 * a->pad - a->KH) / a->stride + 1;
-    p.Wo = (a->W + 2 * a->pad - a->KW) / a->stride + 1;
+    p.KH = a->KH, p.KW = a->KW, p.stride = a->stride * sub, p.pad = a->pad;
+    p.res_sub = sub > 1 ? sub : 0;
+    p.Ho = (a->H + 2 * a->pad - a->KH) / p.stride + 1;
+    p.Wo = (a->W + 2 * a->pad - a->KW) / p.stride + 1;
     HAWQ_REQUIRE(p.Ho > 0 && p.Wo > 0, "hawq_conv2d: empty output");
     const long long M = (long long)a->N * p.Ho * p.Wo;
-    HAWQ_REQUIRE(M * (long long)a->Cout < (1ll << 40) && M < (1ll << 30), "hawq_conv2d: problem too large");
+    HAWQ_REQUIRE(M * (long long)a->Cout < (1ll << 40) && M < (1ll << 30) && (long long)a->N * a->H * a->W < (1ll << 30), "hawq_conv2d: problem too large");
     p.M = (int)M;
     p.in_bits = a->in_bits, p.w_bits = a->w_bits;
     const bool dual = a->in2 != nullptr;

@@ -43,6 +43,9 @@ struct WPP {
     int m_id_s, e_id_s, mq, eq, q_hi;
     int y_lo, y_hi, y_planar, y_nib;   // y_nib: the reduce conv's output is stored hawq4 (two 4-bit channels per byte)
     int spb;             // slices per workgroup along gridDim.y (REDUCE: all of them)
+    // !REDUCE, hawq_conv_args.out_sub = s >= 2: M counts the pixels (n, y', x') of the subsampled grid [N][dHW / dW][dW] - q_out is dense over
+    // them -, x2 and res_in are read at pixel (n, s y', s x') of the source map [N][sHW / sW][sW].  sub <= 1: the grids are the same
+    int sub, sW, sHW, dW, dHW;
     int32_t *flags;
     long long *dbgbuf;   // probe builds (HAWQ_ABLATE, HAWQ_DBG=128): per-phase cycle sums of wave 0 of workgroup 8
 };
@@ -109,6 +112,27 @@ __global__ __launch_bounds__(F::NT, F::MINW) void expand_wp_kernel(const WPP p) 
     const int nsl = p.C3 >> 6;
     const int j0 = blockIdx.y * p.spb, j1 = (j0 + p.spb < nsl) ? j0 + p.spb : nsl;
     char *ct = smem + F::OFF_CT;
+    const int pix0 = blockIdx.x * F::BM + wave * 32;
+    // row of x2 / res_in that output pixel d reads; rows beyond M clamp to the last one's (read, never stored)
+    auto srow = [&](int d) -> unsigned {
+        d = d < p.M ? d : p.M - 1;
+        if constexpr (!F::REDUCE) {
+            if (p.sub > 1) {
+                const int n = d / p.dHW, r = d - n * p.dHW, y = r / p.dW, x = r - y * p.dW;
+                return (unsigned)(n * p.sHW + (y * p.sW + x) * p.sub);
+            }
+        }
+        return (unsigned)d;
+    };
+    // ... worked out here, once and ahead of everything else, for the rows this lane touches: rsrc[k] = row 8k + lane / 8 of the wave's tile
+    // (residual DMA, row stores), xsrc[k] = row 16k + lane / 4 (x2 fragment DMA).  The prologue below stays the straight line it was,
+    // and the slice loop's instruction count (tools/epilogue_census.py) is the one it had before the map existed
+    unsigned rsrc[4], xsrc[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rsrc[k] = srow(pix0 + 8 * k + (lane >> 3));
+#pragma unroll
+    for (int k = 0; k < 2; ++k) xsrc[k] = srow(pix0 + 16 * k + (lane >> 2));
+    asm volatile("" : "+v"(rsrc[0]), "+v"(rsrc[1]), "+v"(rsrc[2]), "+v"(rsrc[3]), "+v"(xsrc[0]), "+v"(xsrc[1]));
     // ---------------------------------------------------------------- LDS-DMA: every wave issues its 16 rows of each pass
     const int prow = t >> 2, pslot = t & 3;
     const int sw = (pslot ^ ((prow >> 2) & 3)) << 4;     // source-side swizzle (same for rows prow + k * RPP)
@@ -134,15 +158,15 @@ __global__ __launch_bounds__(F::NT, F::MINW) void expand_wp_kernel(const WPP p) 
     // physical slot = logical slot ^ (row & 7).  Coalesced side (LDS-DMA in, row stores out): instruction k covers rows
     // 8k .. 8k+7, lane -> (row 8k + lane / 8, physical slot lane % 8).  Lane-per-pixel side: row l31, logical slots 4t + 2h + {0, 1}
     char *stg = smem + F::OFF_STG + wave * 4096;
-    const int pix0 = blockIdx.x * F::BM + wave * 32;
     const int crow = lane >> 3, cslot = lane & 7;
     // byte offset of (row 8k + crow, physical slot cslot) in a [M][C3] uint16 tensor, slice 0: shared by the residual DMA and the
-    // row stores; 32-bit (the launcher refuses tensors of 4 GiB and more), rows beyond M clamp to the last row (never stored)
+    // row stores; 32-bit (the launcher refuses source tensors of 4 GiB and more), rows beyond M clamp to the last row (never stored).
+    // With out_sub these are rows of the SOURCE map: only the residual DMA uses them then (the launcher refuses res_out)
     unsigned coff[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int r = 8 * k + crow;
-        coff[k] = (unsigned)((pix0 + r < p.M) ? pix0 + r : p.M - 1) * (unsigned)(p.C3 * 2) + ((cslot ^ (r & 7)) << 4);
+        coff[k] = rsrc[k] * (unsigned)(p.C3 * 2) + ((cslot ^ (r & 7)) << 4);
     }
     auto dma_res = [&](int j) {
 #pragma unroll
@@ -161,7 +185,7 @@ __global__ __launch_bounds__(F::NT, F::MINW) void expand_wp_kernel(const WPP p) 
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const int r = 16 * k + r2;
-                    const size_t gr = (pix0 + r < p.M) ? pix0 + r : p.M - 1;
+                    const size_t gr = xsrc[k];
                     wp_dma16((const char *)p.x2 + gr * C + kc * 64 + ((s2 ^ ((r >> 2) & 3)) << 4), stg + (kc - kc0) * 2048 + k * 1024);
                 }
             wait_vmcnt<0>();
@@ -404,7 +428,8 @@ constexpr int NUM_WP = sizeof(kWP) / sizeof(kWP[0]);
 bool wp_expand_ok(const hawq_conv_args &e) {
     return (e.in_pitch == 0 || e.in_pitch == e.Cin) && (e.out_pitch == 0 || e.out_pitch == e.Cout) && e.KH == 1 && e.KW == 1 && e.stride == 1 && e.pad == 0 && e.in_bits == 8 && e.w_bits == 8 && e.fast_tables != 0 && !e.in2 &&
            !e.in_planar && e.epilogue == HAWQ_EPI_RESIDUAL && e.res_in && e.res_in_bits == 16 && (!e.res_out || e.res_out_bits == 16) &&
-           e.flags && e.ctab && e.Cout % 64 == 0 && (e.out_bits == 8 || (e.out_bits == 4 && e.q_lo >= 0 && e.q_hi <= 15));   // (4: the expand conv alone writing a hawq4 block input)
+           e.flags && e.ctab && e.Cout % 64 == 0 && (e.out_bits == 8 || (e.out_bits == 4 && e.q_lo >= 0 && e.q_hi <= 15)) &&   // (4: the expand conv alone writing a hawq4 block input)
+           (e.out_sub < 2 || !e.res_out);   // a subsampled launch has no dense residual to write (hawq_conv_args.out_sub)
 }
 
 // index into kWP of the nth (1-based) variant that takes this launch, or -1
@@ -413,6 +438,7 @@ int wp_variant(const hawq_expand_reduce_args *a, int nth) {
     if (!wp_expand_ok(e)) return -1;
     const bool reduce = r.wgt != nullptr;
     if (reduce && e.out_bits != 8) return -1;   // (a fused pair keeps the block input on chip: its storage width is moot, the caller says 8)
+    if (reduce && (e.out_sub >= 2 || r.out_sub >= 2)) return -1;   // only the expand conv alone subsamples its output grid
     if (reduce) {
         if (!(r.KH == 1 && r.KW == 1 && r.stride == 1 && r.pad == 0 && r.in_bits == 8 && r.w_bits == 8 && r.fast_tables != 0 && !r.in2)) return -1;
         if (r.epilogue != HAWQ_EPI_REQUANT || !r.ctab || !r.out_q || (r.out_bits != 8 && r.out_bits != 4) || !e.res_out) return -1;
@@ -449,9 +475,12 @@ int wp_launch(const hawq_expand_reduce_args *a, int nth, void *stream) {
     p.y = wi.reduce ? (uint8_t *)r.out_q : nullptr;
     p.q_out = wi.reduce ? nullptr : (uint8_t *)e.out_q;
     p.q_nib = !wi.reduce && e.out_bits == 4;
-    const long long M = (long long)e.N * e.H * e.W;
-    HAWQ_REQUIRE(M > 0 && M * e.Cout * 2 < (1ll << 32), "hawq_conv_expand_reduce: bad problem size");
+    // out_sub: the grid, q_out and every store run over the subsampled pixels; the 32-bit row offsets address the source map
+    const int sub = e.out_sub >= 2 ? e.out_sub : 1, hd = (e.H - 1) / sub + 1, wd = (e.W - 1) / sub + 1;
+    const long long Msrc = (long long)e.N * e.H * e.W, M = (long long)e.N * hd * wd;
+    HAWQ_REQUIRE(M > 0 && Msrc * e.Cout * 2 < (1ll << 32), "hawq_conv_expand_reduce: bad problem size");
     p.M = (int)M, p.C3 = e.Cout;
+    p.sub = sub, p.sW = e.W, p.sHW = e.H * e.W, p.dW = wd, p.dHW = hd * wd;
     p.m_id_s = e.m_id_scalar, p.e_id_s = e.e_id_scalar, p.mq = e.mq, p.eq = e.eq, p.q_hi = e.q_hi;
     p.y_lo = wi.reduce ? (r.relu && r.q_lo < 0 ? 0 : r.q_lo) : 0, p.y_hi = wi.reduce ? r.q_hi : 0;
     p.y_planar = wi.reduce ? r.out_planar : 0;

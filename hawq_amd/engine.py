@@ -36,6 +36,26 @@ RES_VBITS = 20  # residual / pooled values are 16-bit-ish (uint16 storage satura
 U16_VBITS = 17  # tie-freeness proofs for values that live in uint16 residual tensors (< 2^16 unless flagged)
 
 
+def out_sub_stride(readers) -> int:
+    """Stride s > 1 of the grid on which the block input of a resize unit is read, 0 if some reader needs every pixel.
+    `readers`: (kh, kw, stride, pad) of every conv that reads that block input (the unit's first conv and its identity conv).
+    All of them 1x1 / pad 0 with one common stride s > 1 (the first unit of stages 2-4 of resnet50 / resnet101, whose stride sits
+    on conv1: q_resnet.py:236-240): pixel (y, x) of the block input is read only for y % s == x % s == 0, so the launch that
+    writes it may evaluate those pixels alone (hawq_conv_args.out_sub)."""
+    readers = list(readers)
+    if not readers:
+        return 0
+    s = readers[0][2]
+    if s <= 1 or any((kh, kw, st, pad) != (1, 1, s, 0) for kh, kw, st, pad in readers):
+        return 0
+    return int(s)
+
+
+def out_sub_extent(n: int, s: int) -> int:
+    """Rows (columns) 0, s, 2 s, ... of a map with n of them: what a 1x1 / pad 0 / stride s conv reads."""
+    return (n - 1) // s + 1
+
+
 def _no_preshift(ek) -> bool:
     """True if no entry of a device table (e | k << 8) carries a pre-shift k."""
     return bool((np.asarray(ek, dtype=np.int64) >> 8 == 0).all())
@@ -825,20 +845,27 @@ class IntegerEngine(GraphRunner):
         h, w = H1, W1
         res_bits_in = 16
         fused_in = None
+        sub_out = 0
         self._er_args, self._er_names = [], []
         for ui, u in enumerate(units):
             nxt = units[ui + 1] if ui + 1 < len(units) else None
             x_in, x_bits, hin, win, x_planar = qa, u['a_bits'], h, w, False
+            # sub_in = s: this unit's block input holds only the pixels (s y, s x) its readers want (the previous launch ran with out_sub = s):
+            # conv1 and the identity conv walk it with stride 1
+            sub_in, sub_out = sub_out, 0
+            if nxt is not None and nxt['resize'] and not u['resize'] and not self.keep_acc and not os.environ.get("HAWQ_NO_OUT_SUB"):
+                sub_out = out_sub_stride((r.kh, r.kw, r.stride, r.pad) for r in (nxt['convs'][0]['conv'], nxt['ident']))
             for ci, ent in enumerate(u['convs']):
                 c = ent['conv']
+                c_stride = 1 if (sub_in and ci == 0) else c.stride
                 if ci == 0 and fused_in is not None:   # this unit's reduce conv ran inside the previous unit's launch
                     x_in, x_bits, x_planar = fused_in
-                    hin, win = (hin + 2 * c.pad - c.kh) // c.stride + 1, (win + 2 * c.pad - c.kw) // c.stride + 1
+                    hin, win = (hin + 2 * c.pad - c.kh) // c_stride + 1, (win + 2 * c.pad - c.kw) // c_stride + 1
                     fused_in = None
                     self.n_fast += 1
                     self.n_conv += 1
                     continue
-                ho, wo = (hin + 2 * c.pad - c.kh) // c.stride + 1, (win + 2 * c.pad - c.kw) // c.stride + 1
+                ho, wo = (hin + 2 * c.pad - c.kh) // c_stride + 1, (win + 2 * c.pad - c.kw) // c_stride + 1
                 a = _lib.ConvArgs()
                 a.in_, a.wgt, a.bias = x_in.data_ptr(), c.w.data_ptr(), c.bias.data_ptr()
                 if x_bits == c.w_bits and c.band() is not None:
@@ -846,7 +873,7 @@ class IntegerEngine(GraphRunner):
                 if x_bits == c.w_bits and c.k128() is not None:
                     a.wgt_k128 = c.k128().data_ptr()
                 a.N, a.H, a.W, a.Cin, a.Cout = N, hin, win, c.cin, c.cout
-                a.KH, a.KW, a.stride, a.pad = c.kh, c.kw, c.stride, c.pad
+                a.KH, a.KW, a.stride, a.pad = c.kh, c.kw, c_stride, c.pad
                 a.in_bits, a.w_bits = x_bits, c.w_bits
                 a.m, a.e = ent['m'].data_ptr(), ent['e'].data_ptr()
                 a.flags = self.flags.data_ptr()
@@ -887,7 +914,7 @@ class IntegerEngine(GraphRunner):
                         a.in2, a.wgt2, a.bias2 = qa.data_ptr(), ic.w.data_ptr(), ic.bias.data_ptr()
                         if u['a_bits'] == ic.w_bits and ic.k128() is not None:
                             a.wgt2_k128 = ic.k128().data_ptr()
-                        a.H2, a.W2, a.Cin2, a.stride2 = h, w, ic.cin, ic.stride
+                        a.H2, a.W2, a.Cin2, a.stride2 = h, w, ic.cin, (1 if sub_in else ic.stride)
                         a.in2_bits, a.w2_bits = u['a_bits'], ic.w_bits
                         a.m_id, a.e_id = u['m_id'].data_ptr(), u['e_id'].data_ptr()
                     else:
@@ -895,6 +922,11 @@ class IntegerEngine(GraphRunner):
                         a.m_id_scalar, a.e_id_scalar = u['m_id_s'], u['e_id_s']
                     need_res = (nxt is None) or (not nxt['resize'])
                     new_res = self._alloc(N * ho * wo * c.cout, rdt) if need_res else None
+                    if sub_out:   # (need_res is False: the next unit is a resize unit) only the pixels the next unit reads, stored densely
+                        a.out_sub = sub_out
+                        qh, qw = out_sub_extent(ho, sub_out), out_sub_extent(wo, sub_out)
+                    else:
+                        qh, qw = ho, wo
                     if new_res is not None:
                         a.res_out, a.res_out_bits = new_res.data_ptr(), self.res_bits
                         self.res_taps[u['name']] = (new_res, (N, ho, wo, c.cout))
@@ -910,7 +942,7 @@ class IntegerEngine(GraphRunner):
                 keep.append(a)
                 fz = self._try_fuse(a, u, nxt, N, ho, wo, keep) if (ci == len(u['convs']) - 1 and not self.keep_acc) else None
                 if fz is None and ci == len(u['convs']) - 1 and nxt is not None:
-                    new_qa = self._alloc(N * ho * wo * c.cout * nxt['a_bits'] // 8, torch.uint8)
+                    new_qa = self._alloc(N * qh * qw * c.cout * nxt['a_bits'] // 8, torch.uint8)
                     a.out_q = new_qa.data_ptr()
                     keep.append(new_qa)
                 if fz is not None:
@@ -935,7 +967,7 @@ class IntegerEngine(GraphRunner):
                 ops.append(self._conv_ops[-1])
                 if ci < len(u['convs']) - 1:
                     x_in, x_bits, hin, win, x_planar = x_next, xb_next, ho, wo, planar_next
-            res, qa, h, w = new_res, new_qa, ho, wo
+            res, qa, h, w = new_res, new_qa, qh, qw
             res_bits_in = self.res_bits
         cl = units[-1]['convs'][-1]['conv'].cout
         qf = self._alloc(N * cl, torch.int8)

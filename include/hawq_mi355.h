@@ -151,6 +151,14 @@ typedef struct hawq_conv_args {
        so that the K loop walks full 128-byte lines and every weight piece is a contiguous KiB.  NULL = not provided. */
     const void *wgt_k128;
     const void *wgt2_k128;
+    /* out_sub = s >= 2 (0 and 1: every pixel, as always): the launch evaluates only the output pixels (n, s y', s x') with y' < Ho' = (Ho - 1) / s + 1
+       and x' < Wo' = (Wo - 1) / s + 1 - what a 1x1 / pad 0 / stride s conv (the conv1 and the identity conv of a stage's first unit, q_resnet.py:236-240) reads
+       of the block input this launch writes.  `in` and `res_in` stay tensors of the full H x W map and are read at that source pixel; out_q is stored
+       densely as [N][Ho'][Wo'][Cout] (int8 or hawq4).  Needs: a 1x1 / stride 1 / pad 0 conv, single branch (in2 == NULL) and res_out == NULL (no dense
+       residual is produced; the uint16 overflow flag can only be raised by the pixels that are evaluated).  Taken by hawq_conv2d's general tiles
+       (RESIDUAL epilogue, 16- or 32-bit res_in, dense NHWC rows) and by the expand conv alone of hawq_conv_expand_reduce (reduce.wgt == NULL); the special-purpose
+       tile ids, hawq_conv2d_splitk and the fused pairs refuse it through their applicability queries. */
+    int32_t out_sub;
 } hawq_conv_args;
 
 int hawq_conv2d(const hawq_conv_args *args, void *stream);
