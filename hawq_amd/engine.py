@@ -28,6 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib, packing
+from . import plan as _plan
+from .plan import ChainChoice, StalePlan
 from .quant_utils import requant_table, tables_are_fast, tables_fit_fast
 from .runner import EventTimer, GraphRunner, _act_range, _i32, two_round_min
 
@@ -74,10 +76,6 @@ class _OpList(list):
         self.names.append(name)
         self.next_name = None
         super().append(fn)
-
-
-class StalePlan(ValueError):
-    """A recorded plan does not fit the launch list / kernel inventory of this build: the engine falls back to tuning."""
 
 
 # K-slice counts the tuner tries for a hawq_conv2d launch with fewer output tiles than the chip has CUs (hawq_conv2d_splitk)
@@ -209,22 +207,9 @@ class IntegerEngine(GraphRunner):
     integer buffers / scales as loaded from a quantized checkpoint (quant_train.py:665-670)
     instead of re-deriving them from the float parameters."""
 
-    # launches that recorded plans may still list as tuned although this build runs them on a kernel with nothing to tune
-    _UNTUNED_SINCE = ("quant_output",)
-
     def __init__(self, model, residual_bits: int = 16, from_buffers: bool = False, use_graph: bool = True,
                  keep_accumulators: bool = False, fast: bool = True, autotune: bool = True, chains: int = 0,
-                 plan=None, _parent=None):
-        if _parent is not None:  # a chain of a multi-chain engine: shares parameters, owns stream + buffers
-            self.__dict__.update({k: v for k, v in _parent.__dict__.items()
-                                  if k in ("model", "dev", "res_bits", "from_buffers", "keep_acc", "fast", "autotune",
-                                           "flags", "P", "planar", "fuse_stages", "plan")})
-            self._plan_on = False
-            self.use_graph, self.chains, self.subs = False, 1, []
-            self.stream = torch.cuda.Stream(device=self.dev)
-            self.tile_choice, self.er_choice = {}, {}
-            self._batch = self._graph = None
-            return
+                 plan=None):
         if not model.is_frozen():
             raise RuntimeError("IntegerEngine needs a frozen model (freeze_model) - ranges must be fixed")
         _lib.load()
@@ -242,8 +227,6 @@ class IntegerEngine(GraphRunner):
         self.planar = not keep_accumulators and not os.environ.get("HAWQ_NO_PLANAR")
         # expand conv of unit i + reduce conv of unit i+1 in one launch (hawq_conv_expand_reduce) in these stages
         self.fuse_stages = set() if keep_accumulators else {int(v) for v in os.environ.get("HAWQ_FUSE_STAGES", "1,2,3").split(",") if v}
-        self.tile_choice = {}
-        self.er_choice = {}
         # chains > 1: the batch is split into independent sub-batches whose launch chains run on separate
         # streams inside ONE hipGraph, so that one chain's kernel tails / prologues / epilogues overlap the
         # other's work (the late layers launch fewer workgroups than there are CUs).  0 = choose 1, 2 or 3 by
@@ -257,9 +240,9 @@ class IntegerEngine(GraphRunner):
         # storage policy of 4-bit expand-conv inputs (see _prepare_params): "0" nibbles, "1" int8 in a fusable unit whose successor's block
         # input is 8-bit (rounds 3-5), "2" int8 in every identity-pass-through bottleneck (round 6, the default; env HAWQ_EXPAND_IN8).
         # A recorded plan carries the policy its launch list was built with.
-        # (a plan recorded before round 6 has no such key: it was recorded under policy "1")
-        self.expand_in8 = str(self.plan.get("expand_in8") or "1") if self.plan else os.environ.get("HAWQ_EXPAND_IN8", "2")
+        self.expand_in8 = _plan.expand_in8_of(self.plan) if self.plan else os.environ.get("HAWQ_EXPAND_IN8", "2")
         self.plan_source = "tuned in this process"
+        self._plan_on = False   # the batch shape being built is the one `plan` was recorded for, and the plan fits so far
         self.subs = []
         self.stream = torch.cuda.Stream(device=self.dev)
         self.flags = torch.zeros(1, dtype=torch.int32, device=self.dev)
@@ -271,6 +254,26 @@ class IntegerEngine(GraphRunner):
         self.overflow_fallbacks = 0
         self._flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._prepare_params()
+        self._reset_plan()
+
+    @classmethod
+    def _chain_of(cls, parent):
+        """One chain of the multi-chain engine `parent`: shares its parameters, owns a stream and the buffers of its sub-batch."""
+        sub = cls.__new__(cls)
+        for k in ("model", "dev", "P", "flags", "res_bits", "from_buffers", "keep_acc", "fast", "autotune", "planar", "fuse_stages"):
+            setattr(sub, k, getattr(parent, k))
+        sub.use_graph, sub.chains, sub.chains_req, sub.subs = False, 1, 1, []
+        sub.stream = torch.cuda.Stream(device=sub.dev)
+        sub._batch = sub._graph = None
+        return sub
+
+    def _reset_plan(self):
+        """Everything a build fills in, as it is before the build (the first statement of every build)."""
+        self._conv_args, self._conv_names, self._conv_ops = [], [], []   # hawq_conv2d launches: argument block, name, _ConvLaunch
+        self._er_args, self._er_names = [], []                           # expand(-> reduce) launches: _FusedPair, name
+        self._tile_times, self._er_times = {}, {}                        # what the tuner measured for them (empty: nothing was timed)
+        self.tile_choice, self.er_choice, self.er_split_tiles = {}, {}, {}   # the choice by launch name: written by _apply_choice only
+        self._stem_u8_tail = None
 
     # ------------------------------------------------------------------ host-side preparation
     def _scale(self, act):
@@ -527,11 +530,11 @@ class IntegerEngine(GraphRunner):
     def _alloc(self, n, dtype):
         return torch.empty(n, dtype=dtype, device=self.dev)
 
-    def _build(self, N, H, W, x_view=None, logits_view=None):
+    def _build(self, N, H, W):
         """Allocate activation buffers for batch N and record the launch list (choosing the chain count first
         when it was left open)."""
-        self._build_plan(N, H, W, x_view, logits_view)
-        if x_view is None and not os.environ.get("HAWQ_KEEP_PACKED"):
+        self._build_plan(N, H, W)
+        if not os.environ.get("HAWQ_KEEP_PACKED"):
             self._release_unused_weights()
 
     def _release_unused_weights(self):
@@ -544,16 +547,16 @@ class IntegerEngine(GraphRunner):
         band_ids, gemm_ids = range(n - ng2 - nb2 + 1, n - ng2 + 1), range(n - ng2 + 1, n + 1)
         args = []
         for e in (self.subs or [self]):
-            args += list(getattr(e, "_conv_args", []))
-            for pr in getattr(e, "_er_args", []):
+            args += list(e._conv_args)
+            for pr in e._er_args:
                 if not pr.fused:
                     args += [pr.expand] + ([pr.reduce] if pr.reduce is not None else [])
         live_band = {a.wgt_band for a in args if a.wgt_band and (a.tile in band_ids or a.tile == 0)}   # (tile 0: the library's own default may pick one)
         live_k128 = {ptr for a in args if (a.tile in gemm_ids or a.tile == 0) for ptr in (a.wgt_k128, a.wgt2_k128) if ptr}
         every = []
         for e in (self.subs or [self]):
-            every += list(getattr(e, "_conv_args", []))
-            for pr in getattr(e, "_er_args", []):
+            every += list(e._conv_args)
+            for pr in e._er_args:
                 every += [pr.expand, pr.er.expand, pr.er.reduce] + ([pr.reduce] if pr.reduce is not None else [])
         for a in every:
             if a.wgt_band and a.wgt_band not in live_band:
@@ -569,29 +572,23 @@ class IntegerEngine(GraphRunner):
             c.release(wb is not None and wb.data_ptr() not in live_band, wk is not None and wk.data_ptr() not in live_k128)
             self.packed_weight_bytes += sum(t.numel() for t in (c._w_band, c._w_k128) if t is not None)
 
-    def _build_plan(self, N, H, W, x_view=None, logits_view=None):
-        if x_view is None:
-            self._plan_on = bool(self.plan) and int(self.plan.get("batch", -1)) == N and not self.keep_acc
-            if not self._plan_on and hasattr(self, "chains_req"):
-                # a batch shape the plan was not recorded for: the chain count a replay of ANOTHER shape left behind does not carry over
-                self.chains = max(1, self.chains_req)
-        if x_view is None and self._plan_on:
+    def _build_plan(self, N, H, W):
+        # a batch shape the plan was not recorded for is tuned: the chain count a replay of ANOTHER shape left behind does not carry over
+        self._plan_on = bool(self.plan) and int(self.plan.get("batch", -1)) == N and not self.keep_acc
+        self.chains = max(1, self.chains_req)
+        if self._plan_on:
             try:
-                if int(self.plan.get("num_conv_tiles", -1)) != int(_lib.load().hawq_conv2d_num_tiles()):
-                    raise StalePlan("recorded for a library with another tile inventory")
+                if not self.autotune:   # (every chain applies its part of the plan where it would otherwise tune)
+                    raise StalePlan("autotune=False leaves every launch on the library's default")
                 self.chains = max(1, int(self.plan["chains"]))
-                self._build_chains(N, H, W, x_view, logits_view)
-                names = self.plan.get("conv_launches")
-                if names is not None and [n for n in names if n not in self._UNTUNED_SINCE] != list(self.tile_choice.keys()):
-                    raise StalePlan("recorded for another launch list (other network, schedule or storage rule)")
+                self._build_chains(N, H, W)   # each chain checks the plan against its launch list (plan.decode)
                 self.plan_source = self.plan.get("source", "replayed a recorded plan")
                 return
             except StalePlan as exc:
                 print(f"[hawq_amd] recorded plan ignored ({exc}); tuning instead", file=sys.stderr)
                 self._plan_on = False
                 self.chains = max(1, self.chains_req)
-                self.tile_choice, self.er_choice = {}, {}
-        if x_view is None and getattr(self, "chains_req", 1) == 0 and self.use_graph and self.autotune:
+        if self.chains_req == 0 and self.use_graph and self.autotune:
             timing, plans = {}, {}
             # small batches (what one GPU sees when 128 images are sharded over 4 / 8 ranks) launch fewer workgroups
             # than the chip has CUs in most layers: two concurrent half-batches can still pay, three never did
@@ -612,14 +609,14 @@ class IntegerEngine(GraphRunner):
             winner = None
             for c in order:
                 self.chains = c
-                self._build_chains(N, H, W, x_view, logits_view)
+                self._build_chains(N, H, W)
                 if N < 8 or plans.get(c) is None:
                     winner = (0.0, c, None, ())
                     break
                 # the rebuild tuned again: keep whichever plan for this chain count replays fastest
                 cands = [plans[c], self._plan_snapshot()]
                 for _ in range(max(0, int(os.environ.get("HAWQ_TUNE_TRIALS", "4")) - 2)):
-                    self._build_chains(N, H, W, x_view, logits_view)
+                    self._build_chains(N, H, W)
                     cands.append(self._plan_snapshot())
                 # all on the final buffers, in two interleaved rounds (a plan's replay time drifts by ~1 % with the clocks: the
                 # second round keeps one lucky measurement from deciding), the faster of a plan's two times counts
@@ -632,69 +629,65 @@ class IntegerEngine(GraphRunner):
                     winner = (min(times), c, cands[times.index(min(times))], tuple(round(t, 4) for t in times))
             if self.chains != winner[1]:
                 self.chains = winner[1]
-                self._build_chains(N, H, W, x_view, logits_view)
+                self._build_chains(N, H, W)
             if winner[2] is not None:
                 self._plan_apply(winner[2])
                 self.plan_trials_ms = winner[3]
             return
-        self._build_chains(N, H, W, x_view, logits_view)
-
-    def _fixed(self, key):
-        """Recorded choice for `key` ("chains" / "tiles" / "fused_variants" / "fused_split_tiles" / "splitk"): the plan handed to the constructor
-        while the batch shape it was recorded for is being built (`_plan_on`; the chains of a multi-chain engine inherit it), else
-        the measurement switches HAWQ_CHAINS / HAWQ_TILES / HAWQ_ER_TILES / HAWQ_ER_SPLIT_TILES / HAWQ_SPLITK, else None (tune)."""
-        pl = getattr(self, "plan", None)
-        if pl and getattr(self, "_plan_on", False):
-            # chains whose tuned choices differ (uneven sub-batches, layers only one tile takes) are recorded one by one
-            per = pl.get("per_chain")
-            i = getattr(self, "_chain_index", None)
-            if per and i is not None and key != "chains":
-                if i >= len(per):
-                    raise StalePlan(f"the recorded plan lists {len(per)} chains")
-                if per[i].get(key) not in (None, ""):
-                    return str(per[i][key])
-            if pl.get(key) not in (None, ""):
-                return str(pl[key])
-        return os.environ.get({"chains": "HAWQ_CHAINS", "tiles": "HAWQ_TILES", "fused_variants": "HAWQ_ER_TILES",
-                               "fused_split_tiles": "HAWQ_ER_SPLIT_TILES", "splitk": "HAWQ_SPLITK"}[key])
+        self._build_chains(N, H, W)
 
     def export_plan(self):
-        """The plan of the batch shape built last, as plain strings (what bench.py prints as config.autotuned_tiles / fused_variants /
-        fused_split_tiles / concurrent_sub_batches): feed it back through ``IntegerEngine(model, plan=...)`` to replay it.
-        "splitk" (only written when some launch runs split-K): the K-slice count of every conv launch in the order of "tiles",
-        then two per pair in the order of "fused_variants" (its two-launch form: expand, reduce), 0 = hawq_conv2d."""
+        """The plan of the batch shape built last, as plain strings (plan.encode; what bench.py prints as config.autotuned_tiles /
+        fused_variants / fused_split_tiles / concurrent_sub_batches): feed it back through ``IntegerEngine(model, plan=...)`` to replay it."""
         if self._batch is None:
             raise RuntimeError("export_plan: no batch shape has been built yet")
+        e = (self.subs or [self])[0]
+        return _plan.encode(self._batch[0], self.chains, self.expand_in8, self._plan_snapshot(), e._conv_names, e._er_names,
+                            _lib.load().hawq_conv2d_num_tiles(), e._variant_counts())
 
-        any_split = any(any(e.splitk_choice()) for e in (self.subs or [self]))
+    def _variant_counts(self):
+        return [int(_lib.load().hawq_conv_expand_reduce_variants(C.byref(p.er))) for p in self._er_args]
 
-        def strings(e):   # (with a split launch in any chain, every chain's entry names its own split counts, zeros included)
-            out = {"tiles": ".".join(str(t) for t in e.tile_choice.values()),
-                   "fused_variants": ".".join(str(t) for t in e.er_choice.values()),
-                   "fused_split_tiles": ".".join(f"{a}.{b}" for a, b in getattr(e, "er_split_tiles", {}).values())}
-            if any_split:
-                out["splitk"] = ".".join(str(v) for v in e.splitk_choice())
-            return out
-        per = [strings(e) for e in self.subs]
-        # the top-level strings are chain 0's; "per_chain" is only written when another chain runs something else
-        extra = {"per_chain": per} if any(p != per[0] for p in per[1:]) else {}
-        sk0 = (self.subs[0] if self.subs else self).splitk_choice()
-        if any(sk0):
-            extra["splitk"] = ".".join(str(v) for v in sk0)
-        return {"batch": int(self._batch[0]), "chains": int(self.chains), "expand_in8": self.expand_in8, **extra,
-                "tiles": ".".join(str(t) for t in self.tile_choice.values()),
-                "fused_variants": ".".join(str(t) for t in self.er_choice.values()),
-                "fused_split_tiles": ".".join(f"{a}.{b}" for a, b in getattr(self, "er_split_tiles", {}).values()),
-                "conv_launches": list(self.tile_choice.keys()), "pair_launches": list(self.er_choice.keys()),
-                # guards against replaying a plan on a build whose kernels are numbered differently
-                "num_conv_tiles": int(_lib.load().hawq_conv2d_num_tiles()),
-                "pair_variant_counts": [int(_lib.load().hawq_conv_expand_reduce_variants(C.byref(p.er))) for p in (self.subs[0] if self.subs else self)._er_args]}
+    def _choice(self) -> ChainChoice:
+        """The choice this chain (chain 0 of a multi-chain engine) runs, read off its tuned or replayed launch list."""
+        if self.subs:
+            return self.subs[0]._choice()
+        pairs = self._er_args
+        return ChainChoice([a.tile for a in self._conv_args], [p.er.tile if p.fused else 0 for p in pairs],
+                           [(p.expand.tile, p.reduce.tile if p.reduce is not None else 0) for p in pairs],
+                           [op.splitk for op in self._conv_ops] + [v for p in pairs for v in (p.split_e, p.split_r)])
+
+    def _apply_choice(self, ch):
+        """Make `ch` what this chain runs.  The ONLY code that writes the tile, fused form and split-K fields of the launch list and
+        the by-name dicts derived from them: a replay, the tuners and _set_splitk all end here (a tuner sets a candidate on an argument
+        block only while it times it).  StalePlan, before anything is written, when the library refuses a split."""
+        slots = [op.a for op in self._conv_ops] + [a for p in self._er_args for a in (p.expand, p.reduce)]
+        if len(ch.splitk) != len(slots):
+            raise StalePlan(f"the recorded plan lists {len(ch.splitk)} split-K entries, this plan has {len(slots)} launches")
+        for a, v in zip(slots, ch.splitk):
+            if v:
+                if a is None or not _lib.load().hawq_conv2d_splitk_ok(C.byref(a), v):
+                    raise StalePlan(f"the library refuses split-K with {v} slices for a recorded launch")
+                self._ws.fit(a, v)
+        for op, t, v in zip(self._conv_ops, ch.tiles, ch.splitk):
+            op.a.tile, op.splitk = t, v
+        pair_splits = ch.splitk[len(self._conv_ops):]
+        for k, (p, v, (te, tr)) in enumerate(zip(self._er_args, ch.variants, ch.split_tiles)):
+            p.fused = v != 0
+            if p.fused:   # (the variant of a pair that runs as two launches is read by no launch)
+                p.er.tile = v
+            p.expand.tile = te
+            if p.reduce is not None:
+                p.reduce.tile = tr
+            p.split_e, p.split_r = pair_splits[2 * k:2 * k + 2]
+        for d, names, vals in ((self.tile_choice, self._conv_names, ch.tiles), (self.er_choice, self._er_names, ch.variants),
+                               (self.er_split_tiles, self._er_names, ch.split_tiles)):
+            d.clear()
+            d.update(zip(names, vals))
 
     def splitk_choice(self):
         """K-slice count of every conv launch, then of both launches of every pair's two-launch form (0 = not split)."""
-        if self.subs:
-            return self.subs[0].splitk_choice()
-        return [op.splitk for op in self._conv_ops] + [v for p in self._er_args for v in (p.split_e, p.split_r)]
+        return self._choice().splitk
 
     def n_splitk(self) -> int:
         """Split-K launches in the forward as built (a pair's two-launch form counts only when the pair runs unfused)."""
@@ -703,20 +696,8 @@ class IntegerEngine(GraphRunner):
                    sum((p.split_e > 0) + (p.split_r > 0) for p in e._er_args if not p.fused) for e in engines)
 
     def _set_splitk(self, values):
-        """Apply a splitk_choice() list to this chain (the library must take every non-zero entry)."""
-        ops = list(self._conv_ops) + [None] * (2 * len(self._er_args))
-        if len(values) != len(ops):
-            raise StalePlan(f"the recorded plan lists {len(values)} split-K entries, this plan has {len(ops)} launches")
-        slots = [(op.a, op, "splitk") for op in self._conv_ops]
-        for p in self._er_args:
-            slots += [(p.expand, p, "split_e"), (p.reduce, p, "split_r")]
-        for (a, obj, attr), v in zip(slots, values):
-            v = int(v)
-            if v:
-                if a is None or not _lib.load().hawq_conv2d_splitk_ok(C.byref(a), v):
-                    raise StalePlan(f"the library refuses split-K with {v} slices for a recorded launch")
-                self._ws.fit(a, v)
-            setattr(obj, attr, v)
+        """Apply a splitk_choice() list to this tuned or replayed chain (the library must take every non-zero entry: StalePlan)."""
+        self._apply_choice(self._choice()._replace(splitk=[int(v) for v in values]))
 
     def _splitk_options(self, a):
         """K-slice counts the tuner times for hawq_conv2d launch `a`: the candidates the library takes, when even the library's smallest
@@ -731,29 +712,15 @@ class IntegerEngine(GraphRunner):
         return [s for s in SPLITK_CANDIDATES if _lib.load().hawq_conv2d_splitk_ok(C.byref(a), s)]
 
     def _plan_snapshot(self):
-        """Tile / fused-variant / split-K choice of every launch of the current plan (one entry per chain)."""
-        return [dict(tiles=[a.tile for a in e._conv_args], splitk=e.splitk_choice(),
-                     pairs=[(p.fused, p.er.tile, p.expand.tile, p.reduce.tile if p.reduce is not None else 0) for p in e._er_args],
-                     tile_choice=dict(e.tile_choice), er_choice=dict(e.er_choice), er_split=dict(getattr(e, "er_split_tiles", {})))
-                for e in (self.subs or [self])]
+        return [e._choice() for e in (self.subs or [self])]
 
-    def _plan_apply(self, plan):
+    def _plan_apply(self, choices):
         engines = self.subs or [self]
-        if len(plan) != len(engines) or any(len(pl["tiles"]) != len(e._conv_args) or len(pl["pairs"]) != len(e._er_args)
-                                            for pl, e in zip(plan, engines)):
+        if len(choices) != len(engines) or any(len(ch.tiles) != len(e._conv_args) or len(ch.variants) != len(e._er_args)
+                                               for ch, e in zip(choices, engines)):
             return
-        for pl, e in zip(plan, engines):
-            for a, t in zip(e._conv_args, pl["tiles"]):
-                a.tile = t
-            for p, (fused, vt, te, tr) in zip(e._er_args, pl["pairs"]):
-                p.fused, p.er.tile, p.expand.tile = fused, vt, te
-                if p.reduce is not None:
-                    p.reduce.tile = tr
-            e._set_splitk(pl["splitk"])
-            e.tile_choice.clear(), e.tile_choice.update(pl["tile_choice"])
-            e.er_choice.clear(), e.er_choice.update(pl["er_choice"])
-            if hasattr(e, "er_split_tiles"):
-                e.er_split_tiles.clear(), e.er_split_tiles.update(pl["er_split"])
+        for ch, e in zip(choices, engines):
+            e._apply_choice(ch)
         self._drop_graph()
 
     def _on_graph_dropped(self):
@@ -765,9 +732,13 @@ class IntegerEngine(GraphRunner):
         self.flags.zero_()
         return ms
 
-    def _build_chains(self, N, H, W, x_view=None, logits_view=None):
+    def _build_chains(self, N, H, W, x_view=None, logits_view=None, fixed=None, chain=0):
+        """Buffers and launch list for batch N; chain `chain` of a multi-chain engine on its views, with what fixes the engine's choices."""
         P, dev = self.P, self.dev
         self._drop_graph()
+        self._reset_plan()
+        if fixed is None:   # as plan.decode reads it: the recorded plan while its batch shape is built, else the measurement switches
+            fixed = self.plan if self._plan_on else dict(_plan.from_env(os.environ), num_conv_tiles=int(_lib.load().hawq_conv2d_num_tiles()))
         if self.chains > 1 and N >= 2 * self.chains:
             self.x_in = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
             self.logits = torch.empty(N, P['fc']['nout'], dtype=torch.float32, device=dev)
@@ -778,26 +749,19 @@ class IntegerEngine(GraphRunner):
                 split = [N // self.chains + (1 if i < N % self.chains else 0) for i in range(self.chains)]
             for i in range(self.chains):
                 b1 = b0 + split[i]
-                sub = IntegerEngine(None, _parent=self)
-                sub._chain_index = i
-                sub._plan_on = getattr(self, "_plan_on", False)
-                sub._build(b1 - b0, H, W, self.x_in[b0:b1], self.logits[b0:b1])
+                sub = IntegerEngine._chain_of(self)
+                sub._build_chains(b1 - b0, H, W, self.x_in[b0:b1], self.logits[b0:b1], fixed, i)
                 self.subs.append(sub)
                 b0 = b1
             self._ops, self._keep, self._batch, self._graph = _OpList(), [], (N, H, W), None
-            if (self.autotune and not self._fixed("tiles") and os.environ.get("HAWQ_JOINT_TUNE", "1") != "0"
-                    and all(hasattr(sub, "_tile_times") for sub in self.subs)):
+            if self.autotune and not fixed.get("tiles") and os.environ.get("HAWQ_JOINT_TUNE", "1") != "0":
                 self._autotune_joint()
-            self.n_fast, self.n_conv, self.n_k0, self.n_tie = (self.subs[0].n_fast, self.subs[0].n_conv, self.subs[0].n_k0,
-                                                              self.subs[0].n_tie)
-            self.n_ck0 = self.subs[0].n_ck0
-            self.tile_choice, self.er_choice = self.subs[0].tile_choice, self.subs[0].er_choice
-            self.er_split_tiles = getattr(self.subs[0], "er_split_tiles", {})
+            s0 = self.subs[0]   # (every chain runs the same launch list; the by-name dicts shown are chain 0's own, updated in place)
+            self.n_fast, self.n_conv, self.n_k0, self.n_tie, self.n_ck0 = s0.n_fast, s0.n_conv, s0.n_k0, s0.n_tie, s0.n_ck0
+            self.tile_choice, self.er_choice, self.er_split_tiles = s0.tile_choice, s0.er_choice, s0.er_split_tiles
             return
         self.subs = []
         ops, keep = _OpList(), []
-        self._conv_args, self._conv_names = [], []
-        self._conv_ops = []   # the _ConvLaunch of every entry of _conv_args
         self._ws = _SplitWorkspace(dev)
         self.acc_taps = {}
         self.res_taps = {}   # unit name -> (stored post-ReLU residual tensor of this plan, NHWC shape): parity tests read them back
@@ -846,7 +810,6 @@ class IntegerEngine(GraphRunner):
         res_bits_in = 16
         fused_in = None
         sub_out = 0
-        self._er_args, self._er_names = [], []
         for ui, u in enumerate(units):
             nxt = units[ui + 1] if ui + 1 < len(units) else None
             x_in, x_bits, hin, win, x_planar = qa, u['a_bits'], h, w, False
@@ -1004,7 +967,9 @@ class IntegerEngine(GraphRunner):
         self._ops, self._keep, self._batch = ops, keep, (N, H, W)
         self._graph = None
         if self.autotune and not self.keep_acc:
-            self._autotune_tiles()
+            # what `fixed` records for this chain is applied as it is (no timer, no launch); what it leaves open is timed first
+            ch = _plan.decode(fixed, chain, self._conv_names, len(self._er_args), int(_lib.load().hawq_conv2d_num_tiles()), self._variant_counts())
+            self._apply_choice(self._time_choice(ch) if ch.tiles is None else ch)
 
     def _add_acc_tap(self, ops, keep, a, name, N, ho, wo, cout):
         """Extra RAW launch of the same conv to expose its int32 accumulators (tests only)."""
@@ -1029,64 +994,23 @@ class IntegerEngine(GraphRunner):
         self.acc_taps[u['name'] + ".quant_identity_convbn"] = (acc, (N, ho, wo, ic.cout))
         ops.append(partial(_lib.call, "hawq_conv2d", C.byref(r), self.stream.cuda_stream))
 
-    def _autotune_tiles(self, reps: int = 3):
-        """Time every conv launch with each tile configuration (HIP events on the engine stream, the
-        real buffers, results are identical for every tile) and keep the fastest.  Runs once per batch
-        shape, before the hipGraph is captured: ~50 launches x 4 tiles x reps, a few milliseconds."""
+    def _time_choice(self, pinned, reps: int = 3) -> ChainChoice:
+        """Time every conv launch with each tile configuration (HIP events on the engine stream, the real buffers, results are identical
+        for every tile) and return the fastest choice.  Runs once per batch shape, before the hipGraph is captured: ~50 launches x 4 tiles
+        x reps, a few milliseconds.  `pinned.variants` (HAWQ_ER_TILES without HAWQ_TILES) keeps the pairs as given.  The times stay
+        in _tile_times / _er_times for the joint pass."""
         n_tiles = _lib.load().hawq_conv2d_num_tiles()
         sp = self.stream.cuda_stream
-        self._tile_times, self._er_times = {}, {}
         # tile ids the tuner no longer tries (VERDICT r5 item 8b): never chosen in any plan recorded in rounds 4-6 nor in this round's
         # fresh tuning runs (profiles/r06_retired_tiles.md).  The kernels stay in the library under their ids - recorded plans, the
         # parity tests and tools/tile_sweep.py still reach them - but a tuning pass no longer times them.  HAWQ_RETIRED_TILES="" re-enables.
         retired = {int(v) for v in os.environ.get("HAWQ_RETIRED_TILES", "5,19").split(",") if v}
-        # replay a recorded choice, no timing: the constructor's plan for this batch size, or HAWQ_TILES (dotted list as bench.py prints it).
-        # A chain of a multi-chain engine replays the plan of the WHOLE batch it is a part of
-        fixed = self._fixed("tiles")
-        if fixed:
-            ids = [int(v) for v in fixed.split(".")]
-            names = (self.plan or {}).get("conv_launches") if getattr(self, "_plan_on", False) else None
-            if names is not None and len(names) == len(ids) and list(names) != list(self._conv_names):
-                # a plan recorded with launches this build no longer tunes (_UNTUNED_SINCE: the classifier since round 5): replay by NAME.
-                # The ONLY relaxation: the recorded list minus those launches must be this build's list exactly - a superset recorded
-                # for a larger network (resnet101's plan on resnet50) is stale, not replayable (ADVICE r5)
-                if [n for n in names if n not in self._UNTUNED_SINCE] != list(self._conv_names):
-                    raise StalePlan("recorded for another launch list (other network, schedule or storage rule)")
-                by_name = dict(zip(names, ids))
-                ids = [by_name[n] for n in self._conv_names]
-            if len(ids) != len(self._conv_args):
-                raise StalePlan(f"the recorded plan lists {len(ids)} tiles, this plan has {len(self._conv_args)} conv launches")
-            counts = self.plan.get("pair_variant_counts") if getattr(self, "_plan_on", False) else None
-            if counts is not None and list(counts) != [int(_lib.load().hawq_conv_expand_reduce_variants(C.byref(p.er))) for p in self._er_args]:
-                raise StalePlan("the fused expand(-> reduce) kernels of this build are numbered differently")
-            for name, a, tid in zip(self._conv_names, self._conv_args, ids):
-                a.tile = tid
-                self.tile_choice[name] = tid
-            split = self._fixed("fused_split_tiles")
-            split = [int(x) for x in split.split(".")] if split else None
-            self.er_split_tiles = getattr(self, "er_split_tiles", {})
-            for k, (name, pair) in enumerate(zip(self._er_names, self._er_args)):
-                v = (self._fixed("fused_variants") or ".".join(["1"] * len(self._er_args))).split(".")[k]
-                pair.er.tile = int(v)
-                pair.fused = pair.er.tile != 0
-                if split is not None:   # tiles of the pair's two-launch form (what runs when the recorded variant is 0)
-                    te, tr = split[2 * k:2 * k + 2]
-                    pair.expand.tile = te
-                    if pair.reduce is not None:
-                        pair.reduce.tile = tr
-                    self.er_split_tiles[name] = (te, tr)
-                elif not pair.fused:
-                    raise StalePlan("the recorded plan runs a pair as two launches but lists no tiles for them")
-                self.er_choice[name] = pair.er.tile
-            sk = self._fixed("splitk")   # absent (every plan recorded before split-K existed): no launch is split
-            self._set_splitk([int(v) for v in sk.split(".")] if sk else [0] * (len(self._conv_ops) + 2 * len(self._er_args)))
-            return
         tiles = [t for t in range(1, n_tiles + 1) if t not in retired]
 
         def time_tiles(timer, a):
             """ms per `reps` launches of hawq_conv2d launch `a` for every tile that takes it (keys: tile ids) and, with the fastest of
-            them set in `a`, for its split-K candidates (keys -S: S K slices): (times, fastest tile).  Split-K keeps that tile for
-            the unsplit form of the plan."""
+            them set in `a`, for its split-K candidates (keys -S: S K slices): (times, fastest tile, K slices of the fastest form or 0).
+            Split-K keeps that tile for the unsplit form of the plan."""
             def tile(t):
                 a.tile = t
                 return partial(_lib.call, "hawq_conv2d", C.byref(a), sp)
@@ -1097,42 +1021,27 @@ class IntegerEngine(GraphRunner):
             times = two_round_min(timer, tiles, tile, reps)
             a.tile = best_t = min(times, key=times.get)
             two_round_min(timer, [-s for s in self._splitk_options(a)], split, reps, times)
-            return times, best_t
+            return times, best_t, max(0, -min(times, key=times.get))
 
-        # the events are created only on the timing path (the replay branch above returns or raises StalePlan without them)
+        chosen, splitk = [a.tile for a in self._conv_args], [0] * len(self._conv_args)
+        time_pairs = pinned.variants is None
+        variants, split_tiles = ([], []) if time_pairs else (pinned.variants, pinned.split_tiles)
+        pair_splitk = [0] * (2 * len(self._er_args))
         with torch.cuda.stream(self.stream), EventTimer(sp) as timer:
             self._launch_all()  # every buffer holds valid data
-            for name, a, op in zip(self._conv_names, self._conv_args, self._conv_ops):
+            for k, (name, a) in enumerate(zip(self._conv_names, self._conv_args)):
                 if os.environ.get("HAWQ_TILE_RES") or os.environ.get("HAWQ_TILE_REQ"):
                     break
-                times, best_t = time_tiles(timer, a)
-                best_any = min(times, key=times.get)
-                op.splitk = -best_any if best_any < 0 else 0
+                times, chosen[k], splitk[k] = time_tiles(timer, a)
                 self._tile_times[name] = dict(times)
-                log = [f"{t if t > 0 else f's{-t}'}:{v / reps * 1e3:.1f}" for t, v in times.items()]
                 if os.environ.get("HAWQ_AUTOTUNE_LOG"):
-                    print(f"[autotune N={a.N}] {name}: best {best_t}{f' split {op.splitk}' if op.splitk else ''}  us per tile "
+                    log = [f"{t if t > 0 else f's{-t}'}:{v / reps * 1e3:.1f}" for t, v in times.items()]
+                    print(f"[autotune N={a.N}] {name}: best {chosen[k]}{f' split {splitk[k]}' if splitk[k] else ''}  us per tile "
                           f"(sS: split-K, S slices): {' '.join(log)}", file=sys.stderr)
-                self.tile_choice[name] = best_t
-
-            def best_tile(a):   # fastest applicable tile of one hawq_conv2d launch, and its split-K form: (tile, slices, ms per `reps` launches)
-                times, t = time_tiles(timer, a)
-                best = min(times, key=times.get)
-                return t, (-best if best < 0 else 0), times[best]
-
-            fixed_er = os.environ.get("HAWQ_ER_TILES")   # dotted list as printed by bench.py; 0 = two separate launches
             for k, (name, pair) in enumerate(zip(self._er_names, self._er_args)):
+                if not time_pairs:
+                    break
                 er = pair.er
-                if fixed_er:
-                    er.tile = int(fixed_er.split(".")[k])
-                    pair.fused = er.tile != 0
-                    if not pair.fused:
-                        te, tr = (int(v) for v in os.environ["HAWQ_ER_SPLIT_TILES"].split(".")[2 * k:2 * k + 2])
-                        pair.expand.tile = te
-                        if pair.reduce is not None:
-                            pair.reduce.tile = tr
-                    self.er_choice[name] = er.tile
-                    continue
                 nvar = _lib.load().hawq_conv_expand_reduce_variants(C.byref(er))
                 times = {}
                 for rnd in range(2):   # (no variant may be refused here: an error propagates)
@@ -1140,25 +1049,23 @@ class IntegerEngine(GraphRunner):
                         er.tile = tile
                         ms = timer.elapsed_ms(partial(_lib.call, "hawq_conv_expand_reduce", C.byref(er), sp), reps)
                         times[tile] = min(times.get(tile, ms), ms)
-                er.tile = min(times, key=times.get)
+                v = min(times, key=times.get)
                 self._er_times[name] = dict(times)
-                te, pair.split_e, ms_e = best_tile(pair.expand)
-                tr, pair.split_r, ms_r = best_tile(pair.reduce) if pair.reduce is not None else (0, 0, 0.0)
-                pair.expand.tile = te
-                if pair.reduce is not None:
-                    pair.reduce.tile = tr
-                pair.fused = times[er.tile] <= ms_e + ms_r
+                t_e, te, se = time_tiles(timer, pair.expand)   # the two-launch form: each launch's fastest tile or split-K form
+                t_r, tr, sr = time_tiles(timer, pair.reduce) if pair.reduce is not None else ({0: 0.0}, 0, 0)
+                ms_e, ms_r = min(t_e.values()), min(t_r.values())
+                fused = times[v] <= ms_e + ms_r
                 if os.environ.get("HAWQ_AUTOTUNE_LOG"):
-                    log = [f"{t}:{v / reps * 1e3:.1f}" for t, v in times.items()]
+                    log = [f"{t}:{x / reps * 1e3:.1f}" for t, x in times.items()]
                     print(f"[autotune N={er.expand.N}] {name}+next reduce: fused variants (us) {' '.join(log)} | separate "
-                          f"{ms_e / reps * 1e3:.1f} (tile {te}, split {pair.split_e}) + {ms_r / reps * 1e3:.1f} (tile {tr}, split {pair.split_r})"
-                          f" -> {'fused' if pair.fused else 'separate'}",
-                          file=sys.stderr)
-                self.er_choice[name] = er.tile if pair.fused else 0
-                self.er_split_tiles = getattr(self, "er_split_tiles", {})
-                self.er_split_tiles[name] = (te, tr)
+                          f"{ms_e / reps * 1e3:.1f} (tile {te}, split {se}) + {ms_r / reps * 1e3:.1f} (tile {tr}, split {sr})"
+                          f" -> {'fused' if fused else 'separate'}", file=sys.stderr)
+                variants.append(v if fused else 0)
+                split_tiles.append((te, tr))
+                pair_splitk[2 * k:2 * k + 2] = se, sr
         torch.cuda.synchronize(self.dev)
         self.flags.zero_()  # tuning launches ran on whatever the buffers held; only real forwards may raise the flag
+        return ChainChoice(chosen, variants, split_tiles, splitk + pair_splitk)
 
     def _autotune_joint(self, reps: int = 4, slack: float = 1.6, top: int = 6):
         """Second tuning pass of a plan with concurrent sub-batch chains.  Each chain has picked its tiles by timing its
@@ -1191,6 +1098,7 @@ class IntegerEngine(GraphRunner):
             return best
 
         log = bool(os.environ.get("HAWQ_AUTOTUNE_LOG"))
+        chosen = [sub._choice() for sub in subs]   # what the pass decides, applied at its end (the lists are edited in place)
         with torch.cuda.stream(self.stream):
             n_conv = len(subs[0]._conv_args)
             if any(len(sub._conv_args) != n_conv or sub._conv_names != subs[0]._conv_names for sub in subs):
@@ -1206,12 +1114,12 @@ class IntegerEngine(GraphRunner):
                 lim = slack * min(iso.values())
                 cand = sorted((t for t, v in iso.items() if v <= lim), key=iso.get)[:top]
                 res = {}
-                tiles0 = [sub._conv_args[k].tile for sub in subs]   # each chain's best tile: what a split-K choice keeps for the unsplit form
+                tiles0 = [ch.tiles[k] for ch in chosen]   # each chain's best tile: what a split-K choice keeps for the unsplit form
 
                 def choose(t):   # t > 0: tile id; t < 0: split-K with -t slices
-                    for sub, t0 in zip(subs, tiles0):
-                        sub._conv_args[k].tile = t if t > 0 else t0
-                        sub._conv_ops[k].splitk = -t if t < 0 else 0
+                    for sub, ch, t0 in zip(subs, chosen, tiles0):
+                        sub._conv_args[k].tile = ch.tiles[k] = t if t > 0 else t0
+                        sub._conv_ops[k].splitk = ch.splitk[k] = -t if t < 0 else 0
                 for t in cand:
                     choose(t)
                     res[t] = joint_ms(lambda sub: sub._conv_ops[k]())
@@ -1220,8 +1128,6 @@ class IntegerEngine(GraphRunner):
                     print(f"[joint tune] {name}: " + " ".join(f"{t}:{iso[t] / reps * 1e3:.1f}/{res[t] / reps * 1e3:.1f}" for t in cand)
                           + f" (us alone / all chains; negative: split-K slices) -> {best}", file=sys.stderr)
                 choose(best)
-                for sub in subs:
-                    sub.tile_choice[name] = sub._conv_args[k].tile
             n_er = len(subs[0]._er_args)
             if all(len(sub._er_args) == n_er and sub._er_names == subs[0]._er_names for sub in subs):
                 for k, name in enumerate(subs[0]._er_names):
@@ -1238,14 +1144,11 @@ class IntegerEngine(GraphRunner):
                     if log:
                         print(f"[joint tune] {name}+next reduce: " + " ".join(f"{v}:{t / reps * 1e3:.1f}" for v, t in sorted(res.items()))
                               + f" (us, all chains; 0 = two launches) -> {best}", file=sys.stderr)
-                    for sub in subs:
-                        pair = sub._er_args[k]
-                        pair.fused = best != 0
-                        if best:
-                            pair.er.tile = best
-                        sub.er_choice[name] = best
+                    for ch in chosen:
+                        ch.variants[k] = best
         torch.cuda.synchronize(self.dev)
-        for sub in subs:
+        for sub, ch in zip(subs, chosen):
+            sub._apply_choice(ch)
             sub.flags.zero_()
 
     # ------------------------------------------------------------------ execution
@@ -1290,7 +1193,7 @@ class IntegerEngine(GraphRunner):
 
     def _ensure_u8(self, N, H, W, x_view=None, lut=None):
         if self.subs:
-            if getattr(self, "x_u8", None) is None or self.x_u8.shape[0] != N:
+            if self.x_u8 is None or self.x_u8.shape[0] != N:
                 self.x_u8 = torch.empty(N, H, W, 3, dtype=torch.uint8, device=self.dev)
                 self.lut_dev = torch.zeros(3, 256, dtype=torch.int8, device=self.dev)
                 self._lut_key = None
@@ -1301,12 +1204,12 @@ class IntegerEngine(GraphRunner):
                     b0 += n
             return
         if x_view is None:
-            if getattr(self, "x_u8", None) is not None and self.x_u8.shape[0] == N:
+            if self.x_u8 is not None and self.x_u8.shape[0] == N:
                 return
             x_view = torch.empty(N, H, W, 3, dtype=torch.uint8, device=self.dev)
             lut = torch.zeros(3, 256, dtype=torch.int8, device=self.dev)
             self._lut_key = None
-        if not hasattr(self, "_stem_u8_tail"):
+        if self._stem_u8_tail is None:
             raise RuntimeError("uint8 input needs the fused stem (not available with keep_accumulators / HAWQ_UNFUSED_STEM)")
         self.x_u8, self.lut_dev = x_view, lut
         self._stem_u8_op = partial(_lib.call, "hawq_stem_fused_u8", x_view.data_ptr(), lut.data_ptr(), N, 3, H, W,

@@ -278,7 +278,7 @@ def test_recorded_plan_replays_without_tuning_and_a_stale_plan_is_refused():
     assert {k: got[k] for k in ("batch", "chains", "tiles", "fused_variants", "fused_split_tiles")} == \
            {k: plan[k] for k in ("batch", "chains", "tiles", "fused_variants", "fused_split_tiles")}
     assert rep.plan_source == "replayed unit-test plan"
-    assert not hasattr(rep.subs[0], "_tile_times") or not rep.subs[0]._tile_times   # nothing was timed
+    assert not any(sub._tile_times or sub._er_times for sub in rep.subs)   # nothing was timed
     # another batch shape on the same engine: tuned, not replayed
     x2 = x[:5]
     assert torch.equal(rep(x2), IntegerEngine(model, chains=1)(x2))
@@ -288,6 +288,65 @@ def test_recorded_plan_replays_without_tuning_and_a_stale_plan_is_refused():
         e = IntegerEngine(model, plan=bad, chains=1)
         assert torch.equal(e(x), ref)
         assert e.plan_source == "tuned in this process"
+
+
+def _same_plan(a, b):
+    skip = ("git_head", "source")
+    return {k: v for k, v in a.items() if k not in skip} == {k: v for k, v in b.items() if k not in skip}
+
+
+def test_committed_two_chain_plan_replays_chain_by_chain():
+    """profiles/plans.json["resnet50_uniform8_b32"] (2 chains, `per_chain`) on the model bench.py builds for it: replayed, each chain
+    with its own recorded tiles, re-exported unchanged, logits bit-equal to an untuned one-chain engine."""
+    import json
+    from hawq_amd.api import calibrate
+    from hawq_amd.engine import IntegerEngine
+    from hawq_amd.skeleton import synthetic_images
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "plans.json")) as f:
+        plan = json.load(f)["resnet50_uniform8_b32"]
+    assert plan["chains"] == 2 and len(plan["per_chain"]) == 2
+    model = H.build_model("resnet50", "uniform8")
+    calibrate(model, synthetic_images(8, seed=0).cuda())
+    x = synthetic_images(32, seed=1).cuda()
+    eng = IntegerEngine(model, plan=dict(plan, source="replayed profiles/plans.json"))
+    y = eng(x).clone()
+    assert eng.plan_source.startswith("replayed")
+    assert _same_plan(eng.export_plan(), plan)
+    assert len(eng.subs) == 2
+    for sub, rec in zip(eng.subs, plan["per_chain"]):
+        assert [a.tile for a in sub._conv_args] == [int(t) for t in rec["tiles"].split(".")]
+    assert torch.equal(y, IntegerEngine(model, chains=1, autotune=False)(x))
+
+
+def test_chains_of_a_tuned_plan_replay_their_own_tiles():
+    """Tune two chains at batch 8, give chain 1 another tile (one the tuner timed, so the library takes it) for one conv launch:
+    the replay runs that tile in chain 1 only, records the chains one by one and computes the same logits."""
+    import json
+    from hawq_amd.api import calibrate
+    from hawq_amd.engine import IntegerEngine
+    from hawq_amd.skeleton import synthetic_images
+    model = H.build_model("resnet50", "uniform8")
+    calibrate(model, _images().cuda())
+    x = (synthetic_images(8, seed=7) * 1.1).cuda()
+    tuned = IntegerEngine(model, chains=2)
+    ref = tuned(x).clone()
+    plan = json.loads(json.dumps(tuned.export_plan()))
+    tiles = [[a.tile for a in sub._conv_args] for sub in tuned.subs]
+    unsplit = [v == 0 for v in tuned.subs[1].splitk_choice()]   # (a split launch does not run its tile)
+    k, other = next((k, t) for k, name in enumerate(tuned.subs[1]._conv_names) if unsplit[k]
+                    for t in tuned.subs[1]._tile_times[name] if t > 0 and t != tiles[1][k] and t != tiles[0][k])
+    tiles[1][k] = other
+    strings = lambda i: {"tiles": ".".join(map(str, tiles[i])), "fused_variants": plan["fused_variants"],
+                         "fused_split_tiles": plan["fused_split_tiles"]}
+    per = plan.get("per_chain") or [strings(0), strings(1)]
+    per[1] = dict(per[1], tiles=strings(1)["tiles"])
+    rep = IntegerEngine(model, plan=dict(plan, per_chain=per))
+    y = rep(x).clone()
+    assert rep.plan_source.startswith("replayed")
+    assert [[a.tile for a in sub._conv_args] for sub in rep.subs] == tiles and tiles[0][k] != other
+    got = rep.export_plan()
+    assert [p["tiles"] for p in got["per_chain"]] == [strings(0)["tiles"], strings(1)["tiles"]] and got["tiles"] == plan["tiles"]
+    assert torch.equal(y, ref) and torch.equal(rep(x), ref)
 
 
 def test_model_call_uses_fused_engine_and_cpu_raises():

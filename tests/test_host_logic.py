@@ -593,27 +593,6 @@ def test_pack_w1x1_k128_matches_the_c_twin_and_a_loop_restatement():
     assert lib.hawq_pack_w1x1_k128(bad.ctypes.data_as(ctypes.c_void_p), bad.ctypes.data_as(ctypes.c_void_p), 64, 64) != 0
 
 
-def test_recorded_plan_is_replayed_per_chain_and_by_launch_name():
-    """ADVICE r4 / round 5, host logic only (no GPU): a chain of a multi-chain engine reads ITS entry of a plan's `per_chain` list, the
-    top-level strings otherwise; a chain the plan does not list makes the plan stale; `chains` is never read per chain."""
-    from hawq_amd.engine import IntegerEngine, StalePlan
-    e = IntegerEngine.__new__(IntegerEngine)
-    e.plan = {"chains": 2, "tiles": "1.2.3", "fused_variants": "1.0", "per_chain": [{"tiles": "1.2.3", "fused_variants": "1.0"},
-                                                                                   {"tiles": "4.5.6", "fused_variants": ""}]}
-    e._plan_on = True
-    assert e._fixed("tiles") == "1.2.3" and e._fixed("chains") == "2"          # the parent engine: top-level strings
-    e._chain_index = 1
-    assert e._fixed("tiles") == "4.5.6"
-    assert e._fixed("fused_variants") == "1.0"                                  # an empty per-chain entry falls back to the top level
-    assert e._fixed("chains") == "2"
-    e._chain_index = 2
-    with pytest.raises(StalePlan):
-        e._fixed("tiles")
-    e._plan_on = False                                                          # plan not applicable to this batch shape: environment or tune
-    os.environ.pop("HAWQ_TILES", None)
-    assert e._fixed("tiles") is None
-
-
 def test_profile_tools_on_a_synthetic_kernel_trace(tmp_path):
     """tools/dominant_kernel.py and tools/rocprof_overlap.py (run on the GPU box by tools/profile_round.sh) against a hand-made
     rocprofv3-style `kernels` table: two chains, three forwards, stem + two convs per chain and forward, one tuning kernel."""
