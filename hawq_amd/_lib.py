@@ -87,6 +87,17 @@ class IncepPoolArgs(C.Structure):
         "pre", "m1", "ek1", "lo1", "hi1", "post", "m2", "ek2", "lo2", "hi2")]
 
 
+class ImageDesc(C.Structure):
+    """struct hawq_image_desc (include/hawq_mi355.h): one image of a hawq_image_batch launch."""
+    _fields_ = [("base", C.c_uint64)] + [(n, i32) for n in (
+        "h", "w", "oh", "ow", "top", "left", "skip_h", "skip_v", "hb_off", "hc_off", "vb_off", "vc_off", "kh", "kv")]
+
+
+class ImageTile(C.Structure):
+    """struct hawq_image_tile (include/hawq_mi355.h): the crop rows one workgroup of hawq_image_batch computes."""
+    _fields_ = [("image", i32), ("row0", i32), ("rows", i32)]
+
+
 # name -> (argtypes); every function returns int except hawq_last_error
 SIGNATURES = {
     "hawq_abi_version": [],
@@ -133,6 +144,9 @@ SIGNATURES = {
     "hawq_quantize_im2col3x3s2": [vp, vp, i32, i32, i32, i32, f32, i32, i32, vp],
     "hawq_quantize_im2col3x3s2_u8": [vp, vp, vp, i32, i32, i32, i32, vp],
     "hawq_resample_u8": [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp],
+    "hawq_image_batch": [vp, i32, vp, i32, vp, vp, i32, i32, vp],
+    "hawq_image_batch_ok": [vp, i32, vp, i32, vp, i64, i32, i32],
+    "hawq_image_batch_lds_budget": [],
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
     "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],

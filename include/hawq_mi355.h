@@ -425,6 +425,42 @@ int hawq_quantize_im2col3x3s2_u8(const uint8_t *x, const int8_t *lut, int8_t *ou
 int hawq_resample_u8(const uint8_t *in, int32_t in_w, int32_t C, const int32_t *bounds, const int32_t *coef, int32_t ksize,
                      int32_t out_n, int32_t horizontal, int32_t lines, int32_t line0, uint8_t *out, void *stream);
 
+/* Resize + CenterCrop of a whole batch of variable-size images in ONE launch (hawq_amd/csrc/image_batch.hip): both passes above, the
+ * 8-bit intermediate kept in LDS, the crop written straight into out uint8 [n_images][crop][crop][3].  Three channels only.
+ * One descriptor per image; every *_off is an offset in int32 words into one packed coefficient table `coef`:
+ *   hb_off / vb_off: bounds of the crop's output columns / rows, crop x (first input index, taps), absolute input indices;
+ *   hc_off / vc_off: their coefficients, crop x kh / crop x kv (22 fractional bits, as hawq_resample_u8).
+ * skip_h / skip_v: the resized width / height equals the input's, Pillow skips that pass and the crop window is copied (the
+ * offsets and ksize of a skipped pass are not read).  oh, ow: the resized size the crop window (top, left, crop) lies in.
+ * A descriptor with h = w = 0 marks an image the launch leaves alone (its band exceeds the LDS budget and the caller resamples it with
+ * hawq_resample_u8): it takes no tile and its rows of out are not written. */
+typedef struct hawq_image_desc {
+    uint64_t base;          /* device address of the image, uint8 [h][w][3], any alignment */
+    int32_t h, w, oh, ow;
+    int32_t top, left;
+    int32_t skip_h, skip_v;
+    int32_t hb_off, hc_off, vb_off, vc_off;
+    int32_t kh, kv;
+} hawq_image_desc;
+/* One workgroup: crop rows row0 .. row0 + rows - 1 of image `image`.  It resamples horizontally the crop columns of the input rows
+ * y0 .. y1 - 1 those output rows read (from the vertical bounds; top + row0 .. top + row0 + rows - 1 when skip_v) into a uint8 LDS
+ * band of (y1 - y0) rows x pitch bytes, pitch = crop * 3 rounded up to a multiple of 4, then runs the vertical pass out of it. */
+typedef struct hawq_image_tile {
+    int32_t image, row0, rows;
+} hawq_image_tile;
+/* hawq_image_batch: desc, tiles and coef are device copies of the tables; lds_bytes (dynamic LDS of the launch) >= every tile's band.
+ * hawq_image_batch_ok launches nothing and reads the HOST copies of the tables (desc[i].base is not looked at): 1 when every tile's
+ * row range lies inside the crop and the tiles of each image cover its crop rows exactly once, every band fits lds_bytes,
+ * lds_bytes <= hawq_image_batch_lds_budget, every bounds / coefficient slice lies inside the coef_words words of host_coef, every
+ * (first, taps) pair read stays inside its image with taps <= ksize, and the crop window lies inside the resized image (inside the
+ * input for a skipped pass); else 0 with the reason in hawq_last_error().  Callers run it on every batch before the upload, so the
+ * kernel never sees a table it has not passed.  hawq_image_batch_lds_budget: 65536 bytes - two workgroups share a CU's LDS. */
+int hawq_image_batch(const hawq_image_desc *desc, int32_t n_images, const hawq_image_tile *tiles, int32_t n_tiles, const int32_t *coef,
+                     uint8_t *out, int32_t crop, int32_t lds_bytes, void *stream);
+int hawq_image_batch_ok(const hawq_image_desc *host_desc, int32_t n_images, const hawq_image_tile *host_tiles, int32_t n_tiles,
+                        const int32_t *host_coef, int64_t coef_words, int32_t crop, int32_t lds_bytes);
+int hawq_image_batch_lds_budget(void);
+
 /* ---- range statistics of the un-frozen QuantAct (calibration / QAT range tracking) -----------------
  * x.data.min(), x.data.max() (quant_modules.py:233-236) of a fp32 tensor -> out2[0], out2[1] (device floats).
  * scratch: >= 8 bytes of device memory owned by the caller for the duration of the call. */
