@@ -13,22 +13,27 @@ branches launch one after another on the plan's stream:
   then the 1x1 conv as above;
 * max-pool branches: ``hawq_incep_maxpool3s2`` (16-bit ``q_input_act``, max, concat rescale) into the unit buffer.
 Stem: the input QuantAct (``hawq_fakequant_f32`` + ``hawq_f32_nchw_to_q_nhwc``; under ``fused_stem`` one launch with conv1),
-five convs, two max pools.  Head:
-``hawq_incep_global_avgpool`` (8 x 8 trunc rule + ``q_concat_activ``), the classifier as a 1x1 RAW conv and
-``hawq_acc_nhwc_to_f32_nchw`` (fp32 logits = (acc + bias) * fl(S_w * S_a), quant_modules.py:125-130).
+five convs, two max pools.  Head: ``hawq_incep_global_avgpool`` (8 x 8 trunc rule + ``q_concat_activ``), the classifier as a 1x1
+RAW conv and ``hawq_acc_nhwc_to_f32_nchw`` (fp32 logits = (acc + bias) * fl(S_w * S_a), quant_modules.py:125-130).
 uint8 images (``forward_uint8``): the same plan and buffers with its first three launches (input QuantAct + conv1) replaced by one
 ``hawq_incep_stem_u8``, whose table look-up is ToTensor + Normalize + the input QuantAct (``input_quant_lut``); a graph of its own.
 
 Every requant is the exact dyadic form of fixedpoint_fn (``requant_table(..., lift=False)``).
 
+Mechanism.  ``_build`` emits one ``Launch`` record per launch of that default plan, in its order (``_launches``: 147 records, the
+input QuantAct's two launches and conv1 among the stem's), and nothing rewrites the list afterwards.  What ``tune``, ``plan=`` or
+the defaults decide is one value (``_choose``): the tile id per conv launch or None, and the grouped launches or None.  One writer
+(``_write``) turns records + choice + the engine's options into the callables of a chain (``_ops``, ``_ops_u8``): it picks the entry
+point of every record, the stem that heads the chain and, with groups, the order (``grouped_order``, a pure function).
+
 Conv tiles.  By default every conv launch (94 convs + the classifier) is ``hawq_incep_conv``.  ``InceptionEngine(model, tune=True)``
 times, once the buffers of a batch shape exist and before the graph is captured, every conv launch on its own buffers with tile 0
 (that kernel) and with every LDS-tiled kernel of ``hawq_incep_conv_tiled`` that ``hawq_incep_conv_tile_ok`` accepts (HIP events,
-``_TUNE_WARMUP`` untimed + ``_TUNE_REPS`` timed launches, the median), keeps the fastest id per launch and issues
-``hawq_incep_conv_tiled`` with it; launch list, order, stream and buffers are those of the default plan, and every tile computes
-the same integers, so the result is bit-identical.  The uint8 plan shares the choice (its stem kernel replaces conv1).
+``_TUNE_WARMUP`` untimed + ``_TUNE_REPS`` timed launches, the median: ``EventTimer.median_us``), keeps the fastest id per launch and
+issues ``hawq_incep_conv_tiled`` with it; launch list, order, stream and buffers are those of the default plan, and every tile
+computes the same integers, so the result is bit-identical.  The uint8 plan shares the choice (its stem kernel replaces conv1).
 ``export_plan()`` returns the choice as a JSON-serialisable dict (``make_plan``); ``InceptionEngine(model, plan=p)`` replays it
-without timing anything and raises ``engine.StalePlan`` when it does not fit (``check_plan``: another launch list, tile inventory
+without timing anything and raises ``plan.StalePlan`` when it does not fit (``check_plan``: another launch list, tile inventory
 or batch shape, or a tile the library now refuses).
 
 Pool kernels.  By default the 49 pool / requant launches are the four entry points named above.  ``InceptionEngine(model,
@@ -40,20 +45,20 @@ it composes with ``tune`` and ``plan``.
 Fused fp32 stem.  ``InceptionEngine(model, fused_stem=True)`` replaces the fp32 plan's first three launches (``hawq_fakequant_f32``,
 ``hawq_f32_nchw_to_q_nhwc``, conv1) by one ``hawq_incep_stem_f32`` on ``x_in`` (hawq_amd/csrc/incep_stem_f32.hip), the fp32 twin of the
 uint8 stem kernel: the same bytes in conv1's output buffer, 145 launches instead of 147, and neither the fake-quantised fp32 copy nor
-the 16-channel int8 image is allocated.  A model whose input QuantAct or conv1 the kernel cannot take raises ``PlanNotApplicable``
-(``_stem_refusal``, ``hawq_incep_stem_f32_ok``) - there is no fall-back to the three launches.  ``conv_launches`` keeps conv1's key,
-so plans are interchangeable between engines with and without the option; a fused-stem plan carries conv1's tile id and ignores it,
-as the uint8 plan does, and ``tune=True`` does not time conv1 (its entry records tile 0 and no times).  An engine argument like
-``fast_pools``, composing with it, ``tune``, ``plan`` and ``use_graph``.
+the 16-channel int8 image is allocated (the input QuantAct's two records carry NULL for them and are never issued).  A model whose
+input QuantAct or conv1 the kernel cannot take raises ``PlanNotApplicable`` (``_stem_refusal``, ``hawq_incep_stem_f32_ok``) - there is
+no fall-back to the three launches.  ``conv_launches`` keeps conv1's key, so plans are interchangeable between engines with and
+without the option; a fused-stem plan carries conv1's tile id and ignores it, as the uint8 plan does, and ``tune=True`` does not
+time conv1 (its entry records tile 0 and no times).  An engine argument like ``fast_pools``, composing with every other one.
 
 Grouped conv launches.  ``InceptionEngine(model, grouped=True)`` issues the sibling convs at one depth of a unit's branches
 (``conv_levels``) as ONE ``hawq_incep_conv_group`` launch (hawq_amd/csrc/incep_group.hip): members keep their argument blocks, buffers
 and output slices, only the grid is shared, and the launch writes the bytes the single launches write.  A grouped unit issues its
-entry pool / requant launches first (branch-input requants, the average pool, the max-pool branch), then level 1, level 2, ...; the
-inner-concat requant of an 8 x 8 unit follows the level that holds its 1x3 / 3x1 pair.  Every op owns its output buffer, so the order
-across branches is free.  A level of one conv stays a single launch: 27 grouped launches holding 74 convs and 21 single ones instead
-of 95, ``n_launches`` 100 instead of 147.  ``conv_launches`` keeps the default plan's order, so tile plans cross over between engines
-with and without the option.  Which levels are grouped, and on which tile (one id in 1 .. T for a whole group):
+level-0 records first (branch-input requants, the average pool, the max-pool branch), then level 1, level 2, ...; the inner-concat
+requant of an 8 x 8 unit follows the level that holds its 1x3 / 3x1 pair (``grouped_order``).  Every launch owns its output buffer,
+so the order across branches is free.  A level of one conv stays a single launch: 27 grouped launches holding 74 convs and 21
+single ones instead of 95, ``n_launches`` 100 instead of 147.  ``conv_launches`` keeps the default plan's order, so tile plans cross
+over between engines with and without the option.  Which levels are grouped, and on which tile (one id in 1 .. T for a whole group):
 * neither ``tune`` nor ``plan``: every level of two or more convs on tile 3 if ``hawq_incep_conv_group_ok`` takes it, else singles;
 * ``tune=True``: after the per-conv timing every such level is timed on every tile the group accepts (the same method and buffers)
   and kept with its fastest tile only if that beats the sum of its members' best single times (``group_candidates`` has both);
@@ -67,12 +72,13 @@ import ctypes as C
 import hashlib
 import json
 from functools import partial
+from itertools import groupby
 
 import numpy as np
 import torch
 
 from . import _lib
-from .engine import StalePlan
+from .plan import StalePlan
 from .quant_modules import QuantAct
 from .quant_utils import requant_table
 from .runner import EventTimer, GraphRunner, _rng
@@ -203,6 +209,38 @@ def check_groups(groups, n_convs, levels, ok):
     return out
 
 
+class Launch:
+    """One launch of the default plan: its entry point `name`; `args`, the call's arguments before the stream (for a conv or a pool
+    the ctypes block alone); `kind` "conv" (`ref`: its index in the conv list), "pool" (a pool / requant; `ref`: its
+    ``hawq_incep_pool_v`` op id) or "other"; `place` "stem", the unit's number or "head"; and its `level` inside a unit: 0 for
+    what a branch does before its first conv, d for a conv at depth d, and for an inner-concat requant the level of the 1x3 / 3x1
+    pair it follows."""
+    __slots__ = ("name", "args", "kind", "ref", "place", "level")
+
+    def __init__(self, name, args, kind="other", ref=None, place="stem", level=0):
+        self.name, self.args, self.kind, self.ref, self.place, self.level = name, args, kind, ref, place, level
+
+
+def grouped_order(launches, groups):
+    """The sequence a grouped engine issues: entries (False, i) for record i of `launches` alone and (True, g) for the grouped launch
+    g of `groups` = [(member conv indices, tile)], issued once, where its first member is met.  Stem and head stay in place; a unit
+    issues its level-0 records in their default order, then its levels in ascending order, each in the default order, an inner-concat
+    requant directly after the level of its pair.  Reads the records' tags only."""
+    group_of = {c: g for g, (convs, _) in enumerate(groups) for c in convs}
+    order, issued = [], set()
+    for place, block in groupby(range(len(launches)), key=lambda i: launches[i].place):
+        if place not in ("stem", "head"):   # a stable sort: the default order within a level, its convs before its requant
+            block = sorted(block, key=lambda i: (launches[i].level, launches[i].kind != "conv"))
+        for i in block:
+            g = group_of.get(launches[i].ref) if launches[i].kind == "conv" else None
+            if g is None:
+                order.append((False, i))
+            elif g not in issued:
+                issued.add(g)
+                order.append((True, g))
+    return order
+
+
 class _T:
     """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale."""
 
@@ -222,7 +260,6 @@ class InceptionEngine(GraphRunner):
         self.dev = next(model.parameters()).device
         self.stream = None   # created with the first plan: building the engine object needs no device
         self._batch, self._ops, self._ops_u8, self._u8_why = None, [], None, None
-        self._stem_conv = None               # index in ``_convs`` of a conv the fp32 plan does not launch (conv1 under fused_stem)
 
     def _zeros(self, *a, **k):
         """a plan buffer: kept alive with the plan (the captured launches hold its address)"""
@@ -230,8 +267,15 @@ class InceptionEngine(GraphRunner):
         self._keep.append(t)
         return t
 
-    # ------------------------------------------------------------------ launch builders
-    def _pool(self, name, src: _T, out_buf, out_bits, ldo, c_off, c, h, w, pre=None, post=None):
+    # ------------------------------------------------------------------ launch records
+    def _emit(self, name, args, kind="other", ref=None, level=0):
+        """the next record of the default plan, at the place ``_build`` is at"""
+        r = Launch(name, args, kind, ref, self._place, level)
+        self._launches.append(r)
+        if kind == "conv":
+            self._convs.append(r)   # the conv list: `ref` is the record's index in it
+
+    def _pool(self, name, src: _T, out_buf, out_bits, ldo, c_off, c, h, w, pre=None, post=None, level=0):
         a = _lib.IncepPoolArgs()
         a.in_, a.out = src.buf.data_ptr(), out_buf.data_ptr()
         a.N, a.H, a.W, a.C = self.N, src.h, src.w, c
@@ -242,14 +286,9 @@ class InceptionEngine(GraphRunner):
         if post is not None:
             a.post, (a.m2, a.ek2, a.lo2, a.hi2) = 1, post
         self._keep.append(a)
-        op = _lib.INCEP_POOL_OPS[name]
-        self._pools.append((len(self._ops), a, op))
-        if self.fast_pools and _lib.load().hawq_incep_pool_v_ok(C.byref(a), op):
-            self._ops.append(partial(_lib.call, "hawq_incep_pool_v", C.byref(a), op, self.stream.cuda_stream))
-        else:
-            self._ops.append(partial(_lib.call, name, C.byref(a), self.stream.cuda_stream))
+        self._emit(name, (a,), "pool", _lib.INCEP_POOL_OPS[name], level)
 
-    def _conv(self, ic, src: _T, dst=None, c_off=0, second=None):
+    def _conv(self, ic, src: _T, dst=None, c_off=0, second=None, level=0):
         """Q_InceptConv `ic` on `src` (int8): REQUANT into a new buffer, or - `dst`, `second` = (s_out2, act2) - REQUANT2 into the
         channel slice `c_off` of `dst`.  Returns the output tensor (or `dst`)."""
         cb, act = ic.q_convbn, ic.q_activ
@@ -298,9 +337,7 @@ class InceptionEngine(GraphRunner):
         a.m, a.ek, a.q_lo, a.q_hi = t[2].data_ptr(), t[3].data_ptr(), lo, hi
         a.out_bits, a.ldo, a.c_off = out.bits, ldo, c_off
         self._keep += t + [a]
-        self._convs.append((len(self._ops), a))
-        self._ops.append(partial(_lib.call, "hawq_incep_conv", C.byref(a), self.stream.cuda_stream))
-        self._last_conv = (a, w_int)
+        self._emit("hawq_incep_conv", (a,), "conv", len(self._convs), level)
         return out
 
     def _requant_input(self, act, src: _T):
@@ -321,17 +358,18 @@ class InceptionEngine(GraphRunner):
             raise PlanNotApplicable("unit output other than 16-bit symmetric")
         s_u = _scale(uact)
         branches = list(unit.branches.children())
+        ucs = unit_convs(unit)   # the one walk over the branches: every conv of the unit with its branch and level
+        mine = [[(ic, d) for ic, b, d in ucs if b == bi] for bi in range(len(branches))]
         widths, Ho, Wo = [], None, None
-        for br in branches:   # output widths and size of each branch
+        for br, cs in zip(branches, mine):   # output widths and size of each branch
             if isinstance(br, Q_MaxPoolBranch):
                 widths.append(src.c)
                 h, w = (src.h - 3) // 2 + 1, (src.w - 3) // 2 + 1
             else:
-                convs = [m for m in br.modules() if hasattr(m, "q_convbn")]
-                c = convs[-1].q_convbn.conv
-                widths.append(c.out_channels * (2 if isinstance(br, Q_ConvSeq3x3Branch) else 1))
+                pair = 2 if isinstance(br, Q_ConvSeq3x3Branch) else 0   # the 1x3 / 3x1 pair keeps the size and doubles the width
+                widths.append(cs[-1][0].q_convbn.conv.out_channels * (2 if pair else 1))
                 h, w = src.h, src.w
-                for ic in (list(br.q_conv_list) if hasattr(br, "q_conv_list") else [br.q_conv]):
+                for ic, _ in cs[:len(cs) - pair]:
                     k, p, st = ic.q_convbn.conv.kernel_size, ic.q_convbn.conv.padding, ic.q_convbn.conv.stride[0]
                     h, w = (h + 2 * p[0] - k[0]) // st + 1, (w + 2 * p[1] - k[1]) // st + 1
             if Ho is not None and (Ho, Wo) != (h, w):
@@ -341,8 +379,8 @@ class InceptionEngine(GraphRunner):
         if cu % 16 or any(x % 16 for x in widths):
             raise PlanNotApplicable("channel counts must be multiples of 16")
         dst = _T(self._zeros(self.N * Ho * Wo * cu, dtype=torch.int16, device=self.dev), Ho, Wo, cu, cu, s_u, 16)
-        off, op0, conv0, inner_ops = 0, len(self._ops), len(self._convs), []
-        for br, wd in zip(branches, widths):
+        off = 0
+        for br, wd, cs in zip(branches, widths, mine):
             if isinstance(br, Q_MaxPoolBranch):
                 ia = br.q_input_act
                 s_b = _scale(ia)
@@ -357,31 +395,24 @@ class InceptionEngine(GraphRunner):
                        src.c, src.pitch, s_p, 8)
                 self._pool("hawq_incep_avgpool_branch", src, t.buf, 8, src.pitch, 0, src.c, src.h, src.w,
                            pre=(*_scalar_table(src.scale, s_b), *_rng(ia)), post=(*_scalar_table(s_b, s_p), *_rng(pa)))
-                self._conv(br.q_conv, t, dst, off, (s_u, uact))
+                self._conv(cs[0][0], t, dst, off, (s_u, uact), level=cs[0][1])
             else:
                 x = self._requant_input(br.q_input_act, src)
-                convs = list(br.q_conv_list) if hasattr(br, "q_conv_list") else [br.q_conv]
                 if isinstance(br, Q_ConvSeq3x3Branch):
-                    for ic in convs:
-                        x = self._conv(ic, x)
+                    for ic, d in cs[:-2]:
+                        x = self._conv(ic, x, level=d)
                     ra = br.q_rescaling_activ
                     s_r = _scale(ra)
-                    half = wd // 2
                     inner = _T(self._zeros(self.N * Ho * Wo * wd, dtype=torch.int16, device=self.dev), Ho, Wo, wd, wd, s_r, 16)
-                    self._conv(br.q_conv1x3, x, inner, 0, (s_r, ra))
-                    self._conv(br.q_conv3x1, x, inner, half, (s_r, ra))
+                    for (ic, d), half in zip(cs[-2:], (0, wd // 2)):
+                        self._conv(ic, x, inner, half, (s_r, ra), level=d)
                     self._pool("hawq_incep_requant", inner, dst.buf, 16, cu, off, wd, Ho, Wo,
-                               post=(*_scalar_table(s_r, s_u), *_rng(uact)))
-                    inner_ops.append((len(self._ops) - 1, len(self._convs) - 1))   # this requant reads what that conv completes
+                               post=(*_scalar_table(s_r, s_u), *_rng(uact)), level=d)   # reads what the pair's level completes
                 else:
-                    for ic in convs[:-1]:
-                        x = self._conv(ic, x)
-                    self._conv(convs[-1], x, dst, off, (s_u, uact))
+                    for ic, d in cs[:-1]:
+                        x = self._conv(ic, x, level=d)
+                    self._conv(cs[-1][0], x, dst, off, (s_u, uact), level=cs[-1][1])
             off += wd
-        levels = [[conv0 + i for i in lv] for lv in conv_levels(unit)]
-        if sorted(c for lv in levels for c in lv) != list(range(conv0, len(self._convs))):
-            raise PlanNotApplicable("conv_levels does not describe this unit's conv launches")
-        self._units.append((op0, len(self._ops), levels, inner_ops))
         return dst
 
     # ------------------------------------------------------------------ plan
@@ -391,28 +422,28 @@ class InceptionEngine(GraphRunner):
         if self.stream is None:
             self.stream = torch.cuda.Stream(device=self.dev)
         self.N, dev, q = N, self.dev, self.model
-        self._ops, self._keep, self.unit_out, self._convs, self._pools = [], [], {}, [], []
-        self._units = []                     # per unit: (first op, end op, conv levels as indices into `_convs`, inner-concat requants)
+        self._launches, self._convs, self._place = [], [], "stem"   # the records, the conv records among them, where `_emit` is
+        self._choice = (None, None)          # the default plan's: no tiles, no groups, the default order
+        self._ops, self._keep, self.unit_out = [], [], {}
         self.conv_tiles, self.conv_us = None, None
         self.group_launches, self.group_candidates = [], []
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
         self.x_in = torch.zeros(N, 3, H, W, dtype=torch.float32, device=dev)
-        self._stem_a, self._stem_conv, stem_why = None, None, self._stem_refusal(ib)
+        self._stem_a, stem_why = None, self._stem_refusal(ib)
         if self.fused_stem:
             if stem_why is not None:
                 raise PlanNotApplicable(f"fused_stem: {stem_why}")
-            # conv1's input as the default plan lays it out (that is conv1's launch key); the buffer itself never exists
-            x = _T(None, H, W, 3, 16, s_in, 8)
+            # conv1's input as the default plan lays it out (that is conv1's launch key); neither buffer of the QuantAct ever exists
+            x, xq_p, x_p = _T(None, H, W, 3, 16, s_in, 8), None, None
         else:
             xq_f = torch.zeros_like(self.x_in)
             x = _T(self._zeros(N * H * W * 16, dtype=torch.int8, device=dev), H, W, 3, 16, s_in, 8)
             self._keep += [xq_f]
-            self._ops.append(partial(_lib.call, "hawq_fakequant_f32", self.x_in.data_ptr(), xq_f.data_ptr(), self.x_in.numel(), inv,
-                                     1.0, lo, hi, self.stream.cuda_stream))
-            self._ops.append(partial(_lib.call, "hawq_f32_nchw_to_q_nhwc", xq_f.data_ptr(), x.buf.data_ptr(), N, 3, H, W, 16, 8,
-                                     1.0, self.stream.cuda_stream))
+            xq_p, x_p = xq_f.data_ptr(), x.buf.data_ptr()
+        self._emit("hawq_fakequant_f32", (self.x_in.data_ptr(), xq_p, self.x_in.numel(), inv, 1.0, lo, hi))
+        self._emit("hawq_f32_nchw_to_q_nhwc", (xq_p, x_p, N, 3, H, W, 16, 8, 1.0))
         for name in ("q_conv1", "q_conv2", "q_conv3", "q_pool1", "q_conv4", "q_conv5", "q_pool2"):
             if name.startswith("q_pool"):
                 h, w = (x.h - 3) // 2 + 1, (x.w - 3) // 2 + 1
@@ -421,22 +452,17 @@ class InceptionEngine(GraphRunner):
                 x = y
             else:
                 x = self._conv(getattr(ib, name), x)
-                if name == "q_conv1":   # the launches up to here are what hawq_incep_stem_u8 replaces
-                    self._conv1 = self._last_conv
-                    if self.fused_stem:   # ... and what hawq_incep_stem_f32 stands for: conv1 keeps its place in `_convs`
-                        a = self._stem_args()
-                        if not _lib.load().hawq_incep_stem_f32_ok(self.x_in.data_ptr(), inv, lo, hi, C.byref(a)):
-                            raise PlanNotApplicable("fused_stem: hawq_incep_stem_f32 refuses conv1")
-                        self._stem_conv = len(self._convs) - 1
-                        self._ops[-1] = partial(_lib.call, "hawq_incep_stem_f32", self.x_in.data_ptr(), inv, lo, hi, C.byref(a),
-                                                self.stream.cuda_stream)
-                    self._n_stem_ops = len(self._ops)
+                if name == "q_conv1" and stem_why is None:   # the records up to here are what a one-launch stem stands for
+                    a = self._stem_a = self._stem_args(self._convs[0].args[0], ib.q_conv1.q_convbn.weight_integer)
+                    if self.fused_stem and not _lib.load().hawq_incep_stem_f32_ok(self.x_in.data_ptr(), inv, lo, hi, C.byref(a)):
+                        raise PlanNotApplicable("fused_stem: hawq_incep_stem_f32 refuses conv1")
         self._ops_u8, self._u8_why = None, stem_why
         if x.bits != 16 or x.pitch != x.c:
             raise PlanNotApplicable("the stem output must be 16-bit")
-        for uname, unit in q.units():
+        for self._place, (uname, unit) in enumerate(q.units()):   # a unit's place is its number
             x = self._unit(unit, x)
             self.unit_out[uname] = x
+        self._place = "head"
         ca = q.features.q_concat_activ
         if ca.activation_bit > 8:
             raise PlanNotApplicable("a 16-bit q_concat_activ")
@@ -462,17 +488,13 @@ class InceptionEngine(GraphRunner):
         a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride = N, 1, 1, K, op, 1, 1, 1
         a.epilogue, a.ldo, a.c_off = _lib.INCEP_RAW, op, 0
         self._keep += t + [a, acc]
-        self._convs.append((len(self._ops), a))
-        self._ops.append(partial(_lib.call, "hawq_incep_conv", C.byref(a), self.stream.cuda_stream))
-        self._ops.append(partial(_lib.call, "hawq_acc_nhwc_to_f32_nchw", acc.data_ptr(), self.logits.data_ptr(), N, O, 1, 1, op,
-                                 t[2].data_ptr(), self.stream.cuda_stream))
-        if self.plan is not None or self.tune:
-            self._choose_tiles((N, H, W))
-        if self.grouped:
-            self._schedule_groups(self._choose_groups())
+        self._emit("hawq_incep_conv", (a,), "conv", len(self._convs))
+        self._emit("hawq_acc_nhwc_to_f32_nchw", (acc.data_ptr(), self.logits.data_ptr(), N, O, 1, 1, op, t[2].data_ptr()))
+        self._choice = self._choose((N, H, W))
+        self._ops = self._write()
         self._batch = (N, H, W)
 
-    # ------------------------------------------------------------------ conv tiles
+    # ------------------------------------------------------------------ readers
     @property
     def op_names(self):
         """library entry point of every launch of the fp32 plan, in order"""
@@ -480,76 +502,40 @@ class InceptionEngine(GraphRunner):
 
     @property
     def conv_launches(self):
-        """``launch_key`` of every conv launch (the classifier last), in launch order"""
-        return [launch_key(a) for _, a in self._convs]
+        """``launch_key`` of every conv launch (the classifier last), in the default plan's order"""
+        return [launch_key(r.args[0]) for r in self._convs]
 
     @property
     def pool_launches(self):
-        """(library entry point, op id of ``hawq_incep_pool_v``) of every pool / requant launch, in launch order"""
-        return [(self._ops[idx].args[0], op) for idx, _, op in self._pools]
+        """(library entry point, op id of ``hawq_incep_pool_v``) of every pool / requant launch, in the default plan's order"""
+        return [(self._ops[self._at[r]].args[0], r.ref) for r in self._launches if r.kind == "pool"]
 
-    def _tile_ok(self, i, tile):
-        if i == self._stem_conv:   # not launched: its tile id is carried through a plan, never used
-            return True
-        return bool(_lib.load().hawq_incep_conv_tile_ok(C.byref(self._convs[i][1]), tile))
-
-    def _choose_tiles(self, batch):
-        """replay ``self.plan`` or time the tiles, then re-issue every conv launch as ``hawq_incep_conv_tiled`` with its id"""
-        keys, T = self.conv_launches, _lib.load().hawq_incep_conv_num_tiles()
-        if self.plan is not None:
-            tiles = check_plan(self.plan, batch, keys, T, self._tile_ok)
-            us = [dict(d) for d in self.plan.get("us", [])] or [{} for _ in keys]
-        else:
-            us = self._time_tiles(T)
-            # tile 0 always competes; ties go to the lower id; a conv that was not timed records tile 0
-            tiles = [min(d, key=lambda t: (d[t], t)) if d else 0 for d in us]
-        for i, ((idx, a), t) in enumerate(zip(self._convs, tiles)):
-            if i == self._stem_conv:
-                continue
-            self._ops[idx] = partial(_lib.call, "hawq_incep_conv_tiled", C.byref(a), int(t), self.stream.cuda_stream)
-        self.conv_tiles, self.conv_us = [int(t) for t in tiles], us
-
-    def _time_tiles(self, T):
-        """microseconds of every accepted tile id per conv launch: each launch on its real buffers, which hold the forward of a
-        random image (every conv launch is a pure function of its input buffer, so repeating it changes nothing)"""
-        sp, n, us = self.stream.cuda_stream, _TUNE_REPS, []
-        with EventTimer(sp, n + 1) as ev:
-            torch.cuda.synchronize(self.dev)
-            with torch.cuda.stream(self.stream):
-                self.x_in.normal_()
-                self._launch_all()
-                for i, (_, a) in enumerate(self._convs):
-                    times = {}
-                    if i == self._stem_conv:   # not launched, not timed
-                        us.append(times)
-                        continue
-                    for tile in range(T + 1):
-                        if tile and not self._tile_ok(i, tile):
-                            continue
-                        for _ in range(_TUNE_WARMUP):
-                            _lib.call("hawq_incep_conv_tiled", C.byref(a), tile, sp)
-                        ev.record(0)
-                        for r in range(n):
-                            _lib.call("hawq_incep_conv_tiled", C.byref(a), tile, sp)
-                            ev.record(r + 1)
-                        self.n_timing_launches += _TUNE_WARMUP + n
-                        times[tile] = sorted(ev.ms(r, r + 1) * 1000.0 for r in range(n))[n // 2]
-                    us.append(times)
-        torch.cuda.synchronize(self.dev)
-        return us
-
-    # ------------------------------------------------------------------ grouped conv launches
     @property
     def conv_level_list(self):
         """every conv level of every unit, in unit order, as lists of indices into ``conv_launches``"""
-        return [lv for _, _, levels, _ in self._units for lv in levels]
+        convs = [r for r in self._convs if r.place not in ("stem", "head")]
+        return [[r.ref for r in convs if (r.place, r.level) == k] for k in sorted({(r.place, r.level) for r in convs})]
+
+    @property
+    def n_launches(self):
+        return len(self._ops)
+
+    @property
+    def n_launches_u8(self):
+        """launches of the uint8 plan (built by the first ``forward_uint8`` of a batch shape)"""
+        return len(self._ops_u8)
+
+    def _tile_ok(self, i, tile):
+        if self.fused_stem and i == 0:   # conv1 is not launched: its tile id is carried through a plan, never used
+            return True
+        return bool(_lib.load().hawq_incep_conv_tile_ok(C.byref(self._convs[i].args[0]), tile))
 
     def _group_args(self, convs):
         """the argument block of one grouped launch: copies of the members' blocks, in the order of `convs`"""
         g = _lib.IncepGroupArgs()
         g.n = len(convs)
         for k, c in enumerate(convs):
-            g.conv[k] = self._convs[c][1]
+            g.conv[k] = self._convs[c].args[0]
         return g
 
     def _group_ok(self, convs, tile):
@@ -557,98 +543,62 @@ class InceptionEngine(GraphRunner):
             return False
         return bool(_lib.load().hawq_incep_conv_group_ok(C.byref(self._group_args(convs)), tile))
 
-    def _choose_groups(self):
-        """[(member conv indices, tile), ...]: from the plan, from timing (``tune``), or every level of two or more convs on tile 3"""
+    # ------------------------------------------------------------------ the choice
+    def _choose(self, batch):
+        """What a plan decides, as one value: (tile id per conv launch, or None; grouped launches [(member conv indices, tile)], or
+        None on an engine without ``grouped``).  From ``self.plan``, else from timing (``tune``), else the defaults: no tiles, and
+        every level of two or more convs on tile 3 that the library takes.  Leaves ``conv_tiles`` and what was recorded or measured
+        (``conv_us``, ``group_candidates``) for the readers and ``export_plan``."""
+        T, tiles, groups = _lib.load().hawq_incep_conv_num_tiles(), None, None
         # members with the longest K loop first, so that the heavy workgroups start first (the order is free, and unmeasured)
-        klen = lambda c: -(self._convs[c][1].KH * self._convs[c][1].KW * self._convs[c][1].Cin)   # noqa: E731
-        cands = [sorted(lv, key=klen) for lv in self.conv_level_list if len(lv) >= 2]
+        klen = lambda c: -(self._convs[c].args[0].KH * self._convs[c].args[0].KW * self._convs[c].args[0].Cin)   # noqa: E731
+        cands = [sorted(lv, key=klen) for lv in self.conv_level_list if len(lv) >= 2] if self.grouped else []
         if self.plan is not None:
-            chosen = check_groups(self.plan.get("groups"), len(self._convs), self.conv_level_list, self._group_ok)
-            us = {tuple(g["convs"]): dict(g.get("us", {})) for g in self.plan.get("groups") or []}
-            self.group_candidates = [{"convs": list(c), "tile": t, "us": us[tuple(c)], "kept": True} for c, t in chosen]
-            return chosen
-        if not self.tune:
-            return [(c, 3) for c in cands if self._group_ok(c, 3)]
-        T = _lib.load().hawq_incep_conv_num_tiles()
-        timed = self._time_groups([(c, [t for t in range(1, T + 1) if self._group_ok(c, t)]) for c in cands])
-        chosen = []
-        for c, us in zip(cands, timed):
-            if not us:
-                continue
-            tile = min(us, key=lambda t: (us[t], t))
-            singles = sum(self.conv_us[i][self.conv_tiles[i]] for i in c)
-            kept = us[tile] < singles
-            self.group_candidates.append({"convs": c, "tile": tile, "us": {**{str(t): v for t, v in us.items()}, "singles": singles},
-                                          "kept": kept})
-            if kept:
-                chosen.append((c, tile))
-        return chosen
+            tiles = check_plan(self.plan, batch, self.conv_launches, T, self._tile_ok)
+            self.conv_us = [dict(d) for d in self.plan.get("us", [])] or [{} for _ in tiles]
+            if self.grouped:
+                groups = check_groups(self.plan.get("groups"), len(self._convs), self.conv_level_list, self._group_ok)
+                us = {tuple(g["convs"]): dict(g.get("us", {})) for g in self.plan.get("groups") or []}
+                self.group_candidates = [{"convs": list(c), "tile": t, "us": us[tuple(c)], "kept": True} for c, t in groups]
+        elif self.tune:
+            self.conv_us, timed = self._time(T, cands)
+            # tile 0 always competes; ties go to the lower id; a conv that was not timed records tile 0
+            tiles = [min(d, key=lambda t: (d[t], t)) if d else 0 for d in self.conv_us]
+            for c, us in zip(cands, timed):   # a group is kept, on its fastest tile, only if that beats its members' single launches
+                if us:
+                    tile = min(us, key=lambda t: (us[t], t))
+                    singles = sum(self.conv_us[i][tiles[i]] for i in c)
+                    self.group_candidates.append({"convs": c, "tile": tile, "kept": us[tile] < singles,
+                                                  "us": {**{str(t): v for t, v in us.items()}, "singles": singles}})
+            if self.grouped:
+                groups = [(g["convs"], g["tile"]) for g in self.group_candidates if g["kept"]]
+        elif self.grouped:
+            groups = [(c, 3) for c in cands if self._group_ok(c, 3)]
+        self.conv_tiles = None if tiles is None else [int(t) for t in tiles]
+        return self.conv_tiles, groups
 
-    def _time_groups(self, cands):
-        """microseconds of every (group, tile) of `cands` = [(convs, tiles)], as ``_time_tiles`` times a conv: on the plan's buffers,
-        which hold the forward ``_time_tiles`` ran"""
-        sp, n, out = self.stream.cuda_stream, _TUNE_REPS, []
-        with EventTimer(sp, n + 1) as ev:
+    def _time(self, T, cands):
+        """Microseconds (HIP events, ``EventTimer.median_us``) of every accepted tile id per conv launch, and of every accepted tile
+        per candidate group of `cands`: each launch on its real buffers, which hold the forward of a random image (every conv launch
+        is a pure function of its input buffer, so repeating it changes nothing)."""
+        sp, gtiles = self.stream.cuda_stream, [[t for t in range(1, T + 1) if self._group_ok(c, t)] for c in cands]
+
+        def us(name, block, tiles):
+            self.n_timing_launches += (_TUNE_WARMUP + _TUNE_REPS) * len(tiles)
+            return {t: ev.median_us(lambda: _lib.call(name, C.byref(block), t, sp), _TUNE_REPS, _TUNE_WARMUP) for t in tiles}
+
+        with EventTimer(sp, _TUNE_REPS + 1) as ev:
+            torch.cuda.synchronize(self.dev)
             with torch.cuda.stream(self.stream):
-                for convs, tiles in cands:
-                    g, times = self._group_args(convs), {}
-                    for tile in tiles:
-                        for _ in range(_TUNE_WARMUP):
-                            _lib.call("hawq_incep_conv_group", C.byref(g), tile, sp)
-                        ev.record(0)
-                        for r in range(n):
-                            _lib.call("hawq_incep_conv_group", C.byref(g), tile, sp)
-                            ev.record(r + 1)
-                        self.n_timing_launches += _TUNE_WARMUP + n
-                        times[tile] = sorted(ev.ms(r, r + 1) * 1000.0 for r in range(n))[n // 2]
-                    out.append(times)
+                self.x_in.normal_()
+                for op in self._write():   # ``_choice`` is still the default plan's
+                    op()
+                # conv1 under fused_stem is not launched, not timed
+                convs = [us("hawq_incep_conv_tiled", r.args[0], [t for t in range(T + 1) if t == 0 or self._tile_ok(i, t)]
+                            if i or not self.fused_stem else []) for i, r in enumerate(self._convs)]
+                groups = [us("hawq_incep_conv_group", self._group_args(c), tiles) for c, tiles in zip(cands, gtiles)]
         torch.cuda.synchronize(self.dev)
-        return out
-
-    def _schedule_groups(self, groups):
-        """Re-issue the units' launches in the grouped order (entry pools / requants, then level by level, an inner-concat requant
-        after the level of its pair) with every group of `groups` as one ``hawq_incep_conv_group`` launch at the place of its
-        level; ``_convs`` / ``_pools`` follow their launches (the members of a group share its index)."""
-        sp, old, new, at = self.stream.cuda_stream, self._ops, [], {}
-        op_of = {c: idx for c, (idx, _) in enumerate(self._convs)}
-        group_of = {c: gi for gi, (convs, _) in enumerate(groups) for c in convs}
-        self.group_launches, done = [], 0
-
-        def emit(idx):
-            at[idx] = len(new)
-            new.append(old[idx])
-
-        for op0, op1, levels, inner_ops in self._units:
-            for idx in range(done, op0):
-                emit(idx)
-            later = {op_of[c] for lv in levels for c in lv} | {idx for idx, _ in inner_ops}
-            for idx in range(op0, op1):   # what a branch does before its first conv
-                if idx not in later:
-                    emit(idx)
-            for lv in levels:
-                issued = set()
-                for c in lv:
-                    gi = group_of.get(c)
-                    if gi is None:
-                        emit(op_of[c])
-                    elif gi not in issued:
-                        issued.add(gi)
-                        convs, tile = groups[gi]
-                        g = self._group_args(convs)
-                        self._keep.append(g)
-                        for m in convs:
-                            at[op_of[m]] = len(new)
-                        new.append(partial(_lib.call, "hawq_incep_conv_group", C.byref(g), int(tile), sp))
-                        self.group_launches.append((list(convs), int(tile)))
-                for idx, c in inner_ops:
-                    if c in lv:
-                        emit(idx)
-            done = op1
-        for idx in range(done, len(old)):
-            emit(idx)
-        self._ops = new
-        self._convs = [(at[idx], a) for idx, a in self._convs]
-        self._pools = [(at[idx], a, op) for idx, a, op in self._pools]
+        return convs, groups
 
     def export_plan(self):
         """The conv tile choice of the current batch shape (and, of a grouped engine, its grouped launches) as a JSON-serialisable
@@ -659,18 +609,56 @@ class InceptionEngine(GraphRunner):
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
                          groups)
 
+    # ------------------------------------------------------------------ the writer
+    def _write(self, u8=False):
+        """The callables of one chain, from the records, ``_choice`` and the engine's options - the only place that makes one.  Per
+        record: a conv alone, tiled with its chosen id or as a member of a grouped launch; a pool on its named entry point or, under
+        ``fast_pools`` where the library takes it, on ``hawq_incep_pool_v``.  The stem's head (the records up to conv1) as it stands,
+        as one ``hawq_incep_stem_f32`` (``fused_stem``) or, for the uint8 chain, as one ``hawq_incep_stem_u8`` in front of the fp32
+        chain's own callables.  The records' order, or with groups ``grouped_order``.  The fp32 chain leaves ``_at`` (record -> index
+        of the launch that covers it) and ``group_launches``."""
+        tiles, groups = self._choice
+        lib, sp, launches = _lib.load(), self.stream.cuda_stream, self._launches
+
+        def op(name, *args):
+            return partial(_lib.call, name, *args, sp)
+
+        def single(r):
+            if r.kind == "other":
+                return op(r.name, *r.args)
+            a = C.byref(r.args[0])
+            if r.kind == "conv":
+                return op(r.name, a) if tiles is None else op("hawq_incep_conv_tiled", a, int(tiles[r.ref]))
+            fast = self.fast_pools and lib.hawq_incep_pool_v_ok(a, r.ref)
+            return op("hawq_incep_pool_v", a, r.ref) if fast else op(r.name, a)
+
+        if u8:
+            return [op("hawq_incep_stem_u8", self.x_u8.data_ptr(), self.lut_dev.data_ptr(), C.byref(self._stem_a))] + self._tail
+        head = launches.index(self._convs[0]) + 1
+        if self.fused_stem:
+            ops = [op("hawq_incep_stem_f32", self.x_in.data_ptr(), *self._input_quant(), C.byref(self._stem_a))]
+        else:
+            ops = [single(r) for r in launches[:head]]
+        n_stem, issued = len(ops), []
+        at = {r: min(i, n_stem - 1) for i, r in enumerate(launches[:head])}
+        order = [(False, i) for i in range(len(launches))] if groups is None else grouped_order(launches, groups)
+        for is_group, i in order[head:]:   # the stem stays in place in either order
+            if is_group:
+                convs, tile = groups[i]
+                g = self._group_args(convs)
+                self._keep.append(g)
+                at.update((self._convs[c], len(ops)) for c in convs)
+                ops.append(op("hawq_incep_conv_group", C.byref(g), int(tile)))
+                issued.append((list(convs), int(tile)))
+            else:
+                at[launches[i]] = len(ops)
+                ops.append(single(launches[i]))
+        self._at, self._tail, self.group_launches = at, ops[n_stem:], issued
+        return ops
+
     def _launch_chain(self, u8):
         for op in (self._ops_u8 if u8 else self._ops):
             op()
-
-    @property
-    def n_launches(self):
-        return len(self._ops)
-
-    @property
-    def n_launches_u8(self):
-        """launches of the uint8 plan (built by the first ``forward_uint8`` of a batch shape)"""
-        return len(self._ops_u8)
 
     # ------------------------------------------------------------------ uint8 image input (quant_train.py:427-440)
     def _input_quant(self):
@@ -700,20 +688,18 @@ class InceptionEngine(GraphRunner):
             return "conv1's output is wider than 8 bits"
         return None
 
-    def _stem_args(self):
-        """conv1 as the one-launch stem kernels take it (one block per plan): `in` NULL, 3 input channels, [Cout][32] weights"""
-        if self._stem_a is None:
-            a1, w_int = self._conv1
-            wt = self._zeros(a1.Cout, 32, dtype=torch.int8, device=self.dev)
-            wt.copy_(torch.from_numpy(pack_stem_u8_weights(w_int, a1.Cout)))
-            a = _lib.IncepConvArgs.from_buffer_copy(a1)   # conv1's bias, tables, clamp, output buffer and pitch
-            a.in_, a.wgt, a.Cin = None, wt.data_ptr(), 3
-            self._keep.append(a)
-            self._stem_a = a
-        return self._stem_a
+    def _stem_args(self, a1, w_int):
+        """conv1 (block `a1`, int8 weights `w_int`) as the one-launch stem kernels take it, one block per plan: `in` NULL, 3 input
+        channels, [Cout][32] weights"""
+        wt = self._zeros(a1.Cout, 32, dtype=torch.int8, device=self.dev)
+        wt.copy_(torch.from_numpy(pack_stem_u8_weights(w_int.detach().cpu().numpy().astype(np.int8), a1.Cout)))
+        a = _lib.IncepConvArgs.from_buffer_copy(a1)   # conv1's bias, tables, clamp, output buffer and pitch
+        a.in_, a.wgt, a.Cin = None, wt.data_ptr(), 3
+        self._keep.append(a)
+        return a
 
     def _ensure_u8(self, N, H, W):
-        """the uint8 plan of the current batch shape: image buffer, table, packed conv1 weights and the launch list"""
+        """the uint8 plan of the current batch shape: image buffer, table and the launch list"""
         if self._ops_u8 is not None:
             return
         if self._u8_why is not None:
@@ -721,12 +707,9 @@ class InceptionEngine(GraphRunner):
         self.x_u8 = self._zeros(N, H, W, 3, dtype=torch.uint8, device=self.dev)
         self.lut_dev = self._zeros(3, 256, dtype=torch.int8, device=self.dev)
         self._lut_key = None
-        a = self._stem_args()
-        if not _lib.load().hawq_incep_stem_u8_ok(self.x_u8.data_ptr(), self.lut_dev.data_ptr(), C.byref(a)):
+        if not _lib.load().hawq_incep_stem_u8_ok(self.x_u8.data_ptr(), self.lut_dev.data_ptr(), C.byref(self._stem_a)):
             raise PlanNotApplicable("uint8 input: hawq_incep_stem_u8 refuses conv1")
-        stem = partial(_lib.call, "hawq_incep_stem_u8", self.x_u8.data_ptr(), self.lut_dev.data_ptr(), C.byref(a),
-                       self.stream.cuda_stream)
-        self._ops_u8 = [stem] + self._ops[self._n_stem_ops:]
+        self._ops_u8 = self._write(u8=True)
 
     def forward_uint8(self, x_u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
         """uint8 NHWC images [N,H,W,3] (decoder output, after resize / crop) -> fp32 logits, equal bit for bit to ``self(x)`` with

@@ -77,6 +77,17 @@ class EventTimer:
         self.record(1)
         return self.ms(0, 1)
 
+    def median_us(self, launch, reps, warm) -> float:
+        """``warm`` untimed calls of ``launch``, then ``reps`` calls timed one by one (``n`` > ``reps`` events): their median, in
+        microseconds"""
+        for _ in range(warm):
+            launch()
+        self.record(0)
+        for r in range(reps):
+            launch()
+            self.record(r + 1)
+        return sorted(self.ms(r, r + 1) * 1000.0 for r in range(reps))[reps // 2]
+
 
 def two_round_min(timer, candidates, prepare, reps, times=None):
     """Time every candidate in two rounds and keep each one's minimum (one hiccup must not decide a launch): ``times[c]`` = ms per

@@ -195,6 +195,11 @@ def test_edges(case):
         assert want.shape[1:3] == (1, 1)
 
 
+def _pools(eng):
+    """(op index, argument block, op id) of every pool / requant launch, read from the engine's launch records"""
+    return [(eng._at[r], r.args[0], r.ref) for r in eng._launches if r.kind == "pool"]
+
+
 def test_every_pool_launch_of_the_shipped_networks_is_taken_and_equal():
     """An engine with fast_pools=True for both schedules: every one of its pool / requant launches goes to hawq_incep_pool_v (none
     stays silently on the old kernel), and every distinct description among them, at a small H != W map, equals brute force."""
@@ -214,7 +219,7 @@ def test_every_pool_launch_of_the_shipped_networks_is_taken_and_equal():
         eng._build(1, 299, 299)   # the plan only: nothing is launched
         assert len(eng.pool_launches) == 49 == eng.n_launches - 95 - 3
         assert all(n == "hawq_incep_pool_v" for n, _ in eng.pool_launches), eng.pool_launches
-        for (idx, a, op), (_, op2) in zip(eng._pools, eng.pool_launches):
+        for (idx, a, op), (_, op2) in zip(_pools(eng), eng.pool_launches):
             assert op == op2 and eng._ops[idx].args[2] == op
             assert a.in_pitch == a.C and a.in_off == 0
             descs.add((names[op], a.in_bits, a.out_bits, bool(a.pre), bool(a.post), a.C, a.ldo, a.c_off))

@@ -23,6 +23,11 @@ def calibrated():
     return model
 
 
+def _pools(eng):
+    """(op index, argument block, op id) of every pool / requant launch, read from the engine's launch records"""
+    return [(eng._at[r], r.args[0], r.ref) for r in eng._launches if r.kind == "pool"]
+
+
 @pytest.mark.parametrize("use_graph", [True, False], ids=["graph", "eager"])
 @pytest.mark.parametrize("batch", [2, 3])
 def test_fast_pools_equal_the_default_engine(calibrated, batch, use_graph):
@@ -115,14 +120,14 @@ def test_launch_list_and_plan_format(calibrated):
     assert names.count("hawq_incep_conv") == 95
     assert "hawq_incep_pool_v" not in base.op_names and sum(base.op_names.count(n) for n in OLD_POOLS) == 49
     # launch for launch the same list: only the pool entry points differ, and each keeps its argument block
-    assert [i for i, (a, b) in enumerate(zip(base.op_names, names)) if a != b] == [idx for idx, _, _ in fast._pools]
-    assert [idx for idx, _, _ in base._pools] == [idx for idx, _, _ in fast._pools]
+    assert [i for i, (a, b) in enumerate(zip(base.op_names, names)) if a != b] == [idx for idx, _, _ in _pools(fast)]
+    assert [idx for idx, _, _ in _pools(base)] == [idx for idx, _, _ in _pools(fast)]
     assert len(fast.pool_launches) == 49 and all(n == "hawq_incep_pool_v" for n, _ in fast.pool_launches)
     ops = {"hawq_incep_requant": 0, "hawq_incep_maxpool3s2": 1, "hawq_incep_avgpool_branch": 2, "hawq_incep_global_avgpool": 3}
     assert base.pool_launches == [(n, ops[n]) for n in base.op_names if n in ops]
     assert [op for _, op in fast.pool_launches] == [op for _, op in base.pool_launches]
     assert sorted({op for _, op in fast.pool_launches}) == [0, 1, 2, 3]
-    for (_, a, _), (_, b, _) in zip(base._pools, fast._pools):
+    for (_, a, _), (_, b, _) in zip(_pools(base), _pools(fast)):
         fa, fb = ({f: getattr(s, f) for f, _ in s._fields_ if f not in ("in_", "out")} for s in (a, b))
         assert fa == fb
     # the plan format does not know about the pools

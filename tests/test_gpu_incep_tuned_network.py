@@ -136,7 +136,7 @@ def test_forward_uint8_of_a_tuned_engine_equals_the_default_engine(calibrated):
     assert torch.equal(y0, y1) and y0.abs().max() > 0
     assert tuned.n_launches_u8 == 145 and base.n_launches_u8 == 145
     # the uint8 plan shares the choice: all its conv launches but conv1 (the stem kernel) are the tuned ones
-    assert tuned._ops_u8[1:] == tuned._ops[tuned._n_stem_ops:]
+    assert tuned._ops_u8[1:] == tuned._ops[tuned._at[tuned._convs[0]] + 1:]   # after conv1's launch
     for t in range(1, _num_tiles() + 1):
         forced = InceptionEngine(model, plan=_forced_plan(tuned, t))
         with torch.no_grad():

@@ -94,7 +94,7 @@ def compare_inputs(model, args, b, kinds):
                   flush=True)
         if args.stem_launches:
             # the launches hawq_incep_stem_u8 replaces, and it, eagerly on the plan stream (HIP events around each group of K)
-            stem32, stem8 = eng._ops[:eng._n_stem_ops], eng._ops_u8[:1]
+            stem32, stem8 = eng._ops[:eng._at[eng._convs[0]] + 1], eng._ops_u8[:1]   # up to conv1
             with torch.cuda.stream(eng.stream):
                 for name, ops in (("f32_stem_launches", stem32), ("hawq_incep_stem_u8", stem8)):
                     def run(ops=ops):
@@ -160,6 +160,11 @@ def pool_bytes(a, op):
     return a.N * a.C * (a.H * a.W * a.in_bits + ho * wo * a.out_bits) // 8
 
 
+def pool_blocks(eng):
+    """(argument block, op id of hawq_incep_pool_v) of every pool / requant launch of `eng`, in the default plan's order"""
+    return [(r.args[0], r.ref) for r in eng._launches if r.kind == "pool"]
+
+
 def time_pools(eng, reps=5, warmup=2):
     """[(old us, new us or None)] per pool launch of `eng`, each launch alone on the plan's buffers, which hold a forward (every
     pool launch is a pure function of its input buffer, so repeating it changes nothing)"""
@@ -171,7 +176,7 @@ def time_pools(eng, reps=5, warmup=2):
     with EventTimer(sp, reps + 1) as ev:
         torch.cuda.synchronize()
         with torch.cuda.stream(eng.stream):
-            for _, a, op in eng._pools:
+            for a, op in pool_blocks(eng):
                 row = []
                 for new in (False, True):
                     if new and not _lib.load().hawq_incep_pool_v_ok(C.byref(a), op):
@@ -179,13 +184,7 @@ def time_pools(eng, reps=5, warmup=2):
                         continue
                     launch = (lambda: _lib.call("hawq_incep_pool_v", C.byref(a), op, sp)) if new else \
                         (lambda: _lib.call(old_of[op], C.byref(a), sp))
-                    for _ in range(warmup):
-                        launch()
-                    ev.record(0)
-                    for r in range(reps):
-                        launch()
-                        ev.record(r + 1)
-                    row.append(sorted(ev.ms(r, r + 1) * 1000.0 for r in range(reps))[reps // 2])
+                    row.append(ev.median_us(launch, reps, warmup))
                 out.append(tuple(row))
     torch.cuda.synchronize()
     return out
@@ -211,14 +210,14 @@ def compare_pools(model, args, b):
             us = time_pools(fast)
             print(f"# {wl}: pool launch | entry point | H W C in_bits out_bits ldo c_off | old us | new us | bytes | floor us (bytes / "
                   f"{STREAM_TBS} TB/s) | issued as")
-            for i, ((_, a, op), (name, _), (t0, t1)) in enumerate(zip(fast._pools, fast.pool_launches, us)):
+            for i, ((a, op), (name, _), (t0, t1)) in enumerate(zip(pool_blocks(fast), fast.pool_launches, us)):
                 nb = pool_bytes(a, op)
                 print(f"# {i:2d} | {POOL_NAMES[op]} | {a.H} {a.W} {a.C} {a.in_bits} {a.out_bits} {a.ldo} {a.c_off} | {t0:.1f} | " +
                       ("refused" if t1 is None else f"{t1:.1f}") + f" | {nb} | {nb / (STREAM_TBS * 1e6):.1f} | {name}")
             s0 = sum(t0 for t0, _ in us)
             s1 = sum(t0 if t1 is None else t1 for t0, t1 in us)
             print(json.dumps({"workload": wl, "pool_launches": len(us), "pool_us_old_sum": round(s0, 1), "pool_us_new_sum": round(s1, 1),
-                              "pool_floor_us_sum": round(sum(pool_bytes(a, op) for _, a, op in fast._pools) / (STREAM_TBS * 1e6), 1),
+                              "pool_floor_us_sum": round(sum(pool_bytes(a, op) for a, op in pool_blocks(fast)) / (STREAM_TBS * 1e6), 1),
                               "taken_by_pool_v": sum(n == "hawq_incep_pool_v" for n, _ in fast.pool_launches),
                               "slower_launches": [i for i, (t0, t1) in enumerate(us) if t1 is not None and t1 > t0]}), flush=True)
         for e in engines.values():
@@ -279,10 +278,10 @@ def compare_stems(model, args, b):
                           "default_block_spread_ms": round(max(ms["three_launch_stem"]) - min(ms["three_launch_stem"]), 4),
                           "fused_block_spread_ms": round(max(ms["fused_stem"]) - min(ms["fused_stem"]), 4)}), flush=True)
         if args.stem_launches:
-            a1 = base._conv1[0]
+            a1 = base._convs[0].args[0]
             ho, wo = (a1.H - 3) // 2 + 1, (a1.W - 3) // 2 + 1
             floor_us = (b * 3 * a1.H * a1.W * 4 + b * ho * wo * a1.Cout) / (STREAM_TBS * 1e6)
-            three = base._ops[:base._n_stem_ops]
+            three = base._ops[:base._at[base._convs[0]] + 1]   # up to conv1
             # (name, launches, the engine on whose stream they are issued)
             groups = [(op.args[0], [op], base) for op in three] + [("three_launches", three, base),
                                                                    ("hawq_incep_stem_f32", fused._ops[:1], fused)]
