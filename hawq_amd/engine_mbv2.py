@@ -388,7 +388,7 @@ class MobileNetV2Engine(GraphRunner):
 
     def _tap(self, ops, keep, name, a, N, ho, wo, cout, cout_p):
         """extra RAW launch exposing the conv's int32 accumulators (tests only)"""
-        acc = torch.empty(N * ho * wo * cout_p, dtype=torch.int32, device=self.dev)
+        acc = self._alloc(N * ho * wo * cout_p, torch.int32)
         r = _lib.ConvArgs()
         C.memmove(C.byref(r), C.byref(a), C.sizeof(r))
         r.epilogue, r.out_acc, r.res_in, r.res_out, r.out_q = _lib.EPI_RAW, acc.data_ptr(), None, None, None
@@ -432,6 +432,10 @@ class MobileNetV2Engine(GraphRunner):
         self.subs = []
         self._build_one(N, H, W, x_view, logits_view)
 
+    def _alloc(self, n, dtype):
+        # 64 elements of slack: a conv that reads a narrow tensor through in_pitch fetches up to 48 bytes past the last pixel row
+        return torch.empty(n + 64, dtype=dtype, device=self.dev)[:n]
+
     def _build_one(self, N, H, W, x_view=None, logits_view=None):
         P, dev, sp = self.P, self.dev, self.stream.cuda_stream
         ops, keep, self.taps, self._graph = [], [], {}, None
@@ -440,8 +444,7 @@ class MobileNetV2Engine(GraphRunner):
         self.n_fused_units = 0    # units that run as ONE launch (hawq_linear_bottleneck)
         self.n_fast_closing = 0   # unit-closing launches whose tables are all proved: the direct epilogue with 3-instruction requants
         self.plan_bytes = N * 3 * H * W * 4   # bytes the plan has to move at the networks' true widths (no padding channels)
-        # 64 elements of slack: a conv that reads a narrow tensor through in_pitch fetches up to 48 bytes past the last pixel row
-        alloc = lambda n, dt: torch.empty(n + 64, dtype=dt, device=dev)[:n]
+        alloc = self._alloc
         self.x_in = x_view if x_view is not None else alloc(N * 3 * H * W, torch.float32).view(N, 3, H, W)
         init = P['init']['layer']
         # the init block as ONE launch (hawq_stem3x3s2): input QuantAct + 3x3 / stride 2 conv + closing QuantActs, no patch rows in memory
@@ -464,7 +467,7 @@ class MobileNetV2Engine(GraphRunner):
             self._u8_index = None
             H0, W0 = H, W
             xq_f = alloc(N * 3 * H * W, torch.float32)
-            xq = torch.zeros(N * H * W * init.cin_p, dtype=torch.int8, device=dev)
+            xq = alloc(N * H * W * init.cin_p, torch.int8).zero_()
             ops.append(partial(_lib.call, "hawq_fakequant_f32", self.x_in.data_ptr(), xq_f.data_ptr(), N * 3 * H * W, P['inv_s_in'], P['s_in'], -128, 127, sp))
             ops.append(partial(_lib.call, "hawq_f32_nchw_to_q_nhwc", xq_f.data_ptr(), xq.data_ptr(), N, 3, H, W, init.cin_p, 8, P['s_in'], sp))
             keep += [xq_f, xq]

@@ -8,10 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard import guard_arena, out_buf  # noqa: F401  (guard_arena: fixture)
 from tests.test_gpu_kernels import (conv_args, dev, from_planar, lib, make_conv, nhwc, odyadic, orc, pack_act,  # noqa: F401
                                     rand_tables, stream, to_planar, unpack_q)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_arena")]
 
 # (pixels per workgroup, band pixels per LDS stage) of the kernels, in tile-id order
 GEOM2 = [(128, 256), (256, 384)]
@@ -59,7 +60,7 @@ def test_band2_requant(lib, orc, shape, mode):
     for tile, (bm, band_px) in zip(_ids(lib), GEOM2):
         a, keep = _args(lib, x, wt, b, tile)
         keep.update(ctab=dev(pack_ctab(b, m, e)), m=dev(m), e=dev(e))
-        out = torch.zeros(acc.size, dtype=torch.uint8, device='cuda')
+        out = out_buf(acc.size, torch.uint8, 0)
         a.epilogue, a.relu, a.m, a.e, a.ctab, a.fast_tables = lib.EPI_REQUANT, 1, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), mode
         a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), 8, -128, 127
         if not _applies(bm, band_px, w, cin):
@@ -109,9 +110,9 @@ def test_band2_residual(lib, orc, shape, mode):
             continue
         a, keep = _args(lib, x, wt, b, tile)
         keep.update(ctab=dev(pack_ctab(b, m2, e2)), m=dev(m2), e=dev(e2), res=dev(nhwc(res).astype(np.uint16)))
-        flags = torch.zeros(1, dtype=torch.int32, device='cuda')
-        out_res = torch.zeros(ref_res.size, dtype=torch.uint16, device='cuda')
-        out_q = torch.zeros(ref_res.size, dtype=torch.uint8, device='cuda')
+        flags = out_buf(1, torch.int32, 0)
+        out_res = out_buf(ref_res.size, torch.uint16, 0)
+        out_q = out_buf(ref_res.size, torch.uint8, 0)
         a.epilogue, a.m, a.e, a.ctab, a.flags = lib.EPI_RESIDUAL, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), flags.data_ptr()
         a.res_in, a.res_in_bits, a.m_id_scalar, a.e_id_scalar = keep['res'].data_ptr(), 16, int(m1[0]), int(e1[0])
         a.res_out, a.res_out_bits = out_res.data_ptr(), 16
@@ -160,7 +161,7 @@ def test_band2_full_size_equals_the_band_kernels(lib, name, shape):
     nt, nb, nb2 = lib.load().hawq_conv2d_num_tiles(), lib.load().hawq_conv2d_num_band_tiles(), lib.load().hawq_conv2d_num_band2_tiles()
     a, keep = _args(lib, x, wt, b, 0)
     keep.update(ctab=dev(pack_ctab(b, m, e)), m=dev(m), e=dev(e))
-    out = torch.zeros(n * h * w * cout, dtype=torch.uint8, device='cuda')
+    out = out_buf(n * h * w * cout, torch.uint8, 0)
     a.epilogue, a.relu, a.m, a.e, a.ctab, a.fast_tables = lib.EPI_REQUANT, 1, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), 1
     a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), 8, -128, 127
     ref = None
@@ -204,7 +205,7 @@ def test_band2_hawq4_operands_and_outputs(lib, orc, shape, mode):
             for out_bits, (lo, hi) in ((8, (-128, 127)), (4, (0, 15))):
                 if bits == 8 and out_bits == 8:
                     continue   # test_band2_requant
-                out = torch.zeros(acc.size * out_bits // 8, dtype=torch.uint8, device='cuda')
+                out = out_buf(acc.size * out_bits // 8, torch.uint8, 0)
                 a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), out_bits, lo, hi
                 if not _applies(bm, band_px, w, cin, bits):
                     a.out_planar = 0
@@ -234,7 +235,7 @@ def test_band2_raw_accumulators(lib, orc, shape, bits):
     ran = 0
     for tile, (bm, band_px) in zip(_ids(lib), GEOM2):
         a, keep = _args(lib, x, wt, b, tile, bits)
-        out = torch.full((ref.size,), -7, dtype=torch.int32, device='cuda')
+        out = out_buf(ref.size, torch.int32, -7)
         a.epilogue, a.out_acc = lib.EPI_RAW, out.data_ptr()
         if not _applies(bm, band_px, w, cin, bits):
             assert lib.load().hawq_conv2d(C.byref(a), None) != 0   # refused, not mis-computed

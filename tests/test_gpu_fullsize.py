@@ -10,10 +10,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard import guard_arena, out_buf, release  # noqa: F401  (guard_arena: fixture)
 from tests.test_gpu_kernels import (conv_args, dev, from_planar, lib, make_conv, nhwc, odyadic, orc, pack_act,  # noqa: F401
                                     rand_tables, stream, to_planar, unpack_q)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_arena")]
 
 
 def _tiles(lib):
@@ -53,23 +54,25 @@ def test_full_size_requant_layers(lib, orc, name, shape, bits):
     # 1. raw accumulators (heuristic tile + two autotuner favourites)
     for tile in (0, 11, 14):
         a, keep = conv_args(lib, x, wt, b, stride, pad, bits, bits, tile=tile)
-        out = torch.full((acc.size,), -7, dtype=torch.int32, device='cuda')
+        out = out_buf(acc.size, torch.int32, -7)
         a.epilogue, a.out_acc = lib.EPI_RAW, out.data_ptr()
         lib.call("hawq_conv2d", C.byref(a), stream())
         got = out.cpu().numpy().reshape(n, ho, wo, cout).transpose(0, 3, 1, 2)
         assert np.array_equal(got, acc), f"{name}: raw accumulators, tile {tile}"
+        release(out, *keep.values())
         del out, keep
     # 2. fused requant epilogue, every tile id that takes the layer
     ran = 0
     for tile in [0] + generic + band:
         a, keep = conv_args(lib, x, wt, b, stride, pad, bits, bits, tile=tile)
         keep.update(ctab=dev(pack_ctab(b, m, e)), m=dev(m), e=dev(e))
-        out = torch.zeros(acc.size * bits // 8, dtype=torch.uint8, device='cuda')
+        out = out_buf(acc.size * bits // 8, torch.uint8, 0)
         a.epilogue, a.relu, a.m, a.e, a.ctab, a.fast_tables = (lib.EPI_REQUANT, 1, keep['m'].data_ptr(), keep['e'].data_ptr(),
                                                                 keep['ctab'].data_ptr(), mode)
         a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), bits, lo, hi
         if not _try(lib, a):
             assert tile in band, f"{name}: generic tile {tile} refused"
+            release(out, *keep.values())
             continue
         assert np.array_equal(unpack_q(out, (n, ho, wo, cout), bits), ref_q), f"{name}: requant, tile {tile}"
         if tile in band:  # as the engine launches it: activations in channel-group planes
@@ -84,6 +87,7 @@ def test_full_size_requant_layers(lib, orc, name, shape, bits):
             lib.call("hawq_conv2d", C.byref(a), stream())
             assert np.array_equal(from_planar(out, (n, ho, wo, cout), bits), ref_q), f"{name}: planar output, tile {tile}"
         ran += 1
+        release(out, *keep.values())
         del out, keep
     assert ran >= len(generic) + 1 + (1 if k == 3 and (bits == 8 or cin % 128 == 0) else 0)
     frac_sat = float((ref_q == hi).mean())
@@ -134,9 +138,9 @@ def test_full_size_residual_layers(lib, orc, name, shape, dual):
         else:
             keep['res'] = dev(nhwc(res).astype(np.uint16))
             a.res_in, a.res_in_bits, a.m_id_scalar, a.e_id_scalar = keep['res'].data_ptr(), 16, int(m1[0]), int(e1[0])
-        flags = torch.zeros(1, dtype=torch.int32, device='cuda')
-        out_res = torch.zeros(ref_res.size, dtype=torch.uint16, device='cuda')
-        out_q = torch.zeros(ref_res.size, dtype=torch.uint8, device='cuda')
+        flags = out_buf(1, torch.int32, 0)
+        out_res = out_buf(ref_res.size, torch.uint16, 0)
+        out_q = out_buf(ref_res.size, torch.uint8, 0)
         a.epilogue, a.m, a.e, a.ctab, a.flags = lib.EPI_RESIDUAL, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), flags.data_ptr()
         a.res_out, a.res_out_bits = out_res.data_ptr(), 16
         a.out_q, a.out_bits, a.q_lo, a.q_hi, a.mq, a.eq = out_q.data_ptr(), 8, 0, 127, int(mq[0]), int(eq[0])
@@ -146,4 +150,5 @@ def test_full_size_residual_layers(lib, orc, name, shape, dual):
         assert np.array_equal(got, ref_res), f"{name}: residual, tile {tile}"
         assert np.array_equal(unpack_q(out_q, (n, h, w, cout), 8), ref_q), f"{name}: next QuantAct, tile {tile}"
         assert flags.item() == 0
+        release(out_res, out_q, flags, *keep.values())
         del out_res, out_q, keep

@@ -10,9 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard import guard_arena, out_buf  # noqa: F401  (guard_arena: fixture)
 from tests.test_gpu_kernels import dev, from_planar, lib, make_conv, nhwc, odyadic, orc, rand_tables, stream, unpack_q  # noqa: F401
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_arena")]
 
 
 def _case(lib, orc, n, h, w, c, c3, seed, force_tie=False, dual=False):
@@ -61,8 +62,8 @@ def _case(lib, orc, n, h, w, c, c3, seed, force_tie=False, dual=False):
     keep = dict(x2=dev(nhwc(x2).astype(np.int8).view(np.uint8)), w3=dev(pack_conv_weight(w3, 8)), w1=dev(pack_conv_weight(w1, 8)),
                 b3=dev(b3.astype(np.int32)), b1=dev(b1.astype(np.int32)), m3=dev(m3), e3=dev(e3), m1=dev(m1), e1=dev(e1),
                 ctab3=dev(pack_ctab(b3, m3, e3)), ctab1=dev(pack_ctab(b1, m1, e1)), res=dev(nhwc(res).astype(np.uint16)),
-                flags=torch.zeros(1, dtype=torch.int32, device='cuda'),
-                res_out=torch.zeros(o.size, dtype=torch.uint16, device='cuda'), y=torch.zeros(y.size, dtype=torch.uint8, device='cuda'))
+                flags=out_buf(1, torch.int32, 0),
+                res_out=out_buf(o.size, torch.uint16, 0), y=out_buf(y.size, torch.uint8, 0))
     ex, rd = a.expand, a.reduce
     ex.in_, ex.wgt, ex.bias = keep['x2'].data_ptr(), keep['w3'].data_ptr(), keep['b3'].data_ptr()
     ex.N, ex.H, ex.W, ex.Cin, ex.Cout, ex.KH, ex.KW, ex.stride, ex.pad = n, h, w, c, c3, 1, 1, 1, 0
@@ -153,7 +154,7 @@ def test_expand_alone_wave_private(lib, orc, shape, tie):
         pytest.skip("full-size case once")
     a, keep, o, y = _case(lib, orc, n, h, w, c, c3, zlib.crc32(repr(shape).encode()) + 7, force_tie=tie)
     a.reduce = lib.ExpandReduceArgs().reduce   # zeroed: no reduce conv
-    qbuf = torch.zeros(o.size, dtype=torch.uint8, device='cuda')
+    qbuf = out_buf(o.size, torch.uint8, 0)
     a.expand.out_q = qbuf.data_ptr()
     nvar = lib.load().hawq_conv_expand_reduce_variants(C.byref(a))
     assert nvar >= 1
@@ -176,7 +177,7 @@ def test_expand_alone_wave_private(lib, orc, shape, tie):
         mq4, eq4 = requant_table(torch.tensor([r4 * 0.7], dtype=torch.float32), torch.ones(1), torch.tensor([0.7]))
         q4_ref = odyadic(orc, o, mq4, eq4, (0, 15))
         assert 0.05 < float((q4_ref == 15).mean()) < 0.9
-        q4buf = torch.zeros(o.size // 2, dtype=torch.uint8, device='cuda')
+        q4buf = out_buf(o.size // 2, torch.uint8, 0)
         mq0, eq0 = a.expand.mq, a.expand.eq
         a.expand.out_q, a.expand.out_bits, a.expand.q_lo, a.expand.q_hi, a.expand.mq, a.expand.eq = q4buf.data_ptr(), 4, 0, 15, int(mq4[0]), int(eq4[0])
         a.expand.fast_tables, a.expand.res_out = ft, keep['res_out'].data_ptr()

@@ -7,10 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard import guard_arena, out_buf  # noqa: F401  (guard_arena: fixture)
 from tests.test_gpu_kernels import (conv_args, dev, from_planar, lib, make_conv, nhwc, odyadic, orc, pack_act,  # noqa: F401
                                     rand_tables, stream, unpack_q)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_arena")]
 
 BN2 = [64, 64, 128]   # channel tile of the kernels, in tile-id order
 
@@ -52,7 +53,7 @@ def test_gemm2_requant(lib, orc, shape, mode):
     for tile, bn in zip(_ids(lib), BN2):
         a, keep = _args(lib, x, wt, b, stride, tile)
         keep.update(ctab=dev(pack_ctab(b, m, e)), m=dev(m), e=dev(e))
-        out = torch.zeros(acc.size, dtype=torch.uint8, device='cuda')
+        out = out_buf(acc.size, torch.uint8, 0)
         a.epilogue, a.relu, a.m, a.e, a.ctab, a.fast_tables = lib.EPI_REQUANT, 1, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), mode
         a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), 8, -128, 127
         if cout % bn:
@@ -97,9 +98,9 @@ def test_gemm2_residual(lib, orc, shape, mode):
             continue
         a, keep = _args(lib, x, wt, b, 1, tile)
         keep.update(ctab=dev(pack_ctab(b, m2, e2)), m=dev(m2), e=dev(e2), res=dev(nhwc(res).astype(np.uint16)))
-        flags = torch.zeros(1, dtype=torch.int32, device='cuda')
-        out_res = torch.zeros(ref_res.size, dtype=torch.uint16, device='cuda')
-        out_q = torch.zeros(ref_res.size, dtype=torch.uint8, device='cuda')
+        flags = out_buf(1, torch.int32, 0)
+        out_res = out_buf(ref_res.size, torch.uint16, 0)
+        out_q = out_buf(ref_res.size, torch.uint8, 0)
         a.epilogue, a.m, a.e, a.ctab, a.flags = lib.EPI_RESIDUAL, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), flags.data_ptr()
         a.res_in, a.res_in_bits, a.m_id_scalar, a.e_id_scalar = keep['res'].data_ptr(), 16, int(m1[0]), int(e1[0])
         a.res_out, a.res_out_bits = out_res.data_ptr(), 16
@@ -166,9 +167,9 @@ def test_gemm2_residual_with_identity_conv(lib, orc, shape, mode):
         keep.update(ctab=dev(pack_ctab(b, m2, e2)), ctab_id=dev(pack_ctab(bi, mi, ei)), m=dev(m2), e=dev(e2), mi=dev(mi), ei=dev(ei),
                     x2=dev(pack_act(xi, 8)), w2=dev(pack_conv_weight(wti, 8)), w2k=dev(pack_w1x1_k128(pack_conv_weight(wti, 8), cout, cin2)),
                     b2=dev(bi.astype(np.int32)))
-        flags = torch.zeros(1, dtype=torch.int32, device='cuda')
-        out_res = torch.zeros(ref_res.size, dtype=torch.uint16, device='cuda')
-        out_q = torch.zeros(ref_res.size, dtype=torch.uint8, device='cuda')
+        flags = out_buf(1, torch.int32, 0)
+        out_res = out_buf(ref_res.size, torch.uint16, 0)
+        out_q = out_buf(ref_res.size, torch.uint8, 0)
         a.epilogue, a.m, a.e, a.ctab, a.flags = lib.EPI_RESIDUAL, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), flags.data_ptr()
         a.in2, a.wgt2, a.bias2, a.wgt2_k128 = keep['x2'].data_ptr(), keep['w2'].data_ptr(), keep['b2'].data_ptr(), keep['w2k'].data_ptr()
         a.H2, a.W2, a.Cin2, a.stride2, a.in2_bits, a.w2_bits = h2, w2, cin2, s2, 8, 8
@@ -217,7 +218,7 @@ def test_gemm2_raw_accumulators(lib, orc, shape, bits):
     ran = 0
     for tile, bn in zip(_ids(lib), BN2):
         a, keep = _args_bits(lib, x, wt, b, stride, tile, bits)
-        out = torch.full((ref.size,), -7, dtype=torch.int32, device='cuda')
+        out = out_buf(ref.size, torch.int32, -7)
         a.epilogue, a.out_acc = lib.EPI_RAW, out.data_ptr()
         if cout % bn:
             assert lib.load().hawq_conv2d(C.byref(a), None) != 0
@@ -254,7 +255,7 @@ def test_gemm2_hawq4_operands_and_outputs(lib, orc, shape, mode):
         keep.update(ctab=dev(pack_ctab(b, m, e)), m=dev(m), e=dev(e))
         a.epilogue, a.m, a.e, a.ctab, a.fast_tables = lib.EPI_REQUANT, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), mode
         for ob, (lo, hi) in ((8, (-128, 127)), (4, (0, 15))):
-            out = torch.zeros(acc.size * ob // 8, dtype=torch.uint8, device='cuda')
+            out = out_buf(acc.size * ob // 8, torch.uint8, 0)
             a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), ob, lo, hi
             for relu in ((1, 0) if ob == 8 else (1,)):
                 ref = odyadic(orc, np.maximum(acc, 0) if relu else acc, m, e, (lo, hi))
@@ -292,11 +293,11 @@ def test_gemm2_hawq4_residual_and_identity(lib, orc):
         for dual in (False, True):
             a, keep = _args_bits(lib, x, wt, b, 1, tile, 4)
             keep.update(ctab=dev(pack_ctab(b, m2, e2)), m=dev(m2), e=dev(e2), res=dev(nhwc(res).astype(np.uint16)))
-            flags = torch.zeros(1, dtype=torch.int32, device='cuda')
+            flags = out_buf(1, torch.int32, 0)
             idreq = odyadic(orc, acc_id, mi, ei) if dual else odyadic(orc, res, m1, e1)
             ref_res = np.maximum(odyadic(orc, acc, m2, e2) + idreq, 0)
             assert ref_res.max() < 65536
-            out_res = torch.zeros(ref_res.size, dtype=torch.uint16, device='cuda')
+            out_res = out_buf(ref_res.size, torch.uint16, 0)
             a.epilogue, a.m, a.e, a.ctab, a.flags, a.fast_tables = lib.EPI_RESIDUAL, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), flags.data_ptr(), 1
             a.res_out, a.res_out_bits = out_res.data_ptr(), 16
             if dual:
@@ -309,7 +310,7 @@ def test_gemm2_hawq4_residual_and_identity(lib, orc):
                 a.res_in, a.res_in_bits, a.m_id_scalar, a.e_id_scalar = keep['res'].data_ptr(), 16, int(m1[0]), int(e1[0])
             for ob, hi in ((8, 127), (4, 15)):
                 ref_q = odyadic(orc, ref_res, mq, eq, (0, hi))
-                out_q = torch.zeros(ref_res.size * ob // 8, dtype=torch.uint8, device='cuda')
+                out_q = out_buf(ref_res.size * ob // 8, torch.uint8, 0)
                 a.out_q, a.out_bits, a.q_lo, a.q_hi, a.mq, a.eq = out_q.data_ptr(), ob, 0, hi, int(mq[0]), int(eq[0])
                 out_res.zero_()
                 lib.call("hawq_conv2d", C.byref(a), stream())

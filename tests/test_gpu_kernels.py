@@ -9,8 +9,9 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.guard import dev, guard_arena, out_buf  # noqa: F401  (guard_arena: fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_arena")]
 f32 = np.float32
 
 
@@ -26,10 +27,6 @@ def lib():
 def orc():
     from oracle import oracle
     return oracle
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def stream():
@@ -134,7 +131,7 @@ def test_conv_raw_accumulators(lib, orc, shape, bits):
     ref = orc.conv2d(x, wt, b, stride, pad)
     for tile in range(0, lib.load().hawq_conv2d_num_tiles() + 1 - lib.load().hawq_conv2d_num_band_tiles()):  # the last ids are the 3x3 band kernels
         a, keep = conv_args(lib, x, wt, b, stride, pad, *bits, tile=tile)
-        out = torch.full((ref.size,), -7, dtype=torch.int32, device='cuda')
+        out = out_buf(ref.size, torch.int32, -7)
         a.epilogue, a.out_acc = lib.EPI_RAW, out.data_ptr()
         lib.call("hawq_conv2d", C.byref(a), stream())
         got = out.cpu().numpy().reshape(n, ref.shape[2], ref.shape[3], cout).transpose(0, 3, 1, 2)
@@ -148,7 +145,7 @@ def test_conv_identity_weights_asymmetric(lib):
     wt = np.zeros((c, c, 1, 1), np.int64)
     wt[np.arange(c), np.arange(c), 0, 0] = 1
     a, keep = conv_args(lib, x, wt, np.zeros(c, np.int64), 1, 0, 8, 8)
-    out = torch.empty(n * h * w * c, dtype=torch.int32, device='cuda')
+    out = out_buf(n * h * w * c, torch.int32, None)
     a.epilogue, a.out_acc = lib.EPI_RAW, out.data_ptr()
     lib.call("hawq_conv2d", C.byref(a), stream())
     assert np.array_equal(out.cpu().numpy().reshape(n, h, w, c).transpose(0, 3, 1, 2), x)
@@ -188,7 +185,7 @@ def test_conv_requant_epilogue(lib, orc, bits, out_bits, fast):
         keep['ctab'] = dev(pack_ctab(b, m, e))
         a.ctab = keep['ctab'].data_ptr()
     md, ed = dev(m), dev(e)
-    out = torch.zeros(ref.size * out_bits // 8, dtype=torch.uint8, device='cuda')
+    out = out_buf(ref.size * out_bits // 8, torch.uint8, 0)
     a.epilogue, a.relu, a.m, a.e = lib.EPI_REQUANT, 1, md.data_ptr(), ed.data_ptr()
     a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), out_bits, lo, hi
     lib.call("hawq_conv2d", C.byref(a), stream())
@@ -243,7 +240,7 @@ def test_conv3x3_band_kernels(lib, orc, shape, bits):
         if not applies:
             a, keep = conv_args(lib, x, wt, b, 1, 1, bits, bits, tile=tile)
             keep.update(ctab=dev(pack_ctab(b, m, e)), m=dev(m), e=dev(e))
-            out = torch.zeros(acc.size, dtype=torch.uint8, device='cuda')
+            out = out_buf(acc.size, torch.uint8, 0)
             a.epilogue, a.relu, a.m, a.e, a.ctab, a.fast_tables = lib.EPI_REQUANT, 1, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), 1
             a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), 8, -128, 127
             assert lib.load().hawq_conv2d(C.byref(a), None) != 0   # refused, not mis-computed
@@ -251,7 +248,7 @@ def test_conv3x3_band_kernels(lib, orc, shape, bits):
         for relu, out_bits, (lo, hi) in ((1, 8, (-128, 127)), (0, 8, (-128, 127)), (1, 4, (0, 15))):
             a, keep = conv_args(lib, x, wt, b, 1, 1, bits, bits, tile=tile)
             keep.update(ctab=dev(pack_ctab(b, m, e)), m=dev(m), e=dev(e))
-            out = torch.zeros(acc.size * out_bits // 8, dtype=torch.uint8, device='cuda')
+            out = out_buf(acc.size * out_bits // 8, torch.uint8, 0)
             a.epilogue, a.relu, a.m, a.e, a.ctab, a.fast_tables = lib.EPI_REQUANT, relu, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), 1
             a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), out_bits, lo, hi
             if gi >= PERSIST and out_bits != 8:
@@ -306,9 +303,9 @@ def test_conv3x3_band_residual(lib, orc, shape, bits, mode):
             continue
         a, keep = conv_args(lib, x, wt, b, 1, 1, bits, bits, tile=tile)
         keep.update(ctab=dev(pack_ctab(b, m2, e2)), m=dev(m2), e=dev(e2), res=dev(nhwc(res).astype(np.uint16)))
-        flags = torch.zeros(1, dtype=torch.int32, device='cuda')
-        out_res = torch.zeros(ref_res.size, dtype=torch.uint16, device='cuda')
-        out_q = torch.zeros(ref_res.size, dtype=torch.uint8, device='cuda')
+        flags = out_buf(1, torch.int32, 0)
+        out_res = out_buf(ref_res.size, torch.uint16, 0)
+        out_q = out_buf(ref_res.size, torch.uint8, 0)
         a.epilogue, a.m, a.e, a.ctab, a.flags = lib.EPI_RESIDUAL, keep['m'].data_ptr(), keep['e'].data_ptr(), keep['ctab'].data_ptr(), flags.data_ptr()
         a.res_in, a.res_in_bits, a.m_id_scalar, a.e_id_scalar = keep['res'].data_ptr(), 16, int(m1[0]), int(e1[0])
         a.res_out, a.res_out_bits = out_res.data_ptr(), 16
@@ -365,9 +362,9 @@ def test_conv_residual_epilogue(lib, orc, dual, res_bits, fast):
     mq, eq = requant_table(torch.tensor([0.0039 * 0.7]), torch.ones(1), torch.tensor([0.7]))
     ref_q = odyadic(orc, ref_res, mq, eq, (0, 127))
     md, ed = dev(m2), dev(e2)
-    flags = torch.zeros(1, dtype=torch.int32, device='cuda')
-    out_res = torch.zeros(ref_res.size, dtype=torch.uint16 if res_bits == 16 else torch.int32, device='cuda')
-    out_q = torch.zeros(ref_res.size, dtype=torch.uint8, device='cuda')
+    flags = out_buf(1, torch.int32, 0)
+    out_res = out_buf(ref_res.size, torch.uint16 if res_bits == 16 else torch.int32, 0)
+    out_q = out_buf(ref_res.size, torch.uint8, 0)
     a.epilogue, a.m, a.e, a.flags = lib.EPI_RESIDUAL, md.data_ptr(), ed.data_ptr(), flags.data_ptr()
     a.res_out, a.res_out_bits = out_res.data_ptr(), res_bits
     a.out_q, a.out_bits, a.q_lo, a.q_hi, a.mq, a.eq = out_q.data_ptr(), 8, 0, 127, int(mq[0]), int(eq[0])
@@ -402,8 +399,8 @@ def test_residual_uint16_overflow_sets_flag(lib, orc):
     m2 = np.full(cout, 1 << 30, np.int32)
     e2 = np.full(cout, 33 | (2 << 8), np.int32)  # ratio 1/2 (e=31 lifted by k=2)
     md, ed = dev(m2), dev(e2)
-    flags = torch.zeros(1, dtype=torch.int32, device='cuda')
-    out_res = torch.zeros(n * h * w * cout, dtype=torch.uint16, device='cuda')
+    flags = out_buf(1, torch.int32, 0)
+    out_res = out_buf(n * h * w * cout, torch.uint16, 0)
     a.epilogue, a.m, a.e, a.flags = lib.EPI_RESIDUAL, md.data_ptr(), ed.data_ptr(), flags.data_ptr()
     a.res_in, a.res_in_bits, a.m_id_scalar, a.e_id_scalar = keep['res'].data_ptr(), 16, 1 << 30, 33 | (3 << 8)  # ratio 1
     a.res_out, a.res_out_bits = out_res.data_ptr(), 16
@@ -432,7 +429,7 @@ def test_quantize_input_and_stem(lib, orc):
     ho, wo = (hh + 6 - 7) // 2 + 1, (ww + 6 - 7) // 2 + 1
     hp, wp = max(2 * (ho - 1) + 8, hh + 3), max(2 * (wo - 1) + 8, ww + 4)
     wp += wp & 1
-    xq = torch.zeros(n * hp * wp * 4, dtype=torch.int8, device='cuda')
+    xq = out_buf(n * hp * wp * 4, torch.int8, 0)
     xd = dev(x)
     lib.call("hawq_quantize_input", xd.data_ptr(), xq.data_ptr(), n, 3, hh, ww, hp, wp, 3, 3, float(f32(1) / scale),
              -128, 127, stream())
@@ -444,8 +441,8 @@ def test_quantize_input_and_stem(lib, orc):
     m, e = rand_tables(rng, 64, 2e-3, 4e-2)
     ref16 = np.maximum(odyadic(orc, acc, m, e, (-32768, 32767)), 0)
     wd, bd, md, ed = dev(pack_stem_weight(wt)), dev(b.astype(np.int32)), dev(m), dev(e)
-    out16 = torch.zeros(n * ho * wo * 64, dtype=torch.uint16, device='cuda')
-    out_acc = torch.zeros(n * ho * wo * 64, dtype=torch.int32, device='cuda')
+    out16 = out_buf(n * ho * wo * 64, torch.uint16, 0)
+    out_acc = out_buf(n * ho * wo * 64, torch.int32, 0)
     lib.call("hawq_stem_conv7", xq.data_ptr(), wd.data_ptr(), bd.data_ptr(), md.data_ptr(), ed.data_ptr(), n, hp, wp,
              ho, wo, -32768, 32767, out16.data_ptr(), out_acc.data_ptr(), stream())
     assert np.array_equal(out_acc.cpu().numpy().reshape(n, ho, wo, 64).transpose(0, 3, 1, 2), acc)
@@ -456,13 +453,13 @@ def test_quantize_input_and_stem(lib, orc):
     pooled = orc.maxpool(ref16, 3, 2, 1)
     h1, w1 = pooled.shape[2:]
     for bits, (lo, hi) in ((8, (-128, 127)), (4, (0, 15))):
-        res = torch.zeros(pooled.size, dtype=torch.uint16, device='cuda')
-        qo = torch.zeros(pooled.size * bits // 8, dtype=torch.uint8, device='cuda')
+        res = out_buf(pooled.size, torch.uint16, 0)
+        qo = out_buf(pooled.size * bits // 8, torch.uint8, 0)
         lib.call("hawq_maxpool3s2_requant", out16.data_ptr(), n, ho, wo, 64, res.data_ptr(), qo.data_ptr(), bits,
                  int(mq[0]), int(eq[0]), lo, hi, stream())
         assert np.array_equal(res.cpu().numpy().astype(np.int64).reshape(n, h1, w1, 64).transpose(0, 3, 1, 2), pooled)
         assert np.array_equal(unpack_q(qo, (n, h1, w1, 64), bits), odyadic(orc, pooled, mq, eq, (lo, hi)))
-        q2 = torch.zeros_like(qo)
+        q2 = out_buf(qo.shape, qo.dtype, 0)
         lib.call("hawq_requant_residual", res.data_ptr(), 16, pooled.size, q2.data_ptr(), bits, int(mq[0]), int(eq[0]),
                  lo, hi, stream())
         assert torch.equal(q2, qo)
@@ -490,8 +487,8 @@ def test_fused_stem_matches_unfused_semantics(lib, orc, shape):
     from hawq_amd.quant_utils import tables_are_fast
     can_fast = tables_are_fast(m, e, int(np.abs(acc).max()).bit_length() + 1) and tables_are_fast(mq, eq, 17)
     for bits, (lo, hi), fast in ((8, (-128, 127), 0), (4, (0, 15), 0), (8, (-128, 127), int(can_fast))):
-        res = torch.zeros(acc.size, dtype=torch.uint16, device='cuda')
-        qo = torch.zeros(acc.size * bits // 8, dtype=torch.uint8, device='cuda')
+        res = out_buf(acc.size, torch.uint16, 0)
+        qo = out_buf(acc.size * bits // 8, torch.uint8, 0)
         lib.call("hawq_stem_fused", xd.data_ptr(), n, 3, hh, ww, float(f32(1) / scale), -128, 127, wd.data_ptr(),
                  bd.data_ptr(), md.data_ptr(), ed.data_ptr(), -32768, 32767, res.data_ptr(), qo.data_ptr(), bits,
                  int(mq[0]), int(eq[0]), lo, hi, fast, stream())
@@ -515,8 +512,8 @@ def test_avgpool_requant(lib, orc, res_bits, c):
     mq, eq = requant_table(torch.tensor([0.0038]), torch.ones(1), torch.ones(1))
     ref = odyadic(orc, pooled, mq, eq, (-128, 127))
     xin = dev(nhwc(x).astype(np.uint16 if res_bits == 16 else np.int32))
-    out = torch.zeros(n * c, dtype=torch.int8, device='cuda')
-    pd = torch.zeros(n * c, dtype=torch.int32, device='cuda')
+    out = out_buf(n * c, torch.int8, 0)
+    pd = out_buf(n * c, torch.int32, 0)
     lib.call("hawq_avgpool_requant", xin.data_ptr(), res_bits, n, 49, c, out.data_ptr(), pd.data_ptr(), int(mq[0]),
              int(eq[0]), -128, 127, stream())
     assert np.array_equal(pd.cpu().numpy().reshape(n, c), pooled)
@@ -539,7 +536,7 @@ def test_dequant_epilogue_fc(lib, orc):
     fsp = np.zeros(1024, f32)
     fsp[:nout] = fs
     xd, bd, fd = dev(x.astype(np.int8)), dev(bp), dev(fsp)
-    out = torch.full((bsz, nout), float('nan'), device='cuda')
+    out = out_buf((bsz, nout), torch.float32, float('nan'))
     a = lib.ConvArgs()
     a.in_, a.wgt, a.bias = xd.data_ptr(), wp.data_ptr(), bd.data_ptr()
     a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad = bsz, 1, 1, k, 1024, 1, 1, 1, 0
@@ -567,7 +564,7 @@ def test_fc_dequant_kernel_equals_the_conv_kernels_dequant_epilogue(lib, orc, n,
     wp = dev(pack_conv_weight(wt.reshape(nout, k, 1, 1), 8, k, nout_p))
     xd, bd, fd = dev(x.astype(np.int8)), dev(bp), dev(fsp)
     assert lib.load().hawq_fc_dequant_ok(n, k, nout_p)
-    out = torch.full((n, nout), -7.0, dtype=torch.float32, device="cuda")
+    out = out_buf((n, nout), torch.float32, -7.0)
     lib.call("hawq_fc_dequant", xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), fd.data_ptr(), out.data_ptr(), n, k, nout_p, nout, nout, stream())
     torch.cuda.synchronize()
     ref = (orc.linear(x, wt, b).astype(f32) * fsp[:nout].reshape(1, -1)).astype(f32)
@@ -576,7 +573,7 @@ def test_fc_dequant_kernel_equals_the_conv_kernels_dequant_epilogue(lib, orc, n,
     a.in_, a.wgt, a.bias = xd.data_ptr(), wp.data_ptr(), bd.data_ptr()
     a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad = n, 1, 1, k, nout_p, 1, 1, 1, 0
     a.in_bits, a.w_bits, a.epilogue = 8, 8, lib.EPI_DEQUANT
-    via_conv = torch.full((n, nout), -9.0, dtype=torch.float32, device="cuda")
+    via_conv = out_buf((n, nout), torch.float32, -9.0)
     a.out_f32, a.fscale, a.ldo, a.n_valid = via_conv.data_ptr(), fd.data_ptr(), nout, nout
     lib.call("hawq_conv2d", C.byref(a), stream())
     torch.cuda.synchronize()
@@ -734,8 +731,8 @@ def test_depthwise3x3_matches_the_grouped_kernel_and_numpy(lib, shape):
     ho, wo = (h + 2 - 3) // stride + 1, (w + 2 - 3) // stride + 1
     xd, wg, w9, bd = dev(x), dev(np.ascontiguousarray(wt.reshape(c, 3, 3, 1))), dev(np.ascontiguousarray(wt.reshape(c, 9).T)), dev(b)
     for bias in (bd, None):
-        out_g = torch.zeros(n * ho * wo * c, dtype=torch.int32, device='cuda')
-        out_d = torch.zeros_like(out_g)
+        out_g = out_buf(n * ho * wo * c, torch.int32, 0)
+        out_d = out_buf(out_g.shape, out_g.dtype, 0)
         bp = bias.data_ptr() if bias is not None else None
         lib.call("hawq_conv2d_grouped", xd.data_ptr(), wg.data_ptr(), bp, n, h, w, c, c, 3, 3, stride, 1, c, out_g.data_ptr(), stream())
         lib.call("hawq_depthwise3x3", xd.data_ptr(), w9.data_ptr(), bp, n, h, w, c, stride, out_d.data_ptr(), stream())
@@ -767,14 +764,14 @@ def test_depthwise3x3_requant_matches_accumulators_plus_host_dyadic(lib, orc, sh
     if c >= 8:
         m[-4:] = 0   # a padding channel group (multiplier 0): the kernel skips its loads and MACs, the result is still rne(acc * 0) = 0
     xd, w9, bd, md, ed = dev(x), dev(np.ascontiguousarray(wt.reshape(c, 9).T)), dev(b), dev(m), dev(e)
-    acc = torch.zeros(n * ho * wo * c, dtype=torch.int32, device='cuda')
+    acc = out_buf(n * ho * wo * c, torch.int32, 0)
     lib.call("hawq_depthwise3x3", xd.data_ptr(), w9.data_ptr(), bd.data_ptr(), n, h, w, c, stride, acc.data_ptr(), stream())
     lo, hi = (0, 127) if relu else (-128, 127)
     a = acc.cpu().numpy().astype(np.int64).reshape(n, ho, wo, c)
     ref = odyadic(orc, (np.maximum(a, 0) if relu else a).transpose(0, 3, 1, 2), m, e, (lo, hi)).transpose(0, 2, 3, 1)
     for keep_acc in (True, False):
-        q = torch.full((n * ho * wo * c,), 77, dtype=torch.int8, device='cuda')
-        acc2 = torch.zeros_like(acc)
+        q = out_buf(n * ho * wo * c, torch.int8, 77)
+        acc2 = out_buf(acc.shape, acc.dtype, 0)
         lib.call("hawq_depthwise3x3_requant", xd.data_ptr(), w9.data_ptr(), bd.data_ptr(), md.data_ptr(), ed.data_ptr(), n, h, w, c, 0, stride,
                  relu, lo, hi, q.data_ptr(), acc2.data_ptr() if keep_acc else None, stream())
         assert np.array_equal(q.cpu().numpy().reshape(n, ho, wo, c).astype(np.int64), ref), (shape, keep_acc)
@@ -783,8 +780,8 @@ def test_depthwise3x3_requant_matches_accumulators_plus_host_dyadic(lib, orc, sh
     if c >= 8:   # padding channels declared (C_valid): same tensor with zeros there - their weights, bias and multipliers are zero by contract
         wz, bz = wt.copy(), b.copy()
         wz[c - 4:], bz[c - 4:] = 0, 0
-        q2 = torch.full_like(q, 55)
-        acc3 = torch.full_like(acc, 55)
+        q2 = out_buf(q.shape, q.dtype, 55)
+        acc3 = out_buf(acc.shape, acc.dtype, 55)
         wzd, bzd = dev(np.ascontiguousarray(wz.reshape(c, 9).T)), dev(bz)
         lib.call("hawq_depthwise3x3_requant", xd.data_ptr(), wzd.data_ptr(), bzd.data_ptr(), md.data_ptr(),
                  ed.data_ptr(), n, h, w, c, c - 4, stride, relu, lo, hi, q2.data_ptr(), acc3.data_ptr(), stream())
@@ -837,9 +834,9 @@ def test_residual_epilogue_without_relu_and_with_the_16_bit_clamp(lib, orc, mode
     lo, hi = (0, 127) if mode == "relu_clamp_noid" else (-128, 127)
     ref_q = odyadic(orc, v, mq, eq, (lo, hi))
     md, ed = dev(m2), dev(e2)
-    flags = torch.zeros(1, dtype=torch.int32, device='cuda')
-    out_res = torch.full((v.size,), 7, dtype=torch.int32, device='cuda')
-    out_q = torch.full((v.size,), 7, dtype=torch.int8, device='cuda')
+    flags = out_buf(1, torch.int32, 0)
+    out_res = out_buf(v.size, torch.int32, 7)
+    out_q = out_buf(v.size, torch.int8, 7)
     a.epilogue, a.m, a.e, a.flags = lib.EPI_RESIDUAL, md.data_ptr(), ed.data_ptr(), flags.data_ptr()
     a.res_out, a.res_out_bits = out_res.data_ptr(), 32
     a.out_q, a.out_bits, a.q_lo, a.q_hi, a.mq, a.eq = out_q.data_ptr(), 8, lo, hi, int(mq[0]), int(eq[0])
@@ -865,7 +862,7 @@ def test_quantize_im2col_is_the_input_quantiser_plus_patch_gather(lib, orc, hw):
     scale = f32(0.0173)
     q = orc.quantize_f32(x, scale, 8)
     ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-    out = torch.full((n * ho * wo * 64,), 55, dtype=torch.int8, device='cuda')
+    out = out_buf(n * ho * wo * 64, torch.int8, 55)
     xd = dev(x)
     lib.call("hawq_quantize_im2col3x3s2", xd.data_ptr(), out.data_ptr(), n, 3, h, w, float(f32(1) / scale), -128, 127, stream())
     got = out.cpu().numpy().reshape(n, ho, wo, 64).astype(np.int64)
@@ -884,7 +881,7 @@ def test_quantize_im2col_is_the_input_quantiser_plus_patch_gather(lib, orc, hw):
         w27[:, :27, 0, 0] = wt.transpose(0, 2, 3, 1).reshape(64, 27)
         a, keep = conv_args(lib, ref.transpose(0, 3, 1, 2), w27, b, 1, 0, 8, 8)
         a.in_ = out.data_ptr()
-        o = torch.zeros(n * ho * wo * 64, dtype=torch.int32, device='cuda')
+        o = out_buf(n * ho * wo * 64, torch.int32, 0)
         a.epilogue, a.out_acc = lib.EPI_RAW, o.data_ptr()
         lib.call("hawq_conv2d", C.byref(a), stream())
         assert np.array_equal(o.cpu().numpy().reshape(n, ho, wo, 64).transpose(0, 3, 1, 2), acc)
@@ -910,9 +907,9 @@ def test_range_statistics_kernels_match_reference_kats(lib):
         lo, hi = device_min_max(x.cuda())
         assert float(lo) == float(x.min()) and float(hi) == float(x.max())
         for k in {1, (n + 1) // 2, n}:
-            out = torch.zeros(1, device='cuda')
-            scratch = torch.zeros(264, dtype=torch.int32, device='cuda')
-            xd = x.cuda()
+            out = out_buf(1, torch.float32, 0)
+            scratch = out_buf(264, torch.int32, 0)
+            xd = dev(x.numpy())
             lib.call("hawq_kthvalue_f32", xd.data_ptr(), n, k, 0, out.data_ptr(), scratch.data_ptr(), stream())
             assert float(out) == float(torch.kthvalue(x, k).values), (n, k)
             lib.call("hawq_kthvalue_f32", xd.data_ptr(), n, k, 1, out.data_ptr(), scratch.data_ptr(), stream())

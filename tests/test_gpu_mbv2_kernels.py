@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from tests.guard import dev, guard_arena, out_buf  # noqa: F401  (guard_arena: fixture)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_arena")]
 f32 = np.float32
 
 
@@ -26,10 +28,6 @@ def lib():
 def orc():
     from oracle import oracle
     return oracle
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def stream():
@@ -78,15 +76,15 @@ def fast_scalar(ratio, vmax):
 @pytest.mark.parametrize("fast", [False, True])
 @pytest.mark.parametrize("mode", ["closing_clamp16", "closing_identity", "requant"])
 @pytest.mark.parametrize("widths", [(24, 32, 16, 16), (16, 16, 24, 32), (96, 96, 40, 48)])
-def test_conv2d_on_narrow_tensors(lib, orc, widths, mode, fast):
+def test_conv2d_on_narrow_tensors(lib, orc, widths, mode, fast, nhw=(2, 11, 9)):
     """ABI 4: a 1x1 conv whose K and N are padded to 64 reads rows of in_pitch bytes and writes rows of out_pitch channels.  The bytes a
     64-byte chunk reads beyond its row are the next pixel's (garbage here) and meet zero weights; channels >= out_pitch are not written
-    (the buffer ends right behind the last row).  REQUANT on both its epilogues, and the signed RESIDUAL forms of MobileNetV2 - exact
+    (the buffer ends right behind the last row, and the guard arena of this file checks the bytes behind it).  REQUANT on both its epilogues, and the signed RESIDUAL forms of MobileNetV2 - exact
     and with the fast contract's arithmetic on the direct epilogue (hawq_conv_args.fast_tables with a 32-bit carrier)."""
     from hawq_amd.packing import pack_conv_weight
     cin, ipitch, cout, opitch = widths
     rng = np.random.default_rng(cin * 7 + cout + len(mode) + fast)
-    n, h, w = 2, 11, 9
+    n, h, w = nhw   # (tests/test_gpu_guard_edges.py runs the same cases on 1 x 1 and 3 x 3 maps)
     cin_p, cout_p = (cin + 63) // 64 * 64, (cout + 63) // 64 * 64
     x = rng.integers(0, 128, (n, cin, h, w)).astype(np.int64)
     wt = rng.integers(-127, 128, (cout, cin, 1, 1)).astype(np.int64)
@@ -100,10 +98,10 @@ def test_conv2d_on_narrow_tensors(lib, orc, widths, mode, fast):
     a.in_, a.wgt, a.bias, a.m, a.e = (keep[k].data_ptr() for k in ("x", "w", "b", "m", "e"))
     a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad, a.in_bits, a.w_bits = n, h, w, cin_p, cout_p, 1, 1, 1, 0, 8, 8
     a.in_pitch, a.out_pitch = (ipitch if ipitch != cin_p else 0), (opitch if opitch != cout_p else 0)
-    flags = torch.zeros(1, dtype=torch.int32, device='cuda')
+    flags = out_buf(1, torch.int32, 0)
     a.flags = flags.data_ptr()
     npx = n * h * w
-    out_q = torch.full((npx * opitch,), 7, dtype=torch.int8, device='cuda')
+    out_q = out_buf(npx * opitch, torch.int8, 7)
     a.out_q, a.out_bits = out_q.data_ptr(), 8
     if fast:
         a.fast_tables, a.ctab = fbits & 7, ctab.data_ptr()
@@ -132,7 +130,7 @@ def test_conv2d_on_narrow_tensors(lib, orc, widths, mode, fast):
         if fast and (tie1 or tieq):
             a.fast_tables |= 4
         ref_q = odyadic(orc, v, mq, eq, (-128, 127))
-        out16 = torch.full((npx * opitch,), 7, dtype=torch.int32, device='cuda')
+        out16 = out_buf(npx * opitch, torch.int32, 7)
         a.res_out, a.res_out_bits, a.q_lo, a.q_hi, a.mq, a.eq = out16.data_ptr(), 32, -128, 127, int(mq[0]), int(eq[0])
     tiles = range(1, lib.load().hawq_conv2d_num_tiles() - lib.load().hawq_conv2d_num_band_tiles() + 1)
     ran = 0
@@ -239,8 +237,8 @@ def test_linear_bottleneck_against_the_oracle(lib, orc, unit, tile):
     q.out_pitch = opitch if opitch != cout_p else 0
     # (stride-2 units: the exact-tie instantiation although no table needs it - it is exact round-half-even for any table)
     q.epilogue, q.res_no_relu, q.res_clamp16, q.fast_tables = lib.EPI_RESIDUAL, 1, int(not identity), (f3 & 7) | (4 if (tid[2] or tq[2] or stride == 2) else 0)
-    out16 = torch.full((n * ho * wo * opitch,), 7, dtype=torch.int32, device='cuda')
-    out_q = torch.full((n * ho * wo * opitch,), 7, dtype=torch.int8, device='cuda')
+    out16 = out_buf(n * ho * wo * opitch, torch.int32, 7)
+    out_q = out_buf(n * ho * wo * opitch, torch.int8, 7)
     q.res_out, q.res_out_bits, q.out_q, q.out_bits, q.q_lo, q.q_hi, q.mq, q.eq = out16.data_ptr(), 32, out_q.data_ptr(), 8, -128, 127, int(tq[0][0]), int(tq[1][0])
     if identity:
         q.res_in, q.res_in_bits, q.m_id_scalar, q.e_id_scalar = keep['res'].data_ptr(), 32, int(tid[0][0]), int(tid[1][0])
@@ -290,11 +288,11 @@ def test_stem3x3s2_against_the_oracle(lib, orc, hw, u8):
     a.wgt, a.ctab = keep['w'].data_ptr(), ctab.data_ptr()
     a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad, a.in_bits, a.w_bits = n, Ho, Wo, 64, 64, 1, 1, 1, 0, 8, 8
     a.epilogue, a.res_no_relu, a.res_clamp16, a.fast_tables, a.out_pitch = lib.EPI_RESIDUAL, 0, 1, (fb & 7) | (4 if tq[2] else 0), opitch
-    out16 = torch.full((n * Ho * Wo * opitch,), 7, dtype=torch.int32, device='cuda')
-    out_q = torch.full((n * Ho * Wo * opitch,), 7, dtype=torch.int8, device='cuda')
+    out16 = out_buf(n * Ho * Wo * opitch, torch.int32, 7)
+    out_q = out_buf(n * Ho * Wo * opitch, torch.int8, 7)
     a.res_out, a.res_out_bits, a.out_q, a.out_bits, a.q_lo, a.q_hi, a.mq, a.eq = out16.data_ptr(), 32, out_q.data_ptr(), 8, 0, 127, int(tq[0][0]), int(tq[1][0])
     if u8:
-        keep['x'], keep['lut'] = dev(xu), lut.reshape(-1).cuda()
+        keep['x'], keep['lut'] = dev(xu), dev(lut.reshape(-1).numpy())
         args = (None, keep['x'].data_ptr(), keep['lut'].data_ptr(), H, W, 0.0, 0, 0)
     else:
         keep['x'] = dev(xf)
@@ -329,7 +327,7 @@ def test_depthwise3x3_requant_fast_against_the_oracle(lib, orc, shape, tie):
     keep = dict(x=dev(stored(x, pitch, rng)), w=dev(w9))
     if pitch > c:   # padding channels of a stored activation tensor are zeros
         keep['x'][:n * h * w * pitch].view(-1, pitch)[:, c:] = 0
-    out = torch.full((n * ho * wo * pitch,), 7, dtype=torch.int8, device='cuda')
+    out = out_buf(n * ho * wo * pitch, torch.int8, 7)
     lib.call("hawq_depthwise3x3_requant_fast", keep['x'].data_ptr(), keep['w'].data_ptr(), ctab.data_ptr(), (f & 7) | (4 if tie else 0), n, h, w, pitch, c, stride,
              0, 100, out.data_ptr(), stream())
     assert np.array_equal(unstored(out, n, ho, wo, pitch, c), ref)

@@ -9,10 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard import guard_arena, out_buf  # noqa: F401  (guard_arena: fixture)
 from tests.test_gpu_fused import _case
 from tests.test_gpu_kernels import dev, lib, nhwc, odyadic, orc, stream, unpack_q  # noqa: F401
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_arena")]
 
 S = 2
 # (n, h, w): odd map with M' = 32 (an image boundary inside the single wave tile); non-square with M' = 45 (ragged last wave tile);
@@ -51,7 +52,7 @@ def _launch_sub(lib, entry, args, conv, shape, row_bytes, what):
     """Launch `entry` with conv.out_sub = S into a poisoned buffer: (the M' dense rows, as [n][h'][w'][row_bytes])."""
     n, h, w = shape
     nbytes = n * _sub(h) * _sub(w) * row_bytes
-    buf = torch.full((nbytes + TAIL,), POISON, dtype=torch.uint8, device='cuda')
+    buf = out_buf(nbytes + TAIL, torch.uint8, POISON)
     conv.out_q, conv.out_sub = buf.data_ptr(), S
     lib.call(entry, C.byref(args), stream())
     conv.out_sub = 0
@@ -83,7 +84,7 @@ def test_solo_kernel_equals_the_dense_launch_gathered(lib, orc, c, shape, tie):
         # tie-free tables with all per-channel pre-shifts zero (bit 3), the general form, exact ties (force_tie: fast_tables == 5)
         for k0 in (0, 8) if (keep['k0'] and not tie) else (0,):
             ex.fast_tables = ft | k0
-            dense = torch.full((n * h * w * row_bytes,), POISON, dtype=torch.uint8, device='cuda')
+            dense = out_buf(n * h * w * row_bytes, torch.uint8, POISON)
             ex.out_q, a.tile = dense.data_ptr(), 0
             lib.call("hawq_conv_expand_reduce", C.byref(a), stream())
             want = _dense_rows(dense, shape, row_bytes)[:, ::S, ::S]
@@ -135,7 +136,7 @@ def test_generic_path_equals_the_dense_launch_gathered(lib, orc, c, shape, res_b
     took = 0
     for tile in range(0, n_tiles + 1):
         ex.tile, ex.out_sub = tile, S
-        scratch = torch.empty(n * h * w * c3 + TAIL, dtype=torch.uint8, device='cuda')
+        scratch = out_buf(n * h * w * c3 + TAIL, torch.uint8, None)
         ex.out_q = scratch.data_ptr()
         if lib.load().hawq_conv2d(C.byref(ex), stream()) != 0:
             assert tile > n_tiles - n_special, (tile, "a general tile refused the launch")
@@ -143,7 +144,7 @@ def test_generic_path_equals_the_dense_launch_gathered(lib, orc, c, shape, res_b
             continue
         ex.out_sub = 0
         took += 1
-        dense = torch.full((n * h * w * c3,), POISON, dtype=torch.uint8, device='cuda')
+        dense = out_buf(n * h * w * c3, torch.uint8, POISON)
         ex.out_q = dense.data_ptr()
         lib.call("hawq_conv2d", C.byref(ex), stream())
         want = _dense_rows(dense, shape, c3)[:, ::S, ::S]
@@ -170,7 +171,7 @@ def test_everything_else_refuses_out_sub(lib, orc):
     a.reduce.out_sub = 0
     # the expand conv alone: same count with and without, but not with a dense residual to write
     a.reduce = lib.ExpandReduceArgs().reduce
-    qbuf = torch.zeros(n * h * w * c3, dtype=torch.uint8, device='cuda')
+    qbuf = out_buf(n * h * w * c3, torch.uint8, 0)
     ex.out_q, ex.res_out = qbuf.data_ptr(), None
     nsolo = L.hawq_conv_expand_reduce_variants(C.byref(a))
     ex.out_sub = S

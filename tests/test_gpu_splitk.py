@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard import guard_arena, out_buf  # noqa: F401  (guard_arena: fixture)
 from tests.test_gpu_kernels import conv_args, dev, make_conv, nhwc, pack_act, rand_tables, stream, to_planar
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_arena")]
 
 CANDIDATES = (2, 4, 8, 16, 32)
 
@@ -45,8 +46,8 @@ def orc():
 def workspace(lib, a, s):
     slab, cnt = C.c_int64(), C.c_int64()
     lib.call("hawq_conv2d_splitk_workspace", C.byref(a), s, C.byref(slab), C.byref(cnt))
-    return (torch.full((slab.value,), 0x5a, dtype=torch.uint8, device="cuda"),   # garbage: every slab byte is written before it is read
-            torch.zeros(cnt.value // 4, dtype=torch.int32, device="cuda"))
+    return (out_buf(slab.value, torch.uint8, 0x5a),   # garbage: every slab byte is written before it is read
+            out_buf(cnt.value // 4, torch.int32, 0))
 
 
 def splitk(lib, a, s, ws):
@@ -66,7 +67,7 @@ def test_raw_accumulators_equal_the_oracle_for_every_slice_count(lib, orc, layer
     x, wt, b = make_conv(rng, n, h, w, cin, cout, k, 8, 8)
     ref = nhwc(orc.conv2d(x, wt, b, stride, pad))
     a, keep = conv_args(lib, x, wt, b, stride, pad, 8, 8)
-    out = torch.zeros(ref.size, dtype=torch.int32, device="cuda")
+    out = out_buf(ref.size, torch.int32, 0)
     a.epilogue, a.out_acc = lib.EPI_RAW, out.data_ptr()
     slices = accepted(lib, a)
     assert slices and slices[0] == 2
@@ -87,9 +88,9 @@ def _tables(lib, keep, a, b, m, e, mode):
 
 
 def _outputs(a, M, cout, res_bits=16):
-    t = dict(q=torch.zeros(M * cout, dtype=torch.uint8, device="cuda"),
-             res=torch.zeros(M * cout, dtype=torch.uint16 if res_bits == 16 else torch.int32, device="cuda"),
-             flags=torch.zeros(1, dtype=torch.int32, device="cuda"))
+    t = dict(q=out_buf(M * cout, torch.uint8, 0),
+             res=out_buf(M * cout, torch.uint16 if res_bits == 16 else torch.int32, 0),
+             flags=out_buf(1, torch.int32, 0))
     a.out_q, a.flags = t['q'].data_ptr(), t['flags'].data_ptr()
     if a.epilogue == 2:
         a.res_out, a.res_out_bits = t['res'].data_ptr(), res_bits

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard import guard_arena, out_buf  # noqa: F401  (guard_arena: fixture)
 from tests.test_gpu_kernels import dev, lib, odyadic, orc, rand_tables, stream, unpack_q  # noqa: F401  (lib, orc: fixtures)
 
 f32 = np.float32
@@ -40,7 +41,7 @@ def run_variants(lib, xu8, wt, b, m, e, mq, eq, r16, q_ref, fasts):
     n, hh, ww, cin = xu8.shape
     hp, wp = r16.shape[2:]
     xd, ud = dev(images(xu8)), dev(xu8)
-    lut = input_quant_lut(float(INV), MEAN, STD).cuda()
+    lut = dev(input_quant_lut(float(INV), MEAN, STD).numpy())
     wd, bd, md, ed = dev(pack_stem_weight(wt)), dev(b.astype(np.int32)), dev(m), dev(e)
     tail = lambda res, qo, bits, lo, hi, fast: (wd.data_ptr(), bd.data_ptr(), md.data_ptr(), ed.data_ptr(), -32768, 32767,
                                                 res.data_ptr() if res is not None else 0, qo.data_ptr() if qo is not None else 0,
@@ -49,8 +50,8 @@ def run_variants(lib, xu8, wt, b, m, e, mq, eq, r16, q_ref, fasts):
         for fast in fasts:
             for bits, (lo, hi) in ((8, (-128, 127)), (4, (0, 15))):
                 for want_res, want_q in ((1, 1), (0, 1), (1, 0)):
-                    res = torch.full((r16.size,), 0xABCD, dtype=torch.uint16, device='cuda') if want_res else None
-                    qo = torch.full((r16.size * bits // 8,), 0x5A, dtype=torch.uint8, device='cuda') if want_q else None
+                    res = out_buf(r16.size, torch.uint16, 0xABCD) if want_res else None
+                    qo = out_buf(r16.size * bits // 8, torch.uint8, 0x5A) if want_q else None
                     if entry == "f32":
                         lib.call("hawq_stem_fused", xd.data_ptr(), n, cin, hh, ww, float(INV), -128, 127, *tail(res, qo, bits, lo, hi, fast))
                     else:
@@ -91,6 +92,7 @@ def test_seam_shapes_are_what_they_claim():
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guard_arena")
 @pytest.mark.parametrize("shape", SEAMS + SMALL)
 def test_stem_tile_seams_and_small_maps(lib, orc, shape):
     xu8, wt, b, m, e, mq, eq, r16, q_ref, fasts = random_case(orc, shape)
@@ -142,6 +144,7 @@ def test_directed_cases_put_the_maximum_on_neighbour_owned_positions(orc):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guard_arena")
 def test_stem_directed_neighbour_ownership(lib, orc):
     d = directed_case(orc)
     acc, r16, q_ref = d["ref"]
