@@ -36,14 +36,25 @@ Round 4 (97 k -> 209 k img/s at batch 128):
   * tapped plans (``keep_accumulators``) always run the round-3 launch list - the taps ARE the intermediate tensors.
 Every ``hawq_conv2d`` launch is tile-tuned by timing, and the batch runs as one or two concurrent sub-batch chains inside the one
 hipGraph, whichever replays faster (graph, chains, entry points and event timing: hawq_amd/runner.py).
-Switches (results never change): HAWQ_MBV2_UNFUSED=1 three launches per unit and the im2col init
-block; HAWQ_MBV2_UNIT_TILE=1..4 organisation of the unit launch (``hawq_bottleneck_args.tile``); HAWQ_MBV2_EXACT=1 exact closing
-epilogues; HAWQ_MBV2_PAD64=1 round 3's 64-padded tensors; HAWQ_MBV2_CHAINS, HAWQ_MBV2_TILES.
+Switches (results never change; set by any non-empty string, "0" included; ``Switches.from_env`` reads them ONCE, in the constructor,
+and sub-chains share the record): HAWQ_MBV2_UNFUSED=1 three launches per unit and the im2col init block; HAWQ_MBV2_UNIT_TILE=1..4
+organisation of the unit launch (``hawq_bottleneck_args.tile``; 1 also keeps units wider than 64 channels on three launches);
+HAWQ_MBV2_NO_WIDE_UNITS=1 three launches for the 160-wide units of the 7 x 7 maps; HAWQ_MBV2_EXACT=1 exact closing epilogues and
+depthwise requants, HAWQ_MBV2_PAD64=1 round 3's 64-padded tensors (both with UNFUSED's launch list); HAWQ_NO_FC2=1 the classifier on
+``hawq_conv2d``.  HAWQ_MBV2_CHAINS is read by the constructor too, HAWQ_MBV2_TILES when a batch shape's launches are first tuned.
+
+Records, choice, writer.  The form of a launch is decided by pure functions of the switches and plain numbers: ``unit_launches`` (a
+unit as one launch or three), ``stem_form`` (the init block), ``closing_is_fast`` (a closing conv's epilogue).  ``_build_one`` is the
+sequence of emitter calls for init block, units and head; each appends one ``Launch`` record per launch, in issue order, and the three
+kinds of closing launch (``hawq_conv2d``, unit, stem) fill their closing conv's ``hawq_conv_args`` block in one function, ``_closing``.  Plan
+bytes, counters, the tuner's list, ``taps`` and ``_stem_args`` are read off the records; one writer (``_write``) turns them into the callables
+of a chain: ``_ops`` and, for ``forward_uint8``, ``_ops_u8``, which differs in the input launch alone.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from functools import partial
 
 import numpy as np
@@ -59,13 +70,24 @@ def _pad64(c: int) -> int:
     return (c + 63) // 64 * 64
 
 
-def _pitch(c: int) -> int:
+class Switches(namedtuple("Switches", "unfused exact pad64 unit_tile no_wide_units no_fc2", defaults=(False, False, False, 0, False, False))):
+    """The measurement switches of this engine (module docstring), as its constructor found them."""
+    round3 = property(lambda self: self.unfused or self.exact or self.pad64)   # every unit on three launches, the init block on im2col rows
+
+    @classmethod
+    def from_env(cls, environ) -> "Switches":
+        """From the mapping `environ`; a switch is set by any non-empty string (``os.environ.get`` truthiness: "0" sets it)."""
+        on = [bool(environ.get(var)) for var in ("HAWQ_MBV2_UNFUSED", "HAWQ_MBV2_EXACT", "HAWQ_MBV2_PAD64", "HAWQ_MBV2_NO_WIDE_UNITS", "HAWQ_NO_FC2")]
+        return cls(*on[:3], int(environ.get("HAWQ_MBV2_UNIT_TILE", 0)), *on[3:])
+
+
+def _pitch(c: int, pad64: bool = False) -> int:
     """Channels per STORED pixel row of a c-channel tensor (round 4): the next multiple of 16, not of 64 - MobileNetV2's 16 / 24 / 32 /
     96 / 144 / 160-channel tensors are stored (almost) at their own width.  The GEMMs still see K and N padded to the 64-channel tile:
     a conv reads its K = pad64(c) bytes per pixel through `hawq_conv_args.in_pitch` (the bytes beyond the row meet zero weights) and
-    writes only the first `out_pitch` channels of its 64-channel tiles (include/hawq_mi355.h, ABI 4).  HAWQ_MBV2_PAD64=1 restores the
-    64-padded tensors of round 3 (A/B switch for measurements)."""
-    return _pad64(c) if os.environ.get("HAWQ_MBV2_PAD64") else (c + 15) // 16 * 16
+    writes only the first `out_pitch` channels of its 64-channel tiles (include/hawq_mi355.h, ABI 4).  `pad64` (HAWQ_MBV2_PAD64=1)
+    restores the 64-padded tensors of round 3 (A/B switch for measurements)."""
+    return _pad64(c) if pad64 else (c + 15) // 16 * 16
 
 
 def _padded(v, n, fill=0):
@@ -101,10 +123,93 @@ def _fast_scalar(s_in, s_out, vmax):
     return int(m[0]), int(ek[0]), not tables_are_fast(m, ek, vb)
 
 
+def _lifted(s_in, s_w, s_out, vbits, bias, dev):
+    """The table of QuantAct(conv output) lifted to the conv kernels' fast contract (one v_mad_i64_i32 against a fused per-channel constant):
+    None when it does not fit, else (ctab: the fused constants on the device, `bias` folded; m, e: the lifted tables padded to 64 channels,
+    on the host; the launch's ``fast_tables`` word: bit 0 the contract, bit 2 exact round-half-even where the host cannot exclude a tie, bit 3 no pre-shifts)."""
+    try:
+        m, e = requant_table(s_in, s_w, s_out, vbits=vbits)
+    except ValueError:
+        return None
+    if not tables_fit_fast(m, e, vbits):
+        return None
+    flags = (1 if tables_are_fast(m, e, vbits) else 5) | (8 if not (np.asarray(e) >> 8).any() else 0)
+    cp = _pad64(len(bias))
+    m, e = _padded(m, cp), _padded(e, cp, 33)
+    return _i32(packing.pack_ctab(_padded(bias, cp), m, e), dev), m, e, flags
+
+
+# What ``unit_launches`` reads of a unit: stored width of the block input, true width of the hidden tensors, stored width of the block output;
+# strides and kernels of conv1, conv2, conv3; depthwise: conv1 dense, conv2 one group per channel; residual and whether the identity scalar is
+# lifted; proved: conv1's, conv2's, conv3's table and the next block-input scalar are lifted for the fast contract; tops: conv1's / conv2's clamp
+UnitShape = namedtuple("UnitShape", "cin_s hidden cout_s strides kernels depthwise residual id_proved proved tops",
+                       defaults=((1, 1, 1), (1, 3, 1), True, False, True, (True,) * 4, (127, 127)))
+
+
+def _unit_shape(u, q_proved: bool) -> UnitShape:
+    """of the prepared unit `u` (an entry of ``P['units']``) in front of a block-input QuantAct whose scalar table is lifted or not"""
+    e1, e2 = u['layers']
+    L = L1, L2, L3 = e1['layer'], e2['layer'], u['proj']['layer']
+    return UnitShape(L1.cin_s, L2.cout, L3.cout_s, tuple(l.stride for l in L), tuple(l.kh if l.kh == l.kw else (l.kh, l.kw) for l in L),
+                     L1.groups == 1 and L2.groups != 1, u['residual'], u.get('id_fast') is not None,
+                     (bool(e1.get('fast')), 'dw_ctab' in e2, u['proj']['fast'] is not None, q_proved), (e1['hi'], e2['hi']))
+
+
+def unit_launches(sw: Switches, tapped: bool, u: UnitShape, h: int, w: int) -> int:
+    """1: the unit on the (h, w) map runs as ONE hawq_linear_bottleneck launch; 3: conv1, conv2, conv3 launch by launch.  One launch needs
+    conv1 1x1 + depthwise 3x3 + conv3 1x1, every requant table proved for the fast contract, and block input and output at most 96 channels
+    wide (the launch keeps the projection's accumulators of an 8 x 16 pixel tile in registers) - or, on output maps of at most 8 x 8 pixels
+    (the 7 x 7 maps of the 224 x 224 network), the 160-wide units of the width-1 network (8 x 8 tiles, the projection spread over the waves
+    by output blocks).  Tapped plans (keep_accumulators) always run three launches - the taps ARE the intermediate tensors."""
+    pointwise = u.depthwise and u.kernels == (1, 3, 1) and u.strides[0] == u.strides[2] == 1
+    if tapped or sw.round3 or not pointwise or not all(u.proved) or (u.residual and not u.id_proved) or max(u.tops) > 127:
+        return 3
+    narrow = (16, 32, 64) if sw.unit_tile == 1 else (16, 32, 64, 96)
+    if u.cin_s in narrow and u.cout_s in narrow:
+        return 1
+    s2 = u.strides[1]
+    wide = (sw.unit_tile != 1 and not sw.no_wide_units and (h - 1) // s2 + 1 <= 8 and (w - 1) // s2 + 1 <= 8 and u.hidden > 96
+            and (u.cin_s, u.cout_s, s2) in ((160, 160, 1), (96, 160, 2)))   # (the launch also takes 160 -> 320: 34 us against 29 us as three launches)
+    return 1 if wide else 3
+
+
+def stem_form(sw: Switches, tapped: bool, im2col: bool, cout_s: int, proved: bool) -> str:
+    """The init block: "one" launch (hawq_stem3x3s2: input QuantAct + 3x3 / stride 2 conv + closing QuantActs, no patch rows in memory;
+    `proved`: its table and unit 1's block-input scalar are lifted), "im2col" (the input quantiser writes 27-value patch rows for a 1x1
+    conv) or "nhwc" (int8 NHWC padded to 64 channels: an init conv that is not 3x3 / stride 2 on 3 channels)."""
+    if not im2col:
+        return "nhwc"
+    return "one" if proved and not tapped and not sw.round3 and cout_s in (16, 32) else "im2col"
+
+
+def closing_is_fast(sw: Switches, proved: bool, id_proved: bool, q_proved: bool) -> bool:
+    """A closing conv runs the direct epilogue's 3-instruction requants (hawq_conv2d, ConvP.gfast) when every table of the launch is lifted
+    and bounded by the host - its own, the identity branch's, the next block-input QuantAct's (True where it has none) -, else the exact ones."""
+    return proved and id_proved and q_proved and not sw.exact
+
+
+class Launch:
+    """One launch of a chain: `stage`, the base name of its taps (``init_block``, ``unit7.conv2``, ``final_block``, ``output`` ...; a one-launch
+    unit carries its closing conv's, ``unit7.conv3``); the entry point `name`; `args`, the call's arguments before the stream (a ctypes block
+    stands for its address); `kind`: "conv" (a hawq_conv2d the tuner may give a tile), "unit", "stem", "depthwise" or "other"; `nbytes`, what it
+    moves at the network's true widths; `taps`, the tensors it exposes (name -> (tensor, stored NHWC shape, true channels)); `fast`: "expand" (conv1 on
+    the fast REQUANT epilogue), "closing" (a closing conv, all tables proved) or None; `geom`: (N, H, W, stored C, true C, stride) where `args` hold no block."""
+    __slots__ = ("stage", "name", "args", "kind", "nbytes", "taps", "fast", "geom")
+
+    def __init__(self, stage, name, args, kind="other", nbytes=0, taps=None, fast=None, geom=None):
+        self.stage, self.name, self.args, self.kind, self.nbytes, self.taps, self.fast, self.geom = stage, name, tuple(args), kind, nbytes, taps or {}, fast, geom
+
+
+def plan_totals(launches) -> dict:
+    """what the launches move; conv launches on the fast REQUANT epilogue; units that run as ONE launch; closing launches (conv, unit, stem) with all tables proved"""
+    return dict(plan_bytes=sum(r.nbytes for r in launches), n_fast=sum(r.fast == "expand" for r in launches),
+                n_fused_units=sum(r.kind == "unit" for r in launches), n_fast_closing=sum(r.fast == "closing" for r in launches))
+
+
 class _Layer:
     """Device-resident integer parameters of one QuantBnConv2d, channel-padded."""
 
-    def __init__(self, mod: QuantBnConv2d, s_a, dev, from_buffers, im2col=False):
+    def __init__(self, mod: QuantBnConv2d, s_a, dev, from_buffers, im2col=False, pad64=False):
         if not from_buffers:
             mod.prepare(s_a)
         w = np.rint(mod.weight_integer.detach().cpu().numpy().astype(np.float64)).astype(np.int64)
@@ -117,7 +222,7 @@ class _Layer:
         self.cin = cg * self.groups
         self.cin_p, self.cout_p = _pad64(self.cin), _pad64(self.cout)
         # stored width of the input / output tensor (the im2col rows of the init conv are 64 bytes by construction)
-        self.cin_s, self.cout_s = (self.cin_p if im2col else _pitch(self.cin)), _pitch(self.cout)   # (im2col: the init layer, either input form)
+        self.cin_s, self.cout_s = (self.cin_p if im2col else _pitch(self.cin, pad64)), _pitch(self.cout, pad64)   # (im2col: the init layer, either input form)
         self.s_w = mod.convbn_scaling_factor.detach().float().cpu().reshape(-1)
         b = np.clip(np.rint(mod.bias_integer.detach().cpu().numpy().astype(np.float64)), -2 ** 31, 2 ** 31 - 1).astype(np.int64)
         self.bias = _i32(_padded(b, self.cout_p), dev)
@@ -140,19 +245,6 @@ class _Layer:
             self.w9p = torch.from_numpy(w9p).to(dev)
         else:
             raise PlanNotApplicable("grouped convolutions other than depthwise 3x3 are outside MobileNetV2")
-
-    def fast_closing(self, s_a, s_out, dev):
-        """Fused constants (packing.pack_ctab, bias folded) of this conv's unit-closing requant when the lifted table fits the fast
-        contract: dict(ctab, tie) or None.  Lets the direct RESIDUAL epilogue run 3-instruction requants (hawq_conv2d, ConvP.gfast)."""
-        try:
-            mm, ee = requant_table(s_a, self.s_w, s_out, vbits=self.vbits)
-        except ValueError:
-            return None
-        if not tables_fit_fast(mm, ee, self.vbits):
-            return None
-        cp = self.cout_p
-        return dict(ctab=_i32(packing.pack_ctab(_padded(self.b_host, cp), _padded(mm, cp), _padded(ee, cp, 33)), dev),
-                    tie=not tables_are_fast(mm, ee, self.vbits))
 
     def table(self, s_a, s_out, dev):
         """(m, e) of QuantAct(conv output): ratio S_a * S_w[c] / S_out, padded channels m = 0"""
@@ -180,6 +272,9 @@ def _relu6_is_relu(s_a, s_w, m, e, q_hi) -> bool:
 
 class MobileNetV2Engine(GraphRunner):
     """Callable: fp32 NCHW images on the GPU -> fp32 logits of the frozen Q_MobileNetV2 (see the module docstring)."""
+    # an engine that has not built a plan - and a sub-chain: one chain, no graph of its own
+    use_graph, chains, chains_req, _launches, _ops, taps = False, 1, 1, (), (), {}
+    _batch = x_u8 = _ops_u8 = None
 
     def __init__(self, model, from_buffers=None, use_graph: bool = True, keep_accumulators: bool = False, chains: int = 0):
         """``from_buffers``: run on the modules' integer buffers / stored scales (a network restored by ``load_quantized_checkpoint``)
@@ -205,19 +300,15 @@ class MobileNetV2Engine(GraphRunner):
             raise RuntimeError("MobileNetV2Engine: move the model to the MI355X first (no CPU path)")
         self.stream = torch.cuda.Stream(device=self.dev)
         self.flags = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self._batch = self._graph = None
-        self.taps, self.subs = {}, []
+        self.sw = Switches.from_env(os.environ)
         self.chains_req = 1 if keep_accumulators else max(0, int(os.environ.get("HAWQ_MBV2_CHAINS", chains)))
         self.chains = max(1, self.chains_req)
         self._prepare()
 
     def _spawn(self):
-        """a chain of this plan: shares the prepared parameters, owns its stream and activation buffers"""
+        """a chain of this plan: shares the prepared parameters and the switches, owns its stream and activation buffers"""
         sub = object.__new__(MobileNetV2Engine)
-        sub.model, sub.from_buffers, sub.keep_acc, sub.dev, sub.flags, sub.P = self.model, self.from_buffers, self.keep_acc, self.dev, self.flags, self.P
-        sub.use_graph, sub.stream = False, torch.cuda.Stream(device=self.dev)
-        sub._batch = sub._graph = None
-        sub.taps, sub.subs, sub.chains, sub.chains_req = {}, [], 1, 1
+        sub.keep_acc, sub.dev, sub.flags, sub.P, sub.sw, sub.stream = self.keep_acc, self.dev, self.flags, self.P, self.sw, torch.cuda.Stream(device=self.dev)
         return sub
 
     # ------------------------------------------------------------------ host-side preparation
@@ -239,6 +330,18 @@ class MobileNetV2Engine(GraphRunner):
                 raise PlanNotApplicable("the unit-closing QuantAct must be 16-bit symmetric (every shipped schedule)")
             return self._scale(act)
 
+        def conv_layer(mod, s_a, im2col=False):
+            return _Layer(mod, s_a, dev, self.from_buffers, im2col, self.sw.pad64)
+
+        def closing(L, s_a, s_o, relu6=None):
+            """a conv that closes a stage: its exact table and, where the lifted one fits the fast contract, `fast` = dict(ctab, tie);
+            `relu6` names the QuantAct of the init / final block, behind a ReLU6: refused if that is not ReLU + clamp here"""
+            md, ed, mh, eh = L.table(s_a, s_o, dev)
+            if relu6 and not _relu6_is_relu(float(s_a.item()), L.s_w.numpy(), mh, eh, 32767):
+                raise PlanNotApplicable(f"{relu6} range above 6.0 behind ReLU6")
+            lifted = _lifted(s_a, L.s_w, s_o, L.vbits, L.b_host, dev)
+            return dict(layer=L, m=md, e=ed, fast=None if lifted is None else dict(ctab=lifted[0], tie=bool(lifted[3] & 4))), mh, eh
+
         def activated(layer, s_a, act):
             """conv -> ReLU6 -> QuantAct(case 0): table + clamp; refuses if ReLU6 is not ReLU + clamp here"""
             s_o = self._scale(act)
@@ -246,36 +349,17 @@ class MobileNetV2Engine(GraphRunner):
             lo, hi = _rng(act)
             if not _relu6_is_relu(float(s_a.item()), layer.s_w.numpy(), mh, eh, hi):
                 raise PlanNotApplicable("a QuantAct range above 6.0 behind ReLU6: the integer plan folds ReLU6 into the clamp")
-            ent = dict(m=md, e=ed, lo=max(lo, 0), hi=hi, s=s_o)
-            if layer.groups == 1:
-                # the conv kernels' short requant (one v_mad_i64_i32 against a fused per-channel constant) where the lifted table
-                # fits its contract; bit 2 keeps exact round-half-even where a tie cannot be excluded on the host
-                mm, ee = requant_table(s_a, layer.s_w, s_o, vbits=layer.vbits)
-                if tables_fit_fast(mm, ee, layer.vbits):
-                    cp = layer.cout_p
-                    ent['ctab'] = _i32(packing.pack_ctab(_padded(layer.b_host, cp), _padded(mm, cp), _padded(ee, cp, 33)), dev)
-                    ent['m'], ent['e'] = _i32(_padded(mm, cp), dev), _i32(_padded(ee, cp, 33), dev)
-                    ent['fast'] = (1 if tables_are_fast(mm, ee, layer.vbits) else 5) | (8 if not (np.asarray(ee) >> 8).any() else 0)   # bit 3: no pre-shifts
-            else:
-                # depthwise: the same contract for the one-launch unit (hawq_linear_bottleneck); hawq_depthwise3x3_requant keeps (m, e)
-                try:
-                    mm, ee = requant_table(s_a, layer.s_w, s_o, vbits=layer.vbits)
-                    fits = tables_fit_fast(mm, ee, layer.vbits)
-                except ValueError:
-                    fits = False
-                if fits:
-                    cp = layer.cout_p
-                    ent['dw_ctab'] = _i32(packing.pack_ctab(_padded(layer.b_host, cp), _padded(mm, cp), _padded(ee, cp, 33)), dev)
-                    ent['dw_fast'] = (1 if tables_are_fast(mm, ee, layer.vbits) else 5) | (8 if not (np.asarray(ee) >> 8).any() else 0)
+            ent = dict(layer=layer, m=md, e=ed, lo=max(lo, 0), hi=hi, s=s_o)
+            lifted = _lifted(s_a, layer.s_w, s_o, layer.vbits, layer.b_host, dev)
+            if lifted is not None and layer.groups == 1:   # the conv kernels' short requant instead of the exact table
+                ent.update(ctab=lifted[0], m=_i32(lifted[1], dev), e=_i32(lifted[2], dev), fast=lifted[3])
+            elif lifted is not None:   # depthwise: for the one-launch unit and hawq_depthwise3x3_requant_fast; the exact launch keeps (m, e)
+                ent.update(dw_ctab=lifted[0], dw_fast=lifted[3])
             return ent
 
         # init block: conv -> ReLU6 -> quant_act_int32 (16 bit)
-        init = _Layer(m.init_block, s_in, dev, self.from_buffers, im2col=True)
         s16 = act16(m.quant_act_int32)
-        md, ed, mh, eh = init.table(s_in, s16, dev)
-        if not _relu6_is_relu(float(s_in.item()), init.s_w.numpy(), mh, eh, 32767):
-            raise PlanNotApplicable("quant_act_int32 range above 6.0 behind ReLU6")
-        P['init'] = dict(layer=init, m=md, e=ed, fast=init.fast_closing(s_in, s16, dev))
+        P['init'] = closing(conv_layer(m.init_block, s_in, im2col=True), s_in, s16, "quant_act_int32")[0]
         units = []
         s_prev = s16
         ob_prev = 32768   # bound on |16-bit output| of the producer in front of the current unit (init: ReLU + clamp)
@@ -289,16 +373,12 @@ class MobileNetV2Engine(GraphRunner):
             s_x = s_a
             d['layers'] = []
             for conv, act in u.activated:
-                L = _Layer(getattr(u, conv), s_x, dev, self.from_buffers)
-                ent = activated(L, s_x, getattr(u, act))
-                ent['layer'] = L
+                ent = activated(conv_layer(getattr(u, conv), s_x), s_x, getattr(u, act))
                 d['layers'].append(ent)
                 s_x = ent['s']
-            proj = _Layer(u.conv3, s_x, dev, self.from_buffers)
+            proj = conv_layer(u.conv3, s_x)
             s_o = act16(u.quant_act_int32)
-            md, ed, _, _ = proj.table(s_x, s_o, dev)
-            d['proj'] = dict(layer=proj, m=md, e=ed, fast=proj.fast_closing(s_x, s_o, dev))
-            _, _, mh3, eh3 = proj.table(s_x, s_o, dev)
+            d['proj'], mh3, eh3 = closing(proj, s_x, s_o)
             ob = _requant_bound([(1 << int(v)) for v in proj.vbits], mh3, eh3)
             if d['residual']:
                 m1, e1 = requant_table(s_prev, one, s_o, lift=False)
@@ -318,12 +398,8 @@ class MobileNetV2Engine(GraphRunner):
         s_b = self._scale(qb)
         mq, eq = requant_table(s_prev, one, s_b, lift=False)
         P['before_final'] = dict(mq=int(mq[0]), eq=int(eq[0]), rng=_rng(qb), q_fast=_fast_scalar(s_prev, s_b, ob_prev))
-        fin = _Layer(m.features.final_block, s_b, dev, self.from_buffers)
         s_f = act16(m.quant_act_int32_final)
-        md, ed, mh, eh = fin.table(s_b, s_f, dev)
-        if not _relu6_is_relu(float(s_b.item()), fin.s_w.numpy(), mh, eh, 32767):
-            raise PlanNotApplicable("quant_act_int32_final range above 6.0 behind ReLU6")
-        P['final'] = dict(layer=fin, m=md, e=ed, fast=fin.fast_closing(s_b, s_f, dev))
+        P['final'] = closing(conv_layer(m.features.final_block, s_b), s_b, s_f, "quant_act_int32_final")[0]
         ao = m.quant_act_output
         s8 = self._scale(ao)
         mq, eq = requant_table(s_f, one, s8, lift=False)
@@ -347,61 +423,187 @@ class MobileNetV2Engine(GraphRunner):
         P['fc'] = dict(w=torch.from_numpy(packing.pack_conv_weight(w.reshape(nout, k, 1, 1), 8, _pad64(k), nout_p)).to(dev),
                        bias=_i32(np.zeros(nout_p), dev), fscale=torch.from_numpy(fscale).to(dev), nout=nout, nout_p=nout_p, k=_pad64(k))
 
-    # ------------------------------------------------------------------ launch list
+    # ------------------------------------------------------------------ launch records
+    def _alloc(self, n, dtype):
+        # 64 elements of slack: a conv that reads a narrow tensor through in_pitch fetches up to 48 bytes past the last pixel row
+        return torch.empty(n + 64, dtype=dtype, device=self.dev)[:n]
+
+    def _buf(self, n, dtype):
+        """a plan buffer: kept alive with the plan (the captured launches hold its address)"""
+        self._keep.append(self._alloc(n, dtype))
+        return self._keep[-1]
+
+    def _emit(self, r: Launch, tap=None):
+        """The next record of the chain.  A tapped plan (tests only) first exposes the int32 accumulators of the record's conv, `tap`
+        = (its argument block, true output channels), through a RAW launch on a copy of the block, under the record's stage name."""
+        if tap is not None and self.keep_acc:
+            a, cout = tap
+            ho, wo = (a.H + 2 * a.pad - a.KH) // a.stride + 1, (a.W + 2 * a.pad - a.KW) // a.stride + 1
+            acc, raw = self._buf(a.N * ho * wo * a.Cout, torch.int32), _lib.ConvArgs()   # (the accumulators are dense [M][Cout])
+            C.memmove(C.byref(raw), C.byref(a), C.sizeof(raw))
+            raw.epilogue, raw.out_acc, raw.res_in, raw.res_out, raw.out_q = _lib.EPI_RAW, acc.data_ptr(), None, None, None
+            raw.fast_tables, raw.ctab, raw.out_pitch = 0, None, 0
+            self._launches.append(Launch(r.stage, "hawq_conv2d", (raw,), taps={r.stage: (acc, (a.N, ho, wo, a.Cout), cout)}))
+        self._launches.append(r)
+
     def _conv_args(self, L, x, N, H, W):
         a = _lib.ConvArgs()
         a.in_, a.wgt, a.bias = x.data_ptr(), L.w.data_ptr(), L.bias.data_ptr()
         a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad = N, H, W, L.cin_p, L.cout_p, L.kh, L.kw, L.stride, L.pad
-        a.in_bits = a.w_bits = 8
-        a.flags = self.flags.data_ptr()
+        a.in_bits, a.w_bits, a.flags = 8, 8, self.flags.data_ptr()
         a.in_pitch = L.cin_s if L.cin_s != L.cin_p else 0       # 0 = dense rows
-        a.out_pitch = L.cout_s if L.cout_s != L.cout_p else 0   # (RAW taps reset it: the accumulators are dense [M][Cout])
+        a.out_pitch = L.cout_s if L.cout_s != L.cout_p else 0   # (RAW taps reset it)
         return a
 
-    def _one_launch(self, u, nq_fast, h, w) -> bool:
-        """Does this unit run as one hawq_linear_bottleneck launch?  Needs: conv1 1x1 + depthwise 3x3 + conv3 1x1 with every requant
-        table proved for the fast contract, block input and output at most 96 channels wide (the launch keeps the projection's
-        accumulators of an 8 x 16 pixel tile in registers) - or, on output maps of at most 8 x 8 pixels, the 160 / 320-channel units of
-        the width-1 network (8 x 8 tiles, the projection spread over the waves by output blocks; (h, w) = the unit's input map).  HAWQ_MBV2_UNFUSED=1: three launches per unit everywhere (A/B switch);
-        tapped plans (keep_accumulators) always run the three launches - the taps ARE the intermediate tensors."""
-        if self.keep_acc or os.environ.get("HAWQ_MBV2_UNFUSED") or os.environ.get("HAWQ_MBV2_EXACT") or os.environ.get("HAWQ_MBV2_PAD64"):
-            return False
-        if len(u['layers']) != 2:
-            return False
-        e1, e2 = u['layers']
-        L1, L2, L3 = e1['layer'], e2['layer'], u['proj']['layer']
-        if L1.groups != 1 or (L1.kh, L1.kw, L1.stride) != (1, 1, 1) or L2.groups == 1 or (L3.kh, L3.kw, L3.stride) != (1, 1, 1):
-            return False
-        if not e1.get('fast') or 'dw_ctab' not in e2 or u['proj']['fast'] is None or nq_fast is None:
-            return False
-        if u['residual'] and u.get('id_fast') is None:
-            return False
-        if e1['hi'] > 127 or e2['hi'] > 127:
-            return False
-        narrow = (16, 32, 64) if os.environ.get("HAWQ_MBV2_UNIT_TILE") == "1" else (16, 32, 64, 96)
-        if L1.cin_s in narrow and L3.cout_s in narrow:
-            return True
-        # wider units: the launch's 8 x 8 tile family - output maps of at most 8 x 8 pixels (the 7 x 7 maps of the 224 x 224 network)
-        ho, wo = (h - 1) // L2.stride + 1, (w - 1) // L2.stride + 1
-        return (os.environ.get("HAWQ_MBV2_UNIT_TILE") != "1" and not os.environ.get("HAWQ_MBV2_NO_WIDE_UNITS") and ho <= 8 and wo <= 8 and L2.cout > 96
-                and (L1.cin_s, L3.cout_s, L2.stride) in ((160, 160, 1), (96, 160, 2)))   # (the launch also takes 160 -> 320: 34 us against 29 us as three launches)
+    def _closing(self, stage, ent, x, n, h, w, res, nxt, relu, need16=True, carrier16=False):
+        """The hawq_conv_args block of a closing conv `ent` (P['init'], a unit's 'proj', P['final']) on an (h, w) map with `x`'s address as its input:
+        conv + 16-bit QuantAct - the identity branch `res` = (int32 carrier, m_id, e_id, id_fast) summed in and the sum not clamped, or None - + the
+        next block-input QuantAct `nxt` = (mq, eq, (lo, hi), q_fast) or None.  The carrier is only written where something reads it (`need16`: the next unit's
+        identity, the pool; or a tap), as uint16 where `carrier16` allows.  -> (block, carrier, int8 q, ho, wo, fast, bytes written + weight bytes, taps)"""
+        L = ent['layer']
+        ho, wo = (h + 2 * L.pad - L.kh) // L.stride + 1, (w + 2 * L.pad - L.kw) // L.stride + 1
+        a, taps, out16, q, shape = self._conv_args(L, x, n, h, w), {}, None, None, (n, ho, wo, L.cout_s)
+        a.epilogue, a.m, a.e = _lib.EPI_RESIDUAL, ent['m'].data_ptr(), ent['e'].data_ptr()
+        a.res_no_relu, a.res_clamp16, a.n_valid = int(not relu), int(res is None), L.cout   # (the exact epilogue skips the padding channels)
+        fast = closing_is_fast(self.sw, ent['fast'] is not None, res is None or res[3] is not None, nxt is None or nxt[3] is not None)
+        if fast:
+            tie = ent['fast']['tie'] or (res is not None and res[3][2]) or (nxt is not None and nxt[3][2])
+            a.fast_tables, a.ctab = (5 if tie else 1), ent['fast']['ctab'].data_ptr()
+        u16 = bool(carrier16 and relu and res is None and not self.keep_acc)   # post-ReLU, clamped: 0 .. 32767 fits the uint16 carrier
+        if need16 or self.keep_acc:
+            out16 = self._buf(n * ho * wo * L.cout_s, torch.int16 if u16 else torch.int32)
+            a.res_out, a.res_out_bits, taps[stage + ":out16"] = out16.data_ptr(), (16 if u16 else 32), (out16, shape, L.cout)
+        if res is not None:
+            a.res_in, a.res_in_bits, (a.m_id_scalar, a.e_id_scalar) = res[0].data_ptr(), 32, (res[3][:2] if fast else res[1:3])
+        if nxt is not None:
+            q = self._buf(n * ho * wo * L.cout_s, torch.int8)
+            a.out_q, a.out_bits, (a.q_lo, a.q_hi), (a.mq, a.eq) = q.data_ptr(), 8, nxt[2], (nxt[3][:2] if fast else nxt[:2])
+            taps[stage + ":next_q"] = (q, shape, L.cout)
+        per_pixel = ((2 if u16 else 4) if need16 else 0) + (1 if nxt is not None else 0) + (4 if res is not None else 0)
+        return a, out16, q, ho, wo, fast, n * ho * wo * L.cout * per_pixel + L.weight_bytes, taps
 
-    def _tap(self, ops, keep, name, a, N, ho, wo, cout, cout_p):
-        """extra RAW launch exposing the conv's int32 accumulators (tests only)"""
-        acc = self._alloc(N * ho * wo * cout_p, torch.int32)
-        r = _lib.ConvArgs()
-        C.memmove(C.byref(r), C.byref(a), C.sizeof(r))
-        r.epilogue, r.out_acc, r.res_in, r.res_out, r.out_q = _lib.EPI_RAW, acc.data_ptr(), None, None, None
-        r.fast_tables, r.ctab, r.out_pitch = 0, None, 0
-        keep += [acc, r]
-        self.taps[name] = (acc, (N, ho, wo, cout_p), cout)
-        ops.append(partial(_lib.call, "hawq_conv2d", C.byref(r), self.stream.cuda_stream))
+    def _emit_closing_conv(self, stage, ent, x, n, h, w, res, nxt, relu, need16=True, carrier16=False):
+        """a closing conv on its own: hawq_conv2d on the int8 tensor `x` -> (carrier, q, ho, wo)"""
+        a, out16, q, ho, wo, fast, nbytes, taps = self._closing(stage, ent, x, n, h, w, res, nxt, relu, need16, carrier16)
+        self._emit(Launch(stage, "hawq_conv2d", (a,), "conv", nbytes + n * h * w * ent['layer'].cin, taps, "closing" if fast else None), tap=(a, ent['layer'].cout))
+        return out16, q, ho, wo
 
-    def _time_graph(self, reps: int = 12) -> float:
-        return super()._time_graph(reps)
+    def _emit_unit(self, stage, u, x, n, h, w, res, nxt, need16):
+        """a whole unit on its block input `x` (an (h, w) map) as ONE hawq_linear_bottleneck launch: the hidden tensors stay on chip"""
+        (e1, e2), b = u['layers'], _lib.BottleneckArgs()
+        L1, L2 = e1['layer'], e2['layer']
+        a, out16, q, ho, wo, fast, nbytes, taps = self._closing(stage, u['proj'], x, n, (h - 1) // L2.stride + 1, (w - 1) // L2.stride + 1,
+                                                               res, nxt, False, need16)
+        if not fast:
+            raise RuntimeError("one-launch unit without proved tables (plan logic error)")
+        x1 = self._conv_args(L1, x, n, h, w)
+        x1.epilogue, x1.relu, x1.q_lo, x1.q_hi, x1.out_bits = _lib.EPI_REQUANT, 1, e1['lo'], e1['hi'], 8
+        x1.fast_tables, x1.ctab, x1.out_pitch = e1['fast'], e1['ctab'].data_ptr(), 0
+        C.memmove(C.byref(b.expand), C.byref(x1), C.sizeof(x1))
+        C.memmove(C.byref(b.project), C.byref(a), C.sizeof(a))
+        b.dw_wgt9c, b.dw_ctab, b.tile = L2.w9p.data_ptr(), e2['dw_ctab'].data_ptr(), self.sw.unit_tile   # (tile 1: the [pixel][channel] organisation, A/B switch)
+        b.dw_stride, b.dw_q_lo, b.dw_q_hi, b.dw_fast_tables, b.c_mid = L2.stride, e2['lo'], e2['hi'], e2['dw_fast'], L2.cout
+        if not _lib.load().hawq_linear_bottleneck_ok(C.byref(b)):
+            raise RuntimeError("hawq_linear_bottleneck refuses a unit the plan selected for it")
+        self._emit(Launch(stage, "hawq_linear_bottleneck", (b,), "unit", nbytes + n * h * w * L1.cin + L1.weight_bytes + L2.weight_bytes, taps, "closing"))
+        return out16, q, ho, wo
 
+    def _emit_hidden(self, stage, ent, x, n, h, w):
+        """an activated conv of a unit on its own: conv1 (hawq_conv2d, REQUANT) or the depthwise conv2 -> (int8 tensor, ho, wo)"""
+        L = ent['layer']
+        ho, wo = (h + 2 * L.pad - L.kh) // L.stride + 1, (w + 2 * L.pad - L.kw) // L.stride + 1
+        out, nbytes, shape = self._buf(n * ho * wo * L.cout_s, torch.int8), n * (h * w * L.cin + ho * wo * L.cout) + L.weight_bytes, (n, ho, wo, L.cout_s)
+        taps, geom = {stage + ":q": (out, shape, L.cout)}, (n, h, w, L.cout_s, L.cout, L.stride)
+        if L.groups == 1:
+            a = self._conv_args(L, x, n, h, w)
+            a.epilogue, a.relu, a.m, a.e = _lib.EPI_REQUANT, 1, ent['m'].data_ptr(), ent['e'].data_ptr()
+            a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), 8, ent['lo'], ent['hi']
+            if ent.get('fast'):
+                a.fast_tables, a.ctab = ent['fast'], ent['ctab'].data_ptr()
+            else:
+                a.n_valid = L.cout
+            self._emit(Launch(stage, "hawq_conv2d", (a,), "conv", nbytes, taps, "expand" if ent.get('fast') else None), tap=(a, L.cout))
+        elif not self.keep_acc and 'dw_ctab' in ent and ent['hi'] <= 127 and not self.sw.exact:   # the host-proved short requant
+            self._emit(Launch(stage, "hawq_depthwise3x3_requant_fast", (x.data_ptr(), L.w.data_ptr(), ent['dw_ctab'].data_ptr(), ent['dw_fast'] & 7, *geom,
+                                                                        ent['lo'], ent['hi'], out.data_ptr()), "depthwise", nbytes, taps, geom=geom))
+        else:   # (a tapped plan's accumulators are this launch's second output)
+            acc = self._buf(n * ho * wo * L.cout_s, torch.int32) if self.keep_acc else None
+            taps.update({stage: (acc, shape, L.cout)} if self.keep_acc else {})
+            self._emit(Launch(stage, "hawq_depthwise3x3_requant", (x.data_ptr(), L.w.data_ptr(), L.bias.data_ptr(), ent['m'].data_ptr(), ent['e'].data_ptr(), *geom,
+                                                                   1, ent['lo'], ent['hi'], out.data_ptr(), acc.data_ptr() if self.keep_acc else None), "depthwise", nbytes, taps, geom=geom))
+        return out, ho, wo
+
+    def _emit_init(self, N, H, W, nxt, need16):
+        """the input QuantAct and the init block, in the form ``stem_form`` chooses -> (carrier, q, ho, wo)"""
+        P, ent = self.P, self.P['init']
+        init, x_in, images = ent['layer'], self.x_in.data_ptr(), N * 3 * H * W * 4
+        form = stem_form(self.sw, self.keep_acc, init.im2col, init.cout_s, ent['fast'] is not None and nxt[3] is not None)
+        H0, W0 = ((H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1) if init.im2col else (H, W)
+        if form == "one":   # (no patch rows in memory: the launch reads the images)
+            a, out16, q, ho, wo, fast, nbytes, taps = self._closing("init_block", ent, self.x_in, N, H0, W0, None, nxt, True, need16)
+            if not fast or not _lib.load().hawq_stem3x3s2_ok(x_in, None, None, H, W, C.byref(a)):
+                raise RuntimeError("hawq_stem3x3s2 refuses the init block the plan selected for it")
+            self._emit(Launch("init_block", "hawq_stem3x3s2", (x_in, None, None, H, W, P['inv_s_in'], -128, 127, a), "stem", images + nbytes, taps, "closing"))
+            return out16, q, ho, wo
+        if form == "im2col":   # input QuantAct (quant_modules.py:271-274) straight into the init conv's 27-value patches, one 64-byte row per output pixel
+            xq = self._buf(N * H0 * W0 * 64, torch.int8)
+            self._emit(Launch("quant_input", "hawq_quantize_im2col3x3s2", (x_in, xq.data_ptr(), N, 3, H, W, P['inv_s_in'], -128, 127), nbytes=images))
+        else:   # input QuantAct then int8 NHWC, channels padded to 64
+            xq_f, xq = self._buf(N * 3 * H * W, torch.float32), self._buf(N * H * W * init.cin_p, torch.int8).zero_()
+            self._emit(Launch("quant_input", "hawq_fakequant_f32", (x_in, xq_f.data_ptr(), N * 3 * H * W, P['inv_s_in'], P['s_in'], -128, 127), nbytes=images))
+            self._emit(Launch("quant_input", "hawq_f32_nchw_to_q_nhwc", (xq_f.data_ptr(), xq.data_ptr(), N, 3, H, W, init.cin_p, 8, P['s_in'])))
+        return self._emit_closing_conv("init_block", ent, xq, N, H0, W0, None, nxt, True, need16)
+
+    def _emit_head(self, q, N, h, w, logits_view):
+        """final block, average pool (+ quant_act_output) and the classifier (+ dequant) into ``logits``"""
+        fin, o, fc = self.P['final'], self.P['out'], self.P['fc']
+        x16, _, h, w = self._emit_closing_conv("final_block", fin, q, N, h, w, None, None, True, carrier16=True)   # (post-ReLU, clamped: a uint16 carrier halves what the pool reads)
+        cl = fin['layer'].cout_s
+        if cl != fin['layer'].cout_p:
+            raise PlanNotApplicable("the final block's width must be a multiple of 64 (the pool and the classifier read dense rows)")
+        if fc['k'] != cl:
+            raise RuntimeError("classifier width does not match the final block")
+        qf, pooled = self._buf(N * cl, torch.int8), (self._buf(N * cl, torch.int32) if self.keep_acc else None)
+        self._emit(Launch("pool", "hawq_avgpool_requant", (x16.data_ptr(), 16 if x16.dtype == torch.int16 else 32, N, h * w, cl, qf.data_ptr(),
+                          None if pooled is None else pooled.data_ptr(), o['mq'], o['eq'], o['rng'][0], o['rng'][1]), geom=(N, h, w, cl, cl, 1)))
+        self.logits = logits_view if logits_view is not None else self._buf(N * fc['nout'], torch.float32).view(N, fc['nout'])
+        a = _lib.ConvArgs()
+        a.in_, a.wgt, a.bias = qf.data_ptr(), fc['w'].data_ptr(), fc['bias'].data_ptr()
+        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad = N, 1, 1, fc['k'], fc['nout_p'], 1, 1, 1, 0
+        a.in_bits, a.w_bits, a.epilogue = 8, 8, _lib.EPI_DEQUANT
+        a.out_f32, a.fscale, a.ldo, a.n_valid = self.logits.data_ptr(), fc['fscale'].data_ptr(), fc['nout'], fc['nout']
+        if _lib.load().hawq_fc_dequant_ok(N, fc['k'], fc['nout_p']) and not self.sw.no_fc2:
+            # round 5: the classifier's own kernel (fc_dequant.hip), the same bytes as the DEQUANT epilogue; nothing to tune
+            r = Launch("output", "hawq_fc_dequant", (a.in_, a.wgt, a.bias, a.fscale, a.out_f32, N, fc['k'], fc['nout_p'], fc['nout'], fc['nout']),
+                       geom=(N, 1, 1, fc['k'], fc['nout'], 1))
+        else:
+            r = Launch("output", "hawq_conv2d", (a,), "conv")
+        self._emit(r, tap=(a, fc['nout']))
+
+    def _build_one(self, N, H, W, x_view=None, logits_view=None):
+        """the records of one chain over N images, in issue order - init block, units, head - and its callables"""
+        units, b = self.P['units'], self.P['before_final']
+        self._launches, self._keep, self._graph, self._tuned = [], [], None, False
+        self.x_in = x_view if x_view is not None else self._buf(N * 3 * H * W, torch.float32).view(N, 3, H, W)
+        block_in = [(u['mq'], u['eq'], u['q_rng'], u['q_fast']) for u in units] + [(b['mq'], b['eq'], b['rng'], b['q_fast'])]   # the block-input QuantActs
+        x16, q, h, w = self._emit_init(N, H, W, block_in[0], need16=units[0]['residual'])
+        for ui, u in enumerate(units):
+            name, nxt = f"unit{ui + 1}", block_in[ui + 1]
+            res = (x16, u['m_id'], u['e_id'], u.get('id_fast')) if u['residual'] else None
+            need16 = bool(ui + 1 < len(units) and units[ui + 1]['residual'])
+            if len(u['layers']) == 2 and unit_launches(self.sw, self.keep_acc, _unit_shape(u, nxt[3] is not None), h, w) == 1:
+                x16, q, h, w = self._emit_unit(name + ".conv3", u, q, N, h, w, res, nxt, need16)
+                continue
+            for ent in u['layers']:
+                q, h, w = self._emit_hidden(f"{name}.{'conv1' if ent['layer'].groups == 1 else 'conv2'}", ent, q, N, h, w)
+            x16, q, h, w = self._emit_closing_conv(name + ".conv3", u['proj'], q, N, h, w, res, nxt, False, need16)
+        self._emit_head(q, N, h, w, logits_view)
+        self.taps, self._batch = {k: v for r in self._launches for k, v in r.taps.items()}, (N, H, W)
+        self._ops, self._ops_u8 = self._write(), None
+
+    # ------------------------------------------------------------------ chains, tuning
     def _on_graph_dropped(self):
-        self.x_u8 = None
+        self.x_u8 = self._ops_u8 = None
 
     def _build(self, N, H, W, x_view=None, logits_view=None):
         if x_view is None and self.chains_req == 0 and self.use_graph and N >= 16:
@@ -409,7 +611,7 @@ class MobileNetV2Engine(GraphRunner):
             for c in (1, 2):   # keep whichever chain count replays faster
                 self.chains = c
                 self._build_chains(N, H, W)
-                timing[c] = self._time_graph()
+                timing[c] = self._time_graph(12)
                 self._drop_graph()
             self.chains, self.chain_timing_ms = min(timing, key=timing.get), timing
         self._build_chains(N, H, W, x_view, logits_view)
@@ -417,9 +619,8 @@ class MobileNetV2Engine(GraphRunner):
     def _build_chains(self, N, H, W, x_view=None, logits_view=None):
         self._drop_graph()
         if self.chains > 1 and N >= 2 * self.chains and x_view is None:
-            nout = self.P['fc']['nout']
             self.x_in = torch.empty(N, 3, H, W, dtype=torch.float32, device=self.dev)
-            self.logits = torch.empty(N, nout, dtype=torch.float32, device=self.dev)
+            self.logits = torch.empty(N, self.P['fc']['nout'], dtype=torch.float32, device=self.dev)
             self.subs, b0 = [], 0
             for i in range(self.chains):
                 b1 = b0 + N // self.chains + (1 if i < N % self.chains else 0)
@@ -427,286 +628,89 @@ class MobileNetV2Engine(GraphRunner):
                 sub._build_chains(b1 - b0, H, W, self.x_in[b0:b1], self.logits[b0:b1])
                 self.subs.append(sub)
                 b0 = b1
-            self._ops, self._keep, self._batch, self.taps = [], [], (N, H, W), {}
+            self._launches, self._ops, self._keep, self._batch, self.taps = [], [], [], (N, H, W), {}
             return
         self.subs = []
         self._build_one(N, H, W, x_view, logits_view)
-
-    def _alloc(self, n, dtype):
-        # 64 elements of slack: a conv that reads a narrow tensor through in_pitch fetches up to 48 bytes past the last pixel row
-        return torch.empty(n + 64, dtype=dtype, device=self.dev)[:n]
-
-    def _build_one(self, N, H, W, x_view=None, logits_view=None):
-        P, dev, sp = self.P, self.dev, self.stream.cuda_stream
-        ops, keep, self.taps, self._graph = [], [], {}, None
-        self._convs, self._tuned = [], False   # hawq_conv2d argument structs of the plan (tile autotuning)
-        self.n_fast = 0
-        self.n_fused_units = 0    # units that run as ONE launch (hawq_linear_bottleneck)
-        self.n_fast_closing = 0   # unit-closing launches whose tables are all proved: the direct epilogue with 3-instruction requants
-        self.plan_bytes = N * 3 * H * W * 4   # bytes the plan has to move at the networks' true widths (no padding channels)
-        alloc = self._alloc
-        self.x_in = x_view if x_view is not None else alloc(N * 3 * H * W, torch.float32).view(N, 3, H, W)
-        init = P['init']['layer']
-        # the init block as ONE launch (hawq_stem3x3s2): input QuantAct + 3x3 / stride 2 conv + closing QuantActs, no patch rows in memory
-        one_stem = bool(init.im2col and P['init']['fast'] is not None and P['units'][0]['q_fast'] is not None and not self.keep_acc
-                        and init.cout_s in (16, 32) and not any(os.environ.get(k) for k in ("HAWQ_MBV2_UNFUSED", "HAWQ_MBV2_EXACT", "HAWQ_MBV2_PAD64")))
-        self._stem_args = None
-        if one_stem:
-            H0, W0 = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
-            xq = None
-            self._u8_index, self._xq, self._u8_op = len(ops), None, None   # forward_uint8 swaps this launch for its uint8 form
-        elif init.im2col:
-            # input QuantAct (quant_modules.py:271-274) straight into the init conv's 27-value patches, one 64-byte row per output pixel
-            H0, W0 = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
-            xq = alloc(N * H0 * W0 * 64, torch.int8)
-            self._u8_index, self._xq, self._u8_op = len(ops), xq, None   # forward_uint8 swaps this launch for the table look-up form
-            ops.append(partial(_lib.call, "hawq_quantize_im2col3x3s2", self.x_in.data_ptr(), xq.data_ptr(), N, 3, H, W, P['inv_s_in'], -128, 127, sp))
-            keep.append(xq)
-        else:
-            # input QuantAct then int8 NHWC, channels padded to 64
-            self._u8_index = None
-            H0, W0 = H, W
-            xq_f = alloc(N * 3 * H * W, torch.float32)
-            xq = alloc(N * H * W * init.cin_p, torch.int8).zero_()
-            ops.append(partial(_lib.call, "hawq_fakequant_f32", self.x_in.data_ptr(), xq_f.data_ptr(), N * 3 * H * W, P['inv_s_in'], P['s_in'], -128, 127, sp))
-            ops.append(partial(_lib.call, "hawq_f32_nchw_to_q_nhwc", xq_f.data_ptr(), xq.data_ptr(), N, 3, H, W, init.cin_p, 8, P['s_in'], sp))
-            keep += [xq_f, xq]
-
-        def closing(L, m, e, x, n, h, w, res_in, m_id, e_id, relu, clamp16, nxt_q, name, need16=True, fast=None, id_fast=None, q_fast=None,
-                    unit=None, stem=None, carrier16=False):
-            """conv + unit-closing 16-bit QuantAct (+ the next block-input QuantAct) -> (int32 tensor, int8 q, ho, wo);
-            the 32-bit carrier is only written where something reads it (the next unit's identity, the pool, a tap).
-            ``unit`` = dict(x, h, w, conv1 entry, conv2 entry): the whole unit as ONE launch (hawq_linear_bottleneck) - x is then the
-            unit's block input and (h, w) the depthwise conv's output grid; ``stem`` = (H, W) of the images: the init block as ONE
-            launch on them (hawq_stem3x3s2), L being its im2col form"""
-            ho, wo = (h + 2 * L.pad - L.kh) // L.stride + 1, (w + 2 * L.pad - L.kw) // L.stride + 1
-            a = self._conv_args(L, (x if unit is None else unit['x']) if stem is None else self.x_in, n, h, w)
-            a.epilogue, a.m, a.e = _lib.EPI_RESIDUAL, m.data_ptr(), e.data_ptr()
-            out16 = None
-            u16 = bool(carrier16 and relu and clamp16 and not self.keep_acc)   # post-ReLU, clamped: 0 .. 32767 fits the uint16 carrier
-            if need16 or self.keep_acc:
-                out16 = alloc(n * ho * wo * L.cout_s, torch.int16 if u16 else torch.int32)
-                a.res_out, a.res_out_bits = out16.data_ptr(), (16 if u16 else 32)
-            in_bytes = h * w * L.cin if unit is None else unit['h'] * unit['w'] * unit['e1']['layer'].cin   # (the hidden tensors stay on chip)
-            if stem is not None:
-                in_bytes = 0   # (the images are already counted; no patch rows)
-            self.plan_bytes += n * (in_bytes + ho * wo * L.cout * (((2 if u16 else 4) if need16 else 0) + (1 if nxt_q is not None else 0) + (4 if res_in is not None else 0))) + L.weight_bytes
-            use_fast = (fast is not None and (res_in is None or id_fast is not None) and (nxt_q is None or q_fast is not None)
-                        and not os.environ.get("HAWQ_MBV2_EXACT"))
-            if res_in is not None:
-                a.res_in, a.res_in_bits, a.m_id_scalar, a.e_id_scalar = res_in.data_ptr(), 32, m_id, e_id
-                if use_fast:
-                    a.m_id_scalar, a.e_id_scalar = id_fast[0], id_fast[1]
-            a.res_no_relu, a.res_clamp16 = int(not relu), int(clamp16)
-            a.n_valid = L.cout   # the exact epilogue skips the padding channels
-            # every table of this launch lifted and bounded by the host -> the direct epilogue's 3-instruction requants (hawq_conv2d,
-            # ConvP.gfast); otherwise its exact dyadic_rne form.  HAWQ_MBV2_EXACT=1: A/B switch for measurements
-            if use_fast:
-                tie = fast['tie'] or (res_in is not None and id_fast[2]) or (nxt_q is not None and q_fast[2])
-                a.fast_tables, a.ctab = (5 if tie else 1), fast['ctab'].data_ptr()
-                self.n_fast_closing = getattr(self, "n_fast_closing", 0) + 1
-            q = None
-            if nxt_q is not None:
-                q = alloc(n * ho * wo * L.cout_s, torch.int8)
-                a.out_q, a.out_bits, a.mq, a.eq, (a.q_lo, a.q_hi) = q.data_ptr(), 8, nxt_q[0], nxt_q[1], nxt_q[2]
-                if use_fast:
-                    a.mq, a.eq = q_fast[0], q_fast[1]
-            if self.keep_acc:
-                self._tap(ops, keep, name, a, n, ho, wo, L.cout, L.cout_p)
-            keep.extend([a, out16, q])
-            if unit is not None:
-                if not use_fast:
-                    raise RuntimeError("one-launch unit without proved tables (plan logic error)")
-                e1, e2 = unit['e1'], unit['e2']
-                L1, L2 = e1['layer'], e2['layer']
-                b = _lib.BottleneckArgs()
-                x1 = self._conv_args(L1, unit['x'], n, unit['h'], unit['w'])
-                x1.epilogue, x1.relu, x1.q_lo, x1.q_hi, x1.out_bits = _lib.EPI_REQUANT, 1, e1['lo'], e1['hi'], 8
-                x1.fast_tables, x1.ctab, x1.out_pitch = e1['fast'], e1['ctab'].data_ptr(), 0
-                C.memmove(C.byref(b.expand), C.byref(x1), C.sizeof(x1))
-                C.memmove(C.byref(b.project), C.byref(a), C.sizeof(a))
-                b.dw_wgt9c, b.dw_ctab = L2.w9p.data_ptr(), e2['dw_ctab'].data_ptr()
-                b.dw_stride, b.dw_q_lo, b.dw_q_hi, b.dw_fast_tables, b.c_mid = L2.stride, e2['lo'], e2['hi'], e2['dw_fast'], L2.cout
-                b.tile = int(os.environ.get("HAWQ_MBV2_UNIT_TILE", 0))   # 1: the [pixel][channel] organisation of the launch (A/B switch)
-                if not _lib.load().hawq_linear_bottleneck_ok(C.byref(b)):
-                    raise RuntimeError("hawq_linear_bottleneck refuses a unit the plan selected for it")
-                keep.append(b)
-                self.plan_bytes += L1.weight_bytes + L2.weight_bytes
-                self.n_fused_units += 1
-                ops.append(partial(_lib.call, "hawq_linear_bottleneck", C.byref(b), sp))
-            elif stem is not None:
-                if not use_fast or not _lib.load().hawq_stem3x3s2_ok(self.x_in.data_ptr(), None, None, stem[0], stem[1], C.byref(a)):
-                    raise RuntimeError("hawq_stem3x3s2 refuses the init block the plan selected for it")
-                self._stem_args = a
-                ops.append(partial(_lib.call, "hawq_stem3x3s2", self.x_in.data_ptr(), None, None, stem[0], stem[1], P['inv_s_in'], -128, 127, C.byref(a), sp))
-            else:
-                self._convs.append((name, a))
-                ops.append(partial(_lib.call, "hawq_conv2d", C.byref(a), sp))
-            if out16 is not None:
-                self.taps[name + ":out16"] = (out16, (n, ho, wo, L.cout_s), L.cout)
-            if q is not None:
-                self.taps[name + ":next_q"] = (q, (n, ho, wo, L.cout_s), L.cout)
-            return out16, q, ho, wo
-
-        units = P['units']
-        u0 = units[0]
-        x16, q, h, w = closing(init, P['init']['m'], P['init']['e'], xq, N, H0, W0, None, 0, 33, True, True,
-                               (u0['mq'], u0['eq'], u0['q_rng']), "init_block", need16=u0['residual'], fast=P['init']['fast'], q_fast=u0['q_fast'],
-                               stem=(H, W) if one_stem else None)
-        for ui, u in enumerate(units):
-            name = f"unit{ui + 1}"
-            x = q
-            nxt = units[ui + 1] if ui + 1 < len(units) else None
-            nq = (nxt['mq'], nxt['eq'], nxt['q_rng']) if nxt is not None else (P['before_final']['mq'], P['before_final']['eq'], P['before_final']['rng'])
-            nq_fast = nxt['q_fast'] if nxt is not None else P['before_final']['q_fast']
-            pr = u['proj']
-            if self._one_launch(u, nq_fast, h, w):
-                e1, e2 = u['layers']
-                s2 = e2['layer'].stride
-                ho, wo = (h - 1) // s2 + 1, (w - 1) // s2 + 1
-                x16, q, h, w = closing(pr['layer'], pr['m'], pr['e'], None, N, ho, wo, x16 if u['residual'] else None, u.get('m_id', 0), u.get('e_id', 33),
-                                       False, not u['residual'], nq, name + ".conv3", need16=bool(nxt is not None and nxt['residual']),
-                                       fast=pr['fast'], id_fast=u.get('id_fast'), q_fast=nq_fast, unit=dict(x=x, h=h, w=w, e1=e1, e2=e2))
-                continue
-            for li, ent in enumerate(u['layers']):
-                L = ent['layer']
-                ho, wo = (h + 2 * L.pad - L.kh) // L.stride + 1, (w + 2 * L.pad - L.kw) // L.stride + 1
-                out = alloc(N * ho * wo * L.cout_s, torch.int8)
-                lname = f"{name}.{'conv1' if L.groups == 1 else 'conv2'}"
-                if L.groups == 1:
-                    a = self._conv_args(L, x, N, h, w)
-                    a.epilogue, a.relu, a.m, a.e = _lib.EPI_REQUANT, 1, ent['m'].data_ptr(), ent['e'].data_ptr()
-                    a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), 8, ent['lo'], ent['hi']
-                    if ent.get('fast'):
-                        a.fast_tables, a.ctab = ent['fast'], ent['ctab'].data_ptr()
-                        self.n_fast += 1
-                    else:
-                        a.n_valid = L.cout
-                    if self.keep_acc:
-                        self._tap(ops, keep, lname, a, N, ho, wo, L.cout, L.cout_p)
-                    keep.append(a)
-                    self._convs.append((lname, a))
-                    ops.append(partial(_lib.call, "hawq_conv2d", C.byref(a), sp))
-                else:
-                    acc = alloc(N * ho * wo * L.cout_s, torch.int32) if self.keep_acc else None
-                    if acc is not None:
-                        self.taps[lname] = (acc, (N, ho, wo, L.cout_s), L.cout)
-                    if acc is None and 'dw_ctab' in ent and ent['hi'] <= 127 and not os.environ.get("HAWQ_MBV2_EXACT"):
-                        # the host-proved short requant (the accumulator tap needs the exact launch's second output)
-                        ops.append(partial(_lib.call, "hawq_depthwise3x3_requant_fast", x.data_ptr(), L.w.data_ptr(), ent['dw_ctab'].data_ptr(), ent['dw_fast'] & 7,
-                                           N, h, w, L.cout_s, L.cout, L.stride, ent['lo'], ent['hi'], out.data_ptr(), sp))
-                    else:
-                        ops.append(partial(_lib.call, "hawq_depthwise3x3_requant", x.data_ptr(), L.w.data_ptr(), L.bias.data_ptr(), ent['m'].data_ptr(),
-                                           ent['e'].data_ptr(), N, h, w, L.cout_s, L.cout, L.stride, 1, ent['lo'], ent['hi'], out.data_ptr(),
-                                           None if acc is None else acc.data_ptr(), sp))
-                    keep.append(acc)
-                self.plan_bytes += N * (h * w * L.cin + ho * wo * L.cout) + L.weight_bytes
-                self.taps[lname + ":q"] = (out, (N, ho, wo, L.cout_s), L.cout)
-                keep.append(out)
-                x, h, w = out, ho, wo
-            x16, q, h, w = closing(pr['layer'], pr['m'], pr['e'], x, N, h, w, x16 if u['residual'] else None, u.get('m_id', 0), u.get('e_id', 33),
-                                   False, not u['residual'], nq, name + ".conv3", need16=bool(nxt is not None and nxt['residual']),
-                                   fast=pr['fast'], id_fast=u.get('id_fast'), q_fast=nq_fast)
-        fin = P['final']
-        # (the final block's values are post-ReLU and clamped: a uint16 carrier halves what the pool reads)
-        x16, _, h, w = closing(fin['layer'], fin['m'], fin['e'], q, N, h, w, None, 0, 33, True, True, None, "final_block", fast=fin['fast'], carrier16=True)
-        cl = fin['layer'].cout_s
-        if cl != fin['layer'].cout_p:
-            raise PlanNotApplicable("the final block's width must be a multiple of 64 (the pool and the classifier read dense rows)")
-        qf = alloc(N * cl, torch.int8)
-        pooled = alloc(N * cl, torch.int32) if self.keep_acc else None
-        o = P['out']
-        ops.append(partial(_lib.call, "hawq_avgpool_requant", x16.data_ptr(), 16 if x16.dtype == torch.int16 else 32, N, h * w, cl, qf.data_ptr(), None if pooled is None else pooled.data_ptr(),
-                           o['mq'], o['eq'], o['rng'][0], o['rng'][1], sp))
-        fc = P['fc']
-        if fc['k'] != cl:
-            raise RuntimeError("classifier width does not match the final block")
-        self.logits = logits_view if logits_view is not None else alloc(N * fc['nout'], torch.float32).view(N, fc['nout'])
-        a = _lib.ConvArgs()
-        a.in_, a.wgt, a.bias = qf.data_ptr(), fc['w'].data_ptr(), fc['bias'].data_ptr()
-        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad = N, 1, 1, fc['k'], fc['nout_p'], 1, 1, 1, 0
-        a.in_bits = a.w_bits = 8
-        a.epilogue = _lib.EPI_DEQUANT
-        a.out_f32, a.fscale, a.ldo, a.n_valid = self.logits.data_ptr(), fc['fscale'].data_ptr(), fc['nout'], fc['nout']
-        if self.keep_acc:
-            self._tap(ops, keep, "output", a, N, 1, 1, fc['nout'], fc['nout_p'])
-        if _lib.load().hawq_fc_dequant_ok(N, fc['k'], fc['nout_p']) and not os.environ.get("HAWQ_NO_FC2"):
-            # round 5: the classifier's own kernel (fc_dequant.hip), the same bytes as the DEQUANT epilogue; nothing to tune
-            ops.append(partial(_lib.call, "hawq_fc_dequant", qf.data_ptr(), fc['w'].data_ptr(), fc['bias'].data_ptr(), fc['fscale'].data_ptr(),
-                               self.logits.data_ptr(), N, fc['k'], fc['nout_p'], fc['nout'], fc['nout'], sp))
-        else:
-            self._convs.append(("output", a))
-            ops.append(partial(_lib.call, "hawq_conv2d", C.byref(a), sp))
-        keep += [qf, pooled, a]
-        self._ops, self._keep, self._batch = ops, keep, (N, H, W)
 
     def _autotune(self, reps: int = 3):
         """Time every hawq_conv2d launch of the plan with each tile configuration the library accepts for it (HIP events on the
         engine stream, the real buffers - every tile gives the same integers) and keep the fastest; two rounds, per-tile minimum.
         HAWQ_MBV2_TILES replays a dotted list (as `tile_choice` prints it), HAWQ_MBV2_TILES=0 keeps the library's heuristic."""
         self._tuned = True
-        fixed = os.environ.get("HAWQ_MBV2_TILES")
+        convs, fixed = self._convs, os.environ.get("HAWQ_MBV2_TILES")
         if fixed is not None:
             ids = [int(v) for v in fixed.split(".")]
-            for (_, a), t in zip(self._convs, ids if len(ids) == len(self._convs) else [0] * len(self._convs)):
+            for (_, a), t in zip(convs, ids if len(ids) == len(convs) else [0] * len(convs)):
                 a.tile = t
             return
         lib, sp = _lib.load(), self.stream.cuda_stream
         n_tiles = lib.hawq_conv2d_num_tiles() - lib.hawq_conv2d_num_band_tiles()   # the 3x3 band tiles are not for 1x1 layers
         with EventTimer(sp) as timer:
-            for _, a in self._convs:
+            for _, a in convs:
                 def tile(t):
                     a.tile = t
                     return partial(_lib.call, "hawq_conv2d", C.byref(a), sp)   # (raises when this tile does not take the launch)
                 times = two_round_min(timer, range(1, n_tiles + 1), tile, reps)
                 a.tile = min(times, key=times.get) if times else 0
 
-    @property
-    def tile_choice(self):
-        return self.subs[0].tile_choice if self.subs else ".".join(str(a.tile) for _, a in self._convs)
+    # ------------------------------------------------------------------ read off the records
+    # (stage, argument block) of the hawq_conv2d launches the tuner may give a tile, in issue order
+    _convs = property(lambda self: [(r.stage, r.args[0]) for r in self._launches if r.kind == "conv"])
+    tile_choice = property(lambda self: self.subs[0].tile_choice if self.subs else ".".join(str(a.tile) for _, a in self._convs))
+    # the init block's argument block where it runs as one hawq_stem3x3s2 launch, else None
+    _stem_args = property(lambda self: self._launches[0].args[-1] if self._launches and self._launches[0].kind == "stem" else None)
 
-    @property
-    def total_plan_bytes(self):
-        return sum(sub.plan_bytes for sub in self.subs) if self.subs else self.plan_bytes
+    def _total(self, key):
+        """`key` of ``plan_totals`` for this chain or, of a split batch, for its first sub-chain (every chain takes the same decisions)"""
+        return plan_totals((self.subs[0] if self.subs else self)._launches)[key]
 
-    @property
-    def fast_requant_launches(self):
-        return self.subs[0].n_fast if self.subs else self.n_fast
+    plan_bytes = property(lambda self: plan_totals(self._launches)["plan_bytes"])
+    total_plan_bytes = property(lambda self: sum(sub.plan_bytes for sub in self.subs) if self.subs else self.plan_bytes)
+    n_launches = property(lambda self: sum(len(sub._ops) for sub in self.subs) if self.subs else len(self._ops))
+    fast_requant_launches = property(lambda self: self._total("n_fast"))
+    n_fused_units = property(lambda self: self._total("n_fused_units"))
+    n_fast_closing = property(lambda self: self._total("n_fast_closing"))
 
-    # ------------------------------------------------------------------ execution
+    # ------------------------------------------------------------------ the writer, execution
+    def _write(self, u8=False):
+        """The callables of this chain, from its records - the only place that makes one.  `u8`: the chain of ``forward_uint8``, the fp32
+        chain behind the uint8 form of its input launch (the one-launch stem, or the im2col input quantiser, as a table look-up on ``x_u8``)."""
+        def op(name, *args):
+            return partial(_lib.call, name, *(C.byref(v) if isinstance(v, C.Structure) else v for v in args), self.stream.cuda_stream)
+
+        if not u8:
+            return [op(r.name, *r.args) for r in self._launches]
+        first, (N, H, W) = self._launches[0], self._batch
+        if first.kind == "stem":
+            head = op("hawq_stem3x3s2", None, self.x_u8.data_ptr(), self.lut_dev.data_ptr(), H, W, 0.0, 0, 0, first.args[-1])
+        elif first.name == "hawq_quantize_im2col3x3s2":
+            head = op("hawq_quantize_im2col3x3s2_u8", self.x_u8.data_ptr(), self.lut_dev.data_ptr(), first.args[1], N, 3, H, W)
+        else:
+            raise NotImplementedError("uint8 input needs the im2col input quantiser (3x3 / stride 2 init conv on 3 channels)")
+        return [head] + self._ops[1:]
+
     def _launch_chain(self, u8):
         if not self._tuned and not self.keep_acc:
             for op in self._ops:   # every buffer holds valid data before launches are timed on it
                 op()
             self._autotune()
-        for i, op in enumerate(self._ops):
-            if u8 and i == self._u8_index:
-                self._u8_op()
-            else:
-                op()
+        for op in (self._ops_u8 if u8 else self._ops):
+            op()
 
     # ------------------------------------------------------------------ uint8 image input (quant_train.py:428-440)
     def _ensure_u8(self, N, H, W, x_view=None, lut=None):
-        if getattr(self, "x_u8", None) is not None:
+        if self.x_u8 is not None:
             return
         self.lut_dev = lut if lut is not None else torch.zeros(3 * 256, dtype=torch.int8, device=self.dev)
         self._lut_key = None   # a fresh table buffer: the next forward_uint8 uploads its look-up table
         self.x_u8 = x_view if x_view is not None else torch.empty(N, H, W, 3, dtype=torch.uint8, device=self.dev)
-        if self.subs:
-            b0 = 0
-            for sub in self.subs:
-                n = sub._batch[0]
-                sub._ensure_u8(n, H, W, self.x_u8[b0:b0 + n], self.lut_dev)
-                b0 += n
-            return
-        if self._u8_index is None:
-            raise NotImplementedError("uint8 input needs the im2col input quantiser (3x3 / stride 2 init conv on 3 channels)")
-        if self._stem_args is not None:
-            self._u8_op = partial(_lib.call, "hawq_stem3x3s2", None, self.x_u8.data_ptr(), self.lut_dev.data_ptr(), H, W, 0.0, 0, 0,
-                                  C.byref(self._stem_args), self.stream.cuda_stream)
-            return
-        self._u8_op = partial(_lib.call, "hawq_quantize_im2col3x3s2_u8", self.x_u8.data_ptr(), self.lut_dev.data_ptr(), self._xq.data_ptr(),
-                              N, 3, H, W, self.stream.cuda_stream)
+        b0 = 0
+        for sub in self.subs:
+            sub._ensure_u8(sub._batch[0], H, W, self.x_u8[b0:b0 + sub._batch[0]], self.lut_dev)
+            b0 += sub._batch[0]
+        if not self.subs:
+            self._ops_u8 = self._write(u8=True)
 
     def forward_uint8(self, x_u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
         """uint8 NHWC images [N,H,W,3] (decoder output, after resize / crop) -> fp32 logits; bit for bit what ``self(normalised
@@ -718,10 +722,6 @@ class MobileNetV2Engine(GraphRunner):
 
     def _upload_lut(self, mean, std):   # (this engine's kernels read the table flat)
         self.lut_dev.copy_(input_quant_lut(self.P['inv_s_in'], mean, std).reshape(-1).to(self.dev), non_blocking=False)
-
-    @property
-    def n_launches(self):
-        return sum(len(sub._ops) for sub in self.subs) if self.subs else len(self._ops)
 
     def tap(self, name):
         """int32 / int8 NHWC tensor of a tapped stage as an NCHW int64 numpy array without the padding channels."""

@@ -1,6 +1,6 @@
 """MobileNetV2 (w1, W8A8) fused integer plan, launch by launch: microseconds of every launch of ONE chain over the whole batch (HIP events
-around eager launches, 20 repetitions) beside the bytes it moves as stored (channels padded to 64) and at the network's true widths.
-usage (GPU box): python tools/mbv2_perop.py [batch]"""
+around eager launches, 20 repetitions) with its stage name and geometry, read from the engine's launch records (``eng._launches``).
+usage (GPU box): python tools/mbv2_perop.py [batch] [--preshift]"""
 import sys
 import torch
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
@@ -17,8 +17,7 @@ eng(x)
 torch.cuda.synchronize()
 rows, total = [], 0.0
 with torch.cuda.stream(eng.stream):
-    for i, op in enumerate(eng._ops):
-        name = op.args[0] if hasattr(op, "args") else "op"
+    for i, (r, op) in enumerate(zip(eng._launches, eng._ops)):   # one record per launch, in issue order
         op()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(eng.stream)
@@ -28,18 +27,19 @@ with torch.cuda.stream(eng.stream):
         e1.synchronize()
         us = e0.elapsed_time(e1) / 20 * 1e3
         total += us
-        extra = ""
-        if name in ("hawq_conv2d",):
-            a = op.args[1]._obj
-            extra = f"M={a.N * a.H * a.W // (a.stride * a.stride)} Cin={a.Cin} Cout={a.Cout} k={a.KH} s={a.stride} epi={a.epilogue} tile={a.tile} fast={a.fast_tables} n_valid={a.n_valid}"
-        elif name == "hawq_linear_bottleneck":
-            b = op.args[1]._obj
+        if r.kind == "unit":
+            b = r.args[0]
             extra = (f"N={b.expand.N} {b.expand.H}x{b.expand.W} in_pitch={b.expand.in_pitch or 64} hidden={b.c_mid} stride={b.dw_stride} "
                      f"out_pitch={b.project.out_pitch or 64} identity={int(bool(b.project.res_in))} carrier={int(bool(b.project.res_out))}")
-        elif name == "hawq_depthwise3x3_requant":
-            _, _x, _w, _b, _m, _e, n, h, w, c, cv, s = op.args[:12]
+        elif r.kind in ("conv", "stem"):   # the hawq_conv_args block: the launch's only argument / the stem's last
+            a = r.args[-1]
+            extra = f"M={a.N * a.H * a.W // (a.stride * a.stride)} Cin={a.Cin} Cout={a.Cout} k={a.KH} s={a.stride} epi={a.epilogue} tile={a.tile} fast={a.fast_tables} n_valid={a.n_valid}"
+        elif r.geom is not None:
+            n, h, w, c, cv, s = r.geom
             extra = f"N={n} {h}x{w} C={c} (valid {cv}) stride={s}"
-        rows.append((i, name, us, extra))
+        else:
+            extra = ""
+        rows.append((i, r.name, us, f"{r.stage}: {extra}"))
 if "--preshift" in sys.argv:   # how many per-channel requant tables of each unit carry a pre-shift k > 0 (conv1 / depthwise / conv3)
     for ui, u in enumerate(eng.P['units']):
         def nk(t):
