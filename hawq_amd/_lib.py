@@ -76,6 +76,19 @@ class IncepGroupArgs(C.Structure):
     _fields_ = [("n", i32), ("reserved", i32), ("conv", IncepConvArgs * INCEP_GROUP_MAX)]
 
 
+INCEP_FAN_MAX = 4
+
+
+class IncepFanOut(C.Structure):
+    """struct hawq_incep_fan_out (include/hawq_mi355.h): one int8 copy of a member's output at a consumer's scale."""
+    _fields_ = [("out", vp)] + [(n, i32) for n in ("m", "ek", "lo", "hi", "ldo", "c_off")]
+
+
+class IncepFan(C.Structure):
+    """struct hawq_incep_fan (include/hawq_mi355.h): the fan outputs of one member of hawq_incep_conv_group_fan."""
+    _fields_ = [("n", i32), ("reserved", i32), ("to", IncepFanOut * INCEP_FAN_MAX)]
+
+
 # op ids of hawq_incep_pool_v, by the entry point each one stands for
 INCEP_POOL_OPS = {"hawq_incep_requant": 0, "hawq_incep_maxpool3s2": 1, "hawq_incep_avgpool_branch": 2, "hawq_incep_global_avgpool": 3}
 
@@ -155,6 +168,8 @@ SIGNATURES = {
     "hawq_incep_conv_tiled": [C.POINTER(IncepConvArgs), i32, vp],
     "hawq_incep_conv_group_ok": [C.POINTER(IncepGroupArgs), i32],
     "hawq_incep_conv_group": [C.POINTER(IncepGroupArgs), i32, vp],
+    "hawq_incep_conv_group_fan_ok": [C.POINTER(IncepGroupArgs), C.POINTER(IncepFan), i32],
+    "hawq_incep_conv_group_fan": [C.POINTER(IncepGroupArgs), C.POINTER(IncepFan), i32, vp],
     "hawq_incep_stem_u8": [vp, vp, C.POINTER(IncepConvArgs), vp],
     "hawq_incep_stem_u8_ok": [vp, vp, C.POINTER(IncepConvArgs)],
     "hawq_incep_stem_f32": [vp, f32, i32, i32, C.POINTER(IncepConvArgs), vp],

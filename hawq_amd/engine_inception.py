@@ -22,7 +22,8 @@ Every requant is the exact dyadic form of fixedpoint_fn (``requant_table(..., li
 
 Mechanism.  ``_build`` emits one ``Launch`` record per launch of that default plan, in its order (``_launches``: 147 records, the
 input QuantAct's two launches and conv1 among the stem's), and nothing rewrites the list afterwards.  What ``tune``, ``plan=`` or
-the defaults decide is one value (``_choose``): the tile id per conv launch or None, and the grouped launches or None.  One writer
+the defaults decide is one value (``_choose``): the tile id per conv launch or None, the grouped launches or None, and the fan-out
+boundaries or None.  One writer
 (``_write``) turns records + choice + the engine's options into the callables of a chain (``_ops``, ``_ops_u8``): it picks the entry
 point of every record, the stem that heads the chain and, with groups, the order (``grouped_order``, a pure function).
 
@@ -65,6 +66,29 @@ over between engines with and without the option.  Which levels are grouped, and
 * ``plan=``: the ``"groups"`` entries of the plan (``check_groups``), none if it has no such field; no timing launch.
 ``export_plan()`` of a grouped engine writes ``"groups"``; an engine without ``grouped`` ignores the field.  ``group_launches`` lists
 (member conv indices, tile) per grouped launch in launch order.  Not the default.
+
+Fan-out epilogues.  Every conv branch of a unit starts with a ``hawq_incep_requant`` of the previous unit's whole 16-bit concat
+buffer (31 launches per forward).  ``InceptionEngine(model, fan_out=True)`` lets the convs that wrote that buffer store the int8
+copies themselves: ``hawq_incep_conv_group_fan`` (hawq_amd/csrc/incep_fan.hip), the grouped launch whose epilogue requantises the
+value it has just stored once more per consumer and stores it into the consumer's buffer.  The records stay the default plan's;
+``fan_boundaries`` (a pure function over tags and argument blocks) finds, per unit, its entry requants, which slices of their input a
+conv of the previous unit produced (REQUANT2 into that buffer) and, per producer, the fan targets - each entry requant's output,
+pitch and ``post`` table at the producer's channels.  A boundary with at least one conv-produced slice is a candidate (units 1 - 10;
+unit 0 reads the stem's max pool).  For a chosen boundary the writer issues its producer launches - single convs as groups of one,
+grouped launches with their members' fans - through the fan entry point and drops the entry requants, or, where a pool or an
+inner-concat requant produced part of the input (units 4, 9, 10), issues them on those channel ranges only (``in_off`` / ``c_off`` /
+``C`` of a fresh block; adjacent ranges merged): 128 launches instead of 147, 81 instead of 100 with ``grouped``.  Which boundaries:
+* neither ``tune`` nor a ``"fan_out"`` field in ``plan``: every candidate whose producer launches the library takes, each on tile 3 or
+  else the first of 2, 1, 4 that ``hawq_incep_conv_group_fan_ok`` accepts (a tile plan without the field fixes the other convs only);
+* ``tune=True``: per boundary two blocks of launches are timed on the real buffers - its producers as the rest of the choice issues
+  them followed by its entry requants, and the fan-out producers (each on the fastest tile it accepts) followed by the residual
+  requants - and the boundary is kept only if the second block is faster (``fan_candidates`` has both times);
+* ``plan=`` with the field: exactly its entries (``check_fan_out``: StalePlan for a unit that is no candidate, launches other than
+  the boundary's producer launches, a refused tile); an empty list means none.  No timing launch.
+``export_plan()`` of a fan-out engine writes ``"fan_out": [{"unit", "tiles": {producer launch: tile}, "us"}]``; an engine without
+``fan_out`` ignores the field.  ``fan_launches`` lists (unit, member conv indices, tile) per fan-out launch, ``residual_requants``
+(unit, record, in_off, C) per shortened entry requant.  Pool kernels, inner-concat requants, stem and head are untouched.  Not the
+default: at batch 1 - 16 the longer epilogue costs more than the launches it saves.
 """
 from __future__ import annotations
 
@@ -127,16 +151,20 @@ def launch_digest(keys):
     return hashlib.sha256(json.dumps([list(map(int, k)) for k in keys], separators=(",", ":")).encode()).hexdigest()
 
 
-def make_plan(batch, keys, num_tiles, tiles, us, groups=None):
+def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
     and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
-    ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field"""
+    ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field, and with `fan_out`
+    (a fan-out engine's ``{"unit": k, "tiles": {launch: id}, "us": {...}}`` entries) the ``"fan_out"`` field"""
     plan = {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
             "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
             "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
     if groups is not None:
         plan["groups"] = [{"convs": [int(c) for c in g["convs"]], "tile": int(g["tile"]),
                            "us": {str(k): round(float(v), 3) for k, v in g.get("us", {}).items()}} for g in groups]
+    if fan_out is not None:
+        plan["fan_out"] = [{"unit": int(f["unit"]), "tiles": {str(k): int(t) for k, t in f["tiles"].items()},
+                            "us": {str(k): round(float(v), 3) for k, v in f.get("us", {}).items()}} for f in fan_out]
     return plan
 
 
@@ -241,6 +269,87 @@ def grouped_order(launches, groups):
     return order
 
 
+def fan_boundaries(launches):
+    """The boundary in front of every unit of `launches`, in unit order, read from the records' tags and argument blocks alone:
+    * ``"requants"``: the unit's level-0 ``hawq_incep_requant`` records (the ``q_input_act`` of its conv branches), as indices;
+    * ``"slices"``: ``(c_off, C, producer)`` for every slice of the buffer they read that an earlier record writes, by channel: the
+      index of the conv record that produced it (REQUANT2, 16 bits, into that buffer), or None for a pool / requant record;
+    * ``"producers"``: per such conv record index its fan targets, one per entry requant and in their order:
+      ``(out, ldo, (m, ek, lo, hi), c_off, Cout)`` - that record's output buffer, pitch and ``post`` table, and where the producer's
+      channels go in it;
+    * ``"residual"``: the channel ranges ``(in_off, C)`` of the input that no conv produced, adjacent ones merged - what is left for
+      the entry requants to do;
+    * ``"candidate"``: at least one slice is conv-produced (and the entry requants are plain: one 16-bit source and range, ``post``
+      only, int8 out)."""
+    out = []
+    for k in sorted({r.place for r in launches if isinstance(r.place, int)}):
+        entry = [i for i, r in enumerate(launches)
+                 if r.place == k and r.level == 0 and r.kind == "pool" and r.name == "hawq_incep_requant"]
+        b = {"unit": k, "requants": entry, "slices": [], "producers": {}, "residual": [], "candidate": False}
+        out.append(b)
+        if not entry:
+            continue
+        blocks = [launches[i].args[0] for i in entry]
+        f = blocks[0]
+        src, pitch, lo, hi = f.in_, f.in_pitch, f.in_off, f.in_off + f.C
+        plain = all((a.in_, a.in_pitch, a.in_off, a.C, a.in_bits, a.out_bits, a.pre, a.post) == (src, pitch, lo, f.C, 16, 8, 0, 1)
+                    for a in blocks)
+        for i, r in enumerate(launches[:entry[0]]):
+            if r.kind not in ("conv", "pool"):
+                continue
+            a = r.args[0]
+            if (a.out, a.ldo, a.out_bits) != (src, pitch, 16) or (r.kind == "conv" and a.epilogue == _lib.INCEP_RAW):
+                continue
+            if r.kind == "conv":
+                b["slices"].append((a.c_off, a.Cout, i if a.epilogue == _lib.INCEP_REQUANT2 else None))
+            else:
+                b["slices"].append((a.c_off, a.C, None))
+        b["slices"].sort(key=lambda t: t[0])
+        at = lo   # the residual: what no conv covers of lo .. hi
+        for off, c, prod in [t for t in b["slices"] if t[2] is not None and lo <= t[0] and t[0] + t[1] <= hi] + [(hi, 0, -1)]:
+            if off > at:
+                b["residual"].append((at, off - at))
+            at = max(at, off + c)
+            if prod is not None and prod >= 0:
+                b["producers"][prod] = [(a.out, a.ldo, (a.m2, a.ek2, a.lo2, a.hi2), a.c_off + off - lo, c) for a in blocks]
+        b["candidate"] = plain and bool(b["producers"])
+        if not b["candidate"]:
+            b["producers"], b["residual"] = {}, [(lo, hi - lo)]
+    return out
+
+
+def fan_key(convs):
+    """how a plan's ``"fan_out"`` entry names a producer launch: its member conv indices, in launch order"""
+    return ",".join(str(int(c)) for c in convs)
+
+
+def check_fan_out(entries, candidates, ok):
+    """The boundaries ``[(unit, {launch key: tile}), ...]`` of a plan's ``"fan_out"`` field, or StalePlan: an entry that is not
+    ``{"unit": k, "tiles": {key: id}}``, a unit that is not in `candidates` (unit -> the ``fan_key`` of every producer launch of its
+    boundary) or is named twice, keys other than exactly those launches, or a tile that ``ok(unit, key, tile)`` refuses."""
+    out, seen = [], set()
+    try:
+        pairs = [(e["unit"], dict(e["tiles"])) for e in entries]
+    except (KeyError, TypeError, ValueError) as exc:
+        raise StalePlan(f"not a list of fan-out boundaries: {exc!r}") from exc
+    for unit, tiles in pairs:
+        if not isinstance(unit, int) or isinstance(unit, bool) or unit not in candidates:
+            raise StalePlan(f"fan-out boundary {unit!r}: not a candidate unit")
+        if unit in seen:
+            raise StalePlan(f"fan-out boundary {unit}: named twice")
+        seen.add(unit)
+        if sorted(tiles) != sorted(candidates[unit]):
+            raise StalePlan(f"fan-out boundary {unit}: launches {sorted(tiles)} are not its producers {sorted(candidates[unit])}")
+        for key, tile in tiles.items():
+            if not isinstance(tile, int) or isinstance(tile, bool) or not ok(unit, key, tile):
+                raise StalePlan(f"fan-out boundary {unit}, launch {key}: tile {tile!r} is refused")
+        out.append((unit, {k: tiles[k] for k in candidates[unit]}))
+    return out
+
+
+_FAN_TILES = (3, 2, 1, 4)   # an untuned fan-out launch: tile 3, else the first of these the library takes
+
+
 class _T:
     """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale."""
 
@@ -250,11 +359,12 @@ class _T:
 
 class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
-                 fused_stem: bool = False, grouped: bool = False):
+                 fused_stem: bool = False, grouped: bool = False, fan_out: bool = False):
         self.model, self.use_graph = model, use_graph
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
-        self.grouped = bool(grouped)
+        self.grouped, self.fan_out = bool(grouped), bool(fan_out)
         self.group_launches, self.group_candidates = [], []
+        self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         self.n_timing_launches = 0           # conv launches issued to time tiles (0 for a default or a replayed plan)
         self.conv_tiles, self.conv_us = None, None
         self.dev = next(model.parameters()).device
@@ -423,10 +533,11 @@ class InceptionEngine(GraphRunner):
             self.stream = torch.cuda.Stream(device=self.dev)
         self.N, dev, q = N, self.dev, self.model
         self._launches, self._convs, self._place = [], [], "stem"   # the records, the conv records among them, where `_emit` is
-        self._choice = (None, None)          # the default plan's: no tiles, no groups, the default order
+        self._choice = (None, None, None)    # the default plan's: no tiles, no groups, no fan-out, the default order
         self._ops, self._keep, self.unit_out = [], [], {}
         self.conv_tiles, self.conv_us = None, None
         self.group_launches, self.group_candidates = [], []
+        self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
@@ -543,12 +654,52 @@ class InceptionEngine(GraphRunner):
             return False
         return bool(_lib.load().hawq_incep_conv_group_ok(C.byref(self._group_args(convs)), tile))
 
+    def _fan_sets(self, b, groups):
+        """the launches that hold the producers of boundary `b` under `groups`, as tuples of member conv indices in launch order: a
+        grouped launch with a producer among its members, or the producer alone"""
+        sets = []
+        for i in sorted(b["producers"]):
+            c = self._launches[i].ref
+            s = next((tuple(convs) for convs, _ in groups or [] if c in convs), (c,))
+            if s not in sets:
+                sets.append(s)
+        return sets
+
+    def _fan_args(self, convs, b):
+        """(group block, fan array) of one fan-out launch: the members' blocks, and per member its targets in boundary `b` (none for
+        a member that is no producer); None if a producer has more targets than a fan holds"""
+        targets = {self._launches[i].ref: t for i, t in b["producers"].items()}
+        g, fans = self._group_args(convs), (_lib.IncepFan * len(convs))()
+        for k, c in enumerate(convs):
+            ts = targets.get(c, [])
+            if len(ts) > _lib.INCEP_FAN_MAX:
+                return None
+            fans[k].n = len(ts)
+            for j, (out, ldo, (m, ek, lo, hi), c_off, _) in enumerate(ts):
+                f = fans[k].to[j]
+                f.out, f.m, f.ek, f.lo, f.hi, f.ldo, f.c_off = out, m, ek, lo, hi, ldo, c_off
+        return g, fans
+
+    def _fan_ok(self, convs, b, tile):
+        if not 1 <= len(convs) <= _lib.INCEP_GROUP_MAX or not isinstance(tile, int) or isinstance(tile, bool):
+            return False
+        gf = self._fan_args(convs, b)
+        return gf is not None and bool(_lib.load().hawq_incep_conv_group_fan_ok(C.byref(gf[0]), gf[1], tile))
+
+    def _residual_args(self, r, off, c):
+        """a fresh block for entry requant `r` on the input channels off .. off + c - 1 only"""
+        a = _lib.IncepPoolArgs.from_buffer_copy(r.args[0])
+        a.c_off, a.in_off, a.C = a.c_off + off - a.in_off, off, c
+        return a
+
     # ------------------------------------------------------------------ the choice
     def _choose(self, batch):
         """What a plan decides, as one value: (tile id per conv launch, or None; grouped launches [(member conv indices, tile)], or
-        None on an engine without ``grouped``).  From ``self.plan``, else from timing (``tune``), else the defaults: no tiles, and
-        every level of two or more convs on tile 3 that the library takes.  Leaves ``conv_tiles`` and what was recorded or measured
-        (``conv_us``, ``group_candidates``) for the readers and ``export_plan``."""
+        None on an engine without ``grouped``; fan-out boundaries [(boundary, {producer launch: tile})], or None on an engine
+        without ``fan_out``).  From ``self.plan``, else from timing (``tune``), else the defaults: no tiles, every level of two or
+        more convs on tile 3 that the library takes, and every candidate boundary whose producer launches the library takes.  Leaves
+        ``conv_tiles`` and what was recorded or measured (``conv_us``, ``group_candidates``, ``fan_candidates``) for the readers
+        and ``export_plan``."""
         T, tiles, groups = _lib.load().hawq_incep_conv_num_tiles(), None, None
         # members with the longest K loop first, so that the heavy workgroups start first (the order is free, and unmeasured)
         klen = lambda c: -(self._convs[c].args[0].KH * self._convs[c].args[0].KW * self._convs[c].args[0].Cin)   # noqa: E731
@@ -575,7 +726,78 @@ class InceptionEngine(GraphRunner):
         elif self.grouped:
             groups = [(c, 3) for c in cands if self._group_ok(c, 3)]
         self.conv_tiles = None if tiles is None else [int(t) for t in tiles]
-        return self.conv_tiles, groups
+        return self.conv_tiles, groups, self._choose_fans(self.conv_tiles, groups) if self.fan_out else None
+
+    def _choose_fans(self, tiles, groups):
+        """the third component: from the plan's ``"fan_out"`` field if it has one, else timed against the plain launches (``tune``),
+        else every candidate boundary on the default tiles (a tile plan without the field fixes the other convs' tiles only)"""
+        cands = {b["unit"]: b for b in fan_boundaries(self._launches) if b["candidate"]}
+        sets = {k: self._fan_sets(b, groups) for k, b in cands.items()}
+        if self.plan is not None and "fan_out" in self.plan:
+            by_key = {(k, fan_key(s)): s for k in cands for s in sets[k]}
+            got = check_fan_out(self.plan["fan_out"], {k: [fan_key(s) for s in sets[k]] for k in cands},
+                                lambda k, key, t: self._fan_ok(by_key[k, key], cands[k], t))
+            us = {e["unit"]: dict(e.get("us", {})) for e in self.plan["fan_out"]}
+            self.fan_candidates = [{"unit": k, "tiles": dict(t), "us": us[k], "kept": True} for k, t in got]
+            return [(cands[k], {by_key[k, key]: t for key, t in tl.items()}) for k, tl in got]
+        accepted = {k: {s: [t for t in _FAN_TILES if self._fan_ok(s, b, t)] for s in sets[k]} for k, b in cands.items()}
+        able = [k for k in cands if all(accepted[k][s] for s in sets[k])]   # a boundary with a refused producer launch is not chosen
+        if self.tune and self.plan is None:
+            for k, rec in zip(able, self._time_fans([cands[k] for k in able], [accepted[k] for k in able], tiles, groups)):
+                self.fan_candidates.append({"unit": k, **rec})
+        else:
+            self.fan_candidates = [{"unit": k, "tiles": {fan_key(s): accepted[k][s][0] for s in sets[k]}, "us": {}, "kept": True}
+                                   for k in able]
+        return [(cands[f["unit"]], {s: f["tiles"][fan_key(s)] for s in sets[f["unit"]]}) for f in self.fan_candidates if f["kept"]]
+
+    def _time_fans(self, bounds, accepted, tiles, groups):
+        """Per boundary of `bounds`, on the real buffers as ``_time`` left them (every launch here is a pure function of buffers it
+        does not write): ``"plain"``, the microseconds of its producer launches as (tiles, groups) issue them followed by its entry
+        requants, one block; every producer launch with its fan on every accepted tile (``"<launch>@<tile>"``); and ``"fan"``, one
+        block of the fan-out launches on their fastest tiles followed by the residual requants.  Kept if fan < plain."""
+        sp, lib, out = self.stream.cuda_stream, _lib.load(), []
+
+        def pool(a, ref, name):
+            fast = self.fast_pools and lib.hawq_incep_pool_v_ok(C.byref(a), ref)
+            return partial(_lib.call, "hawq_incep_pool_v", C.byref(a), ref, sp) if fast else partial(_lib.call, name, C.byref(a), sp)
+
+        def block(ops):
+            def run():
+                for op in ops:
+                    op()
+            self.n_timing_launches += (_TUNE_WARMUP + _TUNE_REPS) * len(ops)
+            return ev.median_us(run, _TUNE_REPS, _TUNE_WARMUP)
+
+        with EventTimer(sp, _TUNE_REPS + 1) as ev:
+            torch.cuda.synchronize(self.dev)
+            with torch.cuda.stream(self.stream):
+                for b, acc in zip(bounds, accepted):
+                    gtile = {tuple(c): t for c, t in groups or []}
+                    plain, fan, us, chosen, keep = [], [], {}, {}, []
+                    for s in acc:
+                        if s in gtile:
+                            g = self._group_args(s)
+                            keep.append(g)
+                            plain.append(partial(_lib.call, "hawq_incep_conv_group", C.byref(g), int(gtile[s]), sp))
+                        else:
+                            plain.append(partial(_lib.call, "hawq_incep_conv_tiled", C.byref(self._convs[s[0]].args[0]), int(tiles[s[0]]), sp))
+                        g, f = self._fan_args(s, b)
+                        keep += [g, f]
+                        for t in acc[s]:
+                            us[f"{fan_key(s)}@{t}"] = block([partial(_lib.call, "hawq_incep_conv_group_fan", C.byref(g), f, t, sp)])
+                        chosen[s] = min(acc[s], key=lambda t: (us[f"{fan_key(s)}@{t}"], t))
+                        fan.append(partial(_lib.call, "hawq_incep_conv_group_fan", C.byref(g), f, chosen[s], sp))
+                    for i in b["requants"]:
+                        r = self._launches[i]
+                        plain.append(pool(r.args[0], r.ref, r.name))
+                        for off, c in b["residual"]:
+                            a = self._residual_args(r, off, c)
+                            keep.append(a)
+                            fan.append(pool(a, r.ref, r.name))
+                    us["plain"], us["fan"] = block(plain), block(fan)
+                    out.append({"tiles": {fan_key(s): t for s, t in chosen.items()}, "us": us, "kept": us["fan"] < us["plain"]})
+        torch.cuda.synchronize(self.dev)
+        return out
 
     def _time(self, T, cands):
         """Microseconds (HIP events, ``EventTimer.median_us``) of every accepted tile id per conv launch, and of every accepted tile
@@ -606,8 +828,9 @@ class InceptionEngine(GraphRunner):
         if self.conv_tiles is None:
             raise RuntimeError("export_plan: no tuned plan (build the engine with tune=True or plan=... and run a forward first)")
         groups = [g for g in self.group_candidates if g["kept"]] if self.grouped else None
+        fans = [f for f in self.fan_candidates if f["kept"]] if self.fan_out else None
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
-                         groups)
+                         groups, fans)
 
     # ------------------------------------------------------------------ the writer
     def _write(self, u8=False):
@@ -617,8 +840,10 @@ class InceptionEngine(GraphRunner):
         as one ``hawq_incep_stem_f32`` (``fused_stem``) or, for the uint8 chain, as one ``hawq_incep_stem_u8`` in front of the fp32
         chain's own callables.  The records' order, or with groups ``grouped_order``.  The fp32 chain leaves ``_at`` (record -> index
         of the launch that covers it) and ``group_launches``."""
-        tiles, groups = self._choice
+        tiles, groups, fans = self._choice
         lib, sp, launches = _lib.load(), self.stream.cuda_stream, self._launches
+        fan_of = {s: (b, t) for b, by_set in fans or [] for s, t in by_set.items()}           # producer launch -> its boundary, tile
+        entry = {i: b for b, _ in fans or [] for i in b["requants"]}                          # entry requant record -> its boundary
 
         def op(name, *args):
             return partial(_lib.call, name, *args, sp)
@@ -639,21 +864,41 @@ class InceptionEngine(GraphRunner):
             ops = [op("hawq_incep_stem_f32", self.x_in.data_ptr(), *self._input_quant(), C.byref(self._stem_a))]
         else:
             ops = [single(r) for r in launches[:head]]
-        n_stem, issued = len(ops), []
+        n_stem, issued, fanned, residual = len(ops), [], [], []
         at = {r: min(i, n_stem - 1) for i, r in enumerate(launches[:head])}
         order = [(False, i) for i in range(len(launches))] if groups is None else grouped_order(launches, groups)
         for is_group, i in order[head:]:   # the stem stays in place in either order
-            if is_group:
-                convs, tile = groups[i]
+            r = None if is_group else launches[i]
+            convs, tile = groups[i] if is_group else ([r.ref], None) if r.kind == "conv" else (None, None)
+            if convs is not None and tuple(convs) in fan_of:   # a producer launch of a chosen boundary, alone or grouped
+                b, tile = fan_of[tuple(convs)]
+                g, f = self._fan_args(convs, b)
+                self._keep += [g, f]
+                at.update((self._convs[c], len(ops)) for c in convs)
+                ops.append(op("hawq_incep_conv_group_fan", C.byref(g), f, int(tile)))
+                fanned.append((b["unit"], list(convs), int(tile)))
+                if is_group:
+                    issued.append((list(convs), int(tile)))
+            elif is_group:
                 g = self._group_args(convs)
                 self._keep.append(g)
                 at.update((self._convs[c], len(ops)) for c in convs)
                 ops.append(op("hawq_incep_conv_group", C.byref(g), int(tile)))
                 issued.append((list(convs), int(tile)))
+            elif i in entry:   # its producers wrote the conv-produced channels: the rest, or nothing
+                b = entry[i]
+                at[r] = len(ops) if b["residual"] else at[launches[min(b["producers"])]]
+                for off, c in b["residual"]:
+                    a = self._residual_args(r, off, c)
+                    self._keep.append(a)
+                    fast = self.fast_pools and lib.hawq_incep_pool_v_ok(C.byref(a), r.ref)
+                    ops.append(op("hawq_incep_pool_v", C.byref(a), r.ref) if fast else op(r.name, C.byref(a)))
+                    residual.append((b["unit"], i, off, c))
             else:
-                at[launches[i]] = len(ops)
-                ops.append(single(launches[i]))
+                at[r] = len(ops)
+                ops.append(single(r))
         self._at, self._tail, self.group_launches = at, ops[n_stem:], issued
+        self.fan_launches, self.residual_requants = fanned, residual
         return ops
 
     def _launch_chain(self, u8):

@@ -530,6 +530,34 @@ typedef struct hawq_incep_group_args {
 } hawq_incep_group_args;
 int hawq_incep_conv_group_ok(const hawq_incep_group_args *g, int tile);
 int hawq_incep_conv_group(const hawq_incep_group_args *g, int tile, void *stream);
+/* The grouped launch with a fan-out epilogue (incep_fan.hip).  In the InceptionV3 plan every conv branch of a unit starts by
+ * requantising the previous unit's whole 16-bit concat buffer to int8 at the branch's scale (hawq_incep_requant, one launch per
+ * branch).  The convs that wrote that buffer held those values in registers; here they store the int8 copies themselves.
+ *   hawq_incep_conv_group_fan:    member i writes, byte for byte, what hawq_incep_conv_tiled(&g->conv[i], tile, stream) writes.  In
+ *       addition, for j < fan[i].n, output pixel p and channel co of member i,
+ *           to[j].out[p * ldo + c_off + co] = (int8) clamp(dyadic_rne(y; m, ek), lo, hi)
+ *       where y is the element the member stores as its primary output, after its last clamp - what hawq_incep_requant with
+ *       post = (m, ek, lo, hi) makes of that element.  Other channels of a fan row are never touched.  A single conv with a fan is a
+ *       group of one.  Tile ids 1 .. hawq_incep_conv_num_tiles(); the fan descriptors travel as kernel arguments (2312 bytes in all).
+ *   hawq_incep_conv_group_fan_ok: 1 if the launch takes this description.  Host arithmetic only: nothing is dereferenced or launched,
+ *       no device is needed.  It needs hawq_incep_conv_group_ok(g, tile); every fan[i].n in 0 .. HAWQ_INCEP_FAN_MAX; no fan on a RAW
+ *       member; -128 <= lo <= hi <= 127; m >= 0 and ek = e | k << 8 with 1 <= e <= 62, k <= 15 (common.h dyadic_rne); out 16-byte
+ *       aligned, ldo and c_off multiples of 16, ldo >= c_off + Cout of the member; and no fan output that meets a member's input, a
+ *       member's primary output or another fan output - channel intervals for slices of one buffer (same out and ldo, int8), byte
+ *       extents otherwise.
+ * fan points to g->n entries.  A refused call returns non-zero (the reason in hawq_last_error()), launches nothing, writes nothing.
+ * Not covered: tile 0, 16-bit fan outputs, fans of the pool kernels. */
+#define HAWQ_INCEP_FAN_MAX 4
+typedef struct hawq_incep_fan_out {
+    void *out;   /* int8 rows of ldo elements */
+    int32_t m, ek, lo, hi, ldo, c_off;
+} hawq_incep_fan_out;
+typedef struct hawq_incep_fan {
+    int32_t n, reserved;
+    hawq_incep_fan_out to[HAWQ_INCEP_FAN_MAX];
+} hawq_incep_fan;
+int hawq_incep_conv_group_fan_ok(const hawq_incep_group_args *g, const hawq_incep_fan *fan /* [g->n] */, int tile);
+int hawq_incep_conv_group_fan(const hawq_incep_group_args *g, const hawq_incep_fan *fan, int tile, void *stream);
 /* InceptionV3's input QuantAct + Conv2d_1a_3x3 from uint8 images in one launch (incep_stem.hip): Q_InceptInitBlock's q_input_activ and
  * q_conv1 (q_inceptionv3.py of the reference) on the tensor that ToTensor + Normalize (quant_train.py:432-440) make of the image, with
  * the QuantAct as a table look-up (quant_modules.py:271-274; lut int8 [3][256] from hawq_amd.quant_utils.input_quant_lut).

@@ -32,6 +32,13 @@ launches (``grouped=True``, tuned: the grouped engine times tiles and groups, th
 groups): alternating blocks as above, an assertion that the logits are bit-equal, the launch counts, and a table of the candidate
 groups - member conv launches, fastest tile, its microseconds, the sum of the members' best single microseconds, kept or not.
 
+``--fan-out`` (alone or with ``--grouped``) compares, on one recorded plan with ``fast_pools=True, fused_stem=True``, the plan without
+and with fan-out conv epilogues (``fan_out=True``, tuned: that engine times tiles, groups and boundaries, the other replays its plan
+and ignores the ``"fan_out"`` field, so every conv that is no fan-out producer runs on the same tile in both; a third engine replays
+the plan without the field and so takes every candidate boundary on the default tiles): alternating blocks as above, an assertion that
+the logits are bit-equal, the launch counts, and a table of the boundaries - producer launches + entry requants against fan-out
+producer launches + residual requants, in microseconds, kept or not.
+
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --input f32,u8 [--blocks 6] [--stem-launches 0]
     python tools/inception_bench.py --tune [--batches 128] [--blocks 6] [--save-plan plan.json]
@@ -39,6 +46,7 @@ groups - member conv launches, fastest tile, its microseconds, the sum of the me
     python tools/inception_bench.py --tune --pools --batches 128,1
     python tools/inception_bench.py --fused-stem [--tune --pools] --batches 128,1 --stem-launches 20
     python tools/inception_bench.py --grouped --batches 1,16,128 [--blocks 6]
+    python tools/inception_bench.py --fan-out [--grouped] --batches 1,16,128 [--blocks 6]
 """
 import argparse
 import json
@@ -354,6 +362,62 @@ def compare_grouped(model, args, b):
     return grouped
 
 
+def compare_fan_out(model, args, b):
+    """one recorded plan (fast pools, fused stem, grouped or not) without fan-out, with the boundaries the tuner kept and with every
+    candidate boundary, alternating blocks; returns the tuned fan-out engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    opts = dict(fast_pools=True, fused_stem=True, grouped=args.grouped)
+    with torch.no_grad():
+        fan = InceptionEngine(model, tune=True, fan_out=True, **opts)
+        y1 = fan(x)
+        plan = fan.export_plan()
+        plain = InceptionEngine(model, plan=plan, **opts)   # the same tiles and groups; the field is ignored
+        every = InceptionEngine(model, plan={k: v for k, v in plan.items() if k != "fan_out"}, fan_out=True, **opts)
+        engines = {"plain": plain, "fan_out": fan, "fan_out_all": every}
+        equal = bool(torch.equal(plain(x), y1)) and bool(torch.equal(every(x), y1))
+        assert equal, "the logits with fan-out epilogues differ from the plain plan's"
+        # (a grouped launch that carries a fan runs on the fan's tile, so only the members are compared)
+        assert plain.conv_tiles == fan.conv_tiles and not plain.fan_launches
+        assert [c for c, _ in plain.group_launches] == [c for c, _ in fan.group_launches]
+        print(f"# {wl}: consumer unit | producer launches (member conv launches @ tile) | producers + entry requants us | "
+              f"fan-out producers + residual requants us | kept")
+        for f in fan.fan_candidates:
+            print(f"# {f['unit']:2d} | " + " ".join(f"[{k}]@{t}" for k, t in f["tiles"].items()) +
+                  f" | {f['us']['plain']:.1f} | {f['us']['fan']:.1f} | {'kept' if f['kept'] else 'plain'}")
+        kept = [f for f in fan.fan_candidates if f["kept"]]
+        print(json.dumps({"workload": wl, "grouped": bool(args.grouped), "launches_plain": plain.n_launches,
+                          "launches_fan_out": fan.n_launches, "launches_fan_out_all": every.n_launches,
+                          "boundaries_kept": [f["unit"] for f in kept],
+                          "boundaries_rejected": [f["unit"] for f in fan.fan_candidates if not f["kept"]],
+                          "plain_us_sum": round(sum(f["us"]["plain"] for f in fan.fan_candidates), 1),
+                          "fan_us_sum": round(sum(f["us"]["fan"] for f in fan.fan_candidates), 1),
+                          "kept_plain_us_sum": round(sum(f["us"]["plain"] for f in kept), 1),
+                          "kept_fan_us_sum": round(sum(f["us"]["fan"] for f in kept), 1)}), flush=True)
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": "tuned", "fast_pools": True, "fused_stem": True,
+                              "grouped": bool(args.grouped), "epilogues": k, "ms_per_batch": round(mean, 4),
+                              "images_per_s": round(b * 1000.0 / mean, 1), "block_min_ms": round(min(v), 4),
+                              "block_max_ms": round(max(v), 4), "blocks": len(v), "steps": args.steps, "launches": e.n_launches,
+                              "logits_bit_equal": equal}), flush=True)
+        m0 = sum(ms["plain"]) / args.blocks
+        print(json.dumps({"workload": wl, "grouped": bool(args.grouped),
+                          "gain_ms_fan_out": round(m0 - sum(ms["fan_out"]) / args.blocks, 4),
+                          "gain_ms_fan_out_all": round(m0 - sum(ms["fan_out_all"]) / args.blocks, 4),
+                          "plain_block_spread_ms": round(max(ms["plain"]) - min(ms["plain"]), 4)}), flush=True)
+    return fan
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheme", default="uniform8")
@@ -372,18 +436,20 @@ def main():
     ap.add_argument("--fused-stem", action="store_true", help="compare the default fp32 plan with fused_stem=True on one plan")
     ap.add_argument("--grouped", action="store_true",
                     help="compare one tuned plan (fast pools, fused stem) without and with grouped conv launches")
-    ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped: write export_plan() of the last batch size to this file")
+    ap.add_argument("--fan-out", action="store_true",
+                    help="compare one recorded plan (fast pools, fused stem; grouped with --grouped) without and with fan-out conv epilogues")
+    ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
-    if args.save_plan and not (args.tune or args.plan or args.grouped):
-        ap.error("--save-plan needs --tune, --plan or --grouped: there is no conv tile plan to save otherwise")
+    if args.save_plan and not (args.tune or args.plan or args.grouped or args.fan_out):
+        ap.error("--save-plan needs --tune, --plan, --grouped or --fan-out: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
     for b in (int(v) for v in args.batches.split(",")):
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
-            compare = compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
+        if args.fan_out or args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
+            compare = compare_fan_out if args.fan_out else compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
             tuned = compare(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
