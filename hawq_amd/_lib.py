@@ -111,6 +111,24 @@ class ImageTile(C.Structure):
     _fields_ = [("image", i32), ("row0", i32), ("rows", i32)]
 
 
+class JpegBatchHdr(C.Structure):
+    """struct hawq_jpeg_batch_hdr (include/hawq_mi355.h): offset 0 of the blob of a hawq_jpeg_decode_batch call."""
+    _fields_ = [(n, i32) for n in ("n_images", "n_waves", "desc_off", "wave_off")]
+
+
+class JpegHuff(C.Structure):
+    """struct hawq_jpeg_huff (include/hawq_mi355.h): one canonical Huffman table."""
+    _fields_ = [("mincode", i32 * 17), ("maxcode", i32 * 17), ("valptr", i32 * 17), ("huffval", C.c_uint8 * 256), ("reserved", i32)]
+
+
+class JpegDesc(C.Structure):
+    """struct hawq_jpeg_desc (include/hawq_mi355.h): one image of a hawq_jpeg_decode_batch call."""
+    _fields_ = ([(n, i32) for n in ("width", "height", "ncomp", "hs", "vs", "mcus_x", "mcus_y", "restart", "n_intervals")]
+                + [(n, i32 * 3) for n in ("qt_off", "dc_off", "ac_off")]
+                + [(n, i32) for n in ("stream_off", "stream_len", "interval_off", "reserved")]
+                + [(n, i64) for n in ("coef_block0", "plane_off", "out_off")])
+
+
 # name -> (argtypes); every function returns int except hawq_last_error
 SIGNATURES = {
     "hawq_abi_version": [],
@@ -160,6 +178,8 @@ SIGNATURES = {
     "hawq_image_batch": [vp, i32, vp, i32, vp, vp, i32, i32, vp],
     "hawq_image_batch_ok": [vp, i32, vp, i32, vp, i64, i32, i32],
     "hawq_image_batch_lds_budget": [],
+    "hawq_jpeg_batch_ok": [vp, i64, i64, i64, i64],
+    "hawq_jpeg_decode_batch": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp],
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
     "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],

@@ -1,0 +1,220 @@
+// hawq_jpeg_decode_batch: a batch of baseline JPEGs -> tight uint8 RGB, the bytes libjpeg-turbo (ISLOW, fancy upsampling) gives.
+// Three launches on one stream; the per-block and per-pixel arithmetic is jpeg_entropy.h / jpeg_pixel.h, shared with the host checker.
+//   1 entropy   one 64-lane workgroup (one wave) per (image, restart interval).  Huffman decoding is serial, so every lane runs the
+//               same decoder on the same state; the lanes share the work that is parallel: they fetch the stream 256 bytes at a time into
+//               an LDS window (one byte per lane and load, masked at the interval's end) and copy the image's Huffman tables into LDS.
+//               Lane 0 alone stores coefficients, into the pre-zeroed slab, and the status.
+//   2 idct      eight lanes per 8x8 block: dequantise + column pass into LDS, row pass + range limit -> sample planes (pitch = padded width).
+//   3 colour    one thread per output pixel: fancy upsampling of the chroma planes, YCbCr -> RGB.
+// Everything the kernels index with comes from the blob, and hawq_jpeg_batch_ok has passed that blob on the host before any launch.
+#include <string.h>
+
+#include "common.h"
+#include "jpeg_pixel.h"
+
+namespace {
+constexpr int WAVE = 64;
+constexpr int WINDOW = 256;   // stream bytes in LDS
+constexpr int MAX_SIDE = 8192;
+constexpr int IDCT_THREADS = 256;   // 32 blocks of 8 lanes
+
+struct Geometry {
+    int64_t blocks, plane_bytes, out_bytes;
+    int32_t mcus;
+};
+
+// block / byte counts of an image whose sampling and size have been checked
+Geometry geometry(const hawq_jpeg_desc &d) {
+    Geometry g;
+    g.mcus = d.mcus_x * d.mcus_y;
+    g.blocks = (int64_t)g.mcus * (d.ncomp == 1 ? 1 : d.hs * d.vs + 2);
+    g.plane_bytes = g.blocks * 64;
+    g.out_bytes = (int64_t)d.width * d.height * 3;
+    return g;
+}
+
+bool inside(int64_t off, int64_t len, int64_t total, int align) { return off >= 0 && len >= 0 && off % align == 0 && off <= total && len <= total - off; }
+
+const char *batch_refusal(const void *host_blob, int64_t blob_bytes, int64_t coef_blocks, int64_t plane_bytes, int64_t out_bytes) {
+    if (!host_blob || blob_bytes < (int64_t)sizeof(hawq_jpeg_batch_hdr) || ((uintptr_t)host_blob & 7)) return "no blob, or not 8-byte aligned";
+    const uint8_t *blob = (const uint8_t *)host_blob;
+    hawq_jpeg_batch_hdr hd;
+    memcpy(&hd, blob, sizeof hd);
+    if (hd.n_images <= 0 || hd.n_images > 65535 || hd.n_waves <= 0) return "image or wave count out of range";
+    if (!inside(hd.desc_off, (int64_t)hd.n_images * (int64_t)sizeof(hawq_jpeg_desc), blob_bytes, 16)) return "descriptors outside the blob";
+    if (!inside(hd.wave_off, (int64_t)hd.n_waves * (int64_t)sizeof(hawq_jpeg_wave), blob_bytes, 16)) return "wave list outside the blob";
+    const hawq_jpeg_desc *desc = (const hawq_jpeg_desc *)(blob + hd.desc_off);
+    const hawq_jpeg_wave *waves = (const hawq_jpeg_wave *)(blob + hd.wave_off);
+    int64_t coef_at = 0, plane_at = 0, out_at = 0, wave_at = 0;
+    for (int32_t i = 0; i < hd.n_images; ++i) {
+        const hawq_jpeg_desc &d = desc[i];
+        if (d.width < 1 || d.height < 1 || d.width > MAX_SIDE || d.height > MAX_SIDE) return "image size outside 1..8192";
+        const bool gray = d.ncomp == 1 && d.hs == 1 && d.vs == 1;
+        const bool colour = d.ncomp == 3 && ((d.hs == 1 && d.vs == 1) || (d.hs == 2 && d.vs == 1) || (d.hs == 2 && d.vs == 2));
+        if (!gray && !colour) return "component count or sampling factors not supported";
+        if (d.mcus_x != (d.width + 8 * d.hs - 1) / (8 * d.hs) || d.mcus_y != (d.height + 8 * d.vs - 1) / (8 * d.vs)) return "MCU counts do not follow from the size";
+        const Geometry g = geometry(d);
+        if (d.restart < 0 || d.n_intervals != (d.restart ? (g.mcus + d.restart - 1) / d.restart : 1)) return "interval count does not follow from the restart interval";
+        for (int c = 0; c < d.ncomp; ++c) {
+            if (!inside(d.qt_off[c], 128, blob_bytes, 2)) return "quantisation table outside the blob";
+            if (!inside(d.dc_off[c], sizeof(hawq_jpeg_huff), blob_bytes, 4) || !inside(d.ac_off[c], sizeof(hawq_jpeg_huff), blob_bytes, 4))
+                return "Huffman table outside the blob";
+            for (int k = 0; k < 2; ++k) {
+                const hawq_jpeg_huff *t = (const hawq_jpeg_huff *)(blob + (k ? d.ac_off[c] : d.dc_off[c]));
+                int codes = 0;
+                int32_t code = 0, values = 0;   // the canonical assignment (T.81 C.2)
+                for (int l = 1; l <= 16; ++l, code <<= 1) {
+                    if (t->maxcode[l] < -1 || t->maxcode[l] >= (1 << l)) return "Huffman table: maxcode out of range";
+                    if (t->maxcode[l] >= 0) {
+                        if (t->mincode[l] != code || t->maxcode[l] < code || t->valptr[l] != values) return "Huffman table: not canonical";
+                        values += t->maxcode[l] - code + 1;
+                        if (values > 256) return "Huffman table: values outside huffval";
+                        code = t->maxcode[l] + 1;
+                        ++codes;
+                    }
+                }
+                if (!codes) return "Huffman table missing";
+            }
+        }
+        if (!inside(d.stream_off, d.stream_len, blob_bytes, 16)) return "stream outside the blob";
+        if (!inside(d.interval_off, (int64_t)d.n_intervals * 8, blob_bytes, 4)) return "interval list outside the blob";
+        const int32_t *iv = (const int32_t *)(blob + d.interval_off);
+        for (int32_t k = 0; k < d.n_intervals; ++k)
+            if (iv[2 * k] < 0 || iv[2 * k] > iv[2 * k + 1] || iv[2 * k + 1] > d.stream_len) return "restart interval outside its stream";
+        if (d.coef_block0 < coef_at || g.blocks > coef_blocks - d.coef_block0) return "coefficient blocks outside the slab or overlapping";
+        if (d.plane_off < plane_at || g.plane_bytes > plane_bytes - d.plane_off) return "sample planes outside their buffer or overlapping";
+        if (d.out_off < out_at || (d.out_off & 15) || g.out_bytes > out_bytes - d.out_off) return "output image outside its buffer, overlapping or unaligned";
+        coef_at = d.coef_block0 + g.blocks, plane_at = d.plane_off + g.plane_bytes, out_at = d.out_off + g.out_bytes;
+        for (int32_t k = 0; k < d.n_intervals; ++k, ++wave_at)
+            if (wave_at >= hd.n_waves || waves[wave_at].image != i || waves[wave_at].interval != k) return "wave list does not name every interval once, in order";
+    }
+    if (wave_at != hd.n_waves) return "wave list longer than the intervals";
+    return nullptr;
+}
+
+// ---- stage 1 ---------------------------------------------------------------------------------------------------------------------
+// The stream through a 256-byte LDS window.  Every lane calls byte() with the same position (the decoder's state is the same in all
+// lanes), so the refill is taken by the whole wave; a lane loads only positions inside [0, end) of its interval's stream.
+struct WindowSrc {
+    const uint8_t *stream;   // global
+    uint8_t *win;            // LDS [WINDOW]
+    int32_t base, end, lane;
+    __device__ __forceinline__ uint8_t byte(int32_t pos) {
+        if (pos < base || pos >= base + WINDOW) {
+            __syncthreads();   // single-wave workgroup: orders the LDS reads of the old window before the new one is written
+            base = pos & ~(WINDOW - 1);
+            for (int k = 0; k < WINDOW / WAVE; ++k) {
+                const int32_t at = base + k * WAVE + lane;
+                win[k * WAVE + lane] = at < end ? stream[at] : (uint8_t)0;
+            }
+            __syncthreads();
+        }
+        return win[pos - base];
+    }
+};
+
+__global__ __launch_bounds__(WAVE) void jpeg_entropy_kernel(const uint8_t *__restrict__ blob, int16_t *__restrict__ coef, int32_t *__restrict__ status) {
+    __shared__ hawq_jpeg_huff tables[6];   // dc, ac per component
+    __shared__ uint8_t window[WINDOW];
+    const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= hd.n_waves) return;
+    const hawq_jpeg_wave w = ((const hawq_jpeg_wave *)(blob + hd.wave_off))[blockIdx.x];
+    const hawq_jpeg_desc d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[w.image];
+    const hawq_jpeg_huff *dc[3], *ac[3];
+    for (int c = 0; c < 3; ++c) {
+        const int cc = c < d.ncomp ? c : 0;
+        const uint32_t *sd = (const uint32_t *)(blob + d.dc_off[cc]), *sa = (const uint32_t *)(blob + d.ac_off[cc]);
+        uint32_t *td = (uint32_t *)&tables[2 * c], *ta = (uint32_t *)&tables[2 * c + 1];
+        for (int k = lane; k < (int)(sizeof(hawq_jpeg_huff) / 4); k += WAVE) td[k] = sd[k], ta[k] = sa[k];
+        dc[c] = &tables[2 * c], ac[c] = &tables[2 * c + 1];
+    }
+    __syncthreads();
+    const int32_t *iv = (const int32_t *)(blob + d.interval_off) + 2 * w.interval;
+    const int32_t first = iv[0], last = iv[1];
+    const int32_t mcus = d.mcus_x * d.mcus_y;
+    const int32_t mcu0 = d.restart ? w.interval * d.restart : 0;
+    const int32_t n_mcu = d.restart ? min(d.restart, mcus - mcu0) : mcus;
+    WindowSrc src{blob + d.stream_off, window, -WINDOW, last, lane};
+    JpegBits<WindowSrc> br(src, first, last);
+    const int32_t st = jpeg_decode_interval(br, d, dc, ac, mcu0, n_mcu, coef + d.coef_block0 * 64, lane == 0);
+    if (lane == 0 && st != 0) atomicCAS(&status[w.image], 0, st);
+}
+
+// ---- stage 2 ---------------------------------------------------------------------------------------------------------------------
+// Eight lanes per block: lane x runs column x into the block's workspace in LDS, then lane y runs row y out of it.
+__global__ __launch_bounds__(IDCT_THREADS) void jpeg_idct_kernel(const uint8_t *__restrict__ blob, const int16_t *__restrict__ coef, uint8_t *__restrict__ planes) {
+    __shared__ int32_t ws[IDCT_THREADS / 8][64];
+    const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
+    const hawq_jpeg_desc &d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[blockIdx.y];   // read in place: qt_off is indexed by the component
+    const int slot = threadIdx.x >> 3, lane8 = threadIdx.x & 7;
+    int64_t b = (int64_t)blockIdx.x * (IDCT_THREADS / 8) + slot;   // block of the image, component after component
+    int64_t comp0 = 0, bw = 0;
+    int comp = -1;
+    for (int c = 0; c < d.ncomp && comp < 0; ++c) {
+        bw = (int64_t)d.mcus_x * jpeg_comp_h(d, c);
+        const int64_t n = bw * d.mcus_y * jpeg_comp_v(d, c);
+        if (b < n)
+            comp = c;
+        else
+            b -= n, comp0 += n;
+    }
+    if (comp >= 0) jpeg_idct_column(coef + (d.coef_block0 + comp0 + b) * 64, (const uint16_t *)(blob + d.qt_off[comp]), lane8, ws[slot]);
+    __syncthreads();
+    if (comp >= 0) {
+        const int64_t by = b / bw, bx = b - by * bw, pitch = bw * 8;
+        jpeg_idct_row(ws[slot], lane8, planes + d.plane_off + comp0 * 64 + (by * 8 + lane8) * pitch + bx * 8);
+    }
+}
+
+// ---- stage 3 ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void jpeg_colour_kernel(const uint8_t *__restrict__ blob, const uint8_t *__restrict__ planes, uint8_t *__restrict__ out) {
+    const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
+    const hawq_jpeg_desc d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[blockIdx.y];
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (int64_t)d.width * d.height) return;
+    const int32_t y = (int32_t)(p / d.width), x = (int32_t)(p - (int64_t)y * d.width);
+    uint8_t rgb[3];
+    jpeg_pixel(d, planes + d.plane_off, x, y, rgb);
+    uint8_t *o = out + d.out_off + p * 3;
+    o[0] = rgb[0], o[1] = rgb[1], o[2] = rgb[2];
+}
+}  // namespace
+
+extern "C" int hawq_jpeg_batch_ok(const void *host_blob, int64_t blob_bytes, int64_t coef_blocks, int64_t plane_bytes, int64_t out_bytes) {
+    const char *why = batch_refusal(host_blob, blob_bytes, coef_blocks, plane_bytes, out_bytes);
+    if (why) hawq_set_error("hawq_jpeg_decode_batch: %s", why);
+    return why == nullptr;
+}
+
+extern "C" int hawq_jpeg_decode_batch(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                                      int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *const *events, void *stream) {
+    HAWQ_REQUIRE(blob && coef && planes && out && status, "hawq_jpeg_decode_batch: null pointer");
+    const char *why = batch_refusal(host_blob, blob_bytes, coef_blocks, plane_bytes, out_bytes);
+    HAWQ_REQUIRE(!why, "hawq_jpeg_decode_batch: %s", why);
+    hipStream_t s = (hipStream_t)stream;
+    hawq_jpeg_batch_hdr hd;
+    memcpy(&hd, host_blob, sizeof hd);
+    const hawq_jpeg_desc *desc = (const hawq_jpeg_desc *)((const uint8_t *)host_blob + hd.desc_off);
+    int64_t max_blocks = 0, max_pixels = 0;
+    for (int32_t i = 0; i < hd.n_images; ++i) {
+        const Geometry g = geometry(desc[i]);
+        max_blocks = g.blocks > max_blocks ? g.blocks : max_blocks;
+        max_pixels = g.out_bytes / 3 > max_pixels ? g.out_bytes / 3 : max_pixels;
+    }
+    HAWQ_CHECK_HIP(hipMemsetAsync(coef, 0, (size_t)coef_blocks * 128, s));
+    HAWQ_CHECK_HIP(hipMemsetAsync(status, 0, (size_t)hd.n_images * sizeof(int32_t), s));
+    if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[0], s));
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)hd.n_waves), dim3(WAVE), 0, s, (const uint8_t *)blob, coef, status);
+    HAWQ_CHECK_HIP(hipGetLastError());
+    if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[1], s));
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_THREADS / 8 - 1) / (IDCT_THREADS / 8)), (unsigned)hd.n_images), dim3(IDCT_THREADS), 0, s,
+                       (const uint8_t *)blob, (const int16_t *)coef, planes);
+    HAWQ_CHECK_HIP(hipGetLastError());
+    if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[2], s));
+    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)hd.n_images), dim3(256), 0, s, (const uint8_t *)blob,
+                       (const uint8_t *)planes, out);
+    HAWQ_CHECK_HIP(hipGetLastError());
+    if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[3], s));
+    return 0;
+}

@@ -13,9 +13,10 @@ the two passes run in ``hawq_resample_u8``.  Pinned to REAL Pillow output: ``tes
 ``resize_center_crop`` / ``preprocess_batch`` work image by image; ``preprocess_batch_fused`` does a whole ragged batch with one
 ``hawq_image_batch`` launch from the tables of ``plan_batch``: same coefficients, same bytes.
 
-JPEG decoding stays on the host, as in the reference (``datasets.ImageFolder``'s ``pil_loader`` inside DataLoader workers,
+JPEG decoding is on the host by default, as in the reference (``datasets.ImageFolder``'s ``pil_loader`` inside DataLoader workers,
 quant_train.py:428-445): ``decode_image`` / ``folder_loader`` below use Pillow when it is installed and say so when it is not;
-everything after the decoded uint8 HWC pixels runs on the MI355X.
+everything after the decoded uint8 HWC pixels runs on the MI355X.  ``folder_loader(device_decode=True)`` decodes baseline JPEGs on the
+MI355X as well (``hawq_amd/jpeg.py``, DESIGN.md 12: the same bytes; other files still go through ``decode_image``).
 """
 from __future__ import annotations
 
@@ -387,13 +388,22 @@ def decoded_batches(samples, batch_size: int, workers: int = 0, decode=decode_im
             yield [f.result() for f in cur], [t for _, t in part]
 
 
-def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int = 224, device="cuda", fused: bool = False, workers: int = 0):
+def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int = 224, device="cuda", fused: bool = False, workers: int = 0,
+                  device_decode: bool = False):
     """Iterate an ImageFolder tree as ``(uint8 [n, crop, crop, 3] on the MI355X, int64 targets)`` batches - the validation loader of
     quant_train.py:428-445 (shuffle off) with everything behind the decoder on the device; feed it to ``api.validate(uint8=True)``.
     The defaults are the ResNets' geometry; InceptionV3 wants ``resize=342, crop=299`` (``eval_geometry(arch)``).
     ``fused``: resample each batch in one launch (``preprocess_batch_fused``: one upload instead of one per image).  ``workers``: decode
-    with that many threads (at most 16), one batch ahead of the GPU (``decoded_batches``).  Same order, labels and bytes either way."""
+    with that many threads (at most 16), one batch ahead of the GPU (``decoded_batches``).  ``device_decode``: the threads only read the
+    files; baseline JPEGs are decoded on the MI355X and everything else by the host decoder (``jpeg.decode_jpeg_batch``), and the batch is
+    resampled in place by ``preprocess_batch_fused`` (implies ``fused``).  Same order, labels and bytes either way."""
     samples, _ = image_folder(root)
+    if device_decode:
+        from . import jpeg
+        for datas, targets in decoded_batches(samples, batch_size, workers, decode=jpeg.read_source):
+            imgs, _ = jpeg.decode_jpeg_batch(datas, device)
+            yield preprocess_batch_fused(imgs, resize, crop, device=device), torch.tensor(targets, dtype=torch.int64)
+        return
     for imgs, targets in decoded_batches(samples, batch_size, workers):
         if fused:
             batch = preprocess_batch_fused(imgs, resize, crop, device=device)

@@ -634,6 +634,60 @@ int hawq_event_record(void *ev, void *stream);
 int hawq_event_elapsed_ms(void *ev_start, void *ev_stop, float *ms);
 int hawq_event_destroy(void *ev);
 
+/* ---- batched baseline JPEG decode (hawq_amd/csrc/jpeg_decode.hip, hawq_amd/jpeg.py; DESIGN.md "Device JPEG decode") -----------
+ * One blob holds everything the kernels read: a header, one descriptor per image, the wave list of the entropy stage, and per image
+ * the quantisation tables (64 x uint16, zig-zag order as stored in DQT), the Huffman tables, the entropy-coded bytes and the restart
+ * intervals.  Every *_off below is a byte offset into the blob.  Accepted: baseline sequential, 8-bit, one interleaved scan; three
+ * components with luma sampling hs x vs in {1x1, 2x1, 2x2} and chroma 1x1, or one component.
+ * Output: the bytes of libjpeg-turbo's ISLOW IDCT + fancy upsampling + YCbCr->RGB, tight uint8 [height][width][3] at out_off. */
+enum {
+    HAWQ_JPEG_OK = 0,
+    HAWQ_JPEG_EOF = 1,      /* the interval ran out of bytes */
+    HAWQ_JPEG_CODE = 2,     /* a bit pattern that is no code of the table (or a DC category above 15) */
+    HAWQ_JPEG_INDEX = 3,    /* an AC run went past coefficient 63 */
+    HAWQ_JPEG_MARKER = 4    /* FF xx (xx != 00) inside an interval */
+};
+typedef struct hawq_jpeg_batch_hdr {   /* at offset 0 of the blob */
+    int32_t n_images, n_waves;
+    int32_t desc_off, wave_off;        /* hawq_jpeg_desc[n_images], hawq_jpeg_wave[n_waves]; 16-byte aligned */
+} hawq_jpeg_batch_hdr;
+typedef struct hawq_jpeg_wave {        /* one wave of the entropy stage: one restart interval of one image; image-major, in order */
+    int32_t image, interval;
+} hawq_jpeg_wave;
+/* Canonical Huffman table (JPEG F.2.2.3): codes of length l are mincode[l] .. maxcode[l] (maxcode[l] = -1: none), the value of code c
+ * of length l is huffval[valptr[l] + c - mincode[l]].  Index 0 of the three arrays is unused. */
+typedef struct hawq_jpeg_huff {
+    int32_t mincode[17], maxcode[17], valptr[17];
+    uint8_t huffval[256];
+    int32_t reserved;
+} hawq_jpeg_huff;                      /* 464 bytes */
+typedef struct hawq_jpeg_desc {
+    int32_t width, height, ncomp;      /* ncomp 1 (Y, written as R = G = B) or 3 (Y, Cb, Cr) */
+    int32_t hs, vs;                    /* luma sampling factors; chroma is 1 x 1 */
+    int32_t mcus_x, mcus_y;            /* ceil(width / (8 hs)), ceil(height / (8 vs)) */
+    int32_t restart;                   /* MCUs per restart interval, 0: the whole scan is one interval */
+    int32_t n_intervals;               /* ceil(mcus / restart), 1 without DRI */
+    int32_t qt_off[3], dc_off[3], ac_off[3];   /* per component: uint16[64], hawq_jpeg_huff, hawq_jpeg_huff */
+    int32_t stream_off, stream_len;    /* the entropy-coded segment */
+    int32_t interval_off;              /* int32 [n_intervals][2]: first byte and one past the last, relative to stream_off */
+    int32_t reserved;
+    int64_t coef_block0;               /* first [64] x int16 block of this image in the coefficient slab: component after component,
+                                          each mcus_y * v rows of mcus_x * h blocks */
+    int64_t plane_off;                 /* first byte of this image's sample planes: component after component, pitch mcus_x * h * 8 */
+    int64_t out_off;                   /* first byte of the RGB image in out; 16-byte aligned */
+} hawq_jpeg_desc;                      /* 112 bytes */
+/* hawq_jpeg_batch_ok launches nothing and reads the HOST blob: 1 when the header, every descriptor, table, stream and interval lies
+ * inside blob_bytes at its alignment, the geometry is one of the accepted ones and block counts follow from it, every image's range of
+ * the slab / planes / out lies inside coef_blocks / plane_bytes / out_bytes behind the previous image's, every interval lies inside its
+ * stream, and the wave list names every (image, interval) once in order; else 0 with the reason in hawq_last_error().
+ * hawq_jpeg_decode_batch: blob = device copy of host_blob (which it checks again before it launches anything).  Zeroes coef and status
+ * on `stream`, then entropy decode (one wave per entry of the wave list) -> coef, dequantise + IDCT -> planes, upsample + colour -> out.
+ * status[i]: 0, or the HAWQ_JPEG_* error of one of image i's intervals (which one is not defined): its pixels are not to be used.
+ * events: NULL, or four hipEvent_t recorded before stage 1 and behind stages 1, 2 and 3. */
+int hawq_jpeg_batch_ok(const void *host_blob, int64_t blob_bytes, int64_t coef_blocks, int64_t plane_bytes, int64_t out_bytes);
+int hawq_jpeg_decode_batch(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                           int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *const *events, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
