@@ -517,7 +517,7 @@ extern "C" int hawq_conv_expand_reduce(const hawq_expand_reduce_args *a, void *s
     HAWQ_REQUIRE(v >= 0, "hawq_conv_expand_reduce: this pair of layers cannot be fused (need 1x1/stride-1 int8 fast-contract convs, "
                          "uint16 residual in and out - or a same-shape 1x1 identity branch with Cin 64 -, Cin in {64,128,256}, reduce.Cin == expand.Cout, reduce.Cout == expand.Cin; tile %d)", a->tile);
     const hawq_conv_args &e = a->expand, &r = a->reduce;
-    auto e_fast = [](int ek) { return (ek & 0xff) >= 33 && (ek & 0xff) <= 62; };
+    auto e_fast = [](int ek) { return (ek & 0xff) >= 33 && (ek & 0xff) <= 62 && (ek >> 8) >= 0 && (ek >> 8) < 31; };   // e in [33,62], pre-shift k in [0,30]
     HAWQ_REQUIRE(e.mq >= 0 && e_fast(e.eq) && (e.in2 || (e.m_id_scalar >= 0 && e_fast(e.e_id_scalar))), "hawq_conv_expand_reduce: scalar tables outside the fast contract");
     HAWQ_REQUIRE(e.q_lo <= 0, "hawq_conv_expand_reduce: the block-input QuantAct clamp must admit 0");
     ERP p;

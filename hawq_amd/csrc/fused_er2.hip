@@ -433,7 +433,7 @@ int er2_launch(const hawq_expand_reduce_args *a, int nth, void *stream) {
     const int v = e2_variant(a, nth);
     HAWQ_REQUIRE(v >= 0, "hawq_conv_expand_reduce: no pipelined variant %d for this launch", nth);
     const hawq_conv_args &e = a->expand, &r = a->reduce;
-    auto e_fast = [](int ek) { return (ek & 0xff) >= 33 && (ek & 0xff) <= 62; };
+    auto e_fast = [](int ek) { return (ek & 0xff) >= 33 && (ek & 0xff) <= 62 && (ek >> 8) >= 0 && (ek >> 8) < 31; };   // e in [33,62], pre-shift k in [0,30]
     HAWQ_REQUIRE(e.mq >= 0 && e_fast(e.eq) && e.m_id_scalar >= 0 && e_fast(e.e_id_scalar), "hawq_conv_expand_reduce: scalar tables outside the fast contract");
     HAWQ_REQUIRE(e.q_lo <= 0, "hawq_conv_expand_reduce: the block-input QuantAct clamp must admit 0");
     HAWQ_REQUIRE(e.q_hi >= 0 && e.q_hi <= 32767, "hawq_conv_expand_reduce: q_hi outside [0, 32767]");

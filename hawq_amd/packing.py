@@ -95,7 +95,12 @@ def pack_ctab(bias, m, ek) -> np.ndarray:
     ek = np.asarray(ek, np.int64).reshape(-1)
     e, k = ek & 0xff, ek >> 8
     assert (e >= 33).all() and (e <= 62).all() and (k >= 0).all(), "pack_ctab needs fast-contract tables"
-    cc = (bias << k) * m + (np.int64(1) << (e - 1))
+    # |bias << k| < 2^31 and 0 <= m < 2^31 keep Cc below 1.5 * 2^62; beyond them the int64 arithmetic below would wrap silently
+    if (k > 30).any() or (np.abs(bias) >= (np.int64(1) << (31 - np.minimum(k, 30)))).any():
+        raise ValueError("pack_ctab: |bias << k| must stay below 2^31 (the fast contract's bound on every pre-shifted value)")
+    if ((m < 0) | (m >= (1 << 31))).any():
+        raise ValueError("pack_ctab: m must lie in [0, 2^31)")
+    cc =(bias << k) * m + (np.int64(1) << (e - 1))
     out = np.empty((bias.size, 4), np.int32)
     out[:, 0] = m.astype(np.int32)
     out[:, 1] = ((e - 32) | (k << 8)).astype(np.int32)
