@@ -42,6 +42,14 @@ class ConvArgs(C.Structure):
     ]
 
 
+class ConvChoice(C.Structure):
+    """struct hawq_conv_choice (include/hawq_mi355.h): what hawq_conv2d would launch, from the host-only hawq_conv2d_choice."""
+    _fields_ = [("family", i32), ("tile", i32), ("index", i32), ("fn_table", i32), ("fn", i32 * 3),
+                ("grid", i32), ("block", i32), ("lds_bytes", i32)] + [(n, i32) for n in (
+        "stride", "res_sub", "Ho", "Wo", "M", "q_lo", "mq", "eq", "m_id_s", "e_id_s", "k0", "ck0", "gfast",
+        "in_pitch", "out_pitch", "ring_bytes")]
+
+
 class ExpandReduceArgs(C.Structure):
     """struct hawq_expand_reduce_args (include/hawq_mi355.h)."""
     _fields_ = [("expand", ConvArgs), ("reduce", ConvArgs), ("tile", i32)]
@@ -134,6 +142,7 @@ SIGNATURES = {
     "hawq_abi_version": [],
     "hawq_device_ok": [],
     "hawq_conv2d": [C.POINTER(ConvArgs), vp],
+    "hawq_conv2d_choice": [C.POINTER(ConvArgs), C.POINTER(ConvChoice)],
     "hawq_conv2d_num_tiles": [],
     "hawq_conv2d_num_band_tiles": [],
     "hawq_conv2d_band_tile": [C.POINTER(ConvArgs)],

@@ -2,7 +2,7 @@
 // first 3x3 of a ResNet18/34 stage-1 block; QuantBnConv2d + ReLU + QuantAct, quant_modules.py:527-545, 233-260).
 //
 // Why a second 3x3 kernel.  For these layers K = 576 only: a 256-pixel tile is 2304 matrix-pipe cycles, while the
-// band kernel of conv_igemm.hip spends 4.9 k cycles per tile waiting for its operands (36 KiB of weights - the SAME
+// band kernel of band_v1.hip spends 4.9 k cycles per tile waiting for its operands (36 KiB of weights - the SAME
 // 36 KiB for every tile - plus a 32 KiB band whose plane layout makes every LDS-DMA piece a gather of 64 sixteen-byte
 // segments, the one slow shape of tools/ubench/ingest_shape.hip) and 4.1 k in the epilogue, with two workgroups per
 // CU to overlap them (profiles/r02_band_persist.md).  Here
@@ -18,7 +18,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -331,7 +331,9 @@ __global__ __launch_bounds__(NT, RES ? 3 : 4) void band_persist_kernel(const BPP
 
 }  // namespace
 
-bool band_persist_applies(const hawq_conv_args *a) {
+int band_persist_count(void) { return 2; }   // one / two workgroups per CU
+
+bool band_persist_applies(const hawq_conv_args *a, int) {
     const int wo = a->W, band_rows = (BM + wo - 1) / wo + 1 + 2;
     const bool epi_ok = (a->epilogue == HAWQ_EPI_REQUANT && a->out_q && a->out_bits == 8) ||
                         (a->epilogue == HAWQ_EPI_RESIDUAL && a->res_in && a->res_in_bits == 16 && (!a->res_out || (a->res_out_bits == 16 && a->flags)) &&
@@ -343,9 +345,17 @@ bool band_persist_applies(const hawq_conv_args *a) {
            (long long)a->N * a->H * a->W < (1ll << 23);
 }
 
-// wgs_per_cu: 1 leaves half of every CU (LDS, wave slots) to whatever runs beside this launch - the other sub-batch chain
-// of the engine -, 2 is the faster one when the launch has the chip to itself
-int band_persist_launch(const hawq_conv_args *a, int exact_tie, int dbg, int wgs_per_cu, void *stream) {
+// tile 0 / 1 = 1 / 2 workgroups per CU: 1 leaves half of every CU (LDS, wave slots) to whatever runs beside this launch - the other
+// sub-batch chain of the engine -, 2 is the faster one when the launch has the chip to itself.  The grid is sized at launch.
+int band_persist_choose(const hawq_conv_args *, const ConvForm &f, const ConvP &p, ConvChoice &c) {
+    c.fn[0] = p.k0 == 2 ? 1 : 0, c.fn[1] = f.slot == HAWQ_EPI_RESIDUAL ? 1 : 0;
+    c.grid = -1, c.block = NT, c.lds = LDS_BYTES;
+    return 0;
+}
+
+int band_persist_launch(const hawq_conv_args *a, const ConvChoice &c, const ConvP &args, void *stream) {
+    const int wgs_per_cu = c.tile + 1;
+    const bool exact_tie = c.fn[0] != 0;
     BPP p;
     p.in = (const uint8_t *)a->in, p.wgt = (const uint8_t *)a->wgt, p.ctab = a->ctab, p.out = (uint8_t *)a->out_q;
     const bool res = a->epilogue == HAWQ_EPI_RESIDUAL;
@@ -357,9 +367,7 @@ int band_persist_launch(const hawq_conv_args *a, int exact_tie, int dbg, int wgs
     p.q_lo = a->relu && a->q_lo < 0 ? 0 : a->q_lo, p.q_hi = a->q_hi;
     p.ntiles = (p.M + BM - 1) / BM;
     p.ck0 = (a->fast_tables & 8) != 0;
-    static long long *dbg_dev = nullptr;
-    if (HAWQ_DBG_BIT(dbg, 128) && !dbg_dev) (void)hipMalloc(&dbg_dev, 8 * sizeof(long long));
-    p.dbgbuf = HAWQ_DBG_BIT(dbg, 128) ? dbg_dev : nullptr;
+    p.dbgbuf = conv_dbg_buffer(args.dbg);
     static const int n_cu = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;

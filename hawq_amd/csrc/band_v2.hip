@@ -33,7 +33,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -546,6 +546,7 @@ const V2Info kV2[NUM_V2] = {V2_ENTRY(V128), V2_ENTRY(V256)};
 
 }  // namespace
 
+const int kBandV2Preference[NUM_V2] = {0, 1};
 int band_v2_count(void) { return NUM_V2; }
 
 // [Cout][3][3][Cin] int8 -> [Cout/64][Cin/64][kh][kw][64 rows][64 B], slot s of row r at r * 64 + ((s ^ ((r >> 2) & 3)) << 4) (lds_off)
@@ -584,7 +585,16 @@ bool band_v2_applies(const hawq_conv_args *a, int v) {
            band_len <= vi.band_px - 4 && rowb / 64 * 3 >= 6 && M * rowb < (1ll << 31) && (long long)a->Cout * rowb * 9 < (1ll << 31);
 }
 
-int band_v2_launch(const hawq_conv_args *a, int v, int exact_tie, int dbg, void *stream) {
+int band_v2_choose(const hawq_conv_args *a, const ConvForm &f, const ConvP &p, ConvChoice &c) {
+    const V2Info &vi = kV2[c.tile];
+    c.table = f.slot == HAWQ_EPI_RAW, c.fn[0] = a->in_bits == 4;
+    if (!c.table) c.fn[1] = f.slot == HAWQ_EPI_RESIDUAL, c.fn[2] = p.k0 == 2;
+    c.grid = ((p.M + vi.bm - 1) / vi.bm) * (p.Cout >> 6), c.block = vi.nt, c.lds = vi.lds;
+    return 0;
+}
+
+int band_v2_launch(const hawq_conv_args *a, const ConvChoice &c, const ConvP &args, void *stream) {
+    const int v = c.tile, grid = c.grid;
     const V2Info &vi = kV2[v];
     B2P p;
     p.in = (const char *)a->in, p.wgt = (const char *)a->wgt_band, p.ctab = a->ctab, p.out = (char *)a->out_q;
@@ -599,10 +609,8 @@ int band_v2_launch(const hawq_conv_args *a, int v, int exact_tie, int dbg, void 
     p.mq = a->mq, p.eq = a->eq, p.m_id = a->m_id_scalar, p.e_id = a->e_id_scalar;
     if (a->epilogue == HAWQ_EPI_RESIDUAL && !a->out_q) p.mq = 0, p.eq = 33;   // no next QuantAct: a harmless table
     p.in_bytes = (unsigned)((long long)p.M * rowb), p.wgt_bytes = (unsigned)((long long)a->Cout * rowb * 9);
-    p.dbg = dbg;
-    static long long *dbg_dev = nullptr;
-    if (HAWQ_DBG_BIT(dbg, 128) && !dbg_dev) (void)hipMalloc(&dbg_dev, 8 * sizeof(long long));
-    p.dbgbuf = HAWQ_DBG_BIT(dbg, 128) ? dbg_dev : nullptr;
+    p.dbg = args.dbg;
+    p.dbgbuf = conv_dbg_buffer(args.dbg);
     static const bool attrs = [] {
         bool good = true;
         for (const V2Info &i : kV2)
@@ -613,9 +621,8 @@ int band_v2_launch(const hawq_conv_args *a, int v, int exact_tie, int dbg, void 
         return good;
     }();
     HAWQ_REQUIRE(attrs, "hawq_conv2d: hipFuncSetAttribute failed for the round-5 3x3 kernels");
-    const int grid = ((p.M + vi.bm - 1) / vi.bm) * (p.Cout >> 6);
-    V2Fn fn = a->epilogue == HAWQ_EPI_RAW ? vi.raw[nib ? 1 : 0] : vi.fn[nib ? 1 : 0][a->epilogue == HAWQ_EPI_RESIDUAL ? 1 : 0][exact_tie ? 1 : 0];
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(vi.nt), vi.lds, (hipStream_t)stream, p);
+    V2Fn fn = c.table ? vi.raw[c.fn[0]] : vi.fn[c.fn[0]][c.fn[1]][c.fn[2]];
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(c.block), c.lds, (hipStream_t)stream, p);
     HAWQ_CHECK_HIP(hipGetLastError());
     if (p.dbgbuf) {   // experiment hook (synchronises!)
         long long hb[6];

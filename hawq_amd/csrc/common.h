@@ -148,7 +148,7 @@ __device__ __forceinline__ uint32_t pack8_u4(const int *q) {
     return pack4_i8(q[0], q[1], q[2], q[3]) | (pack4_i8(q[4], q[5], q[6], q[7]) << 4);
 }
 
-// ---- shared device helpers of the conv kernels (conv_igemm.hip, fused_er.hip) ---------------------------
+// ---- shared device helpers of the conv kernels (conv_device.h, fused_er.hip) ---------------------------
 // MFMA C/D row i of a 32x32 tile lives in (reg, half) with i = (reg&3) + 8*(reg>>2) + 4*half.
 // Reading weight row cperm(i) as MFMA row i makes lane-half h own channels 16h..16h+15.
 __device__ __forceinline__ int cperm(int i) { return (((i >> 2) & 1) << 4) + (i & 3) + ((i >> 3) << 2); }

@@ -3,9 +3,9 @@
 // At 64 images per chain the late stages already launch 98-392 workgroups; at 1-16 images the stage 3-4 convs launch
 // 8-50 (ResNet50 batch 1: the stage-4 3x3 conv, M = 49, K = 4608, runs on 8 workgroups of a 256-CU chip) and every launch
 // lasts as long as one workgroup's whole K loop.  Here the grid is (64 px x 64 ch output tiles) x (K slices): each slice
-// workgroup runs the asynchronous MFMA pipeline of conv_igemm.hip over its share of the K chunks and writes its int32
+// workgroup runs the asynchronous MFMA pipeline of conv_device.h over its share of the K chunks and writes its int32
 // partial tile to a slab with plain vector stores; the workgroup that arrives last at its tile sums the slabs and runs
-// the SAME epilogue code as hawq_conv2d (epilogue_fast / epilogue_generic of conv_igemm.hip).  Integer addition is exact
+// the SAME epilogue code as hawq_conv2d (epilogue_fast / epilogue_generic of conv_device.h).  Integer addition is exact
 // in any order, so the outputs are bit-identical to hawq_conv2d whatever the slice count or the arrival order.
 //
 // Arrival protocol (placement independent: a tile's slices may run on different XCDs, each with its own L2):
@@ -19,8 +19,7 @@
 // first launch (every launch leaves them zero).  tiles = ceil(M / 64) * Cout / 64.  The main branch's K chunks (KH * KW *
 // Cin / 64) are cut into S equal slices; a second branch (the identity 1x1 conv of a resize unit) is cut into S2 slices of
 // its own, of the largest chunk count that divides Cin2 / 64 and does not exceed the main branch's.
-#define HAWQ_CONV_IGEMM_DEVICE_ONLY
-#include "conv_igemm.hip"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -121,6 +120,9 @@ struct SplitPlan {
     long long slab_bytes, counter_bytes;
 };
 
+// the staged fast-contract epilogue (epilogue_fast), as opposed to the direct one
+bool splitk_fast_epi(const ConvForm &f) { return f.fast && f.needs_tables && !f.wide_res && !f.signed_res; }
+
 // Does the split-K kernel take this launch with `slices` slices of the main branch?  0 = yes (plan filled), else the
 // reason goes to hawq_last_error.  Checks the form of the launch (geometry, widths, epilogue, layouts), not its pointers.
 int splitk_plan(const hawq_conv_args *a, int slices, SplitPlan &sp) {
@@ -139,12 +141,8 @@ int splitk_plan(const hawq_conv_args *a, int slices, SplitPlan &sp) {
     HAWQ_REQUIRE(epi == HAWQ_EPI_RAW || !a->out_q || a->out_bits == 8, "hawq_conv2d_splitk: out_bits must be 8");
     HAWQ_REQUIRE(epi != HAWQ_EPI_REQUANT || a->out_q, "hawq_conv2d_splitk: REQUANT needs out_q");
     HAWQ_REQUIRE((a->in_planar | a->out_planar | 1) == 1, "hawq_conv2d_splitk: in_planar / out_planar must be 0 or 1");
-    const bool dual = a->in2 != nullptr;
-    const bool fast = a->fast_tables != 0;
-    const bool res = epi == HAWQ_EPI_RESIDUAL;
-    const bool wide_res = res && ((!dual && a->res_in_bits == 32) || (a->res_out && a->res_out_bits == 32));
-    const bool signed_res = res && !dual && (a->res_no_relu || a->res_clamp16 || !a->res_in);
-    const bool fast_epi = fast && epi != HAWQ_EPI_RAW && !wide_res && !signed_res;
+    const ConvForm f = conv_form(a);
+    const bool dual = f.dual, res = epi == HAWQ_EPI_RESIDUAL, fast_epi = splitk_fast_epi(f);
     HAWQ_REQUIRE(!a->in_planar || (!dual && fast_epi), "hawq_conv2d_splitk: in_planar needs a single-branch fast-contract REQUANT / RESIDUAL launch");
     HAWQ_REQUIRE(!a->out_planar || (fast_epi && a->out_q), "hawq_conv2d_splitk: out_planar needs the fast-contract REQUANT / RESIDUAL epilogue");
     sp.Ho = (a->H + 2 * a->pad - a->KH) / a->stride + 1;
@@ -211,70 +209,12 @@ extern "C" int hawq_conv2d_splitk(const hawq_conv_args *a, int32_t slices, void 
     const int rc = splitk_plan(a, slices, sp);
     if (rc) return rc;
     HAWQ_REQUIRE(slab && counters, "hawq_conv2d_splitk: slab and counters must be non-null");
-    HAWQ_REQUIRE(a->in && a->wgt && a->bias, "hawq_conv2d_splitk: in/wgt/bias must be non-null");
-    const bool dual = a->in2 != nullptr;
-    const int epi = a->epilogue;
-    const bool fast = a->fast_tables != 0;
-    ConvP p = {};
-    p.in = (const uint8_t *)a->in, p.wgt = (const uint8_t *)a->wgt, p.bias = a->bias;
-    p.N = a->N, p.H = a->H, p.W = a->W, p.Cin = a->Cin, p.Cout = a->Cout;
-    p.KH = a->KH, p.KW = a->KW, p.stride = a->stride, p.pad = a->pad, p.Ho = sp.Ho, p.Wo = sp.Wo, p.M = sp.M;
-    p.in_bits = 8, p.w_bits = 8;
-    p.in2 = (const uint8_t *)a->in2, p.wgt2 = (const uint8_t *)a->wgt2, p.bias2 = a->bias2;
-    p.H2 = a->H2, p.W2 = a->W2, p.Cin2 = a->Cin2, p.stride2 = a->stride2, p.in2_bits = a->in2_bits, p.w2_bits = a->w2_bits;
-    p.relu = a->relu;
-    p.m = a->m, p.e = a->e, p.m_id = a->m_id, p.e_id = a->e_id, p.m_id_s = a->m_id_scalar, p.e_id_s = a->e_id_scalar;
-    p.res_in = a->res_in, p.res_in_bits = a->res_in_bits, p.res_out = a->res_out, p.res_out_bits = a->res_out_bits;
-    p.res_no_relu = a->res_no_relu, p.res_clamp16 = a->res_clamp16;
-    p.out_q = a->out_q, p.out_bits = a->out_bits, p.q_lo = a->q_lo, p.q_hi = a->q_hi, p.mq = a->mq, p.eq = a->eq;
-    p.out_acc = a->out_acc, p.out_f32 = nullptr, p.fscale = nullptr, p.ldo = 0, p.n_valid = 0;
-    p.flags = a->flags, p.ctab = a->ctab, p.ctab_id = a->ctab_id;
-    p.k0 = (a->fast_tables & 4) ? 2 : ((a->fast_tables & 2) ? 1 : 0);
-    p.ck0 = (a->fast_tables & 8) != 0;
+    ConvForm f;
+    ConvP p;
+    if (const int rc = conv_check(a, "hawq_conv2d_splitk", &f, &p)) return rc;   // hawq_conv2d's argument rules and table preparation
     p.ring_bytes = SK::LDS_BYTES;
-    p.in_planar = a->in_planar, p.out_planar = a->out_planar;
-    p.in_pitch = a->Cin, p.out_pitch = a->Cout;
-    p.dbg = 0, p.dbgbuf = nullptr;
-    // the same argument rules and table preparation as hawq_conv2d (conv_igemm.hip) for the forms taken here
-    const bool res = epi == HAWQ_EPI_RESIDUAL;
-    const bool wide_res = res && ((!dual && a->res_in_bits == 32) || (a->res_out && a->res_out_bits == 32));
-    const bool signed_res = res && !dual && (a->res_no_relu || a->res_clamp16 || !a->res_in);
-    auto e_fast = [](int ek) { return (ek & 0xff) >= 33 && (ek & 0xff) <= 62; };
-    auto e_any = [](int ek) { return (ek & 0xff) >= 1 && (ek & 0xff) <= 62 && (ek >> 8) >= 0 && (ek >> 8) < 31; };
-    if (dual) HAWQ_REQUIRE(a->wgt2 && a->bias2 && a->m_id && a->e_id, "hawq_conv2d_splitk: second branch tables missing");
-    if (epi == HAWQ_EPI_RAW) HAWQ_REQUIRE(a->out_acc, "hawq_conv2d_splitk: RAW needs out_acc");
-    if (epi == HAWQ_EPI_REQUANT) HAWQ_REQUIRE(a->m && a->e, "hawq_conv2d_splitk: REQUANT needs m, e");
-    if (fast && epi != HAWQ_EPI_RAW) {
-        HAWQ_REQUIRE(a->ctab && (!dual || a->ctab_id), "hawq_conv2d_splitk: fast_tables needs ctab (and ctab_id)");
-        if (epi == HAWQ_EPI_REQUANT && a->relu && p.q_lo < 0) p.q_lo = 0;   // ReLU folded into the clamp
-        HAWQ_REQUIRE(!res || !a->out_q || a->q_lo <= 0 || wide_res || signed_res, "hawq_conv2d_splitk: fast RESIDUAL needs q_lo <= 0");
-    }
-    if (res) {
-        HAWQ_REQUIRE(a->m && a->e, "hawq_conv2d_splitk: RESIDUAL needs m, e");
-        HAWQ_REQUIRE(a->res_out || a->out_q, "hawq_conv2d_splitk: RESIDUAL needs res_out and/or out_q");
-        HAWQ_REQUIRE(dual || !a->res_in || a->res_in_bits == 16 || a->res_in_bits == 32, "hawq_conv2d_splitk: res_in_bits 16/32");
-        HAWQ_REQUIRE(!(dual && (a->res_no_relu || a->res_clamp16)), "hawq_conv2d_splitk: res_no_relu / res_clamp16 exist for single-branch launches");
-        HAWQ_REQUIRE(!a->res_no_relu || !a->res_out || a->res_out_bits == 32, "hawq_conv2d_splitk: a residual stored without ReLU is signed: res_out_bits must be 32");
-        HAWQ_REQUIRE(!a->res_out || a->res_out_bits == 32 || (a->res_out_bits == 16 && a->flags), "hawq_conv2d_splitk: res_out_bits 16 (with flags) or 32");
-        if (a->out_q) {
-            HAWQ_REQUIRE(a->mq >= 0 && e_any(a->eq), "hawq_conv2d_splitk: bad (mq, eq)");
-            HAWQ_REQUIRE(!fast || e_fast(a->eq), "hawq_conv2d_splitk: fast_tables needs eq in [33,62]");
-            HAWQ_REQUIRE(!fast || (a->q_hi >= 0 && a->q_hi <= 32767), "hawq_conv2d_splitk: fast_tables needs 0 <= q_hi <= 32767");
-        } else {
-            p.mq = 0, p.eq = 33;
-        }
-        if (dual || !a->res_in) {
-            p.m_id_s = 0, p.e_id_s = 33;
-        } else {
-            HAWQ_REQUIRE(a->m_id_scalar >= 0 && e_any(a->e_id_scalar), "hawq_conv2d_splitk: bad (m_id_scalar, e_id_scalar)");
-            HAWQ_REQUIRE(!fast || e_fast(a->e_id_scalar), "hawq_conv2d_splitk: fast_tables needs e_id_scalar in [33,62]");
-        }
-    } else {
-        p.mq = 0, p.eq = 33, p.m_id_s = 0, p.e_id_s = 33;
-    }
-    const bool fast_epi = fast && epi != HAWQ_EPI_RAW && !wide_res && !signed_res;
-    p.gfast = fast && res && !dual && (wide_res || signed_res);
-    const SplitFn fn = pick_kernel(epi, dual, fast_epi, p.k0 == 2, a->in_planar != 0);
+    p.dbg = 0;
+    const SplitFn fn = pick_kernel(a->epilogue, f.dual, splitk_fast_epi(f), p.k0 == 2, a->in_planar != 0);
     SplitP s;
     s.slab = (int32_t *)slab, s.counters = counters;
     s.tiles_c = sp.tiles_c, s.ntiles = sp.ntiles, s.s1 = sp.s1, s.s2 = sp.s2, s.q1 = sp.q1, s.q2 = sp.q2, s.ns1 = sp.ns1;

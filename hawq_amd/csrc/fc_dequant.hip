@@ -4,7 +4,7 @@
 // with (profiles/r05_c_kernel_trace.md).  Here K is split over the 4 waves of a workgroup, a workgroup owns 32 outputs x 32 images, and
 // the operands go global -> registers -> MFMA with no LDS staging and no barrier in the loop (both operands are tiny and L2-resident:
 // 2 MiB of weights, 128 KiB of activations); the four partial sums meet once in LDS.
-//   out[n][o] = (float)(sum_k q[n][k] * w[o][k] + bias[o]) * fscale[o]          (exactly the DEQUANT epilogue of conv_igemm.hip)
+//   out[n][o] = (float)(sum_k q[n][k] * w[o][k] + bias[o]) * fscale[o]          (exactly the DEQUANT epilogue of conv_device.h)
 #include <stdio.h>
 
 #include "common.h"

@@ -2,7 +2,7 @@
 // bottleneck and the expand conv + identity conv that close the first unit of a stage, q_resnet.py:231-260) as a streaming GEMM
 // built on the machinery of band_v2.hip.
 //
-// Why.  conv_kernel (conv_igemm.hip) walks K in 64-byte chunks with one workgroup barrier per chunk: for these layers a chunk is
+// Why.  conv_kernel (conv_device.h) walks K in 64-byte chunks with one workgroup barrier per chunk: for these layers a chunk is
 // 64-128 cycles of matrix pipe behind ~1000 cycles of LDS-DMA round trip + barrier, so a K = 2048 reduce conv on a 7 x 7 map spends
 // 32 such round trips (15-20 us for 1.3 us of MFMA work), and its operand tiles are 64-byte row segments a row apart - half
 // cache lines, the slow LDS-DMA shape (tools/ubench/dma_issue.hip).  A 1x1 conv has no operand reuse beyond its tile, so what bounds
@@ -30,7 +30,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_dispatch.h"
 
 namespace {
 
@@ -491,7 +491,16 @@ bool gemm_v2_applies(const hawq_conv_args *a, int v) {
            (a->out_pitch == 0 || a->out_pitch == a->Cout) && Min * rowb < (1ll << 31) && (long long)a->Cout * rowb < (1ll << 31) && M * a->Cout < (1ll << 31);
 }
 
-int gemm_v2_launch(const hawq_conv_args *a, int v, int exact_tie, int dbg, void *stream) {
+int gemm_v2_choose(const hawq_conv_args *a, const ConvForm &f, const ConvP &p, ConvChoice &c) {
+    const G2Info &gi = kG2[c.tile];
+    c.table = f.slot == HAWQ_EPI_RAW, c.fn[0] = a->in_bits == 4;
+    if (!c.table) c.fn[1] = f.slot == HAWQ_EPI_REQUANT ? 0 : (f.dual ? 2 : 1), c.fn[2] = p.k0 == 2;
+    c.grid = ((p.M + 127) / 128) * (p.Cout / gi.bn), c.block = gi.nt, c.lds = gi.lds;
+    return 0;
+}
+
+int gemm_v2_launch(const hawq_conv_args *a, const ConvChoice &c, const ConvP &args, void *stream) {
+    const int v = c.tile, grid = c.grid;
     const G2Info &gi = kG2[v];
     const bool dual = a->in2 != nullptr;
     const bool nib = a->in_bits == 4;
@@ -512,10 +521,8 @@ int gemm_v2_launch(const hawq_conv_args *a, int v, int exact_tie, int dbg, void 
     if (a->epilogue != HAWQ_EPI_RESIDUAL || dual) p.m_id = 0, p.e_id = 33;
     p.x_bytes = (unsigned)((long long)a->N * a->H * a->W * rowb), p.w_bytes = (unsigned)((long long)a->Cout * rowb);
     p.x2_bytes = dual ? (unsigned)((long long)a->N * a->H2 * a->W2 * rowb2) : 0, p.w2_bytes = dual ? (unsigned)((long long)a->Cout * rowb2) : 0;
-    p.dbg = dbg;
-    static long long *dbg_dev = nullptr;
-    if (HAWQ_DBG_BIT(dbg, 128) && !dbg_dev) (void)hipMalloc(&dbg_dev, 8 * sizeof(long long));
-    p.dbgbuf = HAWQ_DBG_BIT(dbg, 128) ? dbg_dev : nullptr;
+    p.dbg = args.dbg;
+    p.dbgbuf = conv_dbg_buffer(args.dbg);
     static const bool attrs = [] {
         bool good = true;
         for (const G2Info &i : kG2) {
@@ -525,10 +532,8 @@ int gemm_v2_launch(const hawq_conv_args *a, int v, int exact_tie, int dbg, void 
         return good;
     }();
     HAWQ_REQUIRE(attrs, "hawq_conv2d: hipFuncSetAttribute failed for the round-5 1x1 kernels");
-    const int grid = ((p.M + 127) / 128) * (p.Cout / gi.bn);
-    const int e = a->epilogue == HAWQ_EPI_REQUANT ? 0 : (dual ? 2 : 1);
-    G2Fn fn = a->epilogue == HAWQ_EPI_RAW ? gi.raw[nib ? 1 : 0] : gi.fn[nib ? 1 : 0][e][exact_tie ? 1 : 0];
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(gi.nt), gi.lds, (hipStream_t)stream, p);
+    G2Fn fn = c.table ? gi.raw[c.fn[0]] : gi.fn[c.fn[0]][c.fn[1]][c.fn[2]];
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(c.block), c.lds, (hipStream_t)stream, p);
     HAWQ_CHECK_HIP(hipGetLastError());
     if (p.dbgbuf) {   // experiment hook (synchronises!)
         long long hb[5];

@@ -17,7 +17,7 @@
 //           [output pixel][32] to LDS.  A wave's lanes cover 8 adjacent pixels x 32 channels: contiguous LDS rows.
 //   GEMM2   the 128 output pixels (one 32-pixel block per wave) x K = these 32 hidden channels x Cout (<= 64), accumulated in
 //           registers over all slices.
-//   closing the direct RESIDUAL arithmetic of hawq_conv2d (conv_igemm.hip, ConvP.gfast): per-channel requant + identity requant, no
+//   closing the direct RESIDUAL arithmetic of hawq_conv2d (conv_device.h, ConvP.gfast): per-channel requant + identity requant, no
 //           ReLU, 16-bit clamp without an identity, the next QuantAct; int32 carrier and int8 q leave as 64 / 16 bytes per lane.
 // Two workgroup barriers per slice; weights and table slices are staged through LDS one slice ahead (a few KiB per slice, from L2).
 // HBM bytes per unit = its input + its outputs (+ the identity), e.g. unit 2 (16 -> 96 -> 24, 112^2 -> 56^2, batch 128): 26 MB in,

@@ -162,14 +162,34 @@ typedef struct hawq_conv_args {
 } hawq_conv_args;
 
 int hawq_conv2d(const hawq_conv_args *args, void *stream);
+/* The tile ids 1 .. hawq_conv2d_num_tiles() are five kernel families in a fixed order, each owning consecutive ids (one table in
+ * conv_dispatch.hip; the queries below are read from it): family 0 the general tiles (conv_igemm.hip), which take any layer;
+ * 1 the 3x3/stride-1/pad-1 "band" kernels of rounds 1-3 (band_v1.hip); 2 the weight-stationary persistent kernel (band_persist.hip)
+ * for Cin == Cout == 64 (int8 in and out; REQUANT - or, round 5, single-branch RESIDUAL on uint16 residuals; NHWC or planar output)
+ * with one / two workgroups per CU; 3 (ABI 5) the hawq_conv2d_num_band2_tiles() 3x3 kernels of round 5 (band_v2.hip); 4 the
+ * hawq_conv2d_num_gemm2_tiles() streaming 1x1 kernels of round 5 (gemm_v2.hip). */
 int hawq_conv2d_num_tiles(void);
-/* The LAST hawq_conv2d_num_band_tiles() tile ids are special-purpose kernels (fast-contract layers only; hawq_conv2d refuses them
- * for any layer they are not built for): the 3x3/stride-1/pad-1 "band" kernels of rounds 1-3, then the weight-stationary persistent
- * kernel for Cin == Cout == 64 (int8 in and out; REQUANT - or, round 5, single-branch RESIDUAL on uint16 residuals; NHWC or planar output)
- * with one / two workgroups per CU, then (ABI 5) the
- * hawq_conv2d_num_band2_tiles() 3x3 kernels and the hawq_conv2d_num_gemm2_tiles() streaming 1x1 kernels of round 5.  All other ids
- * take any layer. */
+/* The LAST hawq_conv2d_num_band_tiles() tile ids - families 1 to 4 - are special-purpose kernels (fast-contract layers only;
+ * hawq_conv2d refuses them for any layer they are not built for). */
 int hawq_conv2d_num_band_tiles(void);
+/* What hawq_conv2d would do with `args`, without doing it: the argument check and the choice of kernel, no launch.  Host only - it
+ * never calls the HIP runtime, so it answers on a machine without a GPU (pointers are tested against NULL, never dereferenced).
+ * Returns what hawq_conv2d returns for a refused struct, with the same hawq_last_error text.
+ *   family, tile, index: the family (above), the 1-based tile id the launch resolves to - after the heuristic, the Cout % BN
+ *     fallback and the twin / K-sub rules of the general tiles - and its 0-based position in the family.
+ *   fn_table, fn: the slot of the family's function table.  Family 0: fn_table 0 single[epilogue][variant], 1 dual[variant],
+ *     2 tie_single[epilogue - 1][variant - 1], 3 tie_dual[variant - 1]; family 1: fn[hawq4][exact-tie][residual]; family 2:
+ *     fn[exact-tie][residual]; families 3 and 4: fn_table 0 fn[hawq4][epilogue slot][exact-tie], 1 raw[hawq4].  Unused: -1.
+ *   grid, block, lds_bytes: the launch; grid is -1 where it depends on the device (family 2 sizes it by the CU count).
+ *   stride .. out_pitch: the kernel arguments hawq_conv2d computes rather than copies (effective stride and subsampling, output
+ *     grid, folded clamp, defaulted scalar tables, requant mode, pitches); gfast and ring_bytes are 0 outside family 0. */
+typedef struct hawq_conv_choice {
+    int32_t family, tile, index;
+    int32_t fn_table, fn[3];
+    int32_t grid, block, lds_bytes;
+    int32_t stride, res_sub, Ho, Wo, M, q_lo, mq, eq, m_id_s, e_id_s, k0, ck0, gfast, in_pitch, out_pitch, ring_bytes;
+} hawq_conv_choice;
+int hawq_conv2d_choice(const hawq_conv_args *args, hawq_conv_choice *out);
 /* 1-based id of the preferred band tile that takes this layer as described (geometry, widths, epilogue,
  * fast_tables), 0 if none does: lets a caller decide whether the producer should write planar activations. */
 int hawq_conv2d_band_tile(const hawq_conv_args *args);
