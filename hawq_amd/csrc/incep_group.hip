@@ -8,252 +8,40 @@
 // (pixel block, channel block) from its index inside the member, and runs the tiled kernel's body on the member's argument block.
 // Everything it reads for that is wave-uniform: the totals and the argument blocks are kernel arguments, the member index is a
 // function of the workgroup id, so the descriptor arrives through scalar loads from the kernarg segment (no copy in scratch:
-// DESIGN.md 10).
-#include "common.h"
-
-extern "C" int hawq_incep_conv_tile_ok(const hawq_incep_conv_args *a, int tile);
+// DESIGN.md 10).  The grid (GroupMap, group_member, group_grid) is in incep_tile.h, which incep_fan.hip shares.
+#include "incep_tile.h"
 
 namespace {
 
-// The workgroup body of incep_tiled_kernel (incep_tiled.hip), line for line from its first statement after `cblock` to its last: the
-// same staging, lds_off swizzle, MFMA order and epilogue, so a workgroup writes the bytes the single launch's workgroup writes
-// (tests/test_incep_group_host.py compares the two texts).  A copy and not a shared header: as an inlined function the body costs
-// the 128 x 128 and 256 x 64 instantiations of incep_tiled.hip two VGPRs, and those kernels stay as they are.
+// The tiled kernel's workgroup body (incep_tile_body.h, the text incep_tiled_kernel includes) on one member: the same staging,
+// lds_off swizzle, MFMA order and epilogue, so a workgroup writes the bytes the single launch's workgroup writes.
 // `a`: the member (wave-uniform), Ho x Wo its output map; the workgroup computes pixels pblock .. pblock + BM - 1 and channels
 // cblock .. cblock + BN - 1 in the two LDS stages `lds`.
 template <int BM, int BN, int WPX, int WCH, int KS>
 __device__ __forceinline__ void incep_tiled_body(const hawq_incep_conv_args &a, const int Ho, const int Wo, const long long pblock,
                                                  const int cblock, char *lds) {
-    constexpr int NT = 64 * WPX * WCH * KS, RSTEP = NT / 4;
-    constexpr int WM = BM / WPX / 32, WN = BN / WCH / 32;
-    constexpr int APT = BM / RSTEP, BPT = BN / RSTEP, RPT = APT + BPT;
-    constexpr int STAGE = (BM + BN) * 64;
-    static_assert(BM % RSTEP == 0 && BN % RSTEP == 0 && BM % (32 * WPX) == 0 && BN % (32 * WCH) == 0, "tile shape");
-    static_assert(WM * WN > 1, "a wave owns more than one MFMA tile");
-    static_assert(KS == 1 || (KS == 2 && WM * WN * 16 * 64 * 4 * WPX * WCH <= 2 * STAGE), "K-split reduction must fit the stages");
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
-    const int wk = wave / (WPX * WCH), wr = wave % (WPX * WCH), wpx = wr % WPX, wch = wr / WPX;
-    const int slot = tid & 3, r0 = tid >> 2;
-    const long long P = (long long)a.N * Ho * Wo;
-    const int C16 = a.Cin >> 4, K16 = a.KH * a.KW * C16, steps = (K16 + 3) >> 2;
-    const int8_t *in = (const int8_t *)a.in, *wgt = (const int8_t *)a.wgt;
-
-    // the rows this thread stages
-    const int8_t *abase[APT];
-    int iy0[APT], ix0[APT];
-#pragma unroll
-    for (int i = 0; i < APT; ++i) {
-        const long long p = pblock + r0 + i * RSTEP;
-        abase[i] = in, iy0[i] = -(1 << 20), ix0[i] = 0;   // a row beyond P: every tap fails the bounds test below
-        if (p < P) {
-            const int ox = (int)(p % Wo), oy = (int)((p / Wo) % Ho);
-            abase[i] = in + (size_t)(p / ((long long)Wo * Ho)) * a.H * a.W * a.Cin;
-            iy0[i] = oy * a.stride - a.pad_h, ix0[i] = ox * a.stride - a.pad_w;
-        }
-    }
-    const int8_t *wrow[BPT];
-    bool wv[BPT];
-#pragma unroll
-    for (int j = 0; j < BPT; ++j) {
-        const int q = r0 + j * RSTEP, co = cblock + (q & ~31) + cperm(q & 31);
-        wv[j] = co < a.Cout;
-        wrow[j] = wgt + (wv[j] ? (size_t)co * K16 * 16 : 0);
-    }
-    // this thread's k16 unit of the step to load next
-    int k16 = slot, c16 = k16 % C16, kw = (k16 / C16) % a.KW, kh = (k16 / C16) / a.KW;
-
-    v4i rg[RPT];
-    bool ok[RPT];
-    const v4i zero = {0, 0, 0, 0};
-    // loads are unconditional (a refused element reads the first bytes of its operand) and zeroed when they are written to LDS:
-    // no branch around a load, so all RPT of them are in flight together
-    auto load = [&]() {
-        const bool kv = k16 < K16;
-#pragma unroll
-        for (int i = 0; i < APT; ++i) {
-            const int iy = iy0[i] + kh, ix = ix0[i] + kw;
-            ok[i] = kv && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            const size_t off = ok[i] ? ((size_t)iy * a.W + ix) * a.Cin + c16 * 16 : 0;
-            rg[i] = *reinterpret_cast<const v4i *>((ok[i] ? abase[i] : in) + off);
-        }
-#pragma unroll
-        for (int j = 0; j < BPT; ++j) {
-            ok[APT + j] = kv && wv[j];
-            rg[APT + j] = *reinterpret_cast<const v4i *>(wrow[j] + (ok[APT + j] ? (size_t)k16 * 16 : 0));
-        }
-        k16 += 4, c16 += 4;
-        while (c16 >= C16) {
-            c16 -= C16;
-            if (++kw == a.KW) kw = 0, ++kh;
-        }
-    };
-    auto write = [&](int stage) {
-        char *s = lds + stage * STAGE;
-#pragma unroll
-        for (int i = 0; i < RPT; ++i) {
-            *reinterpret_cast<v4i *>(s + lds_off(r0 + i * RSTEP, slot)) = ok[i] ? rg[i] : zero;
-        }
-    };
-
-    v16i acc[WM][WN];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
-
-    auto compute = [&](int stage) {
-        const char *s = lds + stage * STAGE;
-#pragma unroll
-        for (int t = 0; t < 2 / KS; ++t) {
-            const int kk = KS == 2 ? wk : t;   // the 32-byte half of the step
-            v4i af[WM], bf[WN];
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-                af[i] = *reinterpret_cast<const v4i *>(s + lds_off(wpx * 32 * WM + 32 * i + l31, 2 * kk + h));
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-                bf[j] = *reinterpret_cast<const v4i *>(s + lds_off(BM + wch * 32 * WN + 32 * j + l31, 2 * kk + h));
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bf[j], af[i], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    load();
-    write(0);
-    __syncthreads();
-    for (int s = 0; s < steps; ++s) {
-        const bool more = s + 1 < steps;
-        if (more) load();          // in flight under the MFMAs of step s
-        compute(s & 1);
-        if (more) write((s + 1) & 1);   // the other stage: last read in step s - 1, before the barrier that ended it
-        __syncthreads();
-    }
-
-    if (KS == 2) {   // every wave is past the last barrier: the stages are free
-        int *red = reinterpret_cast<int *>(lds);
-        if (wk == 1) {
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) red[(((i * WN + j) * 16 + r) * (WPX * WCH) + wr) * 64 + lane] = acc[i][j][r];
-        }
-        __syncthreads();
-        if (wk == 1) return;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] += red[(((i * WN + j) * 16 + r) * (WPX * WCH) + wr) * 64 + lane];
-    }
-
-    // acc[i][j][r] = channel cblock + 32 (wch WN + j) + 16 h + r of pixel pblock + 32 (wpx WM + i) + l31
-#pragma unroll
-    for (int i = 0; i < WM; ++i) {
-        const long long p = pblock + 32 * (wpx * WM + i) + l31;
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const int cb = cblock + 32 * (wch * WN + j) + 16 * h;
-            if (p >= P || cb >= a.Cout) continue;   // Cout % 16 == 0: the 16 channels of a lane half are all valid or all not
-            const size_t row = (size_t)p * a.ldo + a.c_off + cb;   // a multiple of 16 elements (hawq_incep_conv_tile_ok)
-            int q[16];
-            if (a.epilogue == HAWQ_INCEP_RAW) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) q[r] = acc[i][j][r] + a.bias[cb + r];
-                v4i *o = reinterpret_cast<v4i *>((int32_t *)a.out + row);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = v4i{q[4 * r], q[4 * r + 1], q[4 * r + 2], q[4 * r + 3]};
-                continue;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = cb + r;
-                int v = acc[i][j][r] + a.bias[co];
-                if (a.relu) v = max(v, 0);
-                q[r] = clampi(dyadic_rne(v, a.m[co], a.ek[co]), a.q_lo, a.q_hi);
-                if (a.epilogue == HAWQ_INCEP_REQUANT2) q[r] = clampi(dyadic_rne(q[r], a.m2, a.ek2), a.q2_lo, a.q2_hi);
-            }
-            if (a.out_bits == 16) {
-                v4i *o = reinterpret_cast<v4i *>((int16_t *)a.out + row);
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    v4i d;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) d[e] = (q[8 * r + 2 * e] & 0xffff) | (int)((unsigned)q[8 * r + 2 * e + 1] << 16);
-                    o[r] = d;
-                }
-            } else {
-                v4i d;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = (int)pack4_i8(q[4 * e], q[4 * e + 1], q[4 * e + 2], q[4 * e + 3]);
-                *reinterpret_cast<v4i *>((int8_t *)a.out + row) = d;
-            }
-        }
-    }
+#define INCEP_TILE_BLOCK
+#define INCEP_TILE_STORED(p, cb, q)
+#include "incep_tile_body.h"
+#undef INCEP_TILE_BLOCK
+#undef INCEP_TILE_STORED
 }
-
-// the tiles of hawq_incep_conv_tiled: ids 1 .. NUM_TILES, BM pixels x BN channels (incep_tiled.hip)
-enum { NUM_TILES = 4 };
-struct TileShape {
-    int bm, bn;
-};
-const TileShape kTiles[NUM_TILES + 1] = {{64, 64}, {128, 128}, {256, 64}, {128, 64}, {64, 32}};
-
-// what the host works out per member: end = workgroups of members 0 .. i (INT32_MAX beyond n), npb = pixel blocks, Ho x Wo = output map
-struct GroupMap {
-    int32_t end[HAWQ_INCEP_GROUP_MAX], npb[HAWQ_INCEP_GROUP_MAX], Ho[HAWQ_INCEP_GROUP_MAX], Wo[HAWQ_INCEP_GROUP_MAX];
-};
 
 template <int BM, int BN, int WPX, int WCH, int KS>
 __global__ __launch_bounds__(64 * WPX * WCH * KS) void incep_group_kernel(hawq_incep_group_args g, GroupMap mp) {
-    const int bid = blockIdx.x;
-    int mi = 0, first = 0;   // the member and its first workgroup
-#pragma unroll
-    for (int j = 0; j < HAWQ_INCEP_GROUP_MAX - 1; ++j) {
-        if (bid >= mp.end[j]) mi = j + 1, first = mp.end[j];
-    }
-    const int local = bid - first, npb = mp.npb[mi];
+    const GroupMember m = group_member(mp, blockIdx.x);
     __shared__ __attribute__((aligned(16))) char lds[2 * (BM + BN) * 64];
-    incep_tiled_body<BM, BN, WPX, WCH, KS>(g.conv[mi], mp.Ho[mi], mp.Wo[mi], (long long)(local % npb) * BM, (local / npb) * BN, lds);
+    incep_tiled_body<BM, BN, WPX, WCH, KS>(g.conv[m.mi], mp.Ho[m.mi], mp.Wo[m.mi], (long long)(m.local % m.npb) * BM, (m.local / m.npb) * BN, lds);
 }
 
-struct Span {
-    uintptr_t lo, hi;   // bytes [lo, hi)
-};
-bool meet(const Span &x, const Span &y) { return x.lo < y.hi && y.lo < x.hi; }
-
-// why tile `tile` does not run group `g` in one launch (NULL: it does, and `mp` / `total` describe the grid).  No pointer is dereferenced.
-const char *group_refusal(const hawq_incep_group_args *g, int tile, GroupMap *mp, long long *total, int *who) {
+// why tile `tile` does not run group `g` in one launch (NULL: it does, and `gg` describes the grid).  No pointer is dereferenced.
+const char *group_refusal(const hawq_incep_group_args *g, int tile, GroupGrid *gg, int *who) {
     *who = -1;
     if (!g) return "null group";
     if (g->n < 1 || g->n > HAWQ_INCEP_GROUP_MAX) return "a group has 1 .. 8 members";
     if (tile < 1 || tile > NUM_TILES) return "no such tile (a group runs on one of the ids 1 .. 4)";
-    const int bm = kTiles[tile].bm, bn = kTiles[tile].bn;
-    Span in[HAWQ_INCEP_GROUP_MAX], out[HAWQ_INCEP_GROUP_MAX];
-    long long wgs = 0;
-    for (int i = 0; i < g->n; ++i) {
-        const hawq_incep_conv_args *a = &g->conv[i];
-        *who = i;
-        if (!hawq_incep_conv_tile_ok(a, tile)) return "the tile refuses this member (hawq_incep_conv_tile_ok)";
-        const int Ho = (a->H + 2 * a->pad_h - a->KH) / a->stride + 1, Wo = (a->W + 2 * a->pad_w - a->KW) / a->stride + 1;
-        const long long P = (long long)a->N * Ho * Wo, npb = (P + bm - 1) / bm;   // npb < 2^31 (hawq_incep_conv_tile_ok)
-        wgs += npb * ((a->Cout + bn - 1) / bn);
-        if (wgs >= (1ll << 31)) return "too many workgroups";
-        mp->end[i] = (int32_t)wgs, mp->npb[i] = (int32_t)npb, mp->Ho[i] = Ho, mp->Wo[i] = Wo;
-        const size_t es = a->epilogue == HAWQ_INCEP_RAW ? 4 : (size_t)a->out_bits / 8;
-        in[i].lo = (uintptr_t)a->in, in[i].hi = in[i].lo + (size_t)a->N * a->H * a->W * a->Cin;
-        out[i].lo = (uintptr_t)a->out + (size_t)a->c_off * es;
-        out[i].hi = (uintptr_t)a->out + ((size_t)(P - 1) * a->ldo + a->c_off + a->Cout) * es;
-    }
-    for (int i = g->n; i < HAWQ_INCEP_GROUP_MAX; ++i) mp->end[i] = INT32_MAX, mp->npb[i] = 1, mp->Ho[i] = mp->Wo[i] = 0;
-    *total = wgs;
+    if (const char *why = group_grid(g, tile, gg, who)) return why;
+    const Span *in = gg->in, *out = gg->out;
     for (int i = 0; i < g->n; ++i) {
         const hawq_incep_conv_args *a = &g->conv[i];
         *who = i;
@@ -271,33 +59,25 @@ const char *group_refusal(const hawq_incep_group_args *g, int tile, GroupMap *mp
     return nullptr;
 }
 
-template <int BM, int BN, int WPX, int WCH, int KS>
-void launch(const hawq_incep_group_args *g, const GroupMap &mp, long long total, hipStream_t stream) {
-    hipLaunchKernelGGL((incep_group_kernel<BM, BN, WPX, WCH, KS>), dim3((unsigned)total), dim3(64 * WPX * WCH * KS), 0, stream, *g, mp);
+template <class T>
+void launch(const hawq_incep_group_args *g, const GroupGrid &gg, hipStream_t stream) {
+    hipLaunchKernelGGL((incep_group_kernel<T::BM, T::BN, T::WPX, T::WCH, T::KS>), dim3((unsigned)gg.total), dim3(T::NT), 0, stream, *g, gg.mp);
 }
 
 }  // namespace
 
 extern "C" int hawq_incep_conv_group_ok(const hawq_incep_group_args *g, int tile) {
-    GroupMap mp;
-    long long total;
+    GroupGrid gg;
     int who;
-    return group_refusal(g, tile, &mp, &total, &who) == nullptr;
+    return group_refusal(g, tile, &gg, &who) == nullptr;
 }
 
 extern "C" int hawq_incep_conv_group(const hawq_incep_group_args *g, int tile, void *stream) {
-    GroupMap mp;
-    long long total = 0;
+    GroupGrid gg;
     int who;
-    const char *why = group_refusal(g, tile, &mp, &total, &who);
+    const char *why = group_refusal(g, tile, &gg, &who);
     HAWQ_REQUIRE(!why, "hawq_incep_conv_group: tile %d refuses the group (member %d): %s", tile, who, why);
-    hipStream_t s = (hipStream_t)stream;
-    switch (tile) {   // the instantiations of hawq_incep_conv_tiled
-        case 1: launch<128, 128, 2, 2, 1>(g, mp, total, s); break;
-        case 2: launch<256, 64, 4, 1, 1>(g, mp, total, s); break;
-        case 3: launch<128, 64, 2, 2, 1>(g, mp, total, s); break;
-        default: launch<64, 32, 1, 1, 2>(g, mp, total, s); break;
-    }
+    for_tile(tile, [&](auto t) { launch<decltype(t)>(g, gg, (hipStream_t)stream); });
     HAWQ_CHECK_HIP(hipGetLastError());
     return 0;
 }

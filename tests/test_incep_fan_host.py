@@ -80,23 +80,6 @@ def test_structs_match_the_header_layout(tmp_path):
     assert C.sizeof(_lib.IncepGroupArgs) + 128 + 8 * C.sizeof(_lib.IncepFan) == 2312 <= 4096
 
 
-def test_the_kernel_body_is_the_group_kernels_text_plus_the_fan_loop():
-    """incep_fan.hip carries incep_group.hip's copy of the tiled body; the only differences are the signature's extra argument and
-    the loop over the fan outputs at the end of the epilogue"""
-    def body(name):
-        lines = [l.strip() for l in open(os.path.join(ROOT, "hawq_amd", "csrc", name)).read().split("\n")]
-        lo = next(i for i, l in enumerate(lines) if l.startswith("constexpr int NT ="))
-        hi = next(i for i, l in enumerate(lines) if l.startswith("// the tiles of hawq_incep_conv_tiled"))
-        return [l for l in lines[lo:hi] if l]
-    grp, fan = body("incep_group.hip"), body("incep_fan.hip")
-    at = next(i for i, l in enumerate(fan) if l.startswith("// the fan:"))
-    loop = fan[at:at + 14]
-    assert fan[:at] + fan[at + 14:] == grp and len(grp) > 120
-    assert loop[1] == "#pragma unroll 1" and loop[2] == "for (int t = 0; t < fn.n; ++t) {" and loop[-1] == "}"
-    assert sum("dyadic_rne(q[4 * e + u], f.m, f.ek), f.lo, f.hi)" in l for l in loop) == 1
-    assert sum("f.out + (size_t)p * f.ldo + f.c_off + cb" in l for l in loop) == 1
-
-
 def test_accepts_groups_of_one_and_three_with_fans_of_0_2_and_4(lib):
     fab = Fab()
     one = concat(fab, 256, [(64, 64)], 35, 35, 192)

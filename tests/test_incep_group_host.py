@@ -92,24 +92,6 @@ def test_struct_size():
     assert _lib.IncepGroupArgs.conv.offset == 8
 
 
-def test_the_kernel_body_is_the_tiled_kernels_text():
-    """incep_group.hip carries a copy of incep_tiled_kernel's body: every statement from the tile constants to the epilogue's last
-    brace is the same text, apart from the three lines that say where the LDS and the workgroup's pixel / channel block come from"""
-    def body(name, end):
-        lines = [l.strip() for l in open(os.path.join(ROOT, "hawq_amd", "csrc", name)).read().split("\n")]
-        lo = next(i for i, l in enumerate(lines) if l.startswith("constexpr int NT ="))
-        hi = next(i for i, l in enumerate(lines) if l.startswith(end))
-        got = [l for l in lines[lo:hi] if l]
-        assert got[-1] == "}"
-        return got[:-1]
-    own = ("__shared__ __attribute__((aligned(16))) char lds[2 * STAGE];", "const long long pblock = (long long)blockIdx.x * BM;",
-           "const int cblock = blockIdx.y * BN;")
-    tiled = body("incep_tiled.hip", "// tile ids 1 .. NUM_TILES")
-    assert sum(l in own for l in tiled) == 3
-    assert [l for l in tiled if l not in own] == body("incep_group.hip", "// the tiles of hawq_incep_conv_tiled")
-    assert len(tiled) > 120
-
-
 def test_accepts_level_1_of_every_unit_type_on_every_tile_its_members_accept(lib):
     for kind, ms in levels_1(Fab()).items():
         assert len(ms) == (4 if kind in "ABC" else 2)

@@ -55,6 +55,26 @@ def test_entry_points_are_declared_and_the_abi_is_unchanged(lib):
     assert lib.hawq_incep_conv_num_tiles() >= 3
 
 
+def test_the_workgroup_body_and_the_tile_table_are_written_once():
+    """the tiled, the grouped and the fan-out kernels share one workgroup body (incep_tile_body.h, included as text by each), one tile
+    table with one dispatch over it and one layout of a group's grid (incep_tile.h): each is written once across the five files"""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hawq_amd", "csrc")
+    kernels = ("incep_tiled.hip", "incep_group.hip", "incep_fan.hip")
+    text = {name: open(os.path.join(csrc, name)).read() for name in ("incep_tile.h", "incep_tile_body.h") + kernels}
+
+    def where(what):
+        return {name: len(re.findall(what, t)) for name, t in text.items() if re.search(what, t)}
+    for what in (r"__builtin_amdgcn_mfma_i32_32x32x32_i8", r"constexpr int NT ="):
+        assert where(what) == {"incep_tile_body.h": 1}, what
+    assert where(r'#include "incep_tile_body\.h"') == dict.fromkeys(kernels, 1)
+    for what in (r"\bkTiles\[[^\]]*\] =", r"enum \{ NUM_TILES\b", r"struct TileShape\b", r"switch \(tile\)", r"128, 128, 2, 2, 1>", r"256, 64, 4, 1, 1>",
+                 r"128, 64, 2, 2, 1>", r"64, 32, 1, 1, 2>", r"struct GroupMap\b", r"struct Span\b", r"bid >= mp\.end\[j\]", r"= INT32_MAX"):
+        assert where(what) == {"incep_tile.h": 1}, what
+    # the loop over a member's fan outputs is the fan kernel's own: its requant and its store
+    for what in (r"#pragma unroll 1\n", r"dyadic_rne\(q\[4 \* e \+ u\], f\.m, f\.ek\), f\.lo, f\.hi\)", r"f\.out \+ \(size_t\)p \* f\.ldo \+ f\.c_off \+ cb"):
+        assert where(what) == {"incep_fan.hip": 1}, what
+
+
 def test_tile_0_takes_every_geometry_of_the_network(lib):
     for g in GEOMETRIES:
         for epi, bits in ((_lib.INCEP_RAW, 32), (_lib.INCEP_REQUANT, 8), (_lib.INCEP_REQUANT, 16), (_lib.INCEP_REQUANT2, 16)):
