@@ -42,6 +42,12 @@ class ConvArgs(C.Structure):
     ]
 
 
+def res_sub(a) -> int:
+    """"res_sub" of a ConvArgs block (hawq_res_sub in csrc/common.h): s >= 2 when a single-branch RESIDUAL launch reads its stored residual
+    on the larger H2 x W2 map at stride2 = s, else 0."""
+    return int(a.stride2) if (a.epilogue == EPI_RESIDUAL and not a.in2 and a.res_in and a.stride2 >= 2) else 0
+
+
 class ConvChoice(C.Structure):
     """struct hawq_conv_choice (include/hawq_mi355.h): what hawq_conv2d would launch, from the host-only hawq_conv2d_choice."""
     _fields_ = [("family", i32), ("tile", i32), ("index", i32), ("fn_table", i32), ("fn", i32 * 3),
@@ -148,6 +154,7 @@ SIGNATURES = {
     "hawq_conv2d_band_tile": [C.POINTER(ConvArgs)],
     "hawq_conv2d_num_band2_tiles": [],
     "hawq_conv2d_band2_tile": [C.POINTER(ConvArgs)],
+    "hawq_conv2d_band2_sub_extent": [C.POINTER(ConvArgs), i32, i32, C.POINTER(i32)],
     "hawq_pack_w3x3_band": [vp, vp, i32, i32],
     "hawq_conv2d_num_gemm2_tiles": [],
     "hawq_conv2d_gemm2_first": [],

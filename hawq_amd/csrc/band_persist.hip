@@ -338,7 +338,7 @@ bool band_persist_applies(const hawq_conv_args *a, int) {
     const bool epi_ok = (a->epilogue == HAWQ_EPI_REQUANT && a->out_q && a->out_bits == 8) ||
                         (a->epilogue == HAWQ_EPI_RESIDUAL && a->res_in && a->res_in_bits == 16 && (!a->res_out || (a->res_out_bits == 16 && a->flags)) &&
                          !a->res_no_relu && !a->res_clamp16 && (a->res_out || a->out_q) && (!a->out_q || a->out_bits == 8));   // (round 5)
-    return a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->in2 == nullptr && a->fast_tables != 0 &&
+    return a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->out_sub < 2 && a->in2 == nullptr && a->fast_tables != 0 &&
            epi_ok && a->in_bits == 8 && a->w_bits == 8 && a->Cin == 64 &&
            a->Cout == 64 && a->ctab && band_rows * (wo + 2) <= ZP && (a->in_pitch == 0 || a->in_pitch == 64) &&
            (a->out_pitch == 0 || a->out_pitch == 64) &&

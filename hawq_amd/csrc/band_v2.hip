@@ -28,9 +28,16 @@
 //     or 32 lanes x 16 B = 512 contiguous bytes (planes).
 // One step = one filter row of one 64-channel slice (3 taps, 12 KiB of weights); W ring of WS stages, band double-buffered
 // per slice.
+// Strided-output mode (template parameter STR, hawq_conv_args.out_sub = s >= 2): the 3x3 conv of the last bottleneck of a
+// stage, whose 1x1 successor is only asked for the pixels (s y', s x').  The band holds the SOURCE pixels between the windows of the
+// tile's first and last output (b2_sub_band - the launcher's query walks every tile of a launch with the same function and refuses a
+// shape whose widest band does not fit), a lane's tap offsets and validity bits are those of its source pixel, the stores use the dense
+// output index.  Consecutive lanes then read band units s * 16 bytes apart: a 2-way conflict on the B-fragment reads for s = 2, accepted
+// (the A-fragment reads are unchanged and a quarter of the MFMAs remain).  Everything else - K loop, flags, weight stream, requant - is shared.
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "conv_dispatch.h"
@@ -54,7 +61,30 @@ struct B2P {
     unsigned in_bytes, wgt_bytes;
     int dbg;
     long long *dbgbuf;
+    // strided-output instantiations (hawq_conv_args.out_sub = s >= 2): M, Ho, Wo describe the dense OUTPUT grid [N][Ho][Wo]; `in` holds
+    // the source map [N][Hs][Ws] (Msrc pixels), output pixel (n, y', x') is the 3x3 window around source pixel (n, s y', s x')
+    int sub, Hs, Ws, Msrc;
 };
+
+// Band geometry of the strided-output mode, shared by the kernel and the launcher's applicability query.
+struct B2Sub {
+    int sub, Hs, Ws, Ho, Wo, M;   // Ho, Wo, M: the dense output grid
+};
+// index, on the source map, of the pixel at the centre of dense output pixel m's window (monotone in m)
+__host__ __device__ inline int b2_src_pixel(const B2Sub &s, int m, int *ys = nullptr, int *xs = nullptr) {
+    const int hw = s.Ho * s.Wo, n = m / hw, r = m - n * hw, yo = r / s.Wo, xo = r - yo * s.Wo;
+    if (ys) *ys = yo * s.sub;
+    if (xs) *xs = xo * s.sub;
+    return (n * s.Hs + yo * s.sub) * s.Ws + xo * s.sub;
+}
+// the band of the pixel tile [m0, m0 + bm): source pixel held by band pixel 0 (line-aligned; may be negative) and the number of band
+// pixels the taps of the tile reach (the source pixels of the first and the last output, one row and one pixel to either side)
+__host__ __device__ inline int b2_sub_band(const B2Sub &s, int m0, int bm, int *mb0, int *slast) {
+    const int mlast = (m0 + bm < s.M ? m0 + bm : s.M) - 1;
+    *mb0 = (b2_src_pixel(s, m0) - s.Ws - 1) & ~7;
+    *slast = b2_src_pixel(s, mlast);
+    return *slast + s.Ws + 1 - *mb0 + 1;
+}
 
 template <int PT_, int WM_, int NPROD_, int WS_, int BAND_PX_, int MINW_>
 struct V2Cfg {
@@ -143,8 +173,12 @@ __device__ __forceinline__ void b2_store_q(const B2P &p, const int (&w)[4], int 
 // the int32 accumulators + bias as a dense [M][Cout] tensor - what the parity tests compare with the oracle's exact sums).
 // MODE: 0 = tie-free tables, 2 = exact-tie correction on every requant (fast_tables bit 2).
 // NIB: both operands hawq4.
-template <class C, int EPI, int MODE, bool NIB>
+// STR: strided-output mode (B2P.sub): the band covers the source pixels of the tile's first to last output, a lane's nine taps are
+// those of its SOURCE pixel (row pitch Ws, validity against Hs x Ws), the epilogue stores with the dense index m.  The K loop, the flag
+// protocol, the weight stream and the requant arithmetic do not know about it.
+template <class C, int EPI, int MODE, bool NIB, bool STR = false>
 __global__ __launch_bounds__(C::NT, C::MINW) void conv3x3_v2_kernel(const B2P p) {
+    static_assert(!STR || EPI != HAWQ_EPI_RESIDUAL, "no strided RESIDUAL form: basic blocks never subsample");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const bool prof = HAWQ_DBG_BIT(p.dbg, 128) && p.dbgbuf;
     const long long t_entry = prof ? (long long)__builtin_readcyclecounter() : 0;
@@ -160,9 +194,18 @@ __global__ __launch_bounds__(C::NT, C::MINW) void conv3x3_v2_kernel(const B2P p)
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);   // scalar: role and k-half branches are scalar branches
     const int Wo = p.Wo;
-    const int mb0 = (m0 - Wo - 1) & ~7;                                  // global pixel held by band pixel 0 (line-aligned; may be negative)
-    const int mlast = (m0 + C::BM < p.M ? m0 + C::BM : p.M) - 1;
-    const int npg = (mlast + Wo + 1 - mb0 + 64) >> 6;                    // 64-pixel groups of a plane that are filled at all
+    int mb0, npg, msrc_all;   // global pixel held by band pixel 0 (line-aligned; may be negative); 64-pixel groups of a plane that are filled at all; pixels of `in`
+    if constexpr (STR) {
+        const B2Sub sg = {p.sub, p.Hs, p.Ws, p.Ho, p.Wo, p.M};
+        int slast;
+        npg = (b2_sub_band(sg, m0, C::BM, &mb0, &slast) + 63) >> 6;
+        msrc_all = p.Msrc;
+    } else {
+        mb0 = (m0 - Wo - 1) & ~7;
+        const int mlast = (m0 + C::BM < p.M ? m0 + C::BM : p.M) - 1;
+        npg = (mlast + Wo + 1 - mb0 + 64) >> 6;
+        msrc_all = p.M;
+    }
     const int nsteps = p.nsteps, cchunks = p.cchunks;
     char *const band = smem, *const wring = smem + C::OFF_W;
     char *const ctab_lds = C::TIGHT ? wring + (nsteps % C::WS) * C::WSTAGE : smem + C::OFF_CTAB;
@@ -178,10 +221,10 @@ __global__ __launch_bounds__(C::NT, C::MINW) void conv3x3_v2_kernel(const B2P p)
 #pragma unroll
         for (int g = 0; g < C::PG; ++g) {
             const int pix = mb0 + g * 64 + lane;
-            bvo[g] = (unsigned)pix < (unsigned)p.M ? (unsigned)pix * 16u : 0x80000000u;
+            bvo[g] = (unsigned)pix < (unsigned)msrc_all ? (unsigned)pix * 16u : 0x80000000u;
         }
         const unsigned wvo = (unsigned)(dw * 1024 + lane * 16);
-        const unsigned plane_bytes = (unsigned)p.M * 16u;
+        const unsigned plane_bytes = (unsigned)msrc_all * 16u;
         const unsigned wbase = (unsigned)tc * (unsigned)nsteps * (unsigned)C::WSTAGE;
         auto issue_band = [&](int cc) {   // returns the pieces issued
             char *dst = band + (cc & 1) * C::BAND_BYTES;
@@ -270,13 +313,20 @@ __global__ __launch_bounds__(C::NT, C::MINW) void conv3x3_v2_kernel(const B2P p)
     for (int q = 0; q < C::PT; ++q) {
         int m = m0 + wave_m * (32 * C::PT) + q * 32 + l31;
         m = m < p.M ? m : p.M - 1;
-        const int Gr = m / Wo, x = m - Gr * Wo, y = Gr % p.Ho;
+        int x, y, ms, pitch, hmap;   // the pixel whose taps this lane reads: coordinates, index, row pitch and rows of ITS map
+        if constexpr (STR) {
+            const B2Sub sg = {p.sub, p.Hs, p.Ws, p.Ho, p.Wo, p.M};
+            ms = b2_src_pixel(sg, m, &y, &x), pitch = p.Ws, hmap = p.Hs;
+        } else {
+            const int Gr = m / Wo;
+            x = m - Gr * Wo, y = Gr % p.Ho, ms = m, pitch = Wo, hmap = p.Ho;
+        }
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
-                const bool v = (unsigned)(y + kh - 1) < (unsigned)p.Ho && (unsigned)(x + kw - 1) < (unsigned)Wo;
-                off[q][kh * 3 + kw] = v ? (unsigned)((2 * g + h) * C::PLANE + (m - mb0 + (kh - 1) * Wo + kw - 1) * 16) : (unsigned)C::ZERO_OFF;
+                const bool v = (unsigned)(y + kh - 1) < (unsigned)hmap && (unsigned)(x + kw - 1) < (unsigned)pitch;
+                off[q][kh * 3 + kw] = v ? (unsigned)((2 * g + h) * C::PLANE + (ms - mb0 + (kh - 1) * pitch + kw - 1) * 16) : (unsigned)C::ZERO_OFF;
             }
     }
     unsigned wofs[2];   // A-fragment byte offsets inside a tap tile (swizzled rows), this group's k-half
@@ -534,15 +584,41 @@ __global__ __launch_bounds__(C::NT, C::MINW) void conv3x3_v2_kernel(const B2P p)
 // 12.4 us on the 14 x 14 layer, profiles/r05_band_v2.md.  Not instantiated.)
 using V128 = V2Cfg<2, 2, 2, 4, 256, 3>;    // 128 px x 64 ch: 4 MFMA waves (64 x 64 each, 2 k-halves) + 2 producers, 80 KiB: two workgroups per CU
 using V256 = V2Cfg<2, 4, 4, 5, 384, 3>;    // 256 px x 64 ch: 8 MFMA waves + 4 producers, 5-stage ring, 109 KiB
+// The strided twins (hawq_conv_args.out_sub): a tile id runs the twin of its config.  The band of a strided tile spans ~4x the pixels
+// per output: 128 outputs reach ~730 band pixels on a 56-wide map, ~650 on a 28-wide one, ~580 on a 14-wide one (2.6 images).
+using S128 = V2Cfg<2, 2, 2, 4, 768, 3>;    // 128 outputs x 64 ch: the waves of V128 over a 768-pixel band, 145 KiB: one workgroup per CU
+using S64 = V2Cfg<2, 1, 2, 4, 512, 3>;     // 64 outputs x 64 ch: 2 MFMA waves + 2 producers, 113 KiB: twice the workgroups on the 14 x 14 / 7 x 7 grids
 constexpr int NUM_V2 = 2;
+static_assert(S128::LDS_BYTES <= 160 * 1024 && S64::LDS_BYTES <= 160 * 1024, "LDS");
 
 typedef void (*V2Fn)(const B2P);
-struct V2Info { V2Fn fn[2][2][2]; V2Fn raw[2]; int bm, band_px, lds, nt, tight; };   // fn[hawq4][residual][exact-tie]; raw[hawq4]
+struct V2Sub { V2Fn fn[2][2]; V2Fn raw[2]; int bm, band_px, lds, nt; };                 // the strided twin: fn[hawq4][exact-tie]; raw[hawq4]
+struct V2Info { V2Fn fn[2][2][2]; V2Fn raw[2]; int bm, band_px, lds, nt, tight; V2Sub sub; };   // fn[hawq4][residual][exact-tie]; raw[hawq4]
+#define V2_SUB(CFG) {{{conv3x3_v2_kernel<CFG, HAWQ_EPI_REQUANT, 0, false, true>, conv3x3_v2_kernel<CFG, HAWQ_EPI_REQUANT, 2, false, true>}, \
+                      {conv3x3_v2_kernel<CFG, HAWQ_EPI_REQUANT, 0, true, true>, conv3x3_v2_kernel<CFG, HAWQ_EPI_REQUANT, 2, true, true>}}, \
+                     {conv3x3_v2_kernel<CFG, HAWQ_EPI_RAW, 0, false, true>, conv3x3_v2_kernel<CFG, HAWQ_EPI_RAW, 0, true, true>}, \
+                     CFG::BM, CFG::BAND_PX, CFG::LDS_BYTES, CFG::NT}
 #define V2_FNS(CFG, N) {{conv3x3_v2_kernel<CFG, HAWQ_EPI_REQUANT, 0, N>, conv3x3_v2_kernel<CFG, HAWQ_EPI_REQUANT, 2, N>}, \
                         {conv3x3_v2_kernel<CFG, HAWQ_EPI_RESIDUAL, 0, N>, conv3x3_v2_kernel<CFG, HAWQ_EPI_RESIDUAL, 2, N>}}
-#define V2_ENTRY(CFG) {{V2_FNS(CFG, false), V2_FNS(CFG, true)}, {conv3x3_v2_kernel<CFG, HAWQ_EPI_RAW, 0, false>, conv3x3_v2_kernel<CFG, HAWQ_EPI_RAW, 0, true>}, \
-                       CFG::BM, CFG::BAND_PX, CFG::LDS_BYTES, CFG::NT, CFG::TIGHT}
-const V2Info kV2[NUM_V2] = {V2_ENTRY(V128), V2_ENTRY(V256)};
+#define V2_ENTRY(CFG, SUB) {{V2_FNS(CFG, false), V2_FNS(CFG, true)}, {conv3x3_v2_kernel<CFG, HAWQ_EPI_RAW, 0, false>, conv3x3_v2_kernel<CFG, HAWQ_EPI_RAW, 0, true>}, \
+                            CFG::BM, CFG::BAND_PX, CFG::LDS_BYTES, CFG::NT, CFG::TIGHT, V2_SUB(SUB)}
+const V2Info kV2[NUM_V2] = {V2_ENTRY(V128, S128), V2_ENTRY(V256, S64)};
+
+B2Sub sub_geometry(const hawq_conv_args *a) {
+    const int s = a->out_sub, ho = (a->H - 1) / s + 1, wo = (a->W - 1) / s + 1;
+    return B2Sub{s, a->H, a->W, ho, wo, a->N * ho * wo};
+}
+// the largest band any pixel tile of a strided launch needs, in pixels (b2_sub_band: what the kernel fills)
+// (band_v2_applies runs on every hawq_conv2d call: the walk over all tiles is kept for the geometry asked last, per thread)
+int sub_max_band(const B2Sub &g, int bm) {
+    struct Last { B2Sub g; int bm, worst; };
+    static thread_local Last last = {{0, 0, 0, 0, 0, 0}, 0, 0};
+    if (last.bm == bm && last.g.sub == g.sub && last.g.Hs == g.Hs && last.g.Ws == g.Ws && last.g.M == g.M) return last.worst;
+    int worst = 0, mb0, slast;
+    for (int m0 = 0; m0 < g.M; m0 += bm) worst = std::max(worst, b2_sub_band(g, m0, bm, &mb0, &slast));
+    last = Last{g, bm, worst};
+    return worst;
+}
 
 }  // namespace
 
@@ -569,8 +645,12 @@ extern "C" int hawq_pack_w3x3_band(const int8_t *src, int8_t *dst, int32_t Cout,
 bool band_v2_applies(const hawq_conv_args *a, int v) {
     if (v < 0 || v >= NUM_V2) return false;
     const V2Info &vi = kV2[v];
-    const long long M = (long long)a->N * a->H * a->W;
-    const int band_len = vi.bm + 2 * a->W + 2 + 7;   // pixels m0 - Wo - 1 .. m0 + BM + Wo, start rounded down to a line
+    const long long M = (long long)a->N * a->H * a->W;   // pixels of `in`
+    const bool sub = a->out_sub >= 2;
+    if (sub && (a->out_planar || a->epilogue == HAWQ_EPI_RESIDUAL || M >= (1ll << 27))) return false;
+    // pixels m0 - Wo - 1 .. m0 + BM + Wo, start rounded down to a line; strided: the widest band of any tile of this very launch
+    const int band_len = sub ? sub_max_band(sub_geometry(a), vi.sub.bm) : vi.bm + 2 * a->W + 2 + 7;
+    const int band_px = sub ? vi.sub.band_px : vi.band_px;
     const bool qout_ok = a->out_bits == 8 || (a->out_bits == 4 && a->q_lo >= 0 && a->q_hi <= 15 && a->Cout % 32 == 0);
     const bool raw = a->epilogue == HAWQ_EPI_RAW;
     const bool epi_ok = (raw && a->out_acc && a->bias) ||
@@ -582,12 +662,32 @@ bool band_v2_applies(const hawq_conv_args *a, int v) {
     return a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->in2 == nullptr && (raw || (a->fast_tables != 0 && a->ctab)) && a->wgt_band != nullptr &&
            a->in_planar == 1 && epi_ok && ((a->in_bits == 8 && a->w_bits == 8) || (nib && a->Cin % 128 == 0)) &&
            (a->in_pitch == 0 || a->in_pitch == rowb) && (a->out_pitch == 0 || a->out_pitch == a->Cout) &&
-           band_len <= vi.band_px - 4 && rowb / 64 * 3 >= 6 && M * rowb < (1ll << 31) && (long long)a->Cout * rowb * 9 < (1ll << 31);
+           band_len <= band_px - 4 && rowb / 64 * 3 >= 6 && M * rowb < (1ll << 31) && (long long)a->Cout * rowb * 9 < (1ll << 31);
+}
+
+// The band of pixel tile `tile` of the strided launch `a` on band_v2 kernel `index` (0-based), as the kernel itself works it out
+// (b2_sub_band): out = {first band pixel on the source map, band pixels reached, band pixels the kernel's LDS stage holds, pixel tiles of
+// the launch, outputs per tile}.  Host only; non-zero for a launch without out_sub, a bad index or a bad tile.
+extern "C" int hawq_conv2d_band2_sub_extent(const hawq_conv_args *a, int32_t index, int32_t tile, int32_t *out) {
+    HAWQ_REQUIRE(a && out && a->out_sub >= 2 && index >= 0 && index < NUM_V2 && a->N > 0 && a->H > 0 && a->W > 0, "hawq_conv2d_band2_sub_extent: bad arguments");
+    const B2Sub g = sub_geometry(a);
+    const int bm = kV2[index].sub.bm, tiles = (g.M + bm - 1) / bm;
+    HAWQ_REQUIRE(tile >= 0 && tile < tiles, "hawq_conv2d_band2_sub_extent: tile %d of %d", tile, tiles);
+    int mb0, slast;
+    out[1] = b2_sub_band(g, tile * bm, bm, &mb0, &slast);
+    out[0] = mb0, out[2] = kV2[index].sub.band_px, out[3] = tiles, out[4] = bm;
+    return 0;
 }
 
 int band_v2_choose(const hawq_conv_args *a, const ConvForm &f, const ConvP &p, ConvChoice &c) {
     const V2Info &vi = kV2[c.tile];
     c.table = f.slot == HAWQ_EPI_RAW, c.fn[0] = a->in_bits == 4;
+    if (a->out_sub >= 2) {   // tables 2 / 3: the strided twin's fn[hawq4][exact-tie] / raw[hawq4]; p.M is the dense output grid's
+        c.table += 2;
+        if (c.table == 2) c.fn[1] = p.k0 == 2;
+        c.grid = ((p.M + vi.sub.bm - 1) / vi.sub.bm) * (p.Cout >> 6), c.block = vi.sub.nt, c.lds = vi.sub.lds;
+        return 0;
+    }
     if (!c.table) c.fn[1] = f.slot == HAWQ_EPI_RESIDUAL, c.fn[2] = p.k0 == 2;
     c.grid = ((p.M + vi.bm - 1) / vi.bm) * (p.Cout >> 6), c.block = vi.nt, c.lds = vi.lds;
     return 0;
@@ -601,6 +701,12 @@ int band_v2_launch(const hawq_conv_args *a, const ConvChoice &c, const ConvP &ar
     p.bias = a->bias, p.out_acc = a->out_acc;
     p.res_in = (const char *)a->res_in, p.res_out = (char *)a->res_out, p.flags = a->flags;
     p.M = a->N * a->H * a->W, p.Ho = a->H, p.Wo = a->W, p.Cin = a->Cin, p.Cout = a->Cout;
+    p.sub = 0, p.Hs = a->H, p.Ws = a->W, p.Msrc = p.M;
+    const bool sub = a->out_sub >= 2;
+    if (sub) {
+        const B2Sub g = sub_geometry(a);
+        p.sub = g.sub, p.Ho = g.Ho, p.Wo = g.Wo, p.M = g.M;
+    }
     const bool nib = a->in_bits == 4;
     const int rowb = nib ? a->Cin >> 1 : a->Cin;
     p.cchunks = rowb >> 6, p.nsteps = 3 * p.cchunks;
@@ -608,7 +714,7 @@ int band_v2_launch(const hawq_conv_args *a, const ConvChoice &c, const ConvP &ar
     p.q_lo = a->relu && a->q_lo < 0 ? 0 : a->q_lo, p.q_hi = a->q_hi;
     p.mq = a->mq, p.eq = a->eq, p.m_id = a->m_id_scalar, p.e_id = a->e_id_scalar;
     if (a->epilogue == HAWQ_EPI_RESIDUAL && !a->out_q) p.mq = 0, p.eq = 33;   // no next QuantAct: a harmless table
-    p.in_bytes = (unsigned)((long long)p.M * rowb), p.wgt_bytes = (unsigned)((long long)a->Cout * rowb * 9);
+    p.in_bytes = (unsigned)((long long)p.Msrc * rowb), p.wgt_bytes = (unsigned)((long long)a->Cout * rowb * 9);
     p.dbg = args.dbg;
     p.dbgbuf = conv_dbg_buffer(args.dbg);
     static const bool attrs = [] {
@@ -617,11 +723,13 @@ int band_v2_launch(const hawq_conv_args *a, const ConvChoice &c, const ConvP &ar
         {
             for (int k = 0; k < 8; ++k) good &= hipFuncSetAttribute((const void *)i.fn[k >> 2][(k >> 1) & 1][k & 1], hipFuncAttributeMaxDynamicSharedMemorySize, i.lds) == hipSuccess;
             for (int k = 0; k < 2; ++k) good &= hipFuncSetAttribute((const void *)i.raw[k], hipFuncAttributeMaxDynamicSharedMemorySize, i.lds) == hipSuccess;
+            for (int k = 0; k < 4; ++k) good &= hipFuncSetAttribute((const void *)i.sub.fn[k >> 1][k & 1], hipFuncAttributeMaxDynamicSharedMemorySize, i.sub.lds) == hipSuccess;
+            for (int k = 0; k < 2; ++k) good &= hipFuncSetAttribute((const void *)i.sub.raw[k], hipFuncAttributeMaxDynamicSharedMemorySize, i.sub.lds) == hipSuccess;
         }
         return good;
     }();
     HAWQ_REQUIRE(attrs, "hawq_conv2d: hipFuncSetAttribute failed for the round-5 3x3 kernels");
-    V2Fn fn = c.table ? vi.raw[c.fn[0]] : vi.fn[c.fn[0]][c.fn[1]][c.fn[2]];
+    V2Fn fn = c.table == 3 ? vi.sub.raw[c.fn[0]] : (c.table == 2 ? vi.sub.fn[c.fn[0]][c.fn[1]] : (c.table ? vi.raw[c.fn[0]] : vi.fn[c.fn[0]][c.fn[1]][c.fn[2]]));
     hipLaunchKernelGGL(fn, dim3(grid), dim3(c.block), c.lds, (hipStream_t)stream, p);
     HAWQ_CHECK_HIP(hipGetLastError());
     if (p.dbgbuf) {   // experiment hook (synchronises!)
@@ -629,7 +737,7 @@ int band_v2_launch(const hawq_conv_args *a, const ConvChoice &c, const ConvP &ar
         (void)hipStreamSynchronize((hipStream_t)stream);
         (void)hipMemcpy(hb, p.dbgbuf, sizeof(hb), hipMemcpyDeviceToHost);
         fprintf(stderr, "[band-v2 %d bm=%d M=%d Cin=%d Cout=%d grid=%d lds=%d] steps %lld: prologue %lld | K loop %lld | epilogue %lld cycles (wave 0 of workgroup 8); first operands %lld, exchange %lld\n",
-                v, vi.bm, p.M, p.Cin, p.Cout, grid, vi.lds, hb[3], hb[0], hb[1], hb[2], hb[4], hb[5]);
+                v, sub ? vi.sub.bm : vi.bm, p.M, p.Cin, p.Cout, grid, c.lds, hb[3], hb[0], hb[1], hb[2], hb[4], hb[5]);
     }
     return 0;
 }

@@ -5,6 +5,12 @@
 
 #include "../../include/hawq_mi355.h"
 
+// "res_sub" of a launch (hawq_mi355.h, at hawq_conv_args.H2): a single-branch RESIDUAL launch whose stored residual lives on the larger H2 x W2
+// map and is read at stride2; 0 for every other launch (the three fields belong to the second branch, or are ignored)
+static inline int hawq_res_sub(const hawq_conv_args &a) {
+    return (a.epilogue == HAWQ_EPI_RESIDUAL && !a.in2 && a.res_in && a.stride2 >= 2) ? a.stride2 : 0;
+}
+
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v16i __attribute__((ext_vector_type(16)));

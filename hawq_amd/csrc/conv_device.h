@@ -56,7 +56,9 @@ struct ConvP {
     int gfast;                  // general (direct) RESIDUAL epilogue with the fast contract's arithmetic: 32-bit / signed residuals whose tables the host has proved
     int in_pitch, out_pitch;    // bytes per pixel row of `in` / channels per pixel row of out_q, res_out, res_in (hawq_conv_args, ABI 4; always > 0 here)
     int res_sub;                // hawq_conv_args.out_sub = s >= 2 (else 0): the launch is a 1x1 conv of stride s (Ho, Wo, M are the subsampled grid's) and
-                                // res_in, a tensor of the H x W source map, is read at pixel (n, s oy, s ox) of it
+                                // res_in, a tensor of the H x W source map, is read at pixel (n, s oy, s ox) of it; or res_sub (hawq_res_sub) = s: `in` is
+                                // dense over the launch's own grid and res_in alone lives on the res_H x res_W map, read at (n, s oy, s ox)
+    int res_H, res_W;           // the map res_in lives on (H x W unless res_sub says otherwise: then H2 x W2)
     int dbg;  // HAWQ_DBG ablation bits (timing experiments only): 1 = skip operand loads, 2 = skip MFMAs
     long long *dbgbuf;  // HAWQ_DBG & 128: per-phase cycle sums of workgroup 0 / wave 0 (band kernel)
 };
@@ -488,11 +490,11 @@ __device__ __forceinline__ void run_segment(v16i (&acc)[C::CT][C::PT], const uin
 
 __device__ __forceinline__ v4i ld4(const int32_t *p) { return *reinterpret_cast<const v4i *>(p); }
 
-// pixel row of res_in that output pixel `pix` (< M) adds: its own, or with out_sub its source pixel on the H x W map
+// pixel row of res_in that output pixel `pix` (< M) adds: its own, or with out_sub / res_sub its source pixel on the res_H x res_W map
 __device__ __forceinline__ size_t res_row(const ConvP &p, int pix) {
     if (p.res_sub > 1) {
         const int hw = p.Ho * p.Wo, n = pix / hw, r = pix - n * hw, oy = r / p.Wo, ox = r - oy * p.Wo;
-        return ((size_t)n * p.H + (size_t)oy * p.res_sub) * p.W + (size_t)ox * p.res_sub;
+        return ((size_t)n * p.res_H + (size_t)oy * p.res_sub) * p.res_W + (size_t)ox * p.res_sub;
     }
     return (size_t)pix;
 }

@@ -89,16 +89,26 @@ int conv_check(const hawq_conv_args *a, const char *who, ConvForm *form, ConvP *
     CHECK(a->KH > 0 && a->KW > 0 && a->stride > 0 && a->pad >= 0 && a->N > 0 && a->H > 0 && a->W > 0, "bad geometry");
     // out_sub = s >= 2: only the output pixels (n, s y', s x') of a 1x1 / stride 1 / pad 0 launch, stored densely - the 1x1 conv of stride s
     // on `in`, with res_in read at the same source pixels (ConvP.res_sub)
-    const int sub = a->out_sub >= 2 ? a->out_sub : 1;
-    CHECK(sub == 1 || (a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad == 0 && !dual && !a->res_out && res && !a->in_planar && !a->out_planar &&
-                       a->in_pitch == 0 && a->out_pitch == 0),
+    // - or of a 3x3 / stride 1 / pad 1 REQUANT / RAW launch: the 3x3 conv of stride s (pad 1 keeps pixel (s y', s x') the window's centre).
+    // res_sub (stride2 = s >= 2 without a second branch: hawq_res_sub): the same 1x1 launch on a dense small-map `in`, only res_in on the larger H2 x W2 map
+    const int sub = a->out_sub >= 2 ? a->out_sub : 1, rsub = hawq_res_sub(*a) ? hawq_res_sub(*a) : 1;
+    const bool dense_rows = !a->out_planar && a->in_pitch == 0 && a->out_pitch == 0;
+    const bool sub_1x1 = a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad == 0 && !dual && !a->res_out && res && !a->in_planar && dense_rows;
+    const bool sub_3x3 = a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && !dual && (epi == HAWQ_EPI_REQUANT || epi == HAWQ_EPI_RAW) && dense_rows;
+    CHECK(sub == 1 || sub_1x1 || sub_3x3,
           "out_sub=%d needs a 1x1 / stride 1 / pad 0 single-branch RESIDUAL launch without res_out, dense NHWC rows", a->out_sub);
+    CHECK(rsub == 1 || (sub == 1 && sub_1x1 && (a->H2 - 1) / rsub + 1 == a->H && (a->W2 - 1) / rsub + 1 == a->W),
+          "res_sub (stride2 without in2)=%d needs a 1x1 / stride 1 / pad 0 single-branch RESIDUAL launch without res_out and without out_sub, dense NHWC rows, and a "
+          "H2 x W2 = %d x %d map whose pixels (s y, s x) are this launch's %d x %d", a->stride2, a->H2, a->W2, a->H, a->W);
     ConvP &p = *pp;
     p = ConvP{};
     p.in = (const uint8_t *)a->in, p.wgt = (const uint8_t *)a->wgt, p.bias = a->bias;
     p.N = a->N, p.H = a->H, p.W = a->W, p.Cin = a->Cin, p.Cout = a->Cout;
     p.KH = a->KH, p.KW = a->KW, p.stride = a->stride * sub, p.pad = a->pad;
-    p.res_sub = sub > 1 ? sub : 0;
+    // where res_in is read: at the source pixel of a subsampled 1x1 launch (its own H x W map), or on the larger map of a res_sub launch
+    p.res_sub = (sub > 1 && sub_1x1) ? sub : (rsub > 1 ? rsub : 0);
+    p.res_H = rsub > 1 ? a->H2 : a->H, p.res_W = rsub > 1 ? a->W2 : a->W;
+    CHECK((long long)a->N * p.res_H * p.res_W < (1ll << 30), "problem too large");
     p.Ho = (a->H + 2 * a->pad - a->KH) / p.stride + 1;
     p.Wo = (a->W + 2 * a->pad - a->KW) / p.stride + 1;
     CHECK(p.Ho > 0 && p.Wo > 0, "empty output");

@@ -136,6 +136,7 @@ int splitk_plan(const hawq_conv_args *a, int slices, SplitPlan &sp) {
     HAWQ_REQUIRE(a->n_valid == 0 && (a->in_pitch == 0 || a->in_pitch == a->Cin) && (a->out_pitch == 0 || a->out_pitch == a->Cout),
                  "hawq_conv2d_splitk: n_valid / in_pitch / out_pitch are not supported");
     HAWQ_REQUIRE(a->out_sub < 2, "hawq_conv2d_splitk: out_sub is not supported");
+    HAWQ_REQUIRE(hawq_res_sub(*a) < 2, "hawq_conv2d_splitk: res_sub is not supported");
     const int epi = a->epilogue;
     HAWQ_REQUIRE(epi == HAWQ_EPI_RAW || epi == HAWQ_EPI_REQUANT || epi == HAWQ_EPI_RESIDUAL, "hawq_conv2d_splitk: RAW, REQUANT or RESIDUAL epilogue only");
     HAWQ_REQUIRE(epi == HAWQ_EPI_RAW || !a->out_q || a->out_bits == 8, "hawq_conv2d_splitk: out_bits must be 8");

@@ -464,7 +464,7 @@ bool dual_branch_fits(const hawq_conv_args &e) {
 // variant index (into kER) for this pair, or -1.  `tile` 0 = default, 1.. = the variants that take channel count C in table order
 int er_variant(const hawq_expand_reduce_args *a) {
     const hawq_conv_args &e = a->expand, &r = a->reduce;
-    if (!conv_is_1x1_int8_fast(e, true) || !conv_is_1x1_int8_fast(r) || e.out_sub >= 2 || r.out_sub >= 2) return -1;   // (out_sub: the expand conv alone, fused_wp.hip)
+    if (!conv_is_1x1_int8_fast(e, true) || !conv_is_1x1_int8_fast(r) || e.out_sub >= 2 || r.out_sub >= 2 || hawq_res_sub(e) >= 2 || hawq_res_sub(r) >= 2) return -1;   // (out_sub: the expand conv alone, fused_wp.hip)
     const bool dual = e.in2 != nullptr;
     if (dual && !dual_branch_fits(e)) return -1;
     if (e.epilogue != HAWQ_EPI_RESIDUAL || r.epilogue != HAWQ_EPI_REQUANT) return -1;

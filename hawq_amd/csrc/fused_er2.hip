@@ -408,7 +408,7 @@ bool e2_conv_ok(const hawq_conv_args &a) {
 // index into kE2 of the nth (1-based) variant that takes this pair, or -1
 int e2_variant(const hawq_expand_reduce_args *a, int nth) {
     const hawq_conv_args &e = a->expand, &r = a->reduce;
-    if (!r.wgt || !e2_conv_ok(e) || !e2_conv_ok(r) || e.out_sub >= 2 || r.out_sub >= 2) return -1;
+    if (!r.wgt || !e2_conv_ok(e) || !e2_conv_ok(r) || e.out_sub >= 2 || r.out_sub >= 2 || hawq_res_sub(e) >= 2 || hawq_res_sub(r) >= 2) return -1;
     if (e.epilogue != HAWQ_EPI_RESIDUAL || r.epilogue != HAWQ_EPI_REQUANT) return -1;
     if (!e.res_in || e.res_in_bits != 16 || !e.res_out || e.res_out_bits != 16 || !e.flags || !e.ctab || !r.ctab || !r.out_q) return -1;
     if ((r.out_bits != 8 && r.out_bits != 4) || e.out_bits != 8) return -1;

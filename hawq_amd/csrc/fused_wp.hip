@@ -45,7 +45,8 @@ struct WPP {
     int spb;             // slices per workgroup along gridDim.y (REDUCE: all of them)
     // !REDUCE, hawq_conv_args.out_sub = s >= 2: M counts the pixels (n, y', x') of the subsampled grid [N][dHW / dW][dW] - q_out is dense over
     // them -, x2 and res_in are read at pixel (n, s y', s x') of the source map [N][sHW / sW][sW].  sub <= 1: the grids are the same
-    int sub, sW, sHW, dW, dHW;
+    // xdense (res_sub, hawq_res_sub()): x2 is dense over the M pixels as q_out is; res_in alone is read on the source map
+    int sub, sW, sHW, dW, dHW, xdense;
     int32_t *flags;
     long long *dbgbuf;   // probe builds (HAWQ_ABLATE, HAWQ_DBG=128): per-phase cycle sums of wave 0 of workgroup 8
 };
@@ -131,7 +132,10 @@ __global__ __launch_bounds__(F::NT, F::MINW) void expand_wp_kernel(const WPP p) 
 #pragma unroll
     for (int k = 0; k < 4; ++k) rsrc[k] = srow(pix0 + 8 * k + (lane >> 3));
 #pragma unroll
-    for (int k = 0; k < 2; ++k) xsrc[k] = srow(pix0 + 16 * k + (lane >> 2));
+    for (int k = 0; k < 2; ++k) {
+        const int d = pix0 + 16 * k + (lane >> 2);
+        xsrc[k] = (!F::REDUCE && p.xdense) ? (unsigned)(d < p.M ? d : p.M - 1) : srow(d);
+    }
     asm volatile("" : "+v"(rsrc[0]), "+v"(rsrc[1]), "+v"(rsrc[2]), "+v"(rsrc[3]), "+v"(xsrc[0]), "+v"(xsrc[1]));
     // ---------------------------------------------------------------- LDS-DMA: every wave issues its 16 rows of each pass
     const int prow = t >> 2, pslot = t & 3;
@@ -429,7 +433,8 @@ bool wp_expand_ok(const hawq_conv_args &e) {
     return (e.in_pitch == 0 || e.in_pitch == e.Cin) && (e.out_pitch == 0 || e.out_pitch == e.Cout) && e.KH == 1 && e.KW == 1 && e.stride == 1 && e.pad == 0 && e.in_bits == 8 && e.w_bits == 8 && e.fast_tables != 0 && !e.in2 &&
            !e.in_planar && e.epilogue == HAWQ_EPI_RESIDUAL && e.res_in && e.res_in_bits == 16 && (!e.res_out || e.res_out_bits == 16) &&
            e.flags && e.ctab && e.Cout % 64 == 0 && (e.out_bits == 8 || (e.out_bits == 4 && e.q_lo >= 0 && e.q_hi <= 15)) &&   // (4: the expand conv alone writing a hawq4 block input)
-           (e.out_sub < 2 || !e.res_out);   // a subsampled launch has no dense residual to write (hawq_conv_args.out_sub)
+           (e.out_sub < 2 || !e.res_out) &&   // a subsampled launch has no dense residual to write (hawq_conv_args.out_sub)
+           (hawq_res_sub(e) < 2 || (!e.res_out && e.out_sub < 2 && (e.H2 - 1) / e.stride2 + 1 == e.H && (e.W2 - 1) / e.stride2 + 1 == e.W));   // (res_sub: the same launch on a dense x2)
 }
 
 // index into kWP of the nth (1-based) variant that takes this launch, or -1
@@ -438,7 +443,7 @@ int wp_variant(const hawq_expand_reduce_args *a, int nth) {
     if (!wp_expand_ok(e)) return -1;
     const bool reduce = r.wgt != nullptr;
     if (reduce && e.out_bits != 8) return -1;   // (a fused pair keeps the block input on chip: its storage width is moot, the caller says 8)
-    if (reduce && (e.out_sub >= 2 || r.out_sub >= 2)) return -1;   // only the expand conv alone subsamples its output grid
+    if (reduce && (e.out_sub >= 2 || r.out_sub >= 2 || hawq_res_sub(e) >= 2 || hawq_res_sub(r) >= 2)) return -1;   // only the expand conv alone subsamples its output grid
     if (reduce) {
         if (!(r.KH == 1 && r.KW == 1 && r.stride == 1 && r.pad == 0 && r.in_bits == 8 && r.w_bits == 8 && r.fast_tables != 0 && !r.in2)) return -1;
         if (r.epilogue != HAWQ_EPI_REQUANT || !r.ctab || !r.out_q || (r.out_bits != 8 && r.out_bits != 4) || !e.res_out) return -1;
@@ -476,11 +481,14 @@ int wp_launch(const hawq_expand_reduce_args *a, int nth, void *stream) {
     p.q_out = wi.reduce ? nullptr : (uint8_t *)e.out_q;
     p.q_nib = !wi.reduce && e.out_bits == 4;
     // out_sub: the grid, q_out and every store run over the subsampled pixels; the 32-bit row offsets address the source map
-    const int sub = e.out_sub >= 2 ? e.out_sub : 1, hd = (e.H - 1) / sub + 1, wd = (e.W - 1) / sub + 1;
-    const long long Msrc = (long long)e.N * e.H * e.W, M = (long long)e.N * hd * wd;
+    // res_sub: the same grid and residual addressing with the roles named from the other side - e.H x e.W is the dense grid, x2 lives on it too
+    const bool rs = hawq_res_sub(e) >= 2;
+    const int sub = rs ? e.stride2 : (e.out_sub >= 2 ? e.out_sub : 1), sh = rs ? e.H2 : e.H, sw = rs ? e.W2 : e.W;
+    const int hd = (sh - 1) / sub + 1, wd = (sw - 1) / sub + 1;
+    const long long Msrc = (long long)e.N * sh * sw, M = (long long)e.N * hd * wd;
     HAWQ_REQUIRE(M > 0 && Msrc * e.Cout * 2 < (1ll << 32), "hawq_conv_expand_reduce: bad problem size");
     p.M = (int)M, p.C3 = e.Cout;
-    p.sub = sub, p.sW = e.W, p.sHW = e.H * e.W, p.dW = wd, p.dHW = hd * wd;
+    p.sub = sub, p.sW = sw, p.sHW = sh * sw, p.dW = wd, p.dHW = hd * wd, p.xdense = rs;
     p.m_id_s = e.m_id_scalar, p.e_id_s = e.e_id_scalar, p.mq = e.mq, p.eq = e.eq, p.q_hi = e.q_hi;
     p.y_lo = wi.reduce ? (r.relu && r.q_lo < 0 ? 0 : r.q_lo) : 0, p.y_hi = wi.reduce ? r.q_hi : 0;
     p.y_planar = wi.reduce ? r.out_planar : 0;

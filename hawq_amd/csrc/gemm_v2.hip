@@ -486,7 +486,7 @@ bool gemm_v2_applies(const hawq_conv_args *a, int v) {
                          !a->res_no_relu && !a->res_clamp16 && (a->res_out || a->out_q) && (!a->out_q || qout_ok));
     const bool dual_ok = !dual || (a->wgt2_k128 && a->ctab_id && a->in2_bits == a->in_bits && a->w2_bits == a->w_bits && rowb2 % 128 == 0 &&
                                    (long long)a->N * a->H2 * a->W2 * rowb2 < (1ll << 31) && (long long)a->Cout * rowb2 < (1ll << 31));
-    return a->KH == 1 && a->KW == 1 && a->stride >= 1 && a->pad == 0 && a->out_sub < 2 && (raw || (a->fast_tables != 0 && a->ctab)) && a->wgt_k128 != nullptr && !a->in_planar && epi_ok && dual_ok &&
+    return a->KH == 1 && a->KW == 1 && a->stride >= 1 && a->pad == 0 && a->out_sub < 2 && hawq_res_sub(*a) < 2 && (raw || (a->fast_tables != 0 && a->ctab)) && a->wgt_k128 != nullptr && !a->in_planar && epi_ok && dual_ok &&
            ((a->in_bits == 8 && a->w_bits == 8) || nib) && rowb % 128 == 0 && a->Cout % gi.bn == 0 && (a->in_pitch == 0 || a->in_pitch == rowb) &&
            (a->out_pitch == 0 || a->out_pitch == a->Cout) && Min * rowb < (1ll << 31) && (long long)a->Cout * rowb < (1ll << 31) && M * a->Cout < (1ll << 31);
 }

@@ -58,6 +58,19 @@ def out_sub_extent(n: int, s: int) -> int:
     return (n - 1) // s + 1
 
 
+def conv2_sub_stride(sub_out: int, convs) -> int:
+    """Stride s on whose grid the MIDDLE conv of a stage-final unit may be evaluated, 0 if it has to run on every pixel.
+    `sub_out`: out_sub_stride() of the unit's readers; `convs`: (kh, kw, stride, pad) of the unit's convs in order.
+    A bottleneck whose last conv is 1x1 / stride 1 / pad 0 and whose middle conv is 3x3 / stride 1 / pad 1: the last conv's output
+    at (s y, s x) needs the middle conv's output at (s y, s x) only, so the 3x3 launch takes out_sub = s and the last conv runs on
+    the small grid, reading only its residual on the full map ("res_sub": hawq_conv_args.stride2 / H2 / W2 without a second branch).  The first conv feeds the 3x3 windows and
+    keeps every pixel.  Basic blocks (two 3x3 convs) and units with the stride on conv2 get 0."""
+    convs = list(convs)
+    if sub_out < 2 or len(convs) != 3 or tuple(convs[1]) != (3, 3, 1, 1) or tuple(convs[2]) != (1, 1, 1, 0):
+        return 0
+    return int(sub_out)
+
+
 def _no_preshift(ek) -> bool:
     """True if no entry of a device table (e | k << 8) carries a pre-shift k."""
     return bool((np.asarray(ek, dtype=np.int64) >> 8 == 0).all())
@@ -439,7 +452,7 @@ class IntegerEngine(GraphRunner):
         raise NotImplementedError("conv inputs wider than 8 bits")
 
     # ------------------------------------------------------------------ launch list
-    def _band_takes(self, ent, N, h, w, in_bits, is_last, u) -> bool:
+    def _band_takes(self, ent, N, h, w, in_bits, is_last, u, out_sub=0) -> bool:
         """Would a 3x3 band kernel take the conv `ent` fed with an [N,h,w] map of `in_bits`-bit activations?  Asked
         of the library itself (hawq_conv2d_band_tile) with the launch's geometry, widths and epilogue class."""
         c = ent['conv']
@@ -454,6 +467,7 @@ class IntegerEngine(GraphRunner):
             q.epilogue, q.res_in, q.res_in_bits, q.res_out_bits = _lib.EPI_RESIDUAL, 1, 16, 16
         else:
             q.epilogue, q.out_q, q.out_bits, q.relu, q.q_lo, q.q_hi = _lib.EPI_REQUANT, 1, ent['out_bits'], 1, ent['rng'][0], ent['rng'][1]
+            q.out_sub = out_sub   # (a 3x3 launch on the next stage's grid: only the strided twins of the round-5 kernels take it)
         if _lib.load().hawq_conv2d_band_tile(C.byref(q)) != 0:
             return True
         # a layer only the round-5 kernels take (planar input, host-packed weight stream): ADVICE r5
@@ -464,9 +478,24 @@ class IntegerEngine(GraphRunner):
             q.res_out_bits, q.flags, q.res_out = 16, 1, 1
         return _lib.load().hawq_conv2d_band2_tile(C.byref(q)) != 0
 
-    def _try_fuse(self, a, u, nxt, N, ho, wo, keep):
+    def _handover(self, units, ui):
+        """(sub_out, c2_sub) of unit `ui`: the stride of the grid on which its LAST launch may be evaluated because the next unit - a
+        resize unit - reads its block input there (out_sub_stride), and the stride its 3x3 conv then already runs on (conv2_sub_stride;
+        HAWQ_NO_CONV2_SUB=1: 0, every 3x3 conv on every pixel as before - the A/B switch).  keep_acc plans and HAWQ_NO_OUT_SUB=1: (0, 0)."""
+        if ui + 1 >= len(units):
+            return 0, 0
+        u, nxt = units[ui], units[ui + 1]
+        if not nxt['resize'] or u['resize'] or self.keep_acc or os.environ.get("HAWQ_NO_OUT_SUB"):
+            return 0, 0
+        sub_out = out_sub_stride((r.kh, r.kw, r.stride, r.pad) for r in (nxt['convs'][0]['conv'], nxt['ident']))
+        if os.environ.get("HAWQ_NO_CONV2_SUB"):
+            return sub_out, 0
+        return sub_out, conv2_sub_stride(sub_out, ((e['conv'].kh, e['conv'].kw, e['conv'].stride, e['conv'].pad) for e in u['convs']))
+
+    def _try_fuse(self, a, u, nxt, N, ho, wo, keep, nxt_c2_sub=0):
         """Expand conv launch `a` of unit `u` (RESIDUAL epilogue, already filled) + reduce conv of unit `nxt`:
-        returns (ExpandReduceArgs, output tensor, out_bits, planar) or None if the library does not take the pair."""
+        returns (ExpandReduceArgs, output tensor, out_bits, planar) or None if the library does not take the pair.
+        `nxt_c2_sub`: the out_sub the 3x3 conv of `nxt`, the reader of the pair's output, will be launched with."""
         if nxt is None or nxt['resize'] or len(nxt['convs']) != 3 or not a.fast_tables:
             return None
         if int(u['name'].split('.')[0][len('stage'):]) not in self.fuse_stages:
@@ -499,7 +528,7 @@ class IntegerEngine(GraphRunner):
             return None
         out = self._alloc(N * ho * wo * c.cout * ob // 8, torch.uint8)
         r.out_q = out.data_ptr()
-        planar = self.planar and self._band_takes(nxt['convs'][1], N, ho, wo, ob, False, nxt)
+        planar = self.planar and self._band_takes(nxt['convs'][1], N, ho, wo, ob, False, nxt, nxt_c2_sub)
         r.out_planar = int(planar)
         # the same two layers as separate launches (the block input q then goes through memory)
         q = self._alloc(N * ho * wo * c.cin * nxt['a_bits'] // 8, torch.uint8)
@@ -669,6 +698,15 @@ class IntegerEngine(GraphRunner):
                 if a is None or not _lib.load().hawq_conv2d_splitk_ok(C.byref(a), v):
                     raise StalePlan(f"the library refuses split-K with {v} slices for a recorded launch")
                 self._ws.fit(a, v)
+        # a recorded tile id the library refuses for the launch as it is built now (a plan recorded before a launch changed form: the
+        # 3x3 launches that run with out_sub, which band_v1 / band_persist refuse) is stale - it is never replaced by another id here
+        probe = _lib.ConvChoice()
+        for op, t in zip(self._conv_ops, ch.tiles):
+            was, op.a.tile = op.a.tile, t
+            rc = _lib.load().hawq_conv2d_choice(C.byref(op.a), C.byref(probe))
+            op.a.tile = was
+            if rc != 0:
+                raise StalePlan(f"the library refuses tile {t} for a recorded launch ({_lib.load().hawq_last_error().decode()})")
         for op, t, v in zip(self._conv_ops, ch.tiles, ch.splitk):
             op.a.tile, op.splitk = t, v
         pair_splits = ch.splitk[len(self._conv_ops):]
@@ -815,9 +853,10 @@ class IntegerEngine(GraphRunner):
             x_in, x_bits, hin, win, x_planar = qa, u['a_bits'], h, w, False
             # sub_in = s: this unit's block input holds only the pixels (s y, s x) its readers want (the previous launch ran with out_sub = s):
             # conv1 and the identity conv walk it with stride 1
-            sub_in, sub_out = sub_out, 0
-            if nxt is not None and nxt['resize'] and not u['resize'] and not self.keep_acc and not os.environ.get("HAWQ_NO_OUT_SUB"):
-                sub_out = out_sub_stride((r.kh, r.kw, r.stride, r.pad) for r in (nxt['convs'][0]['conv'], nxt['ident']))
+            # c2_sub = s: the unit's 3x3 conv already runs on that grid, and the last conv behind it on the small map (res_sub instead of
+            # out_sub)
+            sub_in = sub_out
+            sub_out, c2_sub = self._handover(units, ui)
             for ci, ent in enumerate(u['convs']):
                 c = ent['conv']
                 c_stride = 1 if (sub_in and ci == 0) else c.stride
@@ -860,6 +899,9 @@ class IntegerEngine(GraphRunner):
                 a.in_planar = int(x_planar)
                 tap_name = f"{u['name']}.quant_convbn{ci + 1}"
                 if ci < len(u['convs']) - 1:
+                    if c2_sub and ci == 1:   # only the pixels the last conv will be asked for, stored densely
+                        a.out_sub = c2_sub
+                        ho, wo = out_sub_extent(ho, c2_sub), out_sub_extent(wo, c2_sub)
                     out = self._alloc(N * ho * wo * c.cout * ent['out_bits'] // 8, torch.uint8)
                     a.epilogue, a.relu = _lib.EPI_REQUANT, 1
                     a.out_q, a.out_bits, a.q_lo, a.q_hi = out.data_ptr(), ent['out_bits'], ent['rng'][0], ent['rng'][1]
@@ -868,7 +910,8 @@ class IntegerEngine(GraphRunner):
                     # the only reader of `out` is the next conv of this unit: if that is a 3x3 layer a band kernel
                     # takes, write channel-group planes (what the band kernel's LDS-DMA fill reads at full rate)
                     planar_next = bool(a.fast_tables) and self.planar and self._band_takes(u['convs'][ci + 1], N, ho, wo, xb_next,
-                                                                                            ci + 1 == len(u['convs']) - 1, u)
+                                                                                            ci + 1 == len(u['convs']) - 1, u,
+                                                                                            c2_sub if ci == 0 else 0)
                     a.out_planar = int(planar_next)
                 else:
                     a.epilogue = _lib.EPI_RESIDUAL
@@ -885,7 +928,10 @@ class IntegerEngine(GraphRunner):
                         a.m_id_scalar, a.e_id_scalar = u['m_id_s'], u['e_id_s']
                     need_res = (nxt is None) or (not nxt['resize'])
                     new_res = self._alloc(N * ho * wo * c.cout, rdt) if need_res else None
-                    if sub_out:   # (need_res is False: the next unit is a resize unit) only the pixels the next unit reads, stored densely
+                    if c2_sub:   # this launch already runs on the next unit's grid (its input is dense there); the residual alone is full-size
+                        a.stride2, a.H2, a.W2 = c2_sub, h, w   # (no second branch: the geometry of res_in, "res_sub")
+                        qh, qw = ho, wo
+                    elif sub_out:   # (need_res is False: the next unit is a resize unit) only the pixels the next unit reads, stored densely
                         a.out_sub = sub_out
                         qh, qw = out_sub_extent(ho, sub_out), out_sub_extent(wo, sub_out)
                     else:
@@ -903,7 +949,7 @@ class IntegerEngine(GraphRunner):
                     if ci == len(u['convs']) - 1 and u['resize']:
                         self._add_ident_tap(ops, keep, u, qa, N, h, w, ho, wo)
                 keep.append(a)
-                fz = self._try_fuse(a, u, nxt, N, ho, wo, keep) if (ci == len(u['convs']) - 1 and not self.keep_acc) else None
+                fz = self._try_fuse(a, u, nxt, N, ho, wo, keep, self._handover(units, ui + 1)[1]) if (ci == len(u['convs']) - 1 and not self.keep_acc) else None
                 if fz is None and ci == len(u['convs']) - 1 and nxt is not None:
                     new_qa = self._alloc(N * qh * qw * c.cout * nxt['a_bits'] // 8, torch.uint8)
                     a.out_q = new_qa.data_ptr()

@@ -72,6 +72,18 @@ typedef struct hawq_conv_args {
     const void *wgt2;
     const int32_t *bias2;
     int32_t H2, W2, Cin2, stride2, in2_bits, w2_bits;
+    /* Without a second branch (in2 == NULL) H2, W2 and stride2 describe the OTHER tensor the RESIDUAL epilogue adds, the stored residual: with
+       res_in != NULL and stride2 = s >= 2 ("res_sub"; 0 and 1: res_in is a tensor of this launch's own grid, as always) `in` and out_q are dense
+       [N][H][W] tensors and only res_in lives on a larger map, [N][H2][W2][Cout] with (H2 - 1) / s + 1 == H and (W2 - 1) / s + 1 == W, read at pixel
+       (n, s y, s x) - the expand conv behind a 3x3 launch that ran with out_sub = s.  Same preconditions as out_sub (1x1 / stride 1 / pad 0, RESIDUAL,
+       res_out == NULL, dense NHWC rows), which it excludes.  Taken by the general tiles and by the expand conv alone of hawq_conv_expand_reduce, and
+       refused by everything else.  Other epilogues ignore the three.
+       Why no field of its own: out_sub is pinned as the LAST field of this block - by the ctypes mirror's layout test and by recorded launch
+       lists that hold every field of every block - so three appended fields would have invalidated both; they can follow in a change that
+       re-records those.  The hazard of the reuse: single-branch RESIDUAL launches used to ignore these three fields.  A caller who fills a
+       dual-branch block and then clears in2 (keeping res_in and a stride2 >= 2) no longer gets the plain launch: it is refused unless
+       (H2 - 1) / stride2 + 1 == H and likewise for W, and with such extents res_in is addressed on the H2 x W2 map.  Zero the three fields
+       when in2 is cleared. */
     int32_t epilogue; /* HAWQ_EPI_* */
     int32_t relu;     /* apply max(.,0) to acc+bias before requantising (REQUANT only)         */
     /* requant tables of the main branch: per output channel */
@@ -157,7 +169,11 @@ typedef struct hawq_conv_args {
        densely as [N][Ho'][Wo'][Cout] (int8 or hawq4).  Needs: a 1x1 / stride 1 / pad 0 conv, single branch (in2 == NULL) and res_out == NULL (no dense
        residual is produced; the uint16 overflow flag can only be raised by the pixels that are evaluated).  Taken by hawq_conv2d's general tiles
        (RESIDUAL epilogue, 16- or 32-bit res_in, dense NHWC rows) and by the expand conv alone of hawq_conv_expand_reduce (reduce.wgt == NULL); the special-purpose
-       tile ids, hawq_conv2d_splitk and the fused pairs refuse it through their applicability queries. */
+       tile ids, hawq_conv2d_splitk and the fused pairs refuse it through their applicability queries.
+       Also taken on a 3x3 / stride 1 / pad 1 single-branch launch with the REQUANT or RAW epilogue (the second conv of a stage's last bottleneck, whose
+       1x1 successor runs on the subsampled grid): with pad 1 that is exactly the 3x3 / stride s conv on `in`, which stays the full H x W map;
+       out_q / out_acc are dense over [N][Ho'][Wo'][Cout].  NHWC rows, out_planar refused; the general tiles take it, every special-purpose 3x3 tile id and
+       hawq_conv2d_splitk refuse it through their queries. */
     int32_t out_sub;
 } hawq_conv_args;
 
@@ -179,7 +195,8 @@ int hawq_conv2d_num_band_tiles(void);
  *     fallback and the twin / K-sub rules of the general tiles - and its 0-based position in the family.
  *   fn_table, fn: the slot of the family's function table.  Family 0: fn_table 0 single[epilogue][variant], 1 dual[variant],
  *     2 tie_single[epilogue - 1][variant - 1], 3 tie_dual[variant - 1]; family 1: fn[hawq4][exact-tie][residual]; family 2:
- *     fn[exact-tie][residual]; families 3 and 4: fn_table 0 fn[hawq4][epilogue slot][exact-tie], 1 raw[hawq4].  Unused: -1.
+ *     fn[exact-tie][residual]; families 3 and 4: fn_table 0 fn[hawq4][epilogue slot][exact-tie], 1 raw[hawq4]; family 3 with
+ *     out_sub: 2 the strided twin's fn[hawq4][exact-tie], 3 its raw[hawq4].  Unused: -1.
  *   grid, block, lds_bytes: the launch; grid is -1 where it depends on the device (family 2 sizes it by the CU count).
  *   stride .. out_pitch: the kernel arguments hawq_conv2d computes rather than copies (effective stride and subsampling, output
  *     grid, folded clamp, defaulted scalar tables, requant mode, pitches); gfast and ring_bytes are 0 outside family 0. */
@@ -200,6 +217,13 @@ int hawq_conv2d_band_tile(const hawq_conv_args *args);
  * (dst and src are host pointers of Cout * 9 * Cin bytes; Cin = BYTES per tap row - the channel count for int8 weights, half of it for hawq4 -; Cin and Cout multiples of 64). */
 int hawq_conv2d_num_band2_tiles(void);
 int hawq_conv2d_band2_tile(const hawq_conv_args *args);
+/* A 3x3 launch with out_sub = s >= 2 runs the STRIDED TWIN of a round-5 3x3 kernel under the same tile id (128 outputs over a 768-pixel band, 64 outputs over
+ * a 512-pixel band): the band of a pixel tile covers the source pixels of its first to its last output, a row and a pixel to either side, and the query refuses
+ * every launch in which some tile's band does not fit.  hawq_conv2d_band2_sub_extent: that band for pixel tile `tile` on the `index`-th (0-based) of those
+ * kernels, from the function the kernel itself uses - out[0] first band pixel on the source map (line-aligned, may be negative), out[1] band pixels reached,
+ * out[2] band pixels an LDS stage holds (a launch fits when out[1] <= out[2] - 4 for every tile), out[3] pixel tiles of the launch, out[4] outputs per tile.
+ * Host only. */
+int hawq_conv2d_band2_sub_extent(const hawq_conv_args *args, int32_t index, int32_t tile, int32_t *out);
 int hawq_pack_w3x3_band(const int8_t *src, int8_t *dst, int32_t Cout, int32_t Cin);
 /* ABI 5: the LAST hawq_conv2d_num_gemm2_tiles() tile ids are the round-5 streaming
  * 1x1 kernels (need args->wgt_k128 - and wgt2_k128 with a second branch -, NHWC input, fast_tables; REQUANT, RESIDUAL on uint16
