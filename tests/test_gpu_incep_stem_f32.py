@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.guard import dev, out_buf
 from tests.test_gpu_inception_network import _load_reference_state
 
 pytestmark = pytest.mark.gpu
@@ -115,21 +116,22 @@ def _run_both(x, inv, in_lo, in_hi, w, b, m, ek, cout, ldo, c_off, relu, qrange)
     N, _, Hh, Ww = x.shape
     Ho, Wo = (Hh - 3) // 2 + 1, (Ww - 3) // 2 + 1
     s = torch.cuda.current_stream().cuda_stream
-    xd = torch.from_numpy(x.copy()).cuda()
-    bd, md, ekd = (torch.from_numpy(t.copy()).cuda() for t in (b, m, ek))
+    # (buffers come from the guard arena when the calling test has made one current: tests/test_gpu_contract_edges.py)
+    xd = dev(x.copy())
+    bd, md, ekd = (dev(t.copy()) for t in (b, m, ek))
     # the fused launch
-    wt = torch.from_numpy(pack_stem_u8_weights(w, cout)).cuda()
-    out = torch.full((N * Ho * Wo * ldo,), SENTINEL, dtype=torch.int8, device="cuda")
+    wt = dev(pack_stem_u8_weights(w, cout))
+    out = out_buf(N * Ho * Wo * ldo, torch.int8, SENTINEL)
     a = _conv1_args(N, Hh, Ww, 3, wt, bd, md, ekd, out, cout, ldo, c_off, relu, qrange)
     assert lib.load().hawq_incep_stem_f32_ok(xd.data_ptr(), inv, in_lo, in_hi, C.byref(a)) == 1
     lib.call("hawq_incep_stem_f32", xd.data_ptr(), inv, in_lo, in_hi, C.byref(a), s)
     # the default plan's three launches: fake-quantise, NCHW -> NHWC int8 padded to 16 channels, hawq_incep_conv at K = 9 x 16
-    xq = torch.empty_like(xd)
-    x0 = torch.full((N * Hh * Ww * 16,), SENTINEL, dtype=torch.int8, device="cuda")
+    xq = out_buf(tuple(xd.shape), torch.float32, None)
+    x0 = out_buf(N * Hh * Ww * 16, torch.int8, SENTINEL)
     w16 = np.zeros((cout, 3, 3, 16), np.int8)
     w16[..., :3] = w.transpose(0, 2, 3, 1)
-    w16d = torch.from_numpy(w16).cuda()
-    base = torch.full_like(out, SENTINEL)
+    w16d = dev(w16)
+    base = out_buf(out.numel(), torch.int8, SENTINEL)
     a3 = _conv1_args(N, Hh, Ww, 16, w16d, bd, md, ekd, base, cout, ldo, c_off, relu, qrange, in_=x0.data_ptr())
     lib.call("hawq_fakequant_f32", xd.data_ptr(), xq.data_ptr(), xd.numel(), inv, 1.0, in_lo, in_hi, s)
     lib.call("hawq_f32_nchw_to_q_nhwc", xq.data_ptr(), x0.data_ptr(), N, 3, Hh, Ww, 16, 8, 1.0, s)

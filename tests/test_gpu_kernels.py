@@ -213,10 +213,11 @@ def test_conv_requant_epilogue(lib, orc, bits, out_bits, fast):
 @pytest.mark.parametrize("shape", [(2, 56, 56, 64, 64), (3, 28, 28, 128, 128), (5, 14, 14, 256, 256), (9, 7, 7, 128, 128),
                                    (1, 14, 20, 64, 192), (2, 9, 30, 192, 128), (7, 7, 7, 512, 128), (1, 3, 5, 64, 64)])
 @pytest.mark.parametrize("bits", [8, 4])
-def test_conv3x3_band_kernels(lib, orc, shape, bits):
+def test_conv3x3_band_kernels(lib, orc, shape, bits, expect=None):
     """The LDS-band 3x3 kernels (the last tile ids) vs the oracle: all ResNet50 spatial sizes, several images per
     workgroup, ragged last tile, rectangular maps; both ReLU settings; int8 and hawq4 outputs; int8 and hawq4
-    (W4A4, Cin % 128 == 0) operands."""
+    (W4A4, Cin % 128 == 0) operands.  `expect` (tests/test_gpu_contract_edges.py): the exact indices into BAND_GEOM of the
+    tiles that must have run, in place of the count."""
     from hawq_amd.packing import pack_ctab
     from hawq_amd.quant_utils import tables_are_fast
     n, h, w, cin, cout = shape
@@ -230,7 +231,7 @@ def test_conv3x3_band_kernels(lib, orc, shape, bits):
     # (the round-5 kernels behind them have their own tests: tests/test_gpu_band2.py)
     geom = BAND_GEOM
     assert nband - lib.load().hawq_conv2d_num_band2_tiles() - lib.load().hawq_conv2d_num_gemm2_tiles() == len(geom)
-    ran = 0
+    ran, ran_tiles = 0, []
     for gi, (tile, (bm, bn, band_px, cin64)) in enumerate(zip(range(ntiles - nband + 1, ntiles + 1), geom)):
         chunks = cin // 64 if bits == 8 else cin // 128
         applies = (cout % bn == 0 and ((bm + w - 1) // w + 3) * (w + 2) <= band_px - 4 and (chunks == 1 or not cin64)
@@ -266,7 +267,12 @@ def test_conv3x3_band_kernels(lib, orc, shape, bits):
                 got = from_planar(out, (n, h, w, cout), out_bits) if outp else unpack_q(out, (n, h, w, cout), out_bits)
                 assert np.array_equal(got, ref), (tile, relu, out_bits, inp, outp)
             ran += 1
-    assert ran >= 3 or (bits == 4 and cin % 128)
+            if gi not in ran_tiles:
+                ran_tiles.append(gi)
+    if expect is not None:
+        assert ran_tiles == list(expect), (ran_tiles, expect)
+    else:
+        assert ran >= 3 or (bits == 4 and cin % 128)
     # a layer the band kernels cannot take is refused, not mis-computed
     a, keep = conv_args(lib, x, wt, b, 2, 1, bits, bits, tile=ntiles)
     assert lib.load().hawq_conv2d(C.byref(a), None) != 0
@@ -274,9 +280,9 @@ def test_conv3x3_band_kernels(lib, orc, shape, bits):
 
 @pytest.mark.parametrize("shape", [(2, 56, 56, 64, 64), (3, 28, 28, 128, 128), (5, 14, 14, 256, 256), (9, 7, 7, 128, 256)])
 @pytest.mark.parametrize("bits,mode", [(8, 1), (8, 5), (4, 1)])
-def test_conv3x3_band_residual(lib, orc, shape, bits, mode):
+def test_conv3x3_band_residual(lib, orc, shape, bits, mode, expect=None):
     """Band kernels with the RESIDUAL epilogue (3x3 second conv of a basic block): uint16 residual in and out,
-    fused next-QuantAct output; tie-free and exact-tie instantiations; int8 and hawq4 operands."""
+    fused next-QuantAct output; tie-free and exact-tie instantiations; int8 and hawq4 operands.  `expect`: as above."""
     from hawq_amd.packing import pack_ctab
     from hawq_amd.quant_utils import requant_table, tables_are_fast
     n, h, w, cin, cout = shape
@@ -293,7 +299,7 @@ def test_conv3x3_band_residual(lib, orc, shape, bits, mode):
     ref_q = odyadic(orc, ref_res, mq, eq, (0, 127))
     ntiles, nband = lib.load().hawq_conv2d_num_tiles(), lib.load().hawq_conv2d_num_band_tiles()
     geom = BAND_GEOM
-    ran = 0
+    ran, ran_tiles = 0, []
     for gi, (tile, (bm, bn, band_px, one_chunk)) in enumerate(zip(range(ntiles - nband + 1, ntiles + 1), geom)):
         chunks = cin // 64 if bits == 8 else cin // 128
         if not (cout % bn == 0 and ((bm + w - 1) // w + 3) * (w + 2) <= band_px - 4 and (chunks == 1 or not one_chunk)
@@ -323,7 +329,11 @@ def test_conv3x3_band_residual(lib, orc, shape, bits, mode):
         got = out_res.cpu().numpy().astype(np.int64).reshape(n, h, w, cout).transpose(0, 3, 1, 2)
         assert np.array_equal(got, ref_res) and np.array_equal(from_planar(out_q, (n, h, w, cout), 8), ref_q), tile
         ran += 1
-    assert ran >= 1 or (bits == 4 and cin % 128)
+        ran_tiles.append(gi)
+    if expect is not None:
+        assert ran_tiles == list(expect), (ran_tiles, expect)
+    else:
+        assert ran >= 1 or (bits == 4 and cin % 128)
 
 
 @pytest.mark.parametrize("fast", [0, 1, 3, 5])

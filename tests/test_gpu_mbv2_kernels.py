@@ -178,7 +178,12 @@ UNITS = [(32, 32, 32, 16, 16, 1, False, (2, 20, 37), False),       # unit 1 of t
          (160, 160, 960, 160, 160, 1, True, (2, 7, 7), False),      # the 7 x 7 units of the width-1 network: 8 x 8 tiles, 5 K steps, 5 output blocks
          (160, 160, 960, 320, 320, 1, False, (1, 7, 7), False),     # ten output blocks
          (96, 96, 576, 160, 160, 2, False, (2, 14, 14), False),     # stride 2 onto a 7 x 7 map
-         (160, 160, 128, 160, 160, 1, True, (1, 5, 8), True)]       # as many slices as slice groups, a ragged map, pre-shifts
+         (160, 160, 128, 160, 160, 1, True, (1, 5, 8), True),       # as many slices as slice groups, a ragged map, pre-shifts
+         # the largest map the wide units' check takes, 8 x 8 (the width-1 network at 256 x 256 input): tests/contract_edges.py LB_WIDE_UNITS
+         (160, 160, 960, 160, 160, 1, True, (2, 8, 8), False),
+         (160, 160, 960, 320, 320, 1, False, (1, 8, 8), False),
+         (96, 96, 576, 160, 160, 2, False, (2, 15, 16), False),     # stride 2 from an odd and from an even height onto 8 x 8
+         (96, 96, 576, 160, 160, 2, False, (1, 16, 16), False)]
 
 
 @pytest.mark.parametrize("tile", [0, 1, 2, 3, 4])
