@@ -135,6 +135,16 @@ class JpegHuff(C.Structure):
     _fields_ = [("mincode", i32 * 17), ("maxcode", i32 * 17), ("valptr", i32 * 17), ("huffval", C.c_uint8 * 256), ("reserved", i32)]
 
 
+class JpegSyncJob(C.Structure):
+    """struct hawq_jpeg_sync_job (include/hawq_mi355.h): one long interval of a hawq_jpeg_decode_batch_sync call."""
+    _fields_ = [("wave", i32), ("n_sub", i32), ("scratch_off", i64)]
+
+
+class JpegSyncSub(C.Structure):
+    """struct hawq_jpeg_sync_sub (include/hawq_mi355.h): the scratch record of one sub-sequence."""
+    _fields_ = [(n, i32) for n in ("start_pos", "start_uk", "end_pos", "end_uk", "blocks")] + [("dc", i32 * 3)]
+
+
 class JpegDesc(C.Structure):
     """struct hawq_jpeg_desc (include/hawq_mi355.h): one image of a hawq_jpeg_decode_batch call."""
     _fields_ = ([(n, i32) for n in ("width", "height", "ncomp", "hs", "vs", "mcus_x", "mcus_y", "restart", "n_intervals")]
@@ -196,6 +206,8 @@ SIGNATURES = {
     "hawq_image_batch_lds_budget": [],
     "hawq_jpeg_batch_ok": [vp, i64, i64, i64, i64],
     "hawq_jpeg_decode_batch": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp],
+    "hawq_jpeg_sync_ok": [vp, i64, i32, i32, i64, i32, i64],
+    "hawq_jpeg_decode_batch_sync": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i64, i32, vp, i64, vp, vp],
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
     "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],

@@ -6,6 +6,8 @@ path does not take; ``plan_jpeg_batch`` packs the descriptors, tables, entropy-c
 blob (``struct hawq_jpeg_*`` of include/hawq_mi355.h); ``decode_jpeg_batch`` uploads it in one pinned copy, runs
 ``hawq_jpeg_decode_batch`` (entropy decode -> IDCT -> upsampling + colour) and hands every refused or failed image to the host decoder,
 with the reason.  ``image.folder_loader(device_decode=True)`` feeds the result to ``preprocess_batch_fused`` in place.
+``entropy="sync"`` decodes long restart intervals with many lanes each (``hawq_jpeg_decode_batch_sync``): the planner
+appends a job table, ``hawq_jpeg_sync_ok`` checks it, the launch gets a scratch buffer; everything else is the same.
 """
 from __future__ import annotations
 
@@ -21,6 +23,12 @@ HUFF_BYTES = C.sizeof(_lib.JpegHuff)
 _HUFF = np.dtype(_lib.JpegHuff)
 _DESC = np.dtype(_lib.JpegDesc)
 _HDR = np.dtype(_lib.JpegBatchHdr)
+_JOB = np.dtype(_lib.JpegSyncJob)
+SYNC_SUB_MIN, SYNC_SUB_MAX = 16, 4096   # HAWQ_JPEG_SYNC_SUB_MIN / _MAX
+SYNC_JOB_HDR_BYTES, SYNC_SUB_RECORD_BYTES = 16, C.sizeof(_lib.JpegSyncSub)
+# entropy="sync" defaults: the fastest row of profiles/jpeg_sync.md on files without restart markers that leaves files with them alone
+SUB_BYTES = 32
+MIN_SYNC_BYTES = 4096
 STATUS_NAMES = {1: "ran out of bytes", 2: "code not in table", 3: "coefficient index past 63", 4: "unexpected marker"}
 
 
@@ -229,19 +237,29 @@ def _align16(n: int) -> int:
 class JpegPlan:
     """What ``plan_jpeg_batch`` returns.  ``blob``: uint8 array (the first ``nbytes`` bytes count), ``coef_blocks`` / ``plane_bytes`` /
     ``out_bytes``: the sizes of the three device buffers the launch needs, ``out_offsets`` / ``sizes``: where each image lands in the
-    output and its (height, width), ``n_waves``: restart intervals in the batch."""
-    __slots__ = ("blob", "nbytes", "coef_blocks", "plane_bytes", "out_bytes", "out_offsets", "sizes", "n_waves")
+    output and its (height, width), ``n_waves``: restart intervals in the batch.  With ``sync``: ``sub_bytes`` / ``min_sync_bytes``,
+    ``jobs_off`` / ``n_jobs``: the table of ``hawq_jpeg_sync_job`` in the blob (one per interval of at least ``min_sync_bytes``),
+    ``jobs``: the same as (wave, n_sub, scratch offset) tuples, ``scratch_bytes``: the device scratch the launch needs."""
+    __slots__ = ("blob", "nbytes", "coef_blocks", "plane_bytes", "out_bytes", "out_offsets", "sizes", "n_waves", "sub_bytes", "min_sync_bytes", "jobs_off",
+                 "n_jobs", "jobs", "scratch_bytes")
 
     def ok(self) -> bool:
         """``hawq_jpeg_batch_ok`` on the host blob (no GPU work); the reason of a refusal is in ``hawq_last_error``."""
         return bool(_lib.load().hawq_jpeg_batch_ok(self.blob.ctypes.data, self.nbytes, self.coef_blocks, self.plane_bytes, self.out_bytes))
 
+    def sync_ok(self) -> bool:
+        """``hawq_jpeg_sync_ok`` on the host blob of a plan made with ``sync`` (after ``ok``; no GPU work)."""
+        return bool(_lib.load().hawq_jpeg_sync_ok(self.blob.ctypes.data, self.nbytes, self.sub_bytes, self.min_sync_bytes, self.jobs_off, self.n_jobs,
+                                                  self.scratch_bytes))
 
-def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None) -> JpegPlan:
+
+def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, sync=None) -> JpegPlan:
     """Pack the records of ``parse_jpeg`` into one host blob: header | descriptors | wave list | per image: quantisation tables, Huffman
     tables, intervals, stream - every part at a 16-byte aligned offset.  ``out_offsets`` / ``out_bytes``: where each image goes in an
     output buffer of that size (default: one after the other, 16-byte aligned).  ``reserve(nbytes)`` returns the uint8 array to write
-    into (at least nbytes, 16-byte aligned; e.g. a pinned staging buffer); a fresh array without it."""
+    into (at least nbytes, 16-byte aligned; e.g. a pinned staging buffer); a fresh array without it.  ``sync`` = (sub_bytes,
+    min_sync_bytes): append the job table of ``hawq_jpeg_decode_batch_sync`` behind the streams - one job per interval of at least
+    ``min_sync_bytes`` bytes, cut into sub-sequences of ``sub_bytes``, with its slice of the scratch."""
     records = list(records)
     if not records:
         raise ValueError("empty batch")
@@ -281,6 +299,26 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None) -> 
         d["out_off"] = off
         offs.append(off)
         out_at = _align16(off + r.width * r.height * 3)
+    plan.sub_bytes = plan.min_sync_bytes = plan.jobs_off = plan.n_jobs = plan.scratch_bytes = 0
+    plan.jobs = []
+    if sync is not None:
+        sub_bytes, min_sync_bytes = (int(v) for v in sync)
+        if sub_bytes % 4 or not SYNC_SUB_MIN <= sub_bytes <= SYNC_SUB_MAX:
+            raise ValueError(f"sub_bytes must be a multiple of 4 in {SYNC_SUB_MIN}..{SYNC_SUB_MAX}, not {sub_bytes}")
+        if min_sync_bytes < 1:
+            raise ValueError(f"min_sync_bytes must be at least 1, not {min_sync_bytes}")
+        wave = 0
+        for r in records:
+            for first, last in r.intervals.tolist():
+                if last - first >= min_sync_bytes:
+                    n_sub = -(-(last - first) // sub_bytes)
+                    plan.jobs.append((wave, n_sub, plan.scratch_bytes))
+                    plan.scratch_bytes += SYNC_JOB_HDR_BYTES + SYNC_SUB_RECORD_BYTES * n_sub
+                wave += 1
+        plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off, plan.n_jobs = sub_bytes, min_sync_bytes, at, len(plan.jobs)
+        if plan.jobs:
+            parts.append((at, np.array(plan.jobs, _JOB).view(np.uint8).reshape(-1)))
+        at = _align16(at + _JOB.itemsize * len(plan.jobs))
     if at >= 1 << 31:
         raise ValueError("batch too large for one blob (2 GiB of compressed data)")
     blob = np.zeros(at, np.uint8) if reserve is None else reserve(at)
@@ -300,10 +338,11 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None) -> 
     return plan
 
 
-def _launch(records, out_offsets, out_bytes, dev, events=None):
+def _launch(records, out_offsets, out_bytes, dev, events=None, sync=None, info=None):
     """The device call of ``decode_jpeg_batch``: plan into the pinned staging buffer, check, upload in one copy, run the three stages
     on the current stream.  Returns (uint8 [out_bytes] device tensor, freshly allocated; int32 status per record, on the host - reading
-    it is the one synchronisation of the batch)."""
+    it is the one synchronisation of the batch).  ``sync`` = (sub_bytes, min_sync_bytes): ``hawq_jpeg_decode_batch_sync``; a dict
+    ``info`` then receives ``jobs`` (the plan's) and ``rounds`` / ``decodes`` (what the kernel counted per job)."""
     from .image import _STAGING, _Staging
     lib = _lib.load()
     with torch.cuda.device(dev):
@@ -314,8 +353,8 @@ def _launch(records, out_offsets, out_bytes, dev, events=None):
             held["host"], held["dev"] = st.reserve(nbytes, dev)
             return held["host"].numpy()
 
-        plan = plan_jpeg_batch(records, out_offsets, out_bytes, reserve)
-        if not plan.ok():   # on the host blob, before anything is uploaded or launched
+        plan = plan_jpeg_batch(records, out_offsets, out_bytes, reserve, sync)
+        if not plan.ok() or (sync is not None and not plan.sync_ok()):   # on the host blob, before anything is uploaded or launched
             raise RuntimeError("libhawq_mi355: " + lib.hawq_last_error().decode())
         st.upload(plan.nbytes)
         out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
@@ -323,10 +362,22 @@ def _launch(records, out_offsets, out_bytes, dev, events=None):
         planes = torch.empty(plan.plane_bytes, dtype=torch.uint8, device=dev)
         status = torch.empty(len(records), dtype=torch.int32, device=dev)
         ev = (C.c_void_p * 4)(*events) if events is not None else None
-        _lib.call("hawq_jpeg_decode_batch", held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks,
-                  planes.data_ptr(), plan.plane_bytes, out.data_ptr(), out_bytes, status.data_ptr(), ev,
-                  torch.cuda.current_stream(dev).cuda_stream)
-        return out, status.cpu().numpy()
+        if sync is None:
+            _lib.call("hawq_jpeg_decode_batch", held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks,
+                      planes.data_ptr(), plan.plane_bytes, out.data_ptr(), out_bytes, status.data_ptr(), ev,
+                      torch.cuda.current_stream(dev).cuda_stream)
+            return out, status.cpu().numpy()
+        scratch = torch.empty(max(plan.scratch_bytes, 16), dtype=torch.uint8, device=dev)
+        _lib.call("hawq_jpeg_decode_batch_sync", held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks,
+                  planes.data_ptr(), plan.plane_bytes, out.data_ptr(), out_bytes, status.data_ptr(), plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off,
+                  plan.n_jobs, scratch.data_ptr(), plan.scratch_bytes, ev, torch.cuda.current_stream(dev).cuda_stream)
+        status = status.cpu().numpy()
+        if info is not None:
+            info["jobs"] = list(plan.jobs)
+            host = scratch.cpu().numpy()
+            heads = [host[off:off + 8].view(np.int32) for _, _, off in plan.jobs]
+            info["rounds"], info["decodes"] = [int(h[0]) for h in heads], [int(h[1]) for h in heads]
+        return out, status
 
 
 def read_source(source) -> bytes:
@@ -339,13 +390,21 @@ def read_source(source) -> bytes:
         return f.read()
 
 
-def decode_jpeg_batch(sources, device=None):
+def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, min_sync_bytes=None):
     """Paths or bytes of image files -> ``(images, fallbacks)``: ``images[i]`` a uint8 [H, W, 3] RGB tensor on the MI355X equal to
     ``image.decode_image(sources[i])``, ``fallbacks`` the list of ``(index, reason)`` of the images the HOST decoder produced: files
     ``parse_jpeg`` refuses (progressive, CMYK, not a JPEG, ...) and files whose device decode reported a status (damaged streams).
     All images are views into one device allocation made by this call, at 16-byte aligned offsets, so ``preprocess_batch_fused`` reads
-    them in place.  An error of the host decoder on such a file propagates as it does from ``decode_image``."""
+    them in place.  An error of the host decoder on such a file propagates as it does from ``decode_image``.
+    ``entropy``: ``"serial"`` decodes every restart interval with one wave; ``"sync"`` decodes intervals of at least ``min_sync_bytes``
+    stream bytes with one lane per ``sub_bytes`` of them (``hawq_jpeg_decode_batch_sync``; defaults ``MIN_SYNC_BYTES`` / ``SUB_BYTES``) -
+    the same bytes and the same fallbacks, faster on files without restart markers."""
     from .image import decode_image
+    if entropy not in ("serial", "sync"):
+        raise ValueError(f"entropy must be 'serial' or 'sync', not {entropy!r}")
+    if entropy == "serial" and (sub_bytes is not None or min_sync_bytes is not None):
+        raise ValueError("sub_bytes / min_sync_bytes belong to entropy='sync'")
+    more = {} if entropy == "serial" else {"sync": (SUB_BYTES if sub_bytes is None else int(sub_bytes), MIN_SYNC_BYTES if min_sync_bytes is None else int(min_sync_bytes))}
     datas = [read_source(s) for s in sources]
     if not datas:
         raise ValueError("empty batch")
@@ -366,7 +425,7 @@ def decode_jpeg_batch(sources, device=None):
         total = _align16(total + h * w * 3)
     order = sorted(records)
     if order:
-        out, status = _launch([records[i] for i in order], [offsets[i] for i in order], total, dev)
+        out, status = _launch([records[i] for i in order], [offsets[i] for i in order], total, dev, **more)
         for i, st in zip(order, status):
             if st != 0:
                 fallbacks.append((i, "device status %d: %s" % (st, STATUS_NAMES.get(int(st), "unknown"))))

@@ -732,6 +732,41 @@ int hawq_jpeg_batch_ok(const void *host_blob, int64_t blob_bytes, int64_t coef_b
 int hawq_jpeg_decode_batch(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
                            int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *const *events, void *stream);
 
+/* ---- the same decode with many lanes per long restart interval (jpeg_sync.h) ------------------------------------
+ * Intervals of at least min_sync_bytes stream bytes are cut into n_sub = ceil(bytes / sub_bytes) sub-sequences, decoded speculatively by
+ * one lane each and synchronised until every lane starts where the lane before it ended; shorter intervals run on the serial wave of
+ * hawq_jpeg_decode_batch in the same call.  Same coefficients, same status, same output bytes.
+ * The job table lies in the blob at jobs_off (16-byte aligned): one entry per long interval, in the order of the wave list.  Scratch
+ * is device memory of scratch_bytes; a job's slice is one hawq_jpeg_sync_job_hdr and n_sub hawq_jpeg_sync_sub. */
+enum { HAWQ_JPEG_SYNC_SUB_MIN = 16, HAWQ_JPEG_SYNC_SUB_MAX = 4096 };   /* sub_bytes: a multiple of 4 in this range */
+typedef struct hawq_jpeg_sync_job {
+    int32_t wave;                      /* index into the wave list */
+    int32_t n_sub;                     /* ceil(interval bytes / sub_bytes) */
+    int64_t scratch_off;               /* 16-byte aligned; 16 + 32 * n_sub bytes behind the previous job's */
+} hawq_jpeg_sync_job;                  /* 16 bytes */
+typedef struct hawq_jpeg_sync_job_hdr {/* written by the kernel at scratch_off */
+    int32_t rounds;                    /* decode passes until no lane's start changed: 1 (speculation) .. n_sub */
+    int32_t decodes;                   /* sub-sequence decodes of all of them */
+    int32_t reserved[2];
+} hawq_jpeg_sync_job_hdr;              /* 16 bytes */
+typedef struct hawq_jpeg_sync_sub {    /* one sub-sequence; a state is (byte relative to the stream, bit | u << 8 | k << 16), byte < 0: none */
+    int32_t start_pos, start_uk;       /* the state it last decoded from */
+    int32_t end_pos, end_uk;           /* the state behind its last symbol */
+    int32_t blocks;                    /* blocks that end in it; after the scan: ordinal of its first block in the interval */
+    int32_t dc[3];                     /* sum of its DC differences per component; after the scan: the predictors at its start */
+} hawq_jpeg_sync_sub;                  /* 32 bytes */
+/* hawq_jpeg_sync_ok launches nothing and reads the HOST blob, which hawq_jpeg_batch_ok has passed: 1 when sub_bytes is a multiple of 4
+ * in [HAWQ_JPEG_SYNC_SUB_MIN, HAWQ_JPEG_SYNC_SUB_MAX], min_sync_bytes >= 1, the job table lies inside the blob and names exactly the
+ * waves whose interval has at least min_sync_bytes bytes, in order, each with its n_sub and a scratch slice inside scratch_bytes behind
+ * the previous job's; else 0 with the reason in hawq_last_error().
+ * hawq_jpeg_decode_batch_sync runs both checks again, then works as hawq_jpeg_decode_batch; stage 1 is the serial kernel (which leaves
+ * the long intervals out) and one workgroup per job.  events as there: the second one is recorded behind both stage-1 launches. */
+int hawq_jpeg_sync_ok(const void *host_blob, int64_t blob_bytes, int32_t sub_bytes, int32_t min_sync_bytes, int64_t jobs_off, int32_t n_jobs,
+                      int64_t scratch_bytes);
+int hawq_jpeg_decode_batch_sync(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                                int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, int32_t sub_bytes, int32_t min_sync_bytes,
+                                int64_t jobs_off, int32_t n_jobs, void *scratch, int64_t scratch_bytes, void *const *events, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

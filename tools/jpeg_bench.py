@@ -9,7 +9,15 @@ within each repeat; outputs are compared byte for byte first.  Then the three st
 recorded on the stream before stage 1 and behind each stage (a pair brackets one launch and whatever the stream waits for between the two
 records).  Reported: median (min-max).  Writes the table to ``--out`` (markdown) and prints one JSON line per set.
 
+``--entropy sync`` times the device path with ``entropy="sync"`` (many lanes per long restart interval, ``--sub-bytes`` /
+``--min-sync-bytes``) in place of the serial one; ``--entropy both`` times both device paths, alternating with each other and the host
+path in one process, so the serial path of that process is the baseline of the other; the table gains the wall time and the entropy
+stage of the second path and the decode passes ("rounds") the kernel counted for the largest interval.  ``--sweep`` adds the entropy
+stage of the sync path for sub_bytes in 32 / 64 / 128 / 256 and min_sync_bytes in 256 / 1024 / 4096, each row alternating with the
+serial stage.  ``--sets`` picks sets by index.
+
     python tools/jpeg_bench.py [--batch 128] [--repeats 20] [--warmup 3] [--out profiles/jpeg_decode.md] [--box NAME]
+                               [--entropy serial|sync|both] [--sub-bytes N] [--min-sync-bytes N] [--sweep] [--sets 0,1,3]
 """
 import argparse
 import ctypes as C
@@ -70,7 +78,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode.md"))
     ap.add_argument("--box", default=None, help="label of the machine for the report (default: the device name and architecture)")
+    ap.add_argument("--entropy", choices=("serial", "sync", "both"), default="serial")
+    ap.add_argument("--sub-bytes", type=int, default=jpeg.SUB_BYTES)
+    ap.add_argument("--min-sync-bytes", type=int, default=jpeg.MIN_SYNC_BYTES)
+    ap.add_argument("--sweep", action="store_true", help="entropy stage of the sync path over a grid of sub_bytes x min_sync_bytes")
+    ap.add_argument("--sets", default=None, help="comma-separated indices into SETS (default: all)")
     args = ap.parse_args()
+    paths = ("serial", "sync") if args.entropy == "both" else (args.entropy,)
+    sync_of = {"serial": None, "sync": (args.sub_bytes, args.min_sync_bytes)}
+    picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(SETS))
     if not torch.cuda.is_available():
         sys.exit("jpeg_bench: needs the GPU (a CPU run says nothing about these times)")
     props = torch.cuda.get_device_properties(0)
@@ -82,8 +98,8 @@ def main():
         ev = C.c_void_p()
         _lib.check(lib.hawq_event_create(C.byref(ev)))
         events.append(ev)
-    rows = []
-    for label, variants in SETS.items():
+    rows, sweep_rows = [], []
+    for label, variants in [list(SETS.items())[k] for k in picked]:
         datas = make_set(variants, args.batch)
         samples = [(d, 0) for d in datas]
 
@@ -91,41 +107,76 @@ def main():
             imgs, _ = next(iter(image.decoded_batches(samples, len(samples), workers=16)))
             return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
 
-        def device():
-            imgs, fallbacks = jpeg.decode_jpeg_batch(datas, dev)
+        def device(path=paths[0]):
+            more = {} if path == "serial" else dict(entropy="sync", sub_bytes=args.sub_bytes, min_sync_bytes=args.min_sync_bytes)
+            imgs, fallbacks = jpeg.decode_jpeg_batch(datas, dev, **more)
             assert not fallbacks, fallbacks
             return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
 
-        if not torch.equal(host(), device()):
-            sys.exit(f"jpeg_bench: the two paths differ at {label}")
+        runs = {"host": host}
+        runs.update({p: (lambda p=p: device(p)) for p in paths})
+        want = host()
+        for p in paths:
+            if not torch.equal(want, device(p)):
+                sys.exit(f"jpeg_bench: the host path and the {p} device path differ at {label}")
         for _ in range(args.warmup):
-            host(), device()
-        t = {"host": [], "device": []}
+            for fn in runs.values():
+                fn()
+        t = {name: [] for name in runs}
+        order = list(runs)
         for r in range(args.repeats):
-            for name in (("host", "device") if r % 2 == 0 else ("device", "host")):
-                t[name].append(wall(host if name == "host" else device))
+            for name in order[r % len(order):] + order[:r % len(order)]:   # every path takes every place in turn
+                t[name].append(wall(runs[name]))
         # the stages alone: parsed once, planned + uploaded + launched per call
         records = [jpeg.parse_jpeg(d) for d in datas]
         offsets, total = [], 0
         for r in records:
             offsets.append(total)
             total = (total + r.width * r.height * 3 + 15) & ~15
-        stages = [[], [], []]
-        for k in range(args.warmup + args.repeats):
-            _, status = jpeg._launch(records, offsets, total, dev, events)   # reads the status: synchronised
-            assert not status.any()
-            if k >= args.warmup:
-                for s in range(3):
-                    ms = C.c_float()
-                    _lib.check(lib.hawq_event_elapsed_ms(events[s], events[s + 1], C.byref(ms)))
-                    stages[s].append(ms.value)
+        lengths = [int(v) for r in records for v in (r.intervals[:, 1] - r.intervals[:, 0])]
+
+        def staged(pairs, repeats):
+            """{key: ([stage 1 ms], [stage 2 ms], [stage 3 ms], [rounds of the largest interval or None])} of (key, sync) pairs, alternating"""
+            got = {key: ([], [], [], [None]) for key, _ in pairs}
+            for k in range(args.warmup + repeats):
+                for key, sync in pairs[k % len(pairs):] + pairs[:k % len(pairs)]:
+                    info = {}
+                    more = {} if sync is None else dict(sync=sync, info=info)
+                    _, status = jpeg._launch(records, offsets, total, dev, events, **more)   # reads the status: synchronised
+                    assert not status.any()
+                    if sync is not None and info["jobs"]:
+                        waves = [w for w, _, _ in info["jobs"]]
+                        got[key][3][0] = info["rounds"][max(range(len(waves)), key=lambda j: lengths[waves[j]])]
+                    if k >= args.warmup:
+                        for s in range(3):
+                            ms = C.c_float()
+                            _lib.check(lib.hawq_event_elapsed_ms(events[s], events[s + 1], C.byref(ms)))
+                            got[key][s].append(ms.value)
+            return got
+
+        per_path = staged([(p, sync_of[p]) for p in paths], args.repeats)
+        stages = per_path[paths[0]]
         row = {"set": label, "n": len(datas), "compressed_mb": sum(map(len, datas)) / 1e6, "decoded_mb": total / 1e6,
                "waves": sum(len(r.intervals) for r in records), "largest_interval_bytes": int(max((r.intervals[:, 1] - r.intervals[:, 0]).max() for r in records)),
-               "host_wall_ms": stat(t["host"]), "device_wall_ms": stat(t["device"]), "entropy_ms": stat(stages[0]), "idct_ms": stat(stages[1]),
-               "colour_ms": stat(stages[2])}
+               "entropy_ms": stat(stages[0]), "idct_ms": stat(stages[1]), "colour_ms": stat(stages[2])}
+        row["host_wall_ms"], row["device_wall_ms"] = stat(t["host"]), stat(t[paths[0]])
         row["wall_ratio"] = row["device_wall_ms"][0] / row["host_wall_ms"][0]
+        row["entropy"] = paths[0]
+        if "sync" in paths:
+            row["sub_bytes"], row["min_sync_bytes"], row["rounds_largest"] = args.sub_bytes, args.min_sync_bytes, per_path["sync"][3][0]
+        if len(paths) > 1:
+            row["sync_wall_ms"], row["sync_entropy_ms"] = stat(t["sync"]), stat(per_path["sync"][0])
+            row["sync_wall_ratio"] = row["sync_wall_ms"][0] / row["host_wall_ms"][0]
         rows.append(row)
         print(json.dumps(row), flush=True)
+        if args.sweep:
+            for sub in (32, 64, 128, 256):
+                for low in (256, 1024, 4096):
+                    got = staged([("serial", None), ("sync", (sub, low))], args.repeats)
+                    sw = {"set": label, "sub_bytes": sub, "min_sync_bytes": low, "jobs": sum(v >= low for v in lengths), "serial_entropy_ms": stat(got["serial"][0]),
+                          "sync_entropy_ms": stat(got["sync"][0]), "rounds_largest": got["sync"][3][0]}
+                    sweep_rows.append(sw)
+                    print(json.dumps(sw), flush=True)
     f = lambda v: f"{v[0]:.2f} ({v[0 + 1]:.2f}-{v[2]:.2f})"
     lines = ["# JPEG bytes in memory to the cropped batch on the device: host decode against device decode", "",
              f"Measured on one {box} with `python tools/jpeg_bench.py --batch {args.batch} --repeats {args.repeats} --warmup {args.warmup}`: median (min-max) of "
@@ -137,6 +188,20 @@ def main():
     for r in rows:
         lines.append(f"| {r['n']} x {r['set']} | {r['compressed_mb']:.1f} / {r['decoded_mb']:.1f} | {r['waves']} | {r['largest_interval_bytes']} | "
                      f"{f(r['host_wall_ms'])} | {f(r['device_wall_ms'])} | {r['wall_ratio']:.2f} | {f(r['entropy_ms'])} | {f(r['idct_ms'])} | {f(r['colour_ms'])} |")
+    if args.entropy != "serial":
+        lines += ["", f"`device` above is the `{paths[0]}` entropy stage." + (f"  The `sync` one (sub_bytes {args.sub_bytes}, min_sync_bytes {args.min_sync_bytes}), "
+                  "alternating with it and the host path in the same process:" if len(paths) > 1 else f"  sub_bytes {args.sub_bytes}, min_sync_bytes {args.min_sync_bytes}."), ""]
+    if len(paths) > 1:
+        lines += ["| set | serial wall | sync wall | sync / host | serial entropy | sync entropy | serial / sync entropy | rounds of the largest interval |", "|---|---|---|---|---|---|---|---|"]
+        for r in rows:
+            lines.append(f"| {r['n']} x {r['set']} | {f(r['device_wall_ms'])} | {f(r['sync_wall_ms'])} | {r['sync_wall_ratio']:.2f} | {f(r['entropy_ms'])} | "
+                         f"{f(r['sync_entropy_ms'])} | {r['entropy_ms'][0] / r['sync_entropy_ms'][0]:.1f} | {r['rounds_largest']} |")
+    if sweep_rows:
+        lines += ["", "## Entropy stage over sub_bytes x min_sync_bytes", "",
+                  "Each row: the serial and the sync stage 1 alternating, HIP events around the stage (both kernels of the sync path).", "",
+                  "| set | sub_bytes | min_sync_bytes | jobs | serial entropy | sync entropy | rounds of the largest interval |", "|---|---|---|---|---|---|---|"]
+        for r in sweep_rows:
+            lines.append(f"| {r['set']} | {r['sub_bytes']} | {r['min_sync_bytes']} | {r['jobs']} | {f(r['serial_entropy_ms'])} | {f(r['sync_entropy_ms'])} | {r['rounds_largest']} |")
     lines.append("")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
