@@ -153,6 +153,17 @@ class JpegDesc(C.Structure):
                 + [(n, i64) for n in ("coef_block0", "plane_off", "out_off")])
 
 
+class JpegProgHdr(C.Structure):
+    """struct hawq_jpeg_prog_hdr (include/hawq_mi355.h): byte 16 of the blob of a hawq_jpeg_decode_batch_prog call."""
+    _fields_ = [(n, i32) for n in ("n_scans", "n_levels", "scan_off", "level_off")]
+
+
+class JpegScan(C.Structure):
+    """struct hawq_jpeg_scan (include/hawq_mi355.h): one scan of one progressive image."""
+    _fields_ = ([(n, i32) for n in ("image", "ncomp", "comp0", "ss", "se", "ah", "al", "level")] + [("dc_off", i32 * 3)]
+                + [(n, i32) for n in ("ac_off", "restart", "n_intervals", "interval_off", "stream_off", "stream_len")] + [("reserved", i32 * 3)])
+
+
 # name -> (argtypes); every function returns int except hawq_last_error
 SIGNATURES = {
     "hawq_abi_version": [],
@@ -208,6 +219,8 @@ SIGNATURES = {
     "hawq_jpeg_decode_batch": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp],
     "hawq_jpeg_sync_ok": [vp, i64, i32, i32, i64, i32, i64],
     "hawq_jpeg_decode_batch_sync": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i64, i32, vp, i64, vp, vp],
+    "hawq_jpeg_prog_ok": [vp, i64, i64, i64, i64],
+    "hawq_jpeg_decode_batch_prog": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp],
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
     "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],

@@ -13,32 +13,13 @@
 #include <string.h>
 
 #include "common.h"
-#include "jpeg_pixel.h"
+#include "jpeg_stages.h"
 #include "jpeg_sync.h"
 
 namespace {
-constexpr int WAVE = 64;
-constexpr int WINDOW = 256;   // stream bytes in LDS
-constexpr int MAX_SIDE = 8192;
+using namespace hawq_jpeg;   // jpeg_stages.h: geometry, the checks and the stream window shared with jpeg_prog.hip
 constexpr int IDCT_THREADS = 256;   // 32 blocks of 8 lanes
 constexpr int SYNC_THREADS = 1024;  // lanes of one long interval (hawq_jpeg_decode_batch_sync)
-
-struct Geometry {
-    int64_t blocks, plane_bytes, out_bytes;
-    int32_t mcus;
-};
-
-// block / byte counts of an image whose sampling and size have been checked
-Geometry geometry(const hawq_jpeg_desc &d) {
-    Geometry g;
-    g.mcus = d.mcus_x * d.mcus_y;
-    g.blocks = (int64_t)g.mcus * (d.ncomp == 1 ? 1 : d.hs * d.vs + 2);
-    g.plane_bytes = g.blocks * 64;
-    g.out_bytes = (int64_t)d.width * d.height * 3;
-    return g;
-}
-
-bool inside(int64_t off, int64_t len, int64_t total, int align) { return off >= 0 && len >= 0 && off % align == 0 && off <= total && len <= total - off; }
 
 const char *batch_refusal(const void *host_blob, int64_t blob_bytes, int64_t coef_blocks, int64_t plane_bytes, int64_t out_bytes) {
     if (!host_blob || blob_bytes < (int64_t)sizeof(hawq_jpeg_batch_hdr) || ((uintptr_t)host_blob & 7)) return "no blob, or not 8-byte aligned";
@@ -53,11 +34,7 @@ const char *batch_refusal(const void *host_blob, int64_t blob_bytes, int64_t coe
     int64_t coef_at = 0, plane_at = 0, out_at = 0, wave_at = 0;
     for (int32_t i = 0; i < hd.n_images; ++i) {
         const hawq_jpeg_desc &d = desc[i];
-        if (d.width < 1 || d.height < 1 || d.width > MAX_SIDE || d.height > MAX_SIDE) return "image size outside 1..8192";
-        const bool gray = d.ncomp == 1 && d.hs == 1 && d.vs == 1;
-        const bool colour = d.ncomp == 3 && ((d.hs == 1 && d.vs == 1) || (d.hs == 2 && d.vs == 1) || (d.hs == 2 && d.vs == 2));
-        if (!gray && !colour) return "component count or sampling factors not supported";
-        if (d.mcus_x != (d.width + 8 * d.hs - 1) / (8 * d.hs) || d.mcus_y != (d.height + 8 * d.vs - 1) / (8 * d.vs)) return "MCU counts do not follow from the size";
+        if (const char *why = frame_refusal(d)) return why;
         const Geometry g = geometry(d);
         if (d.restart < 0 || d.n_intervals != (d.restart ? (g.mcus + d.restart - 1) / d.restart : 1)) return "interval count does not follow from the restart interval";
         for (int c = 0; c < d.ncomp; ++c) {
@@ -65,20 +42,7 @@ const char *batch_refusal(const void *host_blob, int64_t blob_bytes, int64_t coe
             if (!inside(d.dc_off[c], sizeof(hawq_jpeg_huff), blob_bytes, 4) || !inside(d.ac_off[c], sizeof(hawq_jpeg_huff), blob_bytes, 4))
                 return "Huffman table outside the blob";
             for (int k = 0; k < 2; ++k) {
-                const hawq_jpeg_huff *t = (const hawq_jpeg_huff *)(blob + (k ? d.ac_off[c] : d.dc_off[c]));
-                int codes = 0;
-                int32_t code = 0, values = 0;   // the canonical assignment (T.81 C.2)
-                for (int l = 1; l <= 16; ++l, code <<= 1) {
-                    if (t->maxcode[l] < -1 || t->maxcode[l] >= (1 << l)) return "Huffman table: maxcode out of range";
-                    if (t->maxcode[l] >= 0) {
-                        if (t->mincode[l] != code || t->maxcode[l] < code || t->valptr[l] != values) return "Huffman table: not canonical";
-                        values += t->maxcode[l] - code + 1;
-                        if (values > 256) return "Huffman table: values outside huffval";
-                        code = t->maxcode[l] + 1;
-                        ++codes;
-                    }
-                }
-                if (!codes) return "Huffman table missing";
+                if (const char *why = huff_refusal((const hawq_jpeg_huff *)(blob + (k ? d.ac_off[c] : d.dc_off[c])))) return why;
             }
         }
         if (!inside(d.stream_off, d.stream_len, blob_bytes, 16)) return "stream outside the blob";
@@ -98,26 +62,7 @@ const char *batch_refusal(const void *host_blob, int64_t blob_bytes, int64_t coe
 }
 
 // ---- stage 1 ---------------------------------------------------------------------------------------------------------------------
-// The stream through a 256-byte LDS window.  Every lane calls byte() with the same position (the decoder's state is the same in all
-// lanes), so the refill is taken by the whole wave; a lane loads only positions inside [0, end) of its interval's stream.
-struct WindowSrc {
-    const uint8_t *stream;   // global
-    uint8_t *win;            // LDS [WINDOW]
-    int32_t base, end, lane;
-    __device__ __forceinline__ uint8_t byte(int32_t pos) {
-        if (pos < base || pos >= base + WINDOW) {
-            __syncthreads();   // single-wave workgroup: orders the LDS reads of the old window before the new one is written
-            base = pos & ~(WINDOW - 1);
-            for (int k = 0; k < WINDOW / WAVE; ++k) {
-                const int32_t at = base + k * WAVE + lane;
-                win[k * WAVE + lane] = at < end ? stream[at] : (uint8_t)0;
-            }
-            __syncthreads();
-        }
-        return win[pos - base];
-    }
-};
-
+// The stream comes through the 256-byte LDS window of jpeg_stages.h (WindowSrc).
 __global__ __launch_bounds__(WAVE) void jpeg_entropy_kernel(const uint8_t *__restrict__ blob, int16_t *__restrict__ coef, int32_t *__restrict__ status, int32_t skip_from) {
     __shared__ hawq_jpeg_huff tables[6];   // dc, ac per component
     __shared__ uint8_t window[WINDOW];
@@ -306,6 +251,25 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const uint8_t *__restr
 }
 }  // namespace
 
+int hawq_jpeg::launch_pixel_stages(const void *blob, const hawq_jpeg_desc *host_desc, int32_t n_images, const int16_t *coef, uint8_t *planes, uint8_t *out,
+                                   void *const *events, hipStream_t s) {
+    int64_t max_blocks = 0, max_pixels = 0;
+    for (int32_t i = 0; i < n_images; ++i) {
+        const Geometry g = geometry(host_desc[i]);
+        max_blocks = g.blocks > max_blocks ? g.blocks : max_blocks;
+        max_pixels = g.out_bytes / 3 > max_pixels ? g.out_bytes / 3 : max_pixels;
+    }
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_THREADS / 8 - 1) / (IDCT_THREADS / 8)), (unsigned)n_images), dim3(IDCT_THREADS), 0, s,
+                       (const uint8_t *)blob, coef, planes);
+    HAWQ_CHECK_HIP(hipGetLastError());
+    if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[2], s));
+    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n_images), dim3(256), 0, s, (const uint8_t *)blob,
+                       (const uint8_t *)planes, out);
+    HAWQ_CHECK_HIP(hipGetLastError());
+    if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[3], s));
+    return 0;
+}
+
 namespace {
 // the job table against the blob batch_refusal has passed
 const char *sync_refusal(const void *host_blob, int64_t blob_bytes, int32_t sub_bytes, int32_t min_sync_bytes, int64_t jobs_off, int32_t n_jobs, int64_t scratch_bytes) {
@@ -360,12 +324,6 @@ int decode_batch(const void *blob, const void *host_blob, int64_t blob_bytes, in
     hawq_jpeg_batch_hdr hd;
     memcpy(&hd, host_blob, sizeof hd);
     const hawq_jpeg_desc *desc = (const hawq_jpeg_desc *)((const uint8_t *)host_blob + hd.desc_off);
-    int64_t max_blocks = 0, max_pixels = 0;
-    for (int32_t i = 0; i < hd.n_images; ++i) {
-        const Geometry g = geometry(desc[i]);
-        max_blocks = g.blocks > max_blocks ? g.blocks : max_blocks;
-        max_pixels = g.out_bytes / 3 > max_pixels ? g.out_bytes / 3 : max_pixels;
-    }
     HAWQ_CHECK_HIP(hipMemsetAsync(coef, 0, (size_t)coef_blocks * 128, s));
     HAWQ_CHECK_HIP(hipMemsetAsync(status, 0, (size_t)hd.n_images * sizeof(int32_t), s));
     if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[0], s));
@@ -377,15 +335,7 @@ int decode_batch(const void *blob, const void *host_blob, int64_t blob_bytes, in
         HAWQ_CHECK_HIP(hipGetLastError());
     }
     if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[1], s));
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_THREADS / 8 - 1) / (IDCT_THREADS / 8)), (unsigned)hd.n_images), dim3(IDCT_THREADS), 0, s,
-                       (const uint8_t *)blob, (const int16_t *)coef, planes);
-    HAWQ_CHECK_HIP(hipGetLastError());
-    if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[2], s));
-    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)hd.n_images), dim3(256), 0, s, (const uint8_t *)blob,
-                       (const uint8_t *)planes, out);
-    HAWQ_CHECK_HIP(hipGetLastError());
-    if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[3], s));
-    return 0;
+    return launch_pixel_stages(blob, desc, hd.n_images, coef, planes, out, events, s);
 }
 }  // namespace
 

@@ -8,9 +8,13 @@ blob (``struct hawq_jpeg_*`` of include/hawq_mi355.h); ``decode_jpeg_batch`` upl
 with the reason.  ``image.folder_loader(device_decode=True)`` feeds the result to ``preprocess_batch_fused`` in place.
 ``entropy="sync"`` decodes long restart intervals with many lanes each (``hawq_jpeg_decode_batch_sync``): the planner
 appends a job table, ``hawq_jpeg_sync_ok`` checks it, the launch gets a scratch buffer; everything else is the same.
+``progressive=True`` takes progressive files (SOF2) too: ``parse_jpeg`` returns a ``JpegProgRecord`` with the list of
+scans, ``plan_jpeg_prog_batch`` packs them with the level of every scan, ``hawq_jpeg_decode_batch_prog`` decodes them, one entropy
+launch per level, into the same output allocation as the baseline files of the batch.
 """
 from __future__ import annotations
 
+import bisect
 import ctypes as C
 
 import numpy as np
@@ -24,6 +28,9 @@ _HUFF = np.dtype(_lib.JpegHuff)
 _DESC = np.dtype(_lib.JpegDesc)
 _HDR = np.dtype(_lib.JpegBatchHdr)
 _JOB = np.dtype(_lib.JpegSyncJob)
+_PHDR = np.dtype(_lib.JpegProgHdr)
+_SCAN = np.dtype(_lib.JpegScan)
+MAX_SCANS = 64   # HAWQ_JPEG_PROG_MAX_SCANS
 SYNC_SUB_MIN, SYNC_SUB_MAX = 16, 4096   # HAWQ_JPEG_SYNC_SUB_MIN / _MAX
 SYNC_JOB_HDR_BYTES, SYNC_SUB_RECORD_BYTES = 16, C.sizeof(_lib.JpegSyncSub)
 # entropy="sync" defaults: the fastest row of profiles/jpeg_sync.md on files without restart markers that leaves files with them alone
@@ -82,11 +89,13 @@ def huffman_table(bits, values):
 _SOF_REASON = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)"}
 
 
-def parse_jpeg(data) -> JpegRecord:
+def parse_jpeg(data, progressive=False):
     """Headers of one JPEG file (bytes) -> ``JpegRecord``, or ``UnsupportedJpeg(reason)`` for anything outside the device path:
     baseline SOF0 with 8-bit samples and tables, one interleaved scan of all components, Huffman table ids 0 and 1, three components
     with ids 1, 2, 3, luma 1x1 / 2x1 / 2x2 and chroma 1x1 without an Adobe marker, or one 1x1 component, restart markers complete
-    and in order, both sides at most 8192."""
+    and in order, both sides at most 8192.  ``progressive``: a progressive Huffman file (SOF2) with the same components, sampling and
+    sizes, whose scans form a legal and complete progression (``parse_progressive``), gives a ``JpegProgRecord`` instead of the refusal
+    "progressive (SOF2)"; baseline files parse as without it."""
     data = bytes(data)
     n = len(data)
     if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
@@ -137,6 +146,8 @@ def parse_jpeg(data) -> JpegRecord:
             frame = [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(seg[5])]
         elif marker in (0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF):
             raise UnsupportedJpeg("arithmetic coding")
+        elif marker == 0xC2 and progressive:
+            return parse_progressive(data)
         elif marker in (0xC1, 0xC2, 0xC3, 0xC5, 0xC6, 0xC7):
             raise UnsupportedJpeg(_SOF_REASON.get(marker, "SOF%d" % (marker - 0xC0)))
         elif marker == 0xC4:
@@ -228,6 +239,246 @@ def parse_jpeg(data) -> JpegRecord:
     lasts = np.concatenate([rst, [end]]) - start
     rec.scan, rec.intervals = (start, end), np.stack([firsts, lasts], 1).astype(np.int32)
     return rec
+
+
+class JpegScan:
+    """One scan of a progressive file.  ``comps``: indices into the record's ``components`` (one, or all of them in order); ``ss`` ``se``
+    ``ah`` ``al``; ``dc``: the DC table (``_lib.JpegHuff`` record) in force at the SOS per component of the scan when it is a first DC
+    scan, ``ac``: the AC table when ``ss > 0``, else None; ``restart``: the restart interval in force, in the scan's units (MCUs of an
+    interleaved scan, blocks of the component's own grid otherwise); ``units``: how many there are; ``scan``: (first byte, one past the
+    last) of the entropy-coded segment in the file; ``intervals``: int32 [n, 2] relative to ``scan[0]``."""
+    __slots__ = ("comps", "ss", "se", "ah", "al", "dc", "ac", "restart", "units", "scan", "intervals")
+
+
+class JpegProgRecord:
+    """What ``parse_jpeg(data, progressive=True)`` returns for a progressive file: the frame fields of ``JpegRecord`` (the Huffman table
+    ids of ``components`` are None: they belong to the scans) and ``scans``, the list of ``JpegScan`` in file order."""
+    __slots__ = ("data", "width", "height", "components", "hs", "vs", "mcus_x", "mcus_y", "qtables", "scans")
+    ncomp = JpegRecord.ncomp
+    blocks = JpegRecord.blocks
+
+    def own_grid(self, c):
+        """(blocks across, blocks down) of component ``c`` in a scan of its own: what its samples need, not the MCU-padded grid."""
+        _, h, v = self.components[c][:3]
+        cw, ch = -(-self.width * h // self.hs), -(-self.height * v // self.vs)   # samples
+        return -(-cw // 8), -(-ch // 8)
+
+
+def scan_levels(scans):
+    """level(scan) = 1 + the largest level of the earlier scans that share a (component, coefficient) with it, 1 without one."""
+    last, levels = np.zeros((3, 64), np.int32), []   # per (component, coefficient): the level of the last scan that covered it
+    for s in scans:
+        cells = last[s.comps[0]:s.comps[-1] + 1, s.ss:s.se + 1]
+        levels.append(int(cells.max()) + 1)
+        cells[:] = levels[-1]
+    return levels
+
+
+def parse_progressive(data) -> JpegProgRecord:
+    """Headers and scans of one progressive Huffman JPEG -> ``JpegProgRecord``, or ``UnsupportedJpeg(reason)``.  Accepted: SOF2 with 8-bit
+    samples and tables, components and sampling as in the baseline path, no Adobe marker, sides at most 8192; 1 to 64 scans, each of all
+    components or of one (AC scans: of one), Ss <= Se <= 63 with Se = 0 when Ss = 0, Al <= 13, Ah = 0 or Al + 1, Huffman table ids 0..3;
+    per (component, coefficient) the first scan has Ah = 0, each later one Ah = the previous Al, the DC comes before any AC, and after
+    the last scan everything has reached Al = 0 ("progression" otherwise: the library smooths an incomplete file, the device does not);
+    between scans only DHT / DRI / COM / APPn segments; restart markers complete and in order per scan; EOI behind the last scan."""
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        raise UnsupportedJpeg("not a JPEG")
+    rec = JpegProgRecord()
+    rec.data, rec.qtables, rec.scans = data, {}, []
+    huffman, restart, frame, adobe, pos = {}, 0, None, False, 2
+    state = np.full((3, 64), -1, np.int32)   # per (component, coefficient): the Al reached, -1 before its first scan
+    arr = np.frombuffer(data, np.uint8)
+    ff = np.flatnonzero(arr[:n - 1] == 0xFF)
+    nxt = arr[ff + 1]
+    all_marks = ff[(nxt != 0) & (nxt != 0xFF)]   # FF xx, xx neither stuffing nor fill
+    mark_list = all_marks.tolist()
+    ends = all_marks[(arr[all_marks + 1] & 0xF8) != 0xD0].tolist()   # those that are no RSTn: one of them ends an entropy-coded segment
+
+    def need(upto):
+        if upto > n:
+            raise UnsupportedJpeg("truncated header" if not rec.scans else "truncated scan")
+
+    while True:
+        need(pos + 2)
+        if data[pos] != 0xFF:
+            raise UnsupportedJpeg("marker expected")
+        while data[pos + 1] == 0xFF:   # fill bytes
+            pos += 1
+            need(pos + 2)
+        marker = data[pos + 1]
+        pos += 2
+        if marker == 0xD9:
+            if not rec.scans:
+                raise UnsupportedJpeg("no scan")
+            break
+        if rec.scans and not (marker in (0xC4, 0xDD, 0xFE, 0xDA) or 0xE0 <= marker <= 0xEF):
+            raise UnsupportedJpeg("DNL" if marker == 0xDC else "DQT between scans" if marker == 0xDB else "marker %02X between scans" % marker)
+        if marker == 0xD8 or marker == 0x01 or 0xD0 <= marker <= 0xD7:
+            continue
+        need(pos + 2)
+        length = (data[pos] << 8) | data[pos + 1]
+        if length < 2:
+            raise UnsupportedJpeg("bad segment length")
+        need(pos + length)
+        seg = data[pos + 2:pos + length]
+        pos += length
+        if marker == 0xC2:
+            if frame is not None:
+                raise UnsupportedJpeg("several frames")
+            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                raise UnsupportedJpeg("bad frame header")
+            if seg[0] != 8:
+                raise UnsupportedJpeg("sample precision not 8")
+            rec.height, rec.width = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4]
+            if rec.height == 0:
+                raise UnsupportedJpeg("DNL (height in the scan)")
+            if rec.width == 0:
+                raise UnsupportedJpeg("bad frame header")
+            if seg[5] == 4:
+                raise UnsupportedJpeg("four components")
+            if seg[5] not in (1, 3):
+                raise UnsupportedJpeg("component count")
+            frame = [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(seg[5])]
+        elif marker in (0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF):
+            raise UnsupportedJpeg("arithmetic coding")
+        elif marker in (0xC0, 0xC1, 0xC3, 0xC5, 0xC6, 0xC7):
+            raise UnsupportedJpeg("several frames")
+        elif marker == 0xC4:
+            at = 0
+            while at < len(seg):
+                if at + 17 > len(seg):
+                    raise UnsupportedJpeg("bad Huffman table")
+                tc, th = seg[at] >> 4, seg[at] & 15
+                bits = seg[at + 1:at + 17]
+                count = sum(bits)
+                if tc > 1 or at + 17 + count > len(seg):
+                    raise UnsupportedJpeg("bad Huffman table")
+                if th > 3:
+                    raise UnsupportedJpeg("Huffman table id above 3")
+                huffman[(tc, th)] = huffman_table(bits, seg[at + 17:at + 17 + count])
+                at += 17 + count
+        elif marker == 0xDB:
+            at = 0
+            while at < len(seg):
+                pq, tq = seg[at] >> 4, seg[at] & 15
+                if pq != 0:
+                    raise UnsupportedJpeg("16-bit quantisation table")
+                if tq > 3 or at + 65 > len(seg):
+                    raise UnsupportedJpeg("bad quantisation table")
+                rec.qtables[tq] = np.frombuffer(seg[at + 1:at + 65], np.uint8).astype(np.uint16)
+                at += 65
+        elif marker == 0xDD:
+            if len(seg) != 2:
+                raise UnsupportedJpeg("bad restart interval")
+            restart = (seg[0] << 8) | seg[1]
+        elif marker == 0xDC:
+            raise UnsupportedJpeg("DNL")
+        elif marker == 0xEE:
+            adobe = adobe or seg[:5] == b"Adobe"
+        elif marker == 0xDA:
+            if not rec.scans:
+                _progressive_frame(rec, frame, adobe)
+            if len(rec.scans) == MAX_SCANS:
+                raise UnsupportedJpeg("too many scans")
+            s = _progressive_scan_header(rec, seg, huffman, state)
+            s.restart = restart
+            # the entropy-coded segment: up to the first marker that is no RSTn
+            at = bisect.bisect_left(ends, pos)
+            if at == len(ends):
+                raise UnsupportedJpeg("truncated scan")
+            end = ends[at]
+            rst = all_marks[bisect.bisect_left(mark_list, pos):bisect.bisect_left(mark_list, end)]   # the RSTn markers inside
+            expected = -(-s.units // restart) - 1 if restart else 0
+            if rst.size != expected or not np.array_equal(arr[rst + 1] & 7, np.arange(rst.size) & 7):
+                raise UnsupportedJpeg("restart markers missing or out of order")
+            if rst.size:
+                firsts = np.concatenate([[pos], rst + 2]) - pos
+                lasts = np.concatenate([rst, [end]]) - pos
+                s.intervals = np.stack([firsts, lasts], 1).astype(np.int32)
+            else:
+                s.intervals = np.array([[0, end - pos]], np.int32)
+            s.scan = (pos, end)
+            rec.scans.append(s)
+            pos = end
+    if state[:len(rec.components)].any():   # something never coded, or not down to Al = 0
+        raise UnsupportedJpeg("progression")
+    return rec
+
+
+def _progressive_frame(rec, frame, adobe):
+    """the frame of ``parse_progressive`` at its first SOS: the components, sampling and sizes of the baseline path"""
+    if frame is None:
+        raise UnsupportedJpeg("scan before the frame header")
+    if adobe:
+        raise UnsupportedJpeg("Adobe marker")
+    if any(tq not in rec.qtables for _, _, _, tq in frame):
+        raise UnsupportedJpeg("missing table")
+    if len(frame) == 3:
+        if [c[0] for c in frame] != [1, 2, 3]:
+            raise UnsupportedJpeg("component ids not 1, 2, 3")
+        if (frame[0][1], frame[0][2]) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in frame[1:]):
+            raise UnsupportedJpeg("sampling factors")
+    elif (frame[0][1], frame[0][2]) != (1, 1):
+        raise UnsupportedJpeg("sampling factors")
+    if rec.width > MAX_SIDE or rec.height > MAX_SIDE:
+        raise UnsupportedJpeg("a side above 8192")
+    rec.components, rec.hs, rec.vs = tuple(c + (None, None) for c in frame), frame[0][1], frame[0][2]
+    rec.mcus_x, rec.mcus_y = -(-rec.width // (8 * rec.hs)), -(-rec.height // (8 * rec.vs))
+
+
+def _progressive_scan_header(rec, seg, huffman, state) -> JpegScan:
+    """one SOS segment of ``parse_progressive``: limits, tables in force, and its step in the progression (``state`` is advanced)"""
+    ncomp = len(rec.components)
+    if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
+        raise UnsupportedJpeg("bad scan header")
+    ns = seg[0]
+    ids = [seg[1 + 2 * i] for i in range(ns)]
+    frame_ids = [c[0] for c in rec.components]
+    if ns == ncomp:
+        if ids != frame_ids:
+            raise UnsupportedJpeg("scan component order")
+        comps = tuple(range(ncomp))
+    elif ns == 1:
+        if ids[0] not in frame_ids:
+            raise UnsupportedJpeg("scan component order")
+        comps = (frame_ids.index(ids[0]),)
+    elif ns == 2 and ncomp == 3:
+        raise UnsupportedJpeg("scan of two components")
+    else:
+        raise UnsupportedJpeg("bad scan header")
+    s = JpegScan()
+    s.comps, s.ss, s.se, s.ah, s.al = comps, seg[-3], seg[-2], seg[-1] >> 4, seg[-1] & 15
+    if s.ss > s.se or s.se > 63 or (s.ss == 0 and s.se != 0):
+        raise UnsupportedJpeg("spectral selection")
+    if s.ss > 0 and ns != 1:
+        raise UnsupportedJpeg("AC scan of several components")
+    if s.al > 13 or s.ah not in (0, s.al + 1):
+        raise UnsupportedJpeg("successive approximation")
+    cells = state[comps[0]:comps[-1] + 1, s.ss:s.se + 1]
+    # a first scan (Ah = 0) of cells never coded, or a refinement of cells whose last scan stopped at Al = Ah; the DC before any AC
+    if np.any(cells != (s.ah if s.ah else -1)) or (s.ss > 0 and state[comps[0], 0] < 0):
+        raise UnsupportedJpeg("progression")
+    cells[:] = s.al
+    s.dc = s.ac = None
+    tables = [(seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15) for i in range(ns)]
+    if any(td > 3 or ta > 3 for td, ta in tables):
+        raise UnsupportedJpeg("Huffman table id above 3")
+    if s.ss == 0 and s.ah == 0:
+        if any((0, td) not in huffman for td, _ in tables):
+            raise UnsupportedJpeg("missing table")
+        s.dc = [huffman[(0, td)] for td, _ in tables]
+    if s.ss > 0:
+        if (1, tables[0][1]) not in huffman:
+            raise UnsupportedJpeg("missing table")
+        s.ac = huffman[(1, tables[0][1])]
+    if ns > 1:
+        s.units = rec.mcus_x * rec.mcus_y
+    else:
+        bw, bh = rec.own_grid(comps[0])
+        s.units = bw * bh
+    return s
 
 
 def _align16(n: int) -> int:
@@ -338,11 +589,135 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, syn
     return plan
 
 
-def _launch(records, out_offsets, out_bytes, dev, events=None, sync=None, info=None):
+class JpegProgPlan:
+    """What ``plan_jpeg_prog_batch`` returns.  ``blob`` ``nbytes`` ``coef_blocks`` ``plane_bytes`` ``out_bytes`` ``out_offsets``
+    ``sizes`` as in ``JpegPlan``; ``n_scans``; ``levels``: the level of every scan, image after image; ``n_levels``: the deepest, the
+    number of entropy launches; ``n_waves``: (scan, restart interval) pairs; ``level_start``: where each level's waves begin in the wave
+    list (n_levels + 1 entries); ``scan_off`` / ``level_off`` / ``wave_off`` / ``desc_off``: where the tables lie in the blob."""
+    __slots__ = ("blob", "nbytes", "coef_blocks", "plane_bytes", "out_bytes", "out_offsets", "sizes", "n_scans", "levels", "n_levels", "n_waves", "level_start",
+                 "scan_off", "level_off", "wave_off", "desc_off")
+
+    def ok(self) -> bool:
+        """``hawq_jpeg_prog_ok`` on the host blob (no GPU work); the reason of a refusal is in ``hawq_last_error``."""
+        return bool(_lib.load().hawq_jpeg_prog_ok(self.blob.ctypes.data, self.nbytes, self.coef_blocks, self.plane_bytes, self.out_bytes))
+
+
+def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None) -> JpegProgPlan:
+    """Pack the ``JpegProgRecord``s of ``parse_jpeg(progressive=True)`` into the host blob of ``hawq_jpeg_decode_batch_prog``: batch header |
+    progressive header | descriptors (entropy fields zero) | scan table | level list | wave lists, level after level | per image: the
+    quantisation tables, then per scan its Huffman tables, intervals and stream - every part at a 16-byte aligned offset.  Computes the
+    level of every scan (``scan_levels``).  ``out_offsets`` / ``out_bytes`` / ``reserve`` as in ``plan_jpeg_batch``."""
+    records = list(records)
+    if not records:
+        raise ValueError("empty batch")
+    n = len(records)
+    n_scans = sum(len(r.scans) for r in records)
+    levels = [lv for r in records for lv in scan_levels(r.scans)]
+    n_levels = max(levels)
+    n_waves = sum(len(s.intervals) for r in records for s in r.scans)
+    desc_off = _align16(_HDR.itemsize + _PHDR.itemsize)
+    scan_off = _align16(desc_off + n * _DESC.itemsize)
+    level_off = _align16(scan_off + n_scans * _SCAN.itemsize)
+    wave_off = _align16(level_off + 4 * (n_levels + 1))
+    at = _align16(wave_off + 8 * n_waves)
+    desc, rows = np.zeros(n, _DESC), []   # rows: the fields of hawq_jpeg_scan, in order
+    parts = []   # (offset, uint8 array)
+
+    def place(arr):
+        nonlocal at
+        raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+        off = at
+        parts.append((off, raw))
+        at = _align16(at + raw.size)
+        return off
+
+    coef_at = plane_at = out_at = k = 0
+    offs = []
+    for i, r in enumerate(records):
+        d = desc[i]
+        d["width"], d["height"], d["ncomp"], d["hs"], d["vs"], d["mcus_x"], d["mcus_y"] = r.width, r.height, r.ncomp, r.hs, r.vs, r.mcus_x, r.mcus_y
+        placed = {}
+        for c, comp in enumerate(r.components):
+            if comp[3] not in placed:
+                placed[comp[3]] = place(r.qtables[comp[3]])
+            d["qt_off"][c] = placed[comp[3]]
+        tables = {}   # id of a table record -> offset: a table stays in force over several scans
+
+        def table(t):
+            if id(t) not in tables:
+                tables[id(t)] = place(t)
+            return tables[id(t)]
+
+        for s in r.scans:
+            dc = [table(t) for t in s.dc or ()]
+            rows.append((i, len(s.comps), s.comps[0], s.ss, s.se, s.ah, s.al, levels[k], tuple(dc + [0] * (3 - len(dc))), 0 if s.ac is None else table(s.ac),
+                         s.restart, len(s.intervals), place(np.ascontiguousarray(s.intervals, np.int32)),
+                         place(np.frombuffer(r.data, np.uint8, s.scan[1] - s.scan[0], s.scan[0])), s.scan[1] - s.scan[0], (0, 0, 0)))
+            k += 1
+        d["coef_block0"], d["plane_off"] = coef_at, plane_at
+        coef_at, plane_at = coef_at + r.blocks, plane_at + r.blocks * 64
+        off = out_at if out_offsets is None else int(out_offsets[i])
+        d["out_off"] = off
+        offs.append(off)
+        out_at = _align16(off + r.width * r.height * 3)
+    if at >= 1 << 31:
+        raise ValueError("batch too large for one blob (2 GiB of compressed data)")
+    scans = np.array(rows, _SCAN)
+    waves, level_start = [], [0]
+    for level in range(1, n_levels + 1):
+        for k in np.flatnonzero(np.array(levels) == level).tolist():
+            waves.append(np.stack([np.full(scans["n_intervals"][k], k, np.int32), np.arange(scans["n_intervals"][k], dtype=np.int32)], 1))
+        level_start.append(sum(len(w) for w in waves))
+    blob = np.zeros(at, np.uint8) if reserve is None else reserve(at)
+    hdr, phdr = np.zeros(1, _HDR), np.zeros(1, _PHDR)
+    hdr["n_images"], hdr["n_waves"], hdr["desc_off"], hdr["wave_off"] = n, n_waves, desc_off, wave_off
+    phdr["n_scans"], phdr["n_levels"], phdr["scan_off"], phdr["level_off"] = n_scans, n_levels, scan_off, level_off
+    for off, arr in ((0, hdr), (_HDR.itemsize, phdr), (desc_off, desc), (scan_off, scans), (level_off, np.array(level_start, np.int32)), (wave_off, np.concatenate(waves))):
+        blob[off:off + arr.nbytes] = arr.view(np.uint8).reshape(-1)
+    for off, raw in parts:
+        blob[off:off + raw.size] = raw
+    plan = JpegProgPlan()
+    plan.blob, plan.nbytes, plan.n_waves, plan.n_scans, plan.levels, plan.n_levels, plan.level_start = blob, at, n_waves, n_scans, levels, n_levels, level_start
+    plan.scan_off, plan.level_off, plan.wave_off, plan.desc_off = scan_off, level_off, wave_off, desc_off
+    plan.coef_blocks, plan.plane_bytes = coef_at, plane_at
+    plan.out_bytes = out_at if out_bytes is None else int(out_bytes)
+    plan.out_offsets, plan.sizes = offs, [(r.height, r.width) for r in records]
+    return plan
+
+
+def _launch_prog(records, out_offsets, out, dev, events=None):
+    """The device call of ``decode_jpeg_batch`` for progressive records: as ``_launch``, with ``plan_jpeg_prog_batch`` /
+    ``hawq_jpeg_decode_batch_prog`` and a staging buffer of its own; writes into ``out``.  Returns the int32 status per record as a
+    device tensor: the caller reads it when everything of the batch is enqueued."""
+    from .image import _STAGING, _Staging
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _STAGING.setdefault((dev.index, "jpeg_prog"), _Staging())
+        held = {}
+
+        def reserve(nbytes):
+            held["host"], held["dev"] = st.reserve(nbytes, dev)
+            return held["host"].numpy()
+
+        plan = plan_jpeg_prog_batch(records, out_offsets, out.numel(), reserve)
+        if not plan.ok():   # on the host blob, before anything is uploaded or launched
+            raise RuntimeError("libhawq_mi355: " + lib.hawq_last_error().decode())
+        st.upload(plan.nbytes)
+        coef = torch.empty(plan.coef_blocks * 64, dtype=torch.int16, device=dev)
+        planes = torch.empty(plan.plane_bytes, dtype=torch.uint8, device=dev)
+        status = torch.empty(len(records), dtype=torch.int32, device=dev)
+        ev = (C.c_void_p * 4)(*events) if events is not None else None
+        _lib.call("hawq_jpeg_decode_batch_prog", held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks, planes.data_ptr(),
+                  plan.plane_bytes, out.data_ptr(), out.numel(), status.data_ptr(), ev, torch.cuda.current_stream(dev).cuda_stream)
+        return status
+
+
+def _launch(records, out_offsets, out_bytes, dev, events=None, sync=None, info=None, out=None):
     """The device call of ``decode_jpeg_batch``: plan into the pinned staging buffer, check, upload in one copy, run the three stages
-    on the current stream.  Returns (uint8 [out_bytes] device tensor, freshly allocated; int32 status per record, on the host - reading
-    it is the one synchronisation of the batch).  ``sync`` = (sub_bytes, min_sync_bytes): ``hawq_jpeg_decode_batch_sync``; a dict
-    ``info`` then receives ``jobs`` (the plan's) and ``rounds`` / ``decodes`` (what the kernel counted per job)."""
+    on the current stream.  Returns (uint8 [out_bytes] device tensor - ``out`` when given, else freshly allocated; int32 status per
+    record, on the host - reading it is the one synchronisation of the batch).  ``sync`` = (sub_bytes, min_sync_bytes):
+    ``hawq_jpeg_decode_batch_sync``; a dict ``info`` then receives ``jobs`` (the plan's) and ``rounds`` / ``decodes`` (what the kernel
+    counted per job)."""
     from .image import _STAGING, _Staging
     lib = _lib.load()
     with torch.cuda.device(dev):
@@ -357,7 +732,8 @@ def _launch(records, out_offsets, out_bytes, dev, events=None, sync=None, info=N
         if not plan.ok() or (sync is not None and not plan.sync_ok()):   # on the host blob, before anything is uploaded or launched
             raise RuntimeError("libhawq_mi355: " + lib.hawq_last_error().decode())
         st.upload(plan.nbytes)
-        out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
         coef = torch.empty(plan.coef_blocks * 64, dtype=torch.int16, device=dev)
         planes = torch.empty(plan.plane_bytes, dtype=torch.uint8, device=dev)
         status = torch.empty(len(records), dtype=torch.int32, device=dev)
@@ -390,7 +766,7 @@ def read_source(source) -> bytes:
         return f.read()
 
 
-def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, min_sync_bytes=None):
+def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, min_sync_bytes=None, progressive=False):
     """Paths or bytes of image files -> ``(images, fallbacks)``: ``images[i]`` a uint8 [H, W, 3] RGB tensor on the MI355X equal to
     ``image.decode_image(sources[i])``, ``fallbacks`` the list of ``(index, reason)`` of the images the HOST decoder produced: files
     ``parse_jpeg`` refuses (progressive, CMYK, not a JPEG, ...) and files whose device decode reported a status (damaged streams).
@@ -398,7 +774,11 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
     them in place.  An error of the host decoder on such a file propagates as it does from ``decode_image``.
     ``entropy``: ``"serial"`` decodes every restart interval with one wave; ``"sync"`` decodes intervals of at least ``min_sync_bytes``
     stream bytes with one lane per ``sub_bytes`` of them (``hawq_jpeg_decode_batch_sync``; defaults ``MIN_SYNC_BYTES`` / ``SUB_BYTES``) -
-    the same bytes and the same fallbacks, faster on files without restart markers."""
+    the same bytes and the same fallbacks, faster on files without restart markers.
+    ``progressive``: progressive files (SOF2) inside the scope of ``parse_progressive`` are decoded on the device as well
+    (``hawq_jpeg_decode_batch_prog``, one wave per scan and restart interval, one entropy launch per level of the batch) into the same
+    allocation, in a second call beside the one for the baseline files; the rest fall back as before.  ``entropy="sync"`` applies to the
+    baseline files only: a progressive scan is decoded by one wave per restart interval."""
     from .image import decode_image
     if entropy not in ("serial", "sync"):
         raise ValueError(f"entropy must be 'serial' or 'sync', not {entropy!r}")
@@ -414,7 +794,7 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
     records, fallbacks, host = {}, [], {}
     for i, data in enumerate(datas):
         try:
-            records[i] = parse_jpeg(data)
+            records[i] = parse_jpeg(data, progressive=True) if progressive else parse_jpeg(data)
         except UnsupportedJpeg as e:
             fallbacks.append((i, e.reason))
             host[i] = decode_image(data)
@@ -423,18 +803,29 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
     for h, w in sizes:
         offsets.append(total)
         total = _align16(total + h * w * 3)
-    order = sorted(records)
-    if order:
-        out, status = _launch([records[i] for i in order], [offsets[i] for i in order], total, dev, **more)
-        for i, st in zip(order, status):
-            if st != 0:
-                fallbacks.append((i, "device status %d: %s" % (st, STATUS_NAMES.get(int(st), "unknown"))))
-                host[i] = decode_image(datas[i])
-                if tuple(host[i].shape[:2]) != sizes[i]:
-                    raise RuntimeError(f"image {i}: the host decoder gives {tuple(host[i].shape[:2])}, the header {sizes[i]}")
+    order = sorted(i for i, r in records.items() if isinstance(r, JpegRecord))
+    prog = sorted(i for i, r in records.items() if isinstance(r, JpegProgRecord))
+    status = {}
+    if prog:   # both calls write into the one allocation; the progressive one is enqueued first and its status read last
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        prog_status = _launch_prog([records[i] for i in prog], [offsets[i] for i in prog], out, dev)
+        if order:
+            status.update(zip(order, _launch([records[i] for i in order], [offsets[i] for i in order], total, dev, out=out, **more)[1]))
+        status.update(zip(prog, prog_status.cpu().numpy()))
+    elif order:
+        out, st = _launch([records[i] for i in order], [offsets[i] for i in order], total, dev, **more)
+        status.update(zip(order, st))
     else:
         out = torch.empty(total, dtype=torch.uint8, device=dev)
+    for i, st in sorted(status.items()):
+        if st != 0:
+            fallbacks.append((i, "device status %d: %s" % (st, STATUS_NAMES.get(int(st), "unknown"))))
+            host[i] = decode_image(datas[i])
+            if tuple(host[i].shape[:2]) != sizes[i]:
+                raise RuntimeError(f"image {i}: the host decoder gives {tuple(host[i].shape[:2])}, the header {sizes[i]}")
     for i, im in host.items():
         out[offsets[i]:offsets[i] + im.numel()].copy_(im.reshape(-1))
     images = [out[offsets[i]:offsets[i] + h * w * 3].view(h, w, 3) for i, (h, w) in enumerate(sizes)]
     return images, sorted(fallbacks)
+
+

@@ -767,6 +767,51 @@ int hawq_jpeg_decode_batch_sync(const void *blob, const void *host_blob, int64_t
                                 int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, int32_t sub_bytes, int32_t min_sync_bytes,
                                 int64_t jobs_off, int32_t n_jobs, void *scratch, int64_t scratch_bytes, void *const *events, void *stream);
 
+/* ---- progressive JPEGs (SOF2, Huffman; hawq_amd/csrc/jpeg_prog.hip + jpeg_prog.h) --------------------------------
+ * The blob begins as the baseline one: hawq_jpeg_batch_hdr, then hawq_jpeg_desc[n_images], whose entropy fields (dc_off, ac_off,
+ * stream_off, stream_len, interval_off, restart, n_intervals) are zero; stages 2 and 3 read nothing else.  Behind the batch header, at
+ * byte 16, stands a hawq_jpeg_prog_hdr.  The scan table lists the scans of image 0 in file order, then image 1's, ...  The wave list at
+ * hawq_jpeg_batch_hdr.wave_off holds hawq_jpeg_prog_wave[n_waves], level after level: the waves of level L are
+ * level_start[L - 1] .. level_start[L] - 1 (int32 level_start[n_levels + 1] at level_off), and within a level they name every interval
+ * of every scan of that level, in the order of the scan table.
+ * level(scan) = 1 + the largest level of the earlier scans of the same image that share a (component, coefficient) with it, 1 without
+ * one: the scans of one level write disjoint int16 words, so one launch per level decodes them side by side.
+ * An interleaved scan (ncomp = the image's) walks the image's MCUs as the baseline decoder does; a scan of one component walks that
+ * component's own grid of ceil(ceil(width * h / hs) / 8) x ceil(ceil(height * v / vs) / 8) blocks in raster order (not the MCU-padded
+ * grid of the slab), and its restart interval counts those blocks. */
+enum { HAWQ_JPEG_PROG_MAX_SCANS = 64 };   /* per image; no progression has more levels than scans */
+typedef struct hawq_jpeg_prog_hdr {    /* at byte 16 of the blob */
+    int32_t n_scans, n_levels;
+    int32_t scan_off;                  /* hawq_jpeg_scan[n_scans]; 16-byte aligned */
+    int32_t level_off;                 /* int32 [n_levels + 1]; 16-byte aligned */
+} hawq_jpeg_prog_hdr;
+typedef struct hawq_jpeg_prog_wave {   /* one wave of the entropy stage: one restart interval of one scan */
+    int32_t scan, interval;
+} hawq_jpeg_prog_wave;
+typedef struct hawq_jpeg_scan {
+    int32_t image;
+    int32_t ncomp, comp0;              /* components comp0 .. comp0 + ncomp - 1: one of them, or all (comp0 = 0) */
+    int32_t ss, se, ah, al;            /* ss <= se <= 63, se = 0 when ss = 0, ncomp = 1 when ss > 0; al <= 13; ah = 0 or al + 1 */
+    int32_t level;
+    int32_t dc_off[3];                 /* hawq_jpeg_huff of the scan's i-th component: read when ss = 0 and ah = 0 */
+    int32_t ac_off;                    /* hawq_jpeg_huff: read when ss > 0 */
+    int32_t restart, n_intervals;      /* MCUs (blocks, in a scan of one component) per restart interval, 0: one interval */
+    int32_t interval_off;              /* int32 [n_intervals][2], relative to stream_off */
+    int32_t stream_off, stream_len;    /* this scan's entropy-coded segment; 16-byte aligned */
+    int32_t reserved[3];
+} hawq_jpeg_scan;                      /* 80 bytes */
+/* hawq_jpeg_prog_ok launches nothing and reads the HOST blob: 1 when every offset and length lies inside the blob at its alignment, the
+ * geometry is accepted, each scan's interval count follows from its grid, every interval lies inside its scan's stream, the Huffman
+ * tables a scan reads are canonical, the scans of every image form a legal and COMPLETE progression (per component and coefficient: the
+ * first scan has ah = 0, each later one ah = the previous al, DC before AC, al = 0 in the end), every scan's level is exactly the one
+ * the rule above gives, the wave lists are as described, and the slab / plane / output slices are disjoint and in bounds; else 0 with
+ * the reason in hawq_last_error().
+ * hawq_jpeg_decode_batch_prog checks again, zeroes coef and status, launches one entropy grid per level on `stream` and then stages 2
+ * and 3 of hawq_jpeg_decode_batch.  status and events as there; the second event is recorded behind the last level. */
+int hawq_jpeg_prog_ok(const void *host_blob, int64_t blob_bytes, int64_t coef_blocks, int64_t plane_bytes, int64_t out_bytes);
+int hawq_jpeg_decode_batch_prog(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                                int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *const *events, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

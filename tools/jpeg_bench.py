@@ -16,8 +16,13 @@ stage of the second path and the decode passes ("rounds") the kernel counted for
 stage of the sync path for sub_bytes in 32 / 64 / 128 / 256 and min_sync_bytes in 256 / 1024 / 4096, each row alternating with the
 serial stage.  ``--sets`` picks sets by index.
 
+``--progressive`` measures progressive files instead (``PROGRESSIVE_SETS``: the sample re-encoded with ``progressive=True``, and batches
+of which a quarter is progressive): host, ``device_decode`` as it is without the option (every progressive file falls back to Pillow on
+the calling thread, one after the other) and ``decode_jpeg_batch(progressive=True)``, the three alternating in one process; then the
+stages of ``hawq_jpeg_decode_batch_prog`` with HIP events (stage 1: all its levels).  Writes profiles/jpeg_progressive.md.
+
     python tools/jpeg_bench.py [--batch 128] [--repeats 20] [--warmup 3] [--out profiles/jpeg_decode.md] [--box NAME]
-                               [--entropy serial|sync|both] [--sub-bytes N] [--min-sync-bytes N] [--sweep] [--sets 0,1,3]
+                               [--entropy serial|sync|both] [--sub-bytes N] [--min-sync-bytes N] [--sweep] [--sets 0,1,3] [--progressive]
 """
 import argparse
 import ctypes as C
@@ -43,6 +48,19 @@ SETS = {
     "mixed sizes / qualities / subsamplings": [(s, dict(quality=q, subsampling=ss)) for s in (0.75, 1.0, 1.5) for q in (75, 90, 95) for ss in (0, 1, 2)],
     "mixed, restart every MCU row": [(s, dict(quality=q, subsampling=ss, restart_marker_rows=1)) for s in (0.75, 1.0, 1.5) for q in (75, 90, 95)
                                      for ss in (0, 1, 2)],
+}
+
+
+_P = dict(progressive=True)
+# name -> list of (scale, save options) cycled over the batch; every fourth file of a "quarter" set is progressive
+PROGRESSIVE_SETS = {
+    "375x500 q90 4:2:0, all progressive": [(1.0, dict(quality=90, subsampling=2, **_P))],
+    "375x500 q90 4:2:0, all progressive, restart every MCU row": [(1.0, dict(quality=90, subsampling=2, restart_marker_rows=1, **_P))],
+    "mixed sizes / qualities / subsamplings, all progressive": [(s, dict(quality=q, subsampling=ss, **_P)) for s in (0.75, 1.0, 1.5) for q in (75, 90, 95)
+                                                                 for ss in (0, 1, 2)],
+    "375x500 q90 4:2:0, a quarter progressive": [(1.0, dict(quality=90, subsampling=2, **(_P if k == 3 else {}))) for k in range(4)],
+    "375x500 q90 4:2:0 restart every MCU row, a quarter progressive": [(1.0, dict(quality=90, subsampling=2, restart_marker_rows=1, **(_P if k == 3 else {})))
+                                                                        for k in range(4)],
 }
 
 
@@ -76,7 +94,8 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode.md"))
+    ap.add_argument("--out", default=None, help="default: profiles/jpeg_decode.md, with --progressive profiles/jpeg_progressive.md")
+    ap.add_argument("--progressive", action="store_true", help="progressive files: host, device_decode without and with progressive=True")
     ap.add_argument("--box", default=None, help="label of the machine for the report (default: the device name and architecture)")
     ap.add_argument("--entropy", choices=("serial", "sync", "both"), default="serial")
     ap.add_argument("--sub-bytes", type=int, default=jpeg.SUB_BYTES)
@@ -84,6 +103,7 @@ def main():
     ap.add_argument("--sweep", action="store_true", help="entropy stage of the sync path over a grid of sub_bytes x min_sync_bytes")
     ap.add_argument("--sets", default=None, help="comma-separated indices into SETS (default: all)")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
     paths = ("serial", "sync") if args.entropy == "both" else (args.entropy,)
     sync_of = {"serial": None, "sync": (args.sub_bytes, args.min_sync_bytes)}
     picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(SETS))
@@ -98,6 +118,8 @@ def main():
         ev = C.c_void_p()
         _lib.check(lib.hawq_event_create(C.byref(ev)))
         events.append(ev)
+    if args.progressive:
+        return progressive(args, box, dev, lib, events)
     rows, sweep_rows = [], []
     for label, variants in [list(SETS.items())[k] for k in picked]:
         datas = make_set(variants, args.batch)
@@ -202,6 +224,88 @@ def main():
                   "| set | sub_bytes | min_sync_bytes | jobs | serial entropy | sync entropy | rounds of the largest interval |", "|---|---|---|---|---|---|---|"]
         for r in sweep_rows:
             lines.append(f"| {r['set']} | {r['sub_bytes']} | {r['min_sync_bytes']} | {r['jobs']} | {f(r['serial_entropy_ms'])} | {f(r['sync_entropy_ms'])} | {r['rounds_largest']} |")
+    lines.append("")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines))
+    print("wrote", args.out)
+
+
+def progressive(args, box, dev, lib, events):
+    """the ``--progressive`` report"""
+    picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(PROGRESSIVE_SETS))
+    rows = []
+    for label, variants in [list(PROGRESSIVE_SETS.items())[k] for k in picked]:
+        datas = make_set(variants, args.batch)
+        samples = [(d, 0) for d in datas]
+        records = [jpeg.parse_jpeg(d, progressive=True) for d in datas]
+        prog = [r for r in records if isinstance(r, jpeg.JpegProgRecord)]
+
+        def host():
+            imgs, _ = next(iter(image.decoded_batches(samples, len(samples), workers=16)))
+            return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
+
+        def device(option):
+            imgs, fallbacks = jpeg.decode_jpeg_batch(datas, dev, **({"progressive": True} if option else {}))
+            assert len(fallbacks) == (0 if option else len(prog)), fallbacks
+            return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
+
+        runs = {"host": host, "device": lambda: device(False), "progressive": lambda: device(True)}
+        want = host()
+        for name in ("device", "progressive"):
+            if not torch.equal(want, runs[name]()):
+                sys.exit(f"jpeg_bench: the host path and the {name} path differ at {label}")
+        for _ in range(args.warmup):
+            for fn in runs.values():
+                fn()
+        t = {name: [] for name in runs}
+        order = list(runs)
+        for r in range(args.repeats):
+            for name in order[r % len(order):] + order[:r % len(order)]:   # every path takes every place in turn
+                t[name].append(wall(runs[name]))
+        # the stages of the progressive call alone: parsed once, planned + uploaded + launched per call
+        offsets, total = [], 0
+        for r in prog:
+            offsets.append(total)
+            total = (total + r.width * r.height * 3 + 15) & ~15
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        stages = ([], [], [])
+        for k in range(args.warmup + args.repeats):
+            status = jpeg._launch_prog(prog, offsets, out, dev, events).cpu()   # reads the status: synchronised
+            assert not status.any()
+            if k >= args.warmup:
+                for s in range(3):
+                    ms = C.c_float()
+                    _lib.check(lib.hawq_event_elapsed_ms(events[s], events[s + 1], C.byref(ms)))
+                    stages[s].append(ms.value)
+        plan = jpeg.plan_jpeg_prog_batch(prog, offsets, total)
+        per_level = {}   # level -> the longest interval of a scan of that level
+        for r in prog:
+            for s, level in zip(r.scans, jpeg.scan_levels(r.scans)):
+                per_level[level] = max(per_level.get(level, 0), int((s.intervals[:, 1] - s.intervals[:, 0]).max()))
+        row = {"set": label, "n": len(datas), "progressive": len(prog), "compressed_mb": sum(map(len, datas)) / 1e6, "levels": plan.n_levels, "waves": plan.n_waves,
+               "largest_interval_per_level": [per_level[k] for k in sorted(per_level)], "entropy_ms": stat(stages[0]), "idct_ms": stat(stages[1]),
+               "colour_ms": stat(stages[2])}
+        for name in runs:
+            row[name + "_wall_ms"] = stat(t[name])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    f = lambda v: f"{v[0]:.2f} ({v[1]:.2f}-{v[2]:.2f})"
+    lines = ["# Progressive JPEG bytes in memory to the cropped batch on the device", "",
+             f"Measured on one {box} with `python tools/jpeg_bench.py --progressive --batch {args.batch} --repeats {args.repeats} --warmup {args.warmup}`: median "
+             f"(min-max) of {args.repeats} calls in milliseconds, the three paths alternating in one process; outputs compared byte for byte first.  Resize / crop "
+             "256 / 224.", "`host`: Pillow in 16 threads + `preprocess_batch_fused`.  `device`: `decode_jpeg_batch` as it is without the option (a progressive file "
+             "falls back to Pillow on the calling thread) + `preprocess_batch_fused`.  `progressive`: the same with `progressive=True`.  All: host clock around the "
+             "call and a device synchronise.  Stages: HIP events around the launches of `hawq_jpeg_decode_batch_prog` for the progressive files of the set alone "
+             "(entropy: all its levels).", "",
+             "| set | progressive files | MB compressed | host wall | device wall | progressive wall | progressive / host | progressive / device |", "|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['n']} x {r['set']} | {r['progressive']} | {r['compressed_mb']:.1f} | {f(r['host_wall_ms'])} | {f(r['device_wall_ms'])} | "
+                     f"{f(r['progressive_wall_ms'])} | {r['progressive_wall_ms'][0] / r['host_wall_ms'][0]:.2f} | {r['progressive_wall_ms'][0] / r['device_wall_ms'][0]:.2f} |")
+    lines += ["", "| set | levels | waves | largest interval per level (bytes) | entropy, all levels | IDCT | upsample + colour |", "|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['n']} x {r['set']} | {r['levels']} | {r['waves']} | {' / '.join(map(str, r['largest_interval_per_level']))} | {f(r['entropy_ms'])} | "
+                     f"{f(r['idct_ms'])} | {f(r['colour_ms'])} |")
     lines.append("")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
