@@ -1,16 +1,20 @@
-"""Batched baseline JPEG decoding on the MI355X (DESIGN.md "Device JPEG decode"): file bytes -> uint8 HWC RGB tensors on the device,
-byte for byte what ``image.decode_image`` (Pillow: libjpeg-turbo, ISLOW IDCT, fancy upsampling) gives on the host.
+"""Batched JPEG decoding on the MI355X (DESIGN.md "Device JPEG decode"): file bytes -> uint8 HWC RGB tensors on the device, byte for
+byte what ``image.decode_image`` (Pillow: libjpeg-turbo, ISLOW IDCT, fancy upsampling) gives on the host.
 
-Host side, pure Python / numpy: ``parse_jpeg`` reads the headers of one file and refuses (``UnsupportedJpeg``) whatever the device
-path does not take; ``plan_jpeg_batch`` packs the descriptors, tables, entropy-coded bytes and restart intervals of a batch into one
-blob (``struct hawq_jpeg_*`` of include/hawq_mi355.h); ``decode_jpeg_batch`` uploads it in one pinned copy, runs
-``hawq_jpeg_decode_batch`` (entropy decode -> IDCT -> upsampling + colour) and hands every refused or failed image to the host decoder,
-with the reason.  ``image.folder_loader(device_decode=True)`` feeds the result to ``preprocess_batch_fused`` in place.
-``entropy="sync"`` decodes long restart intervals with many lanes each (``hawq_jpeg_decode_batch_sync``): the planner
-appends a job table, ``hawq_jpeg_sync_ok`` checks it, the launch gets a scratch buffer; everything else is the same.
-``progressive=True`` takes progressive files (SOF2) too: ``parse_jpeg`` returns a ``JpegProgRecord`` with the list of
-scans, ``plan_jpeg_prog_batch`` packs them with the level of every scan, ``hawq_jpeg_decode_batch_prog`` decodes them, one entropy
-launch per level, into the same output allocation as the baseline files of the batch.
+Host side, pure Python / numpy, one of each:
+- one marker walker (``_parse``) reads a file once, front to back, and refuses (``UnsupportedJpeg``) whatever the device path does not
+  take.  ``parse_jpeg`` gives a ``JpegRecord`` for a baseline file and, with ``progressive=True``, a ``JpegProgRecord`` with the list of
+  scans for a progressive one (SOF2): the file is baseline until its frame header says otherwise, and only what the two
+  kinds do differently at an SOS is written per kind.
+- one blob writer (``_Blob``) and one geometry filler (``_Plan``) under the two planners: ``plan_jpeg_batch`` packs descriptors, tables,
+  entropy-coded bytes and restart intervals of baseline records (``struct hawq_jpeg_*`` of include/hawq_mi355.h), with ``sync`` also the
+  job table of ``entropy="sync"`` (many lanes per long restart interval); ``plan_jpeg_prog_batch`` packs progressive
+  records with the level of every scan.
+- one launch (``_launch``) plans into a pinned staging buffer, has the library check the blob, uploads it in one copy and runs
+  ``hawq_jpeg_decode_batch`` / ``_sync`` / ``_prog`` (entropy decode -> IDCT -> upsampling + colour) into the caller's output.
+``decode_jpeg_batch`` allocates the output, launches the progressive and the baseline files of a batch and hands every refused or failed
+image to the host decoder, with the reason.  ``image.folder_loader(device_decode=True)`` feeds the result to ``preprocess_batch_fused``
+in place.
 """
 from __future__ import annotations
 
@@ -65,182 +69,6 @@ class JpegRecord:
         return self.mcus_x * self.mcus_y * (1 if self.ncomp == 1 else self.hs * self.vs + 2)
 
 
-def huffman_table(bits, values):
-    """BITS (16 counts) + HUFFVAL -> one ``_lib.JpegHuff`` record: canonical mincode / maxcode / valptr per code length (T.81 F.2.2.3)."""
-    t = np.zeros(1, _HUFF)
-    mincode, maxcode, valptr = t["mincode"][0], t["maxcode"][0], t["valptr"][0]
-    maxcode[:] = -1
-    code = k = 0
-    for length in range(1, 17):
-        n = int(bits[length - 1])
-        if n:
-            valptr[length], mincode[length] = k, code
-            code, k = code + n, k + n
-            maxcode[length] = code - 1
-            if code > (1 << length):
-                raise UnsupportedJpeg("bad Huffman table")
-        code <<= 1
-    if k == 0 or k > 256 or k != len(values):
-        raise UnsupportedJpeg("bad Huffman table")
-    t["huffval"][0][:k] = np.frombuffer(bytes(values), np.uint8)
-    return t
-
-
-_SOF_REASON = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)"}
-
-
-def parse_jpeg(data, progressive=False):
-    """Headers of one JPEG file (bytes) -> ``JpegRecord``, or ``UnsupportedJpeg(reason)`` for anything outside the device path:
-    baseline SOF0 with 8-bit samples and tables, one interleaved scan of all components, Huffman table ids 0 and 1, three components
-    with ids 1, 2, 3, luma 1x1 / 2x1 / 2x2 and chroma 1x1 without an Adobe marker, or one 1x1 component, restart markers complete
-    and in order, both sides at most 8192.  ``progressive``: a progressive Huffman file (SOF2) with the same components, sampling and
-    sizes, whose scans form a legal and complete progression (``parse_progressive``), gives a ``JpegProgRecord`` instead of the refusal
-    "progressive (SOF2)"; baseline files parse as without it."""
-    data = bytes(data)
-    n = len(data)
-    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
-        raise UnsupportedJpeg("not a JPEG")
-    rec = JpegRecord()
-    rec.data, rec.qtables, rec.huffman, rec.restart = data, {}, {}, 0
-    frame, adobe, pos = None, False, 2
-
-    def need(upto):
-        if upto > n:
-            raise UnsupportedJpeg("truncated header")
-
-    while True:
-        need(pos + 2)
-        if data[pos] != 0xFF:
-            raise UnsupportedJpeg("marker expected")
-        while data[pos + 1] == 0xFF:   # fill bytes
-            pos += 1
-            need(pos + 2)
-        marker = data[pos + 1]
-        pos += 2
-        if marker == 0xD8 or marker == 0x01 or 0xD0 <= marker <= 0xD7:
-            continue
-        if marker == 0xD9:
-            raise UnsupportedJpeg("no scan")
-        need(pos + 2)
-        length = (data[pos] << 8) | data[pos + 1]
-        if length < 2:
-            raise UnsupportedJpeg("bad segment length")
-        need(pos + length)
-        seg = data[pos + 2:pos + length]
-        if marker == 0xC0:
-            if frame is not None:
-                raise UnsupportedJpeg("several frames")
-            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
-                raise UnsupportedJpeg("bad frame header")
-            if seg[0] != 8:
-                raise UnsupportedJpeg("sample precision not 8")
-            rec.height, rec.width = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4]
-            if rec.height == 0:
-                raise UnsupportedJpeg("DNL (height in the scan)")
-            if rec.width == 0:
-                raise UnsupportedJpeg("bad frame header")
-            if seg[5] == 4:
-                raise UnsupportedJpeg("four components")
-            if seg[5] not in (1, 3):
-                raise UnsupportedJpeg("component count")
-            frame = [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(seg[5])]
-        elif marker in (0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF):
-            raise UnsupportedJpeg("arithmetic coding")
-        elif marker == 0xC2 and progressive:
-            return parse_progressive(data)
-        elif marker in (0xC1, 0xC2, 0xC3, 0xC5, 0xC6, 0xC7):
-            raise UnsupportedJpeg(_SOF_REASON.get(marker, "SOF%d" % (marker - 0xC0)))
-        elif marker == 0xC4:
-            at = 0
-            while at < len(seg):
-                if at + 17 > len(seg):
-                    raise UnsupportedJpeg("bad Huffman table")
-                tc, th = seg[at] >> 4, seg[at] & 15
-                bits = seg[at + 1:at + 17]
-                count = sum(bits)
-                if tc > 1 or at + 17 + count > len(seg):
-                    raise UnsupportedJpeg("bad Huffman table")
-                if th > 1:
-                    raise UnsupportedJpeg("Huffman table id above 1")
-                rec.huffman[(tc, th)] = huffman_table(bits, seg[at + 17:at + 17 + count])
-                at += 17 + count
-        elif marker == 0xDB:
-            at = 0
-            while at < len(seg):
-                pq, tq = seg[at] >> 4, seg[at] & 15
-                if pq != 0:
-                    raise UnsupportedJpeg("16-bit quantisation table")
-                if tq > 3 or at + 65 > len(seg):
-                    raise UnsupportedJpeg("bad quantisation table")
-                rec.qtables[tq] = np.frombuffer(seg[at + 1:at + 65], np.uint8).astype(np.uint16)
-                at += 65
-        elif marker == 0xDD:
-            if len(seg) != 2:
-                raise UnsupportedJpeg("bad restart interval")
-            rec.restart = (seg[0] << 8) | seg[1]
-        elif marker == 0xDC:
-            raise UnsupportedJpeg("DNL")
-        elif marker == 0xEE:
-            adobe = adobe or seg[:5] == b"Adobe"
-        elif marker == 0xDA:
-            break
-        pos += length
-    # the scan header
-    if frame is None:
-        raise UnsupportedJpeg("scan before the frame header")
-    if adobe:
-        raise UnsupportedJpeg("Adobe marker")
-    if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
-        raise UnsupportedJpeg("bad scan header")
-    if seg[0] != len(frame):
-        raise UnsupportedJpeg("several scans")
-    if seg[-3] != 0 or seg[-2] != 63 or seg[-1] != 0:
-        raise UnsupportedJpeg("spectral selection or successive approximation")
-    comps = []
-    for i, (cid, h, v, tq) in enumerate(frame):
-        if seg[1 + 2 * i] != cid:
-            raise UnsupportedJpeg("scan component order")
-        td, ta = seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15
-        if td > 1 or ta > 1:
-            raise UnsupportedJpeg("Huffman table id above 1")
-        if tq not in rec.qtables or (0, td) not in rec.huffman or (1, ta) not in rec.huffman:
-            raise UnsupportedJpeg("missing table")
-        comps.append((cid, h, v, tq, td, ta))
-    if len(comps) == 3:
-        if [c[0] for c in comps] != [1, 2, 3]:
-            raise UnsupportedJpeg("component ids not 1, 2, 3")
-        if (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
-            raise UnsupportedJpeg("sampling factors")
-    elif (comps[0][1], comps[0][2]) != (1, 1):
-        raise UnsupportedJpeg("sampling factors")
-    if rec.width > MAX_SIDE or rec.height > MAX_SIDE:
-        raise UnsupportedJpeg("a side above 8192")
-    rec.components, rec.hs, rec.vs = tuple(comps), comps[0][1], comps[0][2]
-    rec.mcus_x, rec.mcus_y = -(-rec.width // (8 * rec.hs)), -(-rec.height // (8 * rec.vs))
-    # the entropy-coded segment: up to the first marker that is no RSTn; behind it nothing but EOI may follow
-    start = pos + length
-    arr = np.frombuffer(data, np.uint8)
-    ff = np.flatnonzero(arr[start:n - 1] == 0xFF) + start
-    nxt = arr[ff + 1]
-    marks = ff[(nxt != 0) & (nxt != 0xFF)]
-    codes = arr[marks + 1]
-    ends = np.flatnonzero((codes & 0xF8) != 0xD0)
-    if ends.size == 0:
-        raise UnsupportedJpeg("truncated scan")
-    if codes[ends[0]] != 0xD9:
-        raise UnsupportedJpeg("DNL" if codes[ends[0]] == 0xDC else "several scans")
-    end = int(marks[ends[0]])
-    rst, rst_codes = marks[:ends[0]], codes[:ends[0]]
-    mcus = rec.mcus_x * rec.mcus_y
-    expected = -(-mcus // rec.restart) - 1 if rec.restart else 0
-    if rst.size != expected or not np.array_equal(rst_codes & 7, np.arange(rst.size) & 7):
-        raise UnsupportedJpeg("restart markers missing or out of order")
-    firsts = np.concatenate([[start], rst + 2]) - start
-    lasts = np.concatenate([rst, [end]]) - start
-    rec.scan, rec.intervals = (start, end), np.stack([firsts, lasts], 1).astype(np.int32)
-    return rec
-
-
 class JpegScan:
     """One scan of a progressive file.  ``comps``: indices into the record's ``components`` (one, or all of them in order); ``ss`` ``se``
     ``ah`` ``al``; ``dc``: the DC table (``_lib.JpegHuff`` record) in force at the SOS per component of the scan when it is a first DC
@@ -274,31 +102,147 @@ def scan_levels(scans):
     return levels
 
 
-def parse_progressive(data) -> JpegProgRecord:
-    """Headers and scans of one progressive Huffman JPEG -> ``JpegProgRecord``, or ``UnsupportedJpeg(reason)``.  Accepted: SOF2 with 8-bit
-    samples and tables, components and sampling as in the baseline path, no Adobe marker, sides at most 8192; 1 to 64 scans, each of all
-    components or of one (AC scans: of one), Ss <= Se <= 63 with Se = 0 when Ss = 0, Al <= 13, Ah = 0 or Al + 1, Huffman table ids 0..3;
-    per (component, coefficient) the first scan has Ah = 0, each later one Ah = the previous Al, the DC comes before any AC, and after
-    the last scan everything has reached Al = 0 ("progression" otherwise: the library smooths an incomplete file, the device does not);
-    between scans only DHT / DRI / COM / APPn segments; restart markers complete and in order per scan; EOI behind the last scan."""
+def huffman_table(bits, values):
+    """BITS (16 counts) + HUFFVAL -> one ``_lib.JpegHuff`` record: canonical mincode / maxcode / valptr per code length (T.81 F.2.2.3)."""
+    t = np.zeros(1, _HUFF)
+    mincode, maxcode, valptr = t["mincode"][0], t["maxcode"][0], t["valptr"][0]
+    maxcode[:] = -1
+    code = k = 0
+    for length in range(1, 17):
+        n = int(bits[length - 1])
+        if n:
+            valptr[length], mincode[length] = k, code
+            code, k = code + n, k + n
+            maxcode[length] = code - 1
+            if code > (1 << length):
+                raise UnsupportedJpeg("bad Huffman table")
+        code <<= 1
+    if k == 0 or k > 256 or k != len(values):
+        raise UnsupportedJpeg("bad Huffman table")
+    t["huffval"][0][:k] = np.frombuffer(bytes(values), np.uint8)
+    return t
+
+
+# ------------------------------------------------------------------------------------------------------------------ the marker walker
+_SOF0, _SOF2, _DHT, _DQT, _DRI, _DNL, _SOS, _EOI, _ADOBE, _COM = 0xC0, 0xC2, 0xC4, 0xDB, 0xDD, 0xDC, 0xDA, 0xD9, 0xEE, 0xFE
+_SOF_HUFFMAN = (_SOF0, 0xC1, _SOF2, 0xC3, 0xC5, 0xC6, 0xC7)
+_SOF_ARITHMETIC = (0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF)
+_SOF_REASON = {0xC1: "extended sequential (SOF1)", _SOF2: "progressive (SOF2)"}
+
+
+def _frame_header(seg):
+    """An SOF segment -> (height, width, [(component id, h, v, quantisation table id)])"""
+    bad = UnsupportedJpeg("bad frame header")
+    if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+        raise bad
+    if seg[0] != 8:
+        raise UnsupportedJpeg("sample precision not 8")
+    height, width = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4]
+    if height == 0:
+        raise UnsupportedJpeg("DNL (height in the scan)")
+    if width == 0:
+        raise bad
+    if seg[5] == 4:
+        raise UnsupportedJpeg("four components")
+    if seg[5] not in (1, 3):
+        raise UnsupportedJpeg("component count")
+    return height, width, [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(seg[5])]
+
+
+def _huffman_tables(seg, limit, into):
+    """A DHT segment into ``into``: {(class, id): record}; ``limit``: the largest table id the frame kind takes"""
+    at = 0
+    while at < len(seg):
+        if at + 17 > len(seg):
+            raise UnsupportedJpeg("bad Huffman table")
+        tc, th = seg[at] >> 4, seg[at] & 15
+        bits = seg[at + 1:at + 17]
+        count = sum(bits)
+        if tc > 1 or at + 17 + count > len(seg):
+            raise UnsupportedJpeg("bad Huffman table")
+        if th > limit:
+            raise UnsupportedJpeg("Huffman table id above %d" % limit)
+        into[(tc, th)] = huffman_table(bits, seg[at + 17:at + 17 + count])
+        at += 17 + count
+
+
+def _quantisation_tables(seg, into):
+    """A DQT segment into ``into``: {id: uint16 [64]}"""
+    at = 0
+    while at < len(seg):
+        pq, tq = seg[at] >> 4, seg[at] & 15
+        if pq != 0:
+            raise UnsupportedJpeg("16-bit quantisation table")
+        if tq > 3 or at + 65 > len(seg):
+            raise UnsupportedJpeg("bad quantisation table")
+        into[tq] = np.frombuffer(seg[at + 1:at + 65], np.uint8).astype(np.uint16)
+        at += 65
+
+
+def _accept_frame(rec, comps):
+    """The frame both kinds of file must have: component ids, sampling, sizes.  ``comps``: (id, h, v, quantisation table id, DC table
+    id, AC table id) per component, the last two None in a progressive record.  Fills the geometry of ``rec``."""
+    if len(comps) == 3:
+        if [c[0] for c in comps] != [1, 2, 3]:
+            raise UnsupportedJpeg("component ids not 1, 2, 3")
+        if (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            raise UnsupportedJpeg("sampling factors")
+    elif (comps[0][1], comps[0][2]) != (1, 1):
+        raise UnsupportedJpeg("sampling factors")
+    if rec.width > MAX_SIDE or rec.height > MAX_SIDE:
+        raise UnsupportedJpeg("a side above 8192")
+    rec.components, rec.hs, rec.vs = tuple(comps), comps[0][1], comps[0][2]
+    rec.mcus_x, rec.mcus_y = -(-rec.width // (8 * rec.hs)), -(-rec.height // (8 * rec.vs))
+
+
+class _Markers:
+    """Every FF xx of a file with xx neither stuffing (00) nor fill (FF): where (``at``), which (``code``), and the indices of those
+    that are no RSTn (``ends``): one of these ends an entropy-coded segment."""
+
+    def __init__(self, data):
+        arr = np.frombuffer(data, np.uint8)
+        ff = np.flatnonzero(arr[:-1] == 0xFF)
+        nxt = arr[ff + 1]
+        keep = (nxt != 0) & (nxt != 0xFF)
+        self.at, self.code = ff[keep], nxt[keep]
+        self.at_list, self.ends = self.at.tolist(), np.flatnonzero((self.code & 0xF8) != 0xD0).tolist()
+
+    def entropy_segment(self, start, units, restart, last=False):
+        """The entropy-coded segment from ``start`` -> (end: the first marker that is no RSTn, int32 [n, 2] restart intervals relative to
+        ``start``), its RSTn markers complete and in order for ``units`` units at ``restart`` per interval.  ``last``: nothing but EOI
+        may end it."""
+        first = bisect.bisect_left(self.at_list, start)
+        k = bisect.bisect_left(self.ends, first)
+        if k == len(self.ends):
+            raise UnsupportedJpeg("truncated scan")
+        stop = self.ends[k]
+        end = self.at_list[stop]
+        if last and self.code[stop] != _EOI:
+            raise UnsupportedJpeg("DNL" if self.code[stop] == _DNL else "several scans")
+        expected = -(-units // restart) - 1 if restart else 0
+        if stop - first != expected or (expected and ((self.code[first:stop] - np.arange(expected)) & 7).any()):   # RSTn counts modulo 8
+            raise UnsupportedJpeg("restart markers missing or out of order")
+        intervals = np.empty((expected + 1, 2), np.int32)
+        intervals[0, 0], intervals[-1, 1] = 0, end - start
+        if expected:
+            rst = self.at[first:stop] - start   # the RSTn markers inside
+            intervals[1:, 0], intervals[:-1, 1] = rst + 2, rst
+        return end, intervals
+
+
+def _parse(data, progressive, prog):
+    """The one walk over a file.  ``progressive``: SOF2 is taken; ``prog``: the file counts as progressive (from the start for
+    ``parse_progressive``, else from its SOF2 on): Huffman table ids up to 3, and an SOS adds a scan instead of ending the walk."""
     data = bytes(data)
     n = len(data)
     if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
         raise UnsupportedJpeg("not a JPEG")
-    rec = JpegProgRecord()
-    rec.data, rec.qtables, rec.scans = data, {}, []
-    huffman, restart, frame, adobe, pos = {}, 0, None, False, 2
-    state = np.full((3, 64), -1, np.int32)   # per (component, coefficient): the Al reached, -1 before its first scan
-    arr = np.frombuffer(data, np.uint8)
-    ff = np.flatnonzero(arr[:n - 1] == 0xFF)
-    nxt = arr[ff + 1]
-    all_marks = ff[(nxt != 0) & (nxt != 0xFF)]   # FF xx, xx neither stuffing nor fill
-    mark_list = all_marks.tolist()
-    ends = all_marks[(arr[all_marks + 1] & 0xF8) != 0xD0].tolist()   # those that are no RSTn: one of them ends an entropy-coded segment
+    qtables, huffman, scans = {}, {}, []
+    restart, frame, adobe, pos = 0, None, False, 2
 
     def need(upto):
         if upto > n:
-            raise UnsupportedJpeg("truncated header" if not rec.scans else "truncated scan")
+            raise UnsupportedJpeg("truncated scan" if scans else "truncated header")
 
     while True:
         need(pos + 2)
@@ -309,12 +253,12 @@ def parse_progressive(data) -> JpegProgRecord:
             need(pos + 2)
         marker = data[pos + 1]
         pos += 2
-        if marker == 0xD9:
-            if not rec.scans:
+        if marker == _EOI:
+            if not scans:
                 raise UnsupportedJpeg("no scan")
             break
-        if rec.scans and not (marker in (0xC4, 0xDD, 0xFE, 0xDA) or 0xE0 <= marker <= 0xEF):
-            raise UnsupportedJpeg("DNL" if marker == 0xDC else "DQT between scans" if marker == 0xDB else "marker %02X between scans" % marker)
+        if scans and not (marker in (_DHT, _DRI, _COM, _SOS) or 0xE0 <= marker <= 0xEF):
+            raise UnsupportedJpeg("DNL" if marker == _DNL else "DQT between scans" if marker == _DQT else "marker %02X between scans" % marker)
         if marker == 0xD8 or marker == 0x01 or 0xD0 <= marker <= 0xD7:
             continue
         need(pos + 2)
@@ -324,112 +268,108 @@ def parse_progressive(data) -> JpegProgRecord:
         need(pos + length)
         seg = data[pos + 2:pos + length]
         pos += length
-        if marker == 0xC2:
+        if marker == _SOF2 and progressive and not prog:   # baseline until here
             if frame is not None:
                 raise UnsupportedJpeg("several frames")
-            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
-                raise UnsupportedJpeg("bad frame header")
-            if seg[0] != 8:
-                raise UnsupportedJpeg("sample precision not 8")
-            rec.height, rec.width = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4]
-            if rec.height == 0:
-                raise UnsupportedJpeg("DNL (height in the scan)")
-            if rec.width == 0:
-                raise UnsupportedJpeg("bad frame header")
-            if seg[5] == 4:
-                raise UnsupportedJpeg("four components")
-            if seg[5] not in (1, 3):
-                raise UnsupportedJpeg("component count")
-            frame = [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(seg[5])]
-        elif marker in (0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF):
+            prog = True
+        if marker == (_SOF2 if prog else _SOF0):
+            if frame is not None:
+                raise UnsupportedJpeg("several frames")
+            frame = _frame_header(seg)
+        elif marker in _SOF_ARITHMETIC:
             raise UnsupportedJpeg("arithmetic coding")
-        elif marker in (0xC0, 0xC1, 0xC3, 0xC5, 0xC6, 0xC7):
-            raise UnsupportedJpeg("several frames")
-        elif marker == 0xC4:
-            at = 0
-            while at < len(seg):
-                if at + 17 > len(seg):
-                    raise UnsupportedJpeg("bad Huffman table")
-                tc, th = seg[at] >> 4, seg[at] & 15
-                bits = seg[at + 1:at + 17]
-                count = sum(bits)
-                if tc > 1 or at + 17 + count > len(seg):
-                    raise UnsupportedJpeg("bad Huffman table")
-                if th > 3:
-                    raise UnsupportedJpeg("Huffman table id above 3")
-                huffman[(tc, th)] = huffman_table(bits, seg[at + 17:at + 17 + count])
-                at += 17 + count
-        elif marker == 0xDB:
-            at = 0
-            while at < len(seg):
-                pq, tq = seg[at] >> 4, seg[at] & 15
-                if pq != 0:
-                    raise UnsupportedJpeg("16-bit quantisation table")
-                if tq > 3 or at + 65 > len(seg):
-                    raise UnsupportedJpeg("bad quantisation table")
-                rec.qtables[tq] = np.frombuffer(seg[at + 1:at + 65], np.uint8).astype(np.uint16)
-                at += 65
-        elif marker == 0xDD:
+        elif marker in _SOF_HUFFMAN:
+            raise UnsupportedJpeg("several frames" if prog else _SOF_REASON.get(marker, "SOF%d" % (marker - _SOF0)))
+        elif marker == _DHT:
+            _huffman_tables(seg, 3 if prog else 1, huffman)
+        elif marker == _DQT:
+            _quantisation_tables(seg, qtables)
+        elif marker == _DRI:
             if len(seg) != 2:
                 raise UnsupportedJpeg("bad restart interval")
             restart = (seg[0] << 8) | seg[1]
-        elif marker == 0xDC:
+        elif marker == _DNL:
             raise UnsupportedJpeg("DNL")
-        elif marker == 0xEE:
+        elif marker == _ADOBE:
             adobe = adobe or seg[:5] == b"Adobe"
-        elif marker == 0xDA:
-            if not rec.scans:
-                _progressive_frame(rec, frame, adobe)
-            if len(rec.scans) == MAX_SCANS:
+        elif marker == _SOS:
+            if not scans:   # the first SOS, of a baseline file the only one
+                if frame is None:
+                    raise UnsupportedJpeg("scan before the frame header")
+                if adobe:
+                    raise UnsupportedJpeg("Adobe marker")
+                rec = JpegProgRecord() if prog else JpegRecord()
+                rec.data, rec.qtables = data, qtables
+                rec.height, rec.width, frame = frame
+                markers = _Markers(data)
+            if not prog:
+                _accept_frame(rec, _baseline_scan_header(seg, frame, qtables, huffman))
+                rec.huffman, rec.restart = huffman, restart
+                end, rec.intervals = markers.entropy_segment(pos, rec.mcus_x * rec.mcus_y, restart, last=True)
+                rec.scan = (pos, end)
+                return rec
+            if not scans:
+                if any(tq not in qtables for _, _, _, tq in frame):
+                    raise UnsupportedJpeg("missing table")
+                _accept_frame(rec, [c + (None, None) for c in frame])
+                rec.scans = scans
+                state = np.full((3, 64), -1, np.int32)   # per (component, coefficient): the Al reached, -1 before its first scan
+            if len(scans) == MAX_SCANS:
                 raise UnsupportedJpeg("too many scans")
             s = _progressive_scan_header(rec, seg, huffman, state)
             s.restart = restart
-            # the entropy-coded segment: up to the first marker that is no RSTn
-            at = bisect.bisect_left(ends, pos)
-            if at == len(ends):
-                raise UnsupportedJpeg("truncated scan")
-            end = ends[at]
-            rst = all_marks[bisect.bisect_left(mark_list, pos):bisect.bisect_left(mark_list, end)]   # the RSTn markers inside
-            expected = -(-s.units // restart) - 1 if restart else 0
-            if rst.size != expected or not np.array_equal(arr[rst + 1] & 7, np.arange(rst.size) & 7):
-                raise UnsupportedJpeg("restart markers missing or out of order")
-            if rst.size:
-                firsts = np.concatenate([[pos], rst + 2]) - pos
-                lasts = np.concatenate([rst, [end]]) - pos
-                s.intervals = np.stack([firsts, lasts], 1).astype(np.int32)
-            else:
-                s.intervals = np.array([[0, end - pos]], np.int32)
+            end, s.intervals = markers.entropy_segment(pos, s.units, restart)
             s.scan = (pos, end)
-            rec.scans.append(s)
+            scans.append(s)
             pos = end
     if state[:len(rec.components)].any():   # something never coded, or not down to Al = 0
         raise UnsupportedJpeg("progression")
     return rec
 
 
-def _progressive_frame(rec, frame, adobe):
-    """the frame of ``parse_progressive`` at its first SOS: the components, sampling and sizes of the baseline path"""
-    if frame is None:
-        raise UnsupportedJpeg("scan before the frame header")
-    if adobe:
-        raise UnsupportedJpeg("Adobe marker")
-    if any(tq not in rec.qtables for _, _, _, tq in frame):
-        raise UnsupportedJpeg("missing table")
-    if len(frame) == 3:
-        if [c[0] for c in frame] != [1, 2, 3]:
-            raise UnsupportedJpeg("component ids not 1, 2, 3")
-        if (frame[0][1], frame[0][2]) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in frame[1:]):
-            raise UnsupportedJpeg("sampling factors")
-    elif (frame[0][1], frame[0][2]) != (1, 1):
-        raise UnsupportedJpeg("sampling factors")
-    if rec.width > MAX_SIDE or rec.height > MAX_SIDE:
-        raise UnsupportedJpeg("a side above 8192")
-    rec.components, rec.hs, rec.vs = tuple(c + (None, None) for c in frame), frame[0][1], frame[0][2]
-    rec.mcus_x, rec.mcus_y = -(-rec.width // (8 * rec.hs)), -(-rec.height // (8 * rec.vs))
+def parse_jpeg(data, progressive=False):
+    """Headers of one JPEG file (bytes) -> ``JpegRecord``, or ``UnsupportedJpeg(reason)`` for anything outside the device path:
+    baseline SOF0 with 8-bit samples and tables, one interleaved scan of all components, Huffman table ids 0 and 1, three components
+    with ids 1, 2, 3, luma 1x1 / 2x1 / 2x2 and chroma 1x1 without an Adobe marker, or one 1x1 component, restart markers complete
+    and in order, both sides at most 8192.  ``progressive``: a progressive Huffman file (SOF2) with the same components, sampling and
+    sizes, whose scans form a legal and complete progression (``parse_progressive``), gives a ``JpegProgRecord`` instead of the refusal
+    "progressive (SOF2)"; baseline files parse as without it, and Huffman table ids 2 and 3 are taken from the SOF2 marker on."""
+    return _parse(data, progressive, False)
+
+
+def parse_progressive(data) -> JpegProgRecord:
+    """Headers and scans of one progressive Huffman JPEG -> ``JpegProgRecord``, or ``UnsupportedJpeg(reason)``.  Accepted: SOF2 with 8-bit
+    samples and tables, components and sampling as in the baseline path, no Adobe marker, sides at most 8192; 1 to 64 scans, each of all
+    components or of one (AC scans: of one), Ss <= Se <= 63 with Se = 0 when Ss = 0, Al <= 13, Ah = 0 or Al + 1, Huffman table ids 0..3;
+    per (component, coefficient) the first scan has Ah = 0, each later one Ah = the previous Al, the DC comes before any AC, and after
+    the last scan everything has reached Al = 0 ("progression" otherwise: the library smooths an incomplete file, the device does not);
+    between scans only DHT / DRI / COM / APPn segments; restart markers complete and in order per scan; EOI behind the last scan."""
+    return _parse(data, True, True)
+
+
+def _baseline_scan_header(seg, frame, qtables, huffman):
+    """The one SOS segment of a baseline file -> its components as (id, h, v, quantisation table id, DC table id, AC table id)"""
+    if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
+        raise UnsupportedJpeg("bad scan header")
+    if seg[0] != len(frame):
+        raise UnsupportedJpeg("several scans")
+    if seg[-3] != 0 or seg[-2] != 63 or seg[-1] != 0:
+        raise UnsupportedJpeg("spectral selection or successive approximation")
+    comps = []
+    for i, (cid, h, v, tq) in enumerate(frame):
+        if seg[1 + 2 * i] != cid:
+            raise UnsupportedJpeg("scan component order")
+        td, ta = seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15
+        if td > 1 or ta > 1:
+            raise UnsupportedJpeg("Huffman table id above 1")
+        if tq not in qtables or (0, td) not in huffman or (1, ta) not in huffman:
+            raise UnsupportedJpeg("missing table")
+        comps.append((cid, h, v, tq, td, ta))
+    return comps
 
 
 def _progressive_scan_header(rec, seg, huffman, state) -> JpegScan:
-    """one SOS segment of ``parse_progressive``: limits, tables in force, and its step in the progression (``state`` is advanced)"""
+    """One SOS segment of a progressive file: limits, tables in force, and its step in the progression (``state`` is advanced)"""
     ncomp = len(rec.components)
     if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
         raise UnsupportedJpeg("bad scan header")
@@ -481,27 +421,113 @@ def _progressive_scan_header(rec, seg, huffman, state) -> JpegScan:
     return s
 
 
+# ------------------------------------------------------------------------------------------------------------------ the planners
 def _align16(n: int) -> int:
     return (n + 15) & ~15
 
 
-class JpegPlan:
-    """What ``plan_jpeg_batch`` returns.  ``blob``: uint8 array (the first ``nbytes`` bytes count), ``coef_blocks`` / ``plane_bytes`` /
+def output_layout(sizes):
+    """(height, width) per image -> (offsets, total bytes) of the RGB images one after the other, each at a 16-byte aligned offset"""
+    offsets, total = [], 0
+    for h, w in sizes:
+        offsets.append(total)
+        total = _align16(total + h * w * 3)
+    return offsets, total
+
+
+class _Blob:
+    """The host blob of a batch while it is laid out: the cursor ``at`` and the parts with their offsets, every one 16-byte aligned."""
+
+    def __init__(self):
+        self.at, self.parts = 0, []
+
+    def room(self, nbytes):
+        """the offset of ``nbytes`` bytes that ``put`` fills later"""
+        off, self.at = self.at, _align16(self.at + nbytes)
+        return off
+
+    def put(self, off, arr):
+        self.parts.append((off, np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
+
+    def place(self, arr):
+        """``arr`` behind everything so far -> its offset"""
+        raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+        off = self.at
+        self.parts.append((off, raw))
+        self.at = _align16(off + raw.size)
+        return off
+
+    def finish(self, reserve):
+        """-> the uint8 array with every part in place: ``reserve(nbytes)``, or a fresh zeroed one"""
+        if self.at >= 1 << 31:
+            raise ValueError("batch too large for one blob (2 GiB of compressed data)")
+        blob = np.zeros(self.at, np.uint8) if reserve is None else reserve(self.at)
+        for off, raw in self.parts:
+            blob[off:off + raw.size] = raw
+        return blob
+
+
+class _Plan:
+    """What both planners return.  ``blob``: uint8 array (the first ``nbytes`` bytes count), ``coef_blocks`` / ``plane_bytes`` /
     ``out_bytes``: the sizes of the three device buffers the launch needs, ``out_offsets`` / ``sizes``: where each image lands in the
-    output and its (height, width), ``n_waves``: restart intervals in the batch.  With ``sync``: ``sub_bytes`` / ``min_sync_bytes``,
-    ``jobs_off`` / ``n_jobs``: the table of ``hawq_jpeg_sync_job`` in the blob (one per interval of at least ``min_sync_bytes``),
-    ``jobs``: the same as (wave, n_sub, scratch offset) tuples, ``scratch_bytes``: the device scratch the launch needs."""
-    __slots__ = ("blob", "nbytes", "coef_blocks", "plane_bytes", "out_bytes", "out_offsets", "sizes", "n_waves", "sub_bytes", "min_sync_bytes", "jobs_off",
-                 "n_jobs", "jobs", "scratch_bytes")
+    output and its (height, width)."""
+    __slots__ = ("blob", "nbytes", "coef_blocks", "plane_bytes", "out_bytes", "out_offsets", "sizes")
+    checker = None   # the library's check of the blob
+
+    def __init__(self):
+        self.coef_blocks = self.plane_bytes = self.out_bytes = 0
+        self.out_offsets, self.sizes = [], []
 
     def ok(self) -> bool:
-        """``hawq_jpeg_batch_ok`` on the host blob (no GPU work); the reason of a refusal is in ``hawq_last_error``."""
-        return bool(_lib.load().hawq_jpeg_batch_ok(self.blob.ctypes.data, self.nbytes, self.coef_blocks, self.plane_bytes, self.out_bytes))
+        """The library's checker on the host blob (no GPU work); the reason of a refusal is in ``hawq_last_error``."""
+        return bool(getattr(_lib.load(), self.checker)(self.blob.ctypes.data, self.nbytes, self.coef_blocks, self.plane_bytes, self.out_bytes))
+
+    def add_image(self, d, r, blob, out_off, tables=lambda c, comp: None):
+        """The geometry half of descriptor ``d`` for record ``r``, its quantisation tables into ``blob`` (``tables(c, comp)`` places what
+        else component ``c`` needs, behind its quantisation table), and its share of the three buffers; ``out_off``: None = behind the
+        image before."""
+        d["width"], d["height"], d["ncomp"], d["hs"], d["vs"], d["mcus_x"], d["mcus_y"] = r.width, r.height, r.ncomp, r.hs, r.vs, r.mcus_x, r.mcus_y
+        placed = {}
+        for c, comp in enumerate(r.components):
+            if comp[3] not in placed:
+                placed[comp[3]] = blob.place(r.qtables[comp[3]])
+            d["qt_off"][c] = placed[comp[3]]
+            tables(c, comp)
+        d["coef_block0"], d["plane_off"] = self.coef_blocks, self.plane_bytes
+        self.coef_blocks, self.plane_bytes = self.coef_blocks + r.blocks, self.plane_bytes + r.blocks * 64
+        d["out_off"] = off = self.out_bytes if out_off is None else int(out_off)
+        self.out_offsets.append(off)
+        self.sizes.append((r.height, r.width))
+        self.out_bytes = _align16(off + r.width * r.height * 3)
+
+    def finish(self, blob, reserve, out_bytes):
+        self.blob, self.nbytes = blob.finish(reserve), blob.at
+        if out_bytes is not None:
+            self.out_bytes = int(out_bytes)
+        return self
+
+
+class JpegPlan(_Plan):
+    """What ``plan_jpeg_batch`` returns: ``_Plan`` and ``n_waves``: restart intervals in the batch.  With ``sync``: ``sub_bytes`` /
+    ``min_sync_bytes``, ``jobs_off`` / ``n_jobs``: the table of ``hawq_jpeg_sync_job`` in the blob (one per interval of at least
+    ``min_sync_bytes``), ``jobs``: the same as (wave, n_sub, scratch offset) tuples, ``scratch_bytes``: the device scratch the launch
+    needs."""
+    __slots__ = ("n_waves", "sub_bytes", "min_sync_bytes", "jobs_off", "n_jobs", "jobs", "scratch_bytes")
+    checker = "hawq_jpeg_batch_ok"
 
     def sync_ok(self) -> bool:
         """``hawq_jpeg_sync_ok`` on the host blob of a plan made with ``sync`` (after ``ok``; no GPU work)."""
         return bool(_lib.load().hawq_jpeg_sync_ok(self.blob.ctypes.data, self.nbytes, self.sub_bytes, self.min_sync_bytes, self.jobs_off, self.n_jobs,
                                                   self.scratch_bytes))
+
+
+def _wave_list(ks, counts):
+    """int32 [n, 2]: (k, j) for j in range(count), for every k of ``ks`` with its count, in order"""
+    counts = np.asarray(counts, np.int64)
+    waves = np.empty((int(counts.sum()), 2), np.int32)
+    waves[:, 0] = np.repeat(np.asarray(ks), counts)
+    waves[:, 1] = np.arange(len(waves)) - np.repeat(np.cumsum(counts) - counts, counts)
+    return waves
 
 
 def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, sync=None) -> JpegPlan:
@@ -515,41 +541,25 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, syn
     if not records:
         raise ValueError("empty batch")
     n = len(records)
-    n_waves = sum(len(r.intervals) for r in records)
-    desc_off = _align16(_HDR.itemsize)
-    wave_off = _align16(desc_off + n * _DESC.itemsize)
-    at = _align16(wave_off + 8 * n_waves)
-    desc = np.zeros(n, _DESC)
-    parts = []   # (offset, uint8 array)
-    plan = JpegPlan()
-    coef_at = plane_at = out_at = 0
-    offs = []
+    plan, blob = JpegPlan(), _Blob()
+    plan.n_waves = sum(len(r.intervals) for r in records)
+    hdr, desc = np.zeros(1, _HDR), np.zeros(n, _DESC)
+    blob.room(_HDR.itemsize)
+    desc_off, wave_off = blob.room(desc.nbytes), blob.room(8 * plan.n_waves)
+    hdr["n_images"], hdr["n_waves"], hdr["desc_off"], hdr["wave_off"] = n, plan.n_waves, desc_off, wave_off
     for i, r in enumerate(records):
-        d = desc[i]
-        d["width"], d["height"], d["ncomp"], d["hs"], d["vs"] = r.width, r.height, r.ncomp, r.hs, r.vs
-        d["mcus_x"], d["mcus_y"], d["restart"], d["n_intervals"] = r.mcus_x, r.mcus_y, r.restart, len(r.intervals)
-        placed = {}
-        for c, (_, _, _, tq, td, ta) in enumerate(r.components):
-            for field, key, arr in (("qt_off", ("q", tq), r.qtables[tq]), ("dc_off", (0, td), r.huffman[(0, td)]), ("ac_off", (1, ta), r.huffman[(1, ta)])):
+        d, placed = desc[i], {}
+        d["restart"], d["n_intervals"] = r.restart, len(r.intervals)
+
+        def huffman(c, comp):
+            for field, key in (("dc_off", (0, comp[4])), ("ac_off", (1, comp[5]))):
                 if key not in placed:
-                    raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
-                    placed[key] = at
-                    parts.append((at, raw))
-                    at = _align16(at + raw.size)
+                    placed[key] = blob.place(r.huffman[key])
                 d[field][c] = placed[key]
-        raw = np.ascontiguousarray(r.intervals, np.int32).view(np.uint8).reshape(-1)
-        d["interval_off"] = at
-        parts.append((at, raw))
-        at = _align16(at + raw.size)
-        d["stream_off"], d["stream_len"] = at, r.scan[1] - r.scan[0]
-        parts.append((at, np.frombuffer(r.data, np.uint8, r.scan[1] - r.scan[0], r.scan[0])))
-        at = _align16(at + r.scan[1] - r.scan[0])
-        d["coef_block0"], d["plane_off"] = coef_at, plane_at
-        coef_at, plane_at = coef_at + r.blocks, plane_at + r.blocks * 64
-        off = out_at if out_offsets is None else int(out_offsets[i])
-        d["out_off"] = off
-        offs.append(off)
-        out_at = _align16(off + r.width * r.height * 3)
+
+        plan.add_image(d, r, blob, None if out_offsets is None else out_offsets[i], huffman)
+        d["interval_off"] = blob.place(np.ascontiguousarray(r.intervals, np.int32))
+        d["stream_off"], d["stream_len"] = blob.place(np.frombuffer(r.data, np.uint8, r.scan[1] - r.scan[0], r.scan[0])), r.scan[1] - r.scan[0]
     plan.sub_bytes = plan.min_sync_bytes = plan.jobs_off = plan.n_jobs = plan.scratch_bytes = 0
     plan.jobs = []
     if sync is not None:
@@ -566,40 +576,19 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, syn
                     plan.jobs.append((wave, n_sub, plan.scratch_bytes))
                     plan.scratch_bytes += SYNC_JOB_HDR_BYTES + SYNC_SUB_RECORD_BYTES * n_sub
                 wave += 1
-        plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off, plan.n_jobs = sub_bytes, min_sync_bytes, at, len(plan.jobs)
-        if plan.jobs:
-            parts.append((at, np.array(plan.jobs, _JOB).view(np.uint8).reshape(-1)))
-        at = _align16(at + _JOB.itemsize * len(plan.jobs))
-    if at >= 1 << 31:
-        raise ValueError("batch too large for one blob (2 GiB of compressed data)")
-    blob = np.zeros(at, np.uint8) if reserve is None else reserve(at)
-    hdr = np.zeros(1, _HDR)
-    hdr["n_images"], hdr["n_waves"], hdr["desc_off"], hdr["wave_off"] = n, n_waves, desc_off, wave_off
-    blob[:_HDR.itemsize] = hdr.view(np.uint8).reshape(-1)
-    blob[desc_off:desc_off + desc.nbytes] = desc.view(np.uint8).reshape(-1)
-    waves = np.concatenate([np.stack([np.full(len(r.intervals), i, np.int32), np.arange(len(r.intervals), dtype=np.int32)], 1)
-                            for i, r in enumerate(records)])
-    blob[wave_off:wave_off + waves.nbytes] = waves.view(np.uint8).reshape(-1)
-    for off, raw in parts:
-        blob[off:off + raw.size] = raw
-    plan.blob, plan.nbytes, plan.n_waves = blob, at, n_waves
-    plan.coef_blocks, plan.plane_bytes = coef_at, plane_at
-    plan.out_bytes = out_at if out_bytes is None else int(out_bytes)
-    plan.out_offsets, plan.sizes = offs, [(r.height, r.width) for r in records]
-    return plan
+        plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off, plan.n_jobs = sub_bytes, min_sync_bytes, blob.place(np.array(plan.jobs, _JOB)), len(plan.jobs)
+    for off, table in ((0, hdr), (desc_off, desc), (wave_off, _wave_list(range(n), [len(r.intervals) for r in records]))):
+        blob.put(off, table)
+    return plan.finish(blob, reserve, out_bytes)
 
 
-class JpegProgPlan:
-    """What ``plan_jpeg_prog_batch`` returns.  ``blob`` ``nbytes`` ``coef_blocks`` ``plane_bytes`` ``out_bytes`` ``out_offsets``
-    ``sizes`` as in ``JpegPlan``; ``n_scans``; ``levels``: the level of every scan, image after image; ``n_levels``: the deepest, the
-    number of entropy launches; ``n_waves``: (scan, restart interval) pairs; ``level_start``: where each level's waves begin in the wave
-    list (n_levels + 1 entries); ``scan_off`` / ``level_off`` / ``wave_off`` / ``desc_off``: where the tables lie in the blob."""
-    __slots__ = ("blob", "nbytes", "coef_blocks", "plane_bytes", "out_bytes", "out_offsets", "sizes", "n_scans", "levels", "n_levels", "n_waves", "level_start",
-                 "scan_off", "level_off", "wave_off", "desc_off")
-
-    def ok(self) -> bool:
-        """``hawq_jpeg_prog_ok`` on the host blob (no GPU work); the reason of a refusal is in ``hawq_last_error``."""
-        return bool(_lib.load().hawq_jpeg_prog_ok(self.blob.ctypes.data, self.nbytes, self.coef_blocks, self.plane_bytes, self.out_bytes))
+class JpegProgPlan(_Plan):
+    """What ``plan_jpeg_prog_batch`` returns: ``_Plan`` and ``n_scans``; ``levels``: the level of every scan, image after image;
+    ``n_levels``: the deepest, the number of entropy launches; ``n_waves``: (scan, restart interval) pairs; ``level_start``: where each
+    level's waves begin in the wave list (n_levels + 1 entries); ``scan_off`` / ``level_off`` / ``wave_off`` / ``desc_off``: where the
+    tables lie in the blob."""
+    __slots__ = ("n_scans", "levels", "n_levels", "n_waves", "level_start", "scan_off", "level_off", "wave_off", "desc_off")
+    checker = "hawq_jpeg_prog_ok"
 
 
 def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None) -> JpegProgPlan:
@@ -611,149 +600,86 @@ def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None
     if not records:
         raise ValueError("empty batch")
     n = len(records)
-    n_scans = sum(len(r.scans) for r in records)
-    levels = [lv for r in records for lv in scan_levels(r.scans)]
-    n_levels = max(levels)
-    n_waves = sum(len(s.intervals) for r in records for s in r.scans)
-    desc_off = _align16(_HDR.itemsize + _PHDR.itemsize)
-    scan_off = _align16(desc_off + n * _DESC.itemsize)
-    level_off = _align16(scan_off + n_scans * _SCAN.itemsize)
-    wave_off = _align16(level_off + 4 * (n_levels + 1))
-    at = _align16(wave_off + 8 * n_waves)
-    desc, rows = np.zeros(n, _DESC), []   # rows: the fields of hawq_jpeg_scan, in order
-    parts = []   # (offset, uint8 array)
-
-    def place(arr):
-        nonlocal at
-        raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
-        off = at
-        parts.append((off, raw))
-        at = _align16(at + raw.size)
-        return off
-
-    coef_at = plane_at = out_at = k = 0
-    offs = []
+    plan, blob = JpegProgPlan(), _Blob()
+    plan.n_scans = sum(len(r.scans) for r in records)
+    plan.levels = levels = [lv for r in records for lv in scan_levels(r.scans)]
+    plan.n_levels = max(levels)
+    plan.n_waves = sum(len(s.intervals) for r in records for s in r.scans)
+    hdr, phdr, desc = np.zeros(1, _HDR), np.zeros(1, _PHDR), np.zeros(n, _DESC)
+    blob.room(_HDR.itemsize + _PHDR.itemsize)
+    plan.desc_off, plan.scan_off, plan.level_off = blob.room(desc.nbytes), blob.room(plan.n_scans * _SCAN.itemsize), blob.room(4 * (plan.n_levels + 1))
+    plan.wave_off = blob.room(8 * plan.n_waves)
+    hdr["n_images"], hdr["n_waves"], hdr["desc_off"], hdr["wave_off"] = n, plan.n_waves, plan.desc_off, plan.wave_off
+    phdr["n_scans"], phdr["n_levels"], phdr["scan_off"], phdr["level_off"] = plan.n_scans, plan.n_levels, plan.scan_off, plan.level_off
+    rows = []   # the fields of hawq_jpeg_scan, in order
     for i, r in enumerate(records):
-        d = desc[i]
-        d["width"], d["height"], d["ncomp"], d["hs"], d["vs"], d["mcus_x"], d["mcus_y"] = r.width, r.height, r.ncomp, r.hs, r.vs, r.mcus_x, r.mcus_y
-        placed = {}
-        for c, comp in enumerate(r.components):
-            if comp[3] not in placed:
-                placed[comp[3]] = place(r.qtables[comp[3]])
-            d["qt_off"][c] = placed[comp[3]]
+        plan.add_image(desc[i], r, blob, None if out_offsets is None else out_offsets[i])
         tables = {}   # id of a table record -> offset: a table stays in force over several scans
 
         def table(t):
             if id(t) not in tables:
-                tables[id(t)] = place(t)
+                tables[id(t)] = blob.place(t)
             return tables[id(t)]
 
         for s in r.scans:
             dc = [table(t) for t in s.dc or ()]
-            rows.append((i, len(s.comps), s.comps[0], s.ss, s.se, s.ah, s.al, levels[k], tuple(dc + [0] * (3 - len(dc))), 0 if s.ac is None else table(s.ac),
-                         s.restart, len(s.intervals), place(np.ascontiguousarray(s.intervals, np.int32)),
-                         place(np.frombuffer(r.data, np.uint8, s.scan[1] - s.scan[0], s.scan[0])), s.scan[1] - s.scan[0], (0, 0, 0)))
-            k += 1
-        d["coef_block0"], d["plane_off"] = coef_at, plane_at
-        coef_at, plane_at = coef_at + r.blocks, plane_at + r.blocks * 64
-        off = out_at if out_offsets is None else int(out_offsets[i])
-        d["out_off"] = off
-        offs.append(off)
-        out_at = _align16(off + r.width * r.height * 3)
-    if at >= 1 << 31:
-        raise ValueError("batch too large for one blob (2 GiB of compressed data)")
+            rows.append((i, len(s.comps), s.comps[0], s.ss, s.se, s.ah, s.al, levels[len(rows)], tuple(dc + [0] * (3 - len(dc))), 0 if s.ac is None else table(s.ac),
+                         s.restart, len(s.intervals), blob.place(np.ascontiguousarray(s.intervals, np.int32)),
+                         blob.place(np.frombuffer(r.data, np.uint8, s.scan[1] - s.scan[0], s.scan[0])), s.scan[1] - s.scan[0], (0, 0, 0)))
     scans = np.array(rows, _SCAN)
-    waves, level_start = [], [0]
-    for level in range(1, n_levels + 1):
-        for k in np.flatnonzero(np.array(levels) == level).tolist():
-            waves.append(np.stack([np.full(scans["n_intervals"][k], k, np.int32), np.arange(scans["n_intervals"][k], dtype=np.int32)], 1))
-        level_start.append(sum(len(w) for w in waves))
-    blob = np.zeros(at, np.uint8) if reserve is None else reserve(at)
-    hdr, phdr = np.zeros(1, _HDR), np.zeros(1, _PHDR)
-    hdr["n_images"], hdr["n_waves"], hdr["desc_off"], hdr["wave_off"] = n, n_waves, desc_off, wave_off
-    phdr["n_scans"], phdr["n_levels"], phdr["scan_off"], phdr["level_off"] = n_scans, n_levels, scan_off, level_off
-    for off, arr in ((0, hdr), (_HDR.itemsize, phdr), (desc_off, desc), (scan_off, scans), (level_off, np.array(level_start, np.int32)), (wave_off, np.concatenate(waves))):
-        blob[off:off + arr.nbytes] = arr.view(np.uint8).reshape(-1)
-    for off, raw in parts:
-        blob[off:off + raw.size] = raw
-    plan = JpegProgPlan()
-    plan.blob, plan.nbytes, plan.n_waves, plan.n_scans, plan.levels, plan.n_levels, plan.level_start = blob, at, n_waves, n_scans, levels, n_levels, level_start
-    plan.scan_off, plan.level_off, plan.wave_off, plan.desc_off = scan_off, level_off, wave_off, desc_off
-    plan.coef_blocks, plan.plane_bytes = coef_at, plane_at
-    plan.out_bytes = out_at if out_bytes is None else int(out_bytes)
-    plan.out_offsets, plan.sizes = offs, [(r.height, r.width) for r in records]
-    return plan
+    waves, plan.level_start = [], [0]
+    for level in range(1, plan.n_levels + 1):
+        ks = np.flatnonzero(np.array(levels) == level)
+        waves.append(_wave_list(ks, scans["n_intervals"][ks]))
+        plan.level_start.append(plan.level_start[-1] + len(waves[-1]))
+    for off, table in ((0, hdr), (_HDR.itemsize, phdr), (plan.desc_off, desc), (plan.scan_off, scans), (plan.level_off, np.array(plan.level_start, np.int32)),
+                       (plan.wave_off, np.concatenate(waves))):
+        blob.put(off, table)
+    return plan.finish(blob, reserve, out_bytes)
 
 
-def _launch_prog(records, out_offsets, out, dev, events=None):
-    """The device call of ``decode_jpeg_batch`` for progressive records: as ``_launch``, with ``plan_jpeg_prog_batch`` /
-    ``hawq_jpeg_decode_batch_prog`` and a staging buffer of its own; writes into ``out``.  Returns the int32 status per record as a
-    device tensor: the caller reads it when everything of the batch is enqueued."""
+# ------------------------------------------------------------------------------------------------------------------ the device call
+def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None):
+    """The device call of ``decode_jpeg_batch`` for records of one kind: plan into the pinned staging buffer of that kind, check, upload
+    in one copy, run the three stages on the current stream, writing into the uint8 device tensor ``out`` at ``out_offsets``.  Returns
+    the int32 status per record as a device tensor: reading it synchronises, so the caller does that when everything of the batch is
+    enqueued.  ``JpegProgRecord``s: ``hawq_jpeg_decode_batch_prog``.  ``JpegRecord``s: ``hawq_jpeg_decode_batch``, or with ``sync`` =
+    (sub_bytes, min_sync_bytes) ``hawq_jpeg_decode_batch_sync``; a dict ``info`` then receives ``jobs`` (the plan's) and ``rounds`` /
+    ``decodes`` (what the kernel counted per job; a synchronising read of the scratch)."""
     from .image import _STAGING, _Staging
+    prog = isinstance(records[0], JpegProgRecord)
+    if prog and sync is not None:
+        raise ValueError("entropy='sync' does not take progressive records")
+    key, entry = ("jpeg_prog", "hawq_jpeg_decode_batch_prog") if prog else ("jpeg", "hawq_jpeg_decode_batch" if sync is None else "hawq_jpeg_decode_batch_sync")
     lib = _lib.load()
     with torch.cuda.device(dev):
-        st = _STAGING.setdefault((dev.index, "jpeg_prog"), _Staging())
+        st = _STAGING.setdefault((dev.index, key), _Staging())   # one per kind: both blobs of a batch are in flight at once
         held = {}
 
         def reserve(nbytes):
             held["host"], held["dev"] = st.reserve(nbytes, dev)
             return held["host"].numpy()
 
-        plan = plan_jpeg_prog_batch(records, out_offsets, out.numel(), reserve)
-        if not plan.ok():   # on the host blob, before anything is uploaded or launched
-            raise RuntimeError("libhawq_mi355: " + lib.hawq_last_error().decode())
-        st.upload(plan.nbytes)
-        coef = torch.empty(plan.coef_blocks * 64, dtype=torch.int16, device=dev)
-        planes = torch.empty(plan.plane_bytes, dtype=torch.uint8, device=dev)
-        status = torch.empty(len(records), dtype=torch.int32, device=dev)
-        ev = (C.c_void_p * 4)(*events) if events is not None else None
-        _lib.call("hawq_jpeg_decode_batch_prog", held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks, planes.data_ptr(),
-                  plan.plane_bytes, out.data_ptr(), out.numel(), status.data_ptr(), ev, torch.cuda.current_stream(dev).cuda_stream)
-        return status
-
-
-def _launch(records, out_offsets, out_bytes, dev, events=None, sync=None, info=None, out=None):
-    """The device call of ``decode_jpeg_batch``: plan into the pinned staging buffer, check, upload in one copy, run the three stages
-    on the current stream.  Returns (uint8 [out_bytes] device tensor - ``out`` when given, else freshly allocated; int32 status per
-    record, on the host - reading it is the one synchronisation of the batch).  ``sync`` = (sub_bytes, min_sync_bytes):
-    ``hawq_jpeg_decode_batch_sync``; a dict ``info`` then receives ``jobs`` (the plan's) and ``rounds`` / ``decodes`` (what the kernel
-    counted per job)."""
-    from .image import _STAGING, _Staging
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _STAGING.setdefault((dev.index, "jpeg"), _Staging())
-        held = {}
-
-        def reserve(nbytes):
-            held["host"], held["dev"] = st.reserve(nbytes, dev)
-            return held["host"].numpy()
-
-        plan = plan_jpeg_batch(records, out_offsets, out_bytes, reserve, sync)
+        plan = plan_jpeg_prog_batch(records, out_offsets, out.numel(), reserve) if prog else plan_jpeg_batch(records, out_offsets, out.numel(), reserve, sync)
         if not plan.ok() or (sync is not None and not plan.sync_ok()):   # on the host blob, before anything is uploaded or launched
             raise RuntimeError("libhawq_mi355: " + lib.hawq_last_error().decode())
         st.upload(plan.nbytes)
-        if out is None:
-            out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
         coef = torch.empty(plan.coef_blocks * 64, dtype=torch.int16, device=dev)
         planes = torch.empty(plan.plane_bytes, dtype=torch.uint8, device=dev)
         status = torch.empty(len(records), dtype=torch.int32, device=dev)
+        more = ()
+        if sync is not None:
+            scratch = torch.empty(max(plan.scratch_bytes, 16), dtype=torch.uint8, device=dev)
+            more = (plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off, plan.n_jobs, scratch.data_ptr(), plan.scratch_bytes)
         ev = (C.c_void_p * 4)(*events) if events is not None else None
-        if sync is None:
-            _lib.call("hawq_jpeg_decode_batch", held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks,
-                      planes.data_ptr(), plan.plane_bytes, out.data_ptr(), out_bytes, status.data_ptr(), ev,
-                      torch.cuda.current_stream(dev).cuda_stream)
-            return out, status.cpu().numpy()
-        scratch = torch.empty(max(plan.scratch_bytes, 16), dtype=torch.uint8, device=dev)
-        _lib.call("hawq_jpeg_decode_batch_sync", held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks,
-                  planes.data_ptr(), plan.plane_bytes, out.data_ptr(), out_bytes, status.data_ptr(), plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off,
-                  plan.n_jobs, scratch.data_ptr(), plan.scratch_bytes, ev, torch.cuda.current_stream(dev).cuda_stream)
-        status = status.cpu().numpy()
-        if info is not None:
+        _lib.call(entry, held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks, planes.data_ptr(), plan.plane_bytes,
+                  out.data_ptr(), out.numel(), status.data_ptr(), *more, ev, torch.cuda.current_stream(dev).cuda_stream)
+        if sync is not None and info is not None:
             info["jobs"] = list(plan.jobs)
             host = scratch.cpu().numpy()
             heads = [host[off:off + 8].view(np.int32) for _, _, off in plan.jobs]
             info["rounds"], info["decodes"] = [int(h[0]) for h in heads], [int(h[1]) for h in heads]
-        return out, status
+        return status
 
 
 def read_source(source) -> bytes:
@@ -799,24 +725,14 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
             fallbacks.append((i, e.reason))
             host[i] = decode_image(data)
     sizes = [(records[i].height, records[i].width) if i in records else tuple(host[i].shape[:2]) for i in range(len(datas))]
-    offsets, total = [], 0
-    for h, w in sizes:
-        offsets.append(total)
-        total = _align16(total + h * w * 3)
-    order = sorted(i for i, r in records.items() if isinstance(r, JpegRecord))
-    prog = sorted(i for i, r in records.items() if isinstance(r, JpegProgRecord))
-    status = {}
-    if prog:   # both calls write into the one allocation; the progressive one is enqueued first and its status read last
-        out = torch.empty(total, dtype=torch.uint8, device=dev)
-        prog_status = _launch_prog([records[i] for i in prog], [offsets[i] for i in prog], out, dev)
-        if order:
-            status.update(zip(order, _launch([records[i] for i in order], [offsets[i] for i in order], total, dev, out=out, **more)[1]))
-        status.update(zip(prog, prog_status.cpu().numpy()))
-    elif order:
-        out, st = _launch([records[i] for i in order], [offsets[i] for i in order], total, dev, **more)
-        status.update(zip(order, st))
-    else:
-        out = torch.empty(total, dtype=torch.uint8, device=dev)
+    offsets, total = output_layout(sizes)
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    enqueued = []   # (indices, device status): the progressive call first, the baseline call second, both statuses read behind both
+    for kind, options in ((JpegProgRecord, {}), (JpegRecord, more)):
+        idx = sorted(i for i, r in records.items() if isinstance(r, kind))
+        if idx:
+            enqueued.append((idx, _launch([records[i] for i in idx], [offsets[i] for i in idx], out, dev, **options)))
+    status = {i: st for idx, device_status in enqueued for i, st in zip(idx, device_status.cpu().numpy())}
     for i, st in sorted(status.items()):
         if st != 0:
             fallbacks.append((i, "device status %d: %s" % (st, STATUS_NAMES.get(int(st), "unknown"))))
@@ -827,5 +743,3 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
         out[offsets[i]:offsets[i] + im.numel()].copy_(im.reshape(-1))
     images = [out[offsets[i]:offsets[i] + h * w * 3].view(h, w, 3) for i, (h, w) in enumerate(sizes)]
     return images, sorted(fallbacks)
-
-

@@ -13,6 +13,7 @@ import torch
 
 from tests import helpers as H
 from tests import jpeg_model
+from tests.jpeg_stub import stub_launch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -221,24 +222,8 @@ def test_checker_refuses_every_offset_or_count_pushed_out_of_range():
 
 # ------------------------------------------------------------------------------------------------------------------ fallback bookkeeping
 def _stub_launch(monkeypatch, statuses=None):
-    """``jpeg._launch`` replaced by the numpy model writing into a host tensor; ``statuses``: {position among the device images: status}"""
-    from hawq_amd import jpeg
-    calls = []
-
-    def launch(records, out_offsets, out_bytes, dev, events=None):
-        out = torch.zeros(out_bytes, dtype=torch.uint8)
-        status = np.zeros(len(records), np.int32)
-        for k, (r, off) in enumerate(zip(records, out_offsets)):
-            if statuses and k in statuses:
-                status[k] = statuses[k]
-                continue   # a failed image leaves garbage: zeros here
-            rgb = jpeg_model.decode(r.data)
-            out[off:off + rgb.size] = torch.from_numpy(rgb.reshape(-1))
-        calls.append(len(records))
-        return out, status
-
-    monkeypatch.setattr(jpeg, "_launch", launch)
-    return calls
+    """``jpeg._launch`` replaced by the numpy model; ``statuses``: {position among the device images: status}; logs the images per call"""
+    return stub_launch(monkeypatch, {"base": lambda r: jpeg_model.decode(r.data)}, lambda kind, records, out, sync: len(records), {"base": statuses or {}})
 
 
 def test_fallback_bookkeeping_with_a_stub_in_place_of_the_device_call(monkeypatch):

@@ -14,6 +14,7 @@ import torch
 
 from tests import jpeg_model
 from tests import jpeg_prog_model as M
+from tests.jpeg_stub import stub_launch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -317,33 +318,10 @@ def _units(plan, names, k):
 
 # ------------------------------------------------------------------------------------------------------------------ fallback bookkeeping
 def _stub_launches(monkeypatch, statuses=None):
-    """``jpeg._launch`` and ``jpeg._launch_prog`` replaced by the two models writing into host tensors; ``statuses``: {position among the
-    progressive images: status}.  Returns the list of calls: ("base" | "prog", number of records, data_ptr of the output)."""
-    from hawq_amd import jpeg
-    calls = []
-
-    def launch(records, out_offsets, out_bytes, dev, events=None, out=None):
-        out = torch.zeros(out_bytes, dtype=torch.uint8) if out is None else out
-        for r, off in zip(records, out_offsets):
-            rgb = jpeg_model.decode(r.data)
-            out[off:off + rgb.size] = torch.from_numpy(rgb.reshape(-1))
-        calls.append(("base", len(records), out.data_ptr()))
-        return out, np.zeros(len(records), np.int32)
-
-    def launch_prog(records, out_offsets, out, dev, events=None):
-        status = torch.zeros(len(records), dtype=torch.int32)
-        for k, (r, off) in enumerate(zip(records, out_offsets)):
-            if statuses and k in statuses:
-                status[k] = statuses[k]
-                continue
-            rgb = M.pixels(r, M.coefficients(r))
-            out[off:off + rgb.size] = torch.from_numpy(rgb.reshape(-1))
-        calls.append(("prog", len(records), out.data_ptr()))
-        return status
-
-    monkeypatch.setattr(jpeg, "_launch", launch)
-    monkeypatch.setattr(jpeg, "_launch_prog", launch_prog)
-    return calls
+    """``jpeg._launch`` replaced by the two models writing into host tensors; ``statuses``: {position among the progressive images:
+    status}.  Returns the list of calls: ("base" | "prog", number of records, data_ptr of the output)."""
+    return stub_launch(monkeypatch, {"base": lambda r: jpeg_model.decode(r.data), "prog": lambda r: M.pixels(r, M.coefficients(r))},
+                       lambda kind, records, out, sync: (kind, len(records), out.data_ptr()), {"prog": statuses or {}})
 
 
 def test_fallback_bookkeeping_with_stubs_in_place_of_the_device_calls(monkeypatch):

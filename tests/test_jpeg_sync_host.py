@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import jpeg_model, jpeg_sync_model
+from tests.jpeg_stub import stub_launch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -177,24 +178,8 @@ def test_checker_refuses_a_job_table_that_does_not_follow_from_the_blob():
 
 # ------------------------------------------------------------------------------------------------------------------ fallback bookkeeping
 def _stub_launch(monkeypatch, statuses=None):
-    """``jpeg._launch`` replaced by the numpy model writing into a host tensor; ``statuses``: {position among the device images: status}"""
-    from hawq_amd import jpeg
-    calls = []
-
-    def launch(records, out_offsets, out_bytes, dev, events=None, sync=None, info=None):
-        out = torch.zeros(out_bytes, dtype=torch.uint8)
-        status = np.zeros(len(records), np.int32)
-        for k, (r, off) in enumerate(zip(records, out_offsets)):
-            if statuses and k in statuses:
-                status[k] = statuses[k]
-                continue
-            rgb = jpeg_model.decode(r.data)
-            out[off:off + rgb.size] = torch.from_numpy(rgb.reshape(-1))
-        calls.append((len(records), sync))
-        return out, status
-
-    monkeypatch.setattr(jpeg, "_launch", launch)
-    return calls
+    """``jpeg._launch`` replaced by the numpy model; ``statuses``: {position among the device images: status}; logs (images, sync) per call"""
+    return stub_launch(monkeypatch, {"base": lambda r: jpeg_model.decode(r.data)}, lambda kind, records, out, sync: (len(records), sync), {"base": statuses or {}})
 
 
 def test_fallback_bookkeeping_is_the_same_with_either_entropy_stage(monkeypatch):

@@ -151,10 +151,8 @@ def main():
                 t[name].append(wall(runs[name]))
         # the stages alone: parsed once, planned + uploaded + launched per call
         records = [jpeg.parse_jpeg(d) for d in datas]
-        offsets, total = [], 0
-        for r in records:
-            offsets.append(total)
-            total = (total + r.width * r.height * 3 + 15) & ~15
+        offsets, total = jpeg.output_layout([(r.height, r.width) for r in records])
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
         lengths = [int(v) for r in records for v in (r.intervals[:, 1] - r.intervals[:, 0])]
 
         def staged(pairs, repeats):
@@ -164,7 +162,7 @@ def main():
                 for key, sync in pairs[k % len(pairs):] + pairs[:k % len(pairs)]:
                     info = {}
                     more = {} if sync is None else dict(sync=sync, info=info)
-                    _, status = jpeg._launch(records, offsets, total, dev, events, **more)   # reads the status: synchronised
+                    status = jpeg._launch(records, offsets, out, dev, events, **more).cpu()   # reads the status: synchronised
                     assert not status.any()
                     if sync is not None and info["jobs"]:
                         waves = [w for w, _, _ in info["jobs"]]
@@ -264,14 +262,11 @@ def progressive(args, box, dev, lib, events):
             for name in order[r % len(order):] + order[:r % len(order)]:   # every path takes every place in turn
                 t[name].append(wall(runs[name]))
         # the stages of the progressive call alone: parsed once, planned + uploaded + launched per call
-        offsets, total = [], 0
-        for r in prog:
-            offsets.append(total)
-            total = (total + r.width * r.height * 3 + 15) & ~15
+        offsets, total = jpeg.output_layout([(r.height, r.width) for r in prog])
         out = torch.empty(total, dtype=torch.uint8, device=dev)
         stages = ([], [], [])
         for k in range(args.warmup + args.repeats):
-            status = jpeg._launch_prog(prog, offsets, out, dev, events).cpu()   # reads the status: synchronised
+            status = jpeg._launch(prog, offsets, out, dev, events).cpu()   # reads the status: synchronised
             assert not status.any()
             if k >= args.warmup:
                 for s in range(3):
