@@ -187,6 +187,7 @@ SIGNATURES = {
     "hawq_fc_dequant": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "hawq_conv_expand_reduce": [C.POINTER(ExpandReduceArgs), vp],
     "hawq_conv_expand_reduce_variants": [C.POINTER(ExpandReduceArgs)],
+    "hawq_conv_expand_reduce_variant_shape": [C.POINTER(ExpandReduceArgs), i32, C.POINTER(i32), C.POINTER(i32)],
     "hawq_linear_bottleneck": [C.POINTER(BottleneckArgs), vp],
     "hawq_linear_bottleneck_ok": [C.POINTER(BottleneckArgs)],
     "hawq_stem3x3s2": [vp, vp, vp, i32, i32, f32, i32, i32, C.POINTER(ConvArgs), vp],

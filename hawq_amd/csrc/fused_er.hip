@@ -487,6 +487,7 @@ int er_variant(const hawq_expand_reduce_args *a) {
 // wave-private variants (fused_wp.hip): numbered after the variants of this file; they also take reduce.wgt == NULL
 int wp_num_variants(const hawq_expand_reduce_args *a);
 int wp_launch(const hawq_expand_reduce_args *a, int nth, void *stream);
+int wp_variant_shape(const hawq_expand_reduce_args *a, int nth, int *pixels_per_workgroup, int *slice_split);
 // software-pipelined pair variants (fused_er2.hip): numbered after the wave-private ones
 int er2_num_variants(const hawq_expand_reduce_args *a);
 int er2_launch(const hawq_expand_reduce_args *a, int nth, void *stream);
@@ -506,6 +507,14 @@ int er_count(const hawq_expand_reduce_args *a) {   // variants of THIS file that
 extern "C" int hawq_conv_expand_reduce_variants(const hawq_expand_reduce_args *a) {
     if (!a) return 0;
     return er_count(a) + wp_num_variants(a) + er2_num_variants(a);
+}
+
+extern "C" int hawq_conv_expand_reduce_variant_shape(const hawq_expand_reduce_args *a, int nth, int *pixels_per_workgroup, int *slice_split) {
+    if (!a || !pixels_per_workgroup || !slice_split) return 1;
+    const int n_er = er_count(a);
+    if (nth == 0 && n_er == 0) nth = 1;   // the default of hawq_conv_expand_reduce
+    if (nth <= n_er || nth > n_er + wp_num_variants(a)) return 1;
+    return wp_variant_shape(a, nth - n_er, pixels_per_workgroup, slice_split);
 }
 
 extern "C" int hawq_conv_expand_reduce(const hawq_expand_reduce_args *a, void *stream) {

@@ -24,6 +24,10 @@
 //     issues a share of; ONE workgroup barrier per slice (ring hand-over).  Between barriers a wave runs GEMM1 -> epilogue ->
 //     GEMM2 at its own pace, so the waves of a SIMD drift apart and one wave's epilogue VALU runs beside another's MFMAs.
 // int8 x int8, fast-contract tables (exact-tie mode / all-k-zero mode as separate instantiations), uint16 residuals.
+// The variants (kWP, at the end of the file): a pair runs in workgroups of 128 or 256 pixels that walk all C3 / 64 slices, because
+// GEMM2 accumulates over them.  The expand conv alone (reduce.wgt == NULL) has nothing that spans slices: its rows come in 128- and
+// 64-pixel workgroups and split the slices over gridDim.y, down to ONE slice per workgroup - what fills the chip when the launch has
+// fewer pixel tiles than the part has CUs (profiles/solo_split.md).
 #include <stdio.h>
 #include <utility>
 
@@ -372,7 +376,7 @@ __global__ __launch_bounds__(F::NT, F::MINW) void expand_wp_kernel(const WPP p) 
         for (int k = 0; k < 8; ++k) p.dbgbuf[k] = ph[k];
 #endif
 #undef WP_STAMP
-    if ((oor >> 16) != 0) atomicOr(p.flags, 1);
+    if ((oor >> 16) != 0 && p.res_out) atomicOr(p.flags, 1);   // the flag reports a SATURATED STORE (as the general tiles do): q is computed from the un-clamped sum
     // ---------------------------------------------------------------- epilogue 2: the reduce conv's QuantAct
     if constexpr (F::REDUCE) {
         wait_vmcnt<0>();
@@ -423,10 +427,21 @@ using W256 = WPCfg<256, 4, true, 1>;     // stage 3: 82 KiB; one wave per SIMD (
 using N64 = WPCfg<64, 4, false, 4>;      // expand conv alone (last unit of a stage): 10 KiB
 using N128 = WPCfg<128, 4, false, 3>;
 using N256 = WPCfg<256, 4, false, 3>;
-using N512 = WPCfg<512, 4, false, 2>;    // stage 4: 66 KiB; gridDim.y splits the C3 / 64 slices
+using N512 = WPCfg<512, 4, false, 2>;    // stage 4: 66 KiB
+// 64-pixel workgroups of the expand conv alone (two waves): twice the pixel tiles where M is a few thousand pixels.  The ring DMA costs a
+// wave 2 KC passes per slice instead of KC.  (The C = 256 and C = 512 forms, WPCfg<256, 2, false, 3> at 168 and WPCfg<512, 2, false, 2> at
+// 208 registers, were never the fastest form of any recorded workload - profiles/solo_split.md - and are not built)
+using S128 = WPCfg<128, 2, false, 3>;
+// A launch's variants are the rows that take it, numbered in table order, and recorded plans hold those numbers: new rows go at the END.
+// The expand conv alone has no accumulator across slices, so its rows may split the C3 / 64 slices over gridDim.y down to one slice per
+// workgroup (a row whose split does not divide C3 / 64 does not take the launch); the pairs walk every slice in one workgroup.  Rows 1-14
+// are the table as recorded plans first knew it; behind them only the rows that some workload of profiles/plans.json runs
+// (tools/retune_solo_split.py): a row that never wins is not kept
 const WPInfo kWP[] = {WP_ENTRY(W64, 1), WP_ENTRY(W64B, 1), WP_ENTRY(W128, 1), WP_ENTRY(W128B, 1), WP_ENTRY(W256, 1),
                       WP_ENTRY(N64, 1), WP_ENTRY(N128, 1), WP_ENTRY(N256, 1), WP_ENTRY(N256, 2), WP_ENTRY(N256, 4),
-                      WP_ENTRY(N512, 1), WP_ENTRY(N512, 2), WP_ENTRY(N512, 4), WP_ENTRY(N512, 8)};
+                      WP_ENTRY(N512, 1), WP_ENTRY(N512, 2), WP_ENTRY(N512, 4), WP_ENTRY(N512, 8),
+                      WP_ENTRY(N64, 2), WP_ENTRY(N64, 4), WP_ENTRY(N128, 2), WP_ENTRY(N128, 4), WP_ENTRY(N128, 8),
+                      WP_ENTRY(N256, 16), WP_ENTRY(N512, 32), WP_ENTRY(S128, 8)};
 constexpr int NUM_WP = sizeof(kWP) / sizeof(kWP[0]);
 
 bool wp_expand_ok(const hawq_conv_args &e) {
@@ -463,6 +478,14 @@ int wp_num_variants(const hawq_expand_reduce_args *a) {
     int n = 0;
     while (wp_variant(a, n + 1) >= 0) ++n;
     return n;
+}
+
+// pixels per workgroup and slice split (gridDim.y) of the nth wave-private variant that takes this launch; non-zero: there is none
+int wp_variant_shape(const hawq_expand_reduce_args *a, int nth, int *pixels_per_workgroup, int *slice_split) {
+    const int v = wp_variant(a, nth);
+    if (v < 0) return 1;
+    *pixels_per_workgroup = kWP[v].bm, *slice_split = kWP[v].ysplit;
+    return 0;
 }
 
 int wp_launch(const hawq_expand_reduce_args *a, int nth, void *stream) {

@@ -282,6 +282,11 @@ typedef struct hawq_expand_reduce_args {
 int hawq_conv_expand_reduce(const hawq_expand_reduce_args *args, void *stream);
 /* number of kernel variants that take this pair (0: the pair cannot be fused, launch two hawq_conv2d instead) */
 int hawq_conv_expand_reduce_variants(const hawq_expand_reduce_args *args);
+/* Host-only: the launch shape of variant `nth` (numbered as `tile`; 0 = the default) when it is a wave-private variant of
+ * fused_wp.hip - the pixels one workgroup covers (gridDim.x = ceil(M / pixels)) and the number of workgroups along gridDim.y that
+ * share the Cout / 64 output slices of a pixel tile (1 for every pair variant).  Returns 0 and fills both; non-zero, both untouched,
+ * for a variant of another kernel family or an id the launch does not have.  For tests, the tuner's log and tools. */
+int hawq_conv_expand_reduce_variant_shape(const hawq_expand_reduce_args *args, int32_t nth, int32_t *pixels_per_workgroup, int32_t *slice_split);
 
 /* QuantAct input case (quant_modules.py:271-274; quant_utils.py:73-97, 237-258):
  * q = clamp(rint(inv_scale * x), lo, hi); fp32 NCHW [N][3][H][W] -> int8 NHWC4 with a zero
