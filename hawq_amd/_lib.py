@@ -164,6 +164,11 @@ class JpegScan(C.Structure):
                 + [(n, i32) for n in ("ac_off", "restart", "n_intervals", "interval_off", "stream_off", "stream_len")] + [("reserved", i32 * 3)])
 
 
+class JpegResumeSeg(C.Structure):
+    """struct hawq_jpeg_resume_seg (include/hawq_mi355.h): one segment of a restart interval of a resume call."""
+    _fields_ = [(n, i32) for n in ("wave", "unit0", "n_units", "byte", "bit", "eobrun")] + [("pred", i32 * 3), ("reserved", i32)]
+
+
 # name -> (argtypes); every function returns int except hawq_last_error
 SIGNATURES = {
     "hawq_abi_version": [],
@@ -222,6 +227,10 @@ SIGNATURES = {
     "hawq_jpeg_decode_batch_sync": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i64, i32, vp, i64, vp, vp],
     "hawq_jpeg_prog_ok": [vp, i64, i64, i64, i64],
     "hawq_jpeg_decode_batch_prog": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp],
+    "hawq_jpeg_resume_record": [vp, i64, i32, i32, vp, i64, C.POINTER(i64)],
+    "hawq_jpeg_resume_ok": [vp, i64, i32, i64, i64],
+    "hawq_jpeg_decode_batch_resume": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, vp],
+    "hawq_jpeg_decode_batch_prog_resume": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, vp],
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
     "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],

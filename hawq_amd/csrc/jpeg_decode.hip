@@ -8,11 +8,14 @@
 //   3 colour    one thread per output pixel: fancy upsampling of the chroma planes, YCbCr -> RGB.
 //   1 (sync)    hawq_jpeg_decode_batch_sync: intervals of at least min_sync_bytes go to jpeg_sync_kernel instead - one workgroup per interval,
 //               one lane per sub_bytes of it, speculative starts synchronised round after round (jpeg_sync.h); the same coefficients.
-// Everything the kernels index with comes from the blob, and hawq_jpeg_batch_ok (and hawq_jpeg_sync_ok for the job table) has passed
-// that blob on the host before any launch.
+//   1 (resume)  hawq_jpeg_decode_batch_resume: one wave per SEGMENT of a restart interval - the serial kernel started at a recorded
+//               resume point (jpeg_resume.h): a bit position and the predictors there; the same coefficients.
+// Everything the kernels index with comes from the blob, and hawq_jpeg_batch_ok (and hawq_jpeg_sync_ok for the job table,
+// hawq_jpeg_resume_ok for the segment table) has passed that blob on the host before any launch.
 #include <string.h>
 
 #include "common.h"
+#include "jpeg_resume.h"
 #include "jpeg_stages.h"
 #include "jpeg_sync.h"
 
@@ -63,13 +66,23 @@ const char *batch_refusal(const void *host_blob, int64_t blob_bytes, int64_t coe
 
 // ---- stage 1 ---------------------------------------------------------------------------------------------------------------------
 // The stream comes through the 256-byte LDS window of jpeg_stages.h (WindowSrc).
-__global__ __launch_bounds__(WAVE) void jpeg_entropy_kernel(const uint8_t *__restrict__ blob, int16_t *__restrict__ coef, int32_t *__restrict__ status, int32_t skip_from) {
+// RESUME (hawq_jpeg_decode_batch_resume): workgroup x decodes segment x of the table at segs_off - the units, the start position and the
+// predictors its entry names (jpeg_resume.h), the units clamped to those of the entry's interval.
+template <bool RESUME>
+__global__ __launch_bounds__(WAVE) void jpeg_entropy_kernel(const uint8_t *__restrict__ blob, int16_t *__restrict__ coef, int32_t *__restrict__ status, int32_t skip_from,
+                                                            int64_t segs_off) {
     __shared__ hawq_jpeg_huff tables[6];   // dc, ac per component
     __shared__ uint8_t window[WINDOW];
     const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
     const int lane = threadIdx.x;
-    if ((int)blockIdx.x >= hd.n_waves) return;
-    const hawq_jpeg_wave w = ((const hawq_jpeg_wave *)(blob + hd.wave_off))[blockIdx.x];
+    hawq_jpeg_resume_seg seg = {};
+    int32_t wave_at = (int32_t)blockIdx.x;
+    if constexpr (RESUME) {
+        seg = ((const hawq_jpeg_resume_seg *)(blob + segs_off))[blockIdx.x];
+        wave_at = seg.wave;
+    }
+    if (wave_at < 0 || wave_at >= hd.n_waves) return;
+    const hawq_jpeg_wave w = ((const hawq_jpeg_wave *)(blob + hd.wave_off))[wave_at];
     const hawq_jpeg_desc d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[w.image];
     const hawq_jpeg_huff *dc[3], *ac[3];
     for (int c = 0; c < 3; ++c) {
@@ -87,8 +100,15 @@ __global__ __launch_bounds__(WAVE) void jpeg_entropy_kernel(const uint8_t *__res
     const int32_t mcu0 = d.restart ? w.interval * d.restart : 0;
     const int32_t n_mcu = d.restart ? min(d.restart, mcus - mcu0) : mcus;
     WindowSrc src{blob + d.stream_off, window, -WINDOW, last, lane};
-    JpegBits<WindowSrc> br(src, first, last);
-    const int32_t st = jpeg_decode_interval(br, d, dc, ac, mcu0, n_mcu, coef + d.coef_block0 * 64, lane == 0);
+    int32_t st;
+    if constexpr (RESUME) {
+        seg.unit0 = min(max(seg.unit0, 0), n_mcu), seg.n_units = min(max(seg.n_units, 0), n_mcu - seg.unit0);
+        JpegBits<WindowSrc> br(src, min(max(seg.byte, first), last), last);
+        st = jpeg_resume_segment(br, d, dc, ac, mcu0, seg, coef + d.coef_block0 * 64, lane == 0);
+    } else {
+        JpegBits<WindowSrc> br(src, first, last);
+        st = jpeg_decode_interval(br, d, dc, ac, mcu0, n_mcu, coef + d.coef_block0 * 64, lane == 0);
+    }
     if (lane == 0 && st != 0) atomicCAS(&status[w.image], 0, st);
 }
 
@@ -318,8 +338,8 @@ const char *sync_refusal(const void *host_blob, int64_t blob_bytes, int32_t sub_
 }
 
 int decode_batch(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes, int64_t plane_bytes, uint8_t *out,
-                 int64_t out_bytes, int32_t *status, int32_t sub_bytes, int32_t skip_from, int64_t jobs_off, int32_t n_jobs, void *scratch, void *const *events,
-                 void *stream) {
+                 int64_t out_bytes, int32_t *status, int32_t sub_bytes, int32_t skip_from, int64_t jobs_off, int32_t n_jobs, void *scratch, int64_t segs_off,
+                 int64_t n_segs, void *const *events, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     hawq_jpeg_batch_hdr hd;
     memcpy(&hd, host_blob, sizeof hd);
@@ -327,7 +347,10 @@ int decode_batch(const void *blob, const void *host_blob, int64_t blob_bytes, in
     HAWQ_CHECK_HIP(hipMemsetAsync(coef, 0, (size_t)coef_blocks * 128, s));
     HAWQ_CHECK_HIP(hipMemsetAsync(status, 0, (size_t)hd.n_images * sizeof(int32_t), s));
     if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[0], s));
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)hd.n_waves), dim3(WAVE), 0, s, (const uint8_t *)blob, coef, status, skip_from);
+    if (n_segs > 0)   // one wave per segment (hawq_jpeg_decode_batch_resume)
+        hipLaunchKernelGGL((jpeg_entropy_kernel<true>), dim3((unsigned)n_segs), dim3(WAVE), 0, s, (const uint8_t *)blob, coef, status, 0, segs_off);
+    else
+        hipLaunchKernelGGL((jpeg_entropy_kernel<false>), dim3((unsigned)hd.n_waves), dim3(WAVE), 0, s, (const uint8_t *)blob, coef, status, skip_from, (int64_t)0);
     HAWQ_CHECK_HIP(hipGetLastError());
     if (n_jobs > 0) {
         hipLaunchKernelGGL(jpeg_sync_kernel, dim3((unsigned)n_jobs), dim3(SYNC_THREADS), 0, s, (const uint8_t *)blob, coef, status, jobs_off, sub_bytes,
@@ -350,7 +373,7 @@ extern "C" int hawq_jpeg_decode_batch(const void *blob, const void *host_blob, i
     HAWQ_REQUIRE(blob && coef && planes && out && status, "hawq_jpeg_decode_batch: null pointer");
     const char *why = batch_refusal(host_blob, blob_bytes, coef_blocks, plane_bytes, out_bytes);
     HAWQ_REQUIRE(!why, "hawq_jpeg_decode_batch: %s", why);
-    return decode_batch(blob, host_blob, blob_bytes, coef, coef_blocks, planes, plane_bytes, out, out_bytes, status, 0, 0, 0, 0, nullptr, events, stream);
+    return decode_batch(blob, host_blob, blob_bytes, coef, coef_blocks, planes, plane_bytes, out, out_bytes, status, 0, 0, 0, 0, nullptr, 0, 0, events, stream);
 }
 
 extern "C" int hawq_jpeg_sync_ok(const void *host_blob, int64_t blob_bytes, int32_t sub_bytes, int32_t min_sync_bytes, int64_t jobs_off, int32_t n_jobs,
@@ -368,5 +391,15 @@ extern "C" int hawq_jpeg_decode_batch_sync(const void *blob, const void *host_bl
     if (!why) why = sync_refusal(host_blob, blob_bytes, sub_bytes, min_sync_bytes, jobs_off, n_jobs, scratch_bytes);
     HAWQ_REQUIRE(!why, "hawq_jpeg_decode_batch_sync: %s", why);
     return decode_batch(blob, host_blob, blob_bytes, coef, coef_blocks, planes, plane_bytes, out, out_bytes, status, sub_bytes, min_sync_bytes, jobs_off, n_jobs, scratch,
-                        events, stream);
+                        0, 0, events, stream);
+}
+
+extern "C" int hawq_jpeg_decode_batch_resume(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                                             int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, int64_t segs_off, int64_t n_segs,
+                                             void *const *events, void *stream) {
+    HAWQ_REQUIRE(blob && coef && planes && out && status, "hawq_jpeg_decode_batch_resume: null pointer");
+    const char *why = batch_refusal(host_blob, blob_bytes, coef_blocks, plane_bytes, out_bytes);
+    if (!why) why = resume_refusal(host_blob, blob_bytes, 0, segs_off, n_segs);
+    HAWQ_REQUIRE(!why, "hawq_jpeg_decode_batch_resume: %s", why);
+    return decode_batch(blob, host_blob, blob_bytes, coef, coef_blocks, planes, plane_bytes, out, out_bytes, status, 0, 0, 0, 0, nullptr, segs_off, n_segs, events, stream);
 }

@@ -154,14 +154,21 @@ HAWQ_HD int32_t jpeg_decode_block(JpegBits<Src> &br, const hawq_jpeg_huff *dc, c
 HAWQ_HD int jpeg_comp_h(const hawq_jpeg_desc &d, int c) { return c == 0 ? d.hs : 1; }
 HAWQ_HD int jpeg_comp_v(const hawq_jpeg_desc &d, int c) { return c == 0 ? d.vs : 1; }
 
-// One restart interval: MCUs mcu0 .. mcu0 + n_mcu - 1 of image `d` in raster order, predictors starting at 0.  `coef` is the image's
-// first block (d.coef_block0 applied by the caller); `dc` / `ac` the tables per component.  Returns the status.
-template <class Src>
-HAWQ_HD int32_t jpeg_decode_interval(JpegBits<Src> &br, const hawq_jpeg_desc &d, const hawq_jpeg_huff *const *dc, const hawq_jpeg_huff *const *ac,
-                                     int32_t mcu0, int32_t n_mcu, int16_t *coef, bool store) {
-    int32_t pred[3] = {0, 0, 0};
+// What the unit loops tell about every unit they start (jpeg_resume.h records resume points through it); this one listens to nothing.
+struct JpegNoHook {
+    template <class Bits>
+    HAWQ_HD void unit(int32_t, const Bits &, const int32_t *, int32_t) {}
+};
+
+// MCUs mcu0 .. mcu0 + n_mcu - 1 of image `d` in raster order from the predictors `pred`, which it advances.  `coef` is the image's
+// first block (d.coef_block0 applied by the caller); `dc` / `ac` the tables per component.  Before MCU m of them it calls
+// hook.unit(m, reader, predictors, 0).  Returns the status.
+template <class Src, class Hook>
+HAWQ_HD int32_t jpeg_decode_units(JpegBits<Src> &br, const hawq_jpeg_desc &d, const hawq_jpeg_huff *const *dc, const hawq_jpeg_huff *const *ac, int32_t mcu0,
+                                  int32_t n_mcu, int16_t *coef, bool store, int32_t *pred, Hook &hook) {
     int32_t mx = mcu0 % d.mcus_x, my = mcu0 / d.mcus_x;
     for (int32_t m = 0; m < n_mcu; ++m) {
+        hook.unit(m, br, pred, 0);
         int64_t comp0 = 0;   // first block of the component
         for (int c = 0; c < d.ncomp; ++c) {
             const int h = jpeg_comp_h(d, c), v = jpeg_comp_v(d, c);
@@ -176,4 +183,13 @@ HAWQ_HD int32_t jpeg_decode_interval(JpegBits<Src> &br, const hawq_jpeg_desc &d,
         if (++mx == d.mcus_x) mx = 0, ++my;
     }
     return br.status;
+}
+
+// One restart interval: the MCUs with the predictors starting at 0.
+template <class Src>
+HAWQ_HD int32_t jpeg_decode_interval(JpegBits<Src> &br, const hawq_jpeg_desc &d, const hawq_jpeg_huff *const *dc, const hawq_jpeg_huff *const *ac,
+                                     int32_t mcu0, int32_t n_mcu, int16_t *coef, bool store) {
+    int32_t pred[3] = {0, 0, 0};
+    JpegNoHook hook;
+    return jpeg_decode_units(br, d, dc, ac, mcu0, n_mcu, coef, store, pred, hook);
 }

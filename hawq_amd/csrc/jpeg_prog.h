@@ -170,17 +170,18 @@ HAWQ_HD int64_t jpeg_prog_comp0(const hawq_jpeg_desc &d, int c) {
     return at;
 }
 
-// One restart interval: units unit0 .. unit0 + n_units - 1 of scan `sc` of image `d`, predictors and EOBRUN starting at 0.  dc: the
-// tables of the scan's components (first DC pass), ac: the scan's AC table.  Returns the status.
-template <class Src, class Blk>
-HAWQ_HD int32_t jpeg_prog_interval(JpegBits<Src> &br, const hawq_jpeg_desc &d, const hawq_jpeg_scan &sc, const hawq_jpeg_huff *const *dc, const hawq_jpeg_huff *ac,
-                                   int32_t unit0, int32_t n_units, Blk &blk) {
-    JpegProgState st = {{0, 0, 0}, 0};
+// Units unit0 .. unit0 + n_units - 1 of scan `sc` of image `d` from the state `st`, which it advances.  dc: the tables of the scan's
+// components (first DC pass), ac: the scan's AC table.  Before unit n of them it calls hook.unit(n, reader, predictors, EOBRUN).
+// Returns the status.
+template <class Src, class Blk, class Hook>
+HAWQ_HD int32_t jpeg_prog_units_from(JpegBits<Src> &br, const hawq_jpeg_desc &d, const hawq_jpeg_scan &sc, const hawq_jpeg_huff *const *dc, const hawq_jpeg_huff *ac,
+                                     int32_t unit0, int32_t n_units, Blk &blk, JpegProgState &st, Hook &hook) {
     if (sc.ncomp == 1) {
         const int32_t w = jpeg_prog_own_w(d, sc.comp0);
         const int64_t comp0 = jpeg_prog_comp0(d, sc.comp0), bw = (int64_t)d.mcus_x * jpeg_comp_h(d, sc.comp0);
         int32_t bx = unit0 % w, by = unit0 / w;
         for (int32_t n = 0; n < n_units; ++n) {
+            hook.unit(n, br, st.pred, st.eobrun);
             if (jpeg_prog_block(br, sc, dc, ac, 0, st, blk, comp0 + by * bw + bx)) return br.status;
             if (++bx == w) bx = 0, ++by;
         }
@@ -188,6 +189,7 @@ HAWQ_HD int32_t jpeg_prog_interval(JpegBits<Src> &br, const hawq_jpeg_desc &d, c
     }
     int32_t mx = unit0 % d.mcus_x, my = unit0 / d.mcus_x;
     for (int32_t m = 0; m < n_units; ++m) {
+        hook.unit(m, br, st.pred, st.eobrun);
         int64_t comp0 = 0;
         for (int c = 0; c < sc.ncomp; ++c) {
             const int h = jpeg_comp_h(d, c), v = jpeg_comp_v(d, c);
@@ -200,4 +202,13 @@ HAWQ_HD int32_t jpeg_prog_interval(JpegBits<Src> &br, const hawq_jpeg_desc &d, c
         if (++mx == d.mcus_x) mx = 0, ++my;
     }
     return br.status;
+}
+
+// One restart interval: the units with predictors and EOBRUN starting at 0.
+template <class Src, class Blk>
+HAWQ_HD int32_t jpeg_prog_interval(JpegBits<Src> &br, const hawq_jpeg_desc &d, const hawq_jpeg_scan &sc, const hawq_jpeg_huff *const *dc, const hawq_jpeg_huff *ac,
+                                   int32_t unit0, int32_t n_units, Blk &blk) {
+    JpegProgState st = {{0, 0, 0}, 0};
+    JpegNoHook hook;
+    return jpeg_prog_units_from(br, d, sc, dc, ac, unit0, n_units, blk, st, hook);
 }

@@ -11,11 +11,15 @@
 //               lies in the scan's band ss .. se store it back, 16 bits each - never a word another scan of the level owns.  A first
 //               AC pass reads nothing: its stage starts as zeros.  DC scans touch coefficient 0 alone and never branch on it: lane 0
 //               stores it.
-// Everything the kernel indexes with comes from the blob, and hawq_jpeg_prog_ok has passed that blob on the host before any launch.
+//   1 (resume)  hawq_jpeg_decode_batch_prog_resume: one wave per SEGMENT of a restart interval of a scan, started at a recorded resume
+//               point (jpeg_resume.h): a bit position, the predictors and EOBRUN there.  A block belongs to one segment,
+//               so the staged block needs no new ordering; a level's launch holds the segments of the level's waves.
+// Everything the kernel indexes with comes from the blob, and hawq_jpeg_prog_ok (and hawq_jpeg_resume_ok for the segment table) has
+// passed that blob on the host before any launch.
 #include <string.h>
 
 #include "common.h"
-#include "jpeg_prog.h"
+#include "jpeg_resume.h"
 #include "jpeg_stages.h"
 
 namespace {
@@ -55,14 +59,24 @@ struct LdsBlock {
     }
 };
 
-__global__ __launch_bounds__(WAVE) void jpeg_prog_kernel(const uint8_t *__restrict__ blob, int16_t *coef, int32_t *__restrict__ status, int32_t wave0) {
+// RESUME (hawq_jpeg_decode_batch_prog_resume): workgroup x decodes segment wave0 + x of the table at segs_off - the units, the start
+// position and the state its entry names (jpeg_resume.h), the units clamped to those of the entry's interval.
+template <bool RESUME>
+__global__ __launch_bounds__(WAVE) void jpeg_prog_kernel(const uint8_t *__restrict__ blob, int16_t *coef, int32_t *__restrict__ status, int32_t wave0, int64_t segs_off) {
     __shared__ hawq_jpeg_huff tables[3];   // DC per component of the scan, or the AC table in [0]
     __shared__ uint8_t window[WINDOW];
     __shared__ int16_t stage[64];
     const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
     const hawq_jpeg_prog_hdr ph = *(const hawq_jpeg_prog_hdr *)(blob + sizeof(hawq_jpeg_batch_hdr));
     const int lane = threadIdx.x;
-    const hawq_jpeg_prog_wave w = ((const hawq_jpeg_prog_wave *)(blob + hd.wave_off))[wave0 + (int32_t)blockIdx.x];
+    hawq_jpeg_resume_seg seg = {};
+    int32_t wave_at = wave0 + (int32_t)blockIdx.x;
+    if constexpr (RESUME) {
+        seg = ((const hawq_jpeg_resume_seg *)(blob + segs_off))[wave_at];
+        wave_at = seg.wave;
+        if (wave_at < 0 || wave_at >= hd.n_waves) return;
+    }
+    const hawq_jpeg_prog_wave w = ((const hawq_jpeg_prog_wave *)(blob + hd.wave_off))[wave_at];
     const hawq_jpeg_scan sc = ((const hawq_jpeg_scan *)(blob + ph.scan_off))[w.scan];
     const hawq_jpeg_desc d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[sc.image];
     const bool dc_first = sc.ss == 0 && sc.ah == 0, ac = sc.ss > 0;
@@ -83,9 +97,16 @@ __global__ __launch_bounds__(WAVE) void jpeg_prog_kernel(const uint8_t *__restri
     const int32_t unit0 = sc.restart ? w.interval * sc.restart : 0;
     const int32_t n_units = sc.restart ? min(sc.restart, units - unit0) : units;
     WindowSrc src{blob + sc.stream_off, window, -WINDOW, last, lane};
-    JpegBits<WindowSrc> br(src, first, last);
     LdsBlock blk{coef + d.coef_block0 * 64, stage, lane};
-    const int32_t st = jpeg_prog_interval(br, d, sc, dc, &tables[0], unit0, n_units, blk);
+    int32_t st;
+    if constexpr (RESUME) {
+        seg.unit0 = min(max(seg.unit0, 0), n_units), seg.n_units = min(max(seg.n_units, 0), n_units - seg.unit0);
+        JpegBits<WindowSrc> br(src, min(max(seg.byte, first), last), last);
+        st = jpeg_resume_prog_segment(br, d, sc, dc, &tables[0], unit0, seg, blk);
+    } else {
+        JpegBits<WindowSrc> br(src, first, last);
+        st = jpeg_prog_interval(br, d, sc, dc, &tables[0], unit0, n_units, blk);
+    }
     if (lane == 0 && st != 0) atomicCAS(&status[sc.image], 0, st);
 }
 
@@ -195,11 +216,14 @@ extern "C" int hawq_jpeg_prog_ok(const void *host_blob, int64_t blob_bytes, int6
     return why == nullptr;
 }
 
-extern "C" int hawq_jpeg_decode_batch_prog(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
-                                           int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *const *events, void *stream) {
-    HAWQ_REQUIRE(blob && coef && planes && out && status, "hawq_jpeg_decode_batch_prog: null pointer");
+namespace {
+// segs: nullptr, or the host blob's segment table - one wave per segment instead of one per interval
+int decode_prog(const char *name, const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes, int64_t plane_bytes,
+                uint8_t *out, int64_t out_bytes, int32_t *status, int64_t segs_off, int64_t n_segs, void *const *events, void *stream) {
+    HAWQ_REQUIRE(blob && coef && planes && out && status, "%s: null pointer", name);
     const char *why = prog_refusal(host_blob, blob_bytes, coef_blocks, plane_bytes, out_bytes);
-    HAWQ_REQUIRE(!why, "hawq_jpeg_decode_batch_prog: %s", why);
+    if (!why && n_segs >= 0) why = resume_refusal(host_blob, blob_bytes, 1, segs_off, n_segs);
+    HAWQ_REQUIRE(!why, "%s: %s", name, why);
     hipStream_t s = (hipStream_t)stream;
     hawq_jpeg_batch_hdr hd;
     hawq_jpeg_prog_hdr ph;
@@ -207,14 +231,38 @@ extern "C" int hawq_jpeg_decode_batch_prog(const void *blob, const void *host_bl
     memcpy(&ph, (const uint8_t *)host_blob + sizeof hd, sizeof ph);
     const hawq_jpeg_desc *desc = (const hawq_jpeg_desc *)((const uint8_t *)host_blob + hd.desc_off);
     const int32_t *level_start = (const int32_t *)((const uint8_t *)host_blob + ph.level_off);
+    const hawq_jpeg_resume_seg *segs = n_segs >= 0 ? (const hawq_jpeg_resume_seg *)((const uint8_t *)host_blob + segs_off) : nullptr;
     HAWQ_CHECK_HIP(hipMemsetAsync(coef, 0, (size_t)coef_blocks * 128, s));
     HAWQ_CHECK_HIP(hipMemsetAsync(status, 0, (size_t)hd.n_images * sizeof(int32_t), s));
     if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[0], s));
+    int64_t seg_at = 0;
     for (int32_t level = 1; level <= ph.n_levels; ++level) {
-        const int32_t n = level_start[level] - level_start[level - 1];   // >= 1: n_levels is the deepest level a scan has
-        hipLaunchKernelGGL(jpeg_prog_kernel, dim3((unsigned)n), dim3(WAVE), 0, s, (const uint8_t *)blob, coef, status, level_start[level - 1]);
+        if (segs) {   // the segments stand in wave order: those of this level's waves are the next ones
+            int64_t seg_end = seg_at;
+            while (seg_end < n_segs && segs[seg_end].wave < level_start[level]) ++seg_end;
+            hipLaunchKernelGGL((jpeg_prog_kernel<true>), dim3((unsigned)(seg_end - seg_at)), dim3(WAVE), 0, s, (const uint8_t *)blob, coef, status, (int32_t)seg_at,
+                               segs_off);
+            seg_at = seg_end;
+        } else {
+            const int32_t n = level_start[level] - level_start[level - 1];   // >= 1: n_levels is the deepest level a scan has
+            hipLaunchKernelGGL((jpeg_prog_kernel<false>), dim3((unsigned)n), dim3(WAVE), 0, s, (const uint8_t *)blob, coef, status, level_start[level - 1], (int64_t)0);
+        }
         HAWQ_CHECK_HIP(hipGetLastError());
     }
     if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[1], s));
     return launch_pixel_stages(blob, desc, hd.n_images, coef, planes, out, events, s);
+}
+}  // namespace
+
+extern "C" int hawq_jpeg_decode_batch_prog(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                                           int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *const *events, void *stream) {
+    return decode_prog("hawq_jpeg_decode_batch_prog", blob, host_blob, blob_bytes, coef, coef_blocks, planes, plane_bytes, out, out_bytes, status, 0, -1, events, stream);
+}
+
+extern "C" int hawq_jpeg_decode_batch_prog_resume(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                                                  int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, int64_t segs_off, int64_t n_segs,
+                                                  void *const *events, void *stream) {
+    HAWQ_REQUIRE(n_segs >= 0, "hawq_jpeg_decode_batch_prog_resume: segment count negative");
+    return decode_prog("hawq_jpeg_decode_batch_prog_resume", blob, host_blob, blob_bytes, coef, coef_blocks, planes, plane_bytes, out, out_bytes, status, segs_off, n_segs,
+                       events, stream);
 }

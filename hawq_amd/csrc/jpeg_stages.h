@@ -81,4 +81,7 @@ struct WindowSrc {
 // IDCT coef -> planes, upsampling + colour planes -> out.  events: NULL or four; [2] and [3] are recorded behind the two stages.
 int launch_pixel_stages(const void *blob, const hawq_jpeg_desc *host_desc, int32_t n_images, const int16_t *coef, uint8_t *planes, uint8_t *out, void *const *events,
                         hipStream_t stream);
+
+// The segment table of a resume call (jpeg_resume.hip) against a host blob the checker of its kind has passed: nullptr, or why not.
+const char *resume_refusal(const void *host_blob, int64_t blob_bytes, int progressive, int64_t segs_off, int64_t n_segs);
 }  // namespace hawq_jpeg

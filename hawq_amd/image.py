@@ -389,7 +389,7 @@ def decoded_batches(samples, batch_size: int, workers: int = 0, decode=decode_im
 
 
 def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int = 224, device="cuda", fused: bool = False, workers: int = 0,
-                  device_decode: bool = False, entropy: str = "serial", progressive: bool = False):
+                  device_decode: bool = False, entropy: str = "serial", progressive: bool = False, resume=None):
     """Iterate an ImageFolder tree as ``(uint8 [n, crop, crop, 3] on the MI355X, int64 targets)`` batches - the validation loader of
     quant_train.py:428-445 (shuffle off) with everything behind the decoder on the device; feed it to ``api.validate(uint8=True)``.
     The defaults are the ResNets' geometry; InceptionV3 wants ``resize=342, crop=299`` (``eval_geometry(arch)``).
@@ -397,14 +397,19 @@ def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int
     with that many threads (at most 16), one batch ahead of the GPU (``decoded_batches``).  ``device_decode``: the threads only read the
     files; baseline JPEGs are decoded on the MI355X and everything else by the host decoder (``jpeg.decode_jpeg_batch``), and the batch is
     resampled in place by ``preprocess_batch_fused`` (implies ``fused``); ``entropy`` goes to ``decode_jpeg_batch`` (``"sync"``: many
-    lanes per long restart interval); ``progressive`` (needs ``device_decode``): progressive JPEGs are decoded on the MI355X too.
-    Same order, labels and bytes either way."""
+    lanes per long restart interval); ``progressive`` (needs ``device_decode``): progressive JPEGs are decoded on the MI355X too;
+    ``resume`` (needs ``device_decode``): a ``jpeg.ResumeIndex`` or the path of a saved one - the files it has an entry for are decoded
+    from their recorded resume points, many waves per long restart interval.  Same order, labels and bytes either way."""
     if progressive and not device_decode:
         raise ValueError("progressive=True needs device_decode=True")
+    if resume is not None and not device_decode:
+        raise ValueError("resume needs device_decode=True")
     samples, _ = image_folder(root)
     if device_decode:
         from . import jpeg
         more = {"progressive": True} if progressive else {}
+        if resume is not None:
+            more["resume"] = resume if isinstance(resume, jpeg.ResumeIndex) else jpeg.ResumeIndex.load(resume)
         for datas, targets in decoded_batches(samples, batch_size, workers, decode=jpeg.read_source):
             imgs, _ = jpeg.decode_jpeg_batch(datas, device, entropy=entropy, **more)
             yield preprocess_batch_fused(imgs, resize, crop, device=device), torch.tensor(targets, dtype=torch.int64)

@@ -12,6 +12,9 @@ Host side, pure Python / numpy, one of each:
   records with the level of every scan.
 - one launch (``_launch``) plans into a pinned staging buffer, has the library check the blob, uploads it in one copy and runs
   ``hawq_jpeg_decode_batch`` / ``_sync`` / ``_prog`` (entropy decode -> IDCT -> upsampling + colour) into the caller's output.
+- one index of resume points (``ResumeIndex``, ``build_resume_index``): the states in which the serial decoder starts a
+  unit, recorded once per file by the library on the host; both planners place them as a segment table behind the blob they write
+  anyway, and ``_launch`` runs ``hawq_jpeg_decode_batch_resume`` / ``_prog_resume`` on it, one wave per segment of a restart interval.
 ``decode_jpeg_batch`` allocates the output, launches the progressive and the baseline files of a batch and hands every refused or failed
 image to the host decoder, with the reason.  ``image.folder_loader(device_decode=True)`` feeds the result to ``preprocess_batch_fused``
 in place.
@@ -19,7 +22,10 @@ in place.
 from __future__ import annotations
 
 import bisect
+import contextlib
 import ctypes as C
+import zlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -34,12 +40,15 @@ _HDR = np.dtype(_lib.JpegBatchHdr)
 _JOB = np.dtype(_lib.JpegSyncJob)
 _PHDR = np.dtype(_lib.JpegProgHdr)
 _SCAN = np.dtype(_lib.JpegScan)
+_SEG = np.dtype(_lib.JpegResumeSeg)
 MAX_SCANS = 64   # HAWQ_JPEG_PROG_MAX_SCANS
 SYNC_SUB_MIN, SYNC_SUB_MAX = 16, 4096   # HAWQ_JPEG_SYNC_SUB_MIN / _MAX
 SYNC_JOB_HDR_BYTES, SYNC_SUB_RECORD_BYTES = 16, C.sizeof(_lib.JpegSyncSub)
 # entropy="sync" defaults: the fastest row of profiles/jpeg_sync.md on files without restart markers that leaves files with them alone
 SUB_BYTES = 32
 MIN_SYNC_BYTES = 4096
+# resume points: the fastest row of profiles/jpeg_resume.md on progressive files without restart markers that leaves files with them alone
+RESUME_EVERY = 512
 STATUS_NAMES = {1: "ran out of bytes", 2: "code not in table", 3: "coefficient index past 63", 4: "unexpected marker"}
 
 
@@ -530,18 +539,56 @@ def _wave_list(ks, counts):
     return waves
 
 
-def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, sync=None) -> JpegPlan:
+class JpegResumePlan(JpegPlan):
+    """``JpegPlan`` of a plan made with ``resume``: ``segs_off`` / ``n_segs``: the table of ``hawq_jpeg_resume_seg`` in the blob, one segment
+    or more per wave, in the order of the wave list."""
+    __slots__ = ("segs_off", "n_segs")
+
+    def resume_ok(self) -> bool:
+        """``hawq_jpeg_resume_ok`` on the host blob (after ``ok``; no GPU work)."""
+        return bool(_lib.load().hawq_jpeg_resume_ok(self.blob.ctypes.data, self.nbytes, 0, self.segs_off, self.n_segs))
+
+
+def _segment_table(first, units, points):
+    """The ``hawq_jpeg_resume_seg`` table of a blob.  ``first`` / ``units``: per wave of its wave list the first byte of the interval and
+    how many units it has; ``points``: int [k, 8] resume points as (wave, unit, byte, bit, eobrun, pred x 3).  Every wave gets the
+    segment that starts its interval; a point starts another one."""
+    n = len(first)
+    rows = np.zeros((n + len(points), 8), np.int64)
+    rows[:n, 0], rows[:n, 2] = np.arange(n), first
+    rows[n:] = points
+    rows = rows[np.lexsort((rows[:, 1], rows[:, 0]))]
+    segs = np.zeros(len(rows), _SEG)
+    segs["wave"], segs["unit0"], segs["byte"], segs["bit"], segs["eobrun"], segs["pred"] = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5:8]
+    upto = np.asarray(units, np.int64)[np.clip(rows[:, 0], 0, n - 1)]   # a point of no wave: the checker refuses it
+    same = rows[1:, 0] == rows[:-1, 0]
+    upto[:-1][same] = rows[1:, 1][same]
+    segs["n_units"] = upto - rows[:, 1]
+    return segs
+
+
+def _interval_units(units, restart, n_intervals):
+    """units of each of the ``n_intervals`` restart intervals of a scan of ``units`` units"""
+    if not restart:
+        return np.array([units])
+    return np.minimum(restart, units - restart * np.arange(n_intervals))
+
+
+def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, sync=None, resume=None) -> JpegPlan:
     """Pack the records of ``parse_jpeg`` into one host blob: header | descriptors | wave list | per image: quantisation tables, Huffman
     tables, intervals, stream - every part at a 16-byte aligned offset.  ``out_offsets`` / ``out_bytes``: where each image goes in an
     output buffer of that size (default: one after the other, 16-byte aligned).  ``reserve(nbytes)`` returns the uint8 array to write
     into (at least nbytes, 16-byte aligned; e.g. a pinned staging buffer); a fresh array without it.  ``sync`` = (sub_bytes,
     min_sync_bytes): append the job table of ``hawq_jpeg_decode_batch_sync`` behind the streams - one job per interval of at least
-    ``min_sync_bytes`` bytes, cut into sub-sequences of ``sub_bytes``, with its slice of the scratch."""
+    ``min_sync_bytes`` bytes, cut into sub-sequences of ``sub_bytes``, with its slice of the scratch.  ``resume``: per record its resume
+    points (``ResumeIndex.points``): append the segment table of ``hawq_jpeg_decode_batch_resume`` instead (a ``JpegResumePlan``)."""
     records = list(records)
     if not records:
         raise ValueError("empty batch")
+    if sync is not None and resume is not None:
+        raise ValueError("a batch is decoded with entropy='sync' or from resume points, not both")
     n = len(records)
-    plan, blob = JpegPlan(), _Blob()
+    plan, blob = JpegPlan() if resume is None else JpegResumePlan(), _Blob()
     plan.n_waves = sum(len(r.intervals) for r in records)
     hdr, desc = np.zeros(1, _HDR), np.zeros(n, _DESC)
     blob.room(_HDR.itemsize)
@@ -577,6 +624,12 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, syn
                     plan.scratch_bytes += SYNC_JOB_HDR_BYTES + SYNC_SUB_RECORD_BYTES * n_sub
                 wave += 1
         plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off, plan.n_jobs = sub_bytes, min_sync_bytes, blob.place(np.array(plan.jobs, _JOB)), len(plan.jobs)
+    if resume is not None:
+        wave0 = np.cumsum([0] + [len(r.intervals) for r in records])
+        points = [np.column_stack((wave0[i] + p[:, 1], p[:, 2:])) for i, p in enumerate(resume)]
+        segs = _segment_table(np.concatenate([r.intervals[:, 0] for r in records]),
+                              np.concatenate([_interval_units(r.mcus_x * r.mcus_y, r.restart, len(r.intervals)) for r in records]), np.concatenate(points))
+        plan.segs_off, plan.n_segs = blob.place(segs), len(segs)
     for off, table in ((0, hdr), (desc_off, desc), (wave_off, _wave_list(range(n), [len(r.intervals) for r in records]))):
         blob.put(off, table)
     return plan.finish(blob, reserve, out_bytes)
@@ -591,16 +644,25 @@ class JpegProgPlan(_Plan):
     checker = "hawq_jpeg_prog_ok"
 
 
-def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None) -> JpegProgPlan:
+class JpegProgResumePlan(JpegProgPlan):
+    """``JpegProgPlan`` of a plan made with ``resume``: ``segs_off`` / ``n_segs`` as in ``JpegResumePlan``."""
+    __slots__ = ("segs_off", "n_segs")
+
+    def resume_ok(self) -> bool:
+        return bool(_lib.load().hawq_jpeg_resume_ok(self.blob.ctypes.data, self.nbytes, 1, self.segs_off, self.n_segs))
+
+
+def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None, resume=None) -> JpegProgPlan:
     """Pack the ``JpegProgRecord``s of ``parse_jpeg(progressive=True)`` into the host blob of ``hawq_jpeg_decode_batch_prog``: batch header |
     progressive header | descriptors (entropy fields zero) | scan table | level list | wave lists, level after level | per image: the
     quantisation tables, then per scan its Huffman tables, intervals and stream - every part at a 16-byte aligned offset.  Computes the
-    level of every scan (``scan_levels``).  ``out_offsets`` / ``out_bytes`` / ``reserve`` as in ``plan_jpeg_batch``."""
+    level of every scan (``scan_levels``).  ``out_offsets`` / ``out_bytes`` / ``reserve`` / ``resume`` as in ``plan_jpeg_batch``: with
+    ``resume`` the segment table of ``hawq_jpeg_decode_batch_prog_resume`` stands behind the streams (a ``JpegProgResumePlan``)."""
     records = list(records)
     if not records:
         raise ValueError("empty batch")
     n = len(records)
-    plan, blob = JpegProgPlan(), _Blob()
+    plan, blob = JpegProgPlan() if resume is None else JpegProgResumePlan(), _Blob()
     plan.n_scans = sum(len(r.scans) for r in records)
     plan.levels = levels = [lv for r in records for lv in scan_levels(r.scans)]
     plan.n_levels = max(levels)
@@ -632,25 +694,130 @@ def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None
         ks = np.flatnonzero(np.array(levels) == level)
         waves.append(_wave_list(ks, scans["n_intervals"][ks]))
         plan.level_start.append(plan.level_start[-1] + len(waves[-1]))
+    waves = np.concatenate(waves)
+    if resume is not None:
+        heads = waves[:, 1] == 0
+        wave_of = np.zeros(plan.n_scans, np.int64)   # a scan's intervals follow one another in the wave list
+        wave_of[waves[heads, 0]] = np.flatnonzero(heads)
+        scan0 = np.cumsum([0] + [len(r.scans) for r in records])
+        points = [np.column_stack((wave_of[np.clip(scan0[i] + p[:, 0], 0, plan.n_scans - 1)] + p[:, 1], p[:, 2:])) for i, p in enumerate(resume)]
+        flat = [s for r in records for s in r.scans]
+        first, units = np.zeros(plan.n_waves, np.int64), np.zeros(plan.n_waves, np.int64)
+        for k, s in enumerate(flat):
+            first[wave_of[k]:wave_of[k] + len(s.intervals)] = s.intervals[:, 0]
+            units[wave_of[k]:wave_of[k] + len(s.intervals)] = _interval_units(s.units, s.restart, len(s.intervals))
+        segs = _segment_table(first, units, np.concatenate(points))
+        plan.segs_off, plan.n_segs = blob.place(segs), len(segs)
     for off, table in ((0, hdr), (_HDR.itemsize, phdr), (plan.desc_off, desc), (plan.scan_off, scans), (plan.level_off, np.array(plan.level_start, np.int32)),
-                       (plan.wave_off, np.concatenate(waves))):
+                       (plan.wave_off, waves)):
         blob.put(off, table)
     return plan.finish(blob, reserve, out_bytes)
 
 
+# ------------------------------------------------------------------------------------------------------------------ resume points
+class ResumeIndex:
+    """Resume points of JPEG files, recorded once by ``build_resume_index`` and used by ``decode_jpeg_batch(resume=)``
+    every time the same bytes are decoded again.  ``every``: the distance in stream bytes they were recorded at; ``entries``: {(file
+    length, CRC-32 of the file): (progressive, points)} with ``points`` int32 [k, 9], per point (scan - 0 in a baseline file, restart
+    interval, unit, byte, bit, eobrun, predictor x 3) in the order of the file.  A file whose intervals are all shorter than ``every``
+    has an entry without points."""
+
+    def __init__(self, every, entries=None):
+        self.every, self.entries = int(every), dict(entries or {})
+
+    def __len__(self):
+        return len(self.entries)
+
+    @staticmethod
+    def key(data):
+        return len(data), zlib.crc32(data)
+
+    def points(self, data, record):
+        """The points of the file ``data`` that parsed into ``record``, or None: no entry for these bytes, or one of the other kind."""
+        entry = self.entries.get(self.key(data))
+        return entry[1] if entry is not None and entry[0] == isinstance(record, JpegProgRecord) else None
+
+    def save(self, path):
+        """To a path or a binary file object, as one ``.npz`` of plain arrays: ``every``, per entry ``length`` / ``crc`` / ``progressive`` / ``start`` (its first row of
+        ``points``; one more entry at the end), and ``points``."""
+        keys = sorted(self.entries)
+        counts = [len(self.entries[k][1]) for k in keys]
+        with (contextlib.nullcontext(path) if hasattr(path, "write") else open(path, "wb")) as f:   # the name as given: numpy would append .npz
+            np.savez(f, every=np.int32(self.every), length=np.array([k[0] for k in keys], np.int64), crc=np.array([k[1] for k in keys], np.uint32),
+                     progressive=np.array([self.entries[k][0] for k in keys], np.uint8), start=np.cumsum([0] + counts).astype(np.int64),
+                     points=np.concatenate([self.entries[k][1] for k in keys] + [np.zeros((0, 9), np.int32)]))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            start, points = z["start"], np.ascontiguousarray(z["points"], np.int32).reshape(-1, 9)
+            n = len(z["length"])
+            if len(start) != n + 1 or len(z["crc"]) != n or len(z["progressive"]) != n or np.any(np.diff(start) < 0) or start[0] != 0 or start[-1] != len(points):
+                raise ValueError(f"{path}: not a resume index")
+            return cls(int(z["every"]), {(int(n), int(c)): (bool(p), points[a:b]) for n, c, p, a, b in zip(z["length"], z["crc"], z["progressive"], start[:-1], start[1:])})
+
+
+def record_resume_points(record, every):
+    """The resume points of one parsed file, int32 [k, 9] as in ``ResumeIndex``: plans it alone and runs ``hawq_jpeg_resume_record`` - the
+    serial decoders on the host, no GPU work."""
+    prog = isinstance(record, JpegProgRecord)
+    plan = plan_jpeg_prog_batch([record]) if prog else plan_jpeg_batch([record])
+    scans = record.scans if prog else [record]
+    room = plan.n_waves + sum(int(((s.intervals[:, 1] - s.intervals[:, 0]) // every).sum()) for s in scans)
+    segs, n = np.zeros(room, _SEG), C.c_int64(0)
+    _lib.call("hawq_jpeg_resume_record", plan.blob.ctypes.data, plan.nbytes, int(prog), int(every), segs.ctypes.data, room, C.byref(n))
+    segs = segs[:n.value]
+    segs = segs[segs["unit0"] > 0]
+    points = np.empty((len(segs), 9), np.int32)
+    if prog:
+        points[:, :2] = plan.blob[plan.wave_off:plan.wave_off + 8 * plan.n_waves].view(np.int32).reshape(-1, 2)[segs["wave"]]
+    else:
+        points[:, 0], points[:, 1] = 0, segs["wave"]
+    points[:, 2], points[:, 3], points[:, 4], points[:, 5], points[:, 6:] = segs["unit0"], segs["byte"], segs["bit"], segs["eobrun"], segs["pred"]
+    return points[np.lexsort((points[:, 2], points[:, 1], points[:, 0]))]
+
+
+def build_resume_index(sources, every=RESUME_EVERY, progressive=False, workers=0) -> ResumeIndex:
+    """Paths or bytes of image files -> the ``ResumeIndex`` of those the device path takes (``progressive``: progressive files too), with
+    a point at the first unit boundary at least ``every`` stream bytes behind the one before in every restart interval longer than that.
+    The recorder is host code of the library and releases the GIL: ``workers`` threads share the files."""
+    every = int(every)
+    if every < 1:
+        raise ValueError(f"every must be at least 1, not {every}")
+
+    def one(source):
+        data = read_source(source)
+        try:
+            record = parse_jpeg(data, progressive=True) if progressive else parse_jpeg(data)
+        except UnsupportedJpeg:
+            return None
+        return ResumeIndex.key(data), (isinstance(record, JpegProgRecord), record_resume_points(record, every))
+
+    sources = list(sources)
+    if workers > 0:
+        with ThreadPoolExecutor(min(int(workers), 16)) as pool:
+            found = list(pool.map(one, sources))
+    else:
+        found = [one(s) for s in sources]
+    return ResumeIndex(every, dict(f for f in found if f is not None))
+
+
 # ------------------------------------------------------------------------------------------------------------------ the device call
-def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None):
+def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None, resume=None):
     """The device call of ``decode_jpeg_batch`` for records of one kind: plan into the pinned staging buffer of that kind, check, upload
     in one copy, run the three stages on the current stream, writing into the uint8 device tensor ``out`` at ``out_offsets``.  Returns
     the int32 status per record as a device tensor: reading it synchronises, so the caller does that when everything of the batch is
     enqueued.  ``JpegProgRecord``s: ``hawq_jpeg_decode_batch_prog``.  ``JpegRecord``s: ``hawq_jpeg_decode_batch``, or with ``sync`` =
     (sub_bytes, min_sync_bytes) ``hawq_jpeg_decode_batch_sync``; a dict ``info`` then receives ``jobs`` (the plan's) and ``rounds`` /
-    ``decodes`` (what the kernel counted per job; a synchronising read of the scratch)."""
+    ``decodes`` (what the kernel counted per job; a synchronising read of the scratch).  ``resume``: per record its resume points:
+    ``hawq_jpeg_decode_batch_resume`` / ``_prog_resume``, one wave per segment."""
     from .image import _STAGING, _Staging
     prog = isinstance(records[0], JpegProgRecord)
     if prog and sync is not None:
         raise ValueError("entropy='sync' does not take progressive records")
     key, entry = ("jpeg_prog", "hawq_jpeg_decode_batch_prog") if prog else ("jpeg", "hawq_jpeg_decode_batch" if sync is None else "hawq_jpeg_decode_batch_sync")
+    if resume is not None:
+        key, entry = key + "_resume", ("hawq_jpeg_decode_batch_prog" if prog else "hawq_jpeg_decode_batch") + "_resume"
     lib = _lib.load()
     with torch.cuda.device(dev):
         st = _STAGING.setdefault((dev.index, key), _Staging())   # one per kind: both blobs of a batch are in flight at once
@@ -660,8 +827,12 @@ def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None):
             held["host"], held["dev"] = st.reserve(nbytes, dev)
             return held["host"].numpy()
 
-        plan = plan_jpeg_prog_batch(records, out_offsets, out.numel(), reserve) if prog else plan_jpeg_batch(records, out_offsets, out.numel(), reserve, sync)
-        if not plan.ok() or (sync is not None and not plan.sync_ok()):   # on the host blob, before anything is uploaded or launched
+        if prog:
+            plan = plan_jpeg_prog_batch(records, out_offsets, out.numel(), reserve, resume)
+        else:
+            plan = plan_jpeg_batch(records, out_offsets, out.numel(), reserve, sync, resume)
+        # on the host blob, before anything is uploaded or launched
+        if not plan.ok() or (sync is not None and not plan.sync_ok()) or (resume is not None and not plan.resume_ok()):
             raise RuntimeError("libhawq_mi355: " + lib.hawq_last_error().decode())
         st.upload(plan.nbytes)
         coef = torch.empty(plan.coef_blocks * 64, dtype=torch.int16, device=dev)
@@ -671,6 +842,8 @@ def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None):
         if sync is not None:
             scratch = torch.empty(max(plan.scratch_bytes, 16), dtype=torch.uint8, device=dev)
             more = (plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off, plan.n_jobs, scratch.data_ptr(), plan.scratch_bytes)
+        if resume is not None:
+            more = (plan.segs_off, plan.n_segs)
         ev = (C.c_void_p * 4)(*events) if events is not None else None
         _lib.call(entry, held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks, planes.data_ptr(), plan.plane_bytes,
                   out.data_ptr(), out.numel(), status.data_ptr(), *more, ev, torch.cuda.current_stream(dev).cuda_stream)
@@ -692,7 +865,7 @@ def read_source(source) -> bytes:
         return f.read()
 
 
-def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, min_sync_bytes=None, progressive=False):
+def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, min_sync_bytes=None, progressive=False, resume=None):
     """Paths or bytes of image files -> ``(images, fallbacks)``: ``images[i]`` a uint8 [H, W, 3] RGB tensor on the MI355X equal to
     ``image.decode_image(sources[i])``, ``fallbacks`` the list of ``(index, reason)`` of the images the HOST decoder produced: files
     ``parse_jpeg`` refuses (progressive, CMYK, not a JPEG, ...) and files whose device decode reported a status (damaged streams).
@@ -704,7 +877,10 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
     ``progressive``: progressive files (SOF2) inside the scope of ``parse_progressive`` are decoded on the device as well
     (``hawq_jpeg_decode_batch_prog``, one wave per scan and restart interval, one entropy launch per level of the batch) into the same
     allocation, in a second call beside the one for the baseline files; the rest fall back as before.  ``entropy="sync"`` applies to the
-    baseline files only: a progressive scan is decoded by one wave per restart interval."""
+    baseline files only: a progressive scan is decoded by one wave per restart interval.
+    ``resume``: a ``ResumeIndex``.  A file it has an entry for (same length, same CRC-32, same kind) is decoded from its recorded resume
+    points, one wave per segment of a restart interval (``hawq_jpeg_decode_batch_resume`` / ``_prog_resume``), in a call of its own
+    beside those above; every other file goes exactly the way it goes without the option - the same bytes and the same fallbacks."""
     from .image import decode_image
     if entropy not in ("serial", "sync"):
         raise ValueError(f"entropy must be 'serial' or 'sync', not {entropy!r}")
@@ -727,11 +903,16 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
     sizes = [(records[i].height, records[i].width) if i in records else tuple(host[i].shape[:2]) for i in range(len(datas))]
     offsets, total = output_layout(sizes)
     out = torch.empty(total, dtype=torch.uint8, device=dev)
-    enqueued = []   # (indices, device status): the progressive call first, the baseline call second, both statuses read behind both
+    # a file whose entry has no points (no interval longer than the index's distance) has nothing to gain: it goes as without the index
+    points = {} if resume is None else {i: p for i, p in ((i, resume.points(datas[i], r)) for i, r in records.items()) if p is not None and len(p)}
+    enqueued = []   # (indices, device status): the progressive calls first, the baseline calls second, every status read behind all of them
     for kind, options in ((JpegProgRecord, {}), (JpegRecord, more)):
-        idx = sorted(i for i, r in records.items() if isinstance(r, kind))
-        if idx:
-            enqueued.append((idx, _launch([records[i] for i in idx], [offsets[i] for i in idx], out, dev, **options)))
+        for indexed in (False, True) if points else (False,):
+            idx = sorted(i for i, r in records.items() if isinstance(r, kind) and (i in points) == indexed)
+            if idx:
+                if indexed:
+                    options = {"resume": [points[i] for i in idx]}
+                enqueued.append((idx, _launch([records[i] for i in idx], [offsets[i] for i in idx], out, dev, **options)))
     status = {i: st for idx, device_status in enqueued for i, st in zip(idx, device_status.cpu().numpy())}
     for i, st in sorted(status.items()):
         if st != 0:

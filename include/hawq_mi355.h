@@ -817,6 +817,45 @@ int hawq_jpeg_prog_ok(const void *host_blob, int64_t blob_bytes, int64_t coef_bl
 int hawq_jpeg_decode_batch_prog(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
                                 int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *const *events, void *stream);
 
+/* ---- long restart intervals from recorded resume points (hawq_amd/csrc/jpeg_resume.h + jpeg_resume.hip) --------------
+ * A resume point is the state in which the serial decoder starts a unit of a restart interval (an MCU; a block in a scan of one
+ * component): the unit's index in the interval, the canonical byte and bit of the next unread bit (jpeg_sync.h), the DC predictors and
+ * EOBRUN.  Points cut an interval into segments, and a segment is decoded by a wave of its own, as a restart interval with a start bit
+ * and a start state.  The blobs are those of hawq_jpeg_decode_batch / _prog with a segment table behind the existing parts: every wave
+ * of the wave list has one segment or more, the segments stand in the order of the wave list, and those of one wave partition its units
+ * in order. */
+typedef struct hawq_jpeg_resume_seg {
+    int32_t wave;                      /* index into the wave list: (image, interval), or (scan, interval) in a progressive blob */
+    int32_t unit0, n_units;            /* units unit0 .. unit0 + n_units - 1 of the interval, unit0 counted from the interval's first */
+    int32_t byte, bit;                 /* the next unread bit: bit 0..7 (0 = first) of the data byte at `byte`, relative to the stream */
+    int32_t eobrun;                    /* 0..32767; 0 outside an AC scan */
+    int32_t pred[3];                   /* 0 outside a baseline image or a first DC pass, and for components the scan does not have */
+    int32_t reserved;
+} hawq_jpeg_resume_seg;                /* 40 bytes */
+/* hawq_jpeg_resume_record needs no device.  host_blob: a blob hawq_jpeg_batch_ok (progressive = 0) or hawq_jpeg_prog_ok (1) passes.  It
+ * runs the serial decoders on the host, a progressive image scan after scan into a slab of its own, and writes the segments of every
+ * wave to segs, in the order of the wave list: a new segment begins at the first unit boundary that lies at least `every` (>= 1) stream
+ * bytes behind the start of the segment before it, and none begins behind the first decode error of an interval.  *n_segs: how many
+ * there are; more than max_segs is an error (n_waves + sum over the intervals of bytes / every is always enough).
+ * hawq_jpeg_resume_ok launches nothing and reads the HOST blob, which the checker of its kind has passed: 1 when the table lies inside
+ * the blob at a 16-byte aligned offset, every wave has its segments in order, they partition its units in order with at least one unit
+ * each, the first one starts at the interval's first byte, bit 0, with a zero state, every later one at a byte inside the interval that
+ * is not smaller than its predecessor's, with bit in 0..7 and eobrun in 0..32767, and eobrun / pred are zero where the comments above
+ * say so; else 0 with the reason in hawq_last_error().
+ * hawq_jpeg_decode_batch_resume / _prog_resume run the checker of the kind and hawq_jpeg_resume_ok again, then work as
+ * hawq_jpeg_decode_batch / _prog with one wave per segment in stage 1.  Same coefficients, same status, same output bytes, when the
+ * points are those of the blob's streams; with any other table that passes the check every store still goes to a block of the
+ * segment's own units. */
+int hawq_jpeg_resume_record(const void *host_blob, int64_t blob_bytes, int32_t progressive, int32_t every, hawq_jpeg_resume_seg *segs, int64_t max_segs,
+                            int64_t *n_segs);
+int hawq_jpeg_resume_ok(const void *host_blob, int64_t blob_bytes, int32_t progressive, int64_t segs_off, int64_t n_segs);
+int hawq_jpeg_decode_batch_resume(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                                  int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, int64_t segs_off, int64_t n_segs, void *const *events,
+                                  void *stream);
+int hawq_jpeg_decode_batch_prog_resume(const void *blob, const void *host_blob, int64_t blob_bytes, int16_t *coef, int64_t coef_blocks, uint8_t *planes,
+                                       int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, int64_t segs_off, int64_t n_segs,
+                                       void *const *events, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,8 +21,15 @@ of which a quarter is progressive): host, ``device_decode`` as it is without the
 the calling thread, one after the other) and ``decode_jpeg_batch(progressive=True)``, the three alternating in one process; then the
 stages of ``hawq_jpeg_decode_batch_prog`` with HIP events (stage 1: all its levels).  Writes profiles/jpeg_progressive.md.
 
+``--resume`` measures decoding from recorded resume points (``RESUME_SETS``: the baseline set without restart markers, the mixed-size
+set and the progressive sets): the index is built per set (build time and bytes per file reported), then ``decode_jpeg_batch(progressive=
+True)`` as it is, with ``entropy="sync"``, with ``resume=index`` and Pillow in 16 threads alternate in one process; then the entropy
+stage of the three device paths with HIP events, summed over the calls of a batch (one per kind of file), and the entropy stage from
+points recorded ``--every`` 256 .. 4096 bytes apart, each alternating with the serial stage.  Writes profiles/jpeg_resume.md.
+
     python tools/jpeg_bench.py [--batch 128] [--repeats 20] [--warmup 3] [--out profiles/jpeg_decode.md] [--box NAME]
                                [--entropy serial|sync|both] [--sub-bytes N] [--min-sync-bytes N] [--sweep] [--sets 0,1,3] [--progressive]
+                               [--resume] [--every N]
 """
 import argparse
 import ctypes as C
@@ -64,6 +71,12 @@ PROGRESSIVE_SETS = {
 }
 
 
+# the sets of --resume: long intervals of both kinds, and the sets with restart markers that the option must leave where they were
+RESUME_SETS = {k: SETS[k] for k in ("375x500 q90 4:2:0", "mixed sizes / qualities / subsamplings")}
+RESUME_SETS.update(PROGRESSIVE_SETS)
+EVERY_SWEEP = (256, 512, 1024, 2048, 4096)
+
+
 def make_set(variants, n):
     from PIL import Image
     with Image.open(os.path.join(ROOT, "tests", "golden", "sample_500x375.jpg")) as im:
@@ -102,8 +115,10 @@ def main():
     ap.add_argument("--min-sync-bytes", type=int, default=jpeg.MIN_SYNC_BYTES)
     ap.add_argument("--sweep", action="store_true", help="entropy stage of the sync path over a grid of sub_bytes x min_sync_bytes")
     ap.add_argument("--sets", default=None, help="comma-separated indices into SETS (default: all)")
+    ap.add_argument("--resume", action="store_true", help="resume points: the serial, sync and resume device paths and Pillow, and a sweep over the distance")
+    ap.add_argument("--every", type=int, default=jpeg.RESUME_EVERY, help="distance of the resume points of the wall-time rows")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
+    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_resume.md" if args.resume else "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
     paths = ("serial", "sync") if args.entropy == "both" else (args.entropy,)
     sync_of = {"serial": None, "sync": (args.sub_bytes, args.min_sync_bytes)}
     picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(SETS))
@@ -118,6 +133,8 @@ def main():
         ev = C.c_void_p()
         _lib.check(lib.hawq_event_create(C.byref(ev)))
         events.append(ev)
+    if args.resume:
+        return resume(args, box, dev, lib, events)
     if args.progressive:
         return progressive(args, box, dev, lib, events)
     rows, sweep_rows = [], []
@@ -301,6 +318,123 @@ def progressive(args, box, dev, lib, events):
     for r in rows:
         lines.append(f"| {r['n']} x {r['set']} | {r['levels']} | {r['waves']} | {' / '.join(map(str, r['largest_interval_per_level']))} | {f(r['entropy_ms'])} | "
                      f"{f(r['idct_ms'])} | {f(r['colour_ms'])} |")
+    lines.append("")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines))
+    print("wrote", args.out)
+
+
+def resume(args, box, dev, lib, events):
+    """the ``--resume`` report"""
+    picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(RESUME_SETS))
+    sync = (args.sub_bytes, args.min_sync_bytes)
+    rows = []
+    for label, variants in [list(RESUME_SETS.items())[k] for k in picked]:
+        datas = make_set(variants, args.batch)
+        samples = [(d, 0) for d in datas]
+        distinct = list(dict.fromkeys(datas))
+        indexes, build_ms, index_bytes = {}, {}, {}
+        for every in sorted(set(EVERY_SWEEP) | {args.every}):
+            t0 = time.perf_counter()
+            indexes[every] = jpeg.build_resume_index(distinct, every=every, progressive=True)
+            build_ms[every] = (time.perf_counter() - t0) * 1e3 / len(distinct)
+            buf = io.BytesIO()
+            indexes[every].save(buf)
+            index_bytes[every] = len(buf.getvalue()) / len(distinct)
+        index = indexes[args.every]
+
+        def host():
+            imgs, _ = next(iter(image.decoded_batches(samples, len(samples), workers=16)))
+            return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
+
+        def device(**more):
+            imgs, fallbacks = jpeg.decode_jpeg_batch(datas, dev, progressive=True, **more)
+            assert not fallbacks, fallbacks
+            return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
+
+        runs = {"host": host, "serial": device, "sync": lambda: device(entropy="sync", sub_bytes=sync[0], min_sync_bytes=sync[1]), "resume": lambda: device(resume=index)}
+        want = host()
+        for name in ("serial", "sync", "resume"):
+            if not torch.equal(want, runs[name]()):
+                sys.exit(f"jpeg_bench: the host path and the {name} path differ at {label}")
+        for _ in range(args.warmup):
+            for fn in runs.values():
+                fn()
+        t = {name: [] for name in runs}
+        order = list(runs)
+        for r in range(args.repeats):
+            for name in order[r % len(order):] + order[:r % len(order)]:   # every path takes every place in turn
+                t[name].append(wall(runs[name]))
+        # the entropy stage alone, summed over the calls of the batch: parsed once, planned + uploaded + launched per call
+        records = [jpeg.parse_jpeg(d, progressive=True) for d in datas]
+        kinds = [[(r, d) for r, d in zip(records, datas) if isinstance(r, kind)] for kind in (jpeg.JpegProgRecord, jpeg.JpegRecord)]
+        kinds = [k for k in kinds if k]
+        outs = []
+        for kind in kinds:
+            offsets, total = jpeg.output_layout([(r.height, r.width) for r, _ in kind])
+            outs.append((offsets, torch.empty(total, dtype=torch.uint8, device=dev)))
+
+        def entropy_ms(path, every=None):
+            total = 0.0
+            for kind, (offsets, out) in zip(kinds, outs):
+                recs = [r for r, _ in kind]
+                more = {}
+                if path == "sync" and isinstance(recs[0], jpeg.JpegRecord):
+                    more = {"sync": sync}
+                if path == "resume":
+                    more = {"resume": [indexes[every].points(d, r) for r, d in kind]}
+                status = jpeg._launch(recs, offsets, out, dev, events, **more).cpu()   # reads the status: synchronised
+                assert not status.any()
+                ms = C.c_float()
+                _lib.check(lib.hawq_event_elapsed_ms(events[0], events[1], C.byref(ms)))
+                total += ms.value
+            return total
+
+        def staged(pairs):
+            got = {key: [] for key in pairs}
+            for k in range(args.warmup + args.repeats):
+                for key in pairs[k % len(pairs):] + pairs[:k % len(pairs)]:
+                    ms = entropy_ms(*key)
+                    if k >= args.warmup:
+                        got[key].append(ms)
+            return got
+
+        stage = staged([("serial",), ("sync",), ("resume", args.every)])
+        sweep = {every: staged([("serial",), ("resume", every)]) for every in EVERY_SWEEP}
+        lengths = [int(v) for r in records for s in (r.scans if isinstance(r, jpeg.JpegProgRecord) else [r]) for v in (s.intervals[:, 1] - s.intervals[:, 0])]
+        row = {"set": label, "n": len(datas), "every": args.every, "largest_interval_bytes": max(lengths), "waves": len(lengths),
+               "segments": {every: len(lengths) + sum(len(indexes[every].points(d, r)) for r, d in zip(records, datas)) for every in indexes},
+               "index_build_ms_per_file": build_ms, "index_bytes_per_file": index_bytes,
+               "entropy_ms": {name: stat(stage[key]) for name, key in (("serial", ("serial",)), ("sync", ("sync",)), ("resume", ("resume", args.every)))},
+               "sweep_entropy_ms": {every: {"serial": stat(got[("serial",)]), "resume": stat(got[("resume", every)])} for every, got in sweep.items()}}
+        for name in runs:
+            row[name + "_wall_ms"] = stat(t[name])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    f = lambda v: f"{v[0]:.2f} ({v[1]:.2f}-{v[2]:.2f})"
+    lines = ["# JPEG bytes in memory to the cropped batch on the device: long restart intervals from recorded resume points", "",
+             f"Measured on one {box} with `python tools/jpeg_bench.py --resume --batch {args.batch} --repeats {args.repeats} --warmup {args.warmup} --every {args.every}`: "
+             f"median (min-max) of {args.repeats} calls in milliseconds, the paths alternating in one process; outputs compared byte for byte first.  Resize / crop "
+             "256 / 224.", "`Pillow`: Pillow in 16 threads + `preprocess_batch_fused`.  `serial` / `sync` / `resume`: `decode_jpeg_batch(progressive=True)` as it is, with "
+             f"`entropy=\"sync\"` (sub_bytes {sync[0]}, min_sync_bytes {sync[1]}; baseline files only) and with `resume=index` (points every {args.every} bytes, the "
+             "index built before and held in memory) + `preprocess_batch_fused`.  All: host clock around the call and a device synchronise.  Entropy: HIP events "
+             "around stage 1, summed over the calls of a batch (one per kind of file).", "",
+             "| set | largest interval (bytes) | Pillow wall | serial wall | sync wall | resume wall | serial entropy | sync entropy | resume entropy |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        e = r["entropy_ms"]
+        lines.append(f"| {r['n']} x {r['set']} | {r['largest_interval_bytes']} | {f(r['host_wall_ms'])} | {f(r['serial_wall_ms'])} | {f(r['sync_wall_ms'])} | "
+                     f"{f(r['resume_wall_ms'])} | {f(e['serial'])} | {f(e['sync'])} | {f(e['resume'])} |")
+    lines += ["", "## Entropy stage over the distance of the points", "", "Each cell: the resume stage 1 (the serial stage 1 alternating with it), HIP events around the stage.", "",
+              "| set | " + " | ".join(f"every {v}" for v in EVERY_SWEEP) + " |", "|---|" + "---|" * len(EVERY_SWEEP)]
+    for r in rows:
+        lines.append(f"| {r['set']} | " + " | ".join(f"{f(r['sweep_entropy_ms'][v]['resume'])} ({r['sweep_entropy_ms'][v]['serial'][0]:.2f})" for v in EVERY_SWEEP) + " |")
+    lines += ["", "## The index", "", "Waves without an index, segments with one, build time (one thread, parse + plan + record) and size in the saved `.npz` per distinct file.", "",
+              "| set | waves | " + " | ".join(f"segments / ms / bytes at {v}" for v in EVERY_SWEEP) + " |", "|---|---|" + "---|" * len(EVERY_SWEEP)]
+    for r in rows:
+        lines.append(f"| {r['set']} | {r['waves']} | " + " | ".join(f"{r['segments'][v]} / {r['index_build_ms_per_file'][v]:.2f} / {r['index_bytes_per_file'][v]:.0f}"
+                                                                     for v in EVERY_SWEEP) + " |")
     lines.append("")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
