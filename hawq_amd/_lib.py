@@ -169,6 +169,22 @@ class JpegResumeSeg(C.Structure):
     _fields_ = [(n, i32) for n in ("wave", "unit0", "n_units", "byte", "bit", "eobrun")] + [("pred", i32 * 3), ("reserved", i32)]
 
 
+class JpegFrontFile(C.Structure):
+    """struct hawq_jpeg_front_file (include/hawq_mi355.h): where one raw file lies in the files buffer of hawq_jpeg_front_scan."""
+    _fields_ = [("offset", i64), ("length", i64)]
+
+
+class JpegFrontInfo(C.Structure):
+    """struct hawq_jpeg_front_info (include/hawq_mi355.h): what hawq_jpeg_front_scan found in one file."""
+    _fields_ = ([(n, i32) for n in ("defer", "width", "height", "ncomp", "hs", "vs", "restart", "n_intervals")] + [(n, i32 * 3) for n in ("tq", "td", "ta")]
+                + [("qt_at", i32 * 4), ("huff_at", i32 * 4), ("scan_first", i32), ("scan_end", i32), ("reserved", i32 * 5)])
+
+
+class JpegFrontPlace(C.Structure):
+    """struct hawq_jpeg_front_place (include/hawq_mi355.h): where hawq_jpeg_front_fill writes one file's share of the blob."""
+    _fields_ = [("file", i32)] + [(n, i32 * 3) for n in ("qt_off", "dc_off", "ac_off")] + [("interval_off", i32), ("stream_off", i32), ("reserved", i32 * 4)]
+
+
 # name -> (argtypes); every function returns int except hawq_last_error
 SIGNATURES = {
     "hawq_abi_version": [],
@@ -231,6 +247,10 @@ SIGNATURES = {
     "hawq_jpeg_resume_ok": [vp, i64, i32, i64, i64],
     "hawq_jpeg_decode_batch_resume": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, vp],
     "hawq_jpeg_decode_batch_prog_resume": [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, vp],
+    "hawq_jpeg_front_scan": [vp, i64, vp, vp, i32, vp, vp],
+    "hawq_jpeg_front_scan_host": [vp, i64, vp, i32, vp],
+    "hawq_jpeg_front_fill_ok": [vp, vp, i32, vp, i32, i64, i64],
+    "hawq_jpeg_front_fill": [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, i64, vp],
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
     "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],

@@ -389,7 +389,7 @@ def decoded_batches(samples, batch_size: int, workers: int = 0, decode=decode_im
 
 
 def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int = 224, device="cuda", fused: bool = False, workers: int = 0,
-                  device_decode: bool = False, entropy: str = "serial", progressive: bool = False, resume=None):
+                  device_decode: bool = False, entropy: str = "serial", progressive: bool = False, resume=None, front_end: str = "host"):
     """Iterate an ImageFolder tree as ``(uint8 [n, crop, crop, 3] on the MI355X, int64 targets)`` batches - the validation loader of
     quant_train.py:428-445 (shuffle off) with everything behind the decoder on the device; feed it to ``api.validate(uint8=True)``.
     The defaults are the ResNets' geometry; InceptionV3 wants ``resize=342, crop=299`` (``eval_geometry(arch)``).
@@ -399,7 +399,13 @@ def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int
     resampled in place by ``preprocess_batch_fused`` (implies ``fused``); ``entropy`` goes to ``decode_jpeg_batch`` (``"sync"``: many
     lanes per long restart interval); ``progressive`` (needs ``device_decode``): progressive JPEGs are decoded on the MI355X too;
     ``resume`` (needs ``device_decode``): a ``jpeg.ResumeIndex`` or the path of a saved one - the files it has an entry for are decoded
-    from their recorded resume points, many waves per long restart interval.  Same order, labels and bytes either way."""
+    from their recorded resume points, many waves per long restart interval; ``front_end`` (``"device"`` needs ``device_decode``): the
+    MI355X walks the headers of the baseline files and writes their blob itself (``jpeg.decode_jpeg_batch``).  Same order, labels and bytes
+    either way."""
+    if front_end not in ("host", "device"):
+        raise ValueError(f"front_end must be 'host' or 'device', not {front_end!r}")
+    if front_end == "device" and not device_decode:
+        raise ValueError("front_end='device' needs device_decode=True")
     if progressive and not device_decode:
         raise ValueError("progressive=True needs device_decode=True")
     if resume is not None and not device_decode:
@@ -410,6 +416,8 @@ def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int
         more = {"progressive": True} if progressive else {}
         if resume is not None:
             more["resume"] = resume if isinstance(resume, jpeg.ResumeIndex) else jpeg.ResumeIndex.load(resume)
+        if front_end != "host":
+            more["front_end"] = front_end
         for datas, targets in decoded_batches(samples, batch_size, workers, decode=jpeg.read_source):
             imgs, _ = jpeg.decode_jpeg_batch(datas, device, entropy=entropy, **more)
             yield preprocess_batch_fused(imgs, resize, crop, device=device), torch.tensor(targets, dtype=torch.int64)

@@ -856,6 +856,56 @@ int hawq_jpeg_decode_batch_prog_resume(const void *blob, const void *host_blob, 
                                        int64_t plane_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, int64_t segs_off, int64_t n_segs,
                                        void *const *events, void *stream);
 
+/* ---- the front end of the baseline decoder on the device (hawq_amd/csrc/jpeg_front.h + jpeg_front.hip) ----------------
+ * The raw files of a batch lie in one buffer, file i at table[i].offset (16-byte aligned) with table[i].length bytes.  The scan walks
+ * the headers of every file, checks the restart markers of its entropy-coded segment and writes one hawq_jpeg_front_info per file; the
+ * fill writes an accepted file's tables, restart intervals and stream into the blob of hawq_jpeg_decode_batch.  A file the walker does
+ * not take gets a defer code and nothing else; the caller hands it to hawq_amd.jpeg.parse_jpeg, which accepts or refuses it. */
+enum {
+    HAWQ_JPEG_FRONT_OK = 0,
+    HAWQ_JPEG_FRONT_REFUSED = 1,       /* not a baseline file of the accepted kind, or malformed: parse_jpeg refuses it too */
+    HAWQ_JPEG_FRONT_LONG_HEADER = 2,   /* more than HAWQ_JPEG_FRONT_MAX_SEGMENTS marker segments before the scan */
+    HAWQ_JPEG_FRONT_TOO_LARGE = 3      /* more than HAWQ_JPEG_FRONT_MAX_BYTES bytes */
+};
+enum { HAWQ_JPEG_FRONT_MAX_SEGMENTS = 64, HAWQ_JPEG_FRONT_MAX_BYTES = 1 << 30 };
+typedef struct hawq_jpeg_front_file {  /* one entry of the file table */
+    int64_t offset, length;
+} hawq_jpeg_front_file;
+typedef struct hawq_jpeg_front_info {
+    int32_t defer;                     /* HAWQ_JPEG_FRONT_*; every other field is zero unless it is HAWQ_JPEG_FRONT_OK */
+    int32_t width, height, ncomp, hs, vs;
+    int32_t restart, n_intervals;
+    int32_t tq[3], td[3], ta[3];       /* per component: quantisation, DC and AC table id */
+    int32_t qt_at[4];                  /* per quantisation table id: file offset of the 64 bytes in force at the SOS, 0: none */
+    int32_t huff_at[4];                /* per DC id 0, 1, AC id 0, 1: file offset of BITS (16 counts, then the values), 0: none */
+    int32_t scan_first, scan_end;      /* the entropy-coded segment: first byte, one past the last (where EOI stands) */
+    int32_t reserved[5];
+} hawq_jpeg_front_info;                /* 128 bytes */
+typedef struct hawq_jpeg_front_place { /* where the fill writes one accepted file's share of the blob; every offset 16-byte aligned */
+    int32_t file;                      /* index into the file table and the info records */
+    int32_t qt_off[3], dc_off[3], ac_off[3];   /* per component: where its table goes, 0: an earlier component has placed it */
+    int32_t interval_off, stream_off;
+    int32_t reserved[4];
+} hawq_jpeg_front_place;               /* 64 bytes */
+/* hawq_jpeg_front_scan: files / table / info are device memory, host_table the host copy of table, which is checked before anything is
+ * launched: every file 16-byte aligned, inside files_bytes, behind the one before it.  One wave per file on `stream`.
+ * hawq_jpeg_front_scan_host: the same walker over host memory; no device.
+ * hawq_jpeg_front_fill_ok launches nothing and reads host memory: 1 when every entry of host_place names a file of the table whose info
+ * is accepted, every table, the scan and the restart count the info names lie inside that file, and every destination lies inside
+ * blob_bytes at a 16-byte aligned offset behind the one before it (per file: per component its quantisation, DC and AC table where
+ * placed, then the intervals, then the stream); else 0 with the reason in hawq_last_error().
+ * hawq_jpeg_front_fill: info / place are the device copies of host_info / host_place.  It checks again, zeroes blob on `stream` and runs
+ * one workgroup per entry: uint16[64] quantisation tables as stored, canonical hawq_jpeg_huff records, int32 [n_intervals][2] from the
+ * RSTn markers between scan_first and scan_end, and the bytes of the scan.  Header, descriptors and wave list are the caller's. */
+int hawq_jpeg_front_scan(const void *files, int64_t files_bytes, const hawq_jpeg_front_file *table, const hawq_jpeg_front_file *host_table, int32_t n_files,
+                         hawq_jpeg_front_info *info, void *stream);
+int hawq_jpeg_front_scan_host(const void *host_files, int64_t files_bytes, const hawq_jpeg_front_file *host_table, int32_t n_files, hawq_jpeg_front_info *host_info);
+int hawq_jpeg_front_fill_ok(const hawq_jpeg_front_info *host_info, const hawq_jpeg_front_place *host_place, int32_t n, const hawq_jpeg_front_file *host_table,
+                            int32_t n_files, int64_t files_bytes, int64_t blob_bytes);
+int hawq_jpeg_front_fill(const void *files, int64_t files_bytes, const hawq_jpeg_front_file *table, const hawq_jpeg_front_file *host_table, int32_t n_files,
+                         const hawq_jpeg_front_info *info, const hawq_jpeg_front_info *host_info, const hawq_jpeg_front_place *place,
+                         const hawq_jpeg_front_place *host_place, int32_t n, void *blob, int64_t blob_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,9 +27,15 @@ True)`` as it is, with ``entropy="sync"``, with ``resume=index`` and Pillow in 1
 stage of the three device paths with HIP events, summed over the calls of a batch (one per kind of file), and the entropy stage from
 points recorded ``--every`` 256 .. 4096 bytes apart, each alternating with the serial stage.  Writes profiles/jpeg_resume.md.
 
+``--front-end both`` measures the device front end (``decode_jpeg_batch(front_end="device")``) against the host one, the
+two alternating in one process on ``FRONT_SETS``: the set with restart markers every MCU row on the serial entropy stage, the set without
+markers and the mixed set with ``entropy="sync"``.  Per path the wall time of ``decode_jpeg_batch`` + ``preprocess_batch_fused`` and the
+host milliseconds between the call and its first decode launch (parse + plan + upload on the host path; upload, scan, read-back, layout,
+fill and read-back on the device path).  Writes profiles/jpeg_front.md.
+
     python tools/jpeg_bench.py [--batch 128] [--repeats 20] [--warmup 3] [--out profiles/jpeg_decode.md] [--box NAME]
                                [--entropy serial|sync|both] [--sub-bytes N] [--min-sync-bytes N] [--sweep] [--sets 0,1,3] [--progressive]
-                               [--resume] [--every N]
+                               [--resume] [--every N] [--front-end both]
 """
 import argparse
 import ctypes as C
@@ -75,6 +81,8 @@ PROGRESSIVE_SETS = {
 RESUME_SETS = {k: SETS[k] for k in ("375x500 q90 4:2:0", "mixed sizes / qualities / subsamplings")}
 RESUME_SETS.update(PROGRESSIVE_SETS)
 EVERY_SWEEP = (256, 512, 1024, 2048, 4096)
+# the sets of --front-end: (set, entropy stage), as profiles/jpeg_sync.md has them
+FRONT_SETS = [("375x500 q90 4:2:0, restart every MCU row", "serial"), ("375x500 q90 4:2:0", "sync"), ("mixed sizes / qualities / subsamplings", "sync")]
 
 
 def make_set(variants, n):
@@ -116,9 +124,10 @@ def main():
     ap.add_argument("--sweep", action="store_true", help="entropy stage of the sync path over a grid of sub_bytes x min_sync_bytes")
     ap.add_argument("--sets", default=None, help="comma-separated indices into SETS (default: all)")
     ap.add_argument("--resume", action="store_true", help="resume points: the serial, sync and resume device paths and Pillow, and a sweep over the distance")
+    ap.add_argument("--front-end", choices=("both",), default=None, help="the host and the device front end of decode_jpeg_batch, alternating")
     ap.add_argument("--every", type=int, default=jpeg.RESUME_EVERY, help="distance of the resume points of the wall-time rows")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_resume.md" if args.resume else "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
+    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_front.md" if args.front_end else "jpeg_resume.md" if args.resume else "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
     paths = ("serial", "sync") if args.entropy == "both" else (args.entropy,)
     sync_of = {"serial": None, "sync": (args.sub_bytes, args.min_sync_bytes)}
     picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(SETS))
@@ -133,6 +142,8 @@ def main():
         ev = C.c_void_p()
         _lib.check(lib.hawq_event_create(C.byref(ev)))
         events.append(ev)
+    if args.front_end:
+        return front_end(args, box, dev)
     if args.resume:
         return resume(args, box, dev, lib, events)
     if args.progressive:
@@ -239,6 +250,70 @@ def main():
                   "| set | sub_bytes | min_sync_bytes | jobs | serial entropy | sync entropy | rounds of the largest interval |", "|---|---|---|---|---|---|---|"]
         for r in sweep_rows:
             lines.append(f"| {r['set']} | {r['sub_bytes']} | {r['min_sync_bytes']} | {r['jobs']} | {f(r['serial_entropy_ms'])} | {f(r['sync_entropy_ms'])} | {r['rounds_largest']} |")
+    lines.append("")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines))
+    print("wrote", args.out)
+
+
+def front_end(args, box, dev):
+    """the ``--front-end both`` report"""
+    picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(FRONT_SETS))
+    rows, first = [], {}
+    call = _lib.call
+
+    def spy(name, *a):   # when the first decode entry point of a decode_jpeg_batch call is reached
+        if name.startswith("hawq_jpeg_decode_batch") and "t" not in first:
+            first["t"] = time.perf_counter()
+        return call(name, *a)
+
+    _lib.call = spy
+    for label, entropy in [FRONT_SETS[k] for k in picked]:
+        datas = make_set(SETS[label], args.batch)
+        more = {} if entropy == "serial" else dict(entropy="sync", sub_bytes=args.sub_bytes, min_sync_bytes=args.min_sync_bytes)
+
+        def device(front):
+            first.clear()
+            t0 = time.perf_counter()
+            imgs, fallbacks = jpeg.decode_jpeg_batch(datas, dev, front_end=front, **more)
+            assert not fallbacks, fallbacks
+            first["ms"] = (first["t"] - t0) * 1e3
+            return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
+
+        if not torch.equal(device("host"), device("device")):
+            sys.exit(f"jpeg_bench: the two front ends differ at {label}")
+        for _ in range(args.warmup):
+            for front in ("host", "device"):
+                device(front)
+        t, before = {"host": [], "device": []}, {"host": [], "device": []}
+        order = list(t)
+        for r in range(args.repeats):
+            for front in order[r % 2:] + order[:r % 2]:   # each path goes first every other time
+                t[front].append(wall(lambda: device(front)))
+                before[front].append(first["ms"])
+        info = jpeg.front_scan_host(datas)
+        row = {"set": label, "entropy": entropy, "n": len(datas), "compressed_mb": sum(map(len, datas)) / 1e6, "accepted": int((info["defer"] == 0).sum()),
+               "waves": int(info["n_intervals"].sum())}
+        for front in order:
+            row[front + "_wall_ms"], row[front + "_before_launch_ms"] = stat(t[front]), stat(before[front])
+        row["wall_ratio"] = row["device_wall_ms"][0] / row["host_wall_ms"][0]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    _lib.call = call
+    f = lambda v: f"{v[0]:.2f} ({v[1]:.2f}-{v[2]:.2f})"
+    lines = ["# The device front end of the JPEG decoder against the host one, alternating in one process", "",
+             f"Measured on one {box} with `python tools/jpeg_bench.py --front-end both --batch {args.batch} --repeats {args.repeats} --warmup {args.warmup}`: median "
+             f"(min-max) of {args.repeats} calls in milliseconds, the two paths alternating, each going first every other time; outputs compared byte for byte first.  "
+             "Resize / crop 256 / 224.", "`host`: `decode_jpeg_batch` as it is (`parse_jpeg` per file, `plan_jpeg_batch`, one upload) + `preprocess_batch_fused`.  "
+             "`device`: the same with `front_end=\"device\"` (raw files up, `hawq_jpeg_front_scan`, records back, numpy layout, `hawq_jpeg_front_fill`, blob back, "
+             "the library's check).  Wall: host clock around the call and a device synchronise.  Before the launch: host clock from the call to its first "
+             f"`hawq_jpeg_decode_batch` / `_sync`.  `entropy=\"sync\"` with sub_bytes {args.sub_bytes}, min_sync_bytes {args.min_sync_bytes}.", "",
+             "| set | entropy | accepted by the scan | waves | host wall | device wall | device / host | host: before the launch | device: before the launch |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['n']} x {r['set']} | {r['entropy']} | {r['accepted']} | {r['waves']} | {f(r['host_wall_ms'])} | {f(r['device_wall_ms'])} | {r['wall_ratio']:.2f} | "
+                     f"{f(r['host_before_launch_ms'])} | {f(r['device_before_launch_ms'])} |")
     lines.append("")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
