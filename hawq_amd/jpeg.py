@@ -6,12 +6,14 @@ Host side, pure Python / numpy, one of each:
   take.  ``parse_jpeg`` gives a ``JpegRecord`` for a baseline file and, with ``progressive=True``, a ``JpegProgRecord`` with the list of
   scans for a progressive one (SOF2): the file is baseline until its frame header says otherwise, and only what the two
   kinds do differently at an SOS is written per kind.
-- one blob writer (``_Blob``) and one geometry filler (``_Plan``) under the two planners: ``plan_jpeg_batch`` packs descriptors, tables,
-  entropy-coded bytes and restart intervals of baseline records (``struct hawq_jpeg_*`` of include/hawq_mi355.h), with ``sync`` also the
-  job table of ``entropy="sync"`` (many lanes per long restart interval); ``plan_jpeg_prog_batch`` packs progressive
-  records with the level of every scan.
+- one layout of the baseline blob (``_baseline_layout``: descriptors and the offset of every table, interval list and stream, ``struct
+  hawq_jpeg_*`` of include/hawq_mi355.h) and two fillers: ``plan_jpeg_batch`` copies the bytes of baseline records there on the host,
+  with ``sync`` also the job table of ``entropy="sync"`` (many lanes per long restart interval, DESIGN.md 12.1) behind them;
+  ``hawq_jpeg_front_fill`` writes them on the device (below).  ``plan_jpeg_prog_batch`` packs progressive records with the level of
+  every scan into a blob of its own format; one blob writer (``_Blob``) and one plan (``_Plan``) serve both planners.
 - one launch (``_launch``) plans into a pinned staging buffer, has the library check the blob, uploads it in one copy and runs
-  ``hawq_jpeg_decode_batch`` / ``_sync`` / ``_prog`` (entropy decode -> IDCT -> upsampling + colour) into the caller's output.
+  ``hawq_jpeg_decode_batch`` / ``_sync`` / ``_prog`` (entropy decode -> IDCT -> upsampling + colour) into the caller's output; its tail
+  (``_decode``: buffers, entry point, the call) is the device front end's as well.
 - one index of resume points (``ResumeIndex``, ``build_resume_index``): the states in which the serial decoder starts a
   unit, recorded once per file by the library on the host; both planners place them as a segment table behind the blob they write
   anyway, and ``_launch`` runs ``hawq_jpeg_decode_batch_resume`` / ``_prog_resume`` on it, one wave per segment of a restart interval.
@@ -44,6 +46,8 @@ _JOB = np.dtype(_lib.JpegSyncJob)
 _PHDR = np.dtype(_lib.JpegProgHdr)
 _SCAN = np.dtype(_lib.JpegScan)
 _SEG = np.dtype(_lib.JpegResumeSeg)
+_FINFO = np.dtype(_lib.JpegFrontInfo)
+_FPLACE = np.dtype(_lib.JpegFrontPlace)
 MAX_SCANS = 64   # HAWQ_JPEG_PROG_MAX_SCANS
 SYNC_SUB_MIN, SYNC_SUB_MAX = 16, 4096   # HAWQ_JPEG_SYNC_SUB_MIN / _MAX
 SYNC_JOB_HDR_BYTES, SYNC_SUB_RECORD_BYTES = 16, C.sizeof(_lib.JpegSyncSub)
@@ -447,6 +451,13 @@ def output_layout(sizes):
     return offsets, total
 
 
+def _blob_bytes(nbytes: int) -> int:
+    """``nbytes`` as the size of a blob, whose offsets are int32"""
+    if nbytes >= 1 << 31:
+        raise ValueError("batch too large for one blob (2 GiB of compressed data)")
+    return nbytes
+
+
 class _Blob:
     """The host blob of a batch while it is laid out: the cursor ``at`` and the parts with their offsets, every one 16-byte aligned."""
 
@@ -463,17 +474,14 @@ class _Blob:
 
     def place(self, arr):
         """``arr`` behind everything so far -> its offset"""
-        raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
-        off = self.at
-        self.parts.append((off, raw))
-        self.at = _align16(off + raw.size)
+        off = self.room(np.asarray(arr).nbytes)
+        self.put(off, arr)
         return off
 
     def finish(self, reserve):
         """-> the uint8 array with every part in place: ``reserve(nbytes)``, or a fresh zeroed one"""
-        if self.at >= 1 << 31:
-            raise ValueError("batch too large for one blob (2 GiB of compressed data)")
-        blob = np.zeros(self.at, np.uint8) if reserve is None else reserve(self.at)
+        nbytes = _blob_bytes(self.at)
+        blob = np.zeros(nbytes, np.uint8) if reserve is None else reserve(nbytes)
         for off, raw in self.parts:
             blob[off:off + raw.size] = raw
         return blob
@@ -494,17 +502,15 @@ class _Plan:
         """The library's checker on the host blob (no GPU work); the reason of a refusal is in ``hawq_last_error``."""
         return bool(getattr(_lib.load(), self.checker)(self.blob.ctypes.data, self.nbytes, self.coef_blocks, self.plane_bytes, self.out_bytes))
 
-    def add_image(self, d, r, blob, out_off, tables=lambda c, comp: None):
-        """The geometry half of descriptor ``d`` for record ``r``, its quantisation tables into ``blob`` (``tables(c, comp)`` places what
-        else component ``c`` needs, behind its quantisation table), and its share of the three buffers; ``out_off``: None = behind the
-        image before."""
+    def add_image(self, d, r, blob, out_off):
+        """The geometry half of descriptor ``d`` for the progressive record ``r``, its quantisation tables into ``blob``, and its share of
+        the three buffers; ``out_off``: None = behind the image before."""
         d["width"], d["height"], d["ncomp"], d["hs"], d["vs"], d["mcus_x"], d["mcus_y"] = r.width, r.height, r.ncomp, r.hs, r.vs, r.mcus_x, r.mcus_y
         placed = {}
         for c, comp in enumerate(r.components):
             if comp[3] not in placed:
                 placed[comp[3]] = blob.place(r.qtables[comp[3]])
             d["qt_off"][c] = placed[comp[3]]
-            tables(c, comp)
         d["coef_block0"], d["plane_off"] = self.coef_blocks, self.plane_bytes
         self.coef_blocks, self.plane_bytes = self.coef_blocks + r.blocks, self.plane_bytes + r.blocks * 64
         d["out_off"] = off = self.out_bytes if out_off is None else int(out_off)
@@ -600,10 +606,70 @@ def _sync_job_table(lengths, sub_bytes, min_sync_bytes):
     return jobs, int(ends[-1]) if len(ends) else 0
 
 
+# what ``_baseline_layout`` reads of a ``hawq_jpeg_front_info``; ``tq`` ``td`` ``ta``: the quantisation, DC and AC table id per component
+_COLS = _FINFO[["width", "height", "ncomp", "hs", "vs", "restart", "n_intervals", "tq", "td", "ta", "scan_first", "scan_end"]]
+
+
+class FrontLayout:
+    """What ``_baseline_layout`` returns.  ``head``: header | descriptors | wave list as bytes, ``place``: per image where its tables,
+    intervals and stream go (the ``hawq_jpeg_front_place`` table of the fill), ``desc``: the descriptors, ``nbytes``: the blob's size
+    without a job or segment table, ``n_waves`` / ``coef_blocks`` / ``plane_bytes`` / ``out_bytes`` as in ``JpegPlan``."""
+    __slots__ = ("head", "place", "desc", "nbytes", "n_waves", "coef_blocks", "plane_bytes", "out_bytes")
+
+
+def _baseline_layout(o, out_offsets=None, out_bytes=None) -> FrontLayout:
+    """The one place that knows the blob of ``hawq_jpeg_decode_batch``: header | descriptors | wave list | per image, per component the
+    quantisation, DC and AC table it is the first to use, then intervals, then stream - every part at a 16-byte aligned offset; a
+    component that shares a table takes the offset of the first one that has it.  ``o``: the columns ``_COLS`` of the images;
+    ``out_offsets`` / ``out_bytes``: where each image goes in an output buffer of that size (default: one after the other, 16-byte
+    aligned, and the aligned end of the last image).  numpy over the batch, no loop over images.  Two fillers write the bytes of the
+    parts at ``place``: ``plan_jpeg_batch`` on the host, ``hawq_jpeg_front_fill`` on the device."""
+    n = len(o)
+    lay = FrontLayout()
+    colour = o["ncomp"] == 3
+    desc, place = np.zeros(n, _DESC), np.zeros(n, _FPLACE)
+    for f in ("width", "height", "ncomp", "hs", "vs", "restart", "n_intervals"):
+        desc[f] = o[f]
+    desc["mcus_x"], desc["mcus_y"] = -(-o["width"] // (8 * o["hs"])), -(-o["height"] // (8 * o["vs"]))
+    blocks = desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * np.where(colour, o["hs"] * o["vs"] + 2, 1)
+    desc["coef_block0"] = np.cumsum(blocks) - blocks
+    desc["plane_off"] = desc["coef_block0"] * 64
+    rgb = 3 * o["width"].astype(np.int64) * o["height"]
+    desc["out_off"] = np.cumsum((rgb + 15) & ~15) - ((rgb + 15) & ~15) if out_offsets is None else out_offsets
+    desc["stream_len"] = o["scan_end"] - o["scan_first"]
+    lay.n_waves = int(o["n_intervals"].sum())
+    lay.coef_blocks, lay.plane_bytes = int(blocks.sum()), int(blocks.sum()) * 64
+    lay.out_bytes = _align16(int(desc["out_off"][-1] + rgb[-1])) if out_bytes is None else int(out_bytes)
+    # per image the aligned sizes of its parts in blob order: (quantisation, DC, AC) x 3 components, 0 unless the component is the first
+    # to use that table (``first``: per component the first one with its table; a gray image has component 0 alone), intervals, stream
+    sizes, first, used = np.zeros((n, 11), np.int64), {}, colour[:, None] | (np.arange(3) == 0)
+    for k, (ids, nbytes) in enumerate((("tq", 128), ("td", HUFF_BYTES), ("ta", HUFF_BYTES))):
+        t = o[ids]
+        first[ids] = np.stack((0 * t[:, 0], t[:, 1] != t[:, 0], np.where(t[:, 2] == t[:, 0], 0, np.where(t[:, 2] == t[:, 1], 1, 2))), 1) * used
+        sizes[:, k:9:3] = (first[ids] == np.arange(3)) * _align16(nbytes)
+    sizes[:, 9], sizes[:, 10] = (8 * o["n_intervals"].astype(np.int64) + 15) & ~15, (desc["stream_len"].astype(np.int64) + 15) & ~15
+    head = _Blob()
+    hdr_off, desc_off, wave_off = head.room(_HDR.itemsize), head.room(desc.nbytes), head.room(8 * lay.n_waves)
+    ends = head.at + np.cumsum(sizes.reshape(-1)).reshape(n, 11)
+    offs = ends - sizes
+    lay.nbytes = _blob_bytes(int(ends[-1, -1]))
+    for k, (ids, field) in enumerate((("tq", "qt_off"), ("td", "dc_off"), ("ta", "ac_off"))):
+        own = offs[:, k:9:3]
+        place[field] = np.where(first[ids] == np.arange(3), own, 0)
+        desc[field] = np.take_along_axis(own, first[ids], 1) * used
+    place["file"], place["interval_off"], place["stream_off"] = np.arange(n), offs[:, 9], offs[:, 10]
+    desc["interval_off"], desc["stream_off"] = offs[:, 9], offs[:, 10]
+    hdr = np.array([(n, lay.n_waves, desc_off, wave_off)], _HDR)   # n_images, n_waves, desc_off, wave_off
+    for off, table in ((hdr_off, hdr), (desc_off, desc), (wave_off, _wave_list(np.arange(n), o["n_intervals"]))):
+        head.put(off, table)
+    lay.head, lay.place, lay.desc = head.finish(None), place, desc
+    return lay
+
+
 def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, sync=None, resume=None) -> JpegPlan:
-    """Pack the records of ``parse_jpeg`` into one host blob: header | descriptors | wave list | per image: quantisation tables, Huffman
-    tables, intervals, stream - every part at a 16-byte aligned offset.  ``out_offsets`` / ``out_bytes``: where each image goes in an
-    output buffer of that size (default: one after the other, 16-byte aligned).  ``reserve(nbytes)`` returns the uint8 array to write
+    """Pack the records of ``parse_jpeg`` into one host blob laid out by ``_baseline_layout``: the adapter from records to its columns, and
+    the host filler that copies table, interval and stream bytes to the offsets it gives.  ``out_offsets`` / ``out_bytes``: where each
+    image goes in an output buffer of that size (default: one after the other, 16-byte aligned).  ``reserve(nbytes)`` returns the uint8 array to write
     into (at least nbytes, 16-byte aligned; e.g. a pinned staging buffer); a fresh array without it.  ``sync`` = (sub_bytes,
     min_sync_bytes): append the job table of ``hawq_jpeg_decode_batch_sync`` behind the streams - one job per interval of at least
     ``min_sync_bytes`` bytes, cut into sub-sequences of ``sub_bytes``, with its slice of the scratch.  ``resume``: per record its resume
@@ -613,26 +679,20 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, syn
         raise ValueError("empty batch")
     if sync is not None and resume is not None:
         raise ValueError("a batch is decoded with entropy='sync' or from resume points, not both")
-    n = len(records)
+    # a gray record repeats its one component: the layout reads the table ids of component 0 alone
+    cols = [(r.width, r.height, r.ncomp, r.hs, r.vs, r.restart, len(r.intervals)) + tuple(zip(*(c[3:] for c in (r.components * 3)[:3]))) + r.scan for r in records]
+    lay = _baseline_layout(np.array(cols, _COLS), out_offsets, out_bytes)
     plan, blob = JpegPlan() if resume is None else JpegResumePlan(), _Blob()
-    plan.n_waves = sum(len(r.intervals) for r in records)
-    hdr, desc = np.zeros(1, _HDR), np.zeros(n, _DESC)
-    blob.room(_HDR.itemsize)
-    desc_off, wave_off = blob.room(desc.nbytes), blob.room(8 * plan.n_waves)
-    hdr["n_images"], hdr["n_waves"], hdr["desc_off"], hdr["wave_off"] = n, plan.n_waves, desc_off, wave_off
-    for i, r in enumerate(records):
-        d, placed = desc[i], {}
-        d["restart"], d["n_intervals"] = r.restart, len(r.intervals)
-
-        def huffman(c, comp):
-            for field, key in (("dc_off", (0, comp[4])), ("ac_off", (1, comp[5]))):
-                if key not in placed:
-                    placed[key] = blob.place(r.huffman[key])
-                d[field][c] = placed[key]
-
-        plan.add_image(d, r, blob, None if out_offsets is None else out_offsets[i], huffman)
-        d["interval_off"] = blob.place(np.ascontiguousarray(r.intervals, np.int32))
-        d["stream_off"], d["stream_len"] = blob.place(np.frombuffer(r.data, np.uint8, r.scan[1] - r.scan[0], r.scan[0])), r.scan[1] - r.scan[0]
+    plan.n_waves, plan.coef_blocks, plan.plane_bytes = lay.n_waves, lay.coef_blocks, lay.plane_bytes
+    plan.out_offsets, plan.sizes = lay.desc["out_off"].tolist(), [(r.height, r.width) for r in records]
+    blob.put(blob.room(lay.nbytes), lay.head)
+    for r, qt, dc, ac, interval_off, stream_off in zip(records, *(lay.place[f].tolist() for f in ("qt_off", "dc_off", "ac_off", "interval_off", "stream_off"))):
+        for c, (_, _, _, tq, td, ta) in enumerate(r.components):
+            for off, table in ((qt[c], r.qtables[tq]), (dc[c], r.huffman[0, td]), (ac[c], r.huffman[1, ta])):
+                if off:   # 0: an earlier component has placed it
+                    blob.put(off, table)
+        blob.put(interval_off, np.ascontiguousarray(r.intervals, np.int32))
+        blob.put(stream_off, np.frombuffer(r.data, np.uint8, r.scan[1] - r.scan[0], r.scan[0]))
     plan.sub_bytes = plan.min_sync_bytes = plan.jobs_off = plan.n_jobs = plan.scratch_bytes = 0
     plan.jobs = []
     if sync is not None:
@@ -646,9 +706,7 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, syn
         segs = _segment_table(np.concatenate([r.intervals[:, 0] for r in records]),
                               np.concatenate([_interval_units(r.mcus_x * r.mcus_y, r.restart, len(r.intervals)) for r in records]), np.concatenate(points))
         plan.segs_off, plan.n_segs = blob.place(segs), len(segs)
-    for off, table in ((0, hdr), (desc_off, desc), (wave_off, _wave_list(range(n), [len(r.intervals) for r in records]))):
-        blob.put(off, table)
-    return plan.finish(blob, reserve, out_bytes)
+    return plan.finish(blob, reserve, lay.out_bytes)
 
 
 class JpegProgPlan(_Plan):
@@ -820,8 +878,6 @@ def build_resume_index(sources, every=RESUME_EVERY, progressive=False, workers=0
 
 # ------------------------------------------------------------------------------------------------------------------ the device front end
 _FFILE = np.dtype(_lib.JpegFrontFile)
-_FINFO = np.dtype(_lib.JpegFrontInfo)
-_FPLACE = np.dtype(_lib.JpegFrontPlace)
 FRONT_OK, FRONT_REFUSED = 0, 1
 # Defer codes of the device walker (csrc/jpeg_front.h) on files ``parse_jpeg`` may still accept: bounds of the kernel,
 # not properties of the format.  Every other deferred file is one ``parse_jpeg`` refuses.
@@ -851,65 +907,15 @@ def front_scan_host(datas):
     return info
 
 
-class FrontLayout:
-    """Where the accepted files of a scan go in the blob of ``hawq_jpeg_decode_batch``: exactly where ``plan_jpeg_batch`` puts the
-    records of the same files.  ``head``: header | descriptors | wave list as bytes, ``place``: the ``hawq_jpeg_front_place`` table of
-    the fill, ``desc``: the descriptors, ``nbytes``: the blob's size without a job table, ``n_waves`` / ``coef_blocks`` /
-    ``plane_bytes`` / ``out_bytes`` as in ``JpegPlan``."""
-    __slots__ = ("head", "place", "desc", "nbytes", "n_waves", "coef_blocks", "plane_bytes", "out_bytes")
-
-
 def front_layout(info, files, out_offsets, out_bytes) -> FrontLayout:
-    """``info``: the records of a scan; ``files``: indices of accepted ones, ascending; ``out_offsets`` / ``out_bytes``: where each image
-    goes in the output.  numpy over the batch, no loop over files."""
+    """``_baseline_layout`` of the accepted files of a scan, for ``hawq_jpeg_front_fill`` to fill.  ``info``: the records of the scan;
+    ``files``: indices of accepted ones, ascending; ``out_offsets`` / ``out_bytes``: where each image goes in the output."""
     files = np.asarray(files, np.int64)
-    o, n = info[files], len(files)
-    if n == 0 or (o["defer"] != FRONT_OK).any():
+    o = info[files]
+    if len(files) == 0 or (o["defer"] != FRONT_OK).any():
         raise ValueError("front_layout wants accepted files")
-    lay = FrontLayout()
-    colour = o["ncomp"] == 3
-    desc, place = np.zeros(n, _DESC), np.zeros(n, _FPLACE)
-    for f in ("width", "height", "ncomp", "hs", "vs", "restart", "n_intervals"):
-        desc[f] = o[f]
-    desc["mcus_x"], desc["mcus_y"] = -(-o["width"] // (8 * o["hs"])), -(-o["height"] // (8 * o["vs"]))
-    blocks = desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * np.where(colour, o["hs"] * o["vs"] + 2, 1)
-    desc["coef_block0"] = np.cumsum(blocks) - blocks
-    desc["plane_off"] = desc["coef_block0"] * 64
-    desc["out_off"] = out_offsets
-    desc["stream_len"] = o["scan_end"] - o["scan_first"]
-    lay.n_waves = int(o["n_intervals"].sum())
-    lay.coef_blocks, lay.plane_bytes, lay.out_bytes = int(blocks.sum()), int(blocks.sum()) * 64, int(out_bytes)
-    # per file its parts in the planner's order: per component the quantisation, DC and AC table it is the first to use, then intervals
-    # and stream; a component that shares a table takes the offset of the first one that has it
-    sizes, new = np.zeros((n, 11), np.int64), {}
-    for k, (ids, nbytes) in enumerate((("tq", 128), ("td", HUFF_BYTES), ("ta", HUFF_BYTES))):
-        t = o[ids]
-        new[ids] = np.stack((np.ones(n, bool), colour & (t[:, 1] != t[:, 0]), colour & (t[:, 2] != t[:, 0]) & (t[:, 2] != t[:, 1])), 1)
-        sizes[:, k:9:3] = new[ids] * _align16(nbytes)
-    sizes[:, 9], sizes[:, 10] = (8 * o["n_intervals"].astype(np.int64) + 15) & ~15, (desc["stream_len"].astype(np.int64) + 15) & ~15
-    head = _align16(_HDR.itemsize)
-    desc_off, wave_off = head, head + _align16(desc.nbytes)
-    head = wave_off + _align16(8 * lay.n_waves)
-    ends = head + np.cumsum(sizes.reshape(-1)).reshape(n, 11)
-    offs = ends - sizes
-    lay.nbytes = int(ends[-1, -1])
-    if lay.nbytes >= 1 << 31:
-        raise ValueError("batch too large for one blob (2 GiB of compressed data)")
-    for k, (ids, field) in enumerate((("tq", "qt_off"), ("td", "dc_off"), ("ta", "ac_off"))):
-        own, t = offs[:, k:9:3], o[ids]
-        place[field] = np.where(new[ids], own, 0)
-        desc[field][:, 0] = own[:, 0]
-        desc[field][:, 1] = np.where(new[ids][:, 1], own[:, 1], own[:, 0]) * colour
-        desc[field][:, 2] = np.where(new[ids][:, 2], own[:, 2], np.where(t[:, 2] == t[:, 0], own[:, 0], desc[field][:, 1])) * colour
-    place["file"], place["interval_off"], place["stream_off"] = files, offs[:, 9], offs[:, 10]
-    desc["interval_off"], desc["stream_off"] = offs[:, 9], offs[:, 10]
-    hdr = np.zeros(1, _HDR)
-    hdr["n_images"], hdr["n_waves"], hdr["desc_off"], hdr["wave_off"] = n, lay.n_waves, desc_off, wave_off
-    lay.head = np.zeros(head, np.uint8)
-    for off, table in ((0, hdr), (desc_off, desc), (wave_off, _wave_list(np.arange(n), o["n_intervals"]))):
-        raw = table.view(np.uint8).reshape(-1)
-        lay.head[off:off + raw.size] = raw
-    lay.place, lay.desc = place, desc
+    lay = _baseline_layout(o, out_offsets, out_bytes)
+    lay.place["file"] = files
     return lay
 
 
@@ -922,20 +928,14 @@ class _Staged:
 def _front_scan(datas, dev):
     """Pack the raw files into the pinned staging buffer of their kind, upload them in one copy with their table, run
     ``hawq_jpeg_front_scan`` and read the info records back (one synchronisation) -> (info, what ``_front_launch`` needs)."""
-    from .image import _STAGING, _Staging
     s = _Staged()
     with torch.cuda.device(dev):
-        st = _STAGING.setdefault((dev.index, "jpeg_files"), _Staging())
-        held, room = {}, _align16(len(datas) * _FFILE.itemsize)
-
-        def reserve(nbytes):
-            held["host"], held["dev"] = st.reserve(room + nbytes, dev)
-            return held["host"].numpy()[room:]
-
-        s.table, _, s.total = pack_files(datas, reserve)
-        held["host"].numpy()[:s.table.nbytes] = s.table.view(np.uint8)
+        st = _staging(dev, "jpeg_files")
+        room = _align16(len(datas) * _FFILE.itemsize)   # the table in front of the files
+        s.table, _, s.total = pack_files(datas, lambda nbytes: st.reserve(room + nbytes, dev)[0].numpy()[room:])
+        st.host.numpy()[:s.table.nbytes] = s.table.view(np.uint8)
         st.upload(room + s.total)
-        s.table_dev, s.files = held["dev"][:room], held["dev"][room:room + s.total]
+        s.table_dev, s.files = st.dev[:room], st.dev[room:room + s.total]
         s.info_dev = torch.empty(len(datas) * _FINFO.itemsize, dtype=torch.uint8, device=dev)
         _lib.call("hawq_jpeg_front_scan", s.files.data_ptr(), s.total, s.table_dev.data_ptr(), s.table.ctypes.data, len(datas), s.info_dev.data_ptr(),
                   torch.cuda.current_stream(dev).cuda_stream)
@@ -949,13 +949,11 @@ def _front_launch(staged, info, files, out_offsets, out, dev, events=None, sync=
     the host blob to ``hawq_jpeg_decode_batch`` - or ``_sync``, with the job table computed from the intervals just read back and
     uploaded alone - so the library's checker passes the blob before any decode kernel reads it.  Returns the device status as
     ``_launch`` does."""
-    from .image import _STAGING, _Staging
     lay = front_layout(info, files, out_offsets, out.numel())
     n = len(files)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        st_blob = _STAGING.setdefault((dev.index, "jpeg_front"), _Staging())
-        st_tab = _STAGING.setdefault((dev.index, "jpeg_front_tables"), _Staging())
+        st_blob, st_tab = _staging(dev, "jpeg_front"), _staging(dev, "jpeg_front_tables")
         room = lay.nbytes + (_JOB.itemsize * lay.n_waves if sync is not None else 0)   # at most one job per interval
         host_blob, blob = st_blob.reserve(room, dev)
         place_bytes = lay.place.nbytes
@@ -969,7 +967,7 @@ def _front_launch(staged, info, files, out_offsets, out, dev, events=None, sync=
         host_blob[:lay.nbytes].copy_(blob[:lay.nbytes], non_blocking=True)
         stream.synchronize()
         host = host_blob.numpy()
-        nbytes, more, entry = lay.nbytes, (), "hawq_jpeg_decode_batch"
+        nbytes, job_table = lay.nbytes, None
         if sync is not None:
             sub_bytes, min_sync_bytes = _check_sync(sync)
             lengths = [np.diff(host[o:o + 8 * k].view(np.int32).reshape(-1, 2), axis=1).reshape(-1)
@@ -980,19 +978,37 @@ def _front_launch(staged, info, files, out_offsets, out, dev, events=None, sync=
                 blob[nbytes:nbytes + jobs.nbytes].copy_(host_blob[nbytes:nbytes + jobs.nbytes], non_blocking=True)
                 st_blob.event = torch.cuda.Event()
                 st_blob.event.record()
-            scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=dev)
-            more, entry = (sub_bytes, min_sync_bytes, nbytes, len(jobs), scratch.data_ptr(), scratch_bytes), "hawq_jpeg_decode_batch_sync"
+            job_table = (sub_bytes, min_sync_bytes, nbytes, len(jobs), scratch_bytes)
             nbytes += jobs.nbytes
-        coef = torch.empty(lay.coef_blocks * 64, dtype=torch.int16, device=dev)
-        planes = torch.empty(lay.plane_bytes, dtype=torch.uint8, device=dev)
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-        ev = (C.c_void_p * 4)(*events) if events is not None else None
-        _lib.call(entry, blob.data_ptr(), host.ctypes.data, nbytes, coef.data_ptr(), lay.coef_blocks, planes.data_ptr(), lay.plane_bytes, out.data_ptr(), out.numel(),
-                  status.data_ptr(), *more, ev, stream.cuda_stream)
-        return status
+        return _decode("hawq_jpeg_decode_batch", blob, host.ctypes.data, nbytes, lay.coef_blocks, lay.plane_bytes, n, out, events, stream, sync=job_table)[0]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device call
+def _staging(dev, key):
+    """The pinned ``_Staging`` buffer of image.py for the kind ``key`` on ``dev``: one per kind, as the blobs of a batch are in flight at once."""
+    from .image import _STAGING, _Staging
+    return _STAGING.setdefault((dev.index, key), _Staging())
+
+
+def _decode(entry, blob, host_ptr, nbytes, coef_blocks, plane_bytes, n, out, events, stream, more=(), sync=None):
+    """The tail of ``_launch`` and ``_front_launch``: allocate the coefficient slab, the planes and the status of ``n`` images and run the
+    decode entry point ``entry`` on the device blob ``blob``, whose host copy (``nbytes`` bytes at ``host_ptr``) the library checks first.
+    ``more``: the arguments of ``entry`` between the status and the events.  ``sync``: (sub_bytes, min_sync_bytes, jobs_off, n_jobs,
+    scratch_bytes) of a blob with a job table: ``entry`` + ``_sync`` and its scratch.  -> (status, scratch or None) on the device."""
+    dev, scratch = out.device, None
+    if sync is not None:
+        *table, scratch_bytes = sync
+        scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=dev)
+        entry, more = entry + "_sync", (*table, scratch.data_ptr(), scratch_bytes)
+    coef = torch.empty(coef_blocks * 64, dtype=torch.int16, device=dev)
+    planes = torch.empty(plane_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    ev = (C.c_void_p * 4)(*events) if events is not None else None
+    _lib.call(entry, blob.data_ptr(), host_ptr, nbytes, coef.data_ptr(), coef_blocks, planes.data_ptr(), plane_bytes, out.data_ptr(), out.numel(), status.data_ptr(),
+              *more, ev, stream.cuda_stream)
+    return status, scratch
+
+
 def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None, resume=None):
     """The device call of ``decode_jpeg_batch`` for records of one kind: plan into the pinned staging buffer of that kind, check, upload
     in one copy, run the three stages on the current stream, writing into the uint8 device tensor ``out`` at ``out_offsets``.  Returns
@@ -1001,42 +1017,26 @@ def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None, r
     (sub_bytes, min_sync_bytes) ``hawq_jpeg_decode_batch_sync``; a dict ``info`` then receives ``jobs`` (the plan's) and ``rounds`` /
     ``decodes`` (what the kernel counted per job; a synchronising read of the scratch).  ``resume``: per record its resume points:
     ``hawq_jpeg_decode_batch_resume`` / ``_prog_resume``, one wave per segment."""
-    from .image import _STAGING, _Staging
     prog = isinstance(records[0], JpegProgRecord)
     if prog and sync is not None:
         raise ValueError("entropy='sync' does not take progressive records")
-    key, entry = ("jpeg_prog", "hawq_jpeg_decode_batch_prog") if prog else ("jpeg", "hawq_jpeg_decode_batch" if sync is None else "hawq_jpeg_decode_batch_sync")
+    key, entry = ("jpeg_prog", "hawq_jpeg_decode_batch_prog") if prog else ("jpeg", "hawq_jpeg_decode_batch")   # with sync: ``_decode`` picks ``_sync``
     if resume is not None:
-        key, entry = key + "_resume", ("hawq_jpeg_decode_batch_prog" if prog else "hawq_jpeg_decode_batch") + "_resume"
-    lib = _lib.load()
+        key, entry = key + "_resume", entry + "_resume"
     with torch.cuda.device(dev):
-        st = _STAGING.setdefault((dev.index, key), _Staging())   # one per kind: both blobs of a batch are in flight at once
-        held = {}
-
-        def reserve(nbytes):
-            held["host"], held["dev"] = st.reserve(nbytes, dev)
-            return held["host"].numpy()
-
+        st = _staging(dev, key)
+        reserve = lambda nbytes: st.reserve(nbytes, dev)[0].numpy()   # the plan's blob is ``st.host``, its upload ``st.dev``
         if prog:
             plan = plan_jpeg_prog_batch(records, out_offsets, out.numel(), reserve, resume)
         else:
             plan = plan_jpeg_batch(records, out_offsets, out.numel(), reserve, sync, resume)
         # on the host blob, before anything is uploaded or launched
         if not plan.ok() or (sync is not None and not plan.sync_ok()) or (resume is not None and not plan.resume_ok()):
-            raise RuntimeError("libhawq_mi355: " + lib.hawq_last_error().decode())
+            raise RuntimeError("libhawq_mi355: " + _lib.load().hawq_last_error().decode())
         st.upload(plan.nbytes)
-        coef = torch.empty(plan.coef_blocks * 64, dtype=torch.int16, device=dev)
-        planes = torch.empty(plan.plane_bytes, dtype=torch.uint8, device=dev)
-        status = torch.empty(len(records), dtype=torch.int32, device=dev)
-        more = ()
-        if sync is not None:
-            scratch = torch.empty(max(plan.scratch_bytes, 16), dtype=torch.uint8, device=dev)
-            more = (plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off, plan.n_jobs, scratch.data_ptr(), plan.scratch_bytes)
-        if resume is not None:
-            more = (plan.segs_off, plan.n_segs)
-        ev = (C.c_void_p * 4)(*events) if events is not None else None
-        _lib.call(entry, held["dev"].data_ptr(), plan.blob.ctypes.data, plan.nbytes, coef.data_ptr(), plan.coef_blocks, planes.data_ptr(), plan.plane_bytes,
-                  out.data_ptr(), out.numel(), status.data_ptr(), *more, ev, torch.cuda.current_stream(dev).cuda_stream)
+        status, scratch = _decode(entry, st.dev, plan.blob.ctypes.data, plan.nbytes, plan.coef_blocks, plan.plane_bytes, len(records), out, events,
+                                  torch.cuda.current_stream(dev), more=() if resume is None else (plan.segs_off, plan.n_segs),
+                                  sync=None if sync is None else (plan.sub_bytes, plan.min_sync_bytes, plan.jobs_off, plan.n_jobs, plan.scratch_bytes))
         if sync is not None and info is not None:
             info["jobs"] = list(plan.jobs)
             host = scratch.cpu().numpy()

@@ -171,7 +171,7 @@ def _plan_pin(plan):
 
 def planner_pins():
     """{label: {"nbytes", "blob": SHA-256 of blob[:nbytes], "fields": SHA-256 of the plan's other attributes}}"""
-    from hawq_amd.jpeg import plan_jpeg_batch, plan_jpeg_prog_batch
+    from hawq_amd.jpeg import plan_jpeg_batch, plan_jpeg_prog_batch, record_resume_points
     base, sync, prog = _records()
     pins = {"base/all": _plan_pin(plan_jpeg_batch(list(base.values())))}
     for name in ("noise_13x17_420", "noise_40x24_rst4", "smooth_31x33_gray"):
@@ -186,6 +186,9 @@ def planner_pins():
     some = [base[n] for n in ("noise_31x33_422", "noise_40x24_rst4", "smooth_31x33_gray", "noise_16x16_444")]
     pins["base/placed"] = _plan_pin(plan_jpeg_batch(some, [12288, 32, 8192, 4112], 20000))
     pins["sync32_64/placed"] = _plan_pin(plan_jpeg_batch(some, [12288, 32, 8192, 4112], 20000, sync=(32, 64)))
+    # the segment table behind the streams, from resume points recorded every 16 stream bytes
+    pins["resume16/all"] = _plan_pin(plan_jpeg_batch(list(base.values()), resume=[record_resume_points(r, 16) for r in base.values()]))
+    pins["resume16/placed"] = _plan_pin(plan_jpeg_batch(some, [12288, 32, 8192, 4112], 20000, resume=[record_resume_points(r, 16) for r in some]))
     some = [prog[n] for n in ("noise_40x24_420_rst", "noise_7x9_gray", "tables_13x17_422")]
     pins["prog/placed"] = _plan_pin(plan_jpeg_prog_batch(some, [8192, 48, 4096], 16384))
     return pins
