@@ -149,7 +149,7 @@ class JpegDesc(C.Structure):
     """struct hawq_jpeg_desc (include/hawq_mi355.h): one image of a hawq_jpeg_decode_batch call."""
     _fields_ = ([(n, i32) for n in ("width", "height", "ncomp", "hs", "vs", "mcus_x", "mcus_y", "restart", "n_intervals")]
                 + [(n, i32 * 3) for n in ("qt_off", "dc_off", "ac_off")]
-                + [(n, i32) for n in ("stream_off", "stream_len", "interval_off", "reserved")]
+                + [(n, i32) for n in ("stream_off", "stream_len", "interval_off", "scale")]
                 + [(n, i64) for n in ("coef_block0", "plane_off", "out_off")])
 
 

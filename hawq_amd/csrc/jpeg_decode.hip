@@ -6,6 +6,9 @@
 //               Lane 0 alone stores coefficients, into the pre-zeroed slab, and the status.
 //   2 idct      eight lanes per 8x8 block: dequantise + column pass into LDS, row pass + range limit -> sample planes (pitch = padded width).
 //   3 colour    one thread per output pixel: fancy upsampling of the chroma planes, YCbCr -> RGB.
+//   2, 3 (scaled) images with desc.scale = 2, 4, 8 take jpeg_idct_scaled_kernel / jpeg_colour_scaled_kernel instead: the
+//               n x n inverse DCTs of the library's DCT-domain scaling into smaller planes, and one thread per pixel of the reduced image.
+//               Launched only when the batch has such an image; the two kernels above return at once for it.
 //   1 (sync)    hawq_jpeg_decode_batch_sync: intervals of at least min_sync_bytes go to jpeg_sync_kernel instead - one workgroup per interval,
 //               one lane per sub_bytes of it, speculative starts synchronised round after round (jpeg_sync.h); the same coefficients.
 //   1 (resume)  hawq_jpeg_decode_batch_resume: one wave per SEGMENT of a restart interval - the serial kernel started at a recorded
@@ -237,6 +240,7 @@ __global__ __launch_bounds__(IDCT_THREADS) void jpeg_idct_kernel(const uint8_t *
     __shared__ int32_t ws[IDCT_THREADS / 8][64];
     const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
     const hawq_jpeg_desc &d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[blockIdx.y];   // read in place: qt_off is indexed by the component
+    if (d.scale > 1) return;   // jpeg_idct_scaled_kernel's (uniform: before the barrier)
     const int slot = threadIdx.x >> 3, lane8 = threadIdx.x & 7;
     int64_t b = (int64_t)blockIdx.x * (IDCT_THREADS / 8) + slot;   // block of the image, component after component
     int64_t comp0 = 0, bw = 0;
@@ -257,10 +261,39 @@ __global__ __launch_bounds__(IDCT_THREADS) void jpeg_idct_kernel(const uint8_t *
     }
 }
 
+// The same for an image with scale 2, 4 or 8: the n x n inverse DCT, n = jpeg_comp_n of the block's component, into planes of pitch
+// block columns x n.  Lane x runs column x when the row pass reads it, lane y < n runs row y.
+__global__ __launch_bounds__(IDCT_THREADS) void jpeg_idct_scaled_kernel(const uint8_t *__restrict__ blob, const int16_t *__restrict__ coef, uint8_t *__restrict__ planes) {
+    __shared__ int32_t ws[IDCT_THREADS / 8][64];
+    const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
+    const hawq_jpeg_desc &d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[blockIdx.y];
+    if (d.scale <= 1) return;   // jpeg_idct_kernel's (uniform: before the barrier)
+    const int slot = threadIdx.x >> 3, lane8 = threadIdx.x & 7;
+    int64_t b = (int64_t)blockIdx.x * (IDCT_THREADS / 8) + slot;
+    int64_t comp0 = 0, plane0 = 0, bw = 0;   // blocks and plane bytes of the components before the block's
+    int comp = -1, n = 0;
+    for (int c = 0; c < d.ncomp && comp < 0; ++c) {
+        bw = (int64_t)d.mcus_x * jpeg_comp_h(d, c);
+        n = jpeg_comp_n(d, c);
+        const int64_t blocks = bw * d.mcus_y * jpeg_comp_v(d, c);
+        if (b < blocks)
+            comp = c;
+        else
+            b -= blocks, comp0 += blocks, plane0 += blocks * n * n;
+    }
+    if (comp >= 0) jpeg_idct_column_n(coef + (d.coef_block0 + comp0 + b) * 64, (const uint16_t *)(blob + d.qt_off[comp]), n, lane8, ws[slot]);
+    __syncthreads();
+    if (comp >= 0 && lane8 < n) {
+        const int64_t by = b / bw, bx = b - by * bw, pitch = bw * n;
+        jpeg_idct_row_n(ws[slot], n, lane8, planes + d.plane_off + plane0 + (by * n + lane8) * pitch + bx * n);
+    }
+}
+
 // ---- stage 3 ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void jpeg_colour_kernel(const uint8_t *__restrict__ blob, const uint8_t *__restrict__ planes, uint8_t *__restrict__ out) {
     const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
     const hawq_jpeg_desc d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[blockIdx.y];
+    if (d.scale > 1) return;   // jpeg_colour_scaled_kernel's
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= (int64_t)d.width * d.height) return;
     const int32_t y = (int32_t)(p / d.width), x = (int32_t)(p - (int64_t)y * d.width);
@@ -269,23 +302,53 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const uint8_t *__restr
     uint8_t *o = out + d.out_off + p * 3;
     o[0] = rgb[0], o[1] = rgb[1], o[2] = rgb[2];
 }
+
+__global__ __launch_bounds__(256) void jpeg_colour_scaled_kernel(const uint8_t *__restrict__ blob, const uint8_t *__restrict__ planes, uint8_t *__restrict__ out) {
+    const hawq_jpeg_batch_hdr hd = *(const hawq_jpeg_batch_hdr *)blob;
+    const hawq_jpeg_desc d = ((const hawq_jpeg_desc *)(blob + hd.desc_off))[blockIdx.y];
+    if (d.scale <= 1) return;   // jpeg_colour_kernel's
+    const int32_t ow = jpeg_out_width(d);
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (int64_t)ow * jpeg_out_height(d)) return;
+    const int32_t y = (int32_t)(p / ow), x = (int32_t)(p - (int64_t)y * ow);
+    uint8_t rgb[3];
+    jpeg_pixel_scaled(d, planes + d.plane_off, x, y, rgb);
+    uint8_t *o = out + d.out_off + p * 3;
+    o[0] = rgb[0], o[1] = rgb[1], o[2] = rgb[2];
+}
 }  // namespace
 
 int hawq_jpeg::launch_pixel_stages(const void *blob, const hawq_jpeg_desc *host_desc, int32_t n_images, const int16_t *coef, uint8_t *planes, uint8_t *out,
                                    void *const *events, hipStream_t s) {
-    int64_t max_blocks = 0, max_pixels = 0;
+    // [0]: the full-size images, which the two kernels of old decode; [1]: the scaled ones.  A kind without an image launches nothing.
+    int64_t max_blocks[2] = {0, 0}, max_pixels[2] = {0, 0};
     for (int32_t i = 0; i < n_images; ++i) {
         const Geometry g = geometry(host_desc[i]);
-        max_blocks = g.blocks > max_blocks ? g.blocks : max_blocks;
-        max_pixels = g.out_bytes / 3 > max_pixels ? g.out_bytes / 3 : max_pixels;
+        const int k = host_desc[i].scale > 1;
+        max_blocks[k] = g.blocks > max_blocks[k] ? g.blocks : max_blocks[k];
+        max_pixels[k] = g.out_bytes / 3 > max_pixels[k] ? g.out_bytes / 3 : max_pixels[k];
     }
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_THREADS / 8 - 1) / (IDCT_THREADS / 8)), (unsigned)n_images), dim3(IDCT_THREADS), 0, s,
-                       (const uint8_t *)blob, coef, planes);
-    HAWQ_CHECK_HIP(hipGetLastError());
+    if (max_blocks[0]) {
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks[0] + IDCT_THREADS / 8 - 1) / (IDCT_THREADS / 8)), (unsigned)n_images), dim3(IDCT_THREADS), 0, s,
+                           (const uint8_t *)blob, coef, planes);
+        HAWQ_CHECK_HIP(hipGetLastError());
+    }
+    if (max_blocks[1]) {
+        hipLaunchKernelGGL(jpeg_idct_scaled_kernel, dim3((unsigned)((max_blocks[1] + IDCT_THREADS / 8 - 1) / (IDCT_THREADS / 8)), (unsigned)n_images), dim3(IDCT_THREADS),
+                           0, s, (const uint8_t *)blob, coef, planes);
+        HAWQ_CHECK_HIP(hipGetLastError());
+    }
     if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[2], s));
-    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n_images), dim3(256), 0, s, (const uint8_t *)blob,
-                       (const uint8_t *)planes, out);
-    HAWQ_CHECK_HIP(hipGetLastError());
+    if (max_pixels[0]) {
+        hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels[0] + 255) / 256), (unsigned)n_images), dim3(256), 0, s, (const uint8_t *)blob,
+                           (const uint8_t *)planes, out);
+        HAWQ_CHECK_HIP(hipGetLastError());
+    }
+    if (max_pixels[1]) {
+        hipLaunchKernelGGL(jpeg_colour_scaled_kernel, dim3((unsigned)((max_pixels[1] + 255) / 256), (unsigned)n_images), dim3(256), 0, s, (const uint8_t *)blob,
+                           (const uint8_t *)planes, out);
+        HAWQ_CHECK_HIP(hipGetLastError());
+    }
     if (events) HAWQ_CHECK_HIP(hipEventRecord((hipEvent_t)events[3], s));
     return 0;
 }

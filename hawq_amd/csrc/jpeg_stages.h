@@ -21,8 +21,9 @@ inline Geometry geometry(const hawq_jpeg_desc &d) {
     Geometry g;
     g.mcus = d.mcus_x * d.mcus_y;
     g.blocks = (int64_t)g.mcus * (d.ncomp == 1 ? 1 : d.hs * d.vs + 2);
-    g.plane_bytes = g.blocks * 64;
-    g.out_bytes = (int64_t)d.width * d.height * 3;
+    g.plane_bytes = 0;   // n x n samples per block, n = 8 at full size (jpeg_comp_n)
+    for (int c = 0; c < d.ncomp; ++c) g.plane_bytes += (int64_t)g.mcus * jpeg_comp_h(d, c) * jpeg_comp_v(d, c) * jpeg_comp_n(d, c) * jpeg_comp_n(d, c);
+    g.out_bytes = (int64_t)jpeg_out_width(d) * jpeg_out_height(d) * 3;
     return g;
 }
 
@@ -35,6 +36,7 @@ inline const char *frame_refusal(const hawq_jpeg_desc &d) {
     const bool colour = d.ncomp == 3 && ((d.hs == 1 && d.vs == 1) || (d.hs == 2 && d.vs == 1) || (d.hs == 2 && d.vs == 2));
     if (!gray && !colour) return "component count or sampling factors not supported";
     if (d.mcus_x != (d.width + 8 * d.hs - 1) / (8 * d.hs) || d.mcus_y != (d.height + 8 * d.vs - 1) / (8 * d.vs)) return "MCU counts do not follow from the size";
+    if (d.scale != 0 && d.scale != 1 && d.scale != 2 && d.scale != 4 && d.scale != 8) return "scale is none of 0, 1, 2, 4, 8";
     return nullptr;
 }
 

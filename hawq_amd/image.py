@@ -341,9 +341,14 @@ def preprocess_batch_fused(images, resize: int = 256, crop: int = 224, out=None,
 IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
 
 
-def decode_image(source) -> torch.Tensor:
+def decode_image(source, draft=None) -> torch.Tensor:
     """File path, bytes or file object -> uint8 HWC RGB tensor (host), decoded as torchvision's ``pil_loader`` does
-    (``Image.open(f).convert('RGB')``).  Needs Pillow - the decoder is not part of the integer hot path."""
+    (``Image.open(f).convert('RGB')``).  ``draft``: None, or a (width, height) pair: ``im.draft("RGB", draft)`` first - a JPEG is then
+    decoded at the largest of 1/8, 1/4, 1/2 of its size that is still at least that large (``jpeg.draft_scale``), other formats as
+    without it.  Needs Pillow - the decoder is not part of the integer hot path."""
+    if draft is not None:
+        from .jpeg import check_draft
+        draft = check_draft(draft)
     try:
         from PIL import Image
     except ImportError as e:   # pragma: no cover - the build container has Pillow
@@ -352,6 +357,8 @@ def decode_image(source) -> torch.Tensor:
     if isinstance(source, (bytes, bytearray, memoryview)):
         source = io.BytesIO(bytes(source))
     with Image.open(source) as im:
+        if draft is not None:
+            im.draft("RGB", draft)
         arr = np.array(im.convert("RGB"))   # a copy: Pillow's buffer is read-only
     return torch.from_numpy(arr)
 
@@ -389,7 +396,7 @@ def decoded_batches(samples, batch_size: int, workers: int = 0, decode=decode_im
 
 
 def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int = 224, device="cuda", fused: bool = False, workers: int = 0,
-                  device_decode: bool = False, entropy: str = "serial", progressive: bool = False, resume=None, front_end: str = "host"):
+                  device_decode: bool = False, entropy: str = "serial", progressive: bool = False, resume=None, front_end: str = "host", draft: bool = False):
     """Iterate an ImageFolder tree as ``(uint8 [n, crop, crop, 3] on the MI355X, int64 targets)`` batches - the validation loader of
     quant_train.py:428-445 (shuffle off) with everything behind the decoder on the device; feed it to ``api.validate(uint8=True)``.
     The defaults are the ResNets' geometry; InceptionV3 wants ``resize=342, crop=299`` (``eval_geometry(arch)``).
@@ -401,7 +408,12 @@ def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int
     ``resume`` (needs ``device_decode``): a ``jpeg.ResumeIndex`` or the path of a saved one - the files it has an entry for are decoded
     from their recorded resume points, many waves per long restart interval; ``front_end`` (``"device"`` needs ``device_decode``): the
     MI355X walks the headers of the baseline files and writes their blob itself (``jpeg.decode_jpeg_batch``).  Same order, labels and bytes
-    either way."""
+    either way.  ``draft``: JPEGs are decoded at a reduced size where that still leaves at least ``resize`` pixels on both sides (Pillow's
+    draft mode with the request (resize, resize), so ``Resize(resize)`` never enlarges), on the device with ``device_decode`` and by Pillow
+    otherwise: what ``decode_image(f, draft=(resize, resize))`` + ``preprocess_batch_fused`` yield, which for a file of at least twice
+    the requested size is NOT what the loader yields without it."""
+    if draft not in (False, True):
+        raise ValueError(f"draft must be False or True, not {draft!r}")
     if front_end not in ("host", "device"):
         raise ValueError(f"front_end must be 'host' or 'device', not {front_end!r}")
     if front_end == "device" and not device_decode:
@@ -418,11 +430,13 @@ def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int
             more["resume"] = resume if isinstance(resume, jpeg.ResumeIndex) else jpeg.ResumeIndex.load(resume)
         if front_end != "host":
             more["front_end"] = front_end
+        if draft:
+            more["draft"] = (resize, resize)
         for datas, targets in decoded_batches(samples, batch_size, workers, decode=jpeg.read_source):
             imgs, _ = jpeg.decode_jpeg_batch(datas, device, entropy=entropy, **more)
             yield preprocess_batch_fused(imgs, resize, crop, device=device), torch.tensor(targets, dtype=torch.int64)
         return
-    for imgs, targets in decoded_batches(samples, batch_size, workers):
+    for imgs, targets in decoded_batches(samples, batch_size, workers, **({"decode": functools.partial(decode_image, draft=(resize, resize))} if draft else {})):
         if fused:
             batch = preprocess_batch_fused(imgs, resize, crop, device=device)
         else:

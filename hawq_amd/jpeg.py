@@ -20,6 +20,9 @@ Host side, pure Python / numpy, one of each:
 - one device front end (``_front_scan``, ``front_layout``, ``_front_launch``) beside the host one, opt-in: the raw files
   go up, the library walks the headers, checks the restart markers and writes the baseline blob on the device with the walker of
   csrc/jpeg_front.h; what it defers goes through ``parse_jpeg`` as ever.
+- one option for reduced sizes (``draft_scale``, ``check_draft``, ``_plane_bytes``): ``draft=(w, h)`` gives every file the
+  scale Pillow's draft mode gives it, the planners and the layout write it into the descriptor and size planes and output by it, and
+  stages 2 and 3 of every entry point above produce the reduced image with the library's 4x4 / 2x2 / 1x1 inverse DCTs.
 ``decode_jpeg_batch`` allocates the output, launches the progressive and the baseline files of a batch and hands every refused or failed
 image to the host decoder, with the reason.  ``image.folder_loader(device_decode=True)`` feeds the result to ``preprocess_batch_fused``
 in place.
@@ -442,6 +445,54 @@ def _align16(n: int) -> int:
     return (n + 15) & ~15
 
 
+def check_draft(draft):
+    """``draft`` of ``decode_jpeg_batch``: None, or the requested (width, height) as a pair of positive ints"""
+    if draft is None:
+        return None
+    try:
+        w, h = draft
+        w, h = int(w), int(h)
+    except (TypeError, ValueError):
+        raise ValueError(f"draft must be None or a (width, height) pair, not {draft!r}") from None
+    if w < 1 or h < 1:
+        raise ValueError(f"draft sizes must be positive, not {draft!r}")
+    return w, h
+
+
+def draft_scales(widths, heights, draft):
+    """``draft_scale`` over columns: int arrays of file sizes -> int32 array of scales (all 1 for ``draft`` None)"""
+    widths, heights = np.asarray(widths, np.int64), np.asarray(heights, np.int64)
+    if draft is None:
+        return np.ones(widths.shape, np.int32)
+    w, h = check_draft(draft)
+    k = np.minimum(widths // w, heights // h)
+    return np.where(k >= 8, 8, np.where(k >= 4, 4, np.where(k >= 2, 2, 1))).astype(np.int32)
+
+
+def draft_scale(width, height, draft) -> int:
+    """The scale Pillow's ``Image.draft("RGB", draft)`` picks for a ``width`` x ``height`` JPEG: the largest of 8, 4, 2, 1
+    that is at most min(width // draft[0], height // draft[1]), 1 when that is 0 or ``draft`` is None.  The decoded image then has
+    ``scaled_size`` = ceil(size / scale)."""
+    if draft is None:
+        return 1
+    w, h = check_draft(draft)
+    k = min(int(width) // w, int(height) // h)
+    return 8 if k >= 8 else 4 if k >= 4 else 2 if k >= 2 else 1
+
+
+def scaled_size(n, scale):
+    """ceil(n / scale): a side of the reduced image (ints or arrays)"""
+    return -(-n // scale)
+
+
+def _plane_bytes(blocks_luma, blocks_chroma, hs, vs, scale):
+    """Bytes of an image's sample planes: n x n samples per block, n = 8 // scale per side, twice that for the chroma of a 4:2:0 image
+    decoded at a reduced size (jpeg_comp_n of csrc/jpeg_pixel.h); ints or arrays."""
+    m = 8 // scale
+    nc = np.where((hs == 2) & (vs == 2) & (m < 8), 2 * m, m)
+    return blocks_luma * m * m + blocks_chroma * nc * nc
+
+
 def output_layout(sizes):
     """(height, width) per image -> (offsets, total bytes) of the RGB images one after the other, each at a 16-byte aligned offset"""
     offsets, total = [], 0
@@ -490,7 +541,7 @@ class _Blob:
 class _Plan:
     """What both planners return.  ``blob``: uint8 array (the first ``nbytes`` bytes count), ``coef_blocks`` / ``plane_bytes`` /
     ``out_bytes``: the sizes of the three device buffers the launch needs, ``out_offsets`` / ``sizes``: where each image lands in the
-    output and its (height, width)."""
+    output and its (height, width) as decoded: with ``draft`` the reduced ones (the scale itself is in the descriptor)."""
     __slots__ = ("blob", "nbytes", "coef_blocks", "plane_bytes", "out_bytes", "out_offsets", "sizes")
     checker = None   # the library's check of the blob
 
@@ -502,9 +553,9 @@ class _Plan:
         """The library's checker on the host blob (no GPU work); the reason of a refusal is in ``hawq_last_error``."""
         return bool(getattr(_lib.load(), self.checker)(self.blob.ctypes.data, self.nbytes, self.coef_blocks, self.plane_bytes, self.out_bytes))
 
-    def add_image(self, d, r, blob, out_off):
+    def add_image(self, d, r, blob, out_off, scale=None):
         """The geometry half of descriptor ``d`` for the progressive record ``r``, its quantisation tables into ``blob``, and its share of
-        the three buffers; ``out_off``: None = behind the image before."""
+        the three buffers; ``out_off``: None = behind the image before; ``scale``: None (the descriptor says 0: full size), or 1, 2, 4, 8."""
         d["width"], d["height"], d["ncomp"], d["hs"], d["vs"], d["mcus_x"], d["mcus_y"] = r.width, r.height, r.ncomp, r.hs, r.vs, r.mcus_x, r.mcus_y
         placed = {}
         for c, comp in enumerate(r.components):
@@ -512,11 +563,17 @@ class _Plan:
                 placed[comp[3]] = blob.place(r.qtables[comp[3]])
             d["qt_off"][c] = placed[comp[3]]
         d["coef_block0"], d["plane_off"] = self.coef_blocks, self.plane_bytes
-        self.coef_blocks, self.plane_bytes = self.coef_blocks + r.blocks, self.plane_bytes + r.blocks * 64
+        planes, height, width = r.blocks * 64, r.height, r.width
+        if scale is not None:
+            d["scale"] = scale
+            m, luma = 8 // scale, r.mcus_x * r.mcus_y * r.hs * r.vs
+            nc = 2 * m if (r.hs, r.vs) == (2, 2) and m < 8 else m   # ``_plane_bytes`` on one image
+            planes, height, width = luma * m * m + (r.blocks - luma) * nc * nc, scaled_size(r.height, scale), scaled_size(r.width, scale)
+        self.coef_blocks, self.plane_bytes = self.coef_blocks + r.blocks, self.plane_bytes + planes
         d["out_off"] = off = self.out_bytes if out_off is None else int(out_off)
         self.out_offsets.append(off)
-        self.sizes.append((r.height, r.width))
-        self.out_bytes = _align16(off + r.width * r.height * 3)
+        self.sizes.append((height, width))
+        self.out_bytes = _align16(off + width * height * 3)
 
     def finish(self, blob, reserve, out_bytes):
         self.blob, self.nbytes = blob.finish(reserve), blob.at
@@ -617,12 +674,13 @@ class FrontLayout:
     __slots__ = ("head", "place", "desc", "nbytes", "n_waves", "coef_blocks", "plane_bytes", "out_bytes")
 
 
-def _baseline_layout(o, out_offsets=None, out_bytes=None) -> FrontLayout:
+def _baseline_layout(o, out_offsets=None, out_bytes=None, scales=None) -> FrontLayout:
     """The one place that knows the blob of ``hawq_jpeg_decode_batch``: header | descriptors | wave list | per image, per component the
     quantisation, DC and AC table it is the first to use, then intervals, then stream - every part at a 16-byte aligned offset; a
     component that shares a table takes the offset of the first one that has it.  ``o``: the columns ``_COLS`` of the images;
     ``out_offsets`` / ``out_bytes``: where each image goes in an output buffer of that size (default: one after the other, 16-byte
-    aligned, and the aligned end of the last image).  numpy over the batch, no loop over images.  Two fillers write the bytes of the
+    aligned, and the aligned end of the last image).  ``scales``: the scale of every image (1, 2, 4, 8; None: the descriptors say 0, full
+    size): planes and output take the reduced sizes.  numpy over the batch, no loop over images.  Two fillers write the bytes of the
     parts at ``place``: ``plan_jpeg_batch`` on the host, ``hawq_jpeg_front_fill`` on the device."""
     n = len(o)
     lay = FrontLayout()
@@ -633,12 +691,17 @@ def _baseline_layout(o, out_offsets=None, out_bytes=None) -> FrontLayout:
     desc["mcus_x"], desc["mcus_y"] = -(-o["width"] // (8 * o["hs"])), -(-o["height"] // (8 * o["vs"]))
     blocks = desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * np.where(colour, o["hs"] * o["vs"] + 2, 1)
     desc["coef_block0"] = np.cumsum(blocks) - blocks
-    desc["plane_off"] = desc["coef_block0"] * 64
-    rgb = 3 * o["width"].astype(np.int64) * o["height"]
+    planes, rgb = blocks * 64, 3 * o["width"].astype(np.int64) * o["height"]
+    if scales is not None:
+        desc["scale"] = s = np.asarray(scales, np.int64)
+        luma = desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * o["hs"] * o["vs"]
+        planes = _plane_bytes(luma, blocks - luma, o["hs"], o["vs"], s)
+        rgb = 3 * scaled_size(o["width"].astype(np.int64), s) * scaled_size(o["height"].astype(np.int64), s)
+    desc["plane_off"] = np.cumsum(planes) - planes
     desc["out_off"] = np.cumsum((rgb + 15) & ~15) - ((rgb + 15) & ~15) if out_offsets is None else out_offsets
     desc["stream_len"] = o["scan_end"] - o["scan_first"]
     lay.n_waves = int(o["n_intervals"].sum())
-    lay.coef_blocks, lay.plane_bytes = int(blocks.sum()), int(blocks.sum()) * 64
+    lay.coef_blocks, lay.plane_bytes = int(blocks.sum()), int(planes.sum())
     lay.out_bytes = _align16(int(desc["out_off"][-1] + rgb[-1])) if out_bytes is None else int(out_bytes)
     # per image the aligned sizes of its parts in blob order: (quantisation, DC, AC) x 3 components, 0 unless the component is the first
     # to use that table (``first``: per component the first one with its table; a gray image has component 0 alone), intervals, stream
@@ -666,14 +729,16 @@ def _baseline_layout(o, out_offsets=None, out_bytes=None) -> FrontLayout:
     return lay
 
 
-def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, sync=None, resume=None) -> JpegPlan:
+def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, sync=None, resume=None, draft=None) -> JpegPlan:
     """Pack the records of ``parse_jpeg`` into one host blob laid out by ``_baseline_layout``: the adapter from records to its columns, and
     the host filler that copies table, interval and stream bytes to the offsets it gives.  ``out_offsets`` / ``out_bytes``: where each
     image goes in an output buffer of that size (default: one after the other, 16-byte aligned).  ``reserve(nbytes)`` returns the uint8 array to write
     into (at least nbytes, 16-byte aligned; e.g. a pinned staging buffer); a fresh array without it.  ``sync`` = (sub_bytes,
     min_sync_bytes): append the job table of ``hawq_jpeg_decode_batch_sync`` behind the streams - one job per interval of at least
     ``min_sync_bytes`` bytes, cut into sub-sequences of ``sub_bytes``, with its slice of the scratch.  ``resume``: per record its resume
-    points (``ResumeIndex.points``): append the segment table of ``hawq_jpeg_decode_batch_resume`` instead (a ``JpegResumePlan``)."""
+    points (``ResumeIndex.points``): append the segment table of ``hawq_jpeg_decode_batch_resume`` instead (a ``JpegResumePlan``).
+    ``draft``: None, or the (width, height) of Pillow's draft mode: every record gets its ``draft_scale``, and planes, output and
+    ``sizes`` take the reduced sizes; without it the blob is the one of a plan made before the option."""
     records = list(records)
     if not records:
         raise ValueError("empty batch")
@@ -681,10 +746,13 @@ def plan_jpeg_batch(records, out_offsets=None, out_bytes=None, reserve=None, syn
         raise ValueError("a batch is decoded with entropy='sync' or from resume points, not both")
     # a gray record repeats its one component: the layout reads the table ids of component 0 alone
     cols = [(r.width, r.height, r.ncomp, r.hs, r.vs, r.restart, len(r.intervals)) + tuple(zip(*(c[3:] for c in (r.components * 3)[:3]))) + r.scan for r in records]
-    lay = _baseline_layout(np.array(cols, _COLS), out_offsets, out_bytes)
+    scales = None if draft is None else draft_scales([r.width for r in records], [r.height for r in records], draft)
+    lay = _baseline_layout(np.array(cols, _COLS), out_offsets, out_bytes, scales)
     plan, blob = JpegPlan() if resume is None else JpegResumePlan(), _Blob()
     plan.n_waves, plan.coef_blocks, plan.plane_bytes = lay.n_waves, lay.coef_blocks, lay.plane_bytes
     plan.out_offsets, plan.sizes = lay.desc["out_off"].tolist(), [(r.height, r.width) for r in records]
+    if scales is not None:
+        plan.sizes = [(scaled_size(h, s), scaled_size(w, s)) for (h, w), s in zip(plan.sizes, scales.tolist())]
     blob.put(blob.room(lay.nbytes), lay.head)
     for r, qt, dc, ac, interval_off, stream_off in zip(records, *(lay.place[f].tolist() for f in ("qt_off", "dc_off", "ac_off", "interval_off", "stream_off"))):
         for c, (_, _, _, tq, td, ta) in enumerate(r.components):
@@ -726,11 +794,11 @@ class JpegProgResumePlan(JpegProgPlan):
         return bool(_lib.load().hawq_jpeg_resume_ok(self.blob.ctypes.data, self.nbytes, 1, self.segs_off, self.n_segs))
 
 
-def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None, resume=None) -> JpegProgPlan:
+def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None, resume=None, draft=None) -> JpegProgPlan:
     """Pack the ``JpegProgRecord``s of ``parse_jpeg(progressive=True)`` into the host blob of ``hawq_jpeg_decode_batch_prog``: batch header |
     progressive header | descriptors (entropy fields zero) | scan table | level list | wave lists, level after level | per image: the
     quantisation tables, then per scan its Huffman tables, intervals and stream - every part at a 16-byte aligned offset.  Computes the
-    level of every scan (``scan_levels``).  ``out_offsets`` / ``out_bytes`` / ``reserve`` / ``resume`` as in ``plan_jpeg_batch``: with
+    level of every scan (``scan_levels``).  ``out_offsets`` / ``out_bytes`` / ``reserve`` / ``resume`` / ``draft`` as in ``plan_jpeg_batch``: with
     ``resume`` the segment table of ``hawq_jpeg_decode_batch_prog_resume`` stands behind the streams (a ``JpegProgResumePlan``)."""
     records = list(records)
     if not records:
@@ -749,7 +817,7 @@ def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None
     phdr["n_scans"], phdr["n_levels"], phdr["scan_off"], phdr["level_off"] = plan.n_scans, plan.n_levels, plan.scan_off, plan.level_off
     rows = []   # the fields of hawq_jpeg_scan, in order
     for i, r in enumerate(records):
-        plan.add_image(desc[i], r, blob, None if out_offsets is None else out_offsets[i])
+        plan.add_image(desc[i], r, blob, None if out_offsets is None else out_offsets[i], None if draft is None else draft_scale(r.width, r.height, draft))
         tables = {}   # id of a table record -> offset: a table stays in force over several scans
 
         def table(t):
@@ -907,14 +975,15 @@ def front_scan_host(datas):
     return info
 
 
-def front_layout(info, files, out_offsets, out_bytes) -> FrontLayout:
+def front_layout(info, files, out_offsets, out_bytes, draft=None) -> FrontLayout:
     """``_baseline_layout`` of the accepted files of a scan, for ``hawq_jpeg_front_fill`` to fill.  ``info``: the records of the scan;
-    ``files``: indices of accepted ones, ascending; ``out_offsets`` / ``out_bytes``: where each image goes in the output."""
+    ``files``: indices of accepted ones, ascending; ``out_offsets`` / ``out_bytes``: where each image goes in the output; ``draft``: as in
+    ``plan_jpeg_batch``, the scales computed here on the host from the sizes the scan reports."""
     files = np.asarray(files, np.int64)
     o = info[files]
     if len(files) == 0 or (o["defer"] != FRONT_OK).any():
         raise ValueError("front_layout wants accepted files")
-    lay = _baseline_layout(o, out_offsets, out_bytes)
+    lay = _baseline_layout(o, out_offsets, out_bytes, None if draft is None else draft_scales(o["width"], o["height"], draft))
     lay.place["file"] = files
     return lay
 
@@ -943,13 +1012,13 @@ def _front_scan(datas, dev):
     return info, s
 
 
-def _front_launch(staged, info, files, out_offsets, out, dev, events=None, sync=None):
+def _front_launch(staged, info, files, out_offsets, out, dev, events=None, sync=None, draft=None):
     """The device call of ``decode_jpeg_batch(front_end="device")`` for the files the scan accepted: lay the blob out, have
     ``hawq_jpeg_front_fill`` write it from the staged files, read it back into pinned memory (the second synchronisation) and hand it as
     the host blob to ``hawq_jpeg_decode_batch`` - or ``_sync``, with the job table computed from the intervals just read back and
     uploaded alone - so the library's checker passes the blob before any decode kernel reads it.  Returns the device status as
     ``_launch`` does."""
-    lay = front_layout(info, files, out_offsets, out.numel())
+    lay = front_layout(info, files, out_offsets, out.numel(), draft)
     n = len(files)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
@@ -1009,14 +1078,14 @@ def _decode(entry, blob, host_ptr, nbytes, coef_blocks, plane_bytes, n, out, eve
     return status, scratch
 
 
-def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None, resume=None):
+def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None, resume=None, draft=None):
     """The device call of ``decode_jpeg_batch`` for records of one kind: plan into the pinned staging buffer of that kind, check, upload
     in one copy, run the three stages on the current stream, writing into the uint8 device tensor ``out`` at ``out_offsets``.  Returns
     the int32 status per record as a device tensor: reading it synchronises, so the caller does that when everything of the batch is
     enqueued.  ``JpegProgRecord``s: ``hawq_jpeg_decode_batch_prog``.  ``JpegRecord``s: ``hawq_jpeg_decode_batch``, or with ``sync`` =
     (sub_bytes, min_sync_bytes) ``hawq_jpeg_decode_batch_sync``; a dict ``info`` then receives ``jobs`` (the plan's) and ``rounds`` /
     ``decodes`` (what the kernel counted per job; a synchronising read of the scratch).  ``resume``: per record its resume points:
-    ``hawq_jpeg_decode_batch_resume`` / ``_prog_resume``, one wave per segment."""
+    ``hawq_jpeg_decode_batch_resume`` / ``_prog_resume``, one wave per segment.  ``draft``: to the planner."""
     prog = isinstance(records[0], JpegProgRecord)
     if prog and sync is not None:
         raise ValueError("entropy='sync' does not take progressive records")
@@ -1027,9 +1096,9 @@ def _launch(records, out_offsets, out, dev, events=None, sync=None, info=None, r
         st = _staging(dev, key)
         reserve = lambda nbytes: st.reserve(nbytes, dev)[0].numpy()   # the plan's blob is ``st.host``, its upload ``st.dev``
         if prog:
-            plan = plan_jpeg_prog_batch(records, out_offsets, out.numel(), reserve, resume)
+            plan = plan_jpeg_prog_batch(records, out_offsets, out.numel(), reserve, resume, draft)
         else:
-            plan = plan_jpeg_batch(records, out_offsets, out.numel(), reserve, sync, resume)
+            plan = plan_jpeg_batch(records, out_offsets, out.numel(), reserve, sync, resume, draft)
         # on the host blob, before anything is uploaded or launched
         if not plan.ok() or (sync is not None and not plan.sync_ok()) or (resume is not None and not plan.resume_ok()):
             raise RuntimeError("libhawq_mi355: " + _lib.load().hawq_last_error().decode())
@@ -1055,7 +1124,7 @@ def read_source(source) -> bytes:
         return f.read()
 
 
-def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, min_sync_bytes=None, progressive=False, resume=None, front_end="host"):
+def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, min_sync_bytes=None, progressive=False, resume=None, front_end="host", draft=None):
     """Paths or bytes of image files -> ``(images, fallbacks)``: ``images[i]`` a uint8 [H, W, 3] RGB tensor on the MI355X equal to
     ``image.decode_image(sources[i])``, ``fallbacks`` the list of ``(index, reason)`` of the images the HOST decoder produced: files
     ``parse_jpeg`` refuses (progressive, CMYK, not a JPEG, ...) and files whose device decode reported a status (damaged streams).
@@ -1076,8 +1145,13 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
     it accepts (``hawq_jpeg_front_fill``); every file it defers - progressive ones, other formats, refused and malformed ones - goes
     through ``parse_jpeg`` exactly as with ``"host"``.  The same bytes and the same fallbacks, at two more synchronisations per batch
     (profiles/jpeg_front.md: it wins on all three measured sets, 11.8 -> 5.1 ms per 128 files with restart markers); not together with
-    ``resume``."""
+    ``resume``.
+    ``draft``: None, or a (width, height) pair: every image is decoded at the reduced size Pillow's draft mode gives it,
+    ``images[i]`` = ``image.decode_image(sources[i], draft=draft)`` - a JPEG at 1 / ``draft_scale`` of its size, ceil(H / s) x ceil(W / s),
+    produced on the device by the library's reduced inverse DCTs, every other format at full size.  It composes with
+    every option above; the fallbacks are those of the call without it, and the host decoder takes them with the same draft."""
     from .image import decode_image
+    draft = check_draft(draft)
     if front_end not in ("host", "device"):
         raise ValueError(f"front_end must be 'host' or 'device', not {front_end!r}")
     if front_end == "device" and resume is not None:
@@ -1086,6 +1160,7 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
         raise ValueError(f"entropy must be 'serial' or 'sync', not {entropy!r}")
     if entropy == "serial" and (sub_bytes is not None or min_sync_bytes is not None):
         raise ValueError("sub_bytes / min_sync_bytes belong to entropy='sync'")
+    scaled = {} if draft is None else {"draft": draft}   # absent without the option: the launches get today's arguments
     more = {} if entropy == "serial" else {"sync": (SUB_BYTES if sub_bytes is None else int(sub_bytes), MIN_SYNC_BYTES if min_sync_bytes is None else int(min_sync_bytes))}
     datas = [read_source(s) for s in sources]
     if not datas:
@@ -1106,9 +1181,11 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
             records[i] = parse_jpeg(data, progressive=True) if progressive else parse_jpeg(data)
         except UnsupportedJpeg as e:
             fallbacks.append((i, e.reason))
-            host[i] = decode_image(data)
+            host[i] = decode_image(data, **scaled)
     sizes = [(records[i].height, records[i].width) if i in records else (int(info["height"][i]), int(info["width"][i])) if i in taken else tuple(host[i].shape[:2])
              for i in range(len(datas))]
+    if draft is not None:   # what the device decodes comes out reduced; what the host has decoded already is
+        sizes = [(h, w) if i in host else (scaled_size(h, s), scaled_size(w, s)) for i, (h, w) in enumerate(sizes) for s in (draft_scale(w, h, draft),)]
     offsets, total = output_layout(sizes)
     out = torch.empty(total, dtype=torch.uint8, device=dev)
     # a file whose entry has no points (no interval longer than the index's distance) has nothing to gain: it goes as without the index
@@ -1120,14 +1197,14 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
             if idx:
                 if indexed:
                     options = {"resume": [points[i] for i in idx]}
-                enqueued.append((idx, _launch([records[i] for i in idx], [offsets[i] for i in idx], out, dev, **options)))
+                enqueued.append((idx, _launch([records[i] for i in idx], [offsets[i] for i in idx], out, dev, **options, **scaled)))
     if front:
-        enqueued.append((front, _front_launch(staged, info, front, [offsets[i] for i in front], out, dev, **more)))
+        enqueued.append((front, _front_launch(staged, info, front, [offsets[i] for i in front], out, dev, **more, **scaled)))
     status = {i: st for idx, device_status in enqueued for i, st in zip(idx, device_status.cpu().numpy())}
     for i, st in sorted(status.items()):
         if st != 0:
             fallbacks.append((i, "device status %d: %s" % (st, STATUS_NAMES.get(int(st), "unknown"))))
-            host[i] = decode_image(datas[i])
+            host[i] = decode_image(datas[i], **scaled)
             if tuple(host[i].shape[:2]) != sizes[i]:
                 raise RuntimeError(f"image {i}: the host decoder gives {tuple(host[i].shape[:2])}, the header {sizes[i]}")
     for i, im in host.items():

@@ -719,10 +719,13 @@ typedef struct hawq_jpeg_desc {
     int32_t qt_off[3], dc_off[3], ac_off[3];   /* per component: uint16[64], hawq_jpeg_huff, hawq_jpeg_huff */
     int32_t stream_off, stream_len;    /* the entropy-coded segment */
     int32_t interval_off;              /* int32 [n_intervals][2]: first byte and one past the last, relative to stream_off */
-    int32_t reserved;
+    int32_t scale;                     /* 0 or 1: full size.  2, 4, 8: the reduced decode of libjpeg's DCT-domain scaling (Pillow's
+                                          draft mode): stages 2 and 3 produce ceil(width / scale) x ceil(height / scale) pixels from
+                                          n x n inverse DCTs, n = 8 / scale per block side (2 n for the chroma of a 2 x 2 image) */
     int64_t coef_block0;               /* first [64] x int16 block of this image in the coefficient slab: component after component,
                                           each mcus_y * v rows of mcus_x * h blocks */
-    int64_t plane_off;                 /* first byte of this image's sample planes: component after component, pitch mcus_x * h * 8 */
+    int64_t plane_off;                 /* first byte of this image's sample planes: component after component, pitch mcus_x * h * n,
+                                          n = 8 at full size */
     int64_t out_off;                   /* first byte of the RGB image in out; 16-byte aligned */
 } hawq_jpeg_desc;                      /* 112 bytes */
 /* hawq_jpeg_batch_ok launches nothing and reads the HOST blob: 1 when the header, every descriptor, table, stream and interval lies

@@ -33,12 +33,19 @@ markers and the mixed set with ``entropy="sync"``.  Per path the wall time of ``
 host milliseconds between the call and its first decode launch (parse + plan + upload on the host path; upload, scan, read-back, layout,
 fill and read-back on the device path).  Writes profiles/jpeg_front.md.
 
+``--draft`` measures the reduced-size decode (``decode_jpeg_batch(draft=(256, 256))``) on ``DRAFT_SETS``: the sample enlarged
+to 1500 x 2000 and 3000 x 4000, with a restart marker every MCU row (serial entropy stage) and without (``entropy="sync"``).  The call
+without the option and the call with it alternate in one process, each going first every other time; outputs are compared with Pillow's
+draft pipeline first.  Then stages 2 + 3 of both from the HIP events, Pillow in 16 threads with the same draft, and the plane + output
+bytes of the two plans.  Writes profiles/jpeg_draft.md.
+
     python tools/jpeg_bench.py [--batch 128] [--repeats 20] [--warmup 3] [--out profiles/jpeg_decode.md] [--box NAME]
                                [--entropy serial|sync|both] [--sub-bytes N] [--min-sync-bytes N] [--sweep] [--sets 0,1,3] [--progressive]
-                               [--resume] [--every N] [--front-end both]
+                               [--resume] [--every N] [--front-end both] [--draft]
 """
 import argparse
 import ctypes as C
+import functools
 import io
 import json
 import os
@@ -85,6 +92,12 @@ EVERY_SWEEP = (256, 512, 1024, 2048, 4096)
 FRONT_SETS = [("375x500 q90 4:2:0, restart every MCU row", "serial"), ("375x500 q90 4:2:0", "sync"), ("mixed sizes / qualities / subsamplings", "sync")]
 
 
+# the sets of --draft: (label, enlargement of the 375 x 500 sample, save options, entropy stage)
+DRAFT_REQUEST = (256, 256)
+DRAFT_SETS = [(f"{375 * k}x{500 * k} q90 4:2:0{', restart every MCU row' if rst else ''}", float(k), dict(quality=90, subsampling=2, **rst), "serial" if rst else "sync")
+              for k in (4, 8) for rst in (dict(restart_marker_rows=1), {})]
+
+
 def make_set(variants, n):
     from PIL import Image
     with Image.open(os.path.join(ROOT, "tests", "golden", "sample_500x375.jpg")) as im:
@@ -125,9 +138,10 @@ def main():
     ap.add_argument("--sets", default=None, help="comma-separated indices into SETS (default: all)")
     ap.add_argument("--resume", action="store_true", help="resume points: the serial, sync and resume device paths and Pillow, and a sweep over the distance")
     ap.add_argument("--front-end", choices=("both",), default=None, help="the host and the device front end of decode_jpeg_batch, alternating")
+    ap.add_argument("--draft", action="store_true", help="large files: decode_jpeg_batch without and with draft=(256, 256), alternating")
     ap.add_argument("--every", type=int, default=jpeg.RESUME_EVERY, help="distance of the resume points of the wall-time rows")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_front.md" if args.front_end else "jpeg_resume.md" if args.resume else "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
+    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_draft.md" if args.draft else "jpeg_front.md" if args.front_end else "jpeg_resume.md" if args.resume else "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
     paths = ("serial", "sync") if args.entropy == "both" else (args.entropy,)
     sync_of = {"serial": None, "sync": (args.sub_bytes, args.min_sync_bytes)}
     picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(SETS))
@@ -142,6 +156,8 @@ def main():
         ev = C.c_void_p()
         _lib.check(lib.hawq_event_create(C.byref(ev)))
         events.append(ev)
+    if args.draft:
+        return draft(args, box, dev, lib, events)
     if args.front_end:
         return front_end(args, box, dev)
     if args.resume:
@@ -250,6 +266,93 @@ def main():
                   "| set | sub_bytes | min_sync_bytes | jobs | serial entropy | sync entropy | rounds of the largest interval |", "|---|---|---|---|---|---|---|"]
         for r in sweep_rows:
             lines.append(f"| {r['set']} | {r['sub_bytes']} | {r['min_sync_bytes']} | {r['jobs']} | {f(r['serial_entropy_ms'])} | {f(r['sync_entropy_ms'])} | {r['rounds_largest']} |")
+    lines.append("")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines))
+    print("wrote", args.out)
+
+
+def draft(args, box, dev, lib, events):
+    """the ``--draft`` report"""
+    picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(DRAFT_SETS))
+    rows = []
+    for label, scale, kw, entropy in [DRAFT_SETS[k] for k in picked]:
+        datas = make_set([(scale, kw)], args.batch)
+        samples = [(d, 0) for d in datas]
+        more = {} if entropy == "serial" else dict(entropy="sync", sub_bytes=args.sub_bytes, min_sync_bytes=args.min_sync_bytes)
+
+        def pillow(request):
+            decode = image.decode_image if request is None else functools.partial(image.decode_image, draft=request)
+            imgs, _ = next(iter(image.decoded_batches(samples, len(samples), workers=16, decode=decode)))
+            return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
+
+        def device(request):
+            imgs, fallbacks = jpeg.decode_jpeg_batch(datas, dev, draft=request, **more)
+            assert not fallbacks, fallbacks
+            return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
+
+        for request in (None, DRAFT_REQUEST):
+            if not torch.equal(pillow(request), device(request)):
+                sys.exit(f"jpeg_bench: Pillow and the device path differ at {label}, draft {request}")
+        runs = {"full": lambda: device(None), "draft": lambda: device(DRAFT_REQUEST)}
+        for _ in range(args.warmup):
+            for fn in runs.values():
+                fn()
+        t = {name: [] for name in runs}
+        order = list(runs)
+        for r in range(args.repeats):
+            for name in order[r % 2:] + order[:r % 2]:   # each path goes first every other time
+                t[name].append(wall(runs[name]))
+        t["pillow"] = [wall(lambda: pillow(DRAFT_REQUEST)) for _ in range(args.warmup + args.repeats)][args.warmup:]
+        # stages 2 + 3 alone: parsed once, planned + uploaded + launched per call
+        records = [jpeg.parse_jpeg(d) for d in datas]
+        sync = None if entropy == "serial" else (args.sub_bytes, args.min_sync_bytes)
+        row = {"set": label, "entropy": entropy, "n": len(datas), "compressed_mb": sum(map(len, datas)) / 1e6,
+               "scale": jpeg.draft_scale(records[0].width, records[0].height, DRAFT_REQUEST)}
+        stages = {}
+        for name, request in (("full", None), ("draft", DRAFT_REQUEST)):
+            plan = jpeg.plan_jpeg_batch(records, draft=request)
+            row[name + "_plane_mb"], row[name + "_out_mb"], row[name + "_coef_mb"] = plan.plane_bytes / 1e6, plan.out_bytes / 1e6, plan.coef_blocks * 128 / 1e6
+            stages[name] = (plan.out_offsets, torch.empty(plan.out_bytes, dtype=torch.uint8, device=dev), {} if request is None else {"draft": request}, ([], [], []))
+        for k in range(args.warmup + args.repeats):
+            for name in order[k % 2:] + order[:k % 2]:
+                offsets, out, option, got = stages[name]
+                status = jpeg._launch(records, offsets, out, dev, events, **({} if sync is None else {"sync": sync}), **option).cpu()   # reads the status: synchronised
+                assert not status.any()
+                if k >= args.warmup:
+                    for s_ in range(3):
+                        ms = C.c_float()
+                        _lib.check(lib.hawq_event_elapsed_ms(events[s_], events[s_ + 1], C.byref(ms)))
+                        got[s_].append(ms.value)
+        for name in order:
+            got = stages[name][3]
+            row[name + "_wall_ms"], row[name + "_entropy_ms"] = stat(t[name]), stat(got[0])
+            row[name + "_pixel_ms"] = stat([a + b for a, b in zip(got[1], got[2])])
+        row["pillow_wall_ms"] = stat(t["pillow"])
+        row["wall_ratio"] = row["draft_wall_ms"][0] / row["full_wall_ms"][0]
+        del stages
+        torch.cuda.empty_cache()
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    f = lambda v: f"{v[0]:.2f} ({v[1]:.2f}-{v[2]:.2f})"
+    lines = ["# Large JPEGs decoded at reduced size on the device (`draft=`), against the full-size decode", "",
+             f"Measured on one {box} with `python tools/jpeg_bench.py --draft --batch {args.batch} --repeats {args.repeats} --warmup {args.warmup}`: median "
+             f"(min-max) of {args.repeats} calls in milliseconds, the two device paths alternating in one process, each going first every other time; both compared byte "
+             "for byte with Pillow's pipeline (with and without the draft) first.  Resize / crop 256 / 224.",
+             f"`full`: `decode_jpeg_batch` as it is + `preprocess_batch_fused`.  `draft`: the same with `draft={DRAFT_REQUEST}`.  `Pillow`: Pillow in 16 threads with "
+             "the same draft + `preprocess_batch_fused`.  Wall: host clock around the call and a device synchronise.  Stages: HIP events on the stream around stage 1 "
+             f"and around stages 2 + 3 of the decode call alone.  `entropy=\"sync\"` with sub_bytes {args.sub_bytes}, min_sync_bytes {args.min_sync_bytes}.", "",
+             "| set | entropy | scale | full wall | draft wall | draft / full | Pillow (draft) wall | full stages 2 + 3 | draft stages 2 + 3 | full entropy | draft entropy |",
+             "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['n']} x {r['set']} | {r['entropy']} | 1/{r['scale']} | {f(r['full_wall_ms'])} | {f(r['draft_wall_ms'])} | {r['wall_ratio']:.2f} | {f(r['pillow_wall_ms'])} | "
+                     f"{f(r['full_pixel_ms'])} | {f(r['draft_pixel_ms'])} | {f(r['full_entropy_ms'])} | {f(r['draft_entropy_ms'])} |")
+    lines += ["", "Device buffers of the plan, in MB (the coefficient slab is the same for both):", "",
+              "| set | MB compressed | coefficients | full planes | full output | draft planes | draft output |", "|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['n']} x {r['set']} | {r['compressed_mb']:.1f} | {r['full_coef_mb']:.1f} | {r['full_plane_mb']:.1f} | {r['full_out_mb']:.1f} | "
+                     f"{r['draft_plane_mb']:.1f} | {r['draft_out_mb']:.1f} |")
     lines.append("")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
