@@ -185,6 +185,18 @@ class JpegFrontPlace(C.Structure):
     _fields_ = [("file", i32)] + [(n, i32 * 3) for n in ("qt_off", "dc_off", "ac_off")] + [("interval_off", i32), ("stream_off", i32), ("reserved", i32 * 4)]
 
 
+class JpegFrontScanRec(C.Structure):
+    """struct hawq_jpeg_front_scan_rec (include/hawq_mi355.h): what hawq_jpeg_front_scan_prog found in one scan of a progressive file."""
+    _fields_ = ([(n, i32) for n in ("ncomp", "comp0", "ss", "se", "ah", "al", "level")] + [("dc_at", i32 * 3)]
+                + [(n, i32) for n in ("ac_at", "restart", "n_intervals", "scan_first", "scan_end", "reserved")])
+
+
+class JpegFrontScanPlace(C.Structure):
+    """struct hawq_jpeg_front_scan_place (include/hawq_mi355.h): where hawq_jpeg_front_fill_prog writes one scan's share of the blob."""
+    _fields_ = ([("file", i32), ("scan", i32), ("qt_off", i32 * 3), ("dc_off", i32 * 3)]
+                + [(n, i32) for n in ("ac_off", "interval_off", "stream_off")] + [("reserved", i32 * 5)])
+
+
 # name -> (argtypes); every function returns int except hawq_last_error
 SIGNATURES = {
     "hawq_abi_version": [],
@@ -251,6 +263,10 @@ SIGNATURES = {
     "hawq_jpeg_front_scan_host": [vp, i64, vp, i32, vp],
     "hawq_jpeg_front_fill_ok": [vp, vp, i32, vp, i32, i64, i64],
     "hawq_jpeg_front_fill": [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, vp, i64, vp],
+    "hawq_jpeg_front_scan_prog": [vp, i64, vp, vp, i32, vp, vp, vp],
+    "hawq_jpeg_front_scan_prog_host": [vp, i64, vp, i32, vp, vp],
+    "hawq_jpeg_front_fill_prog_ok": [vp, vp, vp, i32, vp, i32, i64, i64],
+    "hawq_jpeg_front_fill_prog": [vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp],
     "hawq_minmax_f32": [vp, i64, vp, vp, vp],
     "hawq_kthvalue_f32": [vp, i64, i64, i32, vp, vp, vp],
     "hawq_incep_conv": [C.POINTER(IncepConvArgs), vp],

@@ -404,7 +404,8 @@ def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int
     with that many threads (at most 16), one batch ahead of the GPU (``decoded_batches``).  ``device_decode``: the threads only read the
     files; baseline JPEGs are decoded on the MI355X and everything else by the host decoder (``jpeg.decode_jpeg_batch``), and the batch is
     resampled in place by ``preprocess_batch_fused`` (implies ``fused``); ``entropy`` goes to ``decode_jpeg_batch`` (``"sync"``: many
-    lanes per long restart interval); ``progressive`` (needs ``device_decode``): progressive JPEGs are decoded on the MI355X too;
+    lanes per long restart interval); ``progressive`` (needs ``device_decode``): progressive JPEGs are decoded on the MI355X too, with
+    ``"device"`` (needs ``front_end="device"``) from headers the MI355X has walked and a blob it has written itself;
     ``resume`` (needs ``device_decode``): a ``jpeg.ResumeIndex`` or the path of a saved one - the files it has an entry for are decoded
     from their recorded resume points, many waves per long restart interval; ``front_end`` (``"device"`` needs ``device_decode``): the
     MI355X walks the headers of the baseline files and writes their blob itself (``jpeg.decode_jpeg_batch``).  Same order, labels and bytes
@@ -418,14 +419,18 @@ def folder_loader(root: str, batch_size: int = 128, resize: int = 256, crop: int
         raise ValueError(f"front_end must be 'host' or 'device', not {front_end!r}")
     if front_end == "device" and not device_decode:
         raise ValueError("front_end='device' needs device_decode=True")
+    if progressive not in (False, True, "device"):
+        raise ValueError(f"progressive must be False, True or 'device', not {progressive!r}")
     if progressive and not device_decode:
         raise ValueError("progressive=True needs device_decode=True")
+    if isinstance(progressive, str) and front_end != "device":
+        raise ValueError("progressive='device' needs front_end='device'")
     if resume is not None and not device_decode:
         raise ValueError("resume needs device_decode=True")
     samples, _ = image_folder(root)
     if device_decode:
         from . import jpeg
-        more = {"progressive": True} if progressive else {}
+        more = {"progressive": progressive} if progressive else {}
         if resume is not None:
             more["resume"] = resume if isinstance(resume, jpeg.ResumeIndex) else jpeg.ResumeIndex.load(resume)
         if front_end != "host":

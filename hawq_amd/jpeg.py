@@ -20,6 +20,9 @@ Host side, pure Python / numpy, one of each:
 - one device front end (``_front_scan``, ``front_layout``, ``_front_launch``) beside the host one, opt-in: the raw files
   go up, the library walks the headers, checks the restart markers and writes the baseline blob on the device with the walker of
   csrc/jpeg_front.h; what it defers goes through ``parse_jpeg`` as ever.
+- the same for progressive files (``_front_scan_prog``, ``front_prog_layout``, ``_front_prog_fill``), opt-in with
+  ``progressive="device"``: one layout of the progressive blob (``_prog_layout``) with the same two fillers, ``plan_jpeg_prog_batch`` on the
+  host and ``hawq_jpeg_front_fill_prog`` on the device, from the scan records of the walker of csrc/jpeg_front_prog.h.
 - one option for reduced sizes (``draft_scale``, ``check_draft``, ``_plane_bytes``): ``draft=(w, h)`` gives every file the
   scale Pillow's draft mode gives it, the planners and the layout write it into the descriptor and size planes and output by it, and
   stages 2 and 3 of every entry point above produce the reduced image with the library's 4x4 / 2x2 / 1x1 inverse DCTs.
@@ -51,6 +54,8 @@ _SCAN = np.dtype(_lib.JpegScan)
 _SEG = np.dtype(_lib.JpegResumeSeg)
 _FINFO = np.dtype(_lib.JpegFrontInfo)
 _FPLACE = np.dtype(_lib.JpegFrontPlace)
+_FSCAN = np.dtype(_lib.JpegFrontScanRec)
+_FSPLACE = np.dtype(_lib.JpegFrontScanPlace)
 MAX_SCANS = 64   # HAWQ_JPEG_PROG_MAX_SCANS
 SYNC_SUB_MIN, SYNC_SUB_MAX = 16, 4096   # HAWQ_JPEG_SYNC_SUB_MIN / _MAX
 SYNC_JOB_HDR_BYTES, SYNC_SUB_RECORD_BYTES = 16, C.sizeof(_lib.JpegSyncSub)
@@ -553,28 +558,6 @@ class _Plan:
         """The library's checker on the host blob (no GPU work); the reason of a refusal is in ``hawq_last_error``."""
         return bool(getattr(_lib.load(), self.checker)(self.blob.ctypes.data, self.nbytes, self.coef_blocks, self.plane_bytes, self.out_bytes))
 
-    def add_image(self, d, r, blob, out_off, scale=None):
-        """The geometry half of descriptor ``d`` for the progressive record ``r``, its quantisation tables into ``blob``, and its share of
-        the three buffers; ``out_off``: None = behind the image before; ``scale``: None (the descriptor says 0: full size), or 1, 2, 4, 8."""
-        d["width"], d["height"], d["ncomp"], d["hs"], d["vs"], d["mcus_x"], d["mcus_y"] = r.width, r.height, r.ncomp, r.hs, r.vs, r.mcus_x, r.mcus_y
-        placed = {}
-        for c, comp in enumerate(r.components):
-            if comp[3] not in placed:
-                placed[comp[3]] = blob.place(r.qtables[comp[3]])
-            d["qt_off"][c] = placed[comp[3]]
-        d["coef_block0"], d["plane_off"] = self.coef_blocks, self.plane_bytes
-        planes, height, width = r.blocks * 64, r.height, r.width
-        if scale is not None:
-            d["scale"] = scale
-            m, luma = 8 // scale, r.mcus_x * r.mcus_y * r.hs * r.vs
-            nc = 2 * m if (r.hs, r.vs) == (2, 2) and m < 8 else m   # ``_plane_bytes`` on one image
-            planes, height, width = luma * m * m + (r.blocks - luma) * nc * nc, scaled_size(r.height, scale), scaled_size(r.width, scale)
-        self.coef_blocks, self.plane_bytes = self.coef_blocks + r.blocks, self.plane_bytes + planes
-        d["out_off"] = off = self.out_bytes if out_off is None else int(out_off)
-        self.out_offsets.append(off)
-        self.sizes.append((height, width))
-        self.out_bytes = _align16(off + width * height * 3)
-
     def finish(self, blob, reserve, out_bytes):
         self.blob, self.nbytes = blob.finish(reserve), blob.at
         if out_bytes is not None:
@@ -674,6 +657,34 @@ class FrontLayout:
     __slots__ = ("head", "place", "desc", "nbytes", "n_waves", "coef_blocks", "plane_bytes", "out_bytes")
 
 
+def _geometry(lay, desc, o, out_offsets, out_bytes, scales):
+    """The geometry half of the descriptors ``desc`` from the columns ``o`` (width, height, ncomp, hs, vs) and every image's share of the
+    three device buffers: coefficient slab, planes, output (``out_offsets`` / ``out_bytes`` / ``scales`` as in ``_baseline_layout``);
+    their sizes into ``lay``.  Both layouts begin with it."""
+    for f in ("width", "height", "ncomp", "hs", "vs"):
+        desc[f] = o[f]
+    desc["mcus_x"], desc["mcus_y"] = -(-o["width"] // (8 * o["hs"])), -(-o["height"] // (8 * o["vs"]))
+    blocks = desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * np.where(o["ncomp"] == 3, o["hs"] * o["vs"] + 2, 1)
+    desc["coef_block0"] = np.cumsum(blocks) - blocks
+    planes, rgb = blocks * 64, 3 * o["width"].astype(np.int64) * o["height"]
+    if scales is not None:
+        desc["scale"] = s = np.asarray(scales, np.int64)
+        luma = desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * o["hs"] * o["vs"]
+        planes = _plane_bytes(luma, blocks - luma, o["hs"], o["vs"], s)
+        rgb = 3 * scaled_size(o["width"].astype(np.int64), s) * scaled_size(o["height"].astype(np.int64), s)
+    desc["plane_off"] = np.cumsum(planes) - planes
+    desc["out_off"] = np.cumsum((rgb + 15) & ~15) - ((rgb + 15) & ~15) if out_offsets is None else out_offsets
+    lay.coef_blocks, lay.plane_bytes = int(blocks.sum()), int(planes.sum())
+    lay.out_bytes = _align16(int(desc["out_off"][-1] + rgb[-1])) if out_bytes is None else int(out_bytes)
+
+
+def _first_user(t, colour):
+    """``t``: int [n, 3] table ids per component -> per component the first one with its table, 0 for the components a gray image
+    (``colour`` false) does not have"""
+    used = colour[:, None] | (np.arange(3) == 0)
+    return np.stack((0 * t[:, 0], t[:, 1] != t[:, 0], np.where(t[:, 2] == t[:, 0], 0, np.where(t[:, 2] == t[:, 1], 1, 2))), 1) * used, used
+
+
 def _baseline_layout(o, out_offsets=None, out_bytes=None, scales=None) -> FrontLayout:
     """The one place that knows the blob of ``hawq_jpeg_decode_batch``: header | descriptors | wave list | per image, per component the
     quantisation, DC and AC table it is the first to use, then intervals, then stream - every part at a 16-byte aligned offset; a
@@ -686,29 +697,16 @@ def _baseline_layout(o, out_offsets=None, out_bytes=None, scales=None) -> FrontL
     lay = FrontLayout()
     colour = o["ncomp"] == 3
     desc, place = np.zeros(n, _DESC), np.zeros(n, _FPLACE)
-    for f in ("width", "height", "ncomp", "hs", "vs", "restart", "n_intervals"):
+    for f in ("restart", "n_intervals"):
         desc[f] = o[f]
-    desc["mcus_x"], desc["mcus_y"] = -(-o["width"] // (8 * o["hs"])), -(-o["height"] // (8 * o["vs"]))
-    blocks = desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * np.where(colour, o["hs"] * o["vs"] + 2, 1)
-    desc["coef_block0"] = np.cumsum(blocks) - blocks
-    planes, rgb = blocks * 64, 3 * o["width"].astype(np.int64) * o["height"]
-    if scales is not None:
-        desc["scale"] = s = np.asarray(scales, np.int64)
-        luma = desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * o["hs"] * o["vs"]
-        planes = _plane_bytes(luma, blocks - luma, o["hs"], o["vs"], s)
-        rgb = 3 * scaled_size(o["width"].astype(np.int64), s) * scaled_size(o["height"].astype(np.int64), s)
-    desc["plane_off"] = np.cumsum(planes) - planes
-    desc["out_off"] = np.cumsum((rgb + 15) & ~15) - ((rgb + 15) & ~15) if out_offsets is None else out_offsets
+    _geometry(lay, desc, o, out_offsets, out_bytes, scales)
     desc["stream_len"] = o["scan_end"] - o["scan_first"]
     lay.n_waves = int(o["n_intervals"].sum())
-    lay.coef_blocks, lay.plane_bytes = int(blocks.sum()), int(planes.sum())
-    lay.out_bytes = _align16(int(desc["out_off"][-1] + rgb[-1])) if out_bytes is None else int(out_bytes)
     # per image the aligned sizes of its parts in blob order: (quantisation, DC, AC) x 3 components, 0 unless the component is the first
     # to use that table (``first``: per component the first one with its table; a gray image has component 0 alone), intervals, stream
-    sizes, first, used = np.zeros((n, 11), np.int64), {}, colour[:, None] | (np.arange(3) == 0)
+    sizes, first = np.zeros((n, 11), np.int64), {}
     for k, (ids, nbytes) in enumerate((("tq", 128), ("td", HUFF_BYTES), ("ta", HUFF_BYTES))):
-        t = o[ids]
-        first[ids] = np.stack((0 * t[:, 0], t[:, 1] != t[:, 0], np.where(t[:, 2] == t[:, 0], 0, np.where(t[:, 2] == t[:, 1], 1, 2))), 1) * used
+        first[ids], used = _first_user(o[ids], colour)
         sizes[:, k:9:3] = (first[ids] == np.arange(3)) * _align16(nbytes)
     sizes[:, 9], sizes[:, 10] = (8 * o["n_intervals"].astype(np.int64) + 15) & ~15, (desc["stream_len"].astype(np.int64) + 15) & ~15
     head = _Blob()
@@ -794,66 +792,136 @@ class JpegProgResumePlan(JpegProgPlan):
         return bool(_lib.load().hawq_jpeg_resume_ok(self.blob.ctypes.data, self.nbytes, 1, self.segs_off, self.n_segs))
 
 
+# what ``_prog_layout`` reads of an image (of a ``hawq_jpeg_front_info``: ``n_scans`` is word 1 of ``reserved``) and of a scan: the columns
+# of a ``hawq_jpeg_front_scan_rec``, where ``dc_at`` / ``ac_at`` need only tell the tables of one image apart (0: none)
+_PROG_IMAGE = np.dtype([(f, np.int32) for f in ("width", "height", "ncomp", "hs", "vs")] + [("tq", np.int32, 3), ("n_scans", np.int32)])
+
+
+class ProgLayout:
+    """What ``_prog_layout`` returns.  ``head``: batch header | progressive header | descriptors | scan table | level list | wave lists as
+    bytes, ``place``: per scan where its tables, intervals and stream go (the ``hawq_jpeg_front_scan_place`` table of the fill; ``file`` is
+    the image's index in the batch), ``desc`` / ``scans`` / ``waves``: the tables in ``head``, ``nbytes``: the blob's size without a
+    segment table, the rest as in ``JpegProgPlan``."""
+    __slots__ = ("head", "place", "desc", "scans", "waves", "nbytes", "n_scans", "n_levels", "n_waves", "level_start", "desc_off", "scan_off", "level_off", "wave_off",
+                 "coef_blocks", "plane_bytes", "out_bytes")
+
+
+def _prog_layout(im, sc, out_offsets=None, out_bytes=None, scales=None) -> ProgLayout:
+    """The one place that knows the blob of ``hawq_jpeg_decode_batch_prog``: batch header | progressive header | descriptors (entropy
+    fields zero) | scan table | level list | wave lists, level after level | per image: the quantisation tables its components are the
+    first to use, then per scan the DC tables and the AC table no earlier scan of the image has placed, its intervals, its stream -
+    every part at a 16-byte aligned offset.  A table in force over several scans stands once: its key is ``dc_at`` / ``ac_at``.  ``im``:
+    the columns ``_PROG_IMAGE`` of the images; ``sc``: the ``hawq_jpeg_front_scan_rec`` columns of their scans, image after image, with
+    the level of every scan; ``out_offsets`` / ``out_bytes`` / ``scales`` as in ``_baseline_layout``.  numpy over the batch, no loop over
+    images or scans.  Two fillers write the bytes of the parts at ``place``: ``plan_jpeg_prog_batch`` on the host,
+    ``hawq_jpeg_front_fill_prog`` on the device."""
+    n, n_scans = len(im), len(sc)
+    lay = ProgLayout()
+    desc, scans, place = np.zeros(n, _DESC), np.zeros(n_scans, _SCAN), np.zeros(n_scans, _FSPLACE)
+    _geometry(lay, desc, im, out_offsets, out_bytes, scales)
+    per_image = im["n_scans"].astype(np.int64)
+    image, scan0 = np.repeat(np.arange(n), per_image), np.cumsum(per_image) - per_image
+    levels, n_intervals = sc["level"].astype(np.int64), sc["n_intervals"].astype(np.int64)
+    lay.n_scans, lay.n_levels, lay.n_waves = n_scans, int(levels.max()), int(n_intervals.sum())
+    # the waves of a level: every interval of every scan of that level, in the order of the scan table
+    order = np.argsort(levels, kind="stable")
+    lay.waves = _wave_list(order, n_intervals[order])
+    level_start = np.concatenate(([0], np.cumsum(np.bincount(levels, n_intervals, lay.n_levels + 1)[1:]))).astype(np.int32)
+    lay.level_start = level_start.tolist()
+    head = _Blob()
+    head.room(_HDR.itemsize + _PHDR.itemsize)
+    lay.desc_off, lay.scan_off, lay.level_off, lay.wave_off = head.room(desc.nbytes), head.room(scans.nbytes), head.room(level_start.nbytes), head.room(lay.waves.nbytes)
+    # per image the quantisation tables; per scan the aligned sizes of its parts in blob order: DC x 3, AC (0 unless the scan is the
+    # first of its image to read that table), intervals, stream
+    first_q, used_q = _first_user(im["tq"], im["ncomp"] == 3)
+    q_sizes = (first_q == np.arange(3)) * used_q * 128
+    keys = np.column_stack((sc["dc_at"], sc["ac_at"])).astype(np.int64)
+    flat = ((image[:, None] << 32) | keys).reshape(-1)
+    _, index, inverse = np.unique(flat, return_index=True, return_inverse=True)
+    first_use = index[inverse.reshape(-1)]   # per table slot the first slot of the batch with that table of that image
+    read = keys.reshape(-1) != 0
+    own = read & (first_use == np.arange(4 * n_scans))
+    sizes = np.zeros((n_scans, 6), np.int64)
+    sizes[:, :4] = own.reshape(n_scans, 4) * _align16(HUFF_BYTES)
+    stream_len = (sc["scan_end"] - sc["scan_first"]).astype(np.int64)
+    sizes[:, 4], sizes[:, 5] = (8 * n_intervals + 15) & ~15, (stream_len + 15) & ~15
+    q_bytes, scan_bytes = q_sizes.sum(1), sizes.sum(1)
+    before = np.cumsum(scan_bytes) - scan_bytes                  # the scans before this one
+    offs = (head.at + np.cumsum(q_bytes)[image] + before)[:, None] + np.cumsum(sizes, 1) - sizes
+    q_offs = (head.at + np.cumsum(q_bytes) - q_bytes + before[scan0])[:, None] + np.cumsum(q_sizes, 1) - q_sizes
+    lay.nbytes = _blob_bytes(int(offs[-1, 5] + sizes[-1, 5]))
+    desc["qt_off"] = np.take_along_axis(q_offs, first_q, 1) * used_q
+    slot_off = offs[:, :4].reshape(-1)
+    table_off, table_place = np.where(read, slot_off[first_use], 0).reshape(n_scans, 4), np.where(own, slot_off, 0).reshape(n_scans, 4)
+    scans["image"] = place["file"] = image
+    place["scan"] = np.arange(n_scans) - scan0[image]
+    for f in ("ncomp", "comp0", "ss", "se", "ah", "al", "level", "restart", "n_intervals"):
+        scans[f] = sc[f]
+    scans["dc_off"], scans["ac_off"], place["dc_off"], place["ac_off"] = table_off[:, :3], table_off[:, 3], table_place[:, :3], table_place[:, 3]
+    scans["interval_off"] = place["interval_off"] = offs[:, 4]
+    scans["stream_off"] = place["stream_off"] = offs[:, 5]
+    scans["stream_len"] = stream_len
+    place["qt_off"][scan0] = np.where(q_sizes > 0, q_offs, 0)
+    hdr = np.array([(n, lay.n_waves, lay.desc_off, lay.wave_off)], _HDR)
+    phdr = np.array([(n_scans, lay.n_levels, lay.scan_off, lay.level_off)], _PHDR)
+    for off, table in ((0, hdr), (_HDR.itemsize, phdr), (lay.desc_off, desc), (lay.scan_off, scans), (lay.level_off, level_start), (lay.wave_off, lay.waves)):
+        head.put(off, table)
+    lay.head, lay.place, lay.desc, lay.scans = head.finish(None), place, desc, scans
+    return lay
+
+
 def plan_jpeg_prog_batch(records, out_offsets=None, out_bytes=None, reserve=None, resume=None, draft=None) -> JpegProgPlan:
-    """Pack the ``JpegProgRecord``s of ``parse_jpeg(progressive=True)`` into the host blob of ``hawq_jpeg_decode_batch_prog``: batch header |
-    progressive header | descriptors (entropy fields zero) | scan table | level list | wave lists, level after level | per image: the
-    quantisation tables, then per scan its Huffman tables, intervals and stream - every part at a 16-byte aligned offset.  Computes the
-    level of every scan (``scan_levels``).  ``out_offsets`` / ``out_bytes`` / ``reserve`` / ``resume`` / ``draft`` as in ``plan_jpeg_batch``: with
-    ``resume`` the segment table of ``hawq_jpeg_decode_batch_prog_resume`` stands behind the streams (a ``JpegProgResumePlan``)."""
+    """Pack the ``JpegProgRecord``s of ``parse_jpeg(progressive=True)`` into the host blob of ``hawq_jpeg_decode_batch_prog``, laid out by
+    ``_prog_layout``: the adapter from records to its columns, with the level of every scan (``scan_levels``), and the host filler that
+    copies table, interval and stream bytes to the offsets it gives.  ``out_offsets`` / ``out_bytes`` / ``reserve`` / ``resume`` / ``draft``
+    as in ``plan_jpeg_batch``: with ``resume`` the segment table of ``hawq_jpeg_decode_batch_prog_resume`` stands behind the streams (a
+    ``JpegProgResumePlan``)."""
     records = list(records)
     if not records:
         raise ValueError("empty batch")
-    n = len(records)
     plan, blob = JpegProgPlan() if resume is None else JpegProgResumePlan(), _Blob()
-    plan.n_scans = sum(len(r.scans) for r in records)
     plan.levels = levels = [lv for r in records for lv in scan_levels(r.scans)]
-    plan.n_levels = max(levels)
-    plan.n_waves = sum(len(s.intervals) for r in records for s in r.scans)
-    hdr, phdr, desc = np.zeros(1, _HDR), np.zeros(1, _PHDR), np.zeros(n, _DESC)
-    blob.room(_HDR.itemsize + _PHDR.itemsize)
-    plan.desc_off, plan.scan_off, plan.level_off = blob.room(desc.nbytes), blob.room(plan.n_scans * _SCAN.itemsize), blob.room(4 * (plan.n_levels + 1))
-    plan.wave_off = blob.room(8 * plan.n_waves)
-    hdr["n_images"], hdr["n_waves"], hdr["desc_off"], hdr["wave_off"] = n, plan.n_waves, plan.desc_off, plan.wave_off
-    phdr["n_scans"], phdr["n_levels"], phdr["scan_off"], phdr["level_off"] = plan.n_scans, plan.n_levels, plan.scan_off, plan.level_off
-    rows = []   # the fields of hawq_jpeg_scan, in order
-    for i, r in enumerate(records):
-        plan.add_image(desc[i], r, blob, None if out_offsets is None else out_offsets[i], None if draft is None else draft_scale(r.width, r.height, draft))
-        tables = {}   # id of a table record -> offset: a table stays in force over several scans
-
-        def table(t):
-            if id(t) not in tables:
-                tables[id(t)] = blob.place(t)
-            return tables[id(t)]
-
+    im = np.array([(r.width, r.height, r.ncomp, r.hs, r.vs, tuple(c[3] for c in (r.components * 3)[:3]), len(r.scans)) for r in records], _PROG_IMAGE)
+    rows, tables = [], []   # per scan the tables it reads: DC x 3, AC, None where it reads none
+    for r in records:
+        keys = {}           # id of a table record -> its key: a table stays in force over several scans
         for s in r.scans:
-            dc = [table(t) for t in s.dc or ()]
-            rows.append((i, len(s.comps), s.comps[0], s.ss, s.se, s.ah, s.al, levels[len(rows)], tuple(dc + [0] * (3 - len(dc))), 0 if s.ac is None else table(s.ac),
-                         s.restart, len(s.intervals), blob.place(np.ascontiguousarray(s.intervals, np.int32)),
-                         blob.place(np.frombuffer(r.data, np.uint8, s.scan[1] - s.scan[0], s.scan[0])), s.scan[1] - s.scan[0], (0, 0, 0)))
-    scans = np.array(rows, _SCAN)
-    waves, plan.level_start = [], [0]
-    for level in range(1, plan.n_levels + 1):
-        ks = np.flatnonzero(np.array(levels) == level)
-        waves.append(_wave_list(ks, scans["n_intervals"][ks]))
-        plan.level_start.append(plan.level_start[-1] + len(waves[-1]))
-    waves = np.concatenate(waves)
+            mine = (list(s.dc or ()) + [None] * 3)[:3] + [s.ac]
+            at = [0 if t is None else keys.setdefault(id(t), len(keys) + 1) for t in mine]
+            rows.append((len(s.comps), s.comps[0], s.ss, s.se, s.ah, s.al, levels[len(rows)], tuple(at[:3]), at[3], s.restart, len(s.intervals), s.scan[0], s.scan[1], 0))
+            tables.append(mine)
+    scales = None if draft is None else draft_scales(im["width"], im["height"], draft)
+    lay = _prog_layout(im, np.array(rows, _FSCAN), out_offsets, out_bytes, scales)
+    for f in ("n_scans", "n_levels", "n_waves", "level_start", "scan_off", "level_off", "wave_off", "desc_off", "coef_blocks", "plane_bytes"):
+        setattr(plan, f, getattr(lay, f))
+    plan.out_offsets, plan.sizes = lay.desc["out_off"].tolist(), [(r.height, r.width) for r in records]
+    if scales is not None:
+        plan.sizes = [(scaled_size(h, s), scaled_size(w, s)) for (h, w), s in zip(plan.sizes, scales.tolist())]
+    blob.put(blob.room(lay.nbytes), lay.head)
+    flat = [(r, s) for r in records for s in r.scans]
+    for (r, s), mine, qt, dc, ac, interval_off, stream_off in zip(flat, tables, *(lay.place[f].tolist() for f in ("qt_off", "dc_off", "ac_off", "interval_off", "stream_off"))):
+        for c, off in enumerate(qt):
+            if off:   # in the first scan of an image, for the first component with that table
+                blob.put(off, r.qtables[r.components[c][3]])
+        for off, table in zip(dc + [ac], mine):
+            if off:   # 0: an earlier scan has placed it, or the scan reads none
+                blob.put(off, table)
+        blob.put(interval_off, np.ascontiguousarray(s.intervals, np.int32))
+        blob.put(stream_off, np.frombuffer(r.data, np.uint8, s.scan[1] - s.scan[0], s.scan[0]))
     if resume is not None:
+        waves = lay.waves
         heads = waves[:, 1] == 0
         wave_of = np.zeros(plan.n_scans, np.int64)   # a scan's intervals follow one another in the wave list
         wave_of[waves[heads, 0]] = np.flatnonzero(heads)
         scan0 = np.cumsum([0] + [len(r.scans) for r in records])
         points = [np.column_stack((wave_of[np.clip(scan0[i] + p[:, 0], 0, plan.n_scans - 1)] + p[:, 1], p[:, 2:])) for i, p in enumerate(resume)]
-        flat = [s for r in records for s in r.scans]
         first, units = np.zeros(plan.n_waves, np.int64), np.zeros(plan.n_waves, np.int64)
-        for k, s in enumerate(flat):
+        for k, (_, s) in enumerate(flat):
             first[wave_of[k]:wave_of[k] + len(s.intervals)] = s.intervals[:, 0]
             units[wave_of[k]:wave_of[k] + len(s.intervals)] = _interval_units(s.units, s.restart, len(s.intervals))
         segs = _segment_table(first, units, np.concatenate(points))
         plan.segs_off, plan.n_segs = blob.place(segs), len(segs)
-    for off, table in ((0, hdr), (_HDR.itemsize, phdr), (plan.desc_off, desc), (plan.scan_off, scans), (plan.level_off, np.array(plan.level_start, np.int32)),
-                       (plan.wave_off, waves)):
-        blob.put(off, table)
-    return plan.finish(blob, reserve, out_bytes)
+    return plan.finish(blob, reserve, lay.out_bytes)
 
 
 # ------------------------------------------------------------------------------------------------------------------ resume points
@@ -975,6 +1043,21 @@ def front_scan_host(datas):
     return info
 
 
+# ``progressive="device"``: the kind of an accepted file is word 0, its number of scans word 1 of ``reserved``
+FRONT_KIND_BASELINE, FRONT_KIND_PROG = 0, 1
+# The defer codes of ``hawq_jpeg_front_scan_prog`` on files ``parse_jpeg(data, progressive=True)`` may still accept, as above
+FRONT_PROG_DEFERS_BY_DESIGN = {2: "more than 64 marker segments up to the frame header, or more than 256 in a progressive file", 3: "a file above 1 GiB"}
+
+
+def front_scan_prog_host(datas):
+    """``hawq_jpeg_front_scan_prog_host`` on the files ``datas``: the walker of the scan kernel for both kinds on the host, no GPU work
+    -> (one ``hawq_jpeg_front_info`` per file, ``hawq_jpeg_front_scan_rec`` [files, 64]: the scans of the progressive ones)."""
+    table, buf, total = pack_files(datas)
+    info, scans = np.zeros(len(datas), _FINFO), np.zeros((len(datas), MAX_SCANS), _FSCAN)
+    _lib.call("hawq_jpeg_front_scan_prog_host", buf.ctypes.data, total, table.ctypes.data, len(datas), info.ctypes.data, scans.ctypes.data)
+    return info, scans
+
+
 def front_layout(info, files, out_offsets, out_bytes, draft=None) -> FrontLayout:
     """``_baseline_layout`` of the accepted files of a scan, for ``hawq_jpeg_front_fill`` to fill.  ``info``: the records of the scan;
     ``files``: indices of accepted ones, ascending; ``out_offsets`` / ``out_bytes``: where each image goes in the output; ``draft``: as in
@@ -990,26 +1073,97 @@ def front_layout(info, files, out_offsets, out_bytes, draft=None) -> FrontLayout
 
 class _Staged:
     """The files of a batch on the device behind ``_front_scan``: ``table`` (host), ``total`` bytes, and the device tensors ``files``,
-    ``table_dev`` and ``info_dev``."""
-    __slots__ = ("table", "total", "files", "table_dev", "info_dev")
+    ``table_dev`` and ``info_dev``; behind ``_front_scan_prog`` ``scans_dev`` as well."""
+    __slots__ = ("table", "total", "files", "table_dev", "info_dev", "scans_dev")
+
+
+def _stage_files(datas, dev) -> _Staged:
+    """Pack the raw files into the pinned staging buffer of their kind and upload them in one copy with their table"""
+    s = _Staged()
+    st = _staging(dev, "jpeg_files")
+    room = _align16(len(datas) * _FFILE.itemsize)   # the table in front of the files
+    s.table, _, s.total = pack_files(datas, lambda nbytes: st.reserve(room + nbytes, dev)[0].numpy()[room:])
+    st.host.numpy()[:s.table.nbytes] = s.table.view(np.uint8)
+    st.upload(room + s.total)
+    s.table_dev, s.files = st.dev[:room], st.dev[room:room + s.total]
+    return s
 
 
 def _front_scan(datas, dev):
     """Pack the raw files into the pinned staging buffer of their kind, upload them in one copy with their table, run
     ``hawq_jpeg_front_scan`` and read the info records back (one synchronisation) -> (info, what ``_front_launch`` needs)."""
-    s = _Staged()
     with torch.cuda.device(dev):
-        st = _staging(dev, "jpeg_files")
-        room = _align16(len(datas) * _FFILE.itemsize)   # the table in front of the files
-        s.table, _, s.total = pack_files(datas, lambda nbytes: st.reserve(room + nbytes, dev)[0].numpy()[room:])
-        st.host.numpy()[:s.table.nbytes] = s.table.view(np.uint8)
-        st.upload(room + s.total)
-        s.table_dev, s.files = st.dev[:room], st.dev[room:room + s.total]
+        s = _stage_files(datas, dev)
         s.info_dev = torch.empty(len(datas) * _FINFO.itemsize, dtype=torch.uint8, device=dev)
         _lib.call("hawq_jpeg_front_scan", s.files.data_ptr(), s.total, s.table_dev.data_ptr(), s.table.ctypes.data, len(datas), s.info_dev.data_ptr(),
                   torch.cuda.current_stream(dev).cuda_stream)
         info = s.info_dev.cpu().numpy().view(_FINFO)
     return info, s
+
+
+def _front_scan_prog(datas, dev):
+    """``_front_scan`` with ``hawq_jpeg_front_scan_prog``: the info records and the scan records come back in one copy (one
+    synchronisation) -> (info, scans [files, 64], what ``_front_launch`` and ``_front_prog_fill`` need)."""
+    n = len(datas)
+    with torch.cuda.device(dev):
+        s = _stage_files(datas, dev)
+        records = torch.empty(n * (_FINFO.itemsize + MAX_SCANS * _FSCAN.itemsize), dtype=torch.uint8, device=dev)
+        s.info_dev, s.scans_dev = records[:n * _FINFO.itemsize], records[n * _FINFO.itemsize:]
+        _lib.call("hawq_jpeg_front_scan_prog", s.files.data_ptr(), s.total, s.table_dev.data_ptr(), s.table.ctypes.data, n, s.info_dev.data_ptr(),
+                  s.scans_dev.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        host = records.cpu().numpy()
+    return host[:n * _FINFO.itemsize].view(_FINFO), host[n * _FINFO.itemsize:].view(_FSCAN).reshape(n, MAX_SCANS), s
+
+
+def front_prog_layout(info, scans, files, out_offsets, out_bytes, draft=None) -> ProgLayout:
+    """``_prog_layout`` of the progressive files a scan accepted, for ``hawq_jpeg_front_fill_prog`` to fill.  ``info`` / ``scans``: the
+    records of ``hawq_jpeg_front_scan_prog``; ``files``: indices of accepted progressive ones, ascending; the rest as in ``front_layout``."""
+    files = np.asarray(files, np.int64)
+    o = info[files]
+    if len(files) == 0 or (o["defer"] != FRONT_OK).any() or (o["reserved"][:, 0] != FRONT_KIND_PROG).any():
+        raise ValueError("front_prog_layout wants accepted progressive files")
+    im = np.zeros(len(files), _PROG_IMAGE)
+    for f in ("width", "height", "ncomp", "hs", "vs", "tq"):
+        im[f] = o[f]
+    im["n_scans"] = o["reserved"][:, 1]
+    sc = scans[files][np.arange(MAX_SCANS) < im["n_scans"][:, None]]   # the scans of the files, file after file
+    lay = _prog_layout(im, sc, out_offsets, out_bytes, None if draft is None else draft_scales(o["width"], o["height"], draft))
+    lay.place["file"] = files[lay.place["file"]]
+    return lay
+
+
+def _front_prog_fill(staged, info, scans, files, out_offsets, out, dev, draft=None):
+    """The first half of the device call of ``decode_jpeg_batch(progressive="device")`` for the progressive files the scan accepted: lay
+    the blob out, have ``hawq_jpeg_front_fill_prog`` write it from the staged files and start its copy back into pinned memory.  Nothing
+    waits here: the caller synchronises the stream once for this blob and the baseline one -> what ``_front_prog_decode`` needs."""
+    lay = front_prog_layout(info, scans, files, out_offsets, out.numel(), draft)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        st_blob, st_tab = _staging(dev, "jpeg_front_prog"), _staging(dev, "jpeg_front_prog_tables")
+        host_blob, blob = st_blob.reserve(lay.nbytes, dev)
+        place_bytes = lay.place.nbytes
+        host_tab, tab = st_tab.reserve(place_bytes + lay.head.size, dev)
+        host_tab.numpy()[:place_bytes] = lay.place.view(np.uint8)
+        host_tab.numpy()[place_bytes:place_bytes + lay.head.size] = lay.head
+        st_tab.upload(place_bytes + lay.head.size)
+        _lib.call("hawq_jpeg_front_fill_prog", staged.files.data_ptr(), staged.total, staged.table_dev.data_ptr(), staged.table.ctypes.data, len(staged.table),
+                  staged.info_dev.data_ptr(), info.ctypes.data, staged.scans_dev.data_ptr(), scans.ctypes.data, tab.data_ptr(), lay.place.ctypes.data, len(lay.place),
+                  blob.data_ptr(), lay.nbytes, stream.cuda_stream)
+        blob[:lay.head.size].copy_(tab[place_bytes:place_bytes + lay.head.size])
+        host_blob[:lay.nbytes].copy_(blob[:lay.nbytes], non_blocking=True)
+    return lay, blob, host_blob, len(files)
+
+
+def _front_prog_decode(filled, out, dev, events=None, wait=True):
+    """The second half, behind a synchronisation of the stream (``wait``: made here; not when the caller has made one since the fill):
+    hand the blob read back as the host blob to ``hawq_jpeg_decode_batch_prog``, so ``hawq_jpeg_prog_ok`` passes it before any decode
+    kernel reads it.  Returns the device status as ``_launch`` does."""
+    lay, blob, host_blob, n = filled
+    with torch.cuda.device(dev):
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        return _decode("hawq_jpeg_decode_batch_prog", blob, host_blob.numpy().ctypes.data, lay.nbytes, lay.coef_blocks, lay.plane_bytes, n, out, events,
+                       torch.cuda.current_stream(dev))[0]
 
 
 def _front_launch(staged, info, files, out_offsets, out, dev, events=None, sync=None, draft=None):
@@ -1146,6 +1300,11 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
     through ``parse_jpeg`` exactly as with ``"host"``.  The same bytes and the same fallbacks, at two more synchronisations per batch
     (profiles/jpeg_front.md: it wins on all three measured sets, 11.8 -> 5.1 ms per 128 files with restart markers); not together with
     ``resume``.
+    ``progressive="device"`` (needs ``front_end="device"``): the MI355X also walks the progressive files inside the scope of
+    ``parse_progressive`` (``hawq_jpeg_front_scan_prog``: one launch for both kinds, with the level of every scan) and writes their blob
+    (``hawq_jpeg_front_fill_prog``, one workgroup per scan), which comes back with the baseline one behind the same synchronisation and
+    goes to ``hawq_jpeg_decode_batch_prog``; what the walker defers goes through ``parse_jpeg(data, progressive=True)`` as with
+    ``True``.  The same bytes and the same fallbacks (profiles/jpeg_front_prog.md says for which batches it was measured to pay).
     ``draft``: None, or a (width, height) pair: every image is decoded at the reduced size Pillow's draft mode gives it,
     ``images[i]`` = ``image.decode_image(sources[i], draft=draft)`` - a JPEG at 1 / ``draft_scale`` of its size, ceil(H / s) x ceil(W / s),
     produced on the device by the library's reduced inverse DCTs, every other format at full size.  It composes with
@@ -1156,6 +1315,11 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
         raise ValueError(f"front_end must be 'host' or 'device', not {front_end!r}")
     if front_end == "device" and resume is not None:
         raise ValueError("front_end='device' does not take resume")
+    if progressive not in (False, True, "device"):
+        raise ValueError(f"progressive must be False, True or 'device', not {progressive!r}")
+    on_device = isinstance(progressive, str)   # "device": the walk and the blob of progressive files on the MI355X too
+    if on_device and front_end != "device":
+        raise ValueError("progressive='device' needs front_end='device'")
     if entropy not in ("serial", "sync"):
         raise ValueError(f"entropy must be 'serial' or 'sync', not {entropy!r}")
     if entropy == "serial" and (sub_bytes is not None or min_sync_bytes is not None):
@@ -1169,11 +1333,16 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     records, fallbacks, host = {}, [], {}
-    info, front = None, []
-    if front_end == "device":
+    info, front, front_prog = None, [], []
+    if on_device:
+        info, scans, staged = _front_scan_prog(datas, dev)
+        accepted = info["defer"] == FRONT_OK
+        front = np.flatnonzero(accepted & (info["reserved"][:, 0] == FRONT_KIND_BASELINE)).tolist()
+        front_prog = np.flatnonzero(accepted & (info["reserved"][:, 0] == FRONT_KIND_PROG)).tolist()
+    elif front_end == "device":
         info, staged = _front_scan(datas, dev)
         front = np.flatnonzero(info["defer"] == FRONT_OK).tolist()
-    taken = set(front)
+    taken = set(front) | set(front_prog)
     for i, data in enumerate(datas):
         if i in taken:
             continue
@@ -1198,8 +1367,12 @@ def decode_jpeg_batch(sources, device=None, entropy="serial", sub_bytes=None, mi
                 if indexed:
                     options = {"resume": [points[i] for i in idx]}
                 enqueued.append((idx, _launch([records[i] for i in idx], [offsets[i] for i in idx], out, dev, **options, **scaled)))
+    # both fills are enqueued before anything waits: the synchronisation inside ``_front_launch`` brings both blobs back
+    filled = _front_prog_fill(staged, info, scans, front_prog, [offsets[i] for i in front_prog], out, dev, **scaled) if front_prog else None
     if front:
         enqueued.append((front, _front_launch(staged, info, front, [offsets[i] for i in front], out, dev, **more, **scaled)))
+    if front_prog:
+        enqueued.append((front_prog, _front_prog_decode(filled, out, dev, wait=not front)))
     status = {i: st for idx, device_status in enqueued for i, st in zip(idx, device_status.cpu().numpy())}
     for i, st in sorted(status.items()):
         if st != 0:

@@ -909,6 +909,55 @@ int hawq_jpeg_front_fill(const void *files, int64_t files_bytes, const hawq_jpeg
                          const hawq_jpeg_front_info *info, const hawq_jpeg_front_info *host_info, const hawq_jpeg_front_place *place,
                          const hawq_jpeg_front_place *host_place, int32_t n, void *blob, int64_t blob_bytes, void *stream);
 
+/* ---- the same front end for progressive files (hawq_amd/csrc/jpeg_front_prog.h + jpeg_front.hip) ----------------------
+ * hawq_jpeg_front_scan_prog walks a batch as hawq_jpeg_front_scan does and writes for a baseline file exactly the record that one
+ * writes.  A file that one refuses is walked again as a progressive Huffman file (SOF2) inside the scope of
+ * hawq_amd.jpeg.parse_progressive, baseline until its SOF2 as parse_jpeg(data, progressive=True) takes it.  An accepted progressive
+ * file has in its hawq_jpeg_front_info: defer 0, the geometry, tq, qt_at, reserved[0] = HAWQ_JPEG_FRONT_KIND_PROG and reserved[1] = its
+ * number of scans (1 .. HAWQ_JPEG_PROG_MAX_SCANS), every other word zero; and one hawq_jpeg_front_scan_rec per scan at
+ * scans[file * HAWQ_JPEG_PROG_MAX_SCANS + k], every other record of the file zero.  Bounds of the kernel, beside those above: a
+ * progressive file with more than HAWQ_JPEG_FRONT_PROG_MAX_SEGMENTS marker segments in all defers with HAWQ_JPEG_FRONT_LONG_HEADER - 64
+ * before the first scan as above, and a DHT and a DRI in front of each of 64 scans behind it. */
+enum { HAWQ_JPEG_FRONT_KIND_BASELINE = 0, HAWQ_JPEG_FRONT_KIND_PROG = 1 };
+enum { HAWQ_JPEG_FRONT_PROG_MAX_SEGMENTS = 256 };
+typedef struct hawq_jpeg_front_scan_rec {
+    int32_t ncomp, comp0;              /* components comp0 .. comp0 + ncomp - 1 of the frame */
+    int32_t ss, se, ah, al;
+    int32_t level;                     /* as hawq_jpeg_scan.level, among the scans of this file */
+    int32_t dc_at[3];                  /* file offset of BITS of the DC table in force at the SOS for the scan's i-th component when ss = 0
+                                          and ah = 0, else 0 */
+    int32_t ac_at;                     /* the same of the AC table when ss > 0, else 0 */
+    int32_t restart, n_intervals;      /* in the scan's units, as hawq_jpeg_scan */
+    int32_t scan_first, scan_end;      /* the entropy-coded segment: first byte, one past the last (where the next marker stands) */
+    int32_t reserved;
+} hawq_jpeg_front_scan_rec;            /* 64 bytes */
+typedef struct hawq_jpeg_front_scan_place {   /* where the fill writes one scan's share of the progressive blob; offsets 16-byte aligned */
+    int32_t file, scan;                /* index into the file table and the info records; the scan's index in that file */
+    int32_t qt_off[3];                 /* in the first scan of a file, per component: where its quantisation table goes, 0: nowhere */
+    int32_t dc_off[3], ac_off;         /* where the table at dc_at[i] / ac_at goes, 0: nowhere (an earlier scan has placed it, or none) */
+    int32_t interval_off, stream_off;
+    int32_t reserved[5];
+} hawq_jpeg_front_scan_place;          /* 64 bytes */
+/* hawq_jpeg_front_scan_prog: as hawq_jpeg_front_scan, with scans = device memory for n_files * HAWQ_JPEG_PROG_MAX_SCANS records, which
+ * it zeroes on `stream` first.  One wave per file.  hawq_jpeg_front_scan_prog_host: the same walker over host memory; no device.
+ * hawq_jpeg_front_fill_prog_ok launches nothing and reads host memory: 1 when every entry of host_place names a scan of an accepted
+ * progressive file, in ascending order, every table it places and the scan's segment lie inside that file, and every destination lies
+ * inside blob_bytes at a 16-byte aligned offset behind the one before it (per scan: quantisation tables, DC tables, AC table,
+ * intervals, stream); else 0 with the reason in hawq_last_error().
+ * hawq_jpeg_front_fill_prog checks again, zeroes blob on `stream` and runs one workgroup per entry, which writes what
+ * hawq_jpeg_front_fill writes for a file.  Headers, descriptors, scan table, level list and wave lists are the caller's; the filled
+ * blob is one hawq_jpeg_prog_ok must pass before hawq_jpeg_decode_batch_prog reads it. */
+int hawq_jpeg_front_scan_prog(const void *files, int64_t files_bytes, const hawq_jpeg_front_file *table, const hawq_jpeg_front_file *host_table,
+                              int32_t n_files, hawq_jpeg_front_info *info, hawq_jpeg_front_scan_rec *scans, void *stream);
+int hawq_jpeg_front_scan_prog_host(const void *host_files, int64_t files_bytes, const hawq_jpeg_front_file *host_table, int32_t n_files,
+                                   hawq_jpeg_front_info *host_info, hawq_jpeg_front_scan_rec *host_scans);
+int hawq_jpeg_front_fill_prog_ok(const hawq_jpeg_front_info *host_info, const hawq_jpeg_front_scan_rec *host_scans, const hawq_jpeg_front_scan_place *host_place,
+                                 int32_t n, const hawq_jpeg_front_file *host_table, int32_t n_files, int64_t files_bytes, int64_t blob_bytes);
+int hawq_jpeg_front_fill_prog(const void *files, int64_t files_bytes, const hawq_jpeg_front_file *table, const hawq_jpeg_front_file *host_table,
+                              int32_t n_files, const hawq_jpeg_front_info *info, const hawq_jpeg_front_info *host_info, const hawq_jpeg_front_scan_rec *scans,
+                              const hawq_jpeg_front_scan_rec *host_scans, const hawq_jpeg_front_scan_place *place,
+                              const hawq_jpeg_front_scan_place *host_place, int32_t n, void *blob, int64_t blob_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

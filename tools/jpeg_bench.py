@@ -32,6 +32,9 @@ two alternating in one process on ``FRONT_SETS``: the set with restart markers e
 markers and the mixed set with ``entropy="sync"``.  Per path the wall time of ``decode_jpeg_batch`` + ``preprocess_batch_fused`` and the
 host milliseconds between the call and its first decode launch (parse + plan + upload on the host path; upload, scan, read-back, layout,
 fill and read-back on the device path).  Writes profiles/jpeg_front.md.
+``--front-end both --progressive`` measures the device front end for progressive files (``progressive="device"``) against
+``progressive=True``, both under ``front_end="device"`` and alternating in one process, on ``PROGRESSIVE_SETS``: wall time, host time to the
+first decode launch, and the stages of the new route.  Writes profiles/jpeg_front_prog.md.
 
 ``--draft`` measures the reduced-size decode (``decode_jpeg_batch(draft=(256, 256))``) on ``DRAFT_SETS``: the sample enlarged
 to 1500 x 2000 and 3000 x 4000, with a restart marker every MCU row (serial entropy stage) and without (``entropy="sync"``).  The call
@@ -53,6 +56,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -141,7 +145,7 @@ def main():
     ap.add_argument("--draft", action="store_true", help="large files: decode_jpeg_batch without and with draft=(256, 256), alternating")
     ap.add_argument("--every", type=int, default=jpeg.RESUME_EVERY, help="distance of the resume points of the wall-time rows")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_draft.md" if args.draft else "jpeg_front.md" if args.front_end else "jpeg_resume.md" if args.resume else "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
+    args.out = args.out or os.path.join(ROOT, "profiles", "jpeg_draft.md" if args.draft else "jpeg_front_prog.md" if args.front_end and args.progressive else "jpeg_front.md" if args.front_end else "jpeg_resume.md" if args.resume else "jpeg_progressive.md" if args.progressive else "jpeg_decode.md")
     paths = ("serial", "sync") if args.entropy == "both" else (args.entropy,)
     sync_of = {"serial": None, "sync": (args.sub_bytes, args.min_sync_bytes)}
     picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(SETS))
@@ -158,6 +162,8 @@ def main():
         events.append(ev)
     if args.draft:
         return draft(args, box, dev, lib, events)
+    if args.front_end and args.progressive:
+        return front_end_progressive(args, box, dev, lib, events)
     if args.front_end:
         return front_end(args, box, dev)
     if args.resume:
@@ -417,6 +423,102 @@ def front_end(args, box, dev):
     for r in rows:
         lines.append(f"| {r['n']} x {r['set']} | {r['entropy']} | {r['accepted']} | {r['waves']} | {f(r['host_wall_ms'])} | {f(r['device_wall_ms'])} | {r['wall_ratio']:.2f} | "
                      f"{f(r['host_before_launch_ms'])} | {f(r['device_before_launch_ms'])} |")
+    lines.append("")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines))
+    print("wrote", args.out)
+
+
+def front_end_progressive(args, box, dev, lib, events):
+    """the ``--front-end both --progressive`` report: ``progressive=True`` against ``progressive="device"``, both under the device front end"""
+    picked = [int(k) for k in args.sets.split(",")] if args.sets else range(len(PROGRESSIVE_SETS))
+    rows, first = [], {}
+    call = _lib.call
+
+    def spy(name, *a):   # when the first decode entry point of a decode_jpeg_batch call is reached
+        if name.startswith("hawq_jpeg_decode_batch") and "t" not in first:
+            first["t"] = time.perf_counter()
+        return call(name, *a)
+
+    for label, variants in [list(PROGRESSIVE_SETS.items())[k] for k in picked]:
+        datas = make_set(variants, args.batch)
+
+        def device(option):
+            first.clear()
+            t0 = time.perf_counter()
+            imgs, fallbacks = jpeg.decode_jpeg_batch(datas, dev, front_end="device", progressive=option)
+            assert not fallbacks, fallbacks
+            first["ms"] = (first["t"] - t0) * 1e3
+            return image.preprocess_batch_fused(imgs, 256, 224, device=dev)
+
+        runs = {"python": True, "device": "device"}
+        _lib.call = spy
+        if not torch.equal(device(True), device("device")):
+            sys.exit(f"jpeg_bench: progressive=True and progressive='device' differ at {label}")
+        for _ in range(args.warmup):
+            for option in runs.values():
+                device(option)
+        t, before = {name: [] for name in runs}, {name: [] for name in runs}
+        order = list(runs)
+        for r in range(args.repeats):
+            for name in order[r % 2:] + order[:r % 2]:   # each path goes first every other time
+                t[name].append(wall(lambda: device(runs[name])))
+                before[name].append(first["ms"])
+        _lib.call = call
+        # the stages of the new route alone: scan, layout, fill and read-back on the host clock, then the decode's launches with HIP events
+        info, scans = jpeg.front_scan_prog_host(datas)
+        prog = np.flatnonzero((info["defer"] == 0) & (info["reserved"][:, 0] == jpeg.FRONT_KIND_PROG)).tolist()
+        sizes = [(int(info["height"][i]), int(info["width"][i])) for i in prog]
+        offsets, total = jpeg.output_layout(sizes)
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        front, stages = ([], []), ([], [], [])
+        for k in range(args.warmup + args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            info_d, scans_d, staged = jpeg._front_scan_prog(datas, dev)
+            t1 = time.perf_counter()
+            filled = jpeg._front_prog_fill(staged, info_d, scans_d, prog, offsets, out, dev)
+            torch.cuda.current_stream(dev).synchronize()
+            t2 = time.perf_counter()
+            status = jpeg._front_prog_decode(filled, out, dev, events, wait=False).cpu()   # reads the status: synchronised
+            assert not status.any()
+            if k >= args.warmup:
+                front[0].append((t1 - t0) * 1e3)
+                front[1].append((t2 - t1) * 1e3)
+                for s in range(3):
+                    ms = C.c_float()
+                    _lib.check(lib.hawq_event_elapsed_ms(events[s], events[s + 1], C.byref(ms)))
+                    stages[s].append(ms.value)
+        row = {"set": label, "n": len(datas), "progressive": len(prog), "compressed_mb": sum(map(len, datas)) / 1e6, "scans": int(info["reserved"][prog, 1].sum()),
+               "blob_mb": filled[0].nbytes / 1e6, "scan_ms": stat(front[0]), "fill_ms": stat(front[1]), "entropy_ms": stat(stages[0]), "idct_ms": stat(stages[1]),
+               "colour_ms": stat(stages[2])}
+        for name in order:
+            row[name + "_wall_ms"], row[name + "_before_launch_ms"] = stat(t[name]), stat(before[name])
+        spread = row["python_wall_ms"][2] - row["python_wall_ms"][1]
+        row["gain_ms"] = row["python_wall_ms"][0] - row["device_wall_ms"][0]
+        row["counts"] = bool(abs(row["gain_ms"]) > spread)   # a difference counts where it exceeds the min-max spread of the old path
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    f = lambda v: f"{v[0]:.2f} ({v[1]:.2f}-{v[2]:.2f})"
+    lines = ["# The device front end for progressive JPEGs against the Python one, alternating in one process", "",
+             f"Measured on one {box} with `python tools/jpeg_bench.py --front-end both --progressive --batch {args.batch} --repeats {args.repeats} --warmup {args.warmup}`: "
+             f"median (min-max) of {args.repeats} calls in milliseconds, the two paths alternating, each going first every other time; outputs compared byte for byte "
+             "first.  Resize / crop 256 / 224.", "`python`: `decode_jpeg_batch(front_end=\"device\", progressive=True)` (the walker defers every progressive file to "
+             "`parse_jpeg` and `plan_jpeg_prog_batch`) + `preprocess_batch_fused`.  `device`: the same with `progressive=\"device\"` (`hawq_jpeg_front_scan_prog`, records "
+             "back, numpy layout, `hawq_jpeg_front_fill_prog`, blob back with the baseline one, the library's check).  Wall: host clock around the call and a device "
+             "synchronise.  Before the launch: host clock from the call to its first `hawq_jpeg_decode_batch*`.  Gain: python wall - device wall, medians; it counts "
+             "where it exceeds the min-max spread of the python path in the same run.", "",
+             "| set | progressive files | scans | python wall | device wall | gain | counts | python: before the launch | device: before the launch |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['n']} x {r['set']} | {r['progressive']} | {r['scans']} | {f(r['python_wall_ms'])} | {f(r['device_wall_ms'])} | {r['gain_ms']:.2f} | "
+                     f"{'yes' if r['counts'] else 'no'} | {f(r['python_before_launch_ms'])} | {f(r['device_before_launch_ms'])} |")
+    lines += ["", "The new route alone on the progressive files of the set: upload + `hawq_jpeg_front_scan_prog` + records back, then layout + "
+              "`hawq_jpeg_front_fill_prog` + blob back (host clock), then the launches of `hawq_jpeg_decode_batch_prog` (HIP events).", "",
+              "| set | blob MB | upload + scan + records back | layout + fill + blob back | entropy, all levels | IDCT | upsample + colour |", "|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['n']} x {r['set']} | {r['blob_mb']:.1f} | {f(r['scan_ms'])} | {f(r['fill_ms'])} | {f(r['entropy_ms'])} | {f(r['idct_ms'])} | {f(r['colour_ms'])} |")
     lines.append("")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
