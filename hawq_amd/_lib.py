@@ -273,6 +273,9 @@ SIGNATURES = {
     "hawq_incep_conv_num_tiles": [],
     "hawq_incep_conv_tile_ok": [C.POINTER(IncepConvArgs), i32],
     "hawq_incep_conv_tiled": [C.POINTER(IncepConvArgs), i32, vp],
+    "hawq_incep_conv_nib_num_tiles": [],
+    "hawq_incep_conv_nib_ok": [C.POINTER(IncepConvArgs), i32],
+    "hawq_incep_conv_nib": [C.POINTER(IncepConvArgs), i32, vp],
     "hawq_incep_conv_group_ok": [C.POINTER(IncepGroupArgs), i32],
     "hawq_incep_conv_group": [C.POINTER(IncepGroupArgs), i32, vp],
     "hawq_incep_conv_group_fan_ok": [C.POINTER(IncepGroupArgs), C.POINTER(IncepFan), i32],

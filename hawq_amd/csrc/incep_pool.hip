@@ -12,6 +12,8 @@
 //     requantised once per tile that sees it instead of once per window, and the nine taps of an output are LDS reads;
 //   * GLOBAL splits the H x W pixels of an image over the lanes of a workgroup and reduces the partial sums through LDS.
 // The requant itself is dyadic_rne + clampi of common.h, unchanged: these tables are per tensor and may hold exact ties.
+// REQUANT also writes hawq4 rows (out_bits 4: values 0 .. 15, ldo and c_off in elements, 8 bytes per 16 channels) - the branch inputs
+// of the nibble conv kernels (incep_nib.hip); the entry points of inception.hip have no such form.
 #include "common.h"
 
 namespace {
@@ -53,6 +55,8 @@ __device__ __forceinline__ void store16(void *base, long long e, const int *v) {
     if (BITS == 16) {
         v4i *p = reinterpret_cast<v4i *>((int16_t *)base + e);
         p[0] = pack8_i16(v), p[1] = pack8_i16(v + 8);
+    } else if (BITS == 4) {   // hawq4 (values 0 .. 15, pool_v_refusal): two dwords at byte e / 2, e a multiple of 16
+        *reinterpret_cast<v2i *>((char *)base + (e >> 1)) = v2i{(int)pack8_u4(v), (int)pack8_u4(v + 8)};
     } else {
         v4i r;
 #pragma unroll
@@ -206,14 +210,16 @@ const char *pool_v_refusal(const hawq_incep_pool_args *a, int op) {
     if (op != HAWQ_INCEP_POOL_REQUANT && op != HAWQ_INCEP_POOL_MAX3S2 && op != HAWQ_INCEP_POOL_AVG3 && op != HAWQ_INCEP_POOL_GLOBAL)
         return "unknown op";
     if (a->N <= 0 || a->H <= 0 || a->W <= 0 || a->C <= 0 || (a->in_bits != 8 && a->in_bits != 16) ||
-        (a->out_bits != 8 && a->out_bits != 16))
+        (a->out_bits != 8 && a->out_bits != 16 && a->out_bits != 4))
         return "bad shape or widths";
+    if (a->out_bits == 4 && (op != HAWQ_INCEP_POOL_REQUANT || !a->post || a->lo2 < 0 || a->hi2 > 15 || a->lo2 > a->hi2))
+        return "out_bits 4 (hawq4 rows) is the REQUANT op's, with a post clamp inside 0 .. 15";
     if (a->in_off < 0 || a->in_pitch < (long long)a->in_off + a->C || a->c_off < 0 || a->ldo < (long long)a->c_off + a->C)
         return "channel slice outside its rows";
     if (a->C % 16 || a->in_pitch % 16 || a->in_off % 16 || a->ldo % 16 || a->c_off % 16)
         return "C, in_pitch, in_off, ldo and c_off must be multiples of 16";
     if (((uintptr_t)a->in | (uintptr_t)a->out) & 15) return "in and out must be 16-byte aligned";
-    const int lim = a->out_bits == 16 ? 32767 : 127;
+    const int lim = a->out_bits == 16 ? 32767 : 127;   // (out_bits 4 has passed the narrower test above)
     if (a->post && (a->lo2 < -lim - 1 || a->hi2 > lim || a->lo2 > a->hi2)) return "post clamp outside the store";
     if (a->pre && a->lo1 > a->hi1) return "bad pre clamp";
     if (!a->post && a->out_bits < a->in_bits) return "a narrowing store needs a post requant";
@@ -296,7 +302,11 @@ extern "C" int hawq_incep_pool_v(const hawq_incep_pool_args *a, int op, void *st
     const char *why = pool_v_refusal(a, op);
     HAWQ_REQUIRE(!why, "hawq_incep_pool_v (op %d): %s", op, why);
     hipStream_t s = (hipStream_t)stream;
-    if (a->in_bits == 16 && a->out_bits == 16) launch<16, 16>(a, op, s);
+    if (a->out_bits == 4) {   // REQUANT only (pool_v_refusal)
+        const unsigned items = (unsigned)((long long)a->N * a->H * a->W * (a->C / 16));
+        if (a->in_bits == 16) hipLaunchKernelGGL((pool_requant_v<16, 4>), dim3((items + 255) / 256), dim3(256), 0, s, *a, items);
+        else hipLaunchKernelGGL((pool_requant_v<8, 4>), dim3((items + 255) / 256), dim3(256), 0, s, *a, items);
+    } else if (a->in_bits == 16 && a->out_bits == 16) launch<16, 16>(a, op, s);
     else if (a->in_bits == 16) launch<16, 8>(a, op, s);
     else if (a->out_bits == 16) launch<8, 16>(a, op, s);
     else launch<8, 8>(a, op, s);

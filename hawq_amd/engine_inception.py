@@ -89,6 +89,23 @@ inner-concat requant produced part of the input (units 4, 9, 10), issues them on
 ``fan_out`` ignores the field.  ``fan_launches`` lists (unit, member conv indices, tile) per fan-out launch, ``residual_requants``
 (unit, record, in_off, C) per shortened entry requant.  Pool kernels, inner-concat requants, stem and head are untouched.  Not the
 default: at batch 1 - 16 the longer epilogue costs more than the launches it saves.
+
+Nibble operands.  ``InceptionEngine(model, nibble=True)`` stores 4-bit tensors and weights hawq4 and runs the convs that read them on
+``hawq_incep_conv_nib`` (hawq_amd/csrc/incep_nib.hip): the launch list keeps its length and order, the integers are the default plan's.
+``nibble_storage`` (a pure function) decides per tensor a conv reads: hawq4 if its values lie in 0 .. 15 (a 4-bit QuantAct behind a
+ReLU, or fed by such values through requants with m >= 0: ``_T.rng``), its producer can write nibbles - a branch-entry requant, issued
+as ``hawq_incep_pool_v`` with ``out_bits`` 4, or a conv that itself runs on the nibble kernel - and every conv that reads it is a
+4-bit x 4-bit conv the kernel takes; int8 otherwise (pool outputs, the stem, 8-bit layers).  A conv runs on the nibble kernel, on
+hawq4 weights, exactly when the tensor it reads is hawq4; the int8 form of such a tensor or weight is not kept.  Which convs:
+* neither ``tune`` nor ``plan``: every conv the policy allows, each on the first tile of ``_NIB_TILES`` the library takes;
+* ``tune=True``: after the int8 tiles every such conv is timed on every nibble tile it accepts, on the buffers of a forward of the
+  all-nibble plan, and counts as a nibble conv only if its fastest nibble tile beats its fastest int8 tile; the policy then runs
+  again, so a tensor falls back to int8 if any of its consumers does (``nibble_us`` has the times);
+* ``plan=`` with a ``"nibble"`` field: exactly its (conv, tile) pairs, StalePlan if the policy would not store those tensors or the
+  library refuses a tile; a plan without the field takes the untuned choice; an engine without ``nibble`` ignores the field.
+``nibble_convs`` maps conv launch -> nibble tile, ``nibble_tensors`` lists the hawq4 tensors, ``nibble_bytes`` the conv operand bytes
+(weights, activations) in int8 containers and in this plan.  It composes with ``fast_pools``, ``fused_stem`` and ``forward_uint8``;
+with ``grouped`` or ``fan_out``, and on a model without such a conv (uniform8), it raises ``PlanNotApplicable``.  Not the default.
 """
 from __future__ import annotations
 
@@ -151,7 +168,7 @@ def launch_digest(keys):
     return hashlib.sha256(json.dumps([list(map(int, k)) for k in keys], separators=(",", ":")).encode()).hexdigest()
 
 
-def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None):
+def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
     and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
     ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field, and with `fan_out`
@@ -165,6 +182,9 @@ def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None):
     if fan_out is not None:
         plan["fan_out"] = [{"unit": int(f["unit"]), "tiles": {str(k): int(t) for k, t in f["tiles"].items()},
                             "us": {str(k): round(float(v), 3) for k, v in f.get("us", {}).items()}} for f in fan_out]
+    if nibble is not None:   # a nibble engine's (conv -> nibble tile, conv -> {tile: microseconds})
+        plan["nibble"] = [[int(c), int(t)] for c, t in sorted(nibble[0].items())]
+        plan["nibble_us"] = {str(c): {str(t): round(float(v), 3) for t, v in d.items()} for c, d in sorted(nibble[1].items())}
     return plan
 
 
@@ -350,19 +370,45 @@ def check_fan_out(entries, candidates, ok):
 _FAN_TILES = (3, 2, 1, 4)   # an untuned fan-out launch: tile 3, else the first of these the library takes
 
 
-class _T:
-    """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale."""
+def nibble_storage(tensors, conv_ok):
+    """The storage policy of a nibble engine, a pure function.  `tensors`: every tensor a conv reads, in the order the plan makes
+    them, as ``(lo, hi, producer, consumers)`` - the range of its values, what writes it (``"requant"``: an entry requant, which
+    has a hawq4 form; ``("conv", i)``: conv i, which writes nibbles only on the nibble kernel; None: a pool or the image, int8
+    only) and the convs that read it; ``conv_ok[i]``: conv i is a 4-bit x 4-bit conv the nibble kernel takes (and, tuned, wins).
+    Returns the indices of the tensors stored hawq4: values inside 0 .. 15, a producer that can write nibbles, and every consumer
+    such a conv; every other tensor is int8.  A conv runs on the nibble kernel exactly when the tensor it reads is hawq4."""
+    src_of = {c: t for t, (_, _, _, cons) in enumerate(tensors) for c in cons}
+    nib = set()
+    for t, (lo, hi, prod, cons) in enumerate(tensors):
+        writes = prod == "requant" or (isinstance(prod, tuple) and src_of.get(prod[1]) in nib)
+        if lo >= 0 and hi <= 15 and writes and cons and all(conv_ok[c] for c in cons):
+            nib.add(t)
+    return nib
 
-    def __init__(self, buf, h, w, c, pitch, scale, bits):
+
+_NIB_TILES = (2, 1, 3)   # an untuned nibble launch: the first of these the library takes
+
+
+class _T:
+    """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale, container bits; the range `rng` of its
+    values where that is known to be narrower than the container, whether they are provably >= 0, and what `nibble_storage` asks:
+    the producer and the convs that read it."""
+
+    def __init__(self, buf, h, w, c, pitch, scale, bits, rng=None, nonneg=False, producer=None):
         self.buf, self.h, self.w, self.c, self.pitch, self.scale, self.bits = buf, h, w, c, pitch, scale, bits
+        lo, hi = rng or (-(1 << (bits - 1)), (1 << (bits - 1)) - 1)
+        self.rng, self.nonneg, self.producer, self.cons = (max(lo, 0) if nonneg else lo, hi), nonneg, producer, []
 
 
 class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
-                 fused_stem: bool = False, grouped: bool = False, fan_out: bool = False):
+                 fused_stem: bool = False, grouped: bool = False, fan_out: bool = False, nibble: bool = False):
         self.model, self.use_graph = model, use_graph
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
-        self.grouped, self.fan_out = bool(grouped), bool(fan_out)
+        self.grouped, self.fan_out, self.nibble = bool(grouped), bool(fan_out), bool(nibble)
+        if self.nibble and (self.grouped or self.fan_out):
+            raise PlanNotApplicable("nibble=True does not compose with grouped or fan_out: their launches have no nibble form")
+        self.nibble_convs, self.nibble_tensors, self.nibble_us, self.nibble_bytes = {}, [], {}, {}
         self.group_launches, self.group_candidates = [], []
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         self.n_timing_launches = 0           # conv launches issued to time tiles (0 for a default or a replayed plan)
@@ -426,8 +472,9 @@ class InceptionEngine(GraphRunner):
         a = _lib.IncepConvArgs()
         if dst is None:
             bits = 8 if act.activation_bit <= 8 else 16
+            # ReLU in front of a requant with m >= 0: the values are >= 0 whatever the clamp's lower bound says
             out = _T(self._zeros(self.N * Ho * Wo * cout_p, dtype=torch.int8 if bits == 8 else torch.int16, device=self.dev),
-                     Ho, Wo, Cout, cout_p, s_out, bits)
+                     Ho, Wo, Cout, cout_p, s_out, bits, rng=(lo, hi), nonneg=True, producer=("conv", len(self._convs)))
             a.epilogue, ldo = _lib.INCEP_REQUANT, cout_p
         else:
             if Cout % 16 or (dst.h, dst.w) != (Ho, Wo):
@@ -447,6 +494,11 @@ class InceptionEngine(GraphRunner):
         a.m, a.ek, a.q_lo, a.q_hi = t[2].data_ptr(), t[3].data_ptr(), lo, hi
         a.out_bits, a.ldo, a.c_off = out.bits, ldo, c_off
         self._keep += t + [a]
+        if src.buf is not None:   # what a nibble engine needs of this conv: the tensors on either side and its integer weights
+            if not src.cons:
+                self._tensors.append(src)
+            src.cons.append(len(self._convs))
+            self._conv_io[len(self._convs)] = (src, out if dst is None else None, w if self.nibble else None, t[0])
         self._emit("hawq_incep_conv", (a,), "conv", len(self._convs), level)
         return out
 
@@ -456,9 +508,10 @@ class InceptionEngine(GraphRunner):
             raise PlanNotApplicable("a 16-bit conv-branch input")
         s = _scale(act)
         out = _T(self._zeros(self.N * src.h * src.w * src.pitch, dtype=torch.int8, device=self.dev), src.h, src.w, src.c,
-                 src.pitch, s, 8)
+                 src.pitch, s, 8, rng=_rng(act), nonneg=src.nonneg, producer="requant")   # m >= 0: the sign is the source's
         self._pool("hawq_incep_requant", src, out.buf, 8, src.pitch, 0, src.pitch, src.h, src.w,
                    post=(*_scalar_table(src.scale, s), *_rng(act)))
+        out.record = self._launches[-1]
         return out
 
     def _unit(self, unit, src: _T):
@@ -488,7 +541,8 @@ class InceptionEngine(GraphRunner):
         cu = sum(widths)
         if cu % 16 or any(x % 16 for x in widths):
             raise PlanNotApplicable("channel counts must be multiples of 16")
-        dst = _T(self._zeros(self.N * Ho * Wo * cu, dtype=torch.int16, device=self.dev), Ho, Wo, cu, cu, s_u, 16)
+        # every slice is a conv's (ReLU) or a pool's of `src`, requantised with m >= 0
+        dst = _T(self._zeros(self.N * Ho * Wo * cu, dtype=torch.int16, device=self.dev), Ho, Wo, cu, cu, s_u, 16, nonneg=src.nonneg)
         off = 0
         for br, wd, cs in zip(branches, widths, mine):
             if isinstance(br, Q_MaxPoolBranch):
@@ -533,8 +587,10 @@ class InceptionEngine(GraphRunner):
             self.stream = torch.cuda.Stream(device=self.dev)
         self.N, dev, q = N, self.dev, self.model
         self._launches, self._convs, self._place = [], [], "stem"   # the records, the conv records among them, where `_emit` is
-        self._choice = (None, None, None)    # the default plan's: no tiles, no groups, no fan-out, the default order
+        self._choice = (None, None, None, None)    # the default plan's: no tiles, no groups, no fan-out, no nibbles, the default order
         self._ops, self._keep, self.unit_out = [], [], {}
+        self._tensors, self._conv_io = [], {}   # the tensors convs read, in the order they are made; conv -> (src, out, weights)
+        self.nibble_convs, self.nibble_tensors, self.nibble_us, self.nibble_bytes = {}, [], {}, {}
         self.conv_tiles, self.conv_us = None, None
         self.group_launches, self.group_candidates = [], []
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
@@ -558,7 +614,8 @@ class InceptionEngine(GraphRunner):
         for name in ("q_conv1", "q_conv2", "q_conv3", "q_pool1", "q_conv4", "q_conv5", "q_pool2"):
             if name.startswith("q_pool"):
                 h, w = (x.h - 3) // 2 + 1, (x.w - 3) // 2 + 1
-                y = _T(self._zeros(N * h * w * x.pitch, dtype=x.buf.dtype, device=dev), h, w, x.c, x.pitch, x.scale, x.bits)
+                y = _T(self._zeros(N * h * w * x.pitch, dtype=x.buf.dtype, device=dev), h, w, x.c, x.pitch, x.scale, x.bits,
+                       nonneg=x.nonneg)
                 self._pool("hawq_incep_maxpool3s2", x, y.buf, x.bits, x.pitch, 0, x.pitch, x.h, x.w)
                 x = y
             else:
@@ -726,7 +783,127 @@ class InceptionEngine(GraphRunner):
         elif self.grouped:
             groups = [(c, 3) for c in cands if self._group_ok(c, 3)]
         self.conv_tiles = None if tiles is None else [int(t) for t in tiles]
-        return self.conv_tiles, groups, self._choose_fans(self.conv_tiles, groups) if self.fan_out else None
+        nib = self._choose_nibbles(T) if self.nibble else None
+        return self.conv_tiles, groups, self._choose_fans(self.conv_tiles, groups) if self.fan_out else None, nib
+
+    # ------------------------------------------------------------------ nibbles
+    def _nib_ok(self, c, tile, block=None):
+        return isinstance(tile, int) and not isinstance(tile, bool) and \
+            bool(_lib.load().hawq_incep_conv_nib_ok(C.byref(block or self._convs[c].args[0]), tile))
+
+    def _nib_table(self):
+        """`nibble_storage`'s view of the plan: one row per tensor of ``_tensors``; an entry requant is a producer of nibbles if
+        ``hawq_incep_pool_v`` takes its launch with ``out_bits`` 4"""
+        def writes(t):
+            if t.producer != "requant":
+                return t.producer
+            p = _lib.IncepPoolArgs.from_buffer_copy(t.record.args[0])
+            p.out_bits, (p.lo2, p.hi2) = 4, t.rng
+            return "requant" if _lib.load().hawq_incep_pool_v_ok(C.byref(p), t.record.ref) else None
+        return [(*t.rng, writes(t), list(t.cons)) for t in self._tensors]
+
+    def _nib_blocks(self, tensors):
+        """The argument blocks of a plan that stores `tensors` (indices into ``_tensors``) hawq4: conv -> its block on
+        ``hawq_incep_conv_nib`` for every conv that reads one of them, entry requant record -> its ``out_bits`` 4 block.  Same
+        tables, same clamps - the lower bound 0 where the values are >= 0 anyway (``_T.rng``) -; hawq4 buffers and weights are made
+        once per tensor and conv (``_nib_buf``, ``_nib_w``)."""
+        from .packing import pack_hawq4
+        convs, pools = {}, {}
+        for ti in tensors:
+            t = self._tensors[ti]
+            if ti not in self._nib_buf:
+                self._nib_buf[ti] = torch.zeros(self.N * t.h * t.w * t.pitch // 2, dtype=torch.uint8, device=self.dev)
+        for ti in tensors:
+            t = self._tensors[ti]
+            if t.producer == "requant":
+                p = _lib.IncepPoolArgs.from_buffer_copy(t.record.args[0])
+                p.out, p.out_bits, (p.lo2, p.hi2) = self._nib_buf[ti].data_ptr(), 4, t.rng
+                pools[t.record] = p
+            for c in t.cons:
+                _, out, w, _ = self._conv_io[c]
+                if c not in self._nib_w:
+                    self._nib_w[c] = torch.from_numpy(pack_hawq4(w).reshape(-1)).to(self.dev)
+                a = _lib.IncepConvArgs.from_buffer_copy(self._convs[c].args[0])
+                a.in_, a.wgt = self._nib_buf[ti].data_ptr(), self._nib_w[c].data_ptr()
+                if out is not None and out.cons and self._tensors.index(out) in tensors:
+                    a.out, a.out_bits, (a.q_lo, a.q_hi) = self._nib_buf[self._tensors.index(out)].data_ptr(), 4, out.rng
+                convs[c] = a
+        return convs, pools
+
+    def _choose_nibbles(self, T):
+        """The fourth component of the choice, {conv: nibble tile}: the convs `nibble_storage` puts on the nibble kernel, given which
+        convs are 4-bit x 4-bit and taken by it - all of them (each on the first tile of ``_NIB_TILES`` it accepts), those that
+        beat their best int8 tile when timed (``tune``), or those a plan's ``"nibble"`` field names.  Leaves ``nibble_convs``,
+        ``nibble_tensors``, ``nibble_us``, ``nibble_bytes`` and the blocks the writer issues, and frees what the choice leaves
+        unused: the int8 form of a hawq4 tensor or weight, and the hawq4 form of everything else."""
+        NT = _lib.load().hawq_incep_conv_nib_num_tiles()
+        self._nib_buf, self._nib_w = {}, {}
+        w4 = {c: w is not None and w.size and int(w.min()) >= -8 and int(w.max()) <= 7 for c, (_, _, w, _) in self._conv_io.items()}
+        tiles_of = {c: [t for t in range(1, NT + 1) if w4.get(c) and self._nib_ok(c, t)] for c in range(len(self._convs))}
+        table, able = self._nib_table(), [bool(tiles_of[c]) for c in range(len(self._convs))]
+        cand = nibble_storage(table, able)
+        if not cand:
+            raise PlanNotApplicable("nibble: no conv of this model reads 4-bit values with 4-bit weights from a tensor that can be "
+                                    "stored hawq4 (a uniform8 schedule has none)")
+        convs_of = lambda ts: sorted(c for ti in ts for c in self._tensors[ti].cons)   # noqa: E731
+        if self.plan is not None and "nibble" in self.plan:
+            try:
+                tile = {int(c): t for c, t in self.plan["nibble"]}
+            except (TypeError, ValueError) as exc:
+                raise StalePlan(f"not a list of (conv, nibble tile): {exc!r}") from exc
+            if any(c not in tiles_of or t not in tiles_of[c] for c, t in tile.items()):
+                raise StalePlan("nibble: a conv or tile of the plan is refused")
+            chosen = nibble_storage(table, [c in tile for c in range(len(self._convs))])
+            if convs_of(chosen) != sorted(tile):
+                raise StalePlan("nibble: the plan's convs are not what the storage policy makes of them")
+            self.nibble_us = {int(c): dict(d) for c, d in self.plan.get("nibble_us", {}).items()}
+        elif self.tune and self.plan is None:
+            self.nibble_us = self._time_nibbles(cand, tiles_of)
+            best = {c: min(us, key=lambda t: (us[t], t)) for c, us in self.nibble_us.items()}
+            wins = [c in best and self.nibble_us[c][best[c]] < self.conv_us[c][self.conv_tiles[c]] for c in range(len(self._convs))]
+            chosen = nibble_storage(table, wins)
+            tile = {c: best[c] for c in convs_of(chosen)}
+        else:
+            chosen = cand
+            tile = {c: next(t for t in _NIB_TILES if t in tiles_of[c]) for c in convs_of(chosen)}
+        self._nib_conv, self._nib_pool = self._nib_blocks(chosen)
+        self.nibble_convs, self.nibble_tensors = tile, sorted(chosen)
+        # bytes of the conv operands, int8 containers against this plan, and the buffers each form no longer needs
+        wb = sum(io[3].numel() for io in self._conv_io.values())
+        ab = sum(t.buf.numel() * t.buf.element_size() for t in self._tensors)
+        dead = {id(self._conv_io[c][3]) for c in tile} | {id(self._tensors[ti].buf) for ti in chosen}
+        self.nibble_bytes = {"weights": (wb, wb - sum(self._conv_io[c][3].numel() // 2 for c in tile)),
+                             "activations": (ab, ab - sum(self._tensors[ti].buf.numel() // 2 for ti in chosen))}
+        self._keep = [x for x in self._keep if id(x) not in dead]
+        self._keep += [self._nib_buf[ti] for ti in chosen] + [self._nib_w[c] for c in tile]
+        self._keep += list(self._nib_conv.values()) + list(self._nib_pool.values())
+        for ti in chosen:
+            self._tensors[ti].buf = self._nib_buf[ti]
+        del self._nib_buf, self._nib_w
+        return tile
+
+    def _time_nibbles(self, cand, tiles_of):
+        """Microseconds of every candidate conv on every nibble tile it accepts, as ``_time`` measures the int8 tiles: on the
+        buffers of a forward of the plan that stores every tensor of `cand` hawq4."""
+        sp = self.stream.cuda_stream
+        self._nib_conv, self._nib_pool = self._nib_blocks(cand)
+        convs = sorted(self._nib_conv)
+        self._choice = (None, None, None, {c: tiles_of[c][0] for c in convs})
+        out = {}
+        with EventTimer(sp, _TUNE_REPS + 1) as ev:
+            torch.cuda.synchronize(self.dev)
+            with torch.cuda.stream(self.stream):
+                for op in self._write():
+                    op()
+                for c in convs:
+                    a = self._nib_conv[c]
+                    tiles = [t for t in tiles_of[c] if self._nib_ok(c, t, a)]
+                    self.n_timing_launches += (_TUNE_WARMUP + _TUNE_REPS) * len(tiles)
+                    out[c] = {t: ev.median_us(lambda: _lib.call("hawq_incep_conv_nib", C.byref(a), t, sp), _TUNE_REPS, _TUNE_WARMUP)
+                              for t in tiles}
+        torch.cuda.synchronize(self.dev)
+        self._choice = (None, None, None, None)
+        return out
 
     def _choose_fans(self, tiles, groups):
         """the third component: from the plan's ``"fan_out"`` field if it has one, else timed against the plain launches (``tune``),
@@ -830,7 +1007,7 @@ class InceptionEngine(GraphRunner):
         groups = [g for g in self.group_candidates if g["kept"]] if self.grouped else None
         fans = [f for f in self.fan_candidates if f["kept"]] if self.fan_out else None
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
-                         groups, fans)
+                         groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None)
 
     # ------------------------------------------------------------------ the writer
     def _write(self, u8=False):
@@ -840,7 +1017,7 @@ class InceptionEngine(GraphRunner):
         as one ``hawq_incep_stem_f32`` (``fused_stem``) or, for the uint8 chain, as one ``hawq_incep_stem_u8`` in front of the fp32
         chain's own callables.  The records' order, or with groups ``grouped_order``.  The fp32 chain leaves ``_at`` (record -> index
         of the launch that covers it) and ``group_launches``."""
-        tiles, groups, fans = self._choice
+        tiles, groups, fans, nib = self._choice
         lib, sp, launches = _lib.load(), self.stream.cuda_stream, self._launches
         fan_of = {s: (b, t) for b, by_set in fans or [] for s, t in by_set.items()}           # producer launch -> its boundary, tile
         entry = {i: b for b, _ in fans or [] for i in b["requants"]}                          # entry requant record -> its boundary
@@ -851,6 +1028,10 @@ class InceptionEngine(GraphRunner):
         def single(r):
             if r.kind == "other":
                 return op(r.name, *r.args)
+            if nib and r.kind == "conv" and r.ref in nib:   # hawq4 operands: the nibble kernel, on its own block
+                return op("hawq_incep_conv_nib", C.byref(self._nib_conv[r.ref]), int(nib[r.ref]))
+            if nib and r in self._nib_pool:   # an entry requant that writes hawq4: only the vectorised family has that form
+                return op("hawq_incep_pool_v", C.byref(self._nib_pool[r]), r.ref)
             a = C.byref(r.args[0])
             if r.kind == "conv":
                 return op(r.name, a) if tiles is None else op("hawq_incep_conv_tiled", a, int(tiles[r.ref]))

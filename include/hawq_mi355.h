@@ -560,6 +560,25 @@ int hawq_incep_conv(const hawq_incep_conv_args *a, void *stream);
 int hawq_incep_conv_num_tiles(void);
 int hawq_incep_conv_tile_ok(const hawq_incep_conv_args *a, int tile);
 int hawq_incep_conv_tiled(const hawq_incep_conv_args *a, int tile, void *stream);
+/* The same launch on nibble-packed operands (incep_nib.hip), on the same argument block:
+ *   in:   UNSIGNED 4-bit activations (0 .. 15), hawq4 NHWC rows: Cin / 2 bytes per pixel
+ *   wgt:  signed 4-bit weights (-8 .. 7), hawq4 [Cout][KH][KW][Cin] (hawq_amd.packing.pack_conv_weight(..., w_bits=4))
+ *   out:  as hawq_incep_conv; REQUANT / REQUANT2 also take out_bits 4: hawq4 rows of ldo elements (ldo / 2 bytes), clamp bounds
+ *         inside 0 .. 15.  ldo and c_off count elements for every width.
+ * Both operands stay packed through LDS and are widened to int8x4 MFMA operands in registers (weights as 16 w, the accumulator
+ * shifted right by 4 in front of the bias); every tile computes, integer for integer, what hawq_incep_conv computes for the same
+ * values in int8 containers.
+ *   hawq_incep_conv_nib_num_tiles: T; tile ids 1 .. T exist (1: 128 px x 128 ch, 2: 128 x 64, 3: 64 x 64 with the K steps split
+ *       between two wave sets).  There is no id 0.
+ *   hawq_incep_conv_nib_ok:  1 if that tile takes this launch.  Host arithmetic on the argument block only: no pointer is
+ *       dereferenced, nothing is launched, no device is needed.  It needs what hawq_incep_conv needs of the shape, and out, in, wgt
+ *       16-byte aligned; ldo and c_off multiples of 16; KH * KW * Cin <= 1118481 (16 * 15 * 8 * K fits int32 for every weight
+ *       tensor); out_bits 4, 8 or 16 under REQUANT / REQUANT2 and not 4 under RAW; tile 1 Cout > 64; tile 3 KH * KW * Cin >= 512.
+ *   hawq_incep_conv_nib:     the launch.  A refused block returns an error (the reason in hawq_last_error()), launches nothing and
+ *       writes no byte of out. */
+int hawq_incep_conv_nib_num_tiles(void);
+int hawq_incep_conv_nib_ok(const hawq_incep_conv_args *a, int tile);
+int hawq_incep_conv_nib(const hawq_incep_conv_args *a, int tile, void *stream);
 /* Grouped launch of the tiled kernels (incep_group.hip): up to HAWQ_INCEP_GROUP_MAX independent convs - the sibling convs at one depth
  * of an Inception unit's branches - in ONE launch.  Members keep their own argument blocks and may differ in everything a block holds;
  * only the grid is shared: a 1-D grid in which member i owns ceil(P_i / BM) * ceil(Cout_i / BN) consecutive workgroups of tile `tile`
@@ -663,6 +682,8 @@ int hawq_incep_global_avgpool(const hawq_incep_pool_args *a, void *stream);
  *   MAX3S2 with pre: m1 >= 0, k = 0, e1 >= in_bits (pre is then monotone, so it commutes with the max);
  *   AVG3 with pre:   lo1, hi1 inside int16 (the staged tile is int16);
  *   GLOBAL:          100 * H * W * max|summand| + H * W < 2^31 (int32 average rule).
+ * REQUANT also takes out_bits 4 here (and only here): hawq4 rows of ldo elements, with a post clamp inside 0 .. 15 - the branch
+ * inputs of hawq_incep_conv_nib.
  * On a refused description hawq_incep_pool_v returns non-zero, sets hawq_last_error() and launches nothing. */
 enum { HAWQ_INCEP_POOL_REQUANT = 0, HAWQ_INCEP_POOL_MAX3S2 = 1, HAWQ_INCEP_POOL_AVG3 = 2, HAWQ_INCEP_POOL_GLOBAL = 3 };
 int hawq_incep_pool_v_ok(const hawq_incep_pool_args *a, int op);

@@ -47,6 +47,7 @@ producer launches + residual requants, in microseconds, kept or not.
     python tools/inception_bench.py --fused-stem [--tune --pools] --batches 128,1 --stem-launches 20
     python tools/inception_bench.py --grouped --batches 1,16,128 [--blocks 6]
     python tools/inception_bench.py --fan-out [--grouped] --batches 1,16,128 [--blocks 6]
+    python tools/inception_bench.py --nibble [--pools] --scheme uniform4 --batches 1,128 [--blocks 6]
 """
 import argparse
 import json
@@ -418,6 +419,47 @@ def compare_fan_out(model, args, b):
     return fan
 
 
+def compare_nibble(model, args, b):
+    """the default plan, the plan on tuned int8 tiles, and both with nibble=True (every hawq4 tensor the storage policy allows; the
+    ones whose convs beat their best int8 tile), alternating blocks; the per-launch times the tuner saw and the operand bytes of the
+    plan before and after; returns the tuned nibble engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    with torch.no_grad():
+        opts = dict(fast_pools=args.pools)   # --pools: every engine on the vectorised pool kernels, which a nibble engine's hawq4
+        engines = {"default": InceptionEngine(model, **opts), "nibble": InceptionEngine(model, nibble=True, **opts),   # requants use anyway
+                   "tuned": InceptionEngine(model, tune=True, **opts), "nibble_tuned": InceptionEngine(model, nibble=True, tune=True, **opts)}
+        y = {k: e(x) for k, e in engines.items()}
+        equal = all(bool(torch.equal(v, y["default"])) for v in y.values())
+        assert equal, "the logits on nibble operands differ from the default plan's"
+        nt = engines["nibble_tuned"]
+        print(f"# {wl}: conv launch | key | best int8 tile us | nibble tile us | kept")
+        for c, us in sorted(nt.nibble_us.items()):
+            i8 = nt.conv_us[c][nt.conv_tiles[c]]
+            print(f"# {c:2d} | {nt.conv_launches[c]} | {nt.conv_tiles[c]}: {i8:.1f} | " + " ".join(f"{t}: {v:.1f}" for t, v in us.items()) +
+                  f" | {'nibble' if c in nt.nibble_convs else 'int8'}")
+        for k in ("nibble", "nibble_tuned"):
+            e = engines[k]
+            print(json.dumps({"workload": wl, "plan": k, "nibble_convs": len(e.nibble_convs), "hawq4_tensors": len(e.nibble_tensors),
+                              "weight_bytes": e.nibble_bytes["weights"], "activation_bytes": e.nibble_bytes["activations"]}), flush=True)
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": k, "fast_pools": bool(args.pools), "ms_per_batch": round(mean, 4),
+                              "images_per_s": round(b * 1000.0 / mean, 1), "block_min_ms": round(min(v), 4),
+                              "block_max_ms": round(max(v), 4), "blocks": len(v), "steps": args.steps, "launches": e.n_launches,
+                              "logits_bit_equal": equal}), flush=True)
+    return nt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheme", default="uniform8")
@@ -438,18 +480,20 @@ def main():
                     help="compare one tuned plan (fast pools, fused stem) without and with grouped conv launches")
     ap.add_argument("--fan-out", action="store_true",
                     help="compare one recorded plan (fast pools, fused stem; grouped with --grouped) without and with fan-out conv epilogues")
-    ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out: write export_plan() of the last batch size to this file")
+    ap.add_argument("--nibble", action="store_true",
+                    help="compare the default and the tuned plan (uniform4) without and with nibble-packed conv operands")
+    ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out / --nibble: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
-    if args.save_plan and not (args.tune or args.plan or args.grouped or args.fan_out):
-        ap.error("--save-plan needs --tune, --plan, --grouped or --fan-out: there is no conv tile plan to save otherwise")
+    if args.save_plan and not (args.tune or args.plan or args.grouped or args.fan_out or args.nibble):
+        ap.error("--save-plan needs --tune, --plan, --grouped, --fan-out or --nibble: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
     for b in (int(v) for v in args.batches.split(",")):
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.fan_out or args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
-            compare = compare_fan_out if args.fan_out else compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
+        if args.nibble or args.fan_out or args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
+            compare = compare_nibble if args.nibble else compare_fan_out if args.fan_out else compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
             tuned = compare(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
