@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("HAWQ_LIB") or os.path.join(_HERE, "lib", "libhawq_mi3
 
 EPI_RAW, EPI_REQUANT, EPI_RESIDUAL, EPI_DEQUANT = 0, 1, 2, 3
 
-i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
+i32, u32, i64, f32, vp = C.c_int32, C.c_uint32, C.c_int64, C.c_float, C.c_void_p
 
 
 class ConvArgs(C.Structure):
@@ -278,6 +278,9 @@ SIGNATURES = {
     "hawq_incep_conv_nib": [C.POINTER(IncepConvArgs), i32, vp],
     "hawq_incep_conv_group_ok": [C.POINTER(IncepGroupArgs), i32],
     "hawq_incep_conv_group": [C.POINTER(IncepGroupArgs), i32, vp],
+    "hawq_incep_conv_group_nib_num_tiles": [],
+    "hawq_incep_conv_group_nib_ok": [C.POINTER(IncepGroupArgs), u32, i32],
+    "hawq_incep_conv_group_nib": [C.POINTER(IncepGroupArgs), u32, i32, vp],
     "hawq_incep_conv_group_fan_ok": [C.POINTER(IncepGroupArgs), C.POINTER(IncepFan), i32],
     "hawq_incep_conv_group_fan": [C.POINTER(IncepGroupArgs), C.POINTER(IncepFan), i32, vp],
     "hawq_incep_stem_u8": [vp, vp, C.POINTER(IncepConvArgs), vp],

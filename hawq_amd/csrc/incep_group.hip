@@ -41,22 +41,7 @@ const char *group_refusal(const hawq_incep_group_args *g, int tile, GroupGrid *g
     if (g->n < 1 || g->n > HAWQ_INCEP_GROUP_MAX) return "a group has 1 .. 8 members";
     if (tile < 1 || tile > NUM_TILES) return "no such tile (a group runs on one of the ids 1 .. 4)";
     if (const char *why = group_grid(g, tile, gg, who)) return why;
-    const Span *in = gg->in, *out = gg->out;
-    for (int i = 0; i < g->n; ++i) {
-        const hawq_incep_conv_args *a = &g->conv[i];
-        *who = i;
-        for (int j = 0; j < g->n; ++j) {
-            const hawq_incep_conv_args *b = &g->conv[j];
-            if (meet(in[i], out[j])) return "a member reads what a member of the group writes";
-            if (j <= i) continue;
-            const bool rows = a->out == b->out && a->ldo == b->ldo && a->out_bits == b->out_bits &&
-                              (a->epilogue == HAWQ_INCEP_RAW) == (b->epilogue == HAWQ_INCEP_RAW);   // slices of one concat buffer
-            if (rows ? (a->c_off < b->c_off + b->Cout && b->c_off < a->c_off + a->Cout) : meet(out[i], out[j]))
-                return "two members write overlapping outputs";
-        }
-    }
-    *who = -1;
-    return nullptr;
+    return group_dependence(g, gg, who);
 }
 
 template <class T>

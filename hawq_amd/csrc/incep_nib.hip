@@ -34,7 +34,7 @@
 //
 // Weight rows are staged in cperm order (LDS row q of a 32-row group holds channel cperm(q)), so lane half h ends up with the 16
 // consecutive channels 16 h .. 16 h + 15 of one pixel - one 8-byte store of hawq4, 16 bytes of int8, 32 of int16, 64 of int32.
-#include "common.h"
+#include "incep_nib.h"
 
 namespace {
 
@@ -50,199 +50,16 @@ constexpr NibShape kNib[NUM_NIB_TILES + 1] = {{0, 0}, {128, 128}, {128, 64}, {64
 // 16 (weights as nibble << 4) * 15 * 8 * K <= 2^31 - 1
 constexpr long long NIB_K_MAX = ((1ll << 31) - 1) / (16 * 15 * 8);
 
-constexpr int NIB_LO = 0x0f0f0f0f, NIB_HI = (int)0xf0f0f0f0u;
-// one unit (dwords d0, d1 = channels 0 - 7, 8 - 15) -> the 16 int8 of an MFMA operand, in channel order
-__device__ __forceinline__ v4i widen_act(int d0, int d1) {
-    return v4i{d0 & NIB_LO, (int)((unsigned)d0 >> 4) & NIB_LO, d1 & NIB_LO, (int)((unsigned)d1 >> 4) & NIB_LO};
-}
-// 16 w per byte
-__device__ __forceinline__ v4i widen_wgt(int d0, int d1) { return v4i{(d0 << 4) & NIB_HI, d0 & NIB_HI, (d1 << 4) & NIB_HI, d1 & NIB_HI}; }
-
+// the body (incep_nib_body.h, shared as text with incep_group_nib.hip) on the workgroup's block of a 2-D grid: pixel blocks in x,
+// channel blocks in y
 template <int BM, int BN, int WPX, int WCH, int KS>
 __global__ __launch_bounds__(64 * WPX * WCH * KS) void incep_nib_kernel(hawq_incep_conv_args a, int Ho, int Wo) {
-    constexpr int NT = 64 * WPX * WCH * KS, RSTEP = NT / 8;
-    constexpr int WM = BM / WPX / 32, WN = BN / WCH / 32;
-    constexpr int APT = BM / RSTEP, BPT = BN / RSTEP, RPT = APT + BPT;
-    constexpr int STAGE = (BM + BN) * 64;
-    static_assert(BM % RSTEP == 0 && BN % RSTEP == 0 && BM % (32 * WPX) == 0 && BN % (32 * WCH) == 0, "tile shape");
-    static_assert(KS == 1 || (KS == 2 && WM * WN * 16 * 64 * 4 * WPX * WCH <= 2 * STAGE), "K-split reduction must fit the stages");
-    __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
-    const int wk = wave / (WPX * WCH), wr = wave % (WPX * WCH), wpx = wr % WPX, wch = wr / WPX;
-    const int unit = tid & 7, r0 = tid >> 3;
-    const long long P = (long long)a.N * Ho * Wo, pblock = (long long)blockIdx.x * BM;
+    __shared__ __attribute__((aligned(16))) char lds[2 * (BM + BN) * 64];
+#define INCEP_NIB_BLOCK                                  \
+    const long long pblock = (long long)blockIdx.x * BM; \
     const int cblock = blockIdx.y * BN;
-    const int C16 = a.Cin >> 4, K16 = a.KH * a.KW * C16, steps = (K16 + 7) >> 3;
-    const size_t pix_bytes = (size_t)a.Cin >> 1;
-    const char *in = (const char *)a.in, *wgt = (const char *)a.wgt;
-
-    // the rows this thread stages
-    const char *abase[APT];
-    int iy0[APT], ix0[APT];
-#pragma unroll
-    for (int i = 0; i < APT; ++i) {
-        const long long p = pblock + r0 + i * RSTEP;
-        abase[i] = in, iy0[i] = -(1 << 20), ix0[i] = 0;   // a row beyond P: every tap fails the bounds test below
-        if (p < P) {
-            const int ox = (int)(p % Wo), oy = (int)((p / Wo) % Ho);
-            abase[i] = in + (size_t)(p / ((long long)Wo * Ho)) * a.H * a.W * pix_bytes;
-            iy0[i] = oy * a.stride - a.pad_h, ix0[i] = ox * a.stride - a.pad_w;
-        }
-    }
-    const char *wrow[BPT];
-    bool wv[BPT];
-#pragma unroll
-    for (int j = 0; j < BPT; ++j) {
-        const int q = r0 + j * RSTEP, co = cblock + (q & ~31) + cperm(q & 31);
-        wv[j] = co < a.Cout;
-        wrow[j] = wgt + (wv[j] ? (size_t)co * K16 * 8 : 0);
-    }
-    // this thread's unit of the step to load next
-    int k16 = unit, c16 = k16 % C16, kw = (k16 / C16) % a.KW, kh = (k16 / C16) / a.KW;
-
-    v2i rg[RPT];
-    bool ok[RPT];
-    const v2i zero = {0, 0};
-    // loads are unconditional (a refused unit reads the first 8 bytes of its operand) and zeroed when they are written to LDS
-    auto load = [&]() {
-        const bool kv = k16 < K16;
-#pragma unroll
-        for (int i = 0; i < APT; ++i) {
-            const int iy = iy0[i] + kh, ix = ix0[i] + kw;
-            ok[i] = kv && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            const size_t off = ok[i] ? ((size_t)iy * a.W + ix) * pix_bytes + c16 * 8 : 0;
-            rg[i] = *reinterpret_cast<const v2i *>((ok[i] ? abase[i] : in) + off);
-        }
-#pragma unroll
-        for (int j = 0; j < BPT; ++j) {
-            ok[APT + j] = kv && wv[j];
-            rg[APT + j] = *reinterpret_cast<const v2i *>(wrow[j] + (ok[APT + j] ? (size_t)k16 * 8 : 0));
-        }
-        k16 += 8, c16 += 8;
-        while (c16 >= C16) {
-            c16 -= C16;
-            if (++kw == a.KW) kw = 0, ++kh;
-        }
-    };
-    auto write = [&](int stage) {
-        char *s = lds + stage * STAGE;
-#pragma unroll
-        for (int i = 0; i < RPT; ++i) {
-            *reinterpret_cast<v2i *>(s + lds_off(r0 + i * RSTEP, unit >> 1) + 8 * (unit & 1)) = ok[i] ? rg[i] : zero;
-        }
-    };
-
-    v16i acc[WM][WN];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
-
-    auto compute = [&](int stage) {
-        const char *s = lds + stage * STAGE;
-#pragma unroll
-        for (int t = 0; t < 2 / KS; ++t) {
-            const int tt = KS == 2 ? wk : t;   // the 32-byte half of the row
-            v4i af[WM], bf[WN];
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-                af[i] = *reinterpret_cast<const v4i *>(s + lds_off(wpx * 32 * WM + 32 * i + l31, 2 * tt + h));
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-                bf[j] = *reinterpret_cast<const v4i *>(s + lds_off(BM + wch * 32 * WN + 32 * j + l31, 2 * tt + h));
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {   // the even unit of every lane's slot, then the odd one
-                v4i wa[WM], wb[WN];
-#pragma unroll
-                for (int i = 0; i < WM; ++i) wa[i] = widen_act(af[i][2 * u], af[i][2 * u + 1]);
-#pragma unroll
-                for (int j = 0; j < WN; ++j) wb[j] = widen_wgt(bf[j][2 * u], bf[j][2 * u + 1]);
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wb[j], wa[i], acc[i][j], 0, 0, 0);
-            }
-        }
-    };
-
-    load();
-    write(0);
-    __syncthreads();
-    for (int s = 0; s < steps; ++s) {
-        const bool more = s + 1 < steps;
-        if (more) load();          // in flight under the MFMAs of step s
-        compute(s & 1);
-        if (more) write((s + 1) & 1);   // the other stage: last read in step s - 1, before the barrier that ended it
-        __syncthreads();
-    }
-
-    if (KS == 2) {   // every wave is past the last barrier: the stages are free
-        int *red = reinterpret_cast<int *>(lds);
-        if (wk == 1) {
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) red[(((i * WN + j) * 16 + r) * (WPX * WCH) + wr) * 64 + lane] = acc[i][j][r];
-        }
-        __syncthreads();
-        if (wk == 1) return;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] += red[(((i * WN + j) * 16 + r) * (WPX * WCH) + wr) * 64 + lane];
-    }
-
-    // acc[i][j][r] = 16 x channel cblock + 32 (wch WN + j) + 16 h + r of pixel pblock + 32 (wpx WM + i) + l31
-#pragma unroll
-    for (int i = 0; i < WM; ++i) {
-        const long long p = pblock + 32 * (wpx * WM + i) + l31;
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const int cb = cblock + 32 * (wch * WN + j) + 16 * h;
-            if (p >= P || cb >= a.Cout) continue;   // Cout % 16 == 0: the 16 channels of a lane half are all valid or all not
-            const size_t row = (size_t)p * a.ldo + a.c_off + cb;   // a multiple of 16 elements (hawq_incep_conv_nib_ok)
-            int q[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) q[r] = (acc[i][j][r] >> 4) + a.bias[cb + r];   // the sum is an exact multiple of 16
-            if (a.epilogue == HAWQ_INCEP_RAW) {
-                v4i *o = reinterpret_cast<v4i *>((int32_t *)a.out + row);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = v4i{q[4 * r], q[4 * r + 1], q[4 * r + 2], q[4 * r + 3]};
-                continue;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = cb + r;
-                if (a.relu) q[r] = max(q[r], 0);
-                q[r] = clampi(dyadic_rne(q[r], a.m[co], a.ek[co]), a.q_lo, a.q_hi);
-                if (a.epilogue == HAWQ_INCEP_REQUANT2) q[r] = clampi(dyadic_rne(q[r], a.m2, a.ek2), a.q2_lo, a.q2_hi);
-            }
-            if (a.out_bits == 16) {
-                v4i *o = reinterpret_cast<v4i *>((int16_t *)a.out + row);
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    v4i d;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) d[e] = (q[8 * r + 2 * e] & 0xffff) | (int)((unsigned)q[8 * r + 2 * e + 1] << 16);
-                    o[r] = d;
-                }
-            } else if (a.out_bits == 8) {
-                v4i d;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = (int)pack4_i8(q[4 * e], q[4 * e + 1], q[4 * e + 2], q[4 * e + 3]);
-                *reinterpret_cast<v4i *>((int8_t *)a.out + row) = d;
-            } else {   // hawq4: 16 channels = two dwords at byte row / 2
-                *reinterpret_cast<v2i *>((char *)a.out + (row >> 1)) = v2i{(int)pack8_u4(q), (int)pack8_u4(q + 8)};
-            }
-        }
-    }
+#include "incep_nib_body.h"
+#undef INCEP_NIB_BLOCK
 }
 
 struct Geo {

@@ -2,7 +2,8 @@
 // on one grid, incep_fan.hip: the grouped launch with a fan-out epilogue):
 //   the tile table and the one place that names each tile's template constants (for_tile)
 //   the workgroup body, in incep_tile_body.h
-//   the grouped launches' grid: GroupMap, the workgroup's member (group_member), the host's layout of it (group_grid)
+//   the grouped launches' grid: GroupMap, the workgroup's member (group_member), the host's layout of it (group_grid) and the test
+//   that its members are independent (group_dependence) - these also serve incep_group_nib.hip, whose members may read hawq4
 //
 // The body is shared as text: each kernel file includes incep_tile_body.h inside its own function template, so every translation
 // unit compiles the token stream it would compile with the body written out, and no kernel's code depends on the sharing.  As one
@@ -84,30 +85,62 @@ struct GroupGrid {
     Span in[HAWQ_INCEP_GROUP_MAX], out[HAWQ_INCEP_GROUP_MAX];
 };
 
-// lays the members of `g` (n in 1 .. 8) out on a grid of tile `tile` (1 .. NUM_TILES); a reason and the member `who` where that
-// cannot be done (NULL: `gg` is filled).  No pointer is dereferenced.
-const char *group_grid(const hawq_incep_group_args *g, int tile, GroupGrid *gg, int *who) {
-    const int bm = kTiles[tile].bm, bn = kTiles[tile].bn;
+// lays the members of `g` (n in 1 .. 8) out on a grid of bm px x bn ch workgroups; a reason and the member `who` where that cannot
+// be done (NULL: `gg` is filled).  `refuses(i, a)`: why the kernel does not take member i (NULL: it does; it has then checked the
+// block's shape, so that npb < 2^31).  Bit i of `nib`: member i reads hawq4 rows, Cin / 2 bytes a pixel.  Extents are in bytes,
+// worked out in half bytes: an out_bits 4 element is one, and c_off and Cout are even.  No pointer is dereferenced.
+template <class R>
+const char *group_grid(const hawq_incep_group_args *g, int bm, int bn, unsigned nib, R &&refuses, GroupGrid *gg, int *who) {
     GroupMap *mp = &gg->mp;
     Span *in = gg->in, *out = gg->out;
     long long wgs = 0;
     for (int i = 0; i < g->n; ++i) {
         const hawq_incep_conv_args *a = &g->conv[i];
         *who = i;
-        if (!hawq_incep_conv_tile_ok(a, tile)) return "the tile refuses this member (hawq_incep_conv_tile_ok)";
+        if (const char *why = refuses(i, a)) return why;
         const int Ho = (a->H + 2 * a->pad_h - a->KH) / a->stride + 1, Wo = (a->W + 2 * a->pad_w - a->KW) / a->stride + 1;
-        const long long P = (long long)a->N * Ho * Wo, npb = (P + bm - 1) / bm;   // npb < 2^31 (hawq_incep_conv_tile_ok)
+        const long long P = (long long)a->N * Ho * Wo, npb = (P + bm - 1) / bm;
         wgs += npb * ((a->Cout + bn - 1) / bn);
         if (wgs >= (1ll << 31)) return "too many workgroups";
         mp->end[i] = (int32_t)wgs, mp->npb[i] = (int32_t)npb, mp->Ho[i] = Ho, mp->Wo[i] = Wo;
-        const size_t es = a->epilogue == HAWQ_INCEP_RAW ? 4 : (size_t)a->out_bits / 8;
+        const size_t hb = a->epilogue == HAWQ_INCEP_RAW ? 8 : (size_t)a->out_bits / 4;   // half bytes per output element
         gg->P[i] = P;
-        in[i].lo = (uintptr_t)a->in, in[i].hi = in[i].lo + (size_t)a->N * a->H * a->W * a->Cin;
-        out[i].lo = (uintptr_t)a->out + (size_t)a->c_off * es;
-        out[i].hi = (uintptr_t)a->out + ((size_t)(P - 1) * a->ldo + a->c_off + a->Cout) * es;
+        in[i].lo = (uintptr_t)a->in, in[i].hi = in[i].lo + ((size_t)a->N * a->H * a->W * a->Cin >> ((nib >> i) & 1));
+        out[i].lo = (uintptr_t)a->out + (size_t)a->c_off * hb / 2;
+        out[i].hi = (uintptr_t)a->out + ((size_t)(P - 1) * a->ldo + a->c_off + a->Cout) * hb / 2;
     }
     for (int i = g->n; i < HAWQ_INCEP_GROUP_MAX; ++i) mp->end[i] = INT32_MAX, mp->npb[i] = 1, mp->Ho[i] = mp->Wo[i] = 0;
     gg->total = wgs;
+    return nullptr;
+}
+
+// the grid of the int8 grouped launches: every member on tile `tile` (1 .. NUM_TILES) of the tiled kernel
+const char *group_grid(const hawq_incep_group_args *g, int tile, GroupGrid *gg, int *who) {
+    auto refuses = [tile](int, const hawq_incep_conv_args *a) -> const char * {
+        return hawq_incep_conv_tile_ok(a, tile) ? nullptr : "the tile refuses this member (hawq_incep_conv_tile_ok)";
+    };
+    return group_grid(g, kTiles[tile].bm, kTiles[tile].bn, 0u, refuses, gg, who);
+}
+
+// why the members of a laid-out group are not independent, and the member `who` (NULL: they are): no member reads what a member
+// writes, and no two write the same bytes - channel intervals for slices of one concat buffer (same base, pitch, element width),
+// byte extents otherwise
+const char *group_dependence(const hawq_incep_group_args *g, const GroupGrid *gg, int *who) {
+    const Span *in = gg->in, *out = gg->out;
+    for (int i = 0; i < g->n; ++i) {
+        const hawq_incep_conv_args *a = &g->conv[i];
+        *who = i;
+        for (int j = 0; j < g->n; ++j) {
+            const hawq_incep_conv_args *b = &g->conv[j];
+            if (meet(in[i], out[j])) return "a member reads what a member of the group writes";
+            if (j <= i) continue;
+            const bool rows = a->out == b->out && a->ldo == b->ldo && a->out_bits == b->out_bits &&
+                              (a->epilogue == HAWQ_INCEP_RAW) == (b->epilogue == HAWQ_INCEP_RAW);   // slices of one concat buffer
+            if (rows ? (a->c_off < b->c_off + b->Cout && b->c_off < a->c_off + a->Cout) : meet(out[i], out[j]))
+                return "two members write overlapping outputs";
+        }
+    }
+    *who = -1;
     return nullptr;
 }
 

@@ -106,6 +106,22 @@ hawq4 weights, exactly when the tensor it reads is hawq4; the int8 form of such 
 ``nibble_convs`` maps conv launch -> nibble tile, ``nibble_tensors`` lists the hawq4 tensors, ``nibble_bytes`` the conv operand bytes
 (weights, activations) in int8 containers and in this plan.  It composes with ``fast_pools``, ``fused_stem`` and ``forward_uint8``;
 with ``grouped`` or ``fan_out``, and on a model without such a conv (uniform8), it raises ``PlanNotApplicable``.  Not the default.
+
+Mixed-form groups.  ``InceptionEngine(model, nibble=True, nibble_groups=True)`` issues the conv levels of a nibble plan as
+``hawq_incep_conv_group_nib`` launches (hawq_amd/csrc/incep_group_nib.hip): the grouped launch whose members are int8 or hawq4 one
+by one, a bit mask saying which.  ``grouped`` names the int8 launch and still does not compose with ``nibble``; ``nibble_groups``
+without ``nibble`` raises ``PlanNotApplicable``.  The nibble choice is made first, exactly as without the option; then every level
+of two or more convs becomes one launch, a nibble conv on its hawq4 block and every other member on its own block, members with the
+most K steps first (K / 64 int8, K / 128 hawq4: free, and unmeasured).  Which levels, and on which of the launch's two tiles:
+* neither ``tune`` nor a ``"nibble_groups"`` field in ``plan``: every level the library takes on tile 2 (128 px x 64 ch), in
+  ``grouped_order`` - the launch count of a ``grouped`` engine;
+* ``tune=True``: after the nibble choice every candidate level is timed on both tiles, on the buffers of a forward of the chosen
+  nibble plan, and kept on the faster one only if that beats the sum of its members' chosen single launches (best int8 tile or best
+  nibble tile);
+* ``plan=`` with the field: exactly its entries (``check_groups``: StalePlan for an entry that is not a level, overlaps another or is
+  refused); ``export_plan()`` writes ``"nibble_groups": [{"convs", "tile", "us"}]``; an engine without the option ignores it.
+``group_launches`` lists (member conv indices, tile) per launch and ``nibble_group_masks`` the mask of each (bit k: member k is
+hawq4).  It composes with ``fast_pools``, ``fused_stem``, ``forward_uint8``, ``tune`` and ``plan``.  Not the default.
 """
 from __future__ import annotations
 
@@ -168,11 +184,12 @@ def launch_digest(keys):
     return hashlib.sha256(json.dumps([list(map(int, k)) for k in keys], separators=(",", ":")).encode()).hexdigest()
 
 
-def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None):
+def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None, nibble_groups=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
     and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
     ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field, and with `fan_out`
-    (a fan-out engine's ``{"unit": k, "tiles": {launch: id}, "us": {...}}`` entries) the ``"fan_out"`` field"""
+    (a fan-out engine's ``{"unit": k, "tiles": {launch: id}, "us": {...}}`` entries) the ``"fan_out"`` field; `nibble_groups`
+    (entries as `groups`, tile ids of ``hawq_incep_conv_group_nib``) the ``"nibble_groups"`` field"""
     plan = {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
             "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
             "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
@@ -185,6 +202,9 @@ def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibb
     if nibble is not None:   # a nibble engine's (conv -> nibble tile, conv -> {tile: microseconds})
         plan["nibble"] = [[int(c), int(t)] for c, t in sorted(nibble[0].items())]
         plan["nibble_us"] = {str(c): {str(t): round(float(v), 3) for t, v in d.items()} for c, d in sorted(nibble[1].items())}
+    if nibble_groups is not None:
+        plan["nibble_groups"] = [{"convs": [int(c) for c in g["convs"]], "tile": int(g["tile"]),
+                                  "us": {str(k): round(float(v), 3) for k, v in g.get("us", {}).items()}} for g in nibble_groups]
     return plan
 
 
@@ -402,14 +422,17 @@ class _T:
 
 class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
-                 fused_stem: bool = False, grouped: bool = False, fan_out: bool = False, nibble: bool = False):
+                 fused_stem: bool = False, grouped: bool = False, fan_out: bool = False, nibble: bool = False,
+                 nibble_groups: bool = False):
         self.model, self.use_graph = model, use_graph
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
-        self.grouped, self.fan_out, self.nibble = bool(grouped), bool(fan_out), bool(nibble)
+        self.grouped, self.fan_out, self.nibble, self.nibble_groups = bool(grouped), bool(fan_out), bool(nibble), bool(nibble_groups)
         if self.nibble and (self.grouped or self.fan_out):
             raise PlanNotApplicable("nibble=True does not compose with grouped or fan_out: their launches have no nibble form")
+        if self.nibble_groups and not self.nibble:
+            raise PlanNotApplicable("nibble_groups=True groups the launches of a nibble plan: it needs nibble=True")
         self.nibble_convs, self.nibble_tensors, self.nibble_us, self.nibble_bytes = {}, [], {}, {}
-        self.group_launches, self.group_candidates = [], []
+        self.group_launches, self.group_candidates, self.nibble_group_masks = [], [], []
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         self.n_timing_launches = 0           # conv launches issued to time tiles (0 for a default or a replayed plan)
         self.conv_tiles, self.conv_us = None, None
@@ -592,7 +615,7 @@ class InceptionEngine(GraphRunner):
         self._tensors, self._conv_io = [], {}   # the tensors convs read, in the order they are made; conv -> (src, out, weights)
         self.nibble_convs, self.nibble_tensors, self.nibble_us, self.nibble_bytes = {}, [], {}, {}
         self.conv_tiles, self.conv_us = None, None
-        self.group_launches, self.group_candidates = [], []
+        self.group_launches, self.group_candidates, self.nibble_group_masks = [], [], []
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
@@ -752,7 +775,7 @@ class InceptionEngine(GraphRunner):
     # ------------------------------------------------------------------ the choice
     def _choose(self, batch):
         """What a plan decides, as one value: (tile id per conv launch, or None; grouped launches [(member conv indices, tile)], or
-        None on an engine without ``grouped``; fan-out boundaries [(boundary, {producer launch: tile})], or None on an engine
+        None on an engine without ``grouped`` - the mixed-form launches of a ``nibble_groups`` engine take this place -; fan-out boundaries [(boundary, {producer launch: tile})], or None on an engine
         without ``fan_out``).  From ``self.plan``, else from timing (``tune``), else the defaults: no tiles, every level of two or
         more convs on tile 3 that the library takes, and every candidate boundary whose producer launches the library takes.  Leaves
         ``conv_tiles`` and what was recorded or measured (``conv_us``, ``group_candidates``, ``fan_candidates``) for the readers
@@ -784,6 +807,8 @@ class InceptionEngine(GraphRunner):
             groups = [(c, 3) for c in cands if self._group_ok(c, 3)]
         self.conv_tiles = None if tiles is None else [int(t) for t in tiles]
         nib = self._choose_nibbles(T) if self.nibble else None
+        if self.nibble_groups:   # the second component then holds the mixed-form launches (``grouped`` is off: the constructor)
+            groups = self._choose_nibble_groups(self.conv_tiles, nib)
         return self.conv_tiles, groups, self._choose_fans(self.conv_tiles, groups) if self.fan_out else None, nib
 
     # ------------------------------------------------------------------ nibbles
@@ -881,6 +906,72 @@ class InceptionEngine(GraphRunner):
             self._tensors[ti].buf = self._nib_buf[ti]
         del self._nib_buf, self._nib_w
         return tile
+
+    # ------------------------------------------------------------------ mixed-form groups
+    def _ngroup_args(self, convs, nib):
+        """(group block, mask) of one ``hawq_incep_conv_group_nib`` launch: a member is on its ``_nib_conv`` block, with its mask bit
+        set, if it is a nibble conv of `nib`, and on its own block otherwise"""
+        g, mask = _lib.IncepGroupArgs(), 0
+        g.n = len(convs)
+        for k, c in enumerate(convs):
+            g.conv[k] = self._nib_conv[c] if c in nib else self._convs[c].args[0]
+            mask |= (c in nib) << k
+        return g, mask
+
+    def _ngroup_ok(self, convs, tile, nib):
+        if not 1 <= len(convs) <= _lib.INCEP_GROUP_MAX or not isinstance(tile, int) or isinstance(tile, bool):
+            return False
+        g, mask = self._ngroup_args(convs, nib)
+        return bool(_lib.load().hawq_incep_conv_group_nib_ok(C.byref(g), mask, tile))
+
+    def _choose_nibble_groups(self, tiles, nib):
+        """The mixed-form grouped launches [(member conv indices, tile of ``hawq_incep_conv_group_nib``)] of a nibble plan whose
+        nibble convs `nib` are chosen: every level of two or more convs that the library takes on tile 2; with ``tune``, on the
+        faster of the two tiles, and only where that beat the sum of its members' chosen single launches; with a plan that has a
+        ``"nibble_groups"`` field, exactly its entries.  Leaves ``group_candidates``."""
+        # members with the most K steps first (K / 64 of an int8 member, K / 128 of a hawq4 one), so that the heavy workgroups
+        # start first: as with the int8 groups, the order is free, and unmeasured
+        def steps(c):
+            a = self._convs[c].args[0]
+            return -(-(a.KH * a.KW * a.Cin) // (128 if c in nib else 64))
+        cands = [sorted(lv, key=lambda c: -steps(c)) for lv in self.conv_level_list if len(lv) >= 2]
+        ok = lambda convs, tile: self._ngroup_ok(convs, tile, nib)   # noqa: E731
+        if self.plan is not None and self.plan.get("nibble_groups") is not None:
+            entries = self.plan["nibble_groups"]
+            groups = check_groups(entries, len(self._convs), self.conv_level_list, ok)
+            us = {tuple(g["convs"]): dict(g.get("us", {})) for g in entries}
+            self.group_candidates = [{"convs": list(c), "tile": t, "us": us[tuple(c)], "kept": True} for c, t in groups]
+        elif self.tune and self.plan is None:
+            NG = _lib.load().hawq_incep_conv_group_nib_num_tiles()
+            gtiles = [[t for t in range(1, NG + 1) if ok(c, t)] for c in cands]
+            for c, us in zip(cands, self._time_nibble_groups(cands, gtiles, tiles, nib)):
+                if us:
+                    tile = min(us, key=lambda t: (us[t], t))
+                    singles = sum(self.nibble_us[i][nib[i]] if i in nib else self.conv_us[i][tiles[i]] for i in c)
+                    self.group_candidates.append({"convs": c, "tile": tile, "kept": us[tile] < singles,
+                                                  "us": {**{str(t): v for t, v in us.items()}, "singles": singles}})
+        else:
+            self.group_candidates = [{"convs": c, "tile": 2, "us": {}, "kept": True} for c in cands if ok(c, 2)]
+        return [(g["convs"], g["tile"]) for g in self.group_candidates if g["kept"]]
+
+    def _time_nibble_groups(self, cands, gtiles, tiles, nib):
+        """Microseconds of every candidate level on every tile of `gtiles` it accepts, as ``_time`` measures the int8 groups: on the
+        buffers of a forward of the chosen nibble plan, its launches single."""
+        sp, out = self.stream.cuda_stream, []
+        self._choice = (tiles, None, None, nib)
+        with EventTimer(sp, _TUNE_REPS + 1) as ev:
+            torch.cuda.synchronize(self.dev)
+            with torch.cuda.stream(self.stream):
+                for op in self._write():
+                    op()
+                for c, ts in zip(cands, gtiles):
+                    g, mask = self._ngroup_args(c, nib)
+                    self.n_timing_launches += (_TUNE_WARMUP + _TUNE_REPS) * len(ts)
+                    out.append({t: ev.median_us(lambda: _lib.call("hawq_incep_conv_group_nib", C.byref(g), mask, t, sp),
+                                                _TUNE_REPS, _TUNE_WARMUP) for t in ts})
+        torch.cuda.synchronize(self.dev)
+        self._choice = (None, None, None, None)
+        return out
 
     def _time_nibbles(self, cand, tiles_of):
         """Microseconds of every candidate conv on every nibble tile it accepts, as ``_time`` measures the int8 tiles: on the
@@ -1006,8 +1097,9 @@ class InceptionEngine(GraphRunner):
             raise RuntimeError("export_plan: no tuned plan (build the engine with tune=True or plan=... and run a forward first)")
         groups = [g for g in self.group_candidates if g["kept"]] if self.grouped else None
         fans = [f for f in self.fan_candidates if f["kept"]] if self.fan_out else None
+        ngroups = [g for g in self.group_candidates if g["kept"]] if self.nibble_groups else None
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
-                         groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None)
+                         groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None, ngroups)
 
     # ------------------------------------------------------------------ the writer
     def _write(self, u8=False):
@@ -1045,7 +1137,7 @@ class InceptionEngine(GraphRunner):
             ops = [op("hawq_incep_stem_f32", self.x_in.data_ptr(), *self._input_quant(), C.byref(self._stem_a))]
         else:
             ops = [single(r) for r in launches[:head]]
-        n_stem, issued, fanned, residual = len(ops), [], [], []
+        n_stem, issued, masks, fanned, residual = len(ops), [], [], [], []
         at = {r: min(i, n_stem - 1) for i, r in enumerate(launches[:head])}
         order = [(False, i) for i in range(len(launches))] if groups is None else grouped_order(launches, groups)
         for is_group, i in order[head:]:   # the stem stays in place in either order
@@ -1060,6 +1152,13 @@ class InceptionEngine(GraphRunner):
                 fanned.append((b["unit"], list(convs), int(tile)))
                 if is_group:
                     issued.append((list(convs), int(tile)))
+            elif is_group and self.nibble_groups:   # members of either operand form, each on the block its single launch has
+                g, mask = self._ngroup_args(convs, nib)
+                self._keep.append(g)
+                at.update((self._convs[c], len(ops)) for c in convs)
+                ops.append(op("hawq_incep_conv_group_nib", C.byref(g), mask, int(tile)))
+                issued.append((list(convs), int(tile)))
+                masks.append(mask)
             elif is_group:
                 g = self._group_args(convs)
                 self._keep.append(g)
@@ -1078,7 +1177,7 @@ class InceptionEngine(GraphRunner):
             else:
                 at[r] = len(ops)
                 ops.append(single(r))
-        self._at, self._tail, self.group_launches = at, ops[n_stem:], issued
+        self._at, self._tail, self.group_launches, self.nibble_group_masks = at, ops[n_stem:], issued, masks
         self.fan_launches, self.residual_requants = fanned, residual
         return ops
 

@@ -598,6 +598,23 @@ typedef struct hawq_incep_group_args {
 } hawq_incep_group_args;
 int hawq_incep_conv_group_ok(const hawq_incep_group_args *g, int tile);
 int hawq_incep_conv_group(const hawq_incep_group_args *g, int tile, void *stream);
+/* The grouped launch for members of both operand forms (incep_group_nib.hip): the grid of hawq_incep_conv_group, with bit i of `mask`
+ * saying that member i's in and wgt are hawq4 as hawq_incep_conv_nib reads them; the other members are int8 as hawq_incep_conv_tiled
+ * reads them.  A workgroup runs its member's own kernel body, both on the same two LDS stages.
+ *   hawq_incep_conv_group_nib_num_tiles: T = 2; the ids name the workgroup shapes both families have: 1 is 128 px x 128 ch (int8 tile
+ *       1, nibble tile 1), 2 is 128 px x 64 ch (int8 tile 3, nibble tile 2).  The K-split shapes differ and have no id here.
+ *   hawq_incep_conv_group_nib:     member i writes, byte for byte, what hawq_incep_conv_nib (mask bit set) or hawq_incep_conv_tiled
+ *       (clear) writes for &g->conv[i] on that shape: every epilogue, out_bits 8 and 16, and 4 for a hawq4 member.
+ *   hawq_incep_conv_group_nib_ok:  1 if the launch takes this group.  Host arithmetic only: nothing is dereferenced or launched, no
+ *       device is needed.  0 for n outside 1 .. 8, mask bits at or beyond n, a tile other than 1 or 2, a member its own family's check
+ *       refuses on the 128 x 64 shape (hawq_incep_conv_tile_ok(a, 3) / hawq_incep_conv_nib_ok(a, 2): the single launches' preference
+ *       of tile 1 for Cout > 64 is not applied to a group, which has one tile for all its members), out_bits 4 on an int8 member, 2^31 or more workgroups, and members that are not independent by
+ *       hawq_incep_conv_group_ok's two rules, on byte extents of the real widths: Cin / 2 bytes per input pixel of a hawq4 member,
+ *       half a byte per out_bits 4 element.
+ * A refused group returns non-zero (the reason, with the member, in hawq_last_error()), launches nothing and writes no byte. */
+int hawq_incep_conv_group_nib_num_tiles(void);
+int hawq_incep_conv_group_nib_ok(const hawq_incep_group_args *g, uint32_t mask, int tile);
+int hawq_incep_conv_group_nib(const hawq_incep_group_args *g, uint32_t mask, int tile, void *stream);
 /* The grouped launch with a fan-out epilogue (incep_fan.hip).  In the InceptionV3 plan every conv branch of a unit starts by
  * requantising the previous unit's whole 16-bit concat buffer to int8 at the branch's scale (hawq_incep_requant, one launch per
  * branch).  The convs that wrote that buffer held those values in registers; here they store the int8 copies themselves.

@@ -48,6 +48,7 @@ producer launches + residual requants, in microseconds, kept or not.
     python tools/inception_bench.py --grouped --batches 1,16,128 [--blocks 6]
     python tools/inception_bench.py --fan-out [--grouped] --batches 1,16,128 [--blocks 6]
     python tools/inception_bench.py --nibble [--pools] --scheme uniform4 --batches 1,128 [--blocks 6]
+    python tools/inception_bench.py --nibble-groups [--pools] --scheme uniform4 --batches 128,1 [--blocks 6]
 """
 import argparse
 import json
@@ -460,6 +461,47 @@ def compare_nibble(model, args, b):
     return nt
 
 
+def compare_nibble_groups(model, args, b):
+    """the two best forms without the option - nibble=True and grouped=True (int8), both tuned - and nibble=True with
+    nibble_groups=True, tuned, alternating blocks; the per-level times the tuner saw (both tiles, the members' single launches, kept
+    or not, which members are hawq4); returns the tuned nibble_groups engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    with torch.no_grad():
+        opts = dict(fast_pools=args.pools, tune=True)
+        engines = {"nibble_tuned": InceptionEngine(model, nibble=True, **opts), "grouped_tuned": InceptionEngine(model, grouped=True, **opts),
+                   "nibble_groups_tuned": InceptionEngine(model, nibble=True, nibble_groups=True, **opts)}
+        y = {k: e(x) for k, e in engines.items()}
+        equal = all(bool(torch.equal(v, y["nibble_tuned"])) for v in y.values())
+        assert equal, "the logits of the three plans differ"
+        ng = engines["nibble_groups_tuned"]
+        print(f"# {wl}: level (convs) | hawq4 members / members | tile 1 us | tile 2 us | singles us | kept on")
+        for g in ng.group_candidates:
+            us = g["us"]
+            print(f"# {g['convs']} | {sum(c in ng.nibble_convs for c in g['convs'])} / {len(g['convs'])} | {us.get('1', float('nan')):.1f} | "
+                  f"{us.get('2', float('nan')):.1f} | {us['singles']:.1f} | {g['tile'] if g['kept'] else '-'}")
+        forms = [(len(c), bin(m).count("1")) for (c, _), m in zip(ng.group_launches, ng.nibble_group_masks)]
+        print(json.dumps({"workload": wl, "levels": len(ng.group_candidates), "kept": len(forms), "nibble_convs": len(ng.nibble_convs),
+                          "kept_all_hawq4": sum(k == n for n, k in forms), "kept_mixed": sum(0 < k < n for n, k in forms),
+                          "kept_all_int8": sum(k == 0 for n, k in forms), "kept_on_tile_1": sum(t == 1 for _, t in ng.group_launches)}), flush=True)
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": k, "fast_pools": bool(args.pools), "ms_per_batch": round(mean, 4),
+                              "images_per_s": round(b * 1000.0 / mean, 1), "block_min_ms": round(min(v), 4),
+                              "block_max_ms": round(max(v), 4), "blocks": len(v), "steps": args.steps, "launches": e.n_launches,
+                              "logits_bit_equal": equal}), flush=True)
+    return ng
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheme", default="uniform8")
@@ -482,9 +524,11 @@ def main():
                     help="compare one recorded plan (fast pools, fused stem; grouped with --grouped) without and with fan-out conv epilogues")
     ap.add_argument("--nibble", action="store_true",
                     help="compare the default and the tuned plan (uniform4) without and with nibble-packed conv operands")
+    ap.add_argument("--nibble-groups", action="store_true",
+                    help="compare the tuned nibble plan and the tuned grouped int8 plan (uniform4) with the tuned nibble plan on mixed-form groups")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out / --nibble: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
-    if args.save_plan and not (args.tune or args.plan or args.grouped or args.fan_out or args.nibble):
+    if args.save_plan and not (args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups):
         ap.error("--save-plan needs --tune, --plan, --grouped, --fan-out or --nibble: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
@@ -492,8 +536,8 @@ def main():
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.nibble or args.fan_out or args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
-            compare = compare_nibble if args.nibble else compare_fan_out if args.fan_out else compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
+        if args.nibble_groups or args.nibble or args.fan_out or args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
+            compare = compare_nibble_groups if args.nibble_groups else compare_nibble if args.nibble else compare_fan_out if args.fan_out else compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
             tuned = compare(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
