@@ -216,6 +216,22 @@ OFFSETS = {   # what the 256 pixels of a 16 x 16 map add to a channel's bias
     "tiny_relu": np.arange(256, dtype=np.int64) % 2,
 }
 
+# What hawq4 operands can add (unsigned activation nibbles 0 .. 15 against signed weight nibbles -8 .. 7): two activation channels
+# (a0, a1) of the 256 pixels against the weights (-8, 1) give a1 - 8 a0.  Kept apart from OFFSETS, whose kinds the int8 tests upload
+# one image each of.
+_I = np.arange(256, dtype=np.int64)
+NIB_INPUTS = {   # kind -> (a0, a1), both inside 0 .. 15
+    "nib": (_I // 16, _I % 16),                          # every offset -120 .. 15, most of them on two pixels
+    "nib_tiny": (np.zeros(256, np.int64), _I % 3),       # 0 .. 2 under a bias one lower: the tables whose whole range is {-1, 0, 1}
+}
+NIB_WEIGHTS = (-8, 1)
+NIB_OFFSETS = {kind: NIB_WEIGHTS[0] * a0 + NIB_WEIGHTS[1] * a1 for kind, (a0, a1) in NIB_INPUTS.items()}
+# (table index, value) pairs of TABLES that no bias puts on a nibble-driven accumulator, each with its reason of arithmetic.  There is
+# none: both kinds are contiguous ranges no wider than the narrowest table they serve (136 values where lim >= 65535, 3 where lim
+# is 1), the bias is a free int32 and |bias| <= lim.  Under a form's ReLU the negative values are clamped before the requant; the
+# tests state that with coverage's `keep`, not here.
+NIB_UNREACHABLE = {}
+
 Launch = namedtuple("Launch", "kind off tidx bias m ek V Q")   # per channel: table index, bias, m, e | k << 8; V, Q: [C][256] values and exact results
 
 
@@ -227,13 +243,16 @@ def check_contract(V, m, ek):
     assert (np.abs(np.asarray(V, np.int64)) <= ((np.int64(1) << (31 - k)) - 1)).all(), "a driven value violates |v << k| < 2^31"
 
 
-def plan(tables, cout=128, relu_inputs=False):
+def plan(tables, cout=128, relu_inputs=False, nibble=False):
     """Lay the list onto launches of `cout` channels: one (table, bias) per channel, tables of a tiny range apart from the others
-    (they need other input columns).  Returns the launches; ``coverage`` says which pairs of the list they hold."""
+    (they need other input columns).  ``nibble``: the offsets hawq4 operands produce (NIB_OFFSETS) instead of the int8 ones.
+    Returns the launches; ``coverage`` says which pairs of the list they hold."""
+    assert not (nibble and relu_inputs)   # hawq4 activations are unsigned anyway; the sign comes from the weights
     out = []
     for tiny in (False, True):
         kind = ("tiny" if tiny else "int8") if not relu_inputs else ("tiny_relu" if tiny else "relu")
-        off = OFFSETS[kind]
+        kind = ("nib_tiny" if tiny else "nib") if nibble else kind
+        off = NIB_OFFSETS[kind] if nibble else OFFSETS[kind]
         slots = [(i, c) for i, t in enumerate(tables) if (t.lim < 128) == tiny for c in centres(t, (int(off.min()), int(off.max())))]
         for at in range(0, len(slots), cout):
             part = slots[at:at + cout]

@@ -93,6 +93,50 @@ def test_mixed_group_equals_int64_conv_and_requant(guard_arena, tile, mask, raw)
     assert np.array_equal(got, exp)
 
 
+# Three hawq4 members on A's map writing neighbouring nibble slices of one row, as the plan's concat buffers are written: channels
+# 16 .. 31, 32 .. 63 and 64 .. 79 of 96, a 16-channel gap of sentinel on either side.  Member i convolves rows ROW_W[i] of A's weights.
+LDO_ROW = 96
+ROW = ((16, 16), (32, 32), (64, 16))               # (c_off, Cout)
+ROW_W = (slice(0, 16), slice(16, 48), slice(48, 64))
+# different forms and clamps, so that a store landing in a neighbour's bytes changes a value there
+ROW_FORMS = (dict(epilogue=REQUANT, q=(0, 15), relu=1), dict(epilogue=REQUANT2, q=(0, 15), m2=5 << 27, ek2=31, q2=(1, 14), relu=1),
+             dict(epilogue=REQUANT, q=(3, 12), relu=0))
+
+
+def row_blocks(ptrs, row=ROW, bits=(4, 4, 4)):
+    """the three members' blocks on ``ptrs[i] = (in, wgt, bias, out, m, ek)``; ``row`` and ``bits`` are what the host test varies"""
+    return [_block(A[:8] + (cout,), ptrs[i], out_bits=bits[i], ldo=LDO_ROW, c_off=c_off, **ROW_FORMS[i]) for i, (c_off, cout) in enumerate(row)]
+
+
+@pytest.mark.parametrize("tile", [1, 2])
+def test_neighbouring_nibble_slices_of_one_row(guard_arena, tile):   # noqa: F811
+    from hawq_amd.packing import pack_conv_weight, pack_hawq4, unpack_hawq4
+    L = _lib().load()
+    x, w, b, ref = _case(A)
+    P = 162
+    out = out_buf(P * LDO_ROW // 2, torch.uint8, 0x77, "row")   # 0x77: two nibbles of 7
+    xd = dev(pack_hawq4(x), "x")
+    ptrs, tabs = [], []
+    for i, ((c_off, cout), rows) in enumerate(zip(ROW, ROW_W)):
+        r = ref[..., rows]
+        m = np.random.default_rng(100 + i).integers(1 << 29, 1 << 30, cout).astype(np.int32)
+        e = np.full(cout, 30 + max(int(np.abs(r).max()).bit_length() - 6, 1), np.int32)   # the larger sums pass the upper clamp
+        m[0], e[0] = 1 << 30, 31   # ratio 1/2: every odd value an exact tie
+        tabs.append((m, e))
+        ptrs.append((xd.data_ptr(), dev(pack_conv_weight(w[rows].transpose(0, 3, 1, 2), 4), f"w{i}").data_ptr(),
+                     dev(b[rows].astype(np.int32), f"b{i}").data_ptr(), out.data_ptr(), dev(m, f"m{i}").data_ptr(), dev(e, f"ek{i}").data_ptr()))
+    blocks = row_blocks(ptrs)
+    assert L.hawq_incep_conv_group_nib(C.byref(group(blocks)), 0b111, tile, torch.cuda.current_stream().cuda_stream) == 0, L.hawq_last_error()
+    torch.cuda.synchronize()
+    exp = np.full((P, LDO_ROW), 7, np.int64)
+    for a, rows, (m, e) in zip(blocks, ROW_W, tabs):
+        want = _want(a, ref[..., rows], m, e).reshape(P, a.Cout)
+        assert len(np.unique(want)) >= 4 and want.min() == (a.q2_lo if a.epilogue == REQUANT2 else a.q_lo)   # several levels, the lower edge
+        exp[:, a.c_off:a.c_off + a.Cout] = want
+    got = unpack_hawq4(out.cpu().numpy().reshape(P, LDO_ROW // 2)).astype(np.int64)
+    assert np.array_equal(got, exp)   # the three slices, and the sentinel in both gaps
+
+
 def test_a_refused_group_is_an_error_and_writes_nothing(guard_arena):   # noqa: F811
     L = _lib().load()
     ab, oc = out_buf(162 * LDO_AB, torch.int16, 77, "out_ab"), out_buf(32 * LDO_C, torch.int8, 77, "out_c")

@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.guard import dev, guard_arena, out_buf  # noqa: F401  (the fixture; the hawq4 tests at the end allocate from it)
+
 pytestmark = pytest.mark.gpu
 
 OLD = {"requant": "hawq_incep_requant", "maxpool": "hawq_incep_maxpool3s2", "avgpool": "hawq_incep_avgpool_branch",
@@ -228,3 +230,92 @@ def test_every_pool_launch_of_the_shipped_networks_is_taken_and_equal():
         H, W = {"requant": (5, 4), "maxpool": (7, 5), "avgpool": (5, 4), "global": (8, 7)}[op]
         post_t = (POST8 if out_bits == 8 else POST16) if post else None
         _check(op, 2, H, W, Cc, in_bits, out_bits, PRE if pre else None, post_t, ldo=ldo, c_off=c_off, seed=100 + i)
+
+
+# ---------------------------------------------------------------------------------------------- REQUANT to hawq4 rows (out_bits 4)
+# No entry point of inception.hip has this form, so the expectation is brute force alone: exact round-half-even, the clamp, and the
+# nibble order of hawq_amd.packing.unpack_hawq4.  The output is a uint8 buffer of N H W ldo / 2 bytes holding 0x77, two nibbles of 7.
+HALF, FIVE_16 = (1 << 30, 31), (5 << 27, 31)   # post ratios 1/2 (every odd value an exact tie) and 5/16 (8 mod 16)
+PRE4 = (3 << 28, 30)                           # ratio 3/4, ties at 2 mod 4
+SLICES = {"c48_slices_both_sides": dict(Cc=48, in_pitch=112, in_off=48, ldo=96, c_off=32),   # 126 px x 3 groups: no multiple of 256 lanes
+          "c16_one_store_per_pixel": dict(Cc=16, in_pitch=16, in_off=0, ldo=48, c_off=16)}
+
+
+def _pool_args(xd, out, N, H, W, Cc, in_bits, in_pitch, in_off, out_bits, ldo, c_off, pre_t, post_t):
+    from hawq_amd import _lib as L
+    a = L.IncepPoolArgs()
+    a.in_, a.out = xd.data_ptr(), out.data_ptr()
+    a.N, a.H, a.W, a.C, a.in_bits, a.in_pitch, a.in_off = N, H, W, Cc, in_bits, in_pitch, in_off
+    a.out_bits, a.ldo, a.c_off = out_bits, ldo, c_off
+    if pre_t:
+        a.pre, (a.m1, a.ek1, a.lo1, a.hi1) = 1, pre_t
+    if post_t:
+        a.post, (a.m2, a.ek2, a.lo2, a.hi2) = 1, post_t
+    return a
+
+
+def hawq4_cases(in_bits, pre, where):
+    """both post tables under the whole nibble and under a narrower clamp, on N = 2, H = 9, W = 7"""
+    lim = 1 << (in_bits - 1)
+    for n, (post, clamp) in enumerate((p, c) for p in (HALF, FIVE_16) for c in ((0, 15), (2, 13))):
+        yield dict(N=2, H=9, W=7, in_bits=in_bits, pre_t=PRE4 + (-lim, lim - 1) if pre else None, post=post, clamp=clamp,
+                   seed=in_bits + n, **SLICES[where])
+
+
+def _case4(N, H, W, Cc, in_bits, pre_t, post, clamp, in_pitch, in_off, seed, **_):
+    """the input rows [N][H][W][in_pitch] and the expected slice [N][H][W][Cc]; needs no device"""
+    lim = 1 << (in_bits - 1)
+    (m2, e2), (lo, hi) = post, clamp
+    ratio = m2 / 2.0 ** e2 * (pre_t[0] / 2.0 ** pre_t[1] if pre_t else 1.0)
+    gen = np.random.default_rng(seed)
+    # results from below -1 to above 16 before the clamp, and the two ends of the input type far outside it
+    xf = gen.integers(int(-2.6 / ratio), int(17.4 / ratio) + 1, (N, H, W, in_pitch)).astype(np.int16 if in_bits == 16 else np.int8)
+    xf[0, 0, 0, in_off], xf[-1, -1, -1, in_off + Cc - 1] = lim - 1, -lim
+    v = xf[..., in_off:in_off + Cc].astype(np.int64)
+    t = _rq(v, pre_t) if pre_t else v
+    raw = _dyadic(t, m2, e2)
+    want = np.clip(raw, lo, hi)
+    # no degenerate inputs: exact ties of the post table, results on both sides of both edges of the nibble and of this clamp,
+    # several levels
+    assert (((t * m2) & ((1 << e2) - 1)) == 1 << (e2 - 1)).sum() >= 8
+    assert {-1, 0, 15, 16, lo - 1, lo, hi, hi + 1} <= set(raw.reshape(-1).tolist())
+    assert want.min() == lo and want.max() == hi and len(np.unique(want)) >= 4
+    return xf, want
+
+
+def _check4(N, H, W, Cc, in_bits, pre_t, post, clamp, ldo, c_off, in_pitch, in_off, seed):
+    from hawq_amd import _lib as L
+    from hawq_amd.packing import unpack_hawq4
+    (m2, e2), (lo, hi) = post, clamp
+    xf, want = _case4(N, H, W, Cc, in_bits, pre_t, post, clamp, in_pitch, in_off, seed)
+    xd = dev(xf, "x")
+    out = out_buf(N * H * W * ldo // 2, torch.uint8, 0x77, "out")
+    a = _pool_args(xd, out, N, H, W, Cc, in_bits, in_pitch, in_off, 4, ldo, c_off, pre_t, (m2, e2, lo, hi))
+    assert L.load().hawq_incep_pool_v_ok(C.byref(a), OPS["requant"]) == 1
+    L.call("hawq_incep_pool_v", C.byref(a), OPS["requant"], torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    got = unpack_hawq4(out.cpu().numpy().reshape(N, H, W, ldo // 2)).astype(np.int64)
+    assert np.array_equal(got[..., c_off:c_off + Cc], want)
+    assert (np.delete(got, np.s_[c_off:c_off + Cc], axis=-1) == 7).all()   # every other nibble of every row
+
+
+@pytest.mark.parametrize("where", sorted(SLICES))
+@pytest.mark.parametrize("pre", [False, True], ids=["post", "pre_post"])
+@pytest.mark.parametrize("in_bits", [8, 16])
+def test_requant_to_hawq4_rows(guard_arena, in_bits, pre, where):   # noqa: F811
+    for kw in hawq4_cases(in_bits, pre, where):
+        _check4(**kw)
+
+
+def test_refused_hawq4_descriptions_write_nothing(guard_arena):   # noqa: F811
+    from hawq_amd import _lib as L
+    from tests.test_incep_pool_host import HAWQ4_REFUSED, _args
+    xd = dev(np.zeros(2 * 8 * 8 * 64, np.int16), "x")
+    out = out_buf(2 * 8 * 8 * 64, torch.uint8, 0x77, "out")   # the bytes of an int8 output of that shape: more than any hawq4 row
+    for case, (op, kw) in sorted(HAWQ4_REFUSED.items()):
+        a = _args(in_ptr=xd.data_ptr(), out_ptr=out.data_ptr(), **kw)
+        assert a.out_bits == 4 and L.load().hawq_incep_pool_v_ok(C.byref(a), op) == 0, case
+        assert L.load().hawq_incep_pool_v(C.byref(a), op, torch.cuda.current_stream().cuda_stream) != 0, case
+        assert L.load().hawq_last_error().decode().startswith("hawq_incep_pool_v"), case
+    torch.cuda.synchronize()
+    assert (out == 0x77).all()

@@ -1043,3 +1043,172 @@ def test_incep_pool_v_requant_at_the_scalar_corners(lib, side):
             assert np.array_equal(o.cpu().numpy().astype(np.int64).reshape(NPIX, c), want), (side, m, ek)
         took += 1
     assert took >= 16
+
+
+# ================================================================================== 9. the nibble-packed InceptionV3 entries
+NIB_CIN = 512   # 1x1: K = 512, the least the K-split nibble tile takes
+
+
+@functools.lru_cache(maxsize=None)
+def nib_plan():
+    launches = R.plan(R.TABLES, COUT, nibble=True)
+    every = {(i, v) for i, t in enumerate(R.TABLES) for v in t.values}
+    assert R.NIB_UNREACHABLE == {} and R.coverage(launches, R.TABLES) == every and len(every) >= 400
+    assert R.coverage(launches, R.TABLES, keep=lambda v: v >= 0) == {(i, v) for i, v in every if v >= 0}   # what a ReLU form reaches
+    return launches
+
+
+class IncepNib:
+    """the driven 1x1 conv on hawq4 operands: activation channels 0 and 1 carry (a0, a1) of R.NIB_INPUTS against the weights (-8, 1)
+    of every output channel; every other activation channel holds random nibbles against zero weights, so that a unit widened or
+    placed wrongly shows"""
+
+    def __init__(self, lib, cout=COUT, cin=NIB_CIN):
+        from hawq_amd.packing import pack_conv_weight, pack_hawq4
+        self.lib, self.cout, self.cin = lib, cout, cin
+        self.x = {}
+        for j, (kind, (a0, a1)) in enumerate(R.NIB_INPUTS.items()):
+            x = np.random.default_rng(40 + j).integers(0, 16, (1, HW, HW, cin))
+            x[0, :, :, 0], x[0, :, :, 1] = a0.reshape(HW, HW), a1.reshape(HW, HW)
+            self.x[kind] = dev(pack_hawq4(x))
+        w = np.zeros((cout, cin, 1, 1), np.int64)
+        w[:, 0, 0, 0], w[:, 1, 0, 0] = R.NIB_WEIGHTS
+        self.w = dev(pack_conv_weight(w, 4))
+
+    def member(self, out, out_bits):
+        t = dict(b=dev(np.zeros(self.cout, np.int32)), m=dev(np.zeros(self.cout, np.int32)), ek=dev(np.zeros(self.cout, np.int32)))
+        a = self.lib.IncepConvArgs()
+        a.wgt, a.bias, a.m, a.ek, a.out = self.w.data_ptr(), t['b'].data_ptr(), t['m'].data_ptr(), t['ek'].data_ptr(), out.data_ptr()
+        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride = 1, HW, HW, self.cin, self.cout, 1, 1, 1
+        a.out_bits, a.ldo = out_bits, self.cout
+        return a, t
+
+    def load(self, a, t, L):
+        R.check_contract(L.V, L.m, L.ek)
+        put(t['b'], i32(L.bias)), put(t['m'], i32(L.m)), put(t['ek'], i32(L.ek))
+        a.in_ = self.x[L.kind].data_ptr()
+
+
+OUT_DT = {4: torch.uint8, 8: torch.int8, 16: torch.int16}
+
+
+def nib_out(bits, c=COUT):
+    return out_buf(NPIX * c // (2 if bits == 4 else 1), OUT_DT[bits], 0)
+
+
+def nib_carrier(t, bits, c=COUT):
+    """device output rows (hawq4 for 4 bits) -> [C][256] int64"""
+    from hawq_amd.packing import unpack_hawq4
+    if bits != 4:
+        return carrier(t, c)
+    return unpack_hawq4(t.cpu().numpy().reshape(NPIX, c // 2)).astype(np.int64).T
+
+
+# (epilogue, out_bits, relu, clamp, second clamp): (3, 12) is inside the nibble, so the clamp and not the pack's width must hold it
+NIB_FORMS = [(lambda lib: lib.INCEP_REQUANT, 16, 0, (-32768, 32767), None), (lambda lib: lib.INCEP_REQUANT, 8, 1, (-128, 127), None),
+             (lambda lib: lib.INCEP_REQUANT, 4, 1, (0, 15), None), (lambda lib: lib.INCEP_REQUANT, 4, 1, (3, 12), None),
+             (lambda lib: lib.INCEP_REQUANT2, 8, 1, (-100, 127), (-128, 127)), (lambda lib: lib.INCEP_REQUANT2, 4, 1, (0, 15), (0, 15))]
+
+
+@pytest.mark.parametrize("form", range(len(NIB_FORMS)))
+def test_incep_nib_and_every_tile_at_the_corners(lib, form):
+    """hawq_incep_conv_nib on every tile id hawq_incep_conv_nib_ok accepts: every table of the list on accumulators driven by hawq4
+    operands; int16, int8 and hawq4 outputs, a clamp narrower than the nibble, and REQUANT2's second table walking through the scalar
+    corners."""
+    epi, out_bits, relu, clamp, clamp2 = NIB_FORMS[form]
+    epi = epi(lib)
+    launches = nib_plan()
+    inc = IncepNib(lib)
+    out = nib_out(out_bits)
+    a, t = inc.member(out, out_bits)
+    a.epilogue, a.relu, a.q_lo, a.q_hi = epi, relu, clamp[0], clamp[1]
+    ntiles = lib.load().hawq_incep_conv_nib_num_tiles()
+    ran, edges = set(), set()
+    for i, L in enumerate(launches):
+        inc.load(a, t, L)
+        second = None
+        if epi == lib.INCEP_REQUANT2:
+            second = (R.SCALAR_TABLES[(i * 5 + form) % len(R.SCALAR_TABLES)], clamp2)
+            (a.m2, a.ek2), (a.q2_lo, a.q2_hi) = second
+        want = incep_expect(L, relu, clamp, second)
+        first = requant(np.maximum(L.V, 0), L) if relu else L.Q
+        edges |= {x for x in (clamp[0] - 1, clamp[0], clamp[1], clamp[1] + 1) if (first == x).any()}
+        for tile in range(1, ntiles + 1):
+            if not lib.load().hawq_incep_conv_nib_ok(C.byref(a), tile):
+                continue
+            stale(out)
+            lib.call("hawq_incep_conv_nib", C.byref(a), tile, K.stream())
+            got = nib_carrier(out, out_bits)
+            bad = np.argwhere(got != want)
+            assert bad.size == 0, (form, i, tile, [(R.TABLES[L.tidx[c]][:3], int(L.V[c, p]), int(got[c, p]), int(want[c, p])) for c, p in bad[:5]])
+            ran.add(tile)
+    assert ran == {1, 2, 3}
+    # results exactly on both sides of both clamp edges were on the device (behind a ReLU, those that are not negative)
+    assert edges == {x for x in (clamp[0] - 1, clamp[0], clamp[1], clamp[1] + 1) if x >= 0 or not relu}
+
+
+@pytest.mark.parametrize("mask", [0b11, 0b01, 0b10])
+def test_incep_group_nib_at_the_corners(lib, mask):
+    """hawq_incep_conv_group_nib, two members on neighbouring launches of their plans, each as hawq4 (the nibble-driven conv) or as int8
+    (the int8-driven conv of `Incep`), on both group tiles: member 0 to 16 bits, member 1 to 4 bits as hawq4 and to 8 bits as int8."""
+    plans = [nib_plan() if (mask >> k_) & 1 else form_plan(0)[1] for k_ in range(2)]
+    srcs = {1: IncepNib(lib), 0: Incep(lib)}
+    bits = [16, 4 if mask & 2 else 8]
+    forms = [(0, (-32768, 32767)), (1, (0, 15) if mask & 2 else (-128, 127))]
+    outs = [nib_out(b) for b in bits]
+    members = [srcs[(mask >> k_) & 1].member(outs[k_], bits[k_]) for k_ in range(2)]
+    g = lib.IncepGroupArgs()
+    g.n = 2
+    ran = set()
+    for i in range(max(len(p) for p in plans)):
+        want = []
+        for k_, ((a, t), (relu, clamp)) in enumerate(zip(members, forms)):
+            Lk = plans[k_][(i + k_) % len(plans[k_])]
+            srcs[(mask >> k_) & 1].load(a, t, Lk)
+            a.epilogue, a.relu, a.q_lo, a.q_hi = lib.INCEP_REQUANT, relu, clamp[0], clamp[1]
+            g.conv[k_] = a
+            want.append(incep_expect(Lk, relu, clamp, None))
+        for tile in range(1, lib.load().hawq_incep_conv_group_nib_num_tiles() + 1):
+            assert lib.load().hawq_incep_conv_group_nib_ok(C.byref(g), mask, tile), (mask, tile)
+            for o in outs:
+                stale(o)
+            lib.call("hawq_incep_conv_group_nib", C.byref(g), mask, tile, K.stream())
+            for k_ in range(2):
+                assert np.array_equal(nib_carrier(outs[k_], bits[k_]), want[k_]), (mask, i, tile, k_)
+            ran.add(tile)
+    assert ran == {1, 2}
+
+
+@pytest.mark.parametrize("clamp", [(0, 15), (2, 13)])
+def test_incep_pool_v_requant_to_hawq4_at_the_scalar_corners(lib, clamp):
+    """The requant op of hawq_incep_pool_v storing hawq4 rows (out_bits 4), with the corner tables on the post side - the only side
+    this store has: int16 data holding the list's values for the table, into a channel slice of a wider nibble row."""
+    from hawq_amd.packing import unpack_hawq4
+    c, ldo, c_off = 64, 96, 16
+    x = dev(np.zeros((NPIX, c), np.int16))
+    out = out_buf(NPIX * ldo // 2, torch.uint8, 0)
+    rng = np.random.default_rng(8)
+    took, edges = 0, set()
+    for m, ek in R.SCALAR_TABLES:
+        lim = min(32767, (1 << (31 - (ek >> 8))) - 1)
+        vals = scalar_values(m, ek, 32767, signed=True)
+        v = rng.integers(-lim, lim + 1, (NPIX, c)).astype(np.int64)
+        v.reshape(-1)[:len(vals) * 23:23] = vals
+        R.check_contract(v, [m], [ek])
+        put(x, v)
+        a = lib.IncepPoolArgs()
+        a.in_, a.N, a.H, a.W, a.C, a.in_bits, a.in_pitch, a.out_bits, a.ldo, a.c_off = x.data_ptr(), 1, HW, HW, c, 16, c, 4, ldo, c_off
+        a.post, a.m2, a.ek2, a.lo2, a.hi2 = 1, m, ek, clamp[0], clamp[1]
+        a.out = out.data_ptr()
+        if not lib.load().hawq_incep_pool_v_ok(C.byref(a), lib.INCEP_POOL_OPS["hawq_incep_requant"]):
+            assert (ek >> 8) != 0, (m, ek)   # every table without a pre-shift is admitted
+            continue
+        raw = scalar(v, m, ek)
+        edges |= {e for e in (clamp[0] - 1, clamp[0], clamp[1], clamp[1] + 1) if (raw == e).any()}
+        out.fill_(0x77)
+        lib.call("hawq_incep_pool_v", C.byref(a), lib.INCEP_POOL_OPS["hawq_incep_requant"], K.stream())
+        got = unpack_hawq4(out.cpu().numpy().reshape(NPIX, ldo // 2)).astype(np.int64)
+        assert np.array_equal(got[:, c_off:c_off + c], np.clip(raw, *clamp)), (m, ek)
+        assert (np.delete(got, np.s_[c_off:c_off + c], axis=-1) == 7).all(), (m, ek)
+        took += 1
+    assert took >= 16 and edges == {clamp[0] - 1, clamp[0], clamp[1], clamp[1] + 1}

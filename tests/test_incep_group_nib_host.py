@@ -46,6 +46,36 @@ def test_extents_are_those_of_the_real_byte_widths():
     assert _ok([y4, z], 0b01, 2) and not _ok([y8, z], 0b01, 2)
 
 
+def _why(blocks, mask, tile):
+    """the reason hawq_incep_conv_group_nib gives for refusing the group (it is refused on the host, before any launch)"""
+    L = _lib().load()
+    assert L.hawq_incep_conv_group_nib(C.byref(group(blocks)), mask, tile, None) != 0
+    return L.hawq_last_error().decode()
+
+
+@pytest.mark.parametrize("tile", [1, 2])
+def test_neighbouring_nibble_slices_of_one_row_are_independent_until_they_overlap(tile):
+    from tests.test_gpu_incep_group_nib_kernels import LDO_ROW, ROW, row_blocks
+    ptrs = [(0x1000000, 0x100000 * (i + 1), 0x200000, AB, 0x300000, 0x300000) for i in range(3)]   # one input, one output row buffer
+    assert _ok(row_blocks(ptrs), 0b111, tile)
+    overlap = "two members write overlapping outputs"
+    middle_moved = (ROW[0], (16, 32), ROW[2])      # onto the first member's slice
+    first_widened = ((16, 32), ROW[1], ROW[2])     # into the middle member's
+    for row in (middle_moved, first_widened):
+        assert not _ok(row_blocks(ptrs, row), 0b111, tile) and overlap in _why(row_blocks(ptrs, row), 0b111, tile)
+    # One member stores 8 bits through the same base pointer: it is no slice of the nibble rows any more (another element width), and its
+    # bytes, 96 a pixel from byte 64 on, cover its neighbours' nibbles.  The extents are compared in bytes worked out in half bytes.
+    for i in range(3):
+        bits = tuple(8 if j == i else 4 for j in range(3))
+        assert not _ok(row_blocks(ptrs, bits=bits), 0b111, tile) and overlap in _why(row_blocks(ptrs, bits=bits), 0b111, tile)
+    # ... and the nibble rows end where half bytes say: 162 pixels of 48 bytes.  An 8-bit member from there on is independent of them;
+    # one row earlier it is not.
+    end = AB + 162 * LDO_ROW // 2
+    for out, ok in ((end, True), (end - LDO_ROW // 2, False)):
+        moved = [ptrs[0], ptrs[1], ptrs[2][:3] + (out,) + ptrs[2][4:]]
+        assert bool(_ok(row_blocks(moved, (ROW[0], ROW[1], (0, 16)), (4, 4, 8)), 0b111, tile)) == ok
+
+
 def test_nibble_groups_needs_nibble():
     from hawq_amd.engine_inception import InceptionEngine, PlanNotApplicable
     with pytest.raises(PlanNotApplicable, match="nibble_groups"):

@@ -71,3 +71,45 @@ def test_nib_ok_refusals_and_the_last_shape_every_tile_accepts():
     assert [ok(_block(Cout=64, ldo=64), t) for t in tiles] == [0, 1, 1] and [ok(_block(Cout=80, ldo=80), t) for t in tiles] == [1, 1, 1]
     assert [ok(_block(Cin=496), t) for t in tiles] == [1, 1, 0] and [ok(_block(Cin=512), t) for t in tiles] == [1, 1, 1]
     assert not ok(_block(N=2 ** 15, H=2048, W=2048), 2)   # 2^37 pixels: 2^31 blocks of 64
+
+
+# ---- the int32 bound, restated in tests/test_gpu_incep_nib_bound.py from the kernel's comment and not read from the library
+def test_the_bound_is_the_pinned_one():
+    from tests.test_gpu_incep_nib_bound import PINNED, WINDOWS, k_accepted, last_cin
+    assert PINNED == {"1x1": (1118480, 1118480, 1118496), "7x7": (22816, 1117984, 22832)}
+    for win, (last, K, first) in PINNED.items():
+        KH, KW = WINDOWS[win][:2]
+        assert last == last_cin(KH, KW) and K == KH * KW * last and first == last + 16
+        assert k_accepted(KH, KW, last) and not k_accepted(KH, KW, first)
+        assert 1920 * K <= 2 ** 31 - 1 < 1920 * KH * KW * first
+
+
+def test_nib_ok_agrees_with_the_restated_bound_on_every_tile():
+    from tests.test_gpu_incep_nib_bound import PINNED, shape
+    from tests.test_gpu_incep_nib_kernels import RAW, _block as block
+    lib = _lib.load()
+    tiles = range(1, lib.hawq_incep_conv_nib_num_tiles() + 1)
+    for win, (last, K, first) in PINNED.items():
+        for cout, at_last in ((16, [0, 1, 1]), (80, [1, 1, 1])):   # tile 1 is for more than 64 channels; K >= 512: tile 3 takes it
+            for cin, want in ((last, at_last), (first, [0, 0, 0])):
+                g, N = shape(win, cin, cout)
+                a = block(g, (0x1000,) * 6, RAW, 32, N=N)
+                assert [lib.hawq_incep_conv_nib_ok(C.byref(a), t) for t in tiles] == want, (win, cout, cin)
+        assert K >= 512
+
+
+def test_group_nib_ok_applies_the_bound_to_hawq4_members_only():
+    from tests.test_gpu_incep_group_nib_kernels import A, group
+    from tests.test_gpu_incep_nib_bound import PINNED, shape
+    from tests.test_gpu_incep_nib_kernels import RAW, _block as block
+    lib = _lib.load()
+    ok = lambda blocks, mask, tile: lib.hawq_incep_conv_group_nib_ok(C.byref(group(blocks)), mask, tile)   # noqa: E731
+    # made-up addresses far apart: the first refused 1x1 input is 6.7 MB as int8
+    small = block(A, (0x10000000, 0x100000, 0x200000, 0x20000000, 0x300000, 0x300000), RAW, 32)
+    for win, (last, _, first) in PINNED.items():
+        member = lambda cin: block(shape(win, cin, 16)[0], (0x30000000, 0x100000, 0x200000, 0x40000000, 0x300000, 0x300000), RAW, 32,   # noqa: E731
+                                   N=shape(win, cin, 16)[1])
+        for tile in (1, 2):
+            assert ok([small, member(last)], 0b10, tile) and ok([small, member(last)], 0b11, tile)
+            assert not ok([small, member(first)], 0b10, tile) and not ok([small, member(first)], 0b11, tile)
+            assert ok([small, member(first)], 0b00, tile) and ok([small, member(first)], 0b01, tile)   # the same geometry as int8

@@ -129,6 +129,47 @@ REFUSED = {
 }
 
 
+# out_bits 4 (hawq4 rows): what the check refuses, as (op, keyword arguments of _args) so that the GPU test can put the same
+# descriptions on device buffers and see that nothing is written
+POST4 = (1 << 30, 31, 0, 15)
+HAWQ4_REFUSED = {
+    "hawq4_hi2_16": (REQUANT, dict(C_=64, out_bits=4, post=(1 << 30, 31, 0, 16))),
+    "hawq4_lo2_negative": (REQUANT, dict(C_=64, out_bits=4, post=(1 << 30, 31, -1, 15))),
+    "hawq4_without_post": (REQUANT, dict(C_=64, out_bits=4, post=None)),
+    "hawq4_maxpool": (MAX3S2, dict(C_=64, out_bits=4, post=POST4)),
+    "hawq4_avgpool": (AVG3, dict(C_=64, out_bits=4, pre=PRE, post=POST4)),
+    "hawq4_global": (GLOBAL, dict(C_=64, out_bits=4, post=POST4)),
+    "hawq4_c_off_8": (REQUANT, dict(C_=16, out_bits=4, post=POST4, ldo=32, c_off=8)),
+}
+REFUSED.update({case: (op, lambda kw=kw: _args(**kw)) for case, (op, kw) in HAWQ4_REFUSED.items()})
+
+
+def test_hawq4_rows_are_the_requant_ops_with_a_post_clamp_inside_the_nibble():
+    """the neighbours of the hawq4 refusals that are taken, and that each refusal is about out_bits 4: the same description to 8 bits
+    is a launch"""
+    for kw in (dict(C_=64, post=POST4), dict(C_=64, post=(5 << 27, 31, 2, 13)), dict(C_=64, pre=PRE, post=POST4), dict(C_=64, in_bits=8, post=POST4),
+               dict(C_=16, post=POST4, ldo=48, c_off=16), dict(C_=48, post=POST4, in_pitch=112, in_off=48, ldo=96, c_off=32)):
+        assert _ok(_args(out_bits=4, **kw), REQUANT) == 1, kw
+    for case in ("hawq4_hi2_16", "hawq4_lo2_negative", "hawq4_maxpool", "hawq4_avgpool", "hawq4_global"):
+        op, kw = HAWQ4_REFUSED[case]
+        assert _ok(_args(**dict(kw, out_bits=8)), op) == 1, case
+
+
+def test_the_hawq4_cases_of_the_gpu_test_are_not_degenerate():
+    """tests/test_gpu_incep_pool_kernels.py asserts on its own reference that ties, both clamp edges, their outer neighbours and several
+    levels occur; here those assertions run without a device"""
+    from tests.test_gpu_incep_pool_kernels import SLICES, _case4, hawq4_cases
+    n = 0
+    for in_bits in (8, 16):
+        for pre in (False, True):
+            for where in SLICES:
+                for kw in hawq4_cases(in_bits, pre, where):
+                    xf, want = _case4(**kw)
+                    assert xf.dtype == (np.int8 if in_bits == 8 else np.int16) and want.shape == (2, 9, 7, kw["Cc"])
+                    n += 1
+    assert n == 32
+
+
 @pytest.mark.parametrize("case", sorted(REFUSED))
 def test_refused_descriptions_launch_nothing_and_say_why(case):
     from hawq_amd import _lib

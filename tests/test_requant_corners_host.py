@@ -97,6 +97,37 @@ def test_the_launch_plan_holds_every_pair_and_nothing_outside_a_contract():
         R.check_contract(np.array([[2 ** 16]]), [3], [34 | 15 << 8])
 
 
+def test_nibble_offsets_are_contiguous_ranges_two_hawq4_channels_produce():
+    for kind, (a0, a1) in R.NIB_INPUTS.items():
+        off = R.NIB_OFFSETS[kind]
+        assert off.shape == (256,) and min(a0.min(), a1.min()) >= 0 and max(a0.max(), a1.max()) <= 15
+        assert -8 <= min(R.NIB_WEIGHTS) and max(R.NIB_WEIGHTS) <= 7 and np.array_equal(off, R.NIB_WEIGHTS[0] * a0 + R.NIB_WEIGHTS[1] * a1)
+        assert set(off.tolist()) == set(range(int(off.min()), int(off.max()) + 1))   # contiguous: `centres` is valid for it
+    assert (int(R.NIB_OFFSETS["nib"].min()), int(R.NIB_OFFSETS["nib"].max())) == (-120, 15)
+    assert set(R.NIB_OFFSETS["nib_tiny"].tolist()) == {0, 1, 2}
+    assert not set(R.NIB_OFFSETS) & set(R.OFFSETS) and sorted(R.OFFSETS) == ["int8", "relu", "tiny", "tiny_relu"]
+    for t in R.TABLES:
+        offs = (0, 1, 2) if t.lim < 128 else tuple(range(-120, 16))
+        reach = {c + o for c in R.centres(t, (offs[0], offs[-1])) for o in offs}
+        assert set(t.values) <= reach and max(abs(v) for v in reach) <= t.lim
+
+
+def test_the_nibble_plan_holds_every_pair_and_nothing_outside_a_contract():
+    every = {(i, v) for i, t in enumerate(R.TABLES) for v in t.values}
+    launches = R.plan(R.TABLES, nibble=True)
+    assert R.NIB_UNREACHABLE == {}   # no pair is left out: the assertions below are on the whole list
+    assert R.coverage(launches, R.TABLES) == every
+    # a form with ReLU clamps the accumulator before the requant: what it can reach is the non-negative half, all of it
+    assert R.coverage(launches, R.TABLES, keep=lambda v: v >= 0) == {(i, v) for i, v in every if v >= 0}
+    assert {L.kind for L in launches} == {'nib', 'nib_tiny'}
+    for L in launches:
+        R.check_contract(L.V, L.m, L.ek)
+        assert L.V.shape == (128, 256) and np.array_equal(L.V, L.bias[:, None] + R.NIB_OFFSETS[L.kind][None, :])
+        assert np.abs(L.bias).max() < 2 ** 31
+    with pytest.raises(AssertionError):
+        R.plan(R.TABLES, relu_inputs=True, nibble=True)
+
+
 def test_the_array_form_of_the_reference_equals_the_python_integers():
     t, v = zip(*PAIRS)
     got = R.np_rne(np.array(v), np.array([x.m for x in t]), np.array([x.e for x in t]), np.array([x.k for x in t]))
