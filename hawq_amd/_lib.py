@@ -281,6 +281,8 @@ SIGNATURES = {
     "hawq_incep_conv_group_nib_num_tiles": [],
     "hawq_incep_conv_group_nib_ok": [C.POINTER(IncepGroupArgs), u32, i32],
     "hawq_incep_conv_group_nib": [C.POINTER(IncepGroupArgs), u32, i32, vp],
+    "hawq_incep_conv_group_nib_fan_ok": [C.POINTER(IncepGroupArgs), u32, C.POINTER(IncepFan), u32, i32],
+    "hawq_incep_conv_group_nib_fan": [C.POINTER(IncepGroupArgs), u32, C.POINTER(IncepFan), u32, i32, vp],
     "hawq_incep_conv_group_fan_ok": [C.POINTER(IncepGroupArgs), C.POINTER(IncepFan), i32],
     "hawq_incep_conv_group_fan": [C.POINTER(IncepGroupArgs), C.POINTER(IncepFan), i32, vp],
     "hawq_incep_stem_u8": [vp, vp, C.POINTER(IncepConvArgs), vp],

@@ -50,8 +50,10 @@ template <int BM, int BN, int WPX, int WCH, int KS>
 __device__ __forceinline__ void gn_nib_body(const hawq_incep_conv_args &a, const int Ho, const int Wo, const long long pblock,
                                             const int cblock, char *lds) {
 #define INCEP_NIB_BLOCK
+#define INCEP_NIB_STORED(p, cb, q)
 #include "incep_nib_body.h"
 #undef INCEP_NIB_BLOCK
+#undef INCEP_NIB_STORED
 }
 
 // The occupancy floor is the parents': 3 waves per SIMD on tile 1 (64 accumulator registers a lane), 4 on tile 2.  The two bodies

@@ -58,8 +58,10 @@ __global__ __launch_bounds__(64 * WPX * WCH * KS) void incep_nib_kernel(hawq_inc
 #define INCEP_NIB_BLOCK                                  \
     const long long pblock = (long long)blockIdx.x * BM; \
     const int cblock = blockIdx.y * BN;
+#define INCEP_NIB_STORED(p, cb, q)
 #include "incep_nib_body.h"
 #undef INCEP_NIB_BLOCK
+#undef INCEP_NIB_STORED
 }
 
 struct Geo {

@@ -1,6 +1,6 @@
 // The workgroup body of the nibble-packed InceptionV3 conv (the method: incep_nib.hip), from the tile constants to the closing brace of
-// the epilogue.  A fragment, not a header, shared as text the way incep_tile_body.h is (incep_tile.h says why): incep_nib.hip and
-// incep_group_nib.hip include it once each as the last statements of a function template (it returns from that function).  It expects
+// the epilogue.  A fragment, not a header, shared as text the way incep_tile_body.h is (incep_tile.h says why): incep_nib.hip,
+// incep_group_nib.hip and incep_fan_nib.hip include it once each as the last statements of a function template (it returns from that function).  It expects
 //   BM, BN, WPX, WCH, KS            the tile's template constants
 //   a, Ho, Wo                       the conv's argument block (hawq_incep_conv_args, wave-uniform; in and wgt hawq4) and its output map
 //   lds                             2 * (BM + BN) * 64 bytes of LDS, 16-byte aligned: the two stages
@@ -9,6 +9,9 @@
 //                                   cblock + BN - 1 (int): in scope, or defined by
 //   INCEP_NIB_BLOCK                 a macro, expanded once after P: empty where the includer got pblock and cblock from its caller,
 //                                   their definitions where it works them out itself (incep_nib_kernel)
+//   INCEP_NIB_STORED(p, cb, q)      a macro, expanded as a statement after a lane has stored the requantised channels cb .. cb + 15 of
+//                                   pixel p, with what it stored in int q[16]: the hook of the fan-out epilogue (incep_fan_nib.hip),
+//                                   empty otherwise (a RAW epilogue does not reach it)
     constexpr int NT = 64 * WPX * WCH * KS, RSTEP = NT / 8;
     constexpr int WM = BM / WPX / 32, WN = BN / WCH / 32;
     constexpr int APT = BM / RSTEP, BPT = BN / RSTEP, RPT = APT + BPT;
@@ -189,5 +192,6 @@
             } else {   // hawq4: 16 channels = two dwords at byte row / 2
                 *reinterpret_cast<v2i *>((char *)a.out + (row >> 1)) = v2i{(int)pack8_u4(q), (int)pack8_u4(q + 8)};
             }
+            INCEP_NIB_STORED(p, cb, q);
         }
     }

@@ -122,6 +122,26 @@ most K steps first (K / 64 int8, K / 128 hawq4: free, and unmeasured).  Which le
   refused); ``export_plan()`` writes ``"nibble_groups": [{"convs", "tile", "us"}]``; an engine without the option ignores it.
 ``group_launches`` lists (member conv indices, tile) per launch and ``nibble_group_masks`` the mask of each (bit k: member k is
 hawq4).  It composes with ``fast_pools``, ``fused_stem``, ``forward_uint8``, ``tune`` and ``plan``.  Not the default.
+
+Fan-out epilogues on a nibble plan.  ``InceptionEngine(model, nibble=True, nibble_fan=True)`` folds the entry requants of a nibble plan
+into the convs that wrote the concat buffer, as ``fan_out`` does on an int8 plan, through ``hawq_incep_conv_group_nib_fan``
+(hawq_amd/csrc/incep_fan_nib.hip): the mixed-form grouped launch whose members store every fan output as int8 or as hawq4 rows, one
+``fan_mask`` bit per output.  ``fan_out`` names the int8 launch and still does not compose with ``nibble``; ``nibble_fan`` without
+``nibble`` raises ``PlanNotApplicable``.  The nibble choice and the group choice are made first, exactly as without the option; then
+``fan_boundaries(launches, issued)`` reads the boundaries with every entry requant as the nibble plan issues it (``out_bits`` 4 into
+its own hawq4 buffer, or the int8 record), so that a fan target carries that block's buffer, clamp and form (``"forms"``).  Residual
+channel ranges (units 4, 9, 10) stay with the entry requants, shortened; a boundary whose hawq4 entry requant ``hawq_incep_pool_v``
+does not take on such a range is no candidate.  A producer launch is a level of ``nibble_groups`` with its members' fans, or a single
+conv as a group of one (its mask bit set if it is a nibble conv).  Which boundaries, and on which of the launch's two tiles:
+* neither ``tune`` nor a ``"nibble_fan"`` field in ``plan``: every candidate the library takes, each producer launch on tile 2, else 1;
+* ``tune=True``: per boundary the two blocks ``fan_out`` times, on the buffers of a forward of the chosen nibble plan - its producer
+  launches and entry requants as that plan issues them against the fan launches and the residual requants - kept only if the second
+  is faster;
+* ``plan=`` with the field: exactly its entries (``check_fan_out`` with the new check); ``export_plan()`` writes ``"nibble_fan":
+  [{"unit", "tiles", "us"}]``; an engine without the option ignores it.
+``fan_launches`` and ``residual_requants`` report as for ``fan_out``, ``nibble_fan_masks`` lists the ``fan_mask`` of each fan launch
+beside ``nibble_group_masks``.  It composes with ``nibble_groups``, ``fast_pools``, ``fused_stem``, ``forward_uint8``, ``tune`` and
+``plan``.  Not the default (DESIGN.md 10.3 has what the tuner keeps).
 """
 from __future__ import annotations
 
@@ -184,21 +204,23 @@ def launch_digest(keys):
     return hashlib.sha256(json.dumps([list(map(int, k)) for k in keys], separators=(",", ":")).encode()).hexdigest()
 
 
-def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None, nibble_groups=None):
+def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None, nibble_groups=None, nibble_fan=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
     and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
     ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field, and with `fan_out`
     (a fan-out engine's ``{"unit": k, "tiles": {launch: id}, "us": {...}}`` entries) the ``"fan_out"`` field; `nibble_groups`
-    (entries as `groups`, tile ids of ``hawq_incep_conv_group_nib``) the ``"nibble_groups"`` field"""
+    (entries as `groups`, tile ids of ``hawq_incep_conv_group_nib``) the ``"nibble_groups"`` field; `nibble_fan` (entries as
+    `fan_out`, tile ids of ``hawq_incep_conv_group_nib_fan``) the ``"nibble_fan"`` field"""
     plan = {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
             "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
             "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
     if groups is not None:
         plan["groups"] = [{"convs": [int(c) for c in g["convs"]], "tile": int(g["tile"]),
                            "us": {str(k): round(float(v), 3) for k, v in g.get("us", {}).items()}} for g in groups]
-    if fan_out is not None:
-        plan["fan_out"] = [{"unit": int(f["unit"]), "tiles": {str(k): int(t) for k, t in f["tiles"].items()},
-                            "us": {str(k): round(float(v), 3) for k, v in f.get("us", {}).items()}} for f in fan_out]
+    for field, fans in (("fan_out", fan_out), ("nibble_fan", nibble_fan)):
+        if fans is not None:
+            plan[field] = [{"unit": int(f["unit"]), "tiles": {str(k): int(t) for k, t in f["tiles"].items()},
+                            "us": {str(k): round(float(v), 3) for k, v in f.get("us", {}).items()}} for f in fans]
     if nibble is not None:   # a nibble engine's (conv -> nibble tile, conv -> {tile: microseconds})
         plan["nibble"] = [[int(c), int(t)] for c, t in sorted(nibble[0].items())]
         plan["nibble_us"] = {str(c): {str(t): round(float(v), 3) for t, v in d.items()} for c, d in sorted(nibble[1].items())}
@@ -309,31 +331,35 @@ def grouped_order(launches, groups):
     return order
 
 
-def fan_boundaries(launches):
-    """The boundary in front of every unit of `launches`, in unit order, read from the records' tags and argument blocks alone:
+def fan_boundaries(launches, issued=None):
+    """The boundary in front of every unit of `launches`, in unit order, read from the records' tags and argument blocks alone
+    (`issued`, of a nibble plan: entry requant record -> the block the plan issues in its place, with ``out_bits`` 4 into a hawq4
+    buffer of its own; a fan target then carries that block's buffer, clamp and form):
     * ``"requants"``: the unit's level-0 ``hawq_incep_requant`` records (the ``q_input_act`` of its conv branches), as indices;
     * ``"slices"``: ``(c_off, C, producer)`` for every slice of the buffer they read that an earlier record writes, by channel: the
       index of the conv record that produced it (REQUANT2, 16 bits, into that buffer), or None for a pool / requant record;
     * ``"producers"``: per such conv record index its fan targets, one per entry requant and in their order:
       ``(out, ldo, (m, ek, lo, hi), c_off, Cout)`` - that record's output buffer, pitch and ``post`` table, and where the producer's
       channels go in it;
+    * ``"forms"``: per entry requant the ``out_bits`` it is issued with - 8, or 4 for a block of `issued`;
     * ``"residual"``: the channel ranges ``(in_off, C)`` of the input that no conv produced, adjacent ones merged - what is left for
       the entry requants to do;
     * ``"candidate"``: at least one slice is conv-produced (and the entry requants are plain: one 16-bit source and range, ``post``
-      only, int8 out)."""
+      only, int8 out - or hawq4, as `issued`)."""
     out = []
     for k in sorted({r.place for r in launches if isinstance(r.place, int)}):
         entry = [i for i, r in enumerate(launches)
                  if r.place == k and r.level == 0 and r.kind == "pool" and r.name == "hawq_incep_requant"]
-        b = {"unit": k, "requants": entry, "slices": [], "producers": {}, "residual": [], "candidate": False}
+        b = {"unit": k, "requants": entry, "slices": [], "producers": {}, "residual": [], "candidate": False, "forms": []}
         out.append(b)
         if not entry:
             continue
-        blocks = [launches[i].args[0] for i in entry]
+        blocks = [(issued or {}).get(launches[i], launches[i].args[0]) for i in entry]
+        b["forms"] = [4 if launches[i] in (issued or {}) else 8 for i in entry]
         f = blocks[0]
         src, pitch, lo, hi = f.in_, f.in_pitch, f.in_off, f.in_off + f.C
-        plain = all((a.in_, a.in_pitch, a.in_off, a.C, a.in_bits, a.out_bits, a.pre, a.post) == (src, pitch, lo, f.C, 16, 8, 0, 1)
-                    for a in blocks)
+        plain = all((a.in_, a.in_pitch, a.in_off, a.C, a.in_bits, a.out_bits, a.pre, a.post) == (src, pitch, lo, f.C, 16, bits, 0, 1)
+                    for a, bits in zip(blocks, b["forms"]))
         for i, r in enumerate(launches[:entry[0]]):
             if r.kind not in ("conv", "pool"):
                 continue
@@ -388,6 +414,7 @@ def check_fan_out(entries, candidates, ok):
 
 
 _FAN_TILES = (3, 2, 1, 4)   # an untuned fan-out launch: tile 3, else the first of these the library takes
+_NIB_FAN_TILES = (2, 1)     # of ``hawq_incep_conv_group_nib_fan``: 128 px x 64 ch, else 128 x 128
 
 
 def nibble_storage(tensors, conv_ok):
@@ -423,16 +450,19 @@ class _T:
 class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
                  fused_stem: bool = False, grouped: bool = False, fan_out: bool = False, nibble: bool = False,
-                 nibble_groups: bool = False):
+                 nibble_groups: bool = False, nibble_fan: bool = False):
         self.model, self.use_graph = model, use_graph
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
         self.grouped, self.fan_out, self.nibble, self.nibble_groups = bool(grouped), bool(fan_out), bool(nibble), bool(nibble_groups)
+        self.nibble_fan = bool(nibble_fan)
         if self.nibble and (self.grouped or self.fan_out):
             raise PlanNotApplicable("nibble=True does not compose with grouped or fan_out: their launches have no nibble form")
         if self.nibble_groups and not self.nibble:
             raise PlanNotApplicable("nibble_groups=True groups the launches of a nibble plan: it needs nibble=True")
+        if self.nibble_fan and not self.nibble:
+            raise PlanNotApplicable("nibble_fan=True folds the entry requants of a nibble plan: it needs nibble=True")
         self.nibble_convs, self.nibble_tensors, self.nibble_us, self.nibble_bytes = {}, [], {}, {}
-        self.group_launches, self.group_candidates, self.nibble_group_masks = [], [], []
+        self.group_launches, self.group_candidates, self.nibble_group_masks, self.nibble_fan_masks = [], [], [], []
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         self.n_timing_launches = 0           # conv launches issued to time tiles (0 for a default or a replayed plan)
         self.conv_tiles, self.conv_us = None, None
@@ -615,7 +645,7 @@ class InceptionEngine(GraphRunner):
         self._tensors, self._conv_io = [], {}   # the tensors convs read, in the order they are made; conv -> (src, out, weights)
         self.nibble_convs, self.nibble_tensors, self.nibble_us, self.nibble_bytes = {}, [], {}, {}
         self.conv_tiles, self.conv_us = None, None
-        self.group_launches, self.group_candidates, self.nibble_group_masks = [], [], []
+        self.group_launches, self.group_candidates, self.nibble_group_masks, self.nibble_fan_masks = [], [], [], []
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
@@ -766,9 +796,27 @@ class InceptionEngine(GraphRunner):
         gf = self._fan_args(convs, b)
         return gf is not None and bool(_lib.load().hawq_incep_conv_group_fan_ok(C.byref(gf[0]), gf[1], tile))
 
-    def _residual_args(self, r, off, c):
-        """a fresh block for entry requant `r` on the input channels off .. off + c - 1 only"""
-        a = _lib.IncepPoolArgs.from_buffer_copy(r.args[0])
+    def _nfan_args(self, convs, b, nib):
+        """(group block, mask, fan array, fan_mask) of one ``hawq_incep_conv_group_nib_fan`` launch: the members as ``_ngroup_args``
+        lays them out, their targets in boundary `b` as ``_fan_args`` does, and a ``fan_mask`` bit for every target whose entry
+        requant the plan issues hawq4 (``b["forms"]``); None if a producer has more targets than a fan holds"""
+        gf = self._fan_args(convs, b)
+        if gf is None:
+            return None
+        g, mask = self._ngroup_args(convs, nib)
+        fan_mask = sum(1 << (_lib.INCEP_FAN_MAX * k + j) for k in range(len(convs)) for j in range(gf[1][k].n) if b["forms"][j] == 4)
+        return g, mask, gf[1], fan_mask
+
+    def _nfan_ok(self, convs, b, tile, nib):
+        if not 1 <= len(convs) <= _lib.INCEP_GROUP_MAX or not isinstance(tile, int) or isinstance(tile, bool):
+            return False
+        a = self._nfan_args(convs, b, nib)
+        return a is not None and bool(_lib.load().hawq_incep_conv_group_nib_fan_ok(C.byref(a[0]), a[1], a[2], a[3], tile))
+
+    def _residual_args(self, r, off, c, block=None):
+        """a fresh block for entry requant `r` (`block`: the block a nibble plan issues in its place) on the input channels
+        off .. off + c - 1 only"""
+        a = _lib.IncepPoolArgs.from_buffer_copy(block or r.args[0])
         a.c_off, a.in_off, a.C = a.c_off + off - a.in_off, off, c
         return a
 
@@ -776,7 +824,7 @@ class InceptionEngine(GraphRunner):
     def _choose(self, batch):
         """What a plan decides, as one value: (tile id per conv launch, or None; grouped launches [(member conv indices, tile)], or
         None on an engine without ``grouped`` - the mixed-form launches of a ``nibble_groups`` engine take this place -; fan-out boundaries [(boundary, {producer launch: tile})], or None on an engine
-        without ``fan_out``).  From ``self.plan``, else from timing (``tune``), else the defaults: no tiles, every level of two or
+        without ``fan_out`` - those of a ``nibble_fan`` engine take this place -).  From ``self.plan``, else from timing (``tune``), else the defaults: no tiles, every level of two or
         more convs on tile 3 that the library takes, and every candidate boundary whose producer launches the library takes.  Leaves
         ``conv_tiles`` and what was recorded or measured (``conv_us``, ``group_candidates``, ``fan_candidates``) for the readers
         and ``export_plan``."""
@@ -809,7 +857,8 @@ class InceptionEngine(GraphRunner):
         nib = self._choose_nibbles(T) if self.nibble else None
         if self.nibble_groups:   # the second component then holds the mixed-form launches (``grouped`` is off: the constructor)
             groups = self._choose_nibble_groups(self.conv_tiles, nib)
-        return self.conv_tiles, groups, self._choose_fans(self.conv_tiles, groups) if self.fan_out else None, nib
+        fans = self._choose_fans(self.conv_tiles, groups, nib if self.nibble_fan else None) if self.fan_out or self.nibble_fan else None
+        return self.conv_tiles, groups, fans, nib
 
     # ------------------------------------------------------------------ nibbles
     def _nib_ok(self, c, tile, block=None):
@@ -996,38 +1045,72 @@ class InceptionEngine(GraphRunner):
         self._choice = (None, None, None, None)
         return out
 
-    def _choose_fans(self, tiles, groups):
+    def _choose_fans(self, tiles, groups, nib=None):
         """the third component: from the plan's ``"fan_out"`` field if it has one, else timed against the plain launches (``tune``),
-        else every candidate boundary on the default tiles (a tile plan without the field fixes the other convs' tiles only)"""
-        cands = {b["unit"]: b for b in fan_boundaries(self._launches) if b["candidate"]}
+        else every candidate boundary on the default tiles (a tile plan without the field fixes the other convs' tiles only).
+        With `nib` (the nibble convs of a ``nibble_fan`` engine) the same for the ``"nibble_fan"`` field, on the launches of
+        ``hawq_incep_conv_group_nib_fan`` and the entry requants as the nibble plan issues them; a boundary whose hawq4 entry
+        requant ``hawq_incep_pool_v`` does not take on a residual range is no candidate."""
+        if nib is None:
+            field, order, bounds, ok = "fan_out", _FAN_TILES, fan_boundaries(self._launches), self._fan_ok
+        else:
+            field, order, bounds = "nibble_fan", _NIB_FAN_TILES, fan_boundaries(self._launches, self._nib_pool)
+            ok = partial(self._nfan_ok, nib=nib)
+            bounds = [b for b in bounds if all(
+                _lib.load().hawq_incep_pool_v_ok(C.byref(self._residual_args(r, off, c, self._nib_pool[r])), r.ref)
+                for r in map(self._launches.__getitem__, b["requants"]) if r in self._nib_pool for off, c in b["residual"])]
+        cands = {b["unit"]: b for b in bounds if b["candidate"]}
         sets = {k: self._fan_sets(b, groups) for k, b in cands.items()}
-        if self.plan is not None and "fan_out" in self.plan:
+        if self.plan is not None and field in self.plan:
             by_key = {(k, fan_key(s)): s for k in cands for s in sets[k]}
-            got = check_fan_out(self.plan["fan_out"], {k: [fan_key(s) for s in sets[k]] for k in cands},
-                                lambda k, key, t: self._fan_ok(by_key[k, key], cands[k], t))
-            us = {e["unit"]: dict(e.get("us", {})) for e in self.plan["fan_out"]}
+            got = check_fan_out(self.plan[field], {k: [fan_key(s) for s in sets[k]] for k in cands},
+                                lambda k, key, t: ok(by_key[k, key], cands[k], t))
+            us = {e["unit"]: dict(e.get("us", {})) for e in self.plan[field]}
             self.fan_candidates = [{"unit": k, "tiles": dict(t), "us": us[k], "kept": True} for k, t in got]
             return [(cands[k], {by_key[k, key]: t for key, t in tl.items()}) for k, tl in got]
-        accepted = {k: {s: [t for t in _FAN_TILES if self._fan_ok(s, b, t)] for s in sets[k]} for k, b in cands.items()}
+        accepted = {k: {s: [t for t in order if ok(s, b, t)] for s in sets[k]} for k, b in cands.items()}
         able = [k for k in cands if all(accepted[k][s] for s in sets[k])]   # a boundary with a refused producer launch is not chosen
         if self.tune and self.plan is None:
-            for k, rec in zip(able, self._time_fans([cands[k] for k in able], [accepted[k] for k in able], tiles, groups)):
+            for k, rec in zip(able, self._time_fans([cands[k] for k in able], [accepted[k] for k in able], tiles, groups, nib)):
                 self.fan_candidates.append({"unit": k, **rec})
         else:
             self.fan_candidates = [{"unit": k, "tiles": {fan_key(s): accepted[k][s][0] for s in sets[k]}, "us": {}, "kept": True}
                                    for k in able]
         return [(cands[f["unit"]], {s: f["tiles"][fan_key(s)] for s in sets[f["unit"]]}) for f in self.fan_candidates if f["kept"]]
 
-    def _time_fans(self, bounds, accepted, tiles, groups):
-        """Per boundary of `bounds`, on the real buffers as ``_time`` left them (every launch here is a pure function of buffers it
-        does not write): ``"plain"``, the microseconds of its producer launches as (tiles, groups) issue them followed by its entry
+    def _time_fans(self, bounds, accepted, tiles, groups, nib=None):
+        """Per boundary of `bounds`, on the real buffers as ``_time`` left them - with `nib`, after a forward of the chosen nibble
+        plan (tiles, groups, nib), whose launches and blocks then stand for the int8 ones below - (every launch here is a pure
+        function of buffers it does not write): ``"plain"``, the microseconds of its producer launches as (tiles, groups) issue them followed by its entry
         requants, one block; every producer launch with its fan on every accepted tile (``"<launch>@<tile>"``); and ``"fan"``, one
         block of the fan-out launches on their fastest tiles followed by the residual requants.  Kept if fan < plain."""
         sp, lib, out = self.stream.cuda_stream, _lib.load(), []
 
-        def pool(a, ref, name):
-            fast = self.fast_pools and lib.hawq_incep_pool_v_ok(C.byref(a), ref)
+        def pool(a, ref, name):   # only the vectorised family stores hawq4
+            fast = a.out_bits == 4 or (self.fast_pools and lib.hawq_incep_pool_v_ok(C.byref(a), ref))
             return partial(_lib.call, "hawq_incep_pool_v", C.byref(a), ref, sp) if fast else partial(_lib.call, name, C.byref(a), sp)
+
+        def producers(s, gtile):   # the launch that holds the producers `s` as the rest of the choice issues it
+            if nib is None and s in gtile:
+                g = self._group_args(s)
+                keep.append(g)
+                return partial(_lib.call, "hawq_incep_conv_group", C.byref(g), int(gtile[s]), sp)
+            if s in gtile:
+                g, mask = self._ngroup_args(s, nib)
+                keep.append(g)
+                return partial(_lib.call, "hawq_incep_conv_group_nib", C.byref(g), mask, int(gtile[s]), sp)
+            if nib is not None and s[0] in nib:
+                return partial(_lib.call, "hawq_incep_conv_nib", C.byref(self._nib_conv[s[0]]), int(nib[s[0]]), sp)
+            return partial(_lib.call, "hawq_incep_conv_tiled", C.byref(self._convs[s[0]].args[0]), int(tiles[s[0]]), sp)
+
+        def fan_launch(s, b, t):
+            if nib is None:
+                g, f = self._fan_args(s, b)
+                keep.extend([g, f])
+                return partial(_lib.call, "hawq_incep_conv_group_fan", C.byref(g), f, t, sp)
+            g, mask, f, fan_mask = self._nfan_args(s, b, nib)
+            keep.extend([g, f])
+            return partial(_lib.call, "hawq_incep_conv_group_nib_fan", C.byref(g), mask, f, fan_mask, t, sp)
 
         def block(ops):
             def run():
@@ -1039,27 +1122,26 @@ class InceptionEngine(GraphRunner):
         with EventTimer(sp, _TUNE_REPS + 1) as ev:
             torch.cuda.synchronize(self.dev)
             with torch.cuda.stream(self.stream):
+                if nib is not None:
+                    self._choice = (tiles, groups, None, nib)
+                    for op in self._write():
+                        op()
+                    self._choice = (None, None, None, None)
                 for b, acc in zip(bounds, accepted):
                     gtile = {tuple(c): t for c, t in groups or []}
                     plain, fan, us, chosen, keep = [], [], {}, {}, []
                     for s in acc:
-                        if s in gtile:
-                            g = self._group_args(s)
-                            keep.append(g)
-                            plain.append(partial(_lib.call, "hawq_incep_conv_group", C.byref(g), int(gtile[s]), sp))
-                        else:
-                            plain.append(partial(_lib.call, "hawq_incep_conv_tiled", C.byref(self._convs[s[0]].args[0]), int(tiles[s[0]]), sp))
-                        g, f = self._fan_args(s, b)
-                        keep += [g, f]
+                        plain.append(producers(s, gtile))
                         for t in acc[s]:
-                            us[f"{fan_key(s)}@{t}"] = block([partial(_lib.call, "hawq_incep_conv_group_fan", C.byref(g), f, t, sp)])
+                            us[f"{fan_key(s)}@{t}"] = block([fan_launch(s, b, t)])
                         chosen[s] = min(acc[s], key=lambda t: (us[f"{fan_key(s)}@{t}"], t))
-                        fan.append(partial(_lib.call, "hawq_incep_conv_group_fan", C.byref(g), f, chosen[s], sp))
+                        fan.append(fan_launch(s, b, chosen[s]))
                     for i in b["requants"]:
                         r = self._launches[i]
-                        plain.append(pool(r.args[0], r.ref, r.name))
+                        issued = self._nib_pool.get(r) if nib is not None else None
+                        plain.append(pool(issued or r.args[0], r.ref, r.name))
                         for off, c in b["residual"]:
-                            a = self._residual_args(r, off, c)
+                            a = self._residual_args(r, off, c, issued)
                             keep.append(a)
                             fan.append(pool(a, r.ref, r.name))
                     us["plain"], us["fan"] = block(plain), block(fan)
@@ -1098,8 +1180,9 @@ class InceptionEngine(GraphRunner):
         groups = [g for g in self.group_candidates if g["kept"]] if self.grouped else None
         fans = [f for f in self.fan_candidates if f["kept"]] if self.fan_out else None
         ngroups = [g for g in self.group_candidates if g["kept"]] if self.nibble_groups else None
+        nfans = [f for f in self.fan_candidates if f["kept"]] if self.nibble_fan else None
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
-                         groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None, ngroups)
+                         groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None, ngroups, nfans)
 
     # ------------------------------------------------------------------ the writer
     def _write(self, u8=False):
@@ -1137,7 +1220,7 @@ class InceptionEngine(GraphRunner):
             ops = [op("hawq_incep_stem_f32", self.x_in.data_ptr(), *self._input_quant(), C.byref(self._stem_a))]
         else:
             ops = [single(r) for r in launches[:head]]
-        n_stem, issued, masks, fanned, residual = len(ops), [], [], [], []
+        n_stem, issued, masks, fanned, fmasks, residual = len(ops), [], [], [], [], []
         at = {r: min(i, n_stem - 1) for i, r in enumerate(launches[:head])}
         order = [(False, i) for i in range(len(launches))] if groups is None else grouped_order(launches, groups)
         for is_group, i in order[head:]:   # the stem stays in place in either order
@@ -1145,10 +1228,17 @@ class InceptionEngine(GraphRunner):
             convs, tile = groups[i] if is_group else ([r.ref], None) if r.kind == "conv" else (None, None)
             if convs is not None and tuple(convs) in fan_of:   # a producer launch of a chosen boundary, alone or grouped
                 b, tile = fan_of[tuple(convs)]
-                g, f = self._fan_args(convs, b)
-                self._keep += [g, f]
                 at.update((self._convs[c], len(ops)) for c in convs)
-                ops.append(op("hawq_incep_conv_group_fan", C.byref(g), f, int(tile)))
+                if self.nibble_fan:   # members and fan outputs of either form
+                    g, mask, f, fan_mask = self._nfan_args(convs, b, nib)
+                    ops.append(op("hawq_incep_conv_group_nib_fan", C.byref(g), mask, f, fan_mask, int(tile)))
+                    fmasks.append(fan_mask)
+                    if is_group:
+                        masks.append(mask)
+                else:
+                    g, f = self._fan_args(convs, b)
+                    ops.append(op("hawq_incep_conv_group_fan", C.byref(g), f, int(tile)))
+                self._keep += [g, f]
                 fanned.append((b["unit"], list(convs), int(tile)))
                 if is_group:
                     issued.append((list(convs), int(tile)))
@@ -1169,16 +1259,16 @@ class InceptionEngine(GraphRunner):
                 b = entry[i]
                 at[r] = len(ops) if b["residual"] else at[launches[min(b["producers"])]]
                 for off, c in b["residual"]:
-                    a = self._residual_args(r, off, c)
+                    a = self._residual_args(r, off, c, self._nib_pool.get(r) if nib else None)
                     self._keep.append(a)
-                    fast = self.fast_pools and lib.hawq_incep_pool_v_ok(C.byref(a), r.ref)
+                    fast = a.out_bits == 4 or (self.fast_pools and lib.hawq_incep_pool_v_ok(C.byref(a), r.ref))   # hawq4: pool_v only
                     ops.append(op("hawq_incep_pool_v", C.byref(a), r.ref) if fast else op(r.name, C.byref(a)))
                     residual.append((b["unit"], i, off, c))
             else:
                 at[r] = len(ops)
                 ops.append(single(r))
         self._at, self._tail, self.group_launches, self.nibble_group_masks = at, ops[n_stem:], issued, masks
-        self.fan_launches, self.residual_requants = fanned, residual
+        self.fan_launches, self.residual_requants, self.nibble_fan_masks = fanned, residual, fmasks
         return ops
 
     def _launch_chain(self, u8):

@@ -643,6 +643,29 @@ typedef struct hawq_incep_fan {
 } hawq_incep_fan;
 int hawq_incep_conv_group_fan_ok(const hawq_incep_group_args *g, const hawq_incep_fan *fan /* [g->n] */, int tile);
 int hawq_incep_conv_group_fan(const hawq_incep_group_args *g, const hawq_incep_fan *fan, int tile, void *stream);
+/* The mixed-form grouped launch with a fan-out epilogue (incep_fan_nib.hip): hawq_incep_conv_group_nib whose members store the next
+ * unit's branch inputs as hawq_incep_conv_group_fan's do, each fan output as int8 or as hawq4 rows.
+ *   hawq_incep_conv_group_nib_fan:    grid, tile ids (1, 2) and `mask` are hawq_incep_conv_group_nib's: member i writes, byte for byte,
+ *       what hawq_incep_conv_nib (mask bit i set) or hawq_incep_conv_tiled (clear) writes on that shape.  In addition, for
+ *       j < fan[i].n, output pixel p and channel co of member i, with s = clamp(dyadic_rne(y; m, ek), lo, hi) of the element y the
+ *       member stored as its primary output (after its last clamp):
+ *           bit 4 i + j of fan_mask clear:  to[j].out[p * ldo + c_off + co] = (int8) s
+ *           set:  nibble p * ldo + c_off + co of to[j].out = s, in hawq4 order (16 channels = the 8 bytes at (p * ldo + c_off + cb) / 2,
+ *                 as the convs' out_bits 4 store writes them); ldo and c_off count elements
+ *       A member of either operand form may carry fan outputs of either form.  Other channels of a fan row are never touched.  The
+ *       descriptors travel as kernel arguments (2320 bytes in all).
+ *   hawq_incep_conv_group_nib_fan_ok: 1 if the launch takes this description.  Host arithmetic only: nothing is dereferenced or
+ *       launched, no device is needed.  It needs hawq_incep_conv_group_nib_ok(g, mask, tile); of every fan output what
+ *       hawq_incep_conv_group_fan_ok needs (n in 0 .. 4, no fan on a RAW member, the dyadic table, out 16-byte aligned, ldo and c_off
+ *       multiples of 16, ldo >= c_off + Cout), with 0 <= lo <= hi <= 15 for a hawq4 output and -128 <= lo <= hi <= 127 for an int8 one;
+ *       no fan_mask bit for a member >= n or an output >= fan[i].n; and no fan output that meets a member's input, a member's primary
+ *       output or another fan output, by hawq_incep_conv_group_ok's two rules on real byte widths (half a byte per hawq4 element).
+ * fan points to g->n entries.  A refused call returns non-zero (the reason, with member and fan output, in hawq_last_error()), launches
+ * nothing, writes nothing.  Not covered: the K-split tiles, 16-bit fan outputs, fans of the pool kernels. */
+int hawq_incep_conv_group_nib_fan_ok(const hawq_incep_group_args *g, uint32_t mask, const hawq_incep_fan *fan /* [g->n] */,
+                                     uint32_t fan_mask, int tile);
+int hawq_incep_conv_group_nib_fan(const hawq_incep_group_args *g, uint32_t mask, const hawq_incep_fan *fan, uint32_t fan_mask, int tile,
+                                  void *stream);
 /* InceptionV3's input QuantAct + Conv2d_1a_3x3 from uint8 images in one launch (incep_stem.hip): Q_InceptInitBlock's q_input_activ and
  * q_conv1 (q_inceptionv3.py of the reference) on the tensor that ToTensor + Normalize (quant_train.py:432-440) make of the image, with
  * the QuantAct as a table look-up (quant_modules.py:271-274; lut int8 [3][256] from hawq_amd.quant_utils.input_quant_lut).

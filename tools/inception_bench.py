@@ -49,6 +49,7 @@ producer launches + residual requants, in microseconds, kept or not.
     python tools/inception_bench.py --fan-out [--grouped] --batches 1,16,128 [--blocks 6]
     python tools/inception_bench.py --nibble [--pools] --scheme uniform4 --batches 1,128 [--blocks 6]
     python tools/inception_bench.py --nibble-groups [--pools] --scheme uniform4 --batches 128,1 [--blocks 6]
+    python tools/inception_bench.py --nibble-fan [--pools] --scheme uniform4 --batches 128,1 [--blocks 6]
 """
 import argparse
 import json
@@ -502,6 +503,47 @@ def compare_nibble_groups(model, args, b):
     return ng
 
 
+def compare_nibble_fan(model, args, b):
+    """the best nibble forward without the option - nibble=True with nibble_groups=True - the same with nibble_fan=True, and the best
+    int8 one - grouped=True with fan_out=True - all tuned, alternating blocks; the per-boundary times the tuner saw (its producer
+    launches and entry requants against the fan launches and residual requants, the forms of the fan outputs, kept or not);
+    returns the tuned nibble_fan engine"""
+    from hawq_amd.engine_inception import InceptionEngine, fan_boundaries
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    with torch.no_grad():
+        opts = dict(fast_pools=args.pools, tune=True)
+        engines = {"nibble_groups_tuned": InceptionEngine(model, nibble=True, nibble_groups=True, **opts),
+                   "nibble_groups_fan_tuned": InceptionEngine(model, nibble=True, nibble_groups=True, nibble_fan=True, **opts),
+                   "grouped_fan_out_tuned": InceptionEngine(model, grouped=True, fan_out=True, **opts)}
+        y = {k: e(x) for k, e in engines.items()}
+        equal = all(bool(torch.equal(v, y["nibble_groups_tuned"])) for v in y.values())
+        assert equal, "the logits of the three plans differ"
+        nf = engines["nibble_groups_fan_tuned"]
+        forms = {bd["unit"]: bd["forms"] for bd in fan_boundaries(nf._launches, nf._nib_pool)}
+        print(f"# {wl}: boundary (unit) | fan outputs hawq4 / all | producer launches: tile | plain us | fan us | kept")
+        for f in nf.fan_candidates:
+            print(f"# {f['unit']} | {forms[f['unit']].count(4)} / {len(forms[f['unit']])} | {f['tiles']} | {f['us']['plain']:.1f} | "
+                  f"{f['us']['fan']:.1f} | {'yes' if f['kept'] else '-'}")
+        print(json.dumps({"workload": wl, "boundaries": len(nf.fan_candidates), "kept": [f["unit"] for f in nf.fan_candidates if f["kept"]],
+                          "fan_launches": len(nf.fan_launches), "residual_requants": len(nf.residual_requants)}), flush=True)
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": k, "fast_pools": bool(args.pools), "ms_per_batch": round(mean, 4),
+                              "images_per_s": round(b * 1000.0 / mean, 1), "block_min_ms": round(min(v), 4),
+                              "block_max_ms": round(max(v), 4), "blocks": len(v), "steps": args.steps, "launches": e.n_launches,
+                              "logits_bit_equal": equal}), flush=True)
+    return nf
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scheme", default="uniform8")
@@ -526,9 +568,12 @@ def main():
                     help="compare the default and the tuned plan (uniform4) without and with nibble-packed conv operands")
     ap.add_argument("--nibble-groups", action="store_true",
                     help="compare the tuned nibble plan and the tuned grouped int8 plan (uniform4) with the tuned nibble plan on mixed-form groups")
+    ap.add_argument("--nibble-fan", action="store_true",
+                    help="compare the tuned nibble plan on mixed-form groups (uniform4) without and with fan-out epilogues, and the tuned int8 "
+                         "grouped fan-out plan")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out / --nibble: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
-    if args.save_plan and not (args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups):
+    if args.save_plan and not (args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
         ap.error("--save-plan needs --tune, --plan, --grouped, --fan-out or --nibble: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
@@ -536,8 +581,8 @@ def main():
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.nibble_groups or args.nibble or args.fan_out or args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
-            compare = compare_nibble_groups if args.nibble_groups else compare_nibble if args.nibble else compare_fan_out if args.fan_out else compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
+        if args.nibble_fan or args.nibble_groups or args.nibble or args.fan_out or args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
+            compare = compare_nibble_fan if args.nibble_fan else compare_nibble_groups if args.nibble_groups else compare_nibble if args.nibble else compare_fan_out if args.fan_out else compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
             tuned = compare(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
