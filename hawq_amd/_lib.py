@@ -278,6 +278,9 @@ SIGNATURES = {
     "hawq_incep_conv_nib": [C.POINTER(IncepConvArgs), i32, vp],
     "hawq_incep_conv_group_ok": [C.POINTER(IncepGroupArgs), i32],
     "hawq_incep_conv_group": [C.POINTER(IncepGroupArgs), i32, vp],
+    "hawq_incep_conv_group_splitk_ok": [C.POINTER(IncepGroupArgs), i32, C.POINTER(i32)],
+    "hawq_incep_conv_group_splitk_workspace": [C.POINTER(IncepGroupArgs), i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)],
+    "hawq_incep_conv_group_splitk": [C.POINTER(IncepGroupArgs), i32, C.POINTER(i32), vp, vp, vp],
     "hawq_incep_conv_group_nib_num_tiles": [],
     "hawq_incep_conv_group_nib_ok": [C.POINTER(IncepGroupArgs), u32, i32],
     "hawq_incep_conv_group_nib": [C.POINTER(IncepGroupArgs), u32, i32, vp],

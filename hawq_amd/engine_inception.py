@@ -142,6 +142,26 @@ conv as a group of one (its mask bit set if it is a nibble conv).  Which boundar
 ``fan_launches`` and ``residual_requants`` report as for ``fan_out``, ``nibble_fan_masks`` lists the ``fan_mask`` of each fan launch
 beside ``nibble_group_masks``.  It composes with ``nibble_groups``, ``fast_pools``, ``fused_stem``, ``forward_uint8``, ``tune`` and
 ``plan``.  Not the default (DESIGN.md 10.3 has what the tuner keeps).
+
+Split-K launches.  ``InceptionEngine(model, grouped=True, splitk=...)`` lets conv launches with few workgroups (batch 1 - 16) run as
+``hawq_incep_conv_group_splitk`` (hawq_amd/csrc/incep_splitk.hip): the grouped launch on 128 px x 64 ch tiles whose members' K loops
+are cut into slices, one workgroup each; the bytes written are the grouped launch's.  Candidates are the conv launches the grouped
+plan issues behind conv1 - a grouped level, a single conv as a group of one, the classifier; records, order and ``n_launches`` stay,
+a split launch takes the place of the launch it replaces.  Which launches, with which slice counts (one per member, 1 = uncut):
+* ``splitk=True``, neither ``tune`` nor ``plan``: a launch of W workgroups (on 128 x 64 tiles) with W < CUs gets S_max = the largest power
+  of two <= min(16, CUs // W) and per member ``split_slices(steps, S_max)`` - at least two K steps a slice, no empty slice; a launch
+  left with all ones, or refused by ``hawq_incep_conv_group_splitk_ok``, stays as it is;
+* ``splitk=n`` (n >= 2): the same with S_max = n for every candidate, whatever W;
+* ``tune=True``: after tiles and groups every candidate with W < CUs is timed as the plan issues it and with S_max in 2, 4, 8, 16 (the
+  method and buffers of the group timing) and kept on its fastest count only if that beats the plain launch (``splitk_candidates``
+  lists convs, slices, times and ``kept``);
+* ``plan=``: exactly the entries of its ``"splitk"`` field, StalePlan for one that is no issued launch of this plan or that the
+  library refuses; a plan without the field splits nothing; an engine without the option ignores the field.
+``export_plan()`` writes ``"splitk": [{"convs", "slices", "us"}]`` only when some launch is split.  ``splitk_launches`` lists (member
+conv indices, slices) per split launch.  One slab and one zeroed counter buffer serve all of them (``_split_workspace``).  Without
+``grouped``, or with ``fan_out``, ``nibble``, ``nibble_groups`` or ``nibble_fan``, it raises ``PlanNotApplicable``; it composes with
+``fast_pools``, ``fused_stem``, ``forward_uint8``, ``tune``, ``plan`` and ``use_graph``.  Not the default: untuned it is slower than
+the grouped plan.
 """
 from __future__ import annotations
 
@@ -204,13 +224,15 @@ def launch_digest(keys):
     return hashlib.sha256(json.dumps([list(map(int, k)) for k in keys], separators=(",", ":")).encode()).hexdigest()
 
 
-def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None, nibble_groups=None, nibble_fan=None):
+def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None, nibble_groups=None, nibble_fan=None,
+              splitk=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
     and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
     ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field, and with `fan_out`
     (a fan-out engine's ``{"unit": k, "tiles": {launch: id}, "us": {...}}`` entries) the ``"fan_out"`` field; `nibble_groups`
     (entries as `groups`, tile ids of ``hawq_incep_conv_group_nib``) the ``"nibble_groups"`` field; `nibble_fan` (entries as
-    `fan_out`, tile ids of ``hawq_incep_conv_group_nib_fan``) the ``"nibble_fan"`` field"""
+    `fan_out`, tile ids of ``hawq_incep_conv_group_nib_fan``) the ``"nibble_fan"`` field; a non-empty `splitk` (a split-K engine's
+    ``{"convs", "slices": [per member], "us"}`` entries) the ``"splitk"`` field"""
     plan = {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
             "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
             "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
@@ -227,6 +249,9 @@ def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibb
     if nibble_groups is not None:
         plan["nibble_groups"] = [{"convs": [int(c) for c in g["convs"]], "tile": int(g["tile"]),
                                   "us": {str(k): round(float(v), 3) for k, v in g.get("us", {}).items()}} for g in nibble_groups]
+    if splitk:   # only when some launch is split
+        plan["splitk"] = [{"convs": [int(c) for c in e["convs"]], "slices": [int(s) for s in e["slices"]],
+                           "us": {str(k): round(float(v), 3) for k, v in e.get("us", {}).items()}} for e in splitk]
     return plan
 
 
@@ -436,6 +461,15 @@ def nibble_storage(tensors, conv_ok):
 _NIB_TILES = (2, 1, 3)   # an untuned nibble launch: the first of these the library takes
 
 
+def split_slices(steps, s_max):
+    """The slice count of a member with `steps` K steps (64 bytes each) under the cap `s_max`: the largest S <= min(s_max, steps // 2,
+    32) without an empty slice, (S - 1) * ceil(steps / S) < steps - ``hawq_incep_conv_group_splitk_ok``'s rule -, else 1."""
+    for s in range(min(s_max, steps // 2, 32), 1, -1):
+        if (s - 1) * -(-steps // s) < steps:
+            return s
+    return 1
+
+
 class _T:
     """An NHWC integer tensor of the plan: buffer, spatial size, channels, row pitch, scale, container bits; the range `rng` of its
     values where that is known to be narrower than the container, whether they are provably >= 0, and what `nibble_storage` asks:
@@ -450,8 +484,16 @@ class _T:
 class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
                  fused_stem: bool = False, grouped: bool = False, fan_out: bool = False, nibble: bool = False,
-                 nibble_groups: bool = False, nibble_fan: bool = False):
+                 nibble_groups: bool = False, nibble_fan: bool = False, splitk=False):
         self.model, self.use_graph = model, use_graph
+        if not isinstance(splitk, (bool, int)) or (not isinstance(splitk, bool) and splitk < 2):
+            raise ValueError("splitk is False, True or a slice count >= 2")
+        self.splitk = splitk
+        if splitk and not grouped:
+            raise PlanNotApplicable("splitk cuts the launches of a grouped plan: it needs grouped=True")
+        if splitk and (fan_out or nibble or nibble_groups or nibble_fan):
+            raise PlanNotApplicable("splitk does not compose with fan_out, nibble, nibble_groups or nibble_fan: their launches have no split-K form")
+        self.splitk_launches, self.splitk_candidates, self._splits = [], [], {}
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
         self.grouped, self.fan_out, self.nibble, self.nibble_groups = bool(grouped), bool(fan_out), bool(nibble), bool(nibble_groups)
         self.nibble_fan = bool(nibble_fan)
@@ -647,6 +689,7 @@ class InceptionEngine(GraphRunner):
         self.conv_tiles, self.conv_us = None, None
         self.group_launches, self.group_candidates, self.nibble_group_masks, self.nibble_fan_masks = [], [], [], []
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
+        self.splitk_launches, self.splitk_candidates, self._splits = [], [], {}
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
@@ -858,7 +901,112 @@ class InceptionEngine(GraphRunner):
         if self.nibble_groups:   # the second component then holds the mixed-form launches (``grouped`` is off: the constructor)
             groups = self._choose_nibble_groups(self.conv_tiles, nib)
         fans = self._choose_fans(self.conv_tiles, groups, nib if self.nibble_fan else None) if self.fan_out or self.nibble_fan else None
+        self._splits = self._choose_splits(self.conv_tiles, groups) if self.splitk else {}   # beside the choice: launch -> slice counts
         return self.conv_tiles, groups, fans, nib
+
+    # ------------------------------------------------------------------ split-K launches
+    def _split_args(self, convs, slices):
+        """(group block, slice counts) of one ``hawq_incep_conv_group_splitk`` launch: a single conv is a group of one"""
+        return self._group_args(convs), (C.c_int32 * _lib.INCEP_GROUP_MAX)(*slices)
+
+    def _split_ok(self, convs, slices):
+        if not 1 <= len(convs) <= _lib.INCEP_GROUP_MAX or not isinstance(slices, (list, tuple)) or len(slices) != len(convs) or \
+                any(not isinstance(s, int) or isinstance(s, bool) for s in slices):
+            return False
+        g, s = self._split_args(convs, slices)
+        return bool(_lib.load().hawq_incep_conv_group_splitk_ok(C.byref(g), 3, s))
+
+    def _split_workspace(self, launches):
+        """one slab and one zeroed counter buffer for the split launches `launches` = [(convs, slices)], sized for the largest of
+        them: every launch leaves the counters zero, and the launches of this engine - the fp32 chain, the uint8 chain (the same
+        callables behind another stem) and the tuner's - all go to ``self.stream``, one after another, so they share it"""
+        slab, cnt, sb, cb = 16, 4, C.c_int64(), C.c_int64()
+        for convs, slices in launches:
+            g, s = self._split_args(convs, slices)
+            _lib.call("hawq_incep_conv_group_splitk_workspace", C.byref(g), 3, s, C.byref(sb), C.byref(cb))
+            slab, cnt = max(slab, sb.value), max(cnt, cb.value)
+        return torch.zeros(slab, dtype=torch.uint8, device=self.dev), torch.zeros(cnt // 4, dtype=torch.int32, device=self.dev)
+
+    def _choose_splits(self, tiles, groups):
+        """Which conv launches of the grouped plan run as ``hawq_incep_conv_group_splitk``, {member conv indices: slice counts}.
+        Candidates are the launches (tiles, groups) issue behind conv1: grouped levels, single convs (groups of one), the classifier.
+        From the plan's ``"splitk"`` field (none without it), else timed (``tune``), else ``split_slices`` with S_max from the CU
+        count (``splitk=True``) or as given (``splitk=n``).  Leaves ``splitk_candidates`` and the workspace."""
+        head = self._launches.index(self._convs[0]) + 1
+        issued = [tuple(groups[i][0]) if is_group else (self._launches[i].ref,)
+                  for is_group, i in grouped_order(self._launches, groups)[head:] if is_group or self._launches[i].kind == "conv"]
+        cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
+
+        def shape(convs):   # workgroups on 128 x 64 tiles, K steps per member
+            blocks = [self._convs[c].args[0] for c in convs]
+            px = [a.N * ((a.H + 2 * a.pad_h - a.KH) // a.stride + 1) * ((a.W + 2 * a.pad_w - a.KW) // a.stride + 1) for a in blocks]
+            return sum(-(-p // 128) * -(-a.Cout // 64) for p, a in zip(px, blocks)), [-(-(a.KH * a.KW * (a.Cin >> 4)) // 4) for a in blocks]
+
+        def slices_for(convs, s_max):   # None: no member is cut, or the library refuses the launch
+            s = [split_slices(st, s_max) for st in shape(convs)[1]]
+            return s if max(s) > 1 and self._split_ok(convs, s) else None
+
+        if self.plan is not None:
+            try:
+                entries = [(tuple(e["convs"]), list(e["slices"]), dict(e.get("us", {}))) for e in self.plan.get("splitk", [])]
+            except (KeyError, TypeError, ValueError) as exc:
+                raise StalePlan(f"not a list of split-K launches: {exc!r}") from exc
+            for convs, slices, _ in entries:
+                if convs not in issued or [c for c, _, _ in entries].count(convs) != 1 or not self._split_ok(convs, slices):
+                    raise StalePlan(f"split-K launch {list(convs)} with slices {slices}: not an issued launch of this plan, or refused")
+            self.splitk_candidates = [{"convs": list(c), "slices": s, "us": us, "kept": True} for c, s, us in entries]
+        elif self.tune:
+            small = [c for c in issued if shape(c)[0] < cus]
+            variants = [{n: s for n in (2, 4, 8, 16) for s in [slices_for(c, n)] if s is not None} for c in small]
+            times = self._time_splits(small, variants, tiles, groups)
+            for c, var, us in zip(small, variants, times):
+                if var:
+                    best = min(var, key=lambda n: (us[str(n)], n))
+                    self.splitk_candidates.append({"convs": list(c), "slices": var[best], "us": us, "kept": us[str(best)] < us["plain"]})
+        else:
+            for c in issued:
+                w = shape(c)[0]
+                if self.splitk is True and w >= cus:
+                    continue
+                s = slices_for(c, 1 << (min(16, cus // w).bit_length() - 1) if self.splitk is True else self.splitk)
+                if s is not None:
+                    self.splitk_candidates.append({"convs": list(c), "slices": s, "us": {}, "kept": True})
+        kept = {tuple(e["convs"]): e["slices"] for e in self.splitk_candidates if e["kept"]}
+        self._split_ws = self._split_workspace(kept.items())
+        self._keep += list(self._split_ws)
+        return kept
+
+    def _time_splits(self, cands, variants, tiles, groups):
+        """Per candidate launch of `cands`, on the buffers of a forward of the plan (tiles, groups) and by the method of the group
+        timing: ``"plain"``, the microseconds of the launch as that plan issues it, and per S_max of `variants` (``"2"`` ..) those
+        of the split launch with its slice counts."""
+        sp, out, gtile = self.stream.cuda_stream, [], {tuple(c): t for c, t in groups}
+        ws = self._split_workspace([(c, s) for c, var in zip(cands, variants) for s in var.values()])
+        self._choice = (tiles, groups, None, None)
+        with EventTimer(sp, _TUNE_REPS + 1) as ev:
+            torch.cuda.synchronize(self.dev)
+            with torch.cuda.stream(self.stream):
+                for op in self._write():
+                    op()
+                for c, var in zip(cands, variants):
+                    if not var:
+                        out.append({})
+                        continue
+                    g = self._group_args(c)
+                    if c in gtile:
+                        plain = partial(_lib.call, "hawq_incep_conv_group", C.byref(g), int(gtile[c]), sp)
+                    else:
+                        plain = partial(_lib.call, "hawq_incep_conv_tiled", C.byref(g.conv[0]), int(tiles[c[0]]), sp)
+                    self.n_timing_launches += (_TUNE_WARMUP + _TUNE_REPS) * (len(var) + 1)
+                    us = {"plain": ev.median_us(plain, _TUNE_REPS, _TUNE_WARMUP)}
+                    for n, s in var.items():
+                        arr = self._split_args(c, s)[1]
+                        us[str(n)] = ev.median_us(partial(_lib.call, "hawq_incep_conv_group_splitk", C.byref(g), 3, arr, ws[0].data_ptr(),
+                                                          ws[1].data_ptr(), sp), _TUNE_REPS, _TUNE_WARMUP)
+                    out.append(us)
+        torch.cuda.synchronize(self.dev)
+        self._choice = (None, None, None, None)
+        return out
 
     # ------------------------------------------------------------------ nibbles
     def _nib_ok(self, c, tile, block=None):
@@ -1182,7 +1330,8 @@ class InceptionEngine(GraphRunner):
         ngroups = [g for g in self.group_candidates if g["kept"]] if self.nibble_groups else None
         nfans = [f for f in self.fan_candidates if f["kept"]] if self.nibble_fan else None
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
-                         groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None, ngroups, nfans)
+                         groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None, ngroups, nfans,
+                         [e for e in self.splitk_candidates if e["kept"]] if self.splitk else None)
 
     # ------------------------------------------------------------------ the writer
     def _write(self, u8=False):
@@ -1191,7 +1340,9 @@ class InceptionEngine(GraphRunner):
         ``fast_pools`` where the library takes it, on ``hawq_incep_pool_v``.  The stem's head (the records up to conv1) as it stands,
         as one ``hawq_incep_stem_f32`` (``fused_stem``) or, for the uint8 chain, as one ``hawq_incep_stem_u8`` in front of the fp32
         chain's own callables.  The records' order, or with groups ``grouped_order``.  The fp32 chain leaves ``_at`` (record -> index
-        of the launch that covers it) and ``group_launches``."""
+        of the launch that covers it) and ``group_launches``.  A conv launch - grouped, or single as a group of one - that ``_splits``
+        names is issued as ``hawq_incep_conv_group_splitk`` with its slice counts on the engine's one workspace, in the place of the
+        launch it replaces (``splitk_launches``); the uint8 chain shares those callables."""
         tiles, groups, fans, nib = self._choice
         lib, sp, launches = _lib.load(), self.stream.cuda_stream, self._launches
         fan_of = {s: (b, t) for b, by_set in fans or [] for s, t in by_set.items()}           # producer launch -> its boundary, tile
@@ -1220,7 +1371,7 @@ class InceptionEngine(GraphRunner):
             ops = [op("hawq_incep_stem_f32", self.x_in.data_ptr(), *self._input_quant(), C.byref(self._stem_a))]
         else:
             ops = [single(r) for r in launches[:head]]
-        n_stem, issued, masks, fanned, fmasks, residual = len(ops), [], [], [], [], []
+        n_stem, issued, masks, fanned, fmasks, residual, split = len(ops), [], [], [], [], [], []
         at = {r: min(i, n_stem - 1) for i, r in enumerate(launches[:head])}
         order = [(False, i) for i in range(len(launches))] if groups is None else grouped_order(launches, groups)
         for is_group, i in order[head:]:   # the stem stays in place in either order
@@ -1240,6 +1391,14 @@ class InceptionEngine(GraphRunner):
                     ops.append(op("hawq_incep_conv_group_fan", C.byref(g), f, int(tile)))
                 self._keep += [g, f]
                 fanned.append((b["unit"], list(convs), int(tile)))
+                if is_group:
+                    issued.append((list(convs), int(tile)))
+            elif convs is not None and tuple(convs) in self._splits:   # in the place of the launch it replaces, a single conv as a group of one
+                g, s = self._split_args(convs, self._splits[tuple(convs)])
+                self._keep += [g, s]
+                at.update((self._convs[c], len(ops)) for c in convs)
+                ops.append(op("hawq_incep_conv_group_splitk", C.byref(g), 3, s, self._split_ws[0].data_ptr(), self._split_ws[1].data_ptr()))
+                split.append((list(convs), list(self._splits[tuple(convs)])))
                 if is_group:
                     issued.append((list(convs), int(tile)))
             elif is_group and self.nibble_groups:   # members of either operand form, each on the block its single launch has
@@ -1269,6 +1428,7 @@ class InceptionEngine(GraphRunner):
                 ops.append(single(r))
         self._at, self._tail, self.group_launches, self.nibble_group_masks = at, ops[n_stem:], issued, masks
         self.fan_launches, self.residual_requants, self.nibble_fan_masks = fanned, residual, fmasks
+        self.splitk_launches = split
         return ops
 
     def _launch_chain(self, u8):

@@ -598,6 +598,28 @@ typedef struct hawq_incep_group_args {
 } hawq_incep_group_args;
 int hawq_incep_conv_group_ok(const hawq_incep_group_args *g, int tile);
 int hawq_incep_conv_group(const hawq_incep_group_args *g, int tile, void *stream);
+/* Split-K form of the grouped launch (incep_splitk.hip) for launches with few output tiles (batch 1 - 16): member i's K loop - the
+ * steps_i = ceil(KH * KW * (Cin / 16) / 4) 64-byte steps of the tiled kernels - is cut into slices[i] slices of q_i = ceil(steps_i /
+ * slices[i]) steps, each run by a workgroup of its own; slices write int32 partial tiles to `slab`, and the slice that arrives last at a
+ * tile (one int32 of `counters` per tile) sums them and runs the tiled kernels' epilogue.  Nothing waits on another workgroup.
+ *   hawq_incep_conv_group_splitk:     writes, byte for byte, what hawq_incep_conv_group(g, tile, stream) writes, whatever the slice
+ *       counts.  `tile` is an id of hawq_incep_conv_num_tiles()'s numbering; only 3 (128 px x 64 ch) has this form so far.  The grid is
+ *       the sum over the members of tiles_i * slices[i] workgroups, tiles_i = ceil(P_i / 128) * ceil(Cout_i / 64).  A member with one
+ *       slice runs its whole K loop and touches neither slab nor counters.  slab: 16-byte aligned, non-NULL.  counters: non-NULL, zero
+ *       before the first launch; every launch leaves them zero, so launches on one stream (and replays of a graph) share one workspace;
+ *       launches that may run concurrently need workspaces of their own.
+ *   hawq_incep_conv_group_splitk_ok:  1 if the launch takes this description.  Host arithmetic only: nothing is dereferenced (but
+ *       slices[0 .. n - 1]) or launched, no device is needed.  It needs tile == 3 and hawq_incep_conv_group_ok(g, 3); every slices[i] in
+ *       1 .. 32; no empty slice, (slices[i] - 1) * q_i < steps_i; at least one slices[i] > 1; fewer than 2^31 workgroups.
+ *   hawq_incep_conv_group_splitk_workspace: *slab_bytes = sum over slices[i] > 1 of tiles_i * slices[i] * 128 * 64 * 4, *counter_bytes =
+ *       4 * sum over slices[i] > 1 of tiles_i; non-zero if the group is refused.
+ * A refused call returns non-zero (the reason, with the member, in hawq_last_error()), launches nothing and writes no byte.
+ * Not covered: hawq4 operands and out_bits 4, fan-out epilogues, tile shapes other than 128 x 64, the stem and pool kernels. */
+int hawq_incep_conv_group_splitk_ok(const hawq_incep_group_args *g, int tile, const int32_t *slices /* [g->n] */);
+int hawq_incep_conv_group_splitk_workspace(const hawq_incep_group_args *g, int tile, const int32_t *slices, int64_t *slab_bytes,
+                                           int64_t *counter_bytes);
+int hawq_incep_conv_group_splitk(const hawq_incep_group_args *g, int tile, const int32_t *slices, void *slab, int32_t *counters,
+                                 void *stream);
 /* The grouped launch for members of both operand forms (incep_group_nib.hip): the grid of hawq_incep_conv_group, with bit i of `mask`
  * saying that member i's in and wgt are hawq4 as hawq_incep_conv_nib reads them; the other members are int8 as hawq_incep_conv_tiled
  * reads them.  A workgroup runs its member's own kernel body, both on the same two LDS stages.

@@ -39,7 +39,14 @@ the plan without the field and so takes every candidate boundary on the default 
 the logits are bit-equal, the launch counts, and a table of the boundaries - producer launches + entry requants against fan-out
 producer launches + residual requants, in microseconds, kept or not.
 
+``--splitk`` (with ``--pools`` for ``fast_pools=True`` on both) compares the tuned grouped plan without and with split-K conv launches
+(``grouped=True, splitk=True``, tuned: that engine times tiles, groups and slice counts, the other replays its plan and ignores the
+``"splitk"`` field): alternating blocks as above, an assertion that the logits are bit-equal, [smallest block, largest block] per
+engine, whether the two ranges overlap, and a table of the candidate launches - workgroups on 128 x 64 tiles, chosen slices, the
+microseconds of the launch as the grouped plan issues it and of its fastest split form, kept or not.
+
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
+    python tools/inception_bench.py --splitk --pools --batches 1,2,4,8,16 [--blocks 6]
     python tools/inception_bench.py --input f32,u8 [--blocks 6] [--stem-launches 0]
     python tools/inception_bench.py --tune [--batches 128] [--blocks 6] [--save-plan plan.json]
     python tools/inception_bench.py --plan plan.json --batches 128
@@ -365,6 +372,53 @@ def compare_grouped(model, args, b):
     return grouped
 
 
+def compare_splitk(model, args, b):
+    """the tuned grouped plan without and with split-K launches (``splitk=True``, tuned: that engine times tiles, groups and slice
+    counts; the other replays its plan and ignores the ``"splitk"`` field, so it is the tuned grouped engine on the same tiles and
+    groups), alternating blocks; returns the split-K engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    opts = dict(fast_pools=args.pools, grouped=True)
+    with torch.no_grad():
+        split = InceptionEngine(model, tune=True, splitk=True, **opts)
+        y1 = split(x)
+        grouped = InceptionEngine(model, plan=split.export_plan(), **opts)
+        replay = InceptionEngine(model, plan=split.export_plan(), splitk=True, **opts)   # both timed engines replay one plan
+        engines = {"grouped": grouped, "splitk": replay}
+        equal = bool(torch.equal(grouped(x), y1)) and bool(torch.equal(replay(x), y1))
+        assert replay.splitk_launches == split.splitk_launches
+        assert equal, "the logits with split-K launches differ from the grouped plan's"
+        assert grouped.conv_tiles == split.conv_tiles and grouped.group_launches == split.group_launches and not grouped.splitk_launches
+        print(f"# {wl}: launch | member conv launches (Cout KHxKW each) | W (128 x 64 workgroups) | slices | us before | us after | kept")
+        for i, e in enumerate(split.splitk_candidates):
+            keys = [split.conv_launches[c] for c in e["convs"]]
+            w = sum(-(-(b * ((k[0] + 2 * k[7] - k[4]) // k[6] + 1) * ((k[1] + 2 * k[8] - k[5]) // k[6] + 1)) // 128) * -(-k[3] // 64) for k in keys)
+            after = min(v for n, v in e["us"].items() if n != "plain")
+            print(f"# {i:2d} | " + " ".join(f"{c}({k[3]} {k[4]}x{k[5]})" for c, k in zip(e["convs"], keys)) +
+                  f" | {w} | {e['slices']} | {e['us']['plain']:.1f} | {after:.1f} | {'kept' if e['kept'] else 'plain'}")
+        kept = [e for e in split.splitk_candidates if e["kept"]]
+        print(json.dumps({"workload": wl, "launches": split.n_launches, "candidates": len(split.splitk_candidates), "kept": len(kept),
+                          "kept_us_before": round(sum(e["us"]["plain"] for e in kept), 1),
+                          "kept_us_after": round(sum(min(v for n, v in e["us"].items() if n != "plain") for e in kept), 1)}), flush=True)
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            print(json.dumps({"workload": wl, "path": "fused", "plan": "tuned", "fast_pools": bool(args.pools), "convs": k,
+                              "ms_per_batch": round(sum(v) / len(v), 4), "block_min_ms": round(min(v), 4), "block_max_ms": round(max(v), 4),
+                              "blocks": len(v), "steps": args.steps, "launches": e.n_launches, "logits_bit_equal": equal}), flush=True)
+        apart = max(ms["splitk"]) < min(ms["grouped"]) or max(ms["grouped"]) < min(ms["splitk"])
+        print(json.dumps({"workload": wl, "splitk_over_grouped_rate": round(sum(ms["grouped"]) / sum(ms["splitk"]), 4),
+                          "block_ranges_overlap": not apart}), flush=True)
+    return split
+
+
 def compare_fan_out(model, args, b):
     """one recorded plan (fast pools, fused stem, grouped or not) without fan-out, with the boundaries the tuner kept and with every
     candidate boundary, alternating blocks; returns the tuned fan-out engine"""
@@ -571,15 +625,23 @@ def main():
     ap.add_argument("--nibble-fan", action="store_true",
                     help="compare the tuned nibble plan on mixed-form groups (uniform4) without and with fan-out epilogues, and the tuned int8 "
                          "grouped fan-out plan")
+    ap.add_argument("--splitk", action="store_true",
+                    help="compare the tuned grouped plan (fast pools with --pools) without and with split-K conv launches")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out / --nibble: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
-    if args.save_plan and not (args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
+    if args.save_plan and not (args.splitk or args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
         ap.error("--save-plan needs --tune, --plan, --grouped, --fan-out or --nibble: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
     for b in (int(v) for v in args.batches.split(",")):
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
+            continue
+        if args.splitk:
+            tuned = compare_splitk(model, args, b)
+            if args.save_plan:
+                with open(args.save_plan, "w") as f:
+                    json.dump(tuned.export_plan(), f)
             continue
         if args.nibble_fan or args.nibble_groups or args.nibble or args.fan_out or args.grouped or args.tune or args.plan or args.pools or args.fused_stem:
             compare = compare_nibble_fan if args.nibble_fan else compare_nibble_groups if args.nibble_groups else compare_nibble if args.nibble else compare_fan_out if args.fan_out else compare_grouped if args.grouped else compare_stems if args.fused_stem else compare_pools if args.pools else compare_plans
