@@ -284,6 +284,9 @@ SIGNATURES = {
     "hawq_incep_conv_group_nib_num_tiles": [],
     "hawq_incep_conv_group_nib_ok": [C.POINTER(IncepGroupArgs), u32, i32],
     "hawq_incep_conv_group_nib": [C.POINTER(IncepGroupArgs), u32, i32, vp],
+    "hawq_incep_conv_group_nib_splitk_ok": [C.POINTER(IncepGroupArgs), u32, i32, C.POINTER(i32)],
+    "hawq_incep_conv_group_nib_splitk_workspace": [C.POINTER(IncepGroupArgs), u32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)],
+    "hawq_incep_conv_group_nib_splitk": [C.POINTER(IncepGroupArgs), u32, i32, C.POINTER(i32), vp, vp, vp],
     "hawq_incep_conv_group_nib_fan_ok": [C.POINTER(IncepGroupArgs), u32, C.POINTER(IncepFan), u32, i32],
     "hawq_incep_conv_group_nib_fan": [C.POINTER(IncepGroupArgs), u32, C.POINTER(IncepFan), u32, i32, vp],
     "hawq_incep_conv_group_fan_ok": [C.POINTER(IncepGroupArgs), C.POINTER(IncepFan), i32],

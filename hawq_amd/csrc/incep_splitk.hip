@@ -35,7 +35,9 @@
 // Workspace: slab [sum over S_i > 1 of tiles_i * S_i][4 waves][2 MFMA tiles][4 register quads][64 lanes][4] int32, tile-major inside a
 // member (a tile's S_i slabs are contiguous); one int32 counter per tile of such a member, zero before the first launch and left zero
 // by every launch.
-#include "incep_tile.h"
+// SliceMap, the host's slice layout and, as text, the arrival protocol are in incep_splitk.h and incep_splitk_arrive.h: the mixed-form
+// split launch (incep_group_nib_splitk.hip) runs the same ones.
+#include "incep_splitk.h"
 
 namespace {
 
@@ -46,14 +48,7 @@ constexpr int WM = BM / WPX / 32, WN = BN / WCH / 32;
 constexpr int STAGE = (BM + BN) * 64;   // bytes of one K step of both operand tiles
 constexpr int CH = 4;                   // K steps per chunk: loads in flight together, LDS stages
 constexpr int SLAB = BM * BN;           // int32 partial sums per slab
-constexpr int MAX_SLICES = 32;
 static_assert(WM == 2 && WN == 1 && APT == 2 && BPT == 1, "the 128 x 64 tile: 4 waves of 64 px x 32 ch");
-
-// per member, by value: output tiles, slices, steps per slice, first slab (in slabs) and first counter of the member
-struct SliceMap {
-    int32_t tiles[HAWQ_INCEP_GROUP_MAX], S[HAWQ_INCEP_GROUP_MAX], q[HAWQ_INCEP_GROUP_MAX], slab0[HAWQ_INCEP_GROUP_MAX],
-        cnt0[HAWQ_INCEP_GROUP_MAX];
-};
 
 __global__ __launch_bounds__(NT) void incep_splitk_kernel(hawq_incep_group_args g, GroupMap mp, SliceMap sm, int32_t *slab, int32_t *counters) {
     __shared__ __attribute__((aligned(16))) char lds[CH * STAGE];
@@ -164,37 +159,7 @@ __global__ __launch_bounds__(NT) void incep_splitk_kernel(hawq_incep_group_args 
         __syncthreads();   // every wave has read the stages the next chunk overwrites
     }
 
-    if (S > 1) {   // wave-uniform: a member's slice count
-        const size_t tile_base = ((size_t)sm.slab0[gm.mi] + (size_t)tile * S) * SLAB + wave * (WM * 1024);
-        int32_t *mine = slab + tile_base + (size_t)z * SLAB;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4)
-                reinterpret_cast<v4i *>(mine)[(i * 4 + q4) * 64 + lane] = v4i{acc[i][4 * q4], acc[i][4 * q4 + 1], acc[i][4 * q4 + 2], acc[i][4 * q4 + 3]};
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // this thread's slab stores are visible chip-wide
-        __syncthreads();
-        int32_t *counter = counters + sm.cnt0[gm.mi] + tile;
-        if (tid == 0) {
-            const int arrived = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = arrived == S - 1;
-        }
-        __syncthreads();
-        if (!last) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // every other slice's stores are visible to this workgroup
-        if (tid == 0) *counter = 0;                          // all slices have arrived: nobody touches it again in this launch
-        for (int j = 0; j < S; ++j) {
-            if (j == z) continue;   // this workgroup's own partial is still in its registers
-            const v4i *theirs = reinterpret_cast<const v4i *>(slab + tile_base + (size_t)j * SLAB);
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const v4i v = theirs[(i * 4 + q4) * 64 + lane];
-                    acc[i][4 * q4] += v.x, acc[i][4 * q4 + 1] += v.y, acc[i][4 * q4 + 2] += v.z, acc[i][4 * q4 + 3] += v.w;
-                }
-        }
-    }
+#include "incep_splitk_arrive.h"
 
     // the tiled body's epilogue: acc[i][r] = channel cblock + 32 wch + 16 h + r of pixel pblock + 32 (wpx WM + i) + l31
 #pragma unroll
@@ -238,13 +203,6 @@ __global__ __launch_bounds__(NT) void incep_splitk_kernel(hawq_incep_group_args 
     }
 }
 
-// the host's view of a split launch
-struct SplitGrid {
-    GroupGrid gg;   // mp.end rewritten to the running totals of tiles_i * S_i
-    SliceMap sm;
-    long long total, slabs, counters;
-};
-
 // why the launch does not take group `g` with slice counts `slices` (NULL: it does, and `sg` describes it); `who`: the member, or -1.
 // No pointer of an argument block is dereferenced.
 const char *split_refusal(const hawq_incep_group_args *g, int tile, const int32_t *slices, SplitGrid *sg, int *who) {
@@ -255,29 +213,8 @@ const char *split_refusal(const hawq_incep_group_args *g, int tile, const int32_
     if (!slices) return "null slice counts";
     if (const char *why = group_grid(g, tile, &sg->gg, who)) return why;
     if (const char *why = group_dependence(g, &sg->gg, who)) return why;
-    GroupMap *mp = &sg->gg.mp;
-    SliceMap *sm = &sg->sm;
-    long long wgs = 0, slabs = 0, counters = 0;
-    int first = 0;
-    bool split = false;
-    for (int i = 0; i < HAWQ_INCEP_GROUP_MAX; ++i) sm->tiles[i] = sm->S[i] = sm->q[i] = 1, sm->slab0[i] = sm->cnt0[i] = 0;
-    for (int i = 0; i < g->n; ++i) {
-        const hawq_incep_conv_args *a = &g->conv[i];
-        *who = i;
-        const int S = slices[i], tiles = mp->end[i] - first;
-        first = mp->end[i];
-        if (S < 1 || S > MAX_SLICES) return "a member has 1 .. 32 slices";
-        const int steps = (a->KH * a->KW * (a->Cin >> 4) + 3) >> 2, q = (steps + S - 1) / S;
-        if ((long long)(S - 1) * q >= steps) return "an empty slice: (S - 1) * ceil(steps / S) must stay below the member's K steps";
-        if (slabs + (long long)tiles * S >= (1ll << 31) || wgs + (long long)tiles * S >= (1ll << 31)) return "too many workgroups";
-        sm->tiles[i] = tiles, sm->S[i] = S, sm->q[i] = q, sm->slab0[i] = (int32_t)slabs, sm->cnt0[i] = (int32_t)counters;
-        if (S > 1) slabs += (long long)tiles * S, counters += tiles, split = true;
-        wgs += (long long)tiles * S;
-        mp->end[i] = (int32_t)wgs;
-    }
-    *who = -1;
-    if (!split) return "no member has more than one slice (that launch is hawq_incep_conv_group)";
-    sg->total = wgs, sg->slabs = slabs, sg->counters = counters;
+    if (const char *why = split_layout(g, 0u, slices, sg, who)) return why;
+    if (!sg->slabs) return "no member has more than one slice (that launch is hawq_incep_conv_group)";
     return nullptr;
 }
 

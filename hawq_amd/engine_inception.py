@@ -159,9 +159,18 @@ a split launch takes the place of the launch it replaces.  Which launches, with 
   library refuses; a plan without the field splits nothing; an engine without the option ignores the field.
 ``export_plan()`` writes ``"splitk": [{"convs", "slices", "us"}]`` only when some launch is split.  ``splitk_launches`` lists (member
 conv indices, slices) per split launch.  One slab and one zeroed counter buffer serve all of them (``_split_workspace``).  Without
-``grouped``, or with ``fan_out``, ``nibble``, ``nibble_groups`` or ``nibble_fan``, it raises ``PlanNotApplicable``; it composes with
-``fast_pools``, ``fused_stem``, ``forward_uint8``, ``tune``, ``plan`` and ``use_graph``.  Not the default: untuned it is slower than
-the grouped plan.
+``grouped`` (and without the nibble form below), or with ``fan_out`` or ``nibble_fan``, it raises ``PlanNotApplicable``; it composes
+with ``fast_pools``, ``fused_stem``, ``forward_uint8``, ``tune``, ``plan`` and ``use_graph``.  Not the default: untuned it is slower
+than the grouped plan.
+``InceptionEngine(model, nibble=True, nibble_groups=True, splitk=...)`` is the same option on a nibble plan: the split launch is
+``hawq_incep_conv_group_nib_splitk`` (hawq_amd/csrc/incep_group_nib_splitk.hip) on mixed-group tile 2, whose members are int8 or
+hawq4 one by one as in ``hawq_incep_conv_group_nib``; the bytes written are that launch's.  The nibble choice and the group choice
+are made first, exactly as without the option.  Candidates are the launches that plan issues behind conv1 - a mixed-form level with
+its mask, a single conv as a group of one (mask 1 if it is a nibble conv), the classifier - and a member's K steps count 64-byte
+rows of its own form: K / 64 int8, K / 128 hawq4, so a hawq4 member has half the steps to cut.  W, S_max, ``split_slices``, the
+timing (against ``hawq_incep_conv_group_nib``, ``hawq_incep_conv_nib`` or ``hawq_incep_conv_tiled``, whichever the plan issues), the
+``"splitk"`` field and its StalePlan rules are as above; which kernel an entry means follows from the plan's own ``"nibble"`` and
+``"nibble_groups"`` fields.  ``nibble=True`` without ``nibble_groups`` has no split form and raises ``PlanNotApplicable``.
 """
 from __future__ import annotations
 
@@ -489,10 +498,10 @@ class InceptionEngine(GraphRunner):
         if not isinstance(splitk, (bool, int)) or (not isinstance(splitk, bool) and splitk < 2):
             raise ValueError("splitk is False, True or a slice count >= 2")
         self.splitk = splitk
-        if splitk and not grouped:
-            raise PlanNotApplicable("splitk cuts the launches of a grouped plan: it needs grouped=True")
-        if splitk and (fan_out or nibble or nibble_groups or nibble_fan):
-            raise PlanNotApplicable("splitk does not compose with fan_out, nibble, nibble_groups or nibble_fan: their launches have no split-K form")
+        if splitk and not grouped and not (nibble and nibble_groups):
+            raise PlanNotApplicable("splitk cuts the launches of a grouped plan: it needs grouped=True, or nibble=True with nibble_groups=True")
+        if splitk and (fan_out or nibble_fan):
+            raise PlanNotApplicable("splitk does not compose with fan_out or nibble_fan: their launches have no split-K form")
         self.splitk_launches, self.splitk_candidates, self._splits = [], [], {}
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
         self.grouped, self.fan_out, self.nibble, self.nibble_groups = bool(grouped), bool(fan_out), bool(nibble), bool(nibble_groups)
@@ -901,20 +910,27 @@ class InceptionEngine(GraphRunner):
         if self.nibble_groups:   # the second component then holds the mixed-form launches (``grouped`` is off: the constructor)
             groups = self._choose_nibble_groups(self.conv_tiles, nib)
         fans = self._choose_fans(self.conv_tiles, groups, nib if self.nibble_fan else None) if self.fan_out or self.nibble_fan else None
-        self._splits = self._choose_splits(self.conv_tiles, groups) if self.splitk else {}   # beside the choice: launch -> slice counts
+        self._splits = self._choose_splits(self.conv_tiles, groups, nib) if self.splitk else {}   # beside the choice: launch -> slice counts
         return self.conv_tiles, groups, fans, nib
 
     # ------------------------------------------------------------------ split-K launches
     def _split_args(self, convs, slices):
-        """(group block, slice counts) of one ``hawq_incep_conv_group_splitk`` launch: a single conv is a group of one"""
-        return self._group_args(convs), (C.c_int32 * _lib.INCEP_GROUP_MAX)(*slices)
+        """(entry point, group block, the call's arguments in front of the workspace) of one split launch; a single conv is a group
+        of one.  ``hawq_incep_conv_group_splitk`` on tile 3 under ``grouped``; under ``nibble_groups`` its mixed-form twin
+        ``hawq_incep_conv_group_nib_splitk`` on mixed-group tile 2, the members' blocks and mask bits from the nibble choice"""
+        s = (C.c_int32 * _lib.INCEP_GROUP_MAX)(*slices)
+        if self.nibble_groups:
+            g, mask = self._ngroup_args(convs, self._split_nib)
+            return "hawq_incep_conv_group_nib_splitk", g, (C.byref(g), mask, 2, s)
+        g = self._group_args(convs)
+        return "hawq_incep_conv_group_splitk", g, (C.byref(g), 3, s)
 
     def _split_ok(self, convs, slices):
         if not 1 <= len(convs) <= _lib.INCEP_GROUP_MAX or not isinstance(slices, (list, tuple)) or len(slices) != len(convs) or \
                 any(not isinstance(s, int) or isinstance(s, bool) for s in slices):
             return False
-        g, s = self._split_args(convs, slices)
-        return bool(_lib.load().hawq_incep_conv_group_splitk_ok(C.byref(g), 3, s))
+        name, _, args = self._split_args(convs, slices)
+        return bool(getattr(_lib.load(), name + "_ok")(*args))
 
     def _split_workspace(self, launches):
         """one slab and one zeroed counter buffer for the split launches `launches` = [(convs, slices)], sized for the largest of
@@ -922,25 +938,29 @@ class InceptionEngine(GraphRunner):
         callables behind another stem) and the tuner's - all go to ``self.stream``, one after another, so they share it"""
         slab, cnt, sb, cb = 16, 4, C.c_int64(), C.c_int64()
         for convs, slices in launches:
-            g, s = self._split_args(convs, slices)
-            _lib.call("hawq_incep_conv_group_splitk_workspace", C.byref(g), 3, s, C.byref(sb), C.byref(cb))
+            name, _, args = self._split_args(convs, slices)
+            _lib.call(name + "_workspace", *args, C.byref(sb), C.byref(cb))
             slab, cnt = max(slab, sb.value), max(cnt, cb.value)
         return torch.zeros(slab, dtype=torch.uint8, device=self.dev), torch.zeros(cnt // 4, dtype=torch.int32, device=self.dev)
 
-    def _choose_splits(self, tiles, groups):
-        """Which conv launches of the grouped plan run as ``hawq_incep_conv_group_splitk``, {member conv indices: slice counts}.
-        Candidates are the launches (tiles, groups) issue behind conv1: grouped levels, single convs (groups of one), the classifier.
+    def _choose_splits(self, tiles, groups, nib=None):
+        """Which conv launches of the grouped plan run as its split launch (``_split_args``), {member conv indices: slice counts}.
+        Candidates are the launches (tiles, groups) issue behind conv1: grouped levels - of a ``nibble_groups`` plan the mixed-form
+        ones -, single convs (groups of one; hawq4 where `nib` names them), the classifier.  A member's K steps are 64-byte rows:
+        four 16-channel units of an int8 member, eight of a hawq4 one.
         From the plan's ``"splitk"`` field (none without it), else timed (``tune``), else ``split_slices`` with S_max from the CU
         count (``splitk=True``) or as given (``splitk=n``).  Leaves ``splitk_candidates`` and the workspace."""
         head = self._launches.index(self._convs[0]) + 1
         issued = [tuple(groups[i][0]) if is_group else (self._launches[i].ref,)
                   for is_group, i in grouped_order(self._launches, groups)[head:] if is_group or self._launches[i].kind == "conv"]
         cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
+        self._split_nib = nib = nib or {}
 
         def shape(convs):   # workgroups on 128 x 64 tiles, K steps per member
             blocks = [self._convs[c].args[0] for c in convs]
             px = [a.N * ((a.H + 2 * a.pad_h - a.KH) // a.stride + 1) * ((a.W + 2 * a.pad_w - a.KW) // a.stride + 1) for a in blocks]
-            return sum(-(-p // 128) * -(-a.Cout // 64) for p, a in zip(px, blocks)), [-(-(a.KH * a.KW * (a.Cin >> 4)) // 4) for a in blocks]
+            return (sum(-(-p // 128) * -(-a.Cout // 64) for p, a in zip(px, blocks)),
+                    [-(-(a.KH * a.KW * (a.Cin >> 4)) // (8 if c in nib else 4)) for c, a in zip(convs, blocks)])
 
         def slices_for(convs, s_max):   # None: no member is cut, or the library refuses the launch
             s = [split_slices(st, s_max) for st in shape(convs)[1]]
@@ -958,7 +978,7 @@ class InceptionEngine(GraphRunner):
         elif self.tune:
             small = [c for c in issued if shape(c)[0] < cus]
             variants = [{n: s for n in (2, 4, 8, 16) for s in [slices_for(c, n)] if s is not None} for c in small]
-            times = self._time_splits(small, variants, tiles, groups)
+            times = self._time_splits(small, variants, tiles, groups, nib)
             for c, var, us in zip(small, variants, times):
                 if var:
                     best = min(var, key=lambda n: (us[str(n)], n))
@@ -976,13 +996,13 @@ class InceptionEngine(GraphRunner):
         self._keep += list(self._split_ws)
         return kept
 
-    def _time_splits(self, cands, variants, tiles, groups):
+    def _time_splits(self, cands, variants, tiles, groups, nib):
         """Per candidate launch of `cands`, on the buffers of a forward of the plan (tiles, groups) and by the method of the group
         timing: ``"plain"``, the microseconds of the launch as that plan issues it, and per S_max of `variants` (``"2"`` ..) those
         of the split launch with its slice counts."""
         sp, out, gtile = self.stream.cuda_stream, [], {tuple(c): t for c, t in groups}
         ws = self._split_workspace([(c, s) for c, var in zip(cands, variants) for s in var.values()])
-        self._choice = (tiles, groups, None, None)
+        self._choice = (tiles, groups, None, nib or None)
         with EventTimer(sp, _TUNE_REPS + 1) as ev:
             torch.cuda.synchronize(self.dev)
             with torch.cuda.stream(self.stream):
@@ -992,17 +1012,20 @@ class InceptionEngine(GraphRunner):
                     if not var:
                         out.append({})
                         continue
-                    g = self._group_args(c)
-                    if c in gtile:
+                    g, mask = self._ngroup_args(c, nib) if self.nibble_groups else (self._group_args(c), 0)
+                    if c in gtile and self.nibble_groups:
+                        plain = partial(_lib.call, "hawq_incep_conv_group_nib", C.byref(g), mask, int(gtile[c]), sp)
+                    elif c in gtile:
                         plain = partial(_lib.call, "hawq_incep_conv_group", C.byref(g), int(gtile[c]), sp)
+                    elif mask:
+                        plain = partial(_lib.call, "hawq_incep_conv_nib", C.byref(g.conv[0]), int(nib[c[0]]), sp)
                     else:
                         plain = partial(_lib.call, "hawq_incep_conv_tiled", C.byref(g.conv[0]), int(tiles[c[0]]), sp)
                     self.n_timing_launches += (_TUNE_WARMUP + _TUNE_REPS) * (len(var) + 1)
                     us = {"plain": ev.median_us(plain, _TUNE_REPS, _TUNE_WARMUP)}
                     for n, s in var.items():
-                        arr = self._split_args(c, s)[1]
-                        us[str(n)] = ev.median_us(partial(_lib.call, "hawq_incep_conv_group_splitk", C.byref(g), 3, arr, ws[0].data_ptr(),
-                                                          ws[1].data_ptr(), sp), _TUNE_REPS, _TUNE_WARMUP)
+                        name, _, args = self._split_args(c, s)
+                        us[str(n)] = ev.median_us(partial(_lib.call, name, *args, ws[0].data_ptr(), ws[1].data_ptr(), sp), _TUNE_REPS, _TUNE_WARMUP)
                     out.append(us)
         torch.cuda.synchronize(self.dev)
         self._choice = (None, None, None, None)
@@ -1341,7 +1364,8 @@ class InceptionEngine(GraphRunner):
         as one ``hawq_incep_stem_f32`` (``fused_stem``) or, for the uint8 chain, as one ``hawq_incep_stem_u8`` in front of the fp32
         chain's own callables.  The records' order, or with groups ``grouped_order``.  The fp32 chain leaves ``_at`` (record -> index
         of the launch that covers it) and ``group_launches``.  A conv launch - grouped, or single as a group of one - that ``_splits``
-        names is issued as ``hawq_incep_conv_group_splitk`` with its slice counts on the engine's one workspace, in the place of the
+        names is issued as the plan's split launch (``_split_args``: ``hawq_incep_conv_group_splitk``, or under ``nibble_groups``
+        ``hawq_incep_conv_group_nib_splitk`` with its mask) with its slice counts on the engine's one workspace, in the place of the
         launch it replaces (``splitk_launches``); the uint8 chain shares those callables."""
         tiles, groups, fans, nib = self._choice
         lib, sp, launches = _lib.load(), self.stream.cuda_stream, self._launches
@@ -1394,13 +1418,15 @@ class InceptionEngine(GraphRunner):
                 if is_group:
                     issued.append((list(convs), int(tile)))
             elif convs is not None and tuple(convs) in self._splits:   # in the place of the launch it replaces, a single conv as a group of one
-                g, s = self._split_args(convs, self._splits[tuple(convs)])
-                self._keep += [g, s]
+                name, g, args = self._split_args(convs, self._splits[tuple(convs)])
+                self._keep += [g, args[-1]]
                 at.update((self._convs[c], len(ops)) for c in convs)
-                ops.append(op("hawq_incep_conv_group_splitk", C.byref(g), 3, s, self._split_ws[0].data_ptr(), self._split_ws[1].data_ptr()))
+                ops.append(op(name, *args, self._split_ws[0].data_ptr(), self._split_ws[1].data_ptr()))
                 split.append((list(convs), list(self._splits[tuple(convs)])))
                 if is_group:
                     issued.append((list(convs), int(tile)))
+                    if self.nibble_groups:
+                        masks.append(args[1])
             elif is_group and self.nibble_groups:   # members of either operand form, each on the block its single launch has
                 g, mask = self._ngroup_args(convs, nib)
                 self._keep.append(g)

@@ -614,7 +614,8 @@ int hawq_incep_conv_group(const hawq_incep_group_args *g, int tile, void *stream
  *   hawq_incep_conv_group_splitk_workspace: *slab_bytes = sum over slices[i] > 1 of tiles_i * slices[i] * 128 * 64 * 4, *counter_bytes =
  *       4 * sum over slices[i] > 1 of tiles_i; non-zero if the group is refused.
  * A refused call returns non-zero (the reason, with the member, in hawq_last_error()), launches nothing and writes no byte.
- * Not covered: hawq4 operands and out_bits 4, fan-out epilogues, tile shapes other than 128 x 64, the stem and pool kernels. */
+ * Not covered: hawq4 operands and out_bits 4 (hawq_incep_conv_group_nib_splitk below), fan-out epilogues, tile shapes other than 128 x 64,
+ * the stem and pool kernels. */
 int hawq_incep_conv_group_splitk_ok(const hawq_incep_group_args *g, int tile, const int32_t *slices /* [g->n] */);
 int hawq_incep_conv_group_splitk_workspace(const hawq_incep_group_args *g, int tile, const int32_t *slices, int64_t *slab_bytes,
                                            int64_t *counter_bytes);
@@ -637,6 +638,25 @@ int hawq_incep_conv_group_splitk(const hawq_incep_group_args *g, int tile, const
 int hawq_incep_conv_group_nib_num_tiles(void);
 int hawq_incep_conv_group_nib_ok(const hawq_incep_group_args *g, uint32_t mask, int tile);
 int hawq_incep_conv_group_nib(const hawq_incep_group_args *g, uint32_t mask, int tile, void *stream);
+/* The split-K form of the mixed-form grouped launch (incep_group_nib_splitk.hip): hawq_incep_conv_group_splitk whose members are int8
+ * or hawq4 one by one, bit i of `mask` as in hawq_incep_conv_group_nib.  `tile` is a mixed-group id; only 2 (128 px x 64 ch) has this
+ * form.  Member i's K loop is cut into slices[i] slices of q_i = ceil(steps_i / slices[i]) 64-byte steps, where steps_i =
+ * ceil(KH * KW * (Cin / 16) / 4) for an int8 member and ceil(KH * KW * (Cin / 16) / 8) for a hawq4 member, whose rows hold twice the K
+ * values.  Slab, counters, their sizes and the rules for sharing them are hawq_incep_conv_group_splitk's.
+ *   hawq_incep_conv_group_nib_splitk:     writes, byte for byte, what hawq_incep_conv_group_nib(g, mask, 2, stream) writes, whatever
+ *       the slice counts: every epilogue, out_bits 8 and 16, and 4 for a hawq4 member.  A hawq4 member's partial sums stay unshifted
+ *       in the slab; the >> 4 of the nibble kernels is applied to the complete sum.
+ *   hawq_incep_conv_group_nib_splitk_ok:  1 if the launch takes this description.  Host arithmetic only: nothing is dereferenced (but
+ *       slices[0 .. n - 1]) or launched, no device is needed.  It needs tile == 2 and hawq_incep_conv_group_nib_ok(g, mask, 2); every
+ *       slices[i] in 1 .. 32; no empty slice, (slices[i] - 1) * q_i < steps_i; at least one slices[i] > 1; fewer than 2^31 workgroups.
+ *   hawq_incep_conv_group_nib_splitk_workspace: the formula of hawq_incep_conv_group_splitk_workspace; non-zero if refused.
+ * A refused call returns non-zero (the reason, with the member, in hawq_last_error()), launches nothing and writes no byte.
+ * Not covered: fan-out epilogues, mixed-group tile 1 (128 x 128). */
+int hawq_incep_conv_group_nib_splitk_ok(const hawq_incep_group_args *g, uint32_t mask, int tile, const int32_t *slices /* [g->n] */);
+int hawq_incep_conv_group_nib_splitk_workspace(const hawq_incep_group_args *g, uint32_t mask, int tile, const int32_t *slices,
+                                               int64_t *slab_bytes, int64_t *counter_bytes);
+int hawq_incep_conv_group_nib_splitk(const hawq_incep_group_args *g, uint32_t mask, int tile, const int32_t *slices, void *slab,
+                                     int32_t *counters, void *stream);
 /* The grouped launch with a fan-out epilogue (incep_fan.hip).  In the InceptionV3 plan every conv branch of a unit starts by
  * requantising the previous unit's whole 16-bit concat buffer to int8 at the branch's scale (hawq_incep_requant, one launch per
  * branch).  The convs that wrote that buffer held those values in registers; here they store the int8 copies themselves.

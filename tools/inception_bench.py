@@ -47,6 +47,7 @@ microseconds of the launch as the grouped plan issues it and of its fastest spli
 
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --splitk --pools --batches 1,2,4,8,16 [--blocks 6]
+    python tools/inception_bench.py --nibble --nibble-groups --splitk --pools --batches 1,2,4,8,16 [--blocks 6]
     python tools/inception_bench.py --input f32,u8 [--blocks 6] [--stem-launches 0]
     python tools/inception_bench.py --tune [--batches 128] [--blocks 6] [--save-plan plan.json]
     python tools/inception_bench.py --plan plan.json --batches 128
@@ -375,11 +376,12 @@ def compare_grouped(model, args, b):
 def compare_splitk(model, args, b):
     """the tuned grouped plan without and with split-K launches (``splitk=True``, tuned: that engine times tiles, groups and slice
     counts; the other replays its plan and ignores the ``"splitk"`` field, so it is the tuned grouped engine on the same tiles and
-    groups), alternating blocks; returns the split-K engine"""
+    groups), alternating blocks; returns the split-K engine.  With ``--nibble-groups`` both are the nibble plan on mixed-form groups
+    (``nibble=True, nibble_groups=True``) and the split launches are ``hawq_incep_conv_group_nib_splitk``; the table is the same"""
     from hawq_amd.engine_inception import InceptionEngine
     x = synthetic_images(b, seed=1, size=299).cuda()
     wl = f"inceptionv3_{args.scheme}_b{b}"
-    opts = dict(fast_pools=args.pools, grouped=True)
+    opts = dict(fast_pools=args.pools, nibble=True, nibble_groups=True) if args.nibble_groups else dict(fast_pools=args.pools, grouped=True)
     with torch.no_grad():
         split = InceptionEngine(model, tune=True, splitk=True, **opts)
         y1 = split(x)
@@ -600,7 +602,7 @@ def compare_nibble_fan(model, args, b):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scheme", default="uniform8")
+    ap.add_argument("--scheme", default=None, help="uniform8, or uniform4 with --splitk --nibble-groups, unless given")
     ap.add_argument("--batches", default="1,128")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -626,9 +628,11 @@ def main():
                     help="compare the tuned nibble plan on mixed-form groups (uniform4) without and with fan-out epilogues, and the tuned int8 "
                          "grouped fan-out plan")
     ap.add_argument("--splitk", action="store_true",
-                    help="compare the tuned grouped plan (fast pools with --pools) without and with split-K conv launches")
+                    help="compare the tuned grouped plan (fast pools with --pools) without and with split-K conv launches; with "
+                         "--nibble-groups (uniform4) the tuned nibble plan on mixed-form groups instead")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out / --nibble: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
+    args.scheme = args.scheme or ("uniform4" if args.splitk and args.nibble_groups else "uniform8")
     if args.save_plan and not (args.splitk or args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
         ap.error("--save-plan needs --tune, --plan, --grouped, --fan-out or --nibble: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
