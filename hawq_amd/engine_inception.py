@@ -171,6 +171,21 @@ rows of its own form: K / 64 int8, K / 128 hawq4, so a hawq4 member has half the
 timing (against ``hawq_incep_conv_group_nib``, ``hawq_incep_conv_nib`` or ``hawq_incep_conv_tiled``, whichever the plan issues), the
 ``"splitk"`` field and its StalePlan rules are as above; which kernel an entry means follows from the plan's own ``"nibble"`` and
 ``"nibble_groups"`` fields.  ``nibble=True`` without ``nibble_groups`` has no split form and raises ``PlanNotApplicable``.
+
+Band kernel for the stem.  ``InceptionEngine(model, stem_band=True)`` runs the stem's 3x3 / stride 1 convs (conv2, conv3, conv5) on
+``hawq_incep_conv_band`` (hawq_amd/csrc/incep_band.hip), which stages a band's input halo in LDS once instead of gathering every tap
+from global memory; same argument block, same bytes.  A candidate is a conv record of the stem that ``hawq_incep_conv_band_ok``
+accepts (conv1 is stride 2; under ``fused_stem`` it is not launched at all).  Records, kinds, ``conv_launches`` and the launch digest
+stay: only the entry point of the chosen records changes.  Which candidates:
+* neither ``tune`` nor ``plan``: all of them;
+* ``tune=True``: each is timed on the band kernel next to its tiles (the same method and buffers) and kept only where the band beats
+  the chosen tile - a tie goes to the tile (``stem_band_us``: conv -> microseconds);
+* ``plan=``: exactly the conv indices of its ``"stem_band"`` field (``check_stem_band``: StalePlan for an entry that is no candidate,
+  is named twice or that the library refuses); a plan without the field runs no band launch.
+``export_plan()`` writes ``"stem_band"`` (and ``"stem_band_us"``) only when the option is on; an engine without it ignores them.
+``stem_band_convs`` lists the kept conv indices.  A record that the plan runs as a split-K launch keeps that launch.  The stem is
+int8 under every other option, so this one composes with all of them.  The units' 3x3 convs are not candidates (their choice
+interacts with the groups).  Not the default.
 """
 from __future__ import annotations
 
@@ -234,14 +249,15 @@ def launch_digest(keys):
 
 
 def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None, nibble_groups=None, nibble_fan=None,
-              splitk=None):
+              splitk=None, stem_band=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
     and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
     ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field, and with `fan_out`
     (a fan-out engine's ``{"unit": k, "tiles": {launch: id}, "us": {...}}`` entries) the ``"fan_out"`` field; `nibble_groups`
     (entries as `groups`, tile ids of ``hawq_incep_conv_group_nib``) the ``"nibble_groups"`` field; `nibble_fan` (entries as
     `fan_out`, tile ids of ``hawq_incep_conv_group_nib_fan``) the ``"nibble_fan"`` field; a non-empty `splitk` (a split-K engine's
-    ``{"convs", "slices": [per member], "us"}`` entries) the ``"splitk"`` field"""
+    ``{"convs", "slices": [per member], "us"}`` entries) the ``"splitk"`` field; `stem_band` (a stem-band engine's (kept conv
+    indices, conv -> microseconds on the band kernel)) the ``"stem_band"`` and ``"stem_band_us"`` fields"""
     plan = {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
             "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
             "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
@@ -261,6 +277,9 @@ def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibb
     if splitk:   # only when some launch is split
         plan["splitk"] = [{"convs": [int(c) for c in e["convs"]], "slices": [int(s) for s in e["slices"]],
                            "us": {str(k): round(float(v), 3) for k, v in e.get("us", {}).items()}} for e in splitk]
+    if stem_band is not None:
+        plan["stem_band"] = sorted(int(c) for c in stem_band[0])
+        plan["stem_band_us"] = {str(c): round(float(v), 3) for c, v in sorted(stem_band[1].items())}
     return plan
 
 
@@ -281,6 +300,24 @@ def check_plan(plan, batch, keys, num_tiles, ok):
         if not isinstance(t, int) or isinstance(t, bool) or not 0 <= t <= num_tiles or not ok(i, t):
             raise StalePlan(f"conv launch {i} {tuple(keys[i])}: tile {t!r} is refused")
     return p_tiles
+
+
+def check_stem_band(entries, candidates, ok):
+    """The conv launches of a plan's ``"stem_band"`` field (None: no such field, no band launch), or StalePlan: not a list, an
+    entry that is not one of `candidates` (the stem's conv launches, as indices into the conv launch list), one named twice, or
+    one that ``ok(i)`` refuses."""
+    if entries is None:
+        return []
+    if not isinstance(entries, (list, tuple)):
+        raise StalePlan(f"not a list of stem conv launches: {entries!r}")
+    for i, c in enumerate(entries):
+        if not isinstance(c, int) or isinstance(c, bool) or c not in candidates:
+            raise StalePlan(f"stem band launch {c!r}: not a conv launch of the stem")
+        if c in entries[:i]:
+            raise StalePlan(f"stem band launch {c}: named twice")
+        if not ok(c):
+            raise StalePlan(f"stem band launch {c}: the band kernel refuses it")
+    return list(entries)
 
 
 def unit_convs(unit):
@@ -493,7 +530,7 @@ class _T:
 class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
                  fused_stem: bool = False, grouped: bool = False, fan_out: bool = False, nibble: bool = False,
-                 nibble_groups: bool = False, nibble_fan: bool = False, splitk=False):
+                 nibble_groups: bool = False, nibble_fan: bool = False, splitk=False, stem_band: bool = False):
         self.model, self.use_graph = model, use_graph
         if not isinstance(splitk, (bool, int)) or (not isinstance(splitk, bool) and splitk < 2):
             raise ValueError("splitk is False, True or a slice count >= 2")
@@ -505,7 +542,8 @@ class InceptionEngine(GraphRunner):
         self.splitk_launches, self.splitk_candidates, self._splits = [], [], {}
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
         self.grouped, self.fan_out, self.nibble, self.nibble_groups = bool(grouped), bool(fan_out), bool(nibble), bool(nibble_groups)
-        self.nibble_fan = bool(nibble_fan)
+        self.nibble_fan, self.stem_band = bool(nibble_fan), bool(stem_band)
+        self.stem_band_convs, self.stem_band_us, self._bands = [], {}, frozenset()
         if self.nibble and (self.grouped or self.fan_out):
             raise PlanNotApplicable("nibble=True does not compose with grouped or fan_out: their launches have no nibble form")
         if self.nibble_groups and not self.nibble:
@@ -699,6 +737,7 @@ class InceptionEngine(GraphRunner):
         self.group_launches, self.group_candidates, self.nibble_group_masks, self.nibble_fan_masks = [], [], [], []
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         self.splitk_launches, self.splitk_candidates, self._splits = [], [], {}
+        self.stem_band_convs, self.stem_band_us, self._bands = [], {}, frozenset()
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
@@ -906,12 +945,33 @@ class InceptionEngine(GraphRunner):
         elif self.grouped:
             groups = [(c, 3) for c in cands if self._group_ok(c, 3)]
         self.conv_tiles = None if tiles is None else [int(t) for t in tiles]
+        if self.stem_band:   # beside the choice, like the splits: the stem convs whose entry point is the band kernel
+            self.stem_band_convs = self._choose_bands()
         nib = self._choose_nibbles(T) if self.nibble else None
         if self.nibble_groups:   # the second component then holds the mixed-form launches (``grouped`` is off: the constructor)
             groups = self._choose_nibble_groups(self.conv_tiles, nib)
         fans = self._choose_fans(self.conv_tiles, groups, nib if self.nibble_fan else None) if self.fan_out or self.nibble_fan else None
         self._splits = self._choose_splits(self.conv_tiles, groups, nib) if self.splitk else {}   # beside the choice: launch -> slice counts
+        self._bands = frozenset(self.stem_band_convs)   # from here on: the timing forwards above ran the default entry points
         return self.conv_tiles, groups, fans, nib
+
+    # ------------------------------------------------------------------ the stem's band kernel
+    def _band_ok(self, c):
+        a = self._convs[c].args[0]
+        return a.in_ is not None and bool(_lib.load().hawq_incep_conv_band_ok(C.byref(a)))
+
+    def _choose_bands(self):
+        """The stem convs that run on ``hawq_incep_conv_band``, as conv indices: the plan's ``"stem_band"`` entries (none without
+        the field), else the candidates whose timed band launch beat their chosen tile (``tune``; ``_time`` left ``stem_band_us``),
+        else every candidate."""
+        stem = [r.ref for r in self._convs if r.place == "stem"]
+        if self.plan is not None:
+            self.stem_band_us = {int(c): float(v) for c, v in (self.plan.get("stem_band_us") or {}).items()}
+            return check_stem_band(self.plan.get("stem_band"), stem, self._band_ok)
+        cands = [c for c in stem if self._band_ok(c)]
+        if self.tune:
+            return [c for c in cands if self.stem_band_us[c] < self.conv_us[c][self.conv_tiles[c]]]
+        return cands
 
     # ------------------------------------------------------------------ split-K launches
     def _split_args(self, convs, slices):
@@ -1019,6 +1079,8 @@ class InceptionEngine(GraphRunner):
                         plain = partial(_lib.call, "hawq_incep_conv_group", C.byref(g), int(gtile[c]), sp)
                     elif mask:
                         plain = partial(_lib.call, "hawq_incep_conv_nib", C.byref(g.conv[0]), int(nib[c[0]]), sp)
+                    elif c[0] in self.stem_band_convs:
+                        plain = partial(_lib.call, "hawq_incep_conv_band", C.byref(g.conv[0]), sp)
                     else:
                         plain = partial(_lib.call, "hawq_incep_conv_tiled", C.byref(g.conv[0]), int(tiles[c[0]]), sp)
                     self.n_timing_launches += (_TUNE_WARMUP + _TUNE_REPS) * (len(var) + 1)
@@ -1340,6 +1402,11 @@ class InceptionEngine(GraphRunner):
                 convs = [us("hawq_incep_conv_tiled", r.args[0], [t for t in range(T + 1) if t == 0 or self._tile_ok(i, t)]
                             if i or not self.fused_stem else []) for i, r in enumerate(self._convs)]
                 groups = [us("hawq_incep_conv_group", self._group_args(c), tiles) for c, tiles in zip(cands, gtiles)]
+                for r in self._convs if self.stem_band else []:   # the band kernel next to the tiles of the stem convs it takes
+                    if r.place == "stem" and self._band_ok(r.ref):
+                        self.n_timing_launches += _TUNE_WARMUP + _TUNE_REPS
+                        self.stem_band_us[r.ref] = ev.median_us(partial(_lib.call, "hawq_incep_conv_band", C.byref(r.args[0]), sp),
+                                                                _TUNE_REPS, _TUNE_WARMUP)
         torch.cuda.synchronize(self.dev)
         return convs, groups
 
@@ -1354,12 +1421,13 @@ class InceptionEngine(GraphRunner):
         nfans = [f for f in self.fan_candidates if f["kept"]] if self.nibble_fan else None
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
                          groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None, ngroups, nfans,
-                         [e for e in self.splitk_candidates if e["kept"]] if self.splitk else None)
+                         [e for e in self.splitk_candidates if e["kept"]] if self.splitk else None,
+                         (self.stem_band_convs, self.stem_band_us) if self.stem_band else None)
 
     # ------------------------------------------------------------------ the writer
     def _write(self, u8=False):
         """The callables of one chain, from the records, ``_choice`` and the engine's options - the only place that makes one.  Per
-        record: a conv alone, tiled with its chosen id or as a member of a grouped launch; a pool on its named entry point or, under
+        record: a conv alone, tiled with its chosen id, on the band kernel (``_bands``) or as a member of a grouped launch; a pool on its named entry point or, under
         ``fast_pools`` where the library takes it, on ``hawq_incep_pool_v``.  The stem's head (the records up to conv1) as it stands,
         as one ``hawq_incep_stem_f32`` (``fused_stem``) or, for the uint8 chain, as one ``hawq_incep_stem_u8`` in front of the fp32
         chain's own callables.  The records' order, or with groups ``grouped_order``.  The fp32 chain leaves ``_at`` (record -> index
@@ -1383,6 +1451,8 @@ class InceptionEngine(GraphRunner):
             if nib and r in self._nib_pool:   # an entry requant that writes hawq4: only the vectorised family has that form
                 return op("hawq_incep_pool_v", C.byref(self._nib_pool[r]), r.ref)
             a = C.byref(r.args[0])
+            if r.kind == "conv" and r.ref in self._bands:   # a stem conv on the band kernel: the record's own block
+                return op("hawq_incep_conv_band", a)
             if r.kind == "conv":
                 return op(r.name, a) if tiles is None else op("hawq_incep_conv_tiled", a, int(tiles[r.ref]))
             fast = self.fast_pools and lib.hawq_incep_pool_v_ok(a, r.ref)

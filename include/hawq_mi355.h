@@ -560,6 +560,18 @@ int hawq_incep_conv(const hawq_incep_conv_args *a, void *stream);
 int hawq_incep_conv_num_tiles(void);
 int hawq_incep_conv_tile_ok(const hawq_incep_conv_args *a, int tile);
 int hawq_incep_conv_tiled(const hawq_incep_conv_args *a, int tile, void *stream);
+/* LDS-band kernel for the same launch where it is a 3x3 / stride 1 conv on a narrow input (incep_band.hip; the stem's convs): a
+ * workgroup stages the input halo of a band of output pixels ((rows + 2) x 34 pixels) in LDS once and keeps its output channels'
+ * weights there, so the nine taps are LDS offsets.  Same argument block, same integers: it writes, byte for byte, what
+ * hawq_incep_conv writes, and never touches a channel of an output row outside c_off .. c_off + Cout - 1.
+ *   hawq_incep_conv_band_ok: 1 if the kernel takes this launch.  Host arithmetic on the argument block only: no pointer is
+ *       dereferenced, nothing is launched, no device is needed.  It needs what hawq_incep_conv needs, KH == KW == 3, stride 1,
+ *       pad_h == pad_w in 0 .. 1, Cin <= 96, in, wgt and out 16-byte aligned, ldo and c_off multiples of 16, and RAW with out_bits 32
+ *       or REQUANT / REQUANT2 with out_bits 8 or 16.
+ *   hawq_incep_conv_band:    the launch.  A refused block returns an error (the reason in hawq_last_error()), launches nothing and
+ *       writes no byte of out. */
+int hawq_incep_conv_band_ok(const hawq_incep_conv_args *a);
+int hawq_incep_conv_band(const hawq_incep_conv_args *a, void *stream);
 /* The same launch on nibble-packed operands (incep_nib.hip), on the same argument block:
  *   in:   UNSIGNED 4-bit activations (0 .. 15), hawq4 NHWC rows: Cin / 2 bytes per pixel
  *   wgt:  signed 4-bit weights (-8 .. 7), hawq4 [Cout][KH][KW][Cin] (hawq_amd.packing.pack_conv_weight(..., w_bits=4))

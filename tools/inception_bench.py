@@ -44,6 +44,10 @@ producer launches + residual requants, in microseconds, kept or not.
 ``"splitk"`` field): alternating blocks as above, an assertion that the logits are bit-equal, [smallest block, largest block] per
 engine, whether the two ranges overlap, and a table of the candidate launches - workgroups on 128 x 64 tiles, chosen slices, the
 microseconds of the launch as the grouped plan issues it and of its fastest split form, kept or not.
+With ``--stem-band``: the tuned plan (``--pools``: on fast pools) against the same plan with ``stem_band=True`` (the stem's 3x3 /
+stride 1 convs on ``hawq_incep_conv_band`` where that beat their best tile): alternating blocks as above, an assertion that the logits
+are bit-equal, and per candidate launch its time on the band kernel and on its best tile, its MACs and bytes (in + weights + out)
+from the shapes, the MAC rate, bytes over time and the byte floor at ``roofline.HBM_PEAK_GBS``.
 
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --splitk --pools --batches 1,2,4,8,16 [--blocks 6]
@@ -52,6 +56,7 @@ microseconds of the launch as the grouped plan issues it and of its fastest spli
     python tools/inception_bench.py --tune [--batches 128] [--blocks 6] [--save-plan plan.json]
     python tools/inception_bench.py --plan plan.json --batches 128
     python tools/inception_bench.py --tune --pools --batches 128,1
+    python tools/inception_bench.py --tune --pools --stem-band --batches 128,1
     python tools/inception_bench.py --fused-stem [--tune --pools] --batches 128,1 --stem-launches 20
     python tools/inception_bench.py --grouped --batches 1,16,128 [--blocks 6]
     python tools/inception_bench.py --fan-out [--grouped] --batches 1,16,128 [--blocks 6]
@@ -373,6 +378,56 @@ def compare_grouped(model, args, b):
     return grouped
 
 
+def compare_stem_band(model, args, b):
+    """the tuned tile plan (fast pools with ``--pools``) without and with the stem's convs on the band kernel, alternating blocks;
+    returns the stem-band engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    from hawq_amd.roofline import HBM_PEAK_GBS
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    with torch.no_grad():
+        band = InceptionEngine(model, tune=True, fast_pools=args.pools, stem_band=True)
+        y1 = band(x)
+        plan = {k: v for k, v in band.export_plan().items() if not k.startswith("stem_band")}
+        tile = InceptionEngine(model, plan=plan, fast_pools=args.pools)   # the same tiles, no band launch
+        engines = {"tile": tile, "band": band}
+        equal = bool(torch.equal(tile(x), y1))
+        assert equal, "the logits with the band kernel differ from the tiled plan's"
+        assert tile.conv_tiles == band.conv_tiles and "hawq_incep_conv_band" not in tile.op_names
+        print(f"# {wl}: conv | HxW Cin->Cout pad | best tile | tile us | band us | kept | GMAC | MB in+wgt+out | band TMAC/s | "
+              f"band GB/s | byte floor us at {HBM_PEAK_GBS:.0f} GB/s | tile TMAC/s")
+        for c, us in sorted(band.stem_band_us.items()):
+            H, W, Cin, Cout, KH, KW, _, ph, pw, _, bits = band.conv_launches[c][:11]
+            Ho, Wo = H + 2 * ph - KH + 1, W + 2 * pw - KW + 1
+            mac = b * Ho * Wo * Cout * KH * KW * Cin
+            nbytes = b * H * W * Cin + Cout * KH * KW * Cin + b * Ho * Wo * Cout * bits // 8
+            t = band.conv_tiles[c]
+            t_us = band.conv_us[c][t]
+            print(f"# {c} | {H}x{W} {Cin}->{Cout} p{ph} | {t} | {t_us:.1f} | {us:.1f} | {'band' if c in band.stem_band_convs else 'tile'} | "
+                  f"{mac / 1e9:.2f} | {nbytes / 1e6:.1f} | {mac / us / 1e6:.1f} | {nbytes / us / 1e3:.0f} | "
+                  f"{nbytes / HBM_PEAK_GBS / 1e3:.1f} | {mac / t_us / 1e6:.1f}")
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": "tuned", "fast_pools": bool(args.pools), "stem": k,
+                              "ms_per_batch": round(mean, 4), "images_per_s": round(b * 1000.0 / mean, 1),
+                              "block_min_ms": round(min(v), 4), "block_max_ms": round(max(v), 4), "blocks": len(v),
+                              "steps": args.steps, "band_launches": e.op_names.count("hawq_incep_conv_band"),
+                              "logits_bit_equal": equal}), flush=True)
+        m0, m1 = sum(ms["tile"]) / args.blocks, sum(ms["band"]) / args.blocks
+        print(json.dumps({"workload": wl, "band_over_tile_rate": round(m0 / m1, 4), "gain_ms": round(m0 - m1, 4),
+                          "stem_band_kept": band.stem_band_convs,
+                          "ranges_overlap": bool(min(ms["tile"]) <= max(ms["band"]) and min(ms["band"]) <= max(ms["tile"]))}), flush=True)
+    return band
+
+
 def compare_splitk(model, args, b):
     """the tuned grouped plan without and with split-K launches (``splitk=True``, tuned: that engine times tiles, groups and slice
     counts; the other replays its plan and ignores the ``"splitk"`` field, so it is the tuned grouped engine on the same tiles and
@@ -630,10 +685,12 @@ def main():
     ap.add_argument("--splitk", action="store_true",
                     help="compare the tuned grouped plan (fast pools with --pools) without and with split-K conv launches; with "
                          "--nibble-groups (uniform4) the tuned nibble plan on mixed-form groups instead")
+    ap.add_argument("--stem-band", action="store_true",
+                    help="compare the tuned plan (fast pools with --pools) without and with the stem's 3x3 convs on the band kernel")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out / --nibble: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
     args.scheme = args.scheme or ("uniform4" if args.splitk and args.nibble_groups else "uniform8")
-    if args.save_plan and not (args.splitk or args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
+    if args.save_plan and not (args.stem_band or args.splitk or args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
         ap.error("--save-plan needs --tune, --plan, --grouped, --fan-out or --nibble: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
@@ -641,8 +698,8 @@ def main():
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.splitk:
-            tuned = compare_splitk(model, args, b)
+        if args.splitk or args.stem_band:
+            tuned = (compare_stem_band if args.stem_band else compare_splitk)(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
                     json.dump(tuned.export_plan(), f)
