@@ -275,6 +275,8 @@ SIGNATURES = {
     "hawq_incep_conv_tiled": [C.POINTER(IncepConvArgs), i32, vp],
     "hawq_incep_conv_band_ok": [C.POINTER(IncepConvArgs)],
     "hawq_incep_conv_band": [C.POINTER(IncepConvArgs), vp],
+    "hawq_incep_conv_band_pool_ok": [C.POINTER(IncepConvArgs)],
+    "hawq_incep_conv_band_pool": [C.POINTER(IncepConvArgs), vp],
     "hawq_incep_conv_nib_num_tiles": [],
     "hawq_incep_conv_nib_ok": [C.POINTER(IncepConvArgs), i32],
     "hawq_incep_conv_nib": [C.POINTER(IncepConvArgs), i32, vp],

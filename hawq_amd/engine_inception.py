@@ -186,6 +186,22 @@ stay: only the entry point of the chosen records changes.  Which candidates:
 ``stem_band_convs`` lists the kept conv indices.  A record that the plan runs as a split-K launch keeps that launch.  The stem is
 int8 under every other option, so this one composes with all of them.  The units' 3x3 convs are not candidates (their choice
 interacts with the groups).  Not the default.
+
+Conv + max pool in one launch for the stem.  ``InceptionEngine(model, stem_pool=True)`` issues a stem conv whose dense output only
+the ``hawq_incep_maxpool3s2`` record behind it reads (no ``pre`` / ``post``; ``stem_pool_pairs``: conv3 + pool1 and conv5 + pool2,
+conv indices 2 and 4) as one ``hawq_incep_conv_band_pool`` (hawq_amd/csrc/incep_band_pool.hip) on a copy of the conv's block whose
+``out`` / ``ldo`` / ``c_off`` are the pool's: the full-resolution tensor is never written.  The records stay; ``_write`` issues the
+launch in the conv's place and nothing in the pool's, so ``n_launches`` drops by one per pair (``pool_launches`` names the fused
+launch for such a pool).  The conv's buffer stays allocated (the tuner and the two-launch form use it).  Which pairs:
+* neither ``tune`` nor ``plan``: every candidate ``hawq_incep_conv_band_pool_ok`` accepts;
+* ``tune=True``: last of all choices, the pair as the plan issues it (conv on its chosen tile or band launch, then the pool on the
+  entry point ``fast_pools`` selects) is timed as a block against the fused launch, which is kept only where it is faster - a tie
+  goes to the pair (``stem_pool_us``: conv -> [pair, fused] microseconds);
+* ``plan=``: exactly the conv indices of its ``"stem_pool"`` field (``check_stem_pool``: StalePlan for an entry that is no
+  candidate, is named twice or that the library refuses); a plan without the field fuses nothing.
+``export_plan()`` writes ``"stem_pool"`` and ``"stem_pool_us"`` only when the option is on; an engine without it ignores them.
+``stem_pool_convs`` lists the kept convs; ``stem_band_convs`` leaves them out (the pooled launch wins).  A conv that the plan runs
+as a split-K launch keeps that launch and its pool.  No candidate at all raises ``PlanNotApplicable``.  Not the default.
 """
 from __future__ import annotations
 
@@ -249,7 +265,7 @@ def launch_digest(keys):
 
 
 def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None, nibble_groups=None, nibble_fan=None,
-              splitk=None, stem_band=None):
+              splitk=None, stem_band=None, stem_pool=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
     and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
     ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field, and with `fan_out`
@@ -257,7 +273,8 @@ def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibb
     (entries as `groups`, tile ids of ``hawq_incep_conv_group_nib``) the ``"nibble_groups"`` field; `nibble_fan` (entries as
     `fan_out`, tile ids of ``hawq_incep_conv_group_nib_fan``) the ``"nibble_fan"`` field; a non-empty `splitk` (a split-K engine's
     ``{"convs", "slices": [per member], "us"}`` entries) the ``"splitk"`` field; `stem_band` (a stem-band engine's (kept conv
-    indices, conv -> microseconds on the band kernel)) the ``"stem_band"`` and ``"stem_band_us"`` fields"""
+    indices, conv -> microseconds on the band kernel)) the ``"stem_band"`` and ``"stem_band_us"`` fields; `stem_pool` (a stem-pool
+    engine's (kept conv indices, conv -> [pair, fused] microseconds)) the ``"stem_pool"`` and ``"stem_pool_us"`` fields"""
     plan = {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
             "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
             "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
@@ -280,6 +297,9 @@ def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibb
     if stem_band is not None:
         plan["stem_band"] = sorted(int(c) for c in stem_band[0])
         plan["stem_band_us"] = {str(c): round(float(v), 3) for c, v in sorted(stem_band[1].items())}
+    if stem_pool is not None:
+        plan["stem_pool"] = sorted(int(c) for c in stem_pool[0])
+        plan["stem_pool_us"] = {str(c): [round(float(v), 3) for v in us] for c, us in sorted(stem_pool[1].items())}
     return plan
 
 
@@ -317,6 +337,43 @@ def check_stem_band(entries, candidates, ok):
             raise StalePlan(f"stem band launch {c}: named twice")
         if not ok(c):
             raise StalePlan(f"stem band launch {c}: the band kernel refuses it")
+    return list(entries)
+
+
+def stem_pool_pairs(records):
+    """conv index -> (conv record, pool record) of every stem conv + max pool pair that one ``hawq_incep_conv_band_pool`` launch
+    can stand for: a conv record of the stem that writes a dense tensor which the ``hawq_incep_maxpool3s2`` record behind it reads
+    whole, in the same container and without ``pre`` / ``post`` tables, and which no other record reads."""
+    def reads(q, ptr):
+        return q.args[0].in_ == ptr if q.kind in ("conv", "pool") else ptr in q.args
+
+    pairs = {}
+    for r, p in zip(records, records[1:]):
+        if r.kind != "conv" or r.place != "stem" or p.kind != "pool" or p.name != "hawq_incep_maxpool3s2":
+            continue
+        a, b = r.args[0], p.args[0]
+        dense = a.c_off == 0 and a.ldo == a.Cout and b.in_off == 0 and b.in_pitch == a.ldo and b.C == a.Cout
+        if dense and b.in_ == a.out and not b.pre and not b.post and b.in_bits == a.out_bits == b.out_bits and \
+                not any(reads(q, a.out) for q in records if q is not p):
+            pairs[r.ref] = (r, p)
+    return pairs
+
+
+def check_stem_pool(entries, candidates, ok):
+    """The stem convs of a plan's ``"stem_pool"`` field (None: no such field, no fused launch), or StalePlan: not a list, an entry
+    that is not one of `candidates` (``stem_pool_pairs``, as indices into the conv launch list), one named twice, or one that
+    ``ok(i)`` refuses."""
+    if entries is None:
+        return []
+    if not isinstance(entries, (list, tuple)):
+        raise StalePlan(f"not a list of stem conv launches: {entries!r}")
+    for i, c in enumerate(entries):
+        if not isinstance(c, int) or isinstance(c, bool) or c not in candidates:
+            raise StalePlan(f"stem pool launch {c!r}: not a stem conv that only a max pool reads")
+        if c in entries[:i]:
+            raise StalePlan(f"stem pool launch {c}: named twice")
+        if not ok(c):
+            raise StalePlan(f"stem pool launch {c}: the fused kernel refuses it")
     return list(entries)
 
 
@@ -530,7 +587,8 @@ class _T:
 class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
                  fused_stem: bool = False, grouped: bool = False, fan_out: bool = False, nibble: bool = False,
-                 nibble_groups: bool = False, nibble_fan: bool = False, splitk=False, stem_band: bool = False):
+                 nibble_groups: bool = False, nibble_fan: bool = False, splitk=False, stem_band: bool = False,
+                 stem_pool: bool = False):
         self.model, self.use_graph = model, use_graph
         if not isinstance(splitk, (bool, int)) or (not isinstance(splitk, bool) and splitk < 2):
             raise ValueError("splitk is False, True or a slice count >= 2")
@@ -542,8 +600,9 @@ class InceptionEngine(GraphRunner):
         self.splitk_launches, self.splitk_candidates, self._splits = [], [], {}
         self.tune, self.plan, self.fast_pools, self.fused_stem = bool(tune), plan, bool(fast_pools), bool(fused_stem)
         self.grouped, self.fan_out, self.nibble, self.nibble_groups = bool(grouped), bool(fan_out), bool(nibble), bool(nibble_groups)
-        self.nibble_fan, self.stem_band = bool(nibble_fan), bool(stem_band)
+        self.nibble_fan, self.stem_band, self.stem_pool = bool(nibble_fan), bool(stem_band), bool(stem_pool)
         self.stem_band_convs, self.stem_band_us, self._bands = [], {}, frozenset()
+        self.stem_pool_convs, self.stem_pool_us, self._pooled = [], {}, {}
         if self.nibble and (self.grouped or self.fan_out):
             raise PlanNotApplicable("nibble=True does not compose with grouped or fan_out: their launches have no nibble form")
         if self.nibble_groups and not self.nibble:
@@ -738,6 +797,7 @@ class InceptionEngine(GraphRunner):
         self.fan_launches, self.fan_candidates, self.residual_requants = [], [], []
         self.splitk_launches, self.splitk_candidates, self._splits = [], [], {}
         self.stem_band_convs, self.stem_band_us, self._bands = [], {}, frozenset()
+        self.stem_pool_convs, self.stem_pool_us, self._pooled = [], {}, {}
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
@@ -952,7 +1012,12 @@ class InceptionEngine(GraphRunner):
             groups = self._choose_nibble_groups(self.conv_tiles, nib)
         fans = self._choose_fans(self.conv_tiles, groups, nib if self.nibble_fan else None) if self.fan_out or self.nibble_fan else None
         self._splits = self._choose_splits(self.conv_tiles, groups, nib) if self.splitk else {}   # beside the choice: launch -> slice counts
+        if self.stem_pool:   # last: the pair it competes with is the one the rest of the choice issues
+            fused = self._choose_pools(self.conv_tiles, groups, nib)
+            self.stem_pool_convs = sorted(fused)
+            self.stem_band_convs = [c for c in self.stem_band_convs if c not in fused]   # the pooled launch wins
         self._bands = frozenset(self.stem_band_convs)   # from here on: the timing forwards above ran the default entry points
+        self._pooled = fused if self.stem_pool else {}
         return self.conv_tiles, groups, fans, nib
 
     # ------------------------------------------------------------------ the stem's band kernel
@@ -972,6 +1037,60 @@ class InceptionEngine(GraphRunner):
         if self.tune:
             return [c for c in cands if self.stem_band_us[c] < self.conv_us[c][self.conv_tiles[c]]]
         return cands
+
+    # ------------------------------------------------------------------ the stem's conv + max pool launches
+    def _choose_pools(self, tiles, groups, nib):
+        """The stem conv + max pool pairs that run as one ``hawq_incep_conv_band_pool``, as conv index -> (the launch's block, the
+        pool record it leaves nothing of): the plan's ``"stem_pool"`` entries (none without the field), else the candidates whose
+        timed fused launch beat the pair as the plan issues it (``tune``; ``stem_pool_us``: conv -> [pair, fused]), else every
+        candidate the library takes.  A conv that the plan runs as a split-K launch is no candidate."""
+        pairs, blocks = stem_pool_pairs(self._launches), {}
+        if not pairs:
+            raise PlanNotApplicable("stem_pool: no stem conv of this model is read by a table-free 3x3 / stride 2 max pool alone")
+        for c, (r, p) in pairs.items():   # the conv's block, writing where the pool writes
+            f = _lib.IncepConvArgs.from_buffer_copy(r.args[0])
+            f.out, f.ldo, f.c_off = p.args[0].out, p.args[0].ldo, p.args[0].c_off
+            blocks[c] = f
+        ok = lambda c: blocks[c].in_ is not None and (c,) not in self._splits and \
+            bool(_lib.load().hawq_incep_conv_band_pool_ok(C.byref(blocks[c])))   # noqa: E731
+        if self.plan is not None:
+            self.stem_pool_us = {int(c): [float(v) for v in us] for c, us in (self.plan.get("stem_pool_us") or {}).items()}
+            kept = check_stem_pool(self.plan.get("stem_pool"), list(pairs), ok)
+        else:
+            kept = [c for c in pairs if ok(c)]
+            if self.tune and kept:
+                self._time_pools(kept, pairs, blocks, tiles, groups, nib)
+                kept = [c for c in kept if self.stem_pool_us[c][1] < self.stem_pool_us[c][0]]   # a tie goes to the pair
+        self._keep += [blocks[c] for c in kept]
+        return {c: (blocks[c], pairs[c][1]) for c in kept}
+
+    def _time_pools(self, cands, pairs, blocks, tiles, groups, nib):
+        """``stem_pool_us[c]`` = [the pair, the fused launch] in microseconds for every conv of `cands`, on the buffers of a forward
+        of the plan and by the method of the other timings; the pair is the conv on its chosen tile or band launch, then the pool
+        on the entry point ``fast_pools`` selects, timed as a block."""
+        lib, sp = _lib.load(), self.stream.cuda_stream
+        self._choice = (tiles, groups, None, nib or None)
+        with EventTimer(sp, _TUNE_REPS + 1) as ev:
+            torch.cuda.synchronize(self.dev)
+            with torch.cuda.stream(self.stream):
+                for op in self._write():
+                    op()
+                for c in cands:
+                    a, b = C.byref(pairs[c][0].args[0]), C.byref(pairs[c][1].args[0])
+                    if c in self.stem_band_convs:
+                        conv = partial(_lib.call, "hawq_incep_conv_band", a, sp)
+                    else:
+                        conv = partial(_lib.call, "hawq_incep_conv_tiled", a, int(tiles[c]), sp)
+                    if self.fast_pools and lib.hawq_incep_pool_v_ok(b, pairs[c][1].ref):
+                        pool = partial(_lib.call, "hawq_incep_pool_v", b, pairs[c][1].ref, sp)
+                    else:
+                        pool = partial(_lib.call, pairs[c][1].name, b, sp)
+                    fused = partial(_lib.call, "hawq_incep_conv_band_pool", C.byref(blocks[c]), sp)
+                    self.n_timing_launches += 3 * (_TUNE_WARMUP + _TUNE_REPS)
+                    self.stem_pool_us[c] = [ev.median_us(lambda: (conv(), pool()), _TUNE_REPS, _TUNE_WARMUP),
+                                            ev.median_us(fused, _TUNE_REPS, _TUNE_WARMUP)]
+        torch.cuda.synchronize(self.dev)
+        self._choice = (None, None, None, None)
 
     # ------------------------------------------------------------------ split-K launches
     def _split_args(self, convs, slices):
@@ -1422,7 +1541,8 @@ class InceptionEngine(GraphRunner):
         return make_plan(self._batch, self.conv_launches, _lib.load().hawq_incep_conv_num_tiles(), self.conv_tiles, self.conv_us,
                          groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None, ngroups, nfans,
                          [e for e in self.splitk_candidates if e["kept"]] if self.splitk else None,
-                         (self.stem_band_convs, self.stem_band_us) if self.stem_band else None)
+                         (self.stem_band_convs, self.stem_band_us) if self.stem_band else None,
+                         (self.stem_pool_convs, self.stem_pool_us) if self.stem_pool else None)
 
     # ------------------------------------------------------------------ the writer
     def _write(self, u8=False):
@@ -1434,7 +1554,8 @@ class InceptionEngine(GraphRunner):
         of the launch that covers it) and ``group_launches``.  A conv launch - grouped, or single as a group of one - that ``_splits``
         names is issued as the plan's split launch (``_split_args``: ``hawq_incep_conv_group_splitk``, or under ``nibble_groups``
         ``hawq_incep_conv_group_nib_splitk`` with its mask) with its slice counts on the engine's one workspace, in the place of the
-        launch it replaces (``splitk_launches``); the uint8 chain shares those callables."""
+        launch it replaces (``splitk_launches``); the uint8 chain shares those callables.  A stem conv that ``_pooled`` names is
+        issued as one ``hawq_incep_conv_band_pool`` on the block kept there, and nothing is issued for its max pool record."""
         tiles, groups, fans, nib = self._choice
         lib, sp, launches = _lib.load(), self.stream.cuda_stream, self._launches
         fan_of = {s: (b, t) for b, by_set in fans or [] for s, t in by_set.items()}           # producer launch -> its boundary, tile
@@ -1519,6 +1640,11 @@ class InceptionEngine(GraphRunner):
                     fast = a.out_bits == 4 or (self.fast_pools and lib.hawq_incep_pool_v_ok(C.byref(a), r.ref))   # hawq4: pool_v only
                     ops.append(op("hawq_incep_pool_v", C.byref(a), r.ref) if fast else op(r.name, C.byref(a)))
                     residual.append((b["unit"], i, off, c))
+            elif r.kind == "conv" and r.ref in self._pooled:   # a stem conv + max pool pair in one launch, in the conv's place
+                at[r] = at[self._pooled[r.ref][1]] = len(ops)
+                ops.append(op("hawq_incep_conv_band_pool", C.byref(self._pooled[r.ref][0])))
+            elif r.kind == "pool" and any(r is p for _, p in self._pooled.values()):   # nothing in the pool's place
+                pass
             else:
                 at[r] = len(ops)
                 ops.append(single(r))

@@ -572,6 +572,19 @@ int hawq_incep_conv_tiled(const hawq_incep_conv_args *a, int tile, void *stream)
  *       writes no byte of out. */
 int hawq_incep_conv_band_ok(const hawq_incep_conv_args *a);
 int hawq_incep_conv_band(const hawq_incep_conv_args *a, void *stream);
+/* The same 3x3 / stride 1 conv followed by a 3x3 / stride 2 max pool without padding, in one launch (incep_band_pool.hip; the stem
+ * pairs q_conv3 + q_pool1 and q_conv5 + q_pool2).  The block describes the conv as above; out, ldo, c_off and out_bits describe the
+ * POOLED tensor [N][Hp][Wp][ldo] with Ho = H + 2 pad - 2, Hp = (Ho - 3) / 2 + 1 and likewise for the width.  It writes, byte for
+ * byte, what hawq_incep_conv (REQUANT, out_bits 8 or 16) into a dense [N][Ho][Wo][Cout] tensor followed by hawq_incep_maxpool3s2
+ * without tables writes; the dense tensor never reaches memory: the requantised values stay in an LDS ring of conv rows that the
+ * workgroup pools as it walks its column strip downwards.  Channels outside c_off .. c_off + Cout - 1 of a pooled row are not touched.
+ *   hawq_incep_conv_band_pool_ok: 1 if the kernel takes this launch (host arithmetic only, nothing dereferenced): what
+ *       hawq_incep_conv_band_ok needs, the REQUANT epilogue (RAW and REQUANT2 are refused), out_bits 8 or 16, Ho >= 3 and Wo >= 3,
+ *       ldo >= c_off + Cout, and fewer than 2^31 - 1024 strips (images x column strips).
+ *   hawq_incep_conv_band_pool:    the launch.  A refused block returns an error (the reason in hawq_last_error()), launches nothing
+ *       and writes no byte of out. */
+int hawq_incep_conv_band_pool_ok(const hawq_incep_conv_args *a);
+int hawq_incep_conv_band_pool(const hawq_incep_conv_args *a, void *stream);
 /* The same launch on nibble-packed operands (incep_nib.hip), on the same argument block:
  *   in:   UNSIGNED 4-bit activations (0 .. 15), hawq4 NHWC rows: Cin / 2 bytes per pixel
  *   wgt:  signed 4-bit weights (-8 .. 7), hawq4 [Cout][KH][KW][Cin] (hawq_amd.packing.pack_conv_weight(..., w_bits=4))

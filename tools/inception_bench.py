@@ -48,6 +48,11 @@ With ``--stem-band``: the tuned plan (``--pools``: on fast pools) against the sa
 stride 1 convs on ``hawq_incep_conv_band`` where that beat their best tile): alternating blocks as above, an assertion that the logits
 are bit-equal, and per candidate launch its time on the band kernel and on its best tile, its MACs and bytes (in + weights + out)
 from the shapes, the MAC rate, bytes over time and the byte floor at ``roofline.HBM_PEAK_GBS``.
+With ``--stem-pool``: one tuned plan (``--pools``, ``--fused-stem``, ``--grouped``, ``--fan-out`` select its other options) against the
+same plan with ``stem_pool=True`` (a stem conv + max pool pair as one ``hawq_incep_conv_band_pool`` where that beat the pair):
+alternating blocks as above, an assertion that the logits are bit-equal, and per pair the microseconds of the pair and of the fused
+launch, which one runs, the bytes each form moves (input + weights + outputs, the full-resolution tensor written and read once by
+the pair) and the byte floor of each at ``roofline.HBM_PEAK_GBS``.
 
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --splitk --pools --batches 1,2,4,8,16 [--blocks 6]
@@ -57,6 +62,7 @@ from the shapes, the MAC rate, bytes over time and the byte floor at ``roofline.
     python tools/inception_bench.py --plan plan.json --batches 128
     python tools/inception_bench.py --tune --pools --batches 128,1
     python tools/inception_bench.py --tune --pools --stem-band --batches 128,1
+    python tools/inception_bench.py --tune --pools --stem-pool [--grouped --fan-out] --batches 128,1
     python tools/inception_bench.py --fused-stem [--tune --pools] --batches 128,1 --stem-launches 20
     python tools/inception_bench.py --grouped --batches 1,16,128 [--blocks 6]
     python tools/inception_bench.py --fan-out [--grouped] --batches 1,16,128 [--blocks 6]
@@ -428,6 +434,57 @@ def compare_stem_band(model, args, b):
     return band
 
 
+def compare_stem_pool(model, args, b):
+    """one tuned plan without and with the stem's conv + max pool pairs in one launch each, alternating blocks; returns the
+    stem-pool engine"""
+    from hawq_amd.engine_inception import InceptionEngine
+    from hawq_amd.roofline import HBM_PEAK_GBS
+    FUSED = "hawq_incep_conv_band_pool"
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    opts = dict(fast_pools=args.pools, fused_stem=args.fused_stem, grouped=args.grouped, fan_out=args.fan_out)
+    with torch.no_grad():
+        pooled = InceptionEngine(model, tune=True, stem_pool=True, **opts)
+        y1 = pooled(x)
+        plan = {k: v for k, v in pooled.export_plan().items() if not k.startswith("stem_pool")}
+        pair = InceptionEngine(model, plan=plan, **opts)   # the same choice, every pair as two launches
+        engines = {"pair": pair, "fused": pooled}
+        equal = bool(torch.equal(pair(x), y1))
+        assert equal, "the logits with the fused conv + pool launches differ from the two-launch plan's"
+        assert pair.conv_tiles == pooled.conv_tiles and FUSED not in pair.op_names
+        print(f"# {wl}: conv | HxW Cin->Cout pad, bits | pair us | fused us | runs | pair MB | fused MB | pair floor us | fused floor us "
+              f"at {HBM_PEAK_GBS:.0f} GB/s | fused GB/s")
+        for c, (t_pair, t_fused) in sorted(pooled.stem_pool_us.items()):
+            H, W, Cin, Cout, KH, KW, _, ph, pw, _, bits = pooled.conv_launches[c][:11]
+            Ho, Wo = H + 2 * ph - KH + 1, W + 2 * pw - KW + 1
+            full, small = b * Ho * Wo * Cout * bits // 8, b * ((Ho - 3) // 2 + 1) * ((Wo - 3) // 2 + 1) * Cout * bits // 8
+            base = b * H * W * Cin + Cout * KH * KW * Cin
+            print(f"# {c} | {H}x{W} {Cin}->{Cout} p{ph}, {bits} | {t_pair:.1f} | {t_fused:.1f} | "
+                  f"{'fused' if c in pooled.stem_pool_convs else 'pair'} | {(base + 2 * full + small) / 1e6:.1f} | {(base + small) / 1e6:.1f} | "
+                  f"{(base + 2 * full + small) / HBM_PEAK_GBS / 1e3:.1f} | {(base + small) / HBM_PEAK_GBS / 1e3:.1f} | "
+                  f"{(base + small) / t_fused / 1e3:.0f}")
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": "tuned", **{o: bool(f) for o, f in opts.items()}, "stem": k,
+                              "ms_per_batch": round(mean, 4), "images_per_s": round(b * 1000.0 / mean, 1),
+                              "block_min_ms": round(min(v), 4), "block_max_ms": round(max(v), 4), "blocks": len(v),
+                              "steps": args.steps, "launches": e.n_launches, "fused_launches": e.op_names.count(FUSED),
+                              "logits_bit_equal": equal}), flush=True)
+        m0, m1 = sum(ms["pair"]) / args.blocks, sum(ms["fused"]) / args.blocks
+        print(json.dumps({"workload": wl, "fused_over_pair_rate": round(m0 / m1, 4), "gain_ms": round(m0 - m1, 4),
+                          "stem_pool_kept": pooled.stem_pool_convs,
+                          "ranges_overlap": bool(min(ms["pair"]) <= max(ms["fused"]) and min(ms["fused"]) <= max(ms["pair"]))}), flush=True)
+    return pooled
+
+
 def compare_splitk(model, args, b):
     """the tuned grouped plan without and with split-K launches (``splitk=True``, tuned: that engine times tiles, groups and slice
     counts; the other replays its plan and ignores the ``"splitk"`` field, so it is the tuned grouped engine on the same tiles and
@@ -687,10 +744,13 @@ def main():
                          "--nibble-groups (uniform4) the tuned nibble plan on mixed-form groups instead")
     ap.add_argument("--stem-band", action="store_true",
                     help="compare the tuned plan (fast pools with --pools) without and with the stem's 3x3 convs on the band kernel")
+    ap.add_argument("--stem-pool", action="store_true",
+                    help="compare one tuned plan (--pools, --fused-stem, --grouped, --fan-out select its other options) without and "
+                         "with the stem's conv + max pool pairs in one launch each")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out / --nibble: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
     args.scheme = args.scheme or ("uniform4" if args.splitk and args.nibble_groups else "uniform8")
-    if args.save_plan and not (args.stem_band or args.splitk or args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
+    if args.save_plan and not (args.stem_pool or args.stem_band or args.splitk or args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
         ap.error("--save-plan needs --tune, --plan, --grouped, --fan-out or --nibble: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
@@ -698,8 +758,8 @@ def main():
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.splitk or args.stem_band:
-            tuned = (compare_stem_band if args.stem_band else compare_splitk)(model, args, b)
+        if args.stem_pool or args.splitk or args.stem_band:
+            tuned = (compare_stem_pool if args.stem_pool else compare_stem_band if args.stem_band else compare_splitk)(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
                     json.dump(tuned.export_plan(), f)
