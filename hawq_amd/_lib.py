@@ -307,6 +307,8 @@ SIGNATURES = {
     "hawq_incep_pool_v_ok": [C.POINTER(IncepPoolArgs), i32],
     "hawq_incep_pool_v": [C.POINTER(IncepPoolArgs), i32, vp],
     "hawq_incep_pool_v_avg3_tile": [C.POINTER(IncepPoolArgs), C.POINTER(i32), C.POINTER(i32)],
+    "hawq_incep_avgpool_conv_ok": [C.POINTER(IncepPoolArgs), C.POINTER(IncepConvArgs)],
+    "hawq_incep_avgpool_conv": [C.POINTER(IncepPoolArgs), C.POINTER(IncepConvArgs), vp],
     "hawq_graph_begin": [vp],
     "hawq_graph_end": [vp, C.POINTER(vp)],
     "hawq_graph_launch": [vp, vp],

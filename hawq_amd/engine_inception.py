@@ -202,6 +202,26 @@ launch for such a pool).  The conv's buffer stays allocated (the tuner and the t
 ``export_plan()`` writes ``"stem_pool"`` and ``"stem_pool_us"`` only when the option is on; an engine without it ignores them.
 ``stem_pool_convs`` lists the kept convs; ``stem_band_convs`` leaves them out (the pooled launch wins).  A conv that the plan runs
 as a split-K launch keeps that launch and its pool.  No candidate at all raises ``PlanNotApplicable``.  Not the default.
+
+Average pool + 1x1 conv in one launch.  ``InceptionEngine(model, pool_conv=True)`` issues an average-pool branch - the
+``hawq_incep_avgpool_branch`` record and the 1x1 conv record behind it, the only reader of its dense int8 output
+(``pool_conv_pairs``: nine, one per Inception-A, -B and -C unit) - as one ``hawq_incep_avgpool_conv`` (hawq_amd/csrc/incep_pool_conv.hip)
+on the two records' own blocks.  The records stay; ``_write`` issues the launch in the conv's place and nothing in the pool's, so
+``n_launches`` drops by one per pair - not under ``grouped``, where the conv was a member of its level's launch and the fused
+launch takes the pool's slot; the int8 intermediate stays allocated (the tuner and the two-launch form use it).  Which pairs:
+* neither ``tune`` nor ``plan``: every candidate ``hawq_incep_avgpool_conv_ok`` accepts;
+* ``tune=True``: after tiles and groups and before the fans, two blocks are timed per candidate on the buffers of a forward - the
+  pool (on the entry point ``fast_pools`` selects) followed by the unit's level-1 conv launch as the choice issues it (a group, or the
+  conv alone), against the fused launch followed by that level without the conv - and the pair is fused only where the second block
+  is faster; a tie goes to the two launches (``pool_conv_us``: conv -> [two launches, fused] microseconds);
+* ``plan=``: exactly the conv indices of its ``"pool_conv"`` field (``check_pool_conv``: StalePlan for an entry that is no candidate,
+  is named twice or that the library refuses); a plan without the field fuses nothing.
+``export_plan()`` writes ``"pool_conv"`` and ``"pool_conv_us"`` only when the option is on; an engine without it ignores them.
+Under ``grouped`` a fused conv leaves its level before the level is issued: the rest keeps the level's tile if the library takes
+the smaller group and runs as single launches otherwise (the plan's ``"groups"`` still name whole levels).  Under ``fan_out`` a
+fused conv does not fan out: its slice of the unit buffer is one of the boundary's residual ranges (``fan_boundaries(...,
+unfanned)``).  ``pool_conv_convs`` lists the fused convs.  With ``nibble``, ``nibble_groups``, ``nibble_fan`` or ``splitk`` it raises
+``PlanNotApplicable`` (the kernel has no nibble or split form).  Not the default.
 """
 from __future__ import annotations
 
@@ -265,7 +285,7 @@ def launch_digest(keys):
 
 
 def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibble=None, nibble_groups=None, nibble_fan=None,
-              splitk=None, stem_band=None, stem_pool=None):
+              splitk=None, stem_band=None, stem_pool=None, pool_conv=None):
     """the dict ``export_plan`` returns: batch shape (N, H, W), digest of the launch list, tile inventory, chosen id per conv launch
     and, for the record, the measured microseconds per launch and tile id (``us[i][str(tile)]``); with `groups` (a grouped engine's
     ``{"convs": [indices into the launch list], "tile": id, "us": {...}}`` entries) also the ``"groups"`` field, and with `fan_out`
@@ -274,7 +294,8 @@ def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibb
     `fan_out`, tile ids of ``hawq_incep_conv_group_nib_fan``) the ``"nibble_fan"`` field; a non-empty `splitk` (a split-K engine's
     ``{"convs", "slices": [per member], "us"}`` entries) the ``"splitk"`` field; `stem_band` (a stem-band engine's (kept conv
     indices, conv -> microseconds on the band kernel)) the ``"stem_band"`` and ``"stem_band_us"`` fields; `stem_pool` (a stem-pool
-    engine's (kept conv indices, conv -> [pair, fused] microseconds)) the ``"stem_pool"`` and ``"stem_pool_us"`` fields"""
+    engine's (kept conv indices, conv -> [pair, fused] microseconds)) the ``"stem_pool"`` and ``"stem_pool_us"`` fields; `pool_conv`
+    (a pool-conv engine's (fused conv indices, conv -> [two launches, fused] microseconds)) ``"pool_conv"`` and ``"pool_conv_us"``"""
     plan = {"network": "inceptionv3", "batch": [int(v) for v in batch], "launches": launch_digest(keys), "n_launches": len(keys),
             "num_tiles": int(num_tiles), "tiles": [int(t) for t in tiles],
             "us": [{str(t): round(float(v), 3) for t, v in sorted(d.items(), key=lambda kv: int(kv[0]))} for d in us]}
@@ -300,6 +321,9 @@ def make_plan(batch, keys, num_tiles, tiles, us, groups=None, fan_out=None, nibb
     if stem_pool is not None:
         plan["stem_pool"] = sorted(int(c) for c in stem_pool[0])
         plan["stem_pool_us"] = {str(c): [round(float(v), 3) for v in us] for c, us in sorted(stem_pool[1].items())}
+    if pool_conv is not None:
+        plan["pool_conv"] = sorted(int(c) for c in pool_conv[0])
+        plan["pool_conv_us"] = {str(c): [round(float(v), 3) for v in us] for c, us in sorted(pool_conv[1].items())}
     return plan
 
 
@@ -374,6 +398,42 @@ def check_stem_pool(entries, candidates, ok):
             raise StalePlan(f"stem pool launch {c}: named twice")
         if not ok(c):
             raise StalePlan(f"stem pool launch {c}: the fused kernel refuses it")
+    return list(entries)
+
+
+def pool_conv_pairs(records):
+    """conv index -> (pool record, conv record) of every average-pool branch that one ``hawq_incep_avgpool_conv`` launch can stand
+    for: a ``hawq_incep_avgpool_branch`` record that writes a dense int8 tensor which the 1x1 conv record behind it reads whole, and
+    which no other record reads."""
+    def reads(q, ptr):
+        return q.args[0].in_ == ptr if q.kind in ("conv", "pool") else ptr in q.args
+
+    pairs = {}
+    for p, r in zip(records, records[1:]):
+        if p.kind != "pool" or p.name != "hawq_incep_avgpool_branch" or r.kind != "conv":
+            continue
+        a, b = p.args[0], r.args[0]
+        dense = a.c_off == 0 and a.ldo == a.C == b.Cin and a.out_bits == 8 and (b.N, b.H, b.W) == (a.N, a.H, a.W)
+        if dense and b.in_ == a.out and (b.KH, b.KW) == (1, 1) and not any(reads(q, a.out) for q in records if q is not r):
+            pairs[r.ref] = (p, r)
+    return pairs
+
+
+def check_pool_conv(entries, candidates, ok):
+    """The convs of a plan's ``"pool_conv"`` field (None: no such field, no fused launch), or StalePlan: not a list, an entry that
+    is not one of `candidates` (``pool_conv_pairs``, as indices into the conv launch list), one named twice, or one that ``ok(i)``
+    refuses."""
+    if entries is None:
+        return []
+    if not isinstance(entries, (list, tuple)):
+        raise StalePlan(f"not a list of pool-branch conv launches: {entries!r}")
+    for i, c in enumerate(entries):
+        if not isinstance(c, int) or isinstance(c, bool) or c not in candidates:
+            raise StalePlan(f"pool conv launch {c!r}: not a 1x1 conv that alone reads an average-pool branch")
+        if c in entries[:i]:
+            raise StalePlan(f"pool conv launch {c}: named twice")
+        if not ok(c):
+            raise StalePlan(f"pool conv launch {c}: the fused kernel refuses it")
     return list(entries)
 
 
@@ -459,10 +519,11 @@ def grouped_order(launches, groups):
     return order
 
 
-def fan_boundaries(launches, issued=None):
+def fan_boundaries(launches, issued=None, unfanned=()):
     """The boundary in front of every unit of `launches`, in unit order, read from the records' tags and argument blocks alone
     (`issued`, of a nibble plan: entry requant record -> the block the plan issues in its place, with ``out_bits`` 4 into a hawq4
-    buffer of its own; a fan target then carries that block's buffer, clamp and form):
+    buffer of its own; a fan target then carries that block's buffer, clamp and form; `unfanned`: conv records, as indices, whose launch
+    has no fan-out form - their slices count as produced by no conv):
     * ``"requants"``: the unit's level-0 ``hawq_incep_requant`` records (the ``q_input_act`` of its conv branches), as indices;
     * ``"slices"``: ``(c_off, C, producer)`` for every slice of the buffer they read that an earlier record writes, by channel: the
       index of the conv record that produced it (REQUANT2, 16 bits, into that buffer), or None for a pool / requant record;
@@ -495,7 +556,7 @@ def fan_boundaries(launches, issued=None):
             if (a.out, a.ldo, a.out_bits) != (src, pitch, 16) or (r.kind == "conv" and a.epilogue == _lib.INCEP_RAW):
                 continue
             if r.kind == "conv":
-                b["slices"].append((a.c_off, a.Cout, i if a.epilogue == _lib.INCEP_REQUANT2 else None))
+                b["slices"].append((a.c_off, a.Cout, i if a.epilogue == _lib.INCEP_REQUANT2 and i not in unfanned else None))
             else:
                 b["slices"].append((a.c_off, a.C, None))
         b["slices"].sort(key=lambda t: t[0])
@@ -588,7 +649,7 @@ class InceptionEngine(GraphRunner):
     def __init__(self, model, use_graph: bool = True, tune: bool = False, plan=None, fast_pools: bool = False,
                  fused_stem: bool = False, grouped: bool = False, fan_out: bool = False, nibble: bool = False,
                  nibble_groups: bool = False, nibble_fan: bool = False, splitk=False, stem_band: bool = False,
-                 stem_pool: bool = False):
+                 stem_pool: bool = False, pool_conv: bool = False):
         self.model, self.use_graph = model, use_graph
         if not isinstance(splitk, (bool, int)) or (not isinstance(splitk, bool) and splitk < 2):
             raise ValueError("splitk is False, True or a slice count >= 2")
@@ -603,6 +664,10 @@ class InceptionEngine(GraphRunner):
         self.nibble_fan, self.stem_band, self.stem_pool = bool(nibble_fan), bool(stem_band), bool(stem_pool)
         self.stem_band_convs, self.stem_band_us, self._bands = [], {}, frozenset()
         self.stem_pool_convs, self.stem_pool_us, self._pooled = [], {}, {}
+        self.pool_conv, self.pool_conv_convs, self.pool_conv_us, self._avg_fused = bool(pool_conv), [], {}, {}
+        if self.pool_conv and (nibble or nibble_groups or nibble_fan or splitk):
+            raise PlanNotApplicable("pool_conv does not compose with nibble, nibble_groups, nibble_fan or splitk: "
+                                    "hawq_incep_avgpool_conv has no nibble or split form")
         if self.nibble and (self.grouped or self.fan_out):
             raise PlanNotApplicable("nibble=True does not compose with grouped or fan_out: their launches have no nibble form")
         if self.nibble_groups and not self.nibble:
@@ -798,6 +863,7 @@ class InceptionEngine(GraphRunner):
         self.splitk_launches, self.splitk_candidates, self._splits = [], [], {}
         self.stem_band_convs, self.stem_band_us, self._bands = [], {}, frozenset()
         self.stem_pool_convs, self.stem_pool_us, self._pooled = [], {}, {}
+        self.pool_conv_convs, self.pool_conv_us, self._avg_fused = [], {}, {}
         ib = q.features.q_init_block
         s_in = _scale(ib.q_input_activ)
         inv, lo, hi = self._input_quant()
@@ -1010,7 +1076,13 @@ class InceptionEngine(GraphRunner):
         nib = self._choose_nibbles(T) if self.nibble else None
         if self.nibble_groups:   # the second component then holds the mixed-form launches (``grouped`` is off: the constructor)
             groups = self._choose_nibble_groups(self.conv_tiles, nib)
-        fans = self._choose_fans(self.conv_tiles, groups, nib if self.nibble_fan else None) if self.fan_out or self.nibble_fan else None
+        avg = {}
+        if self.pool_conv:   # in front of the fans: a fused conv is no fan producer, and its level is issued without it
+            avg = self._choose_pool_convs(self.conv_tiles, groups)
+            self.pool_conv_convs, groups = sorted(avg), self._groups_without(groups, avg)
+        unfanned = frozenset(self._launches.index(r) for _, r in avg.values())
+        fans = self._choose_fans(self.conv_tiles, groups, nib if self.nibble_fan else None, unfanned) \
+            if self.fan_out or self.nibble_fan else None
         self._splits = self._choose_splits(self.conv_tiles, groups, nib) if self.splitk else {}   # beside the choice: launch -> slice counts
         if self.stem_pool:   # last: the pair it competes with is the one the rest of the choice issues
             fused = self._choose_pools(self.conv_tiles, groups, nib)
@@ -1018,7 +1090,72 @@ class InceptionEngine(GraphRunner):
             self.stem_band_convs = [c for c in self.stem_band_convs if c not in fused]   # the pooled launch wins
         self._bands = frozenset(self.stem_band_convs)   # from here on: the timing forwards above ran the default entry points
         self._pooled = fused if self.stem_pool else {}
+        self._avg_fused = avg
         return self.conv_tiles, groups, fans, nib
+
+    # ------------------------------------------------------------------ the average-pool branches' pool + conv launches
+    def _groups_without(self, groups, gone):
+        """`groups` as they are issued once the convs `gone` run elsewhere: a level keeps its tile on the members that are left if
+        there are two or more and the library takes the smaller group, and is issued as single launches otherwise"""
+        if groups is None:
+            return None
+        rest = [([c for c in convs if c not in gone], tile, len(convs)) for convs, tile in groups]
+        return [(r, tile) for r, tile, n in rest if len(r) == n or (len(r) >= 2 and self._group_ok(r, tile))]
+
+    def _choose_pool_convs(self, tiles, groups):
+        """The average-pool branches that run as one ``hawq_incep_avgpool_conv``, as conv index -> (pool record, conv record): the
+        plan's ``"pool_conv"`` entries (none without the field), else the candidates whose fused block beat the two-launch block
+        (``tune``; ``pool_conv_us``: conv -> [two launches, fused]), else every candidate the library takes."""
+        pairs = pool_conv_pairs(self._launches)
+        if not pairs:
+            raise PlanNotApplicable("pool_conv: no 1x1 conv of this model alone reads an average-pool branch")
+        ok = lambda c: bool(_lib.load().hawq_incep_avgpool_conv_ok(C.byref(pairs[c][0].args[0]), C.byref(pairs[c][1].args[0])))   # noqa: E731
+        if self.plan is not None:
+            self.pool_conv_us = {int(c): [float(v) for v in us] for c, us in (self.plan.get("pool_conv_us") or {}).items()}
+            kept = check_pool_conv(self.plan.get("pool_conv"), list(pairs), ok)
+        else:
+            kept = [c for c in pairs if ok(c)]
+            if self.tune and kept:
+                self._time_pool_convs(kept, pairs, tiles, groups)
+                kept = [c for c in kept if self.pool_conv_us[c][1] < self.pool_conv_us[c][0]]   # a tie goes to the two launches
+        return {c: pairs[c] for c in kept}
+
+    def _time_pool_convs(self, cands, pairs, tiles, groups):
+        """``pool_conv_us[c]`` = [two launches, fused] in microseconds for every conv of `cands`, each a block timed as a whole on
+        the buffers of a forward of the plan: the pool on the entry point ``fast_pools`` selects, then the level-1 launch that holds
+        the conv as (tiles, groups) issue it; against the fused launch, then that level without the conv (``_groups_without``)."""
+        lib, sp, keep = _lib.load(), self.stream.cuda_stream, []
+
+        def level(c, gs):   # the launches of c's level as the groups `gs` issue them (c alone where no group holds it)
+            convs, tile = next(((cv, t) for cv, t in gs or [] if c in cv), ([c], None))
+            if tile is not None:
+                keep.append(self._group_args(convs))
+                return [partial(_lib.call, "hawq_incep_conv_group", C.byref(keep[-1]), int(tile), sp)]
+            return [partial(_lib.call, "hawq_incep_conv_tiled", C.byref(self._convs[c].args[0]), int(tiles[c]), sp)]
+
+        self._choice = (tiles, groups, None, None)
+        with EventTimer(sp, _TUNE_REPS + 1) as ev:
+            torch.cuda.synchronize(self.dev)
+            with torch.cuda.stream(self.stream):
+                for op in self._write():
+                    op()
+                for c in cands:
+                    p, r = pairs[c]
+                    a = C.byref(p.args[0])
+                    fast = self.fast_pools and lib.hawq_incep_pool_v_ok(a, p.ref)
+                    two = [partial(_lib.call, "hawq_incep_pool_v", a, p.ref, sp) if fast else partial(_lib.call, p.name, a, sp)]
+                    two += level(c, groups)
+                    one = [partial(_lib.call, "hawq_incep_avgpool_conv", a, C.byref(r.args[0]), sp)]
+                    held = [g for g in groups or [] if c in g[0]]   # the rest of the level: a smaller group, or each conv alone
+                    smaller = self._groups_without(held, {c})
+                    for m in [x for g in held for x in g[0] if x != c][:1 if smaller else None]:
+                        one += level(m, smaller)
+                    run = lambda ops: [op() for op in ops]   # noqa: E731
+                    self.n_timing_launches += (len(two) + len(one)) * (_TUNE_WARMUP + _TUNE_REPS)
+                    self.pool_conv_us[c] = [ev.median_us(partial(run, two), _TUNE_REPS, _TUNE_WARMUP),
+                                            ev.median_us(partial(run, one), _TUNE_REPS, _TUNE_WARMUP)]
+        torch.cuda.synchronize(self.dev)
+        self._choice = (None, None, None, None)
 
     # ------------------------------------------------------------------ the stem's band kernel
     def _band_ok(self, c):
@@ -1397,14 +1534,14 @@ class InceptionEngine(GraphRunner):
         self._choice = (None, None, None, None)
         return out
 
-    def _choose_fans(self, tiles, groups, nib=None):
+    def _choose_fans(self, tiles, groups, nib=None, unfanned=()):
         """the third component: from the plan's ``"fan_out"`` field if it has one, else timed against the plain launches (``tune``),
         else every candidate boundary on the default tiles (a tile plan without the field fixes the other convs' tiles only).
         With `nib` (the nibble convs of a ``nibble_fan`` engine) the same for the ``"nibble_fan"`` field, on the launches of
         ``hawq_incep_conv_group_nib_fan`` and the entry requants as the nibble plan issues them; a boundary whose hawq4 entry
         requant ``hawq_incep_pool_v`` does not take on a residual range is no candidate."""
         if nib is None:
-            field, order, bounds, ok = "fan_out", _FAN_TILES, fan_boundaries(self._launches), self._fan_ok
+            field, order, bounds, ok = "fan_out", _FAN_TILES, fan_boundaries(self._launches, unfanned=unfanned), self._fan_ok
         else:
             field, order, bounds = "nibble_fan", _NIB_FAN_TILES, fan_boundaries(self._launches, self._nib_pool)
             ok = partial(self._nfan_ok, nib=nib)
@@ -1542,7 +1679,8 @@ class InceptionEngine(GraphRunner):
                          groups, fans, (self.nibble_convs, self.nibble_us) if self.nibble else None, ngroups, nfans,
                          [e for e in self.splitk_candidates if e["kept"]] if self.splitk else None,
                          (self.stem_band_convs, self.stem_band_us) if self.stem_band else None,
-                         (self.stem_pool_convs, self.stem_pool_us) if self.stem_pool else None)
+                         (self.stem_pool_convs, self.stem_pool_us) if self.stem_pool else None,
+                         (self.pool_conv_convs, self.pool_conv_us) if self.pool_conv else None)
 
     # ------------------------------------------------------------------ the writer
     def _write(self, u8=False):
@@ -1555,7 +1693,8 @@ class InceptionEngine(GraphRunner):
         names is issued as the plan's split launch (``_split_args``: ``hawq_incep_conv_group_splitk``, or under ``nibble_groups``
         ``hawq_incep_conv_group_nib_splitk`` with its mask) with its slice counts on the engine's one workspace, in the place of the
         launch it replaces (``splitk_launches``); the uint8 chain shares those callables.  A stem conv that ``_pooled`` names is
-        issued as one ``hawq_incep_conv_band_pool`` on the block kept there, and nothing is issued for its max pool record."""
+        issued as one ``hawq_incep_conv_band_pool`` on the block kept there, and nothing is issued for its max pool record; likewise a
+        conv that ``_avg_fused`` names is issued as one ``hawq_incep_avgpool_conv`` on its pool record's block and its own."""
         tiles, groups, fans, nib = self._choice
         lib, sp, launches = _lib.load(), self.stream.cuda_stream, self._launches
         fan_of = {s: (b, t) for b, by_set in fans or [] for s, t in by_set.items()}           # producer launch -> its boundary, tile
@@ -1644,6 +1783,11 @@ class InceptionEngine(GraphRunner):
                 at[r] = at[self._pooled[r.ref][1]] = len(ops)
                 ops.append(op("hawq_incep_conv_band_pool", C.byref(self._pooled[r.ref][0])))
             elif r.kind == "pool" and any(r is p for _, p in self._pooled.values()):   # nothing in the pool's place
+                pass
+            elif r.kind == "conv" and r.ref in self._avg_fused:   # an average-pool branch in one launch, in the conv's place
+                at[r] = at[self._avg_fused[r.ref][0]] = len(ops)
+                ops.append(op("hawq_incep_avgpool_conv", C.byref(self._avg_fused[r.ref][0].args[0]), C.byref(r.args[0])))
+            elif r.kind == "pool" and any(r is p for p, _ in self._avg_fused.values()):   # nothing in the pool's place
                 pass
             else:
                 at[r] = len(ops)

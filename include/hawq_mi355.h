@@ -798,6 +798,22 @@ int hawq_incep_pool_v(const hawq_incep_pool_args *a, int op, void *stream);
 /* the workgroup tile (th rows x tw columns of output pixels, x 32 channels) hawq_incep_pool_v uses for this AVG3 description (it
  * depends on the map and, through the workgroup count, on N and C); non-zero with hawq_last_error() on a refused description */
 int hawq_incep_pool_v_avg3_tile(const hawq_incep_pool_args *a, int32_t *th, int32_t *tw);
+/* hawq_incep_avgpool_branch(p) followed by the 1x1 hawq_incep_conv(c) that reads its dense int8 output, in one launch
+ * (incep_pool_conv.hip; the average-pool branches of the Inception-A, -B and -C units).  Both argument blocks are those of the two
+ * launches, unchanged; p->out, p->ldo, p->c_off and c->in are ignored and may be NULL / 0.  It writes, byte for byte, what the two
+ * launches write into c->out; the pooled tensor never reaches memory: a workgroup pools a band of full rows of one image into an LDS
+ * A-operand tile, 64 channels at a time, and feeds the MFMAs of all Cout channels from there.  Channels outside c_off .. c_off +
+ * Cout - 1 of an output row are not touched.
+ *   hawq_incep_avgpool_conv_ok: 1 if the kernel takes the pair (host arithmetic only, nothing dereferenced, nothing launched): c is
+ *       1x1 / stride 1 / pad 0 with c->N/H/W == p->N/H/W and c->Cin == p->C; p->out_bits == 8, p->in_bits 8 or 16, a pre clamp
+ *       inside int16, a post clamp inside int8 (without post the pooled values must already lie inside int8); C, in_pitch, in_off,
+ *       Cout, ldo and c_off multiples of 16, ldo >= c_off + Cout; in, wgt and out 16-byte aligned; REQUANT or REQUANT2 (RAW is
+ *       refused) with out_bits 8 or 16; Cout <= 192 (the accumulator budget) and W <= 110 for Cout <= 64, W <= 62 otherwise (a
+ *       workgroup's band holds full rows); fewer than 2^31 workgroups.
+ *   hawq_incep_avgpool_conv:    the launch.  A refused pair returns non-zero (the reason in hawq_last_error()), launches nothing and
+ *       writes nothing. */
+int hawq_incep_avgpool_conv_ok(const hawq_incep_pool_args *p, const hawq_incep_conv_args *c);
+int hawq_incep_avgpool_conv(const hawq_incep_pool_args *p, const hawq_incep_conv_args *c, void *stream);
 
 /* ---- hipGraph helpers: capture a sequence of the launches above once, replay per batch */
 int hawq_graph_begin(void *stream);

@@ -53,6 +53,9 @@ same plan with ``stem_pool=True`` (a stem conv + max pool pair as one ``hawq_inc
 alternating blocks as above, an assertion that the logits are bit-equal, and per pair the microseconds of the pair and of the fused
 launch, which one runs, the bytes each form moves (input + weights + outputs, the full-resolution tensor written and read once by
 the pair) and the byte floor of each at ``roofline.HBM_PEAK_GBS``.
+With ``--pool-conv``: one tuned plan (the options above and ``--stem-pool`` select its other options) against the same plan with
+``pool_conv=True`` (an average-pool branch as one ``hawq_incep_avgpool_conv`` where that beat the two launches): alternating blocks,
+an assertion that the logits are bit-equal, and per branch the microseconds of [pool + level-1 launch, fused + rest of the level].
 
     python tools/inception_bench.py [--scheme uniform8] [--steps 5] [--warmup 2] [--paths fused,module]
     python tools/inception_bench.py --splitk --pools --batches 1,2,4,8,16 [--blocks 6]
@@ -63,6 +66,7 @@ the pair) and the byte floor of each at ``roofline.HBM_PEAK_GBS``.
     python tools/inception_bench.py --tune --pools --batches 128,1
     python tools/inception_bench.py --tune --pools --stem-band --batches 128,1
     python tools/inception_bench.py --tune --pools --stem-pool [--grouped --fan-out] --batches 128,1
+    python tools/inception_bench.py --tune --pools --pool-conv [--grouped --fan-out --stem-pool] --batches 128,1
     python tools/inception_bench.py --fused-stem [--tune --pools] --batches 128,1 --stem-launches 20
     python tools/inception_bench.py --grouped --batches 1,16,128 [--blocks 6]
     python tools/inception_bench.py --fan-out [--grouped] --batches 1,16,128 [--blocks 6]
@@ -485,6 +489,56 @@ def compare_stem_pool(model, args, b):
     return pooled
 
 
+def compare_pool_conv(model, args, b):
+    """one tuned plan without and with the average-pool branches in one launch each (``pool_conv=True``), alternating blocks;
+    returns the pool-conv engine.  The other engine replays the same plan minus the ``"pool_conv"`` fields; only where the tuner
+    fused a branch under ``--fan-out`` is it tuned on its own (a fan-out plan names its producer launches, which differ once a fused
+    conv has left its level).  Without ``--fan-out`` a third engine replays the plan with every candidate forced fused: the bit-equal
+    assertion and the forward of the all-fused plan, whatever the tuner kept"""
+    from hawq_amd.engine_inception import InceptionEngine
+    FUSED = "hawq_incep_avgpool_conv"
+    x = synthetic_images(b, seed=1, size=299).cuda()
+    wl = f"inceptionv3_{args.scheme}_b{b}"
+    opts = dict(fast_pools=args.pools, fused_stem=args.fused_stem, grouped=args.grouped, fan_out=args.fan_out, stem_pool=args.stem_pool)
+    with torch.no_grad():
+        fused = InceptionEngine(model, tune=True, pool_conv=True, **opts)
+        y1 = fused(x)
+        plan = {k: v for k, v in fused.export_plan().items() if not k.startswith("pool_conv")}
+        own = bool(args.fan_out and fused.pool_conv_convs)
+        pair = InceptionEngine(model, tune=True, **opts) if own else InceptionEngine(model, plan=plan, **opts)
+        engines = {"pair": pair, "fused": fused}
+        if not args.fan_out:
+            engines["forced"] = InceptionEngine(model, plan={**plan, "pool_conv": sorted(fused.pool_conv_us)}, pool_conv=True, **opts)
+        equal = all(bool(torch.equal(e(x), y1)) for k, e in engines.items() if k != "fused")
+        assert equal, "the logits with the fused pool + conv launches differ from the two-launch plan's"
+        assert FUSED not in pair.op_names and (own or pair.conv_tiles == fused.conv_tiles)
+        assert "forced" not in engines or engines["forced"].op_names.count(FUSED) == len(fused.pool_conv_us)
+        print(f"# {wl}: conv | HxW C->Cout | two launches us (pool + level) | fused us (fused + rest of level) | runs")
+        for c, (t_pair, t_fused) in sorted(fused.pool_conv_us.items()):
+            H, W, Cin, Cout = fused.conv_launches[c][:4]
+            print(f"# {c} | {H}x{W} {Cin}->{Cout} | {t_pair:.1f} | {t_fused:.1f} | {'fused' if c in fused.pool_conv_convs else 'pair'}")
+        for e in engines.values():
+            for _ in range(args.warmup):
+                e(x)
+        ms = {k: [] for k in engines}
+        for _ in range(args.blocks):
+            for k, e in engines.items():
+                ms[k].append(_timed(lambda e=e: e(x), args.steps) / args.steps)
+        for k, e in engines.items():
+            v = ms[k]
+            mean = sum(v) / len(v)
+            print(json.dumps({"workload": wl, "path": "fused", "plan": "tuned", **{o: bool(f) for o, f in opts.items()}, "pool_branch": k,
+                              "ms_per_batch": round(mean, 4), "images_per_s": round(b * 1000.0 / mean, 1),
+                              "block_min_ms": round(min(v), 4), "block_max_ms": round(max(v), 4), "blocks": len(v),
+                              "steps": args.steps, "launches": e.n_launches, "fused_launches": e.op_names.count(FUSED),
+                              "logits_bit_equal": equal}), flush=True)
+        m0, m1 = sum(ms["pair"]) / args.blocks, sum(ms["fused"]) / args.blocks
+        print(json.dumps({"workload": wl, "fused_over_pair_rate": round(m0 / m1, 4), "gain_ms": round(m0 - m1, 4),
+                          "pool_conv_kept": fused.pool_conv_convs, "other_engine": "tuned on its own" if own else "same plan",
+                          "ranges_overlap": bool(min(ms["pair"]) <= max(ms["fused"]) and min(ms["fused"]) <= max(ms["pair"]))}), flush=True)
+    return fused
+
+
 def compare_splitk(model, args, b):
     """the tuned grouped plan without and with split-K launches (``splitk=True``, tuned: that engine times tiles, groups and slice
     counts; the other replays its plan and ignores the ``"splitk"`` field, so it is the tuned grouped engine on the same tiles and
@@ -747,10 +801,13 @@ def main():
     ap.add_argument("--stem-pool", action="store_true",
                     help="compare one tuned plan (--pools, --fused-stem, --grouped, --fan-out select its other options) without and "
                          "with the stem's conv + max pool pairs in one launch each")
+    ap.add_argument("--pool-conv", action="store_true",
+                    help="compare one tuned plan (--pools, --fused-stem, --grouped, --fan-out, --stem-pool select its other options) "
+                         "without and with the average-pool branches (3x3 average pool + 1x1 conv) in one launch each")
     ap.add_argument("--save-plan", default=None, help="--tune / --plan / --grouped / --fan-out / --nibble: write export_plan() of the last batch size to this file")
     args = ap.parse_args()
     args.scheme = args.scheme or ("uniform4" if args.splitk and args.nibble_groups else "uniform8")
-    if args.save_plan and not (args.stem_pool or args.stem_band or args.splitk or args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
+    if args.save_plan and not (args.pool_conv or args.stem_pool or args.stem_band or args.splitk or args.tune or args.plan or args.grouped or args.fan_out or args.nibble or args.nibble_groups or args.nibble_fan):
         ap.error("--save-plan needs --tune, --plan, --grouped, --fan-out or --nibble: there is no conv tile plan to save otherwise")
     model = build_quantized_resnet("inceptionv3", args.scheme, seed=0).cuda()
     calibrate(model, synthetic_images(2, seed=0, size=299).cuda())
@@ -758,8 +815,8 @@ def main():
         if args.input:
             compare_inputs(model, args, b, args.input.split(","))
             continue
-        if args.stem_pool or args.splitk or args.stem_band:
-            tuned = (compare_stem_pool if args.stem_pool else compare_stem_band if args.stem_band else compare_splitk)(model, args, b)
+        if args.pool_conv or args.stem_pool or args.splitk or args.stem_band:
+            tuned = (compare_pool_conv if args.pool_conv else compare_stem_pool if args.stem_pool else compare_stem_band if args.stem_band else compare_splitk)(model, args, b)
             if args.save_plan:
                 with open(args.save_plan, "w") as f:
                     json.dump(tuned.export_plan(), f)
